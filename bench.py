@@ -27,6 +27,11 @@ side and three all-reduces of 8 KB of partial sums.  `config.workload` is identi
                onset of yielding of the SVC phase (a plastic step of this configuration takes seconds: use --steps 1..3).
 PLFX_BENCH_TRANSPORT=host runs the same path over gloo with the host-staged transport (several ranks on ONE GPU: a
 functional check, not a measurement).
+  --dump-outputs DIR   (one process) after the timed steps, write what the solve hands its caller at the end of the last
+               timed step -- nodal u, f, du, element sig, eps, epl, the sgl / egl / epgl histories -- as DIR/<name>.npy
+               (float64; arrays larger than 2^20 values as a fixed, seeded sample of their rows, < 64 MB in all).  The
+               inputs are synthetic and fixed, so two builds run with the same arguments can be compared array by array.
+               DIR = bench_outputs is ignored by git.
 """
 import argparse
 import gc
@@ -132,6 +137,35 @@ def committed_svc_profile():
         if mv:
             return {'source': os.path.relpath(path, ROOT), 'valu': float(mv.group(1)), 'fp64_flop': float(mf.group(1)) if mf else None}
     return None
+
+
+DUMP_MAX_VALUES = 1 << 20   # float64 values per dumped array (8 MB): the nine arrays of dump_outputs stay below 64 MB
+DUMP_SEED = 1234
+
+
+def dump_rows(a, max_values=DUMP_MAX_VALUES, seed=DUMP_SEED):
+    """`a` as float64; with more than `max_values` values, a fixed sample of its rows (seeded, in index order) -- the same
+    rows for every array of the same shape, so that two runs are compared on the same nodes / elements"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.size <= max_values:
+        return a
+    per_row = a.size // a.shape[0]
+    keep = np.random.default_rng(seed).choice(a.shape[0], max_values // per_row, replace=False)
+    return a[np.sort(keep)]
+
+
+def dump_outputs(fe, dirname):
+    """What Model.solve hands its caller after the last timed step -> dirname/<name>.npy"""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {'u': fe.u.reshape(-1, 2), 'f': fe.f.reshape(-1, 2), 'du': fe.du.reshape(-1, 2),   # per node (x, y)
+              'sig': fe._state('sig'), 'eps': fe._state('eps'), 'epl': fe._state('epl'),      # per element (Voigt)
+              'sgl': fe.sgl, 'egl': fe.egl, 'epgl': fe.epgl}                                   # per load step
+    total = 0
+    for name, a in arrays.items():
+        a = dump_rows(a)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        total += a.nbytes
+    assert total < 64e6, total
 
 
 def hill_material(FE):
@@ -640,13 +674,19 @@ def main():
     ap.add_argument('--all-families', action='store_true',
                     help='HIP-event timing of every kernel family (kernel_ms table) instead of only the two roofline kernels; '
                          'costs about 0.1 ms per load step')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed solve returns after its last step as DIR/<name>.npy (see the top of this file)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if world != args.gpus and world > 1:
         raise SystemExit('--gpus %d but WORLD_SIZE=%d' % (args.gpus, world))
+    if args.dump_outputs and world > 1:
+        raise SystemExit('--dump-outputs: one process only (a rank holds the results of its own strip)')
 
     # watchdog: a rank that waits forever for a peer (a collective that never completes) ends the job with a stack dump instead
     # of hanging the node until the caller's own limit
@@ -767,6 +807,9 @@ def main():
     if dbg:
         print('hook times (ms since t0):', [(i, round(1e3 * (t - marks['t0']), 3)) for i, t in dbg if i >= pre + W],
               't1', round(1e3 * (marks['t1'] - marks['t0']), 3), file=sys.stderr)
+    # the solve stopped after the last timed step: its results are what the model holds now (outside the timed window)
+    if args.dump_outputs:
+        dump_outputs(fe, args.dump_outputs)
     dt = marks['t1'] - marks['t0']
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device='cpu' if host_transport else 'cuda')
