@@ -402,6 +402,25 @@ int plfx_comm_info(plfx_ctx *ctx, int *rank, int *nranks, int *device_collective
 int plfx_comm_unique_id(char id[128]);
 int plfx_comm_init(plfx_ctx *ctx, const char id[128], int rank, int nranks);
 
+/* ---------------------------------------------------------------- SVC training (Material.train_SVC, material.py:1596-1640)
+ * Binary RBF C-SVC fits by libsvm's non-shrinking SMO, many problems in one call (grid search: one per (C, gamma, fold)).
+ * X [n*d] row-major features shared by all problems (1 <= d <= 16), y [n] labels -1 / +1; problem p trains on the rows
+ * idx[off[p] .. off[p+1]) of X with C[p] > 0, gamma[p] > 0; tol: stopping tolerance of m(a) - M(a) (scikit-learn's 1e-3);
+ * max_iter <= 0: max(10^7, 100 n_p).  Out: alpha[off[nprob]] in the order of idx (0 <= alpha <= C), rho[nprob] with
+ * decision(x) = sum_k y_k alpha_k exp(-gamma |x - x_k|^2) - rho (scikit-learn: dual_coef_ = y alpha over alpha > 0,
+ * intercept_ = -rho), obj[nprob] (NULL allowed) the dual objective, iters[nprob] SMO iterations, status[nprob] 0 converged,
+ * 1 max_iter reached (libsvm's warning).  Rejects C or gamma <= 0, labels other than -1 / +1, d > 16, one-class problems. */
+int plfx_svc_fit_batch(plfx_ctx *ctx, int n, int d, const double *X, const double *y, int nprob, const int32_t *off,
+                       const int32_t *idx, const double *C, const double *gamma, double tol, int64_t max_iter,
+                       double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status);
+/* Decision values of nprob RBF-SVC models on rows of the shared X: problem p has the support vectors
+ * X[sv_idx[sv_off[p] .. sv_off[p+1])] with coefficients coef[...] (dual_coef_), intercept[p] and gamma[p], and is evaluated
+ * on the rows q_idx[q_off[p] .. q_off[p+1]) of X: dec[k] = sum_s coef_s exp(-gamma |x_q - x_s|^2) + intercept[p], summed in
+ * the order given (libsvm's predict sums in support-vector order). */
+int plfx_svc_decision_batch(plfx_ctx *ctx, int n, int d, const double *X, int nprob, const int32_t *sv_off,
+                            const int32_t *sv_idx, const double *coef, const double *intercept, const double *gamma,
+                            const int32_t *q_off, const int32_t *q_idx, double *dec);
+
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_wave<0>), 1 spmv(+dot), 2 cg vector

@@ -54,6 +54,7 @@ SYMBOLS = [
     'plfx_indefinite_info', 'plfx_pattern_selftest', 'plfx_precond_bench', 'plfx_set_wh_mode', 'plfx_wh_info', 'plfx_wh_carry', 'plfx_set_mesh_structured',
     'plfx_svc_info', 'plfx_sqmr_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
+    'plfx_svc_fit_batch', 'plfx_svc_decision_batch',
 ]
 
 _lib = None
@@ -290,6 +291,62 @@ class Context(object):
         self._chk(self.lib.plfx_full_yf_batch(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(ldp),
                                               _dp(out), _dp(st)))
         return out, st
+
+    # -- SVC training (plfx_svm.hpp)
+    @staticmethod
+    def _lists(lists, name):
+        """list of index arrays -> (off[nprob+1], idx) int32"""
+        lists = [np.asarray(l, dtype=np.int64).reshape(-1) for l in lists]
+        if not lists:
+            raise ValueError('%s: at least one problem expected' % name)
+        off = np.zeros(len(lists) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(l) for l in lists])
+        return off, _i32(np.concatenate(lists))
+
+    def svc_fit_batch(self, X, y, problems, C, gamma, tol=1e-3, max_iter=-1):
+        """Fit one binary RBF C-SVC per problem (libsvm's non-shrinking SMO) in one batched call.
+        X (n, d) shared features, y (n,) labels -1 / +1, problems: list of row-index arrays into X; C, gamma: scalars or one
+        per problem.  Returns a list of dicts (alpha in the order of the index array, rho with decision = sum y alpha K - rho,
+        obj, n_iter, status 0 converged / 1 max_iter reached)."""
+        import ctypes   # (the argument C shadows this module's ctypes alias)
+        X = _f64(X)
+        if X.ndim != 2:
+            raise ValueError('svc_fit_batch: X must be (n, d)')
+        y = _f64(y).reshape(-1)
+        if len(y) != len(X):
+            raise ValueError('svc_fit_batch: X and y differ in length')
+        off, idx = self._lists(problems, 'svc_fit_batch')
+        npb = len(off) - 1
+        Cs = _f64(np.broadcast_to(np.asarray(C, dtype=float), (npb,)))
+        gs = _f64(np.broadcast_to(np.asarray(gamma, dtype=float), (npb,)))
+        alpha = np.empty(len(idx))
+        rho, obj = np.empty(npb), np.empty(npb)
+        it, st = np.empty(npb, dtype=np.int32), np.empty(npb, dtype=np.int32)
+        self._chk(self.lib.plfx_svc_fit_batch(self.h, len(X), X.shape[1], _dp(X), _dp(y), npb, _dp(off), _dp(idx),
+                                              _dp(Cs), _dp(gs), ctypes.c_double(tol), ctypes.c_int64(int(max_iter)),
+                                              _dp(alpha), _dp(rho), _dp(obj), _dp(it), _dp(st)))
+        return [dict(alpha=alpha[off[p]:off[p + 1]], rho=float(rho[p]), obj=float(obj[p]), n_iter=int(it[p]),
+                     status=int(st[p])) for p in range(npb)]
+
+    def svc_decision_batch(self, X, sv_lists, coefs, intercepts, gamma, query_lists):
+        """Decision values of several RBF-SVC models whose support vectors and query points are rows of the shared X:
+        model p = (rows sv_lists[p], dual coefficients coefs[p], intercepts[p], gamma[p]) on the rows query_lists[p].
+        Returns a list of arrays, one per model."""
+        X = _f64(X)
+        so, si = self._lists(sv_lists, 'svc_decision_batch')
+        qo, qi = self._lists(query_lists, 'svc_decision_batch')
+        npb = len(so) - 1
+        if len(qo) - 1 != npb or len(coefs) != npb:
+            raise ValueError('svc_decision_batch: one support-vector list, coefficient array and query list per model')
+        cf = _f64(np.concatenate([np.asarray(c, dtype=float).reshape(-1) for c in coefs]))
+        if len(cf) != len(si):
+            raise ValueError('svc_decision_batch: one coefficient per support vector expected')
+        ic = _f64(np.broadcast_to(np.asarray(intercepts, dtype=float), (npb,)))
+        gs = _f64(np.broadcast_to(np.asarray(gamma, dtype=float), (npb,)))
+        out = np.empty(len(qi))
+        self._chk(self.lib.plfx_svc_decision_batch(self.h, len(X), X.shape[1], _dp(X), npb, _dp(so), _dp(si), _dp(cf),
+                                                   _dp(ic), _dp(gs), _dp(qo), _dp(qi), _dp(out)))
+        return [out[qo[p]:qo[p + 1]] for p in range(npb)]
 
     def set_response_maxit(self, maxit=50):
         self._chk(self.lib.plfx_set_response_maxit(self.h, int(maxit)))

@@ -110,6 +110,20 @@ def sig_polar_ang(sig):
     return theta[0] if single else theta
 
 
+def sig_cyl2princ(s_cyl):
+    """Principal deviatoric stresses of cylindrical stresses (seq, theta) in the deviatoric plane (basic.py:180-209);
+    (2,) or (N,2)."""
+    sc = np.asarray(s_cyl, dtype=float)
+    single = sc.shape == (2,)
+    if single:
+        sc = sc[None, :]
+    seq, theta = sc[:, 0], sc[:, 1]
+    b = np.array([0., 0.5, -0.5]) * np.sqrt(2)   # the reference's form of the second in-plane unit vector
+    sp = (np.tensordot(np.cos(theta), _A_VEC, axes=0) + np.tensordot(np.sin(theta), b, axes=0)) * \
+        np.sqrt(2. / 3.) * np.array([seq, seq, seq]).T
+    return sp[0] if single else sp
+
+
 class Stress(object):
     """A Voigt stress with its tensor, principal values (axis-tracking order), hydrostatic and deviatoric parts
     (basic.py:366-484); ``seq(mat)`` is the material's equivalent stress (evaluated on the GPU through

@@ -1665,6 +1665,8 @@ void strip_free(plfx_ctx *c)
 
 }  // namespace
 
+#include "plfx_svm.hpp"
+
 extern "C" {
 
 const char *plfx_version(void) { return PLFX_VERSION; }
@@ -3029,6 +3031,20 @@ int plfx_predict_info(plfx_ctx *c, int64_t *applied, int64_t *skipped, int64_t *
     if (skipped) *skipped = c->n_pred_skipped;
     if (rejected) *rejected = c->n_pred_rejected;
     return PLFX_OK;
+}
+
+int plfx_svc_fit_batch(plfx_ctx *c, int n, int d, const double *X, const double *y, int nprob, const int32_t *off,
+                       const int32_t *idx, const double *C, const double *gamma, double tol, int64_t max_iter,
+                       double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status)
+{
+    return svc_fit_batch_impl(c, n, d, X, y, nprob, off, idx, C, gamma, tol, max_iter, alpha, rho, obj, iters, status);
+}
+
+int plfx_svc_decision_batch(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *sv_off,
+                            const int32_t *sv_idx, const double *coef, const double *intercept, const double *gamma,
+                            const int32_t *q_off, const int32_t *q_idx, double *dec)
+{
+    return svc_decision_batch_impl(c, n, d, X, nprob, sv_off, sv_idx, coef, intercept, gamma, q_off, q_idx, dec);
 }
 
 int plfx_set_response_maxit(plfx_ctx *c, int maxit)

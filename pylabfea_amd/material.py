@@ -7,8 +7,8 @@ the path named by BASELINE.json: ``elasticity`` (:2401), ``plasticity`` (:2466),
 (:974), ``epl_dot`` (:1009), ``C_tan`` (:1057) and the test harness ``calc_properties`` (:3062).
 Same names, argument meaning and error behaviour; arguments are never mutated.
 
-Out of scope here: SVC *training*, data import, plotting, texture/work-hardening
-features.  A trained SVC enters through :meth:`Material.set_svc` / :meth:`Material.from_sklearn`.
+Out of scope here: data import, plotting, texture/work-hardening features.  A trained SVC enters through
+:meth:`Material.train_SVC` (trained on the GPU), :meth:`Material.set_svc` or :meth:`Material.from_sklearn`.
 sdim=3 flow rules use the reference's axis-tracking principal stresses (exact for plane states);
 Tresca and Barlat Yld2004-18p are equivalent stresses only (the reference has no normal for them).
 ML materials: 6 stress features (sdim=6) or the 2 features (seq, polar angle) of ``setup_yf_SVM_3D`` (sdim=3).
@@ -20,7 +20,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .basic import eps_eq, sig_dev, sig_eq_j2, sig_polar_ang, sig_princ, yf_tolerance
+from .basic import eps_eq, sig_cyl2princ, sig_dev, sig_eq_j2, sig_polar_ang, sig_princ, yf_tolerance
 
 _point_ctx = {}        # shared contexts for point evaluations, one per GPU (each remembers the record it holds)
 
@@ -700,6 +700,215 @@ class Material(object):
         ca = Cel @ a
         return Cel - np.outer(ca, ca) / (a @ ca + self.khard)
 
+    # ------------------------------------------------------------------ SVC training
+    def create_sig_data(self, N=None, mat_ref=None, sdata=None, Nseq=2, sflow=None, offs=0.01, extend=False, rand=False,
+                        Fe=0.1, Ce=0.99):
+        """Training stresses and labels (material.py:1950-2056): yield-locus stresses of ``mat_ref`` along N directions
+        (or the given ``sdata``), scaled by Fe .. Ce into the elastic (label -1) and by 2-Ce .. 2-Fe (and 2.4, 3, 4, 5 with
+        ``extend``) into the plastic regime (label +1).  Returns (st (M, sdim), yt (M,))."""
+        if sflow is not None:
+            print('WARNING: Parameter "sflow" no longer used in function "create_sig_data".')
+        if self.sdim not in (3, 6):
+            raise ValueError('create_sig_data: call plasticity(sdim=3 or 6) first')
+        if sdata is None:
+            if mat_ref is None:
+                raise ValueError('create_data_sig: Neither sdata nor mat_ref are provided, cannot generate training data')
+            if self.sdim == 3:
+                if N is None:
+                    warnings.warn('create_sig_data: Neither N not theta provided. Continuing with N=36 (sdim=3)')
+                    N = 36
+                theta = np.linspace(-np.pi, np.pi, N) if not rand else 2. * (np.random.rand(N) - 0.5) * np.pi
+                sc = np.ones((N, 2))
+                sc[:, 1] = theta
+                su = sig_cyl2princ(sc)
+            else:
+                if N is None:
+                    warnings.warn('create_sig_data: Neither N not theta provided. Continuing with N=300 (sdim=6)')
+                    N = 300
+                from .training import load_cases
+                n3 = int(N / 3)
+                su = load_cases(n3, N - n3)
+                if self.dev_only:
+                    su = sig_dev(su)
+            sdata = su * mat_ref._yield_scale(su)[:, None]   # yield stress tensors representing ground truth
+        else:
+            sdata = np.asarray(sdata, dtype=float)
+            if N is not None and N != len(sdata):
+                warnings.warn(f'create_sig_data: N and dimension of sdata do not agree. Continuing with N ={len(sdata)}')
+            if mat_ref is not None:
+                warnings.warn('create_sig_data: using sdata for training, ignoring mat_ref')
+            N = len(sdata)
+        if self.dev_only:
+            sdata = sig_dev(sdata)
+        if Nseq == 1:
+            midpoint = 0.5 * (Fe + Ce)
+            seq = np.array([midpoint, 2. - midpoint])
+        else:
+            seq = np.append(np.linspace(Fe, Ce, Nseq), np.linspace(2. - Ce, 2. - Fe, Nseq))
+        if extend:
+            seq = np.append(seq, np.array([2.4, 3., 4., 5.]))
+        Nd = len(seq)
+        st = np.zeros((N * Nd, self.sdim))
+        yt = np.zeros(N * Nd)
+        for i in range(Nd):
+            st[i * N:(i + 1) * N, :] = sdata[:, 0:self.sdim] * seq[i]
+            yt[i * N:(i + 1) * N] = -1. if i < Nseq else +1.
+        return st, yt
+
+    def _yield_scale(self, su):
+        """factor x per unit stress with calc_yf(x su) = 0 (the root of find_yloc that the reference takes with fsolve):
+        sy / calc_seq(su) for the homogeneous analytic yield functions (J2, Hill, Drucker-Prager), a bracketed bisection on
+        the device's calc_yf otherwise"""
+        su = np.asarray(su, dtype=float)
+        if self.sy is None:
+            raise ValueError('create_sig_data: the reference material has no yield strength')
+        if not (self.ML_yf or self.tresca or self.barlat or getattr(self, 'whdat', False)):
+            return self.sy / self.calc_seq(su)
+        n = len(su)
+        lo, hi = np.zeros(n), np.full(n, float(self.sy))
+        for _ in range(60):   # bracket: grow hi until the yield function is positive
+            f = self.find_yloc(hi, su)
+            if np.all(f > 0.):
+                break
+            hi = np.where(f > 0., hi, 2. * hi)
+        else:
+            raise ValueError('create_sig_data: yield locus of the reference material could not be bracketed')
+        for _ in range(64):
+            mid = 0.5 * (lo + hi)
+            f = self.find_yloc(mid, su)
+            lo, hi = np.where(f > 0., lo, mid), np.where(f > 0., mid, hi)
+        return 0.5 * (lo + hi)
+
+    def _svc_refuse(self, what):
+        if getattr(self, 'msparam', None) is not None or getattr(self, 'txdat', False) or getattr(self, 'whdat', False):
+            raise NotImplementedError('%s: training from microstructure data (msparam / Data / texture / work hardening) '
+                                      'is not supported; train from mat_ref or sdata' % what)
+
+    def _svc_fit(self, X, y, C, gamma, gridsearch, cvals, gvals, dflt_c, dflt_g, metric):
+        """fit the SVC on the GPU (with grid search: all candidates x 5 folds in one batched call, then the refit) and
+        install it; returns (training score, fitted model)"""
+        y = np.asarray(y, dtype=float)
+        if np.any((y != 1.) & (y != -1.)):
+            raise NotImplementedError('train_SVC: only binary labels -1 / +1 are supported (got %s)' % np.unique(y))
+        if metric not in ('acc', 'mcc'):
+            raise ValueError(f"{metric} must be acc or mcc")
+        if not (C > 0 and gamma > 0):
+            raise ValueError('train_SVC: C and gamma must be > 0 (got C=%r, gamma=%r)' % (C, gamma))
+        ctx = _ctx()
+        if gridsearch:
+            from .training import param_grid, stratified_folds
+            if cvals is None:   # the reference's default grid, extended by the given C and gamma
+                cvals = list(dflt_c) + ([] if C in dflt_c else [C])
+            if gvals is None:
+                gvals = list(dflt_g) + ([] if gamma in dflt_g else [gamma])
+            self.grid = svc_grid_search(ctx, X, y, param_grid(cvals, gvals), stratified_folds(y))
+            print('The best hyperparameters are:', self.grid['best_params_'])
+            C, gamma = self.grid['best_params_']['C'], self.grid['best_params_']['gamma']
+        model = SVCModel.fit(ctx, X, y, C, gamma)
+        self.svm_yf = model
+        self.gam_yf, self.C_yf = gamma, C
+        pred = model.predict(X)
+        sc = 100. * float(np.mean(pred == y)) if metric == 'acc' else _mcc(y, pred)
+        return sc, model
+
+    def _svc_score(self, model, X, y, metric='acc'):
+        if X is None:
+            return None
+        pred = model.predict(X)
+        return 100. * float(np.mean(pred == np.asarray(y))) if metric == 'acc' else _mcc(np.asarray(y), pred)
+
+    def setup_yf_SVM_6D(self, x, y_train, x_test=None, y_test=None, C=10., gamma=1., plot=False, gridsearch=False,
+                        cvals=None, gvals=None, verbose=3, pca_dim=10, metric='acc'):
+        """Train the SVC yield function on (N, 6) Voigt stresses scaled by sy (material.py:1109-1278) on the GPU;
+        returns (train score, test score or None) for ``metric`` 'acc' (percent) or 'mcc'."""
+        self._svc_refuse('setup_yf_SVM_6D')
+        if plot:
+            raise NotImplementedError('setup_yf_SVM_6D: plotting is not supported')
+        if self.sdim != 6:
+            raise ValueError('setup_yf_SVM_6D: material must have sdim=6')
+        self.scale_seq = self.sy
+        self.Ndof, self.whdat = 6, False
+        X_train = self.create_scaled_input(np.asarray(x, dtype=float)[:, 0:6])
+        X_test = None if x_test is None else self.create_scaled_input(np.asarray(x_test, dtype=float)[:, 0:6])
+        train_sc, m = self._svc_fit(X_train, y_train, C, gamma, gridsearch, cvals, gvals,
+                                    [1, 2, 4, 10], [0.5, 1, 1.5, 2, 2.5, 3], metric)
+        self.set_svc(m.support_vectors_, m.dual_coef_[0], m.intercept_[0], m.gamma, self.scale_seq, dev_only=self.dev_only,
+                     C=m.C)
+        return train_sc, self._svc_score(m, X_test, y_test, metric)
+
+    def setup_yf_SVM_3D(self, x, y_train, x_test=None, y_test=None, C=10., gamma=1., fs=0.1, plot=False, cyl=False,
+                        gridsearch=False, cvals=None, gvals=None, pca_dim=10):
+        """Train the 2-feature SVC yield function of sdim = 3 (material.py:1280-1440) on the GPU: features
+        (seq_J2 / sy - 1, polar angle / pi) of principal (or, with ``cyl``, cylindrical) stresses, with the borders
+        |theta/pi| > 1 - fs copied across the period; returns (train score, test score or None) in percent."""
+        self._svc_refuse('setup_yf_SVM_3D')
+        if plot:
+            raise NotImplementedError('setup_yf_SVM_3D: plotting is not supported')
+        if self.sdim != 3:
+            raise ValueError('setup_yf_SVM_3D: material must have sdim=3')
+        self.scale_seq = self.sy
+        self.Ndof, self.whdat = 2, False
+
+        def feat(v):
+            v = np.asarray(v, dtype=float)
+            X = np.zeros((len(v), 2))
+            if not cyl:
+                X[:, 0] = sig_eq_j2(v[:, 0:3]) / self.scale_seq - 1.
+                X[:, 1] = sig_polar_ang(v[:, 0:3]) / np.pi
+            else:
+                X[:, 0] = v[:, 0] / self.scale_seq - 1.
+                X[:, 1] = v[:, 1] / np.pi
+            return X
+        X_train, y_train = feat(x), np.asarray(y_train, dtype=float)
+        indr = np.nonzero(X_train[:, 1] > 1. - fs)
+        indl = np.nonzero(X_train[:, 1] < fs - 1.)
+        Xr, Xl = X_train[indr], X_train[indl]
+        Xr[:, 1] -= 2.
+        Xl[:, 1] += 2.
+        X_train = np.append(X_train, np.append(Xr, Xl, axis=0), axis=0)
+        y_train = np.append(y_train, np.append(y_train[indr], y_train[indl], axis=0), axis=0)
+        X_test = None if x_test is None else feat(x_test)
+        train_sc, m = self._svc_fit(X_train, y_train, C, gamma, gridsearch, cvals, gvals,
+                                    [2, 4, 6, 8, 10, 15], [1, 1.5, 2, 2.5, 3], 'acc')
+        self.set_svc(m.support_vectors_, m.dual_coef_[0], m.intercept_[0], m.gamma, self.scale_seq, C=m.C)
+        return train_sc, self._svc_score(m, X_test, y_test)
+
+    def train_SVC(self, C=10, gamma=4, Nlc=36, Nseq=25, fs=0.3, extend=False, mat_ref=None, sdata=None, plot=False,
+                  fontsize=16, gridsearch=False, cvals=None, gvals=None, Fe=0.1, Ce=0.99, scaler=None, pca=None,
+                  train_index=None, test_index=None, verbose=1, metric='acc', pca_dim=10, reversal=None):
+        """Train the SVC yield function (material.py:1442-1640, the branch without microstructure data): elasticity and
+        plasticity from ``mat_ref`` (or sy = mean J2 stress of ``sdata``), training data from ``create_sig_data``, the fit
+        by the batched SMO solver on the GPU (libsvm's C-SVC).  Returns (train score, test score)."""
+        self._svc_refuse('train_SVC')
+        if scaler is not None or pca is not None or train_index is not None or test_index is not None:
+            raise NotImplementedError('train_SVC: scaler / pca / train_index / test_index belong to the texture path, '
+                                      'which is not supported')
+        if plot:
+            raise NotImplementedError('train_SVC: plotting is not supported')
+        if reversal is not None:
+            print('WARNING in "train_SVC": Parameter "reversal" is depracted and will be ignored.')
+        if sdata is None:
+            if mat_ref is None:
+                raise ValueError('create_data_sig: Neither sdata nor mat_ref are provided, cannot generate training data')
+            self.elasticity(CV=mat_ref.CV)
+            self.plasticity(sy=mat_ref.sy, sdim=mat_ref.sdim)
+            xt, yt = self.create_sig_data(N=Nlc, mat_ref=mat_ref, Nseq=Nseq, Fe=Fe, Ce=Ce, extend=extend)
+            print('Training data created from reference material', mat_ref.name, ', with', Nlc, 'load cases.')
+        else:
+            sdata = np.asarray(sdata, dtype=float)
+            self.plasticity(sy=np.mean(sig_eq_j2(sdata)), sdim=len(sdata[0, :]))
+            xt, yt = self.create_sig_data(sdata=sdata, Nseq=Nseq, Fe=Fe, Ce=Ce, extend=extend)
+            print('Training data created from {}-dimensional yield stresses with {} load cases.'.format(self.sdim, len(sdata)))
+        if self.sdim == 3:
+            train_sc, test_sc = self.setup_yf_SVM_3D(xt, yt, C=C, gamma=gamma, fs=0.3, gridsearch=gridsearch,
+                                                     cvals=cvals, gvals=gvals)
+        else:
+            train_sc, test_sc = self.setup_yf_SVM_6D(xt, yt, C=C, gamma=gamma, gridsearch=gridsearch, cvals=cvals,
+                                                     gvals=gvals, verbose=verbose, metric=metric)
+        if not gridsearch:
+            print(f"Training completed with score: {train_sc}")
+        return train_sc, test_sc
+
     # ------------------------------------------------------------------ harness
     def calc_properties(self, size=2, Nel=2, verb=False, eps=0.005, min_step=None, sigeps=False,
                         load_cases=['stx', 'sty', 'et2', 'ect']):
@@ -740,3 +949,90 @@ class Material(object):
             calc_strength(v1, n1, v2, n2, case)
             self.prop[case]['style'] = style
             self.prop[case]['name'] = label
+
+
+def _mcc(a, b):
+    from .training import _mcc as m
+    return m(a, b)
+
+
+class SVCModel(object):
+    """A fitted binary RBF C-SVC in scikit-learn's layout (``support_``, ``support_vectors_``, ``dual_coef_`` (1, nSV),
+    ``intercept_`` (1,), ``n_iter_`` (1,), ``n_support_``, ``C``, ``gamma``): what ``Material.svm_yf`` holds after
+    ``train_SVC``.  Fitted and evaluated on the GPU (plfx_svc_fit_batch / plfx_svc_decision_batch)."""
+
+    def __init__(self, ctx, X, y, C, gamma, alpha, rho, n_iter, status, obj):
+        X = np.asarray(X, dtype=float)
+        y = np.asarray(y, dtype=float)
+        order = np.concatenate([np.nonzero(y < 0)[0], np.nonzero(y > 0)[0]])   # libsvm's order: class -1 first
+        sv = order[alpha[order] > 0.]
+        self._ctx = ctx
+        self.C, self.gamma, self._gamma = float(C), float(gamma), float(gamma)
+        self.classes_ = np.array([-1., 1.])
+        self.support_ = sv.astype(np.int32)
+        self.support_vectors_ = X[sv]
+        self.dual_coef_ = (y[sv] * alpha[sv])[None, :]
+        self.intercept_ = np.array([-rho])
+        self.n_support_ = np.array([np.sum(y[sv] < 0), np.sum(y[sv] > 0)], dtype=np.int32)
+        self.n_iter_ = np.array([n_iter], dtype=np.int32)
+        self.fit_status_ = int(status)
+        self.dual_objective_ = float(obj)
+        if status:
+            warnings.warn('Solver terminated early (max_iter=%d).  Consider pre-processing your data with '
+                          'StandardScaler or MinMaxScaler.' % n_iter)
+
+    @classmethod
+    def fit(cls, ctx, X, y, C, gamma, tol=1e-3, max_iter=-1):
+        r = ctx.svc_fit_batch(X, y, [np.arange(len(y))], C, gamma, tol=tol, max_iter=max_iter)[0]
+        return cls(ctx, X, y, C, gamma, r['alpha'], r['rho'], r['n_iter'], r['status'], r['obj'])
+
+    def decision_function(self, X):
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        Xa = np.concatenate([self.support_vectors_, X])
+        nsv = len(self.support_vectors_)
+        return self._ctx.svc_decision_batch(Xa, [np.arange(nsv)], [self.dual_coef_[0]], [self.intercept_[0]], [self.gamma],
+                                            [nsv + np.arange(len(X))])[0]
+
+    def predict(self, X):
+        """labels as libsvm assigns them: decision >= 0 -> +1"""
+        return np.where(self.decision_function(X) >= 0., 1., -1.)
+
+    def score(self, X, y):
+        return float(np.mean(self.predict(X) == np.asarray(y)))
+
+
+def svc_grid_search(ctx, X, y, candidates, folds):
+    """Cross-validated grid search in ONE batched device call: every (C, gamma) candidate on every fold (train on the
+    other folds), then every fitted model on its held-out fold.  Returns dict(params, mean_test_score (mean fold
+    accuracy per candidate), split_test_scores, best_index_, best_params_); the best candidate is the first one with the
+    highest mean accuracy (GridSearchCV's rule)."""
+    X = np.asarray(X, dtype=float)
+    y = np.asarray(y, dtype=float)
+    n = len(y)
+    trains = [np.setdiff1d(np.arange(n), f) for f in folds]
+    probs, Cs, gs = [], [], []
+    for c, g in candidates:
+        for tr in trains:
+            probs.append(tr)
+            Cs.append(float(c))
+            gs.append(float(g))
+    fits = ctx.svc_fit_batch(X, y, probs, np.array(Cs), np.array(gs))
+    sv_lists, coefs, icpt, qlists = [], [], [], []
+    for k, r in enumerate(fits):
+        tr = probs[k]
+        yt = y[tr]
+        order = np.concatenate([np.nonzero(yt < 0)[0], np.nonzero(yt > 0)[0]])
+        sv = order[r['alpha'][order] > 0.]
+        sv_lists.append(tr[sv])
+        coefs.append(yt[sv] * r['alpha'][sv])
+        icpt.append(-r['rho'])
+        qlists.append(folds[k % len(folds)])
+    dec = ctx.svc_decision_batch(X, sv_lists, coefs, icpt, np.array(gs), qlists)
+    nf = len(folds)
+    split = np.array([float(np.mean(np.where(dec[k] >= 0., 1., -1.) == y[qlists[k]])) for k in range(len(fits))])
+    split = split.reshape(len(candidates), nf)
+    mean = np.array([np.average(s) for s in split])
+    best = int(np.flatnonzero(mean == mean.max())[0])
+    return dict(params=[{'C': c, 'gamma': g} for c, g in candidates], mean_test_score=mean, split_test_scores=split,
+                n_iter=np.array([r['n_iter'] for r in fits]).reshape(len(candidates), nf),
+                best_index_=best, best_params_={'C': candidates[best][0], 'gamma': candidates[best][1]})

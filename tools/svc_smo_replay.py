@@ -1,0 +1,159 @@
+#!/usr/bin/env python3
+"""CPU replay of the SMO rules that the device solver (pylabfea_amd/csrc/plfx_svm.hpp) follows, in NumPy.
+
+This is the debugging aid for the device solver: libsvm's non-shrinking C-SVC solver step for step (second-order working-set
+selection, the analytic two-variable update, G from both kernel rows), with kernel rows computed in FP64 and stored as FP32
+like libsvm's ``Qfloat``.  It can print the working pair (i, j) of every iteration, so the first iteration where the device
+and this replay (or libsvm) part can be found.
+
+The problem is laid out as libsvm sees it inside scikit-learn: the classes are sorted, so the rows of label -1 come first
+(internal y = +1) and the rows of label +1 follow (internal y = -1).  Results are returned in scikit-learn's convention
+(``dual_coef_ = label * alpha``, ``intercept_ = -rho``, decision > 0 <-> label +1) with ``support_`` in libsvm's order.
+
+Usage:  python tools/svc_smo_replay.py FIXTURE.npz CASE [--trace N]     (FIXTURE from tools/gen_svc_training.py)
+"""
+import argparse
+import sys
+
+import numpy as np
+
+TAU = 1e-12
+
+
+def libsvm_order(y):
+    """row order of libsvm's binary sub-problem (label -1 first) and the internal labels in that order"""
+    y = np.asarray(y)
+    perm = np.concatenate([np.nonzero(y < 0)[0], np.nonzero(y > 0)[0]])
+    return perm, np.where(y[perm] < 0, 1, -1).astype(np.int8)
+
+
+def smo(X, y, C, gamma, tol=1e-3, max_iter=None, trace=0):
+    """non-shrinking libsvm SMO on (X, y in {-1, +1}); returns dict(support_, dual_coef_, intercept_, n_iter_, obj, alpha)"""
+    X = np.ascontiguousarray(X, dtype=float)
+    perm, yi = libsvm_order(y)
+    Xp = X[perm]
+    n = len(Xp)
+    if max_iter is None:
+        max_iter = max(10000000, 100 * n)
+    xsq = np.einsum('ij,ij->i', Xp, Xp)
+    yd = yi.astype(float)
+
+    def row(i):   # Q_i as libsvm's SVC_Q::get_Q: (Qfloat)(y_i y_t K(i, t))
+        k = np.exp(-gamma * (xsq[i] + xsq - 2 * (Xp @ Xp[i])))
+        return (yd[i] * yd * k).astype(np.float32)
+
+    QD = np.exp(-gamma * (xsq + xsq - 2 * xsq))
+    alpha = np.zeros(n)
+    G = -np.ones(n)
+    it = 0
+    while it < max_iter:
+        up = alpha >= C
+        lo = alpha <= 0
+        # i: argmax of -y G over I_up, ties to the LAST index (libsvm compares with >=)
+        v = np.where(yi > 0, np.where(~up, -G, -np.inf), np.where(~lo, G, -np.inf))
+        Gmax = v.max()
+        if Gmax == -np.inf:
+            break
+        i = n - 1 - int(np.argmax(v[::-1]))
+        Qi = row(i)
+        cand = np.where(yi > 0, ~lo, ~up)
+        g2 = np.where(yi > 0, G, -G)
+        Gmax2 = np.max(np.where(cand, g2, -np.inf))
+        gd = np.where(yi > 0, Gmax + G, Gmax - G)
+        quad = QD[i] + QD - np.where(yi > 0, 1., -1.) * (2.0 * yd[i] * Qi.astype(float))
+        quad = np.where(quad > 0, quad, TAU)
+        od = np.where(cand & (gd > 0), -(gd * gd) / quad, np.inf)
+        if Gmax + Gmax2 < tol or not np.any(cand & (gd > 0)):
+            break
+        j = n - 1 - int(np.argmin(od[::-1]))
+        it += 1
+        if trace and it <= trace:
+            print('iter %d  i=%d j=%d  Gmax=%.17g' % (it, i, j, Gmax))
+        Qj = row(j)
+        ai, aj = alpha[i], alpha[j]
+        if yi[i] != yi[j]:
+            q = QD[i] + QD[j] + 2 * float(Qi[j])
+            if q <= 0:
+                q = TAU
+            delta = (-G[i] - G[j]) / q
+            diff = ai - aj
+            ni, nj = ai + delta, aj + delta
+            if diff > 0:
+                if nj < 0:
+                    nj, ni = 0., diff
+            elif ni < 0:
+                ni, nj = 0., -diff
+            if diff > 0:    # C_i - C_j = 0
+                if ni > C:
+                    ni, nj = C, C - diff
+            elif nj > C:
+                nj, ni = C, C + diff
+        else:
+            q = QD[i] + QD[j] - 2 * float(Qi[j])
+            if q <= 0:
+                q = TAU
+            delta = (G[i] - G[j]) / q
+            s = ai + aj
+            ni, nj = ai - delta, aj + delta
+            if s > C:
+                if ni > C:
+                    ni, nj = C, s - C
+            elif nj < 0:
+                nj, ni = 0., s
+            if s > C:
+                if nj > C:
+                    nj, ni = C, s - C
+            elif ni < 0:
+                ni, nj = 0., s
+        alpha[i], alpha[j] = ni, nj
+        G += Qi.astype(float) * (ni - ai) + Qj.astype(float) * (nj - aj)
+    rho = calc_rho(alpha, G, yi, C)
+    sv = np.nonzero(alpha > 0)[0]
+    return dict(support_=perm[sv], dual_coef_=-(yd[sv] * alpha[sv]), intercept_=rho, n_iter_=it,
+                obj=0.5 * float(np.sum(alpha * (G - 1.))), alpha=alpha, perm=perm)
+
+
+def calc_rho(alpha, G, yi, C):
+    """libsvm's Solver::calculate_rho, sequential sum as there"""
+    ub, lb, s, nf = np.inf, -np.inf, 0., 0
+    for a, g, y in zip(alpha, G, yi):
+        yG = y * g
+        if a >= C:
+            if y == -1:
+                ub = min(ub, yG)
+            else:
+                lb = max(lb, yG)
+        elif a <= 0:
+            if y == 1:
+                ub = min(ub, yG)
+            else:
+                lb = max(lb, yG)
+        else:
+            nf += 1
+            s += yG
+    return s / nf if nf else 0.5 * (ub + lb)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('fixture')
+    ap.add_argument('case')
+    ap.add_argument('--trace', type=int, default=0, help='print (i, j) of the first N iterations')
+    a = ap.parse_args()
+    z = np.load(a.fixture)
+    c = a.case
+    if c + '_X' in z.files:
+        X, y = z[c + '_X'], z[c + '_y']
+    else:   # compact form: the training stresses are seq[i] * sdata block by block, the features those over sy
+        sd, seq = z[c + '_sdata'], z[c + '_seq']
+        X = (seq[:, None, None] * sd[None, :, :]).reshape(-1, sd.shape[1]) / float(z[c + '_sy'])
+        y = np.repeat(np.where(np.arange(len(seq)) < int(z[c + '_Nseq']), -1., 1.), len(sd))
+    r = smo(X, y, float(z[c + '_C']), float(z[c + '_gamma']), trace=a.trace)
+    print('n_iter %d (libsvm without shrinking: %d), nSV %d (%d), intercept %.17g (%.17g)' % (
+        r['n_iter_'], int(z[c + '_ns_n_iter']), len(r['support_']), len(z[c + '_ns_support']), r['intercept_'],
+        float(z[c + '_ns_intercept'])))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
