@@ -2,7 +2,8 @@
 //
 // HBM layout (FP64 / int32, everything resident for the life of the mesh):
 //   per owned element e (SoA, component-major [c*nel + e]): sig[6] epl[6] eps[6] res_sig[6]
-//     res_depl[6] elstiff[21, symmetric] M[6] (compact stiffness generator) fyn max_steps cls
+//     res_depl[6] tangent (TanStore: form tag, factors[7], elstiff[21, symmetric]) M[6] (compact stiffness generator)
+//     fyn max_steps cls
 //   connectivity conn[nel_total*4] (global element ids), per node: block-ELL matrix
 //     val[nslot][2x2][nnode], col[nslot][nnode], contrib[nslot][nq][nnode] (assembly gather lists)
 //   per DOF (interleaved x,y per node = double2): u f du rhs dinv diag is_presc + PCG vectors
@@ -174,7 +175,11 @@ struct plfx_ctx {
 
     // element state (owned)
     double *sig = nullptr, *epl = nullptr, *eps = nullptr, *res_sig = nullptr, *res_depl = nullptr;
-    double *elstiff = nullptr, *Mel = nullptr, *fyn = nullptr, *scf_hh = nullptr;
+    double *Mel = nullptr, *fyn = nullptr, *scf_hh = nullptr;
+    // element tangents (TanStore, plfx_kernels.hpp): one allocation tan_buf = [21][nel] full entries (elstiff), [7][nel] factors
+    // (elfac), [nel] form tags (eltag)
+    double *tan_buf = nullptr, *elstiff = nullptr, *elfac = nullptr;
+    uint8_t *eltag = nullptr;
     double *kh_el = nullptr;   // hardening modulus per material point (work-hardening SVC: mutable, carried from sweep to sweep)
     // work-hardening SVC, sequential carry (the reference's semantics, plfx_kernels.hpp: k_wh_entry): kh_el holds the ENTRY
     // modulus of every element, kh_out / kh_touch what its response() left, wh_carry the value each material object holds now
@@ -426,6 +431,28 @@ void dfree(T *&p)
     if (p) hipFree(p);
     p = nullptr;
 }
+
+// doubles of the tangent store of n elements: 21 entries + 7 factors + one tag byte per element
+inline size_t tan_words(size_t n) { return 28 * n + (n + 7) / 8; }
+
+int tan_alloc(plfx_ctx *c, size_t n)
+{
+    int rc = dalloc(c, &c->tan_buf, tan_words(n));
+    if (rc) return rc;
+    c->elstiff = c->tan_buf;
+    c->elfac = c->tan_buf + 21 * n;
+    c->eltag = reinterpret_cast<uint8_t *>(c->tan_buf + 28 * n);
+    return 0;
+}
+
+void tan_free(plfx_ctx *c)
+{
+    dfree(c->tan_buf);
+    c->elstiff = c->elfac = nullptr;
+    c->eltag = nullptr;
+}
+
+inline TanStore tan_store(const plfx_ctx *c) { return TanStore{c->eltag, c->elfac, c->elstiff}; }
 
 // blocks of the kernels that reduce the 18 element sums of calc_global (part_g): k_update_state<1> at 1024^2, same-box
 // rocprofv3 averages (tools/probes/r04_sumpart_ab.sh): 1024 blocks with 18 sequential block sums 86-88 us; the 18 sums behind
@@ -809,7 +836,7 @@ void free_mesh(plfx_ctx *c)
     dfree(c->eps);
     dfree(c->res_sig);
     dfree(c->res_depl);
-    dfree(c->elstiff);
+    tan_free(c);
     dfree(c->Mel);
     dfree(c->fyn);
     dfree(c->scf_hh);
@@ -1841,6 +1868,13 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
 {
     if (!c || !c->stream) return PLFX_ERR_STATE;
     if (nmat < 1 || nmat > MAXMAT || !mats) return fail(c, PLFX_ERR_ARG, "nmat must be in 1..%d", MAXMAT);
+    if (c->tan_buf && c->dmat && c->nel > 0) {
+        // the tangent store refers to the CV of the current materials: hold every stored tangent in full form first
+        hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
+                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->elstiff, 1);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, stream_sync(c));
+    }
     free_materials(c);
     c->has_svc = c->has_svc3 = c->has_analytic = c->has_elastic = c->has_princ = false;
     c->has_barlat = false;
@@ -2352,7 +2386,7 @@ static int set_mesh_impl(plfx_ctx *c, int nel, int nnode, const int32_t *conn, c
     ALLOC(c->eps, (size_t)6 * nown);
     ALLOC(c->res_sig, (size_t)6 * nown);
     ALLOC(c->res_depl, (size_t)6 * nown);
-    ALLOC(c->elstiff, (size_t)21 * nown);
+    if ((rc = tan_alloc(c, nown))) return rc;
     ALLOC(c->Mel, (size_t)6 * nel);  // whole mesh (global element ids)
     ALLOC(c->fyn, nown);
     ALLOC(c->scf_hh, nown);
@@ -3278,7 +3312,7 @@ int plfx_state_reset(plfx_ctx *c)
         c->kh_out_valid = false;
     }
     hipLaunchKernelGGL(k_init_tangent, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                       c->dmat, c->dcls, c->nel, c->dcls_id, c->elstiff, c->Mel + c->e0, c->nel_total);
+                       c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->Mel + c->e0, c->nel_total);
     if (c->sharded)
         hipLaunchKernelGGL(k_init_M_all, dim3((c->nel_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
                            c->dmat, c->dcls, c->nel_total, c->dcls_all, c->Mel);
@@ -3331,8 +3365,20 @@ int plfx_state_get(plfx_ctx *c, int which, double *out)
         return PLFX_OK;
     }
     std::vector<double> t(comps * n);
-    HIPCHK(c, hipMemcpyAsync(t.data(), p, 8 * comps * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
+    if (which == 5) {  // the tangent store expanded to 21 entries per element
+        double *tmp = nullptr;
+        if ((rc = dalloc(c, &tmp, 21 * n))) return rc;
+        hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
+                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), tmp, 0);
+        hipError_t er = hipGetLastError();
+        if (er == hipSuccess) er = hipMemcpyAsync(t.data(), tmp, 8 * comps * n, hipMemcpyDeviceToHost, c->stream);
+        if (er == hipSuccess) er = stream_sync(c);
+        dfree(tmp);
+        HIPCHK(c, er);
+    } else {
+        HIPCHK(c, hipMemcpyAsync(t.data(), p, 8 * comps * n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, stream_sync(c));
+    }
     if (comps == 6) {
         for (size_t e = 0; e < n; e++)
             for (int k = 0; k < 6; k++) out[6 * e + k] = t[(size_t)k * n + e];
@@ -3370,10 +3416,11 @@ int plfx_state_set(plfx_ctx *c, int which, const double *in)
                 for (int j = i; j < 6; j++) t[(size_t)sym_idx(i, j) * n + e] = in[36 * e + 6 * i + j];
     }
     HIPCHK(c, hipMemcpyAsync(p, t.data(), 8 * comps * n, hipMemcpyHostToDevice, c->stream));
-    if (which == 5) {
+    if (which == 5) {  // every element's tangent is now held in full form
         c->M_dirty = true;
+        HIPCHK(c, hipMemsetAsync(c->eltag, TAN_FULL, n, c->stream));
         hipLaunchKernelGGL(k_refresh_M, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                           c->dcls, c->nel, c->dcls_id, c->elstiff, c->Mel + c->e0, c->nel_total);
+                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->Mel + c->e0, c->nel_total);
         HIPCHK(c, hipGetLastError());
         int rcm = sync_M(c);
         if (rcm) return rcm;
@@ -3907,7 +3954,7 @@ int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
     const int g = grid_for(c->nel, SUMPART);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->dcls, c->nel,
                        c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
-                       c->eps, c->elstiff, c->res_sig, c->res_depl, c->nonlin ? 1 : 0, c->part_g,
+                       c->eps, tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, c->part_g,
                        c->strip.on ? c->strip.eown_lo : 0, c->strip.on ? c->strip.eown_hi : 0x7fffffff);
     const int n = c->fin_n;
     const int tot = 2 * n + 18;
@@ -4957,7 +5004,16 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
                 fprintf(stderr, "\n      epl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
                 for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_depl + k * n + e, 8, hipMemcpyDeviceToHost);
                 fprintf(stderr, "\n      res_depl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-                for (int k = 0; k < 21; k++) hipMemcpy(&v[k], c->elstiff + k * n + e, 8, hipMemcpyDeviceToHost);
+                {
+                    double *tmp = nullptr;
+                    if (!dalloc(c, &tmp, 21 * n)) {
+                        hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
+                                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), tmp, 0);
+                        hipStreamSynchronize(c->stream);
+                        for (int k = 0; k < 21; k++) hipMemcpy(&v[k], tmp + k * n + e, 8, hipMemcpyDeviceToHost);
+                        dfree(tmp);
+                    }
+                }
                 fprintf(stderr, "\n      elstiff(21) =");
                 for (int k = 0; k < 21; k++) fprintf(stderr, " %.5e", v[k]);
                 hipMemcpy(&ms, c->max_steps + e, 4, hipMemcpyDeviceToHost);
@@ -5108,7 +5164,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     EvPair *ev;
     tim_begin(c, 0, &ev);
 #define SWEEP_ARGS(lds) c->dmat, c->nmat, c->dcls, c->ncls, lds, c->nel, c->e0, c->dconn, c->dcls_id,          \
-                        (const double2 *)c->du, c->sig, c->epl, c->elstiff, c->Mel + c->e0, c->nel_total,   \
+                        (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, \
                         c->res_sig, c->res_depl, c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     // phase 1 per material kind present (the first launched instantiation also clears fyn of elastic elements)
     int first = 1;
@@ -5119,7 +5175,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     const int grid_w = std::max(1, std::min((c->nel + 3) / 4, 1024));
     const int grid_r = std::max(1, std::min((c->nel + 31) / 32, 1024));   // 16 lanes per element: 32 elements per block and round
 #define WAVE_ARGS c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,  \
-                  c->sig, c->epl, c->elstiff, c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,         \
+                  c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,       \
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh)) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
@@ -5169,7 +5225,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     if (c->has_svcwh && wh_wave) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_wh_wave<0>), dim3(grid_wh), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
                            c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn, c->dcls_id,
-                           (const double2 *)c->du, c->sig, c->epl, c->elstiff, c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
+                           (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
                            c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list, first, c->kh_el,
                            wh_seq ? c->kh_out : (double *)nullptr, wh_seq ? c->kh_touch : (int32_t *)nullptr);
         first = 0;
@@ -5211,7 +5267,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     if (c->has_svcwh && wh_wave)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_wh_wave<1>), dim3(grid_wh), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
                            c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn, c->dcls_id,
-                           (const double2 *)c->du, c->sig, c->epl, c->elstiff, c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
+                           (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
                            c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list, 0, c->kh_el,
                            wh_seq ? c->kh_out : (double *)nullptr, wh_seq ? c->kh_touch : (int32_t *)nullptr);
     else if (c->has_svcwh)
@@ -5289,11 +5345,11 @@ static int sweep_wh_sequential(plfx_ctx *c, int nit, int *changed, int *conv)
     if (!c->kh_out) {
         if ((rc = dalloc(c, &c->kh_out, ne)) || (rc = dalloc(c, &c->kh_new, ne)) || (rc = dalloc(c, &c->kh_touch, ne)) ||
             (rc = dalloc(c, &c->wh_bmax, (size_t)nblk)) || (rc = dalloc(c, &c->wh_cnt, 4)) ||
-            (rc = dalloc(c, &c->wh_snap_el, 21 * ne)) || (rc = dalloc(c, &c->wh_snap_M, (size_t)6 * c->nel_total)) ||
+            (rc = dalloc(c, &c->wh_snap_el, tan_words(ne))) || (rc = dalloc(c, &c->wh_snap_M, (size_t)6 * c->nel_total)) ||
             (rc = dalloc(c, &c->wh_snap_ms, ne)))
             return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(c->wh_snap_el, c->elstiff, 21 * ne * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->wh_snap_el, c->tan_buf, tan_words(ne) * 8, hipMemcpyDeviceToDevice, c->stream));  // tags and factors too
     HIPCHK(c, hipMemcpyAsync(c->wh_snap_M, c->Mel, (size_t)6 * c->nel_total * 8, hipMemcpyDeviceToDevice, c->stream));
     // max_steps is a running maximum (sweep_epilogue): passes that ran with entry moduli the chain does not confirm must not leave their counts
     HIPCHK(c, hipMemcpyAsync(c->wh_snap_ms, c->max_steps, ne * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -5313,7 +5369,7 @@ static int sweep_wh_sequential(plfx_ctx *c, int nit, int *changed, int *conv)
     int pass = 0;
     for (;; pass++) {
         if (pass > 0) {
-            HIPCHK(c, hipMemcpyAsync(c->elstiff, c->wh_snap_el, 21 * ne * 8, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->tan_buf, c->wh_snap_el, tan_words(ne) * 8, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(c->Mel, c->wh_snap_M, (size_t)6 * c->nel_total * 8, hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(c->max_steps, c->wh_snap_ms, ne * 4, hipMemcpyDeviceToDevice, c->stream));
         }
@@ -5429,13 +5485,13 @@ static void launch_scf_elements(plfx_ctx *c)
     const unsigned fast = (svc_poly() == 2) ? svc_fast_mask(c) : 0u;
     hipLaunchKernelGGL(k_scf_elements, dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
                        c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn,
-                       c->dcls_id, (const double2 *)c->du, c->sig, c->epl, c->elstiff,
+                       c->dcls_id, (const double2 *)c->du, c->sig, c->epl, tan_store(c),
                        c->small + 32, c->scf_hh, c->scf_mult, scf_moduli(c), fast);
     for (int k = 0; k < c->nmat; k++)
         if ((fast >> k) & 1u)
             LAUNCH_ROW1(c, k, k_scf_row, dim3(std::max(1, std::min((c->nel + 31) / 32, 1024))),
                        c->dmat, c->nmat, c->dcls, k, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                       c->sig, c->epl, c->elstiff, c->small + 32, c->scf_hh, c->scf_mult);
+                       c->sig, c->epl, tan_store(c), c->small + 32, c->scf_hh, c->scf_mult);
 }
 
 int plfx_scf_stats(plfx_ctx *c, const double *sld, double *sum, double *sumsq_c, double *minv,
@@ -5527,7 +5583,7 @@ int plfx_update_state(plfx_ctx *c)
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
                        c->dmat, c->dcls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                       (const double2 *)c->u, c->sig, c->epl, c->eps, c->elstiff, c->res_sig,
+                       (const double2 *)c->u, c->sig, c->epl, c->eps, tan_store(c), c->res_sig,
                        c->res_depl, c->nonlin ? 1 : 0, (double *)nullptr);
     HIPCHK(c, hipGetLastError());
     return PLFX_OK;

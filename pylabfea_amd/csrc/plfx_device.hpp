@@ -1908,6 +1908,8 @@ using YfSvcWave = YfSvcT<6, NC, POLY>;
 //   increment and st_scal the plastic share; fy/depl/Ct are not valid yet.
 // response_heavy: the maxit = 50 sub-steps with radial scale-back (:295-344).
 // In/out: sig (updated to the end of the step).  Out: fy, depl, Ct (21 symmetric entries).
+// response_light<true> (the sweeps, which keep tangents in factored form -- TanStore): Ct is left alone on an elastic step
+// (the tangent is CV) and receives (w1, ca[0..5]) on a one-step return, from which its 21 entries follow (tan_fac_entry).
 // yf.fgrad(sig) followed by yf.plain(s2): one pass over the support vectors for policies that offer it (YfSvcRow)
 template <class YF>
 __device__ __forceinline__ auto grad_and_yf(const YF &yf, const double *sig, const double *epl, const double *s2, double *a)
@@ -1922,7 +1924,7 @@ __device__ __forceinline__ double grad_and_yf(const YF &yf, const double *sig, c
     return yf.plain(s2, epl);
 }
 
-template <class YF>
+template <bool FAC = false, class YF>
 __device__ inline int response_light(const MatDev &m, const YF &yf, double *sig, const double *epl,
                                      const double *deps, double &fy, double *depl, double *Ct,
                                      double *deps_r, double &st_scal)
@@ -1940,8 +1942,10 @@ __device__ inline int response_light(const MatDev &m, const YF &yf, double *sig,
     if (fy1 < toler) {               // purely elastic step :253-256
 #pragma unroll
         for (int i = 0; i < 6; i++) sig[i] = tmp[i];
+        if (!FAC) {
 #pragma unroll
-        for (int i = 0; i < 21; i++) Ct[i] = CV[i];
+            for (int i = 0; i < 21; i++) Ct[i] = CV[i];
+        }
         fy = fy1;
         return 0;
     }
@@ -1989,10 +1993,16 @@ __device__ inline int response_light(const MatDev &m, const YF &yf, double *sig,
                 sig[i] = tmp[i];
                 depl[i] = ddepl[i];
             }
+            if (FAC) {
+                Ct[0] = w1;
 #pragma unroll
-            for (int i = 0; i < 6; i++)
+                for (int i = 0; i < 6; i++) Ct[1 + i] = ca[i];
+            } else {
 #pragma unroll
-                for (int j = i; j < 6; j++) Ct[sym_idx(i, j)] = fma(-w1 * ca[i], ca[j], CV[sym_idx(i, j)]);
+                for (int i = 0; i < 6; i++)
+#pragma unroll
+                    for (int j = i; j < 6; j++) Ct[sym_idx(i, j)] = fma(-w1 * ca[i], ca[j], CV[sym_idx(i, j)]);
+            }
             fy = fy1;
             return 1;
         }

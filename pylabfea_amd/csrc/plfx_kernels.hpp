@@ -426,11 +426,66 @@ __device__ __forceinline__ void tangent_to_M(const double *D, double kappa, doub
     M[5] = D[sym_idx(5, 5)];                                                                       // SS
 }
 
+// Element tangent store.  Almost every stored tangent is one of two cheap forms, so each owned element
+// keeps a form tag and only what its form needs (SoA, component k of element e at [k*nel + e]):
+//   TAN_CV   the elastic tangent CV of the element's material (nothing stored)
+//   TAN_FAC  the tangent of a one-step plastic return, Ct[ij] = fma(-w1*ca[i], ca[j], CV[ij]): fac = (w1, ca[0..5])
+//   TAN_FULL all 21 symmetric entries in `full` (50-sub-step corrector, averaged tangent of K-iteration >= 15, state_set)
+// Expanding a form repeats the very operation that produced the entries, so every reader sees the same bits as from a
+// stored 21-entry tangent.
+enum : uint8_t { TAN_CV = 0, TAN_FAC = 1, TAN_FULL = 2 };
+struct TanStore {
+    uint8_t *tag;  // [nel]
+    double *fac;   // [7][nel]
+    double *full;  // [21][nel]
+};
+
+__device__ __forceinline__ double tan_fac_entry(const double *CV, const double *f, int i, int j)
+{
+    return fma(-f[0] * f[1 + i], f[1 + j], CV[sym_idx(i, j)]);  // response_light, one-step return
+}
+
+// the 21 entries of a tangent in form `form`; T = factors (TAN_FAC) or entries (TAN_FULL) held in registers
+__device__ __forceinline__ void tan_expand(int form, const double *CV, const double *T, double *D)
+{
+    if (form == TAN_FULL) {
+#pragma unroll
+        for (int k = 0; k < 21; k++) D[k] = T[k];
+    } else if (form == TAN_FAC) {
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int j = i; j < 6; j++) D[sym_idx(i, j)] = tan_fac_entry(CV, T, i, j);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 21; k++) D[k] = CV[k];
+    }
+}
+
+// the 21 entries of the stored tangent of element e (CV: that of the element's material)
+__device__ __forceinline__ void tan_load(const TanStore &ts, int nel, int e, const double *CV, double *D)
+{
+    const int form = ts.tag[e];
+    if (form == TAN_FULL) {
+#pragma unroll
+        for (int k = 0; k < 21; k++) D[k] = ts.full[(size_t)k * nel + e];
+    } else if (form == TAN_FAC) {
+        double f[7];
+#pragma unroll
+        for (int k = 0; k < 7; k++) f[k] = ts.fac[(size_t)k * nel + e];
+        tan_expand(TAN_FAC, CV, f, D);
+    } else {
+        tan_expand(TAN_CV, CV, nullptr, D);
+    }
+}
+
 // Tail of the per-element sweep (model.py:1343-1357): store the response, yield-function ratio,
 // tangent test ||elstiff - Ct||_F > 1e-3 and tangent / stiffness-generator refresh.
+// The new tangent Ct comes in form `form` (response_light<true>: TAN_CV for st 0 with Ct unused, TAN_FAC for st 1 with the
+// factors in Ct[0..6]; the corrector: TAN_FULL).
 __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &m, int e, int nel,
                                                const double *s, const double *ep, const double *depl,
-                                               double *Ct, double fy, int ns, double *elstiff,
+                                               int form, const double *Ct, double fy, int ns, const TanStore &ts,
                                                double *Mel, int mel_stride, double *res_sig,
                                                double *res_depl, double *fyn, int32_t *max_steps, int nit,
                                                int &changed, int &nconv, double kh = -1.)
@@ -444,24 +499,34 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
     fyn[e] = f;
     if (!(f <= YF_TOL * 1.0001)) nconv = 1;  // model.py:1361
     // Frobenius norm of the tangent change over the full 6x6 (model.py:1346)
+    double Dold[21], Dnew[21];
+    tan_load(ts, nel, e, m.CV, Dold);
+    tan_expand(form, m.CV, Ct, Dnew);
     double hh = 0.;
 #pragma unroll
     for (int i = 0; i < 6; i++)
 #pragma unroll
         for (int j = i; j < 6; j++) {
-            const double d = elstiff[(size_t)sym_idx(i, j) * nel + e] - Ct[sym_idx(i, j)];
+            const double d = Dold[sym_idx(i, j)] - Dnew[sym_idx(i, j)];
             hh += (i == j ? 1. : 2.) * d * d;
         }
     hh = sqrt(hh);
     if (hh > 1.e-3) {  // model.py:1348-1355
         if (nit >= 15) {
 #pragma unroll
-            for (int k = 0; k < 21; k++) Ct[k] = 0.5 * (Ct[k] + elstiff[(size_t)k * nel + e]);
+            for (int k = 0; k < 21; k++) Dnew[k] = 0.5 * (Dnew[k] + Dold[k]);
+            form = TAN_FULL;
         }
+        ts.tag[e] = (uint8_t)form;
+        if (form == TAN_FULL) {
 #pragma unroll
-        for (int k = 0; k < 21; k++) elstiff[(size_t)k * nel + e] = Ct[k];
+            for (int k = 0; k < 21; k++) ts.full[(size_t)k * nel + e] = Dnew[k];
+        } else if (form == TAN_FAC) {
+#pragma unroll
+            for (int k = 0; k < 7; k++) ts.fac[(size_t)k * nel + e] = Ct[k];
+        }
         double M[6];
-        tangent_to_M(Ct, c.kappa, M);
+        tangent_to_M(Dnew, c.kappa, M);
 #pragma unroll
         for (int k = 0; k < 6; k++) Mel[(size_t)k * mel_stride + e] = M[k];
         changed += 1;  // counts the elements whose tangent (and generator) this thread rewrote
@@ -585,7 +650,7 @@ __global__ void __launch_bounds__(BLOCK, (KIND == 2 && PLFX_SWEEP_WAVES < 2) ? 2
 k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
               int lds_doubles, int nel, int e_off, const int32_t *__restrict__ conn,
               const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
-              const double *__restrict__ sig, const double *__restrict__ epl, double *elstiff,
+              const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts,
               double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
               int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, unsigned skip_mask,
               double *kh_el = nullptr /* KIND 7: hardening modulus of every material point, carried from sweep to sweep */,
@@ -623,11 +688,11 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
                 const bool staged = (c.mat == svc_mat);
                 const typename YfOf<KIND>::type yf =
                     make_policy<KIND>(m, staged ? sv : nullptr, staged ? dual : nullptr, (KIND == 7 && kh_el) ? kh_el[e] : m.khard);
-                const int st = response_light(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
+                const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
                 if (st == 2)
                     heavy = true;  // (the corrector kernel repeats the prelude from the same entry modulus)
                 else {
-                    sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, 0, elstiff, Mel, mel_stride, res_sig,
+                    sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, Mel, mel_stride, res_sig,
                                    res_depl, fyn, max_steps, nit, changed, nconv, KIND == 7 ? yf.kh() : -1.);
                     if (KIND == 7 && kh_el) {
                         (kh_out ? kh_out : kh_el)[e] = yf.kh();
@@ -656,7 +721,7 @@ __global__ void __launch_bounds__(BLOCK)
 k_sweep_heavy(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
               int lds_doubles, int nel, int e_off, const int32_t *__restrict__ conn,
               const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
-              const double *__restrict__ sig, const double *__restrict__ epl, double *elstiff,
+              const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts,
               double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
               int32_t *max_steps, int nit, int *flags, int *bflags, const int32_t *__restrict__ list, unsigned skip_mask,
               double *kh_el = nullptr, double *kh_out = nullptr, int32_t *kh_touch = nullptr)
@@ -689,9 +754,9 @@ k_sweep_heavy(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
         const bool staged = (c.mat == svc_mat);
         const typename YfOf<KIND>::type yf =
             make_policy<KIND>(m, staged ? sv : nullptr, staged ? dual : nullptr, (KIND == 7 && kh_el) ? kh_el[e] : m.khard);
-        response_light(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);  // recompute the prelude
+        response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);  // recompute the prelude
         response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
-        sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, MAXIT - 1, elstiff, Mel, mel_stride, res_sig,
+        sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, Mel, mel_stride, res_sig,
                        res_depl, fyn, max_steps, nit, changed, nconv, KIND == 7 ? yf.kh() : -1.);
         if (KIND == 7 && kh_el) {
             (kh_out ? kh_out : kh_el)[e] = yf.kh();
@@ -787,7 +852,7 @@ __global__ void __launch_bounds__(HEAVY ? PLFX_HEAVY_THREADS : 512)
 k_sweep_svc_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
                  int nel, int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls,
                  const double2 *__restrict__ du2, const double *__restrict__ sig, const double *__restrict__ epl,
-                 double *elstiff, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
+                 TanStore ts, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
                  int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, int wave_mat)
 {
     const int count = HEAVY ? flags[2] : nel;
@@ -817,16 +882,16 @@ k_sweep_svc_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__re
             ep[k] = epl[(size_t)k * nel + e];
         }
         const YfSvcWave<NC, POLY> yf(m, nullptr, nullptr, npad);
-        const int st = response_light(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
+        const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
         if (HEAVY) {
             response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
             if (lane == 0)
-                sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, MAXIT - 1, elstiff, Mel, mel_stride, res_sig,
+                sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, Mel, mel_stride, res_sig,
                                res_depl, fyn, max_steps, nit, changed, nconv);
         } else if (st == 2) {
             if (lane == 0) list[atomicAdd(&flags[2], 1)] = e;
         } else if (lane == 0) {
-            sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, 0, elstiff, Mel, mel_stride, res_sig, res_depl, fyn,
+            sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, Mel, mel_stride, res_sig, res_depl, fyn,
                            max_steps, nit, changed, nconv);
         }
     }
@@ -917,7 +982,7 @@ __global__ void __launch_bounds__(512)
 k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
                 int nel, int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls,
                 const double2 *__restrict__ du2, const double *__restrict__ sig, const double *__restrict__ epl,
-                double *elstiff, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
+                TanStore ts, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
                 int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, int wave_mat)
 {
     const int count = HEAVY ? flags[2] : nel;
@@ -950,16 +1015,16 @@ k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
             ep[k] = epl[(size_t)k * nel + e];
         }
         const YfSvcRow<NC, INLDS> yf(m, npad);
-        const int st = response_light(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
+        const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
         if (HEAVY) {
             response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
             if (l16 == 0)
-                sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, MAXIT - 1, elstiff, Mel, mel_stride, res_sig,
+                sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, Mel, mel_stride, res_sig,
                                res_depl, fyn, max_steps, nit, changed, nconv);
         } else if (st == 2) {
             if (l16 == 0) list[atomicAdd(&flags[2], 1)] = e;
         } else if (l16 == 0) {
-            sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, 0, elstiff, Mel, mel_stride, res_sig, res_depl, fyn,
+            sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, Mel, mel_stride, res_sig, res_depl, fyn,
                            max_steps, nit, changed, nconv);
         }
     }
@@ -975,7 +1040,7 @@ __global__ void __launch_bounds__(BLOCK)
 k_sweep_wh_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int lds_doubles,
                 int nel, int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls,
                 const double2 *__restrict__ du2, const double *__restrict__ sig, const double *__restrict__ epl,
-                double *elstiff, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
+                TanStore ts, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
                 int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind,
                 double *kh_el, double *kh_out, int32_t *kh_touch)
 {
@@ -1008,14 +1073,14 @@ k_sweep_wh_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
         }
         const bool staged = (c.mat == svc_mat);
         const YfSvcWhT<1> yf(m, staged ? sv : m.sv, staged ? dual : m.dual, kh_el ? kh_el[e] : m.khard);
-        const int st = response_light(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
+        const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
         if (HEAVY) response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
         if (!HEAVY && st == 2) {
             if (lane == 0) list[atomicAdd(&flags[2], 1)] = e;
             continue;
         }
         if (lane == 0) {
-            sweep_epilogue(c, m, e, nel, s, ep, depl, Ct, fy, HEAVY ? MAXIT - 1 : 0, elstiff, Mel, mel_stride, res_sig, res_depl, fyn,
+            sweep_epilogue(c, m, e, nel, s, ep, depl, HEAVY ? TAN_FULL : st, Ct, fy, HEAVY ? MAXIT - 1 : 0, ts, Mel, mel_stride, res_sig, res_depl, fyn,
                            max_steps, nit, changed, nconv, yf.kh());
             if (kh_el) {
                 (kh_out ? kh_out : kh_el)[e] = yf.kh();
@@ -1026,23 +1091,18 @@ k_sweep_wh_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
     post_block_flags(lane == 0 ? changed : 0, lane == 0 ? nconv : 0, bflags);
 }
 
-// elstiff = CV, M from CV for all owned elements (model.py:1219-1221)
+// elstiff = CV, M from CV for all owned elements (model.py:1219-1221): the tag alone stores the tangent
 __global__ void __launch_bounds__(BLOCK)
 k_init_tangent(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_t *cls,
-               double *elstiff, double *Mel, int mel_stride)
+               TanStore ts, double *Mel, int mel_stride)
 {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
     if (e >= nel) return;
     const ClassDev &c = gcls[cls[e]];
     const MatDev &m = gmat[c.mat];
-    double D[21];
-#pragma unroll
-    for (int k = 0; k < 21; k++) {
-        D[k] = m.CV[k];
-        elstiff[(size_t)k * nel + e] = D[k];
-    }
+    ts.tag[e] = TAN_CV;
     double M[6];
-    tangent_to_M(D, c.kappa, M);
+    tangent_to_M(m.CV, c.kappa, M);
 #pragma unroll
     for (int k = 0; k < 6; k++) Mel[(size_t)k * mel_stride + e] = M[k];
 }
@@ -1138,17 +1198,31 @@ k_zero_foreign_M(int nel_total, int e0, int e1, double *Mel)
 
 // recompute M from elstiff (after plfx_state_set of the tangent)
 __global__ void __launch_bounds__(BLOCK)
-k_refresh_M(const ClassDev *gcls, int nel, const int32_t *cls, const double *elstiff, double *Mel,
+k_refresh_M(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_t *cls, TanStore ts, double *Mel,
             int mel_stride)
 {
     const int e = blockIdx.x * BLOCK + threadIdx.x;
     if (e >= nel) return;
+    const ClassDev &c = gcls[cls[e]];
     double D[21], M[6];
-#pragma unroll
-    for (int k = 0; k < 21; k++) D[k] = elstiff[(size_t)k * nel + e];
-    tangent_to_M(D, gcls[cls[e]].kappa, M);
+    tan_load(ts, nel, e, gmat[c.mat].CV, D);
+    tangent_to_M(D, c.kappa, M);
 #pragma unroll
     for (int k = 0; k < 6; k++) Mel[(size_t)k * mel_stride + e] = M[k];
+}
+
+// the stored tangents as 21 entries each, out[k*nel + e] (plfx_state_get); to_full != 0: also rewrite the store itself in
+// full form (before plfx_set_materials replaces the CV that the other two forms refer to)
+__global__ void __launch_bounds__(BLOCK)
+k_tangent_expand(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_t *cls, TanStore ts, double *out, int to_full)
+{
+    const int e = blockIdx.x * BLOCK + threadIdx.x;
+    if (e >= nel) return;
+    double D[21];
+    tan_load(ts, nel, e, gmat[gcls[cls[e]].mat].CV, D);
+#pragma unroll
+    for (int k = 0; k < 21; k++) out[(size_t)k * nel + e] = D[k];
+    if (to_full) ts.tag[e] = TAN_FULL;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2451,7 +2525,7 @@ template <int SUMS>
 __global__ void __launch_bounds__(BLOCK)
 k_update_state(const MatDev *__restrict__ gmat, const ClassDev *__restrict__ gcls, int nel, int e_off, const int32_t *__restrict__ conn,
                const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
-               double *__restrict__ eps, const double *__restrict__ elstiff, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
+               double *__restrict__ eps, TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
                int nonlin, double *__restrict__ part /* SUMS: [18][gridDim.x] volume-weighted sums of the new sig, eps, epl */,
                int sum_lo = 0, int sum_hi = 0x7fffffff /* elements that enter the sums (strip: owned columns) */)
 {
@@ -2476,8 +2550,7 @@ k_update_state(const MatDev *__restrict__ gmat, const ClassDev *__restrict__ gcl
         } else {  // el.sig += elstiff @ deps ; depl = 0 for elastic materials (model.py:1387-1388)
             double de[6], D[21], ds[6];
             class_strain(c, du2, n0, n1, n2, n3, de);
-#pragma unroll
-            for (int k = 0; k < 21; k++) D[k] = elstiff[(size_t)k * nel + e];
+            tan_load(ts, nel, e, m.CV, D);
             symv(D, de, ds);
 #pragma unroll
             for (int k = 0; k < 6; k++) {
@@ -2539,7 +2612,7 @@ __global__ void __launch_bounds__(BLOCK) k_reduce_rows(const double *part, int n
 __global__ void __launch_bounds__(BLOCK)
 k_scf_elements(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int lds_doubles, int nel,
                int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
-               const double *__restrict__ sig, const double *__restrict__ epl, const double *__restrict__ elstiff, const double *__restrict__ sld,
+               const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts, const double *__restrict__ sld,
                double *__restrict__ hh_out, int32_t *__restrict__ mult_out, const double *__restrict__ kh_el = nullptr,
                unsigned skip_mask = 0u /* materials done by k_scf_row */)
 {
@@ -2561,8 +2634,7 @@ k_scf_elements(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
         const size_t ge = (size_t)e + e_off;
         double de[6], D[21], ds[6];
         class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], de);
-#pragma unroll
-        for (int k = 0; k < 21; k++) D[k] = elstiff[(size_t)k * nel + e];
+        tan_load(ts, nel, e, smat[c.mat].CV, D);
         symv(D, de, ds);
         int mult = 0;
         double hh = 0.;
@@ -2626,7 +2698,7 @@ template <bool INLDS>
 __global__ void __launch_bounds__(512)
 k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int mat, int nel,
           int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
-          const double *__restrict__ sig, const double *__restrict__ epl, const double *__restrict__ elstiff, const double *__restrict__ sld,
+          const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts, const double *__restrict__ sld,
           double *__restrict__ hh_out, int32_t *__restrict__ mult_out)
 {
     __shared__ MatDev smat[MAXMAT];
@@ -2645,8 +2717,7 @@ k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict_
         const size_t ge = (size_t)e + e_off;
         double de[6], D[21], ds[6];
         class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], de);
-#pragma unroll
-        for (int k = 0; k < 21; k++) D[k] = elstiff[(size_t)k * nel + e];
+        tan_load(ts, nel, e, smat[c.mat].CV, D);
         symv(D, de, ds);
         int mult = 0;
         double hh = 0.;
