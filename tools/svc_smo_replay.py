@@ -4,7 +4,8 @@
 This is the debugging aid for the device solver: libsvm's non-shrinking C-SVC solver step for step (second-order working-set
 selection, the analytic two-variable update, G from both kernel rows), with kernel rows computed in FP64 and stored as FP32
 like libsvm's ``Qfloat``.  It can print the working pair (i, j) of every iteration, so the first iteration where the device
-and this replay (or libsvm) part can be found.
+and this replay (or libsvm) part can be found.  It is also the reference of tests/test_gpu_svc_smo.py (pinned to libsvm by
+tests/test_svc_replay_cpu.py), together with the FP64 checks ``kkt_gap`` and ``dual_obj``.
 
 The problem is laid out as libsvm sees it inside scikit-learn: the classes are sorted, so the rows of label -1 come first
 (internal y = +1) and the rows of label +1 follow (internal y = -1).  Results are returned in scikit-learn's convention
@@ -27,19 +28,31 @@ def libsvm_order(y):
     return perm, np.where(y[perm] < 0, 1, -1).astype(np.int8)
 
 
-def smo(X, y, C, gamma, tol=1e-3, max_iter=None, trace=0):
-    """non-shrinking libsvm SMO on (X, y in {-1, +1}); returns dict(support_, dual_coef_, intercept_, n_iter_, obj, alpha)"""
+def dot_seq(A, x):
+    """A @ x summed feature by feature in order, as libsvm's dense dot and the device do (a BLAS dot may not)"""
+    s = np.zeros(len(A))
+    for f in range(A.shape[1]):
+        s = s + A[:, f] * x[f]
+    return s
+
+
+def smo(X, y, C, gamma, tol=1e-3, max_iter=-1, trace=0):
+    """non-shrinking libsvm SMO on (X, y in {-1, +1}); returns dict(support_, dual_coef_, intercept_, n_iter_, obj, alpha,
+    perm, status).  max_iter <= 0 (or None) means libsvm's default max(10 000 000, 100 n); status is 1 when the loop ended
+    because the iteration count reached max_iter (libsvm's warning), else 0."""
     X = np.ascontiguousarray(X, dtype=float)
     perm, yi = libsvm_order(y)
     Xp = X[perm]
     n = len(Xp)
-    if max_iter is None:
+    if max_iter is None or max_iter <= 0:
         max_iter = max(10000000, 100 * n)
-    xsq = np.einsum('ij,ij->i', Xp, Xp)
+    xsq = np.zeros(n)
+    for f in range(Xp.shape[1]):
+        xsq = xsq + Xp[:, f] * Xp[:, f]
     yd = yi.astype(float)
 
     def row(i):   # Q_i as libsvm's SVC_Q::get_Q: (Qfloat)(y_i y_t K(i, t))
-        k = np.exp(-gamma * (xsq[i] + xsq - 2 * (Xp @ Xp[i])))
+        k = np.exp(-gamma * (xsq[i] + xsq - 2 * dot_seq(Xp, Xp[i])))
         return (yd[i] * yd * k).astype(np.float32)
 
     QD = np.exp(-gamma * (xsq + xsq - 2 * xsq))
@@ -110,7 +123,7 @@ def smo(X, y, C, gamma, tol=1e-3, max_iter=None, trace=0):
     rho = calc_rho(alpha, G, yi, C)
     sv = np.nonzero(alpha > 0)[0]
     return dict(support_=perm[sv], dual_coef_=-(yd[sv] * alpha[sv]), intercept_=rho, n_iter_=it,
-                obj=0.5 * float(np.sum(alpha * (G - 1.))), alpha=alpha, perm=perm)
+                obj=0.5 * float(np.sum(alpha * (G - 1.))), alpha=alpha, perm=perm, status=int(it >= max_iter))
 
 
 def calc_rho(alpha, G, yi, C):
@@ -134,6 +147,34 @@ def calc_rho(alpha, G, yi, C):
     return s / nf if nf else 0.5 * (ub + lb)
 
 
+def kernel_fp64(A, B, gamma):
+    """RBF kernel matrix K(A, B) in FP64 (squared distances from the norms, clipped at 0)"""
+    sa, sb = np.sum(A * A, axis=1), np.sum(B * B, axis=1)
+    return np.exp(-gamma * np.maximum(sa[:, None] + sb[None, :] - 2. * A @ B.T, 0.))
+
+
+def kkt_gap(X, y, alpha, C, gamma):
+    """m(a) - M(a) of a fit in FP64 (labels y in {-1, +1}, alpha in the order of X): the maximal violation of the KKT
+    conditions, which the solver drives below tol; -inf when one of the two index sets is empty"""
+    X, y, a = np.asarray(X, dtype=float), np.asarray(y, dtype=float), np.asarray(alpha, dtype=float)
+    sv = np.nonzero(a > 0)[0]
+    G = y * (kernel_fp64(X, X[sv], gamma) @ (y[sv] * a[sv])) - 1.
+    v = -y * G
+    up = ((y > 0) & (a < C)) | ((y < 0) & (a > 0))
+    low = ((y > 0) & (a > 0)) | ((y < 0) & (a < C))
+    if not np.any(up) or not np.any(low):
+        return -np.inf
+    return np.max(v[up]) - np.min(v[low])
+
+
+def dual_obj(X, y, alpha, gamma):
+    """1/2 a'Qa - e'a in FP64"""
+    X, y, a = np.asarray(X, dtype=float), np.asarray(y, dtype=float), np.asarray(alpha, dtype=float)
+    sv = np.nonzero(a > 0)[0]
+    ya = y[sv] * a[sv]
+    return 0.5 * float(ya @ (kernel_fp64(X[sv], X[sv], gamma) @ ya)) - float(np.sum(a))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('fixture')
@@ -149,8 +190,8 @@ def main():
         X = (seq[:, None, None] * sd[None, :, :]).reshape(-1, sd.shape[1]) / float(z[c + '_sy'])
         y = np.repeat(np.where(np.arange(len(seq)) < int(z[c + '_Nseq']), -1., 1.), len(sd))
     r = smo(X, y, float(z[c + '_C']), float(z[c + '_gamma']), trace=a.trace)
-    print('n_iter %d (libsvm without shrinking: %d), nSV %d (%d), intercept %.17g (%.17g)' % (
-        r['n_iter_'], int(z[c + '_ns_n_iter']), len(r['support_']), len(z[c + '_ns_support']), r['intercept_'],
+    print('n_iter %d (libsvm without shrinking: %d), status %d, nSV %d (%d), intercept %.17g (%.17g)' % (
+        r['n_iter_'], int(z[c + '_ns_n_iter']), r['status'], len(r['support_']), len(z[c + '_ns_support']), r['intercept_'],
         float(z[c + '_ns_intercept'])))
     return 0
 
