@@ -413,6 +413,13 @@ int plfx_comm_init(plfx_ctx *ctx, const char id[128], int rank, int nranks);
 int plfx_svc_fit_batch(plfx_ctx *ctx, int n, int d, const double *X, const double *y, int nprob, const int32_t *off,
                        const int32_t *idx, const double *C, const double *gamma, double tol, int64_t max_iter,
                        double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status);
+/* One fit over ALL rows of X (same problem, arithmetic and outputs as plfx_svc_fit_batch with nprob = 1 and idx = 0 .. n-1,
+ * bit for bit) spread over nwg workgroups that exchange the two selections of every SMO iteration grid-wide (k_smo_wide,
+ * DESIGN.md §14).  nwg = 0: automatic (grows with n); a problem too large for the register-resident rows of one workgroup
+ * per CU then runs on the plfx_svc_fit_batch solver.  A forced nwg must not exceed the CUs.  A grid-wide exchange that
+ * does not complete within its time bound ends the fit with PLFX_ERR_HIP. */
+int plfx_svc_fit_wide(plfx_ctx *ctx, int n, int d, const double *X, const double *y, double C, double gamma, double tol,
+                      int64_t max_iter, int nwg, double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status);
 /* Decision values of nprob RBF-SVC models on rows of the shared X: problem p has the support vectors
  * X[sv_idx[sv_off[p] .. sv_off[p+1])] with coefficients coef[...] (dual_coef_), intercept[p] and gamma[p], and is evaluated
  * on the rows q_idx[q_off[p] .. q_off[p+1]) of X: dec[k] = sum_s coef_s exp(-gamma |x_q - x_s|^2) + intercept[p], summed in

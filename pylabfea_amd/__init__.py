@@ -6,11 +6,12 @@ HIP kernels (gfx950) in ``libplfx.so`` behind the reference's own ``Model`` / ``
 See DESIGN.md for the scope table and INTEGRATION.md for the C-ABI.
 """
 from .basic import Strain, Stress, eps_eq, sig_cyl2princ, sig_dev, sig_eq_j2, sig_polar_ang, sig_princ, yf_tolerance
+from .data import Data
 from .material import Material
 from .model import Model
 from .training import load_cases, training_score
 from ._dist import host_transport
 
 __version__ = '0.1.0'
-__all__ = ['Material', 'Model', 'host_transport', 'Stress', 'Strain', 'eps_eq', 'sig_dev', 'sig_eq_j2', 'sig_polar_ang', 'sig_princ',
+__all__ = ['Data', 'Material', 'Model', 'host_transport', 'Stress', 'Strain', 'eps_eq', 'sig_dev', 'sig_eq_j2', 'sig_polar_ang', 'sig_princ',
            'yf_tolerance', 'sig_cyl2princ', 'load_cases', 'training_score']

@@ -54,7 +54,7 @@ SYMBOLS = [
     'plfx_indefinite_info', 'plfx_pattern_selftest', 'plfx_precond_bench', 'plfx_set_wh_mode', 'plfx_wh_info', 'plfx_wh_carry', 'plfx_set_mesh_structured',
     'plfx_svc_info', 'plfx_sqmr_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
-    'plfx_svc_fit_batch', 'plfx_svc_decision_batch',
+    'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide',
 ]
 
 _lib = None
@@ -327,6 +327,25 @@ class Context(object):
                                               _dp(alpha), _dp(rho), _dp(obj), _dp(it), _dp(st)))
         return [dict(alpha=alpha[off[p]:off[p + 1]], rho=float(rho[p]), obj=float(obj[p]), n_iter=int(it[p]),
                      status=int(st[p])) for p in range(npb)]
+
+    def svc_fit_wide(self, X, y, C, gamma, tol=1e-3, max_iter=-1, nwg=0):
+        """One binary RBF C-SVC fit over all rows of X spread across nwg workgroups (0: automatic): the result of
+        svc_fit_batch(X, y, [arange(n)], C, gamma) bit for bit.  Returns one dict like svc_fit_batch's entries."""
+        import ctypes   # (the argument C shadows this module's ctypes alias)
+        X = _f64(X)
+        if X.ndim != 2:
+            raise ValueError('svc_fit_wide: X must be (n, d)')
+        y = _f64(y).reshape(-1)
+        if len(y) != len(X):
+            raise ValueError('svc_fit_wide: X and y differ in length')
+        alpha = np.empty(len(y))
+        rho, obj = np.empty(1), np.empty(1)
+        it, st = np.empty(1, dtype=np.int32), np.empty(1, dtype=np.int32)
+        self._chk(self.lib.plfx_svc_fit_wide(self.h, len(X), X.shape[1], _dp(X), _dp(y), ctypes.c_double(float(C)),
+                                             ctypes.c_double(float(gamma)), ctypes.c_double(tol),
+                                             ctypes.c_int64(int(max_iter)), int(nwg), _dp(alpha), _dp(rho), _dp(obj),
+                                             _dp(it), _dp(st)))
+        return dict(alpha=alpha, rho=float(rho[0]), obj=float(obj[0]), n_iter=int(it[0]), status=int(st[0]))
 
     def svc_decision_batch(self, X, sv_lists, coefs, intercepts, gamma, query_lists):
         """Decision values of several RBF-SVC models whose support vectors and query points are rows of the shared X:

@@ -3074,6 +3074,12 @@ int plfx_svc_fit_batch(plfx_ctx *c, int n, int d, const double *X, const double 
     return svc_fit_batch_impl(c, n, d, X, y, nprob, off, idx, C, gamma, tol, max_iter, alpha, rho, obj, iters, status);
 }
 
+int plfx_svc_fit_wide(plfx_ctx *c, int n, int d, const double *X, const double *y, double C, double gamma, double tol,
+                      int64_t max_iter, int nwg, double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status)
+{
+    return svc_fit_wide_impl(c, n, d, X, y, C, gamma, tol, max_iter, nwg, alpha, rho, obj, iters, status);
+}
+
 int plfx_svc_decision_batch(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *sv_off,
                             const int32_t *sv_idx, const double *coef, const double *intercept, const double *gamma,
                             const int32_t *q_off, const int32_t *q_idx, double *dec)

@@ -58,7 +58,26 @@ __device__ inline void smo_load_x(const double *X, int d, int r, double (&x)[SMO
     for (int f = 0; f < SMO_DMAX; f++) x[f] = f < d ? X[(size_t)r * d + f] : 0.;
 }
 
-// libsvm's Kernel::kernel_rbf, then (Qfloat)(y_i y_k K)
+// libsvm's Kernel::kernel_rbf, then (Qfloat)(y_i y_k K): the entry from the dot product x_i.x_k summed feature by feature
+__device__ inline float smo_qdot(double dot, double xsq_i, double xsq_k, int yy, double g)
+{
+#pragma clang fp contract(off)
+    const double t = (xsq_i + xsq_k) - 2. * dot;
+    return (float)((double)yy * exp(-g * t));
+}
+
+// x_i.x_k with x_k in registers (k_smo_wide) or in X (k_smo), features in order
+template <int D>
+__device__ inline double smo_dot(const double (&xi)[SMO_DMAX], const double (&xk)[D], int d)
+{
+#pragma clang fp contract(off)
+    double dot = 0.;
+#pragma unroll
+    for (int f = 0; f < D; f++)
+        if (f < d) dot = dot + xi[f] * xk[f];
+    return dot;
+}
+
 __device__ inline float smo_q(const double (&xi)[SMO_DMAX], double xsq_i, int yy, const double *X, int d, int r,
                               double xsq_k, double g)
 {
@@ -67,8 +86,7 @@ __device__ inline float smo_q(const double (&xi)[SMO_DMAX], double xsq_i, int yy
 #pragma unroll
     for (int f = 0; f < SMO_DMAX; f++)
         if (f < d) dot = dot + xi[f] * X[(size_t)r * d + f];
-    const double t = (xsq_i + xsq_k) - 2. * dot;
-    return (float)((double)yy * exp(-g * t));
+    return smo_qdot(dot, xsq_i, xsq_k, yy, g);
 }
 
 __global__ void __launch_bounds__(256) k_smo_init(SmoArgs a)
@@ -89,6 +107,130 @@ __global__ void __launch_bounds__(256) k_smo_init(SmoArgs a)
     if (threadIdx.x == 0) a.st[2 * p] = a.st[2 * p + 1] = 0;
 }
 
+// ---- the in-workgroup parts of an SMO iteration, shared by k_smo and k_smo_wide (same arithmetic, same order)
+
+// candidate for i from one row: max over I_up of -y G, ties to the last index (libsvm: `>=`)
+__device__ inline void smo_cand_i(int yk, double ak, double gk, double C, int k, double &av, int &ai, double &aa)
+{
+    if (yk > 0) {
+        if (!(ak >= C) && -gk >= av) av = -gk, ai = k, aa = ak;
+    } else if (!(ak <= 0.) && gk >= av) av = gk, ai = k, aa = ak;
+}
+
+// candidate for j from one row (min of the second-order objective decrease, ties to the last index) and Gmax2
+__device__ inline void smo_cand_j(int yk, double ak, double gk, double qdk, float q, int k, double C, double Gmax, int y_i,
+                                  double qd_i, double &bv, int &bj, double &ba, double &bg, double &bq, double &g2)
+{
+#pragma clang fp contract(off)
+    if (yk > 0) {
+        if (!(ak <= 0.)) {
+            const double gd = Gmax + gk;
+            if (gk >= g2) g2 = gk;
+            if (gd > 0.) {
+                const double quad = (qd_i + qdk) - (2.0 * y_i) * (double)q;
+                const double od = quad > 0. ? -(gd * gd) / quad : -(gd * gd) / SMO_TAU;
+                if (od <= bv) bv = od, bj = k, ba = ak, bg = gk, bq = q;
+            }
+        }
+    } else if (!(ak >= C)) {
+        const double gd = Gmax - gk;
+        if (-gk >= g2) g2 = -gk;
+        if (gd > 0.) {
+            const double quad = (qd_i + qdk) + (2.0 * y_i) * (double)q;
+            const double od = quad > 0. ? -(gd * gd) / quad : -(gd * gd) / SMO_TAU;
+            if (od <= bv) bv = od, bj = k, ba = ak, bg = gk, bq = q;
+        }
+    }
+}
+
+// wave64 reductions; the result is exact and independent of the order of the rows (max / min with last-index ties)
+__device__ inline void smo_wave_max(double &v, int &ix)
+{
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double v2 = __shfl_xor(v, m, 64);
+        const int i2 = __shfl_xor(ix, m, 64);
+        if (v2 > v || (v2 == v && i2 > ix)) v = v2, ix = i2;
+    }
+}
+__device__ inline void smo_wave_min(double &v, int &ix, double &m2)
+{
+    for (int m = 32; m >= 1; m >>= 1) {
+        const double v2 = __shfl_xor(v, m, 64);
+        const int i2 = __shfl_xor(ix, m, 64);
+        m2 = fmax(m2, __shfl_xor(m2, m, 64));
+        if (v2 < v || (v2 == v && i2 > ix)) v = v2, ix = i2;
+    }
+}
+
+// merge of per-wave (or per-workgroup) winners, slots in index order
+template <int NS>
+__device__ inline void smo_merge_a(const SmoSlotA *s, int ns, double &Gmax, int &i, double &alpha_i)
+{
+    for (int w = 0; w < (NS > 0 ? NS : ns); w++) {
+        const SmoSlotA t = s[w];
+        if (t.v > Gmax || (t.v == Gmax && t.idx > i)) Gmax = t.v, i = t.idx, alpha_i = t.a;
+    }
+}
+template <int NS>
+__device__ inline void smo_merge_b(const SmoSlotB *s, int ns, double &omin, int &j, double &alpha_j, double &G_j,
+                                   double &Q_ij, double &Gmax2)
+{
+    for (int w = 0; w < (NS > 0 ? NS : ns); w++) {
+        const SmoSlotB t = s[w];
+        Gmax2 = fmax(Gmax2, t.g2);
+        if (t.v < omin || (t.v == omin && t.idx > j)) omin = t.v, j = t.idx, alpha_j = t.a, G_j = t.g, Q_ij = t.q;
+    }
+}
+
+// the two-variable update of Solver::Solve, computed alike by every thread
+__device__ inline void smo_pair(int y_i, int y_j, double qd_i, double qd_j, double Q_ij, double G_i, double G_j,
+                                double alpha_i, double alpha_j, double C, double &ni, double &nj)
+{
+#pragma clang fp contract(off)
+    if (y_i != y_j) {
+        double quad = (qd_i + qd_j) + 2. * Q_ij;
+        if (quad <= 0.) quad = SMO_TAU;
+        const double delta = (-G_i - G_j) / quad;
+        const double diff = alpha_i - alpha_j;
+        ni = alpha_i + delta;
+        nj = alpha_j + delta;
+        if (diff > 0.) {
+            if (nj < 0.) nj = 0., ni = diff;
+        } else if (ni < 0.) {
+            ni = 0., nj = -diff;
+        }
+        if (diff > 0.) {   // C_i - C_j = 0
+            if (ni > C) ni = C, nj = C - diff;
+        } else if (nj > C) {
+            nj = C, ni = C + diff;
+        }
+    } else {
+        double quad = (qd_i + qd_j) - 2. * Q_ij;
+        if (quad <= 0.) quad = SMO_TAU;
+        const double delta = (G_i - G_j) / quad;
+        const double sum = alpha_i + alpha_j;
+        ni = alpha_i - delta;
+        nj = alpha_j + delta;
+        if (sum > C) {
+            if (ni > C) ni = C, nj = sum - C;
+        } else if (nj < 0.) {
+            nj = 0., ni = sum;
+        }
+        if (sum > C) {
+            if (nj > C) nj = C, ni = sum - C;
+        } else if (ni < 0.) {
+            ni = 0., nj = sum;
+        }
+    }
+}
+
+// new G of one row from the two kernel rows
+__device__ inline double smo_g_update(double gk, float qi, float qj, double dai, double daj)
+{
+#pragma clang fp contract(off)
+    return gk + ((double)qi * dai + (double)qj * daj);
+}
+
 __global__ void __launch_bounds__(SMO_BLOCK) k_smo(SmoArgs a, const int32_t *active, int chunk)
 {
 #pragma clang fp contract(off)
@@ -107,15 +249,9 @@ __global__ void __launch_bounds__(SMO_BLOCK) k_smo(SmoArgs a, const int32_t *act
     const int8_t *yv = a.yi + o;
     const double INF = __builtin_huge_val();
 
-    // candidate for i: max over I_up of -y G, ties to the last index (libsvm: `>=`)
     double av = -INF, aa = 0.;
     int ai = -1;
-    for (int k = tid; k < n; k += SMO_BLOCK) {
-        const double ak = al[k], gk = G[k];
-        if (yv[k] > 0) {
-            if (!(ak >= C) && -gk >= av) av = -gk, ai = k, aa = ak;
-        } else if (!(ak <= 0.) && gk >= av) av = gk, ai = k, aa = ak;
-    }
+    for (int k = tid; k < n; k += SMO_BLOCK) smo_cand_i(yv[k], al[k], G[k], C, k, av, ai, aa);
     int iter = a.st[2 * p], state = 0;
     for (int step = 0;; step++) {
         if (iter >= maxit) {
@@ -127,20 +263,13 @@ __global__ void __launch_bounds__(SMO_BLOCK) k_smo(SmoArgs a, const int32_t *act
         {
             double v = av;
             int ix = ai;
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double v2 = __shfl_xor(v, m, 64);
-                const int i2 = __shfl_xor(ix, m, 64);
-                if (v2 > v || (v2 == v && i2 > ix)) v = v2, ix = i2;
-            }
+            smo_wave_max(v, ix);
             if ((ix >= 0 && ai == ix) || (ix < 0 && lane == 0)) sa[wave] = SmoSlotA{v, aa, ix};
         }
         __syncthreads();
         double Gmax = -INF, alpha_i = 0.;
         int i = -1;
-        for (int w = 0; w < SMO_WAVES; w++) {
-            const SmoSlotA s = sa[w];
-            if (s.v > Gmax || (s.v == Gmax && s.idx > i)) Gmax = s.v, i = s.idx, alpha_i = s.a;
-        }
+        smo_merge_a<SMO_WAVES>(sa, SMO_WAVES, Gmax, i, alpha_i);
         if (i < 0) {   // Gmax = -INF: libsvm finds no j either
             state = 1;
             break;
@@ -151,53 +280,25 @@ __global__ void __launch_bounds__(SMO_BLOCK) k_smo(SmoArgs a, const int32_t *act
         double xi[SMO_DMAX];
         smo_load_x(a.X, d, row[i], xi);
 
-        // ---- row i, candidate for j (min of the second-order objective decrease, ties to the last index), and Gmax2
+        // ---- row i, candidate for j and Gmax2
         double bv = INF, ba = 0., bg = 0., bq = 0., g2 = -INF;
         int bj = -1;
         for (int k = tid; k < n; k += SMO_BLOCK) {
             const int yk = yv[k];
             const float q = smo_q(xi, xsq_i, y_i * yk, a.X, d, row[k], xsq[k], g);
             qr[k] = q;
-            const double ak = al[k], gk = G[k];
-            if (yk > 0) {
-                if (!(ak <= 0.)) {
-                    const double gd = Gmax + gk;
-                    if (gk >= g2) g2 = gk;
-                    if (gd > 0.) {
-                        const double quad = (qd_i + qd[k]) - (2.0 * y_i) * (double)q;
-                        const double od = quad > 0. ? -(gd * gd) / quad : -(gd * gd) / SMO_TAU;
-                        if (od <= bv) bv = od, bj = k, ba = ak, bg = gk, bq = q;
-                    }
-                }
-            } else if (!(ak >= C)) {
-                const double gd = Gmax - gk;
-                if (-gk >= g2) g2 = -gk;
-                if (gd > 0.) {
-                    const double quad = (qd_i + qd[k]) + (2.0 * y_i) * (double)q;
-                    const double od = quad > 0. ? -(gd * gd) / quad : -(gd * gd) / SMO_TAU;
-                    if (od <= bv) bv = od, bj = k, ba = ak, bg = gk, bq = q;
-                }
-            }
+            smo_cand_j(yk, al[k], G[k], qd[k], q, k, C, Gmax, y_i, qd_i, bv, bj, ba, bg, bq, g2);
         }
         {
             double v = bv, m2 = g2;
             int ix = bj;
-            for (int m = 32; m >= 1; m >>= 1) {
-                const double v2 = __shfl_xor(v, m, 64);
-                const int i2 = __shfl_xor(ix, m, 64);
-                m2 = fmax(m2, __shfl_xor(m2, m, 64));
-                if (v2 < v || (v2 == v && i2 > ix)) v = v2, ix = i2;
-            }
+            smo_wave_min(v, ix, m2);
             if ((ix >= 0 && bj == ix) || (ix < 0 && lane == 0)) sb[wave] = SmoSlotB{v, ba, bg, bq, m2, ix};
         }
         __syncthreads();
         double omin = INF, alpha_j = 0., G_j = 0., Q_ij = 0., Gmax2 = -INF;
         int j = -1;
-        for (int w = 0; w < SMO_WAVES; w++) {
-            const SmoSlotB s = sb[w];
-            Gmax2 = fmax(Gmax2, s.g2);
-            if (s.v < omin || (s.v == omin && s.idx > j)) omin = s.v, j = s.idx, alpha_j = s.a, G_j = s.g, Q_ij = s.q;
-        }
+        smo_merge_b<SMO_WAVES>(sb, SMO_WAVES, omin, j, alpha_j, G_j, Q_ij, Gmax2);
         if (Gmax + Gmax2 < tol || j < 0) {
             state = 1;
             break;
@@ -209,41 +310,7 @@ __global__ void __launch_bounds__(SMO_BLOCK) k_smo(SmoArgs a, const int32_t *act
         const int y_j = yv[j];
         const double qd_j = qd[j];
         double ni, nj;
-        if (y_i != y_j) {
-            double quad = (qd_i + qd_j) + 2. * Q_ij;
-            if (quad <= 0.) quad = SMO_TAU;
-            const double delta = (-G_i - G_j) / quad;
-            const double diff = alpha_i - alpha_j;
-            ni = alpha_i + delta;
-            nj = alpha_j + delta;
-            if (diff > 0.) {
-                if (nj < 0.) nj = 0., ni = diff;
-            } else if (ni < 0.) {
-                ni = 0., nj = -diff;
-            }
-            if (diff > 0.) {   // C_i - C_j = 0
-                if (ni > C) ni = C, nj = C - diff;
-            } else if (nj > C) {
-                nj = C, ni = C + diff;
-            }
-        } else {
-            double quad = (qd_i + qd_j) - 2. * Q_ij;
-            if (quad <= 0.) quad = SMO_TAU;
-            const double delta = (G_i - G_j) / quad;
-            const double sum = alpha_i + alpha_j;
-            ni = alpha_i - delta;
-            nj = alpha_j + delta;
-            if (sum > C) {
-                if (ni > C) ni = C, nj = sum - C;
-            } else if (nj < 0.) {
-                nj = 0., ni = sum;
-            }
-            if (sum > C) {
-                if (nj > C) nj = C, ni = sum - C;
-            } else if (ni < 0.) {
-                ni = 0., nj = sum;
-            }
-        }
+        smo_pair(y_i, y_j, qd_i, qd_j, Q_ij, G_i, G_j, alpha_i, alpha_j, C, ni, nj);
         const double dai = ni - alpha_i, daj = nj - alpha_j, xsq_j = xsq[j];
         double xj[SMO_DMAX];
         smo_load_x(a.X, d, row[j], xj);
@@ -252,19 +319,284 @@ __global__ void __launch_bounds__(SMO_BLOCK) k_smo(SmoArgs a, const int32_t *act
         for (int k = tid; k < n; k += SMO_BLOCK) {
             const int yk = yv[k];
             const float qj = smo_q(xj, xsq_j, y_j * yk, a.X, d, row[k], xsq[k], g);
-            const double gk = G[k] + ((double)qr[k] * dai + (double)qj * daj);
+            const double gk = smo_g_update(G[k], qr[k], qj, dai, daj);
             G[k] = gk;
             double ak = al[k];
             if (k == i) al[k] = ak = ni;
             if (k == j) al[k] = ak = nj;
-            if (yk > 0) {
-                if (!(ak >= C) && -gk >= av) av = -gk, ai = k, aa = ak;
-            } else if (!(ak <= 0.) && gk >= av) av = gk, ai = k, aa = ak;
+            smo_cand_i(yk, ak, gk, C, k, av, ai, aa);
         }
     }
     if (tid == 0) {
         a.st[2 * p] = iter;
         a.st[2 * p + 1] = state;
+    }
+}
+
+// ---- k_smo_wide: ONE problem over nwg workgroups (plfx_svc_fit_wide).  The same iteration sequence as k_smo bit for bit:
+// the only values that cross threads are the arg-max for i, the arg-min for j (with their last-index ties and the
+// winner's own a, G, Q_ij) and the max Gmax2; all three are exact and do not depend on how rows are partitioned, and the
+// two-variable update is the same scalar arithmetic in every thread.  Rows go to threads in contiguous slices of R
+// (thread t of the grid owns rows t R .. t R + R - 1); each thread keeps its rows' features, a, G, |x|^2, Q_ii, label and
+// FP32 row-i entry in registers for the whole launch and writes a and G back at its end (resume, host rho).
+//
+// Exchange: two grid-wide all-gathers per iteration (select i; select j).  Each workgroup reduces its rows (wave
+// shuffles + LDS, as k_smo), then ONE lane publishes the workgroup's record: the payload as 8-byte agent-scope atomic
+// stores (sc1, write-through), s_waitcnt vmcnt(0), then the tag granule (epoch << 32 | index) -- cdna_hip_programming.md
+// Guideline 16, recipe R1 with the flag folded into the record.  Wave 0 of every workgroup then sweeps the tags of all
+// nwg records with relaxed agent-scope loads until every one carries this epoch, reads the payloads with the same sc1
+// loads (no other load of the kernel reads bytes another workgroup writes in the launch, so the acquire is the wavefront
+// fence of the Guideline's sc1 form), and reduces the records in slot order.  epoch = 2 (step + 1) - 1 for i and
+// 2 (step + 1) for j, counted within the launch; the record block is zeroed by a memset before every launch.  One
+// record per phase suffices: a workgroup overwrites its i record of step s + 1 only after it has seen every j record of
+// step s, which every workgroup publishes after it has read all i records of step s (likewise for j).
+// Every spin is bounded (SMOW_SPIN_TICKS of the 100 MHz s_memrealtime clock); on timeout, or when another workgroup has
+// set the error word, all workgroups leave and the host reports PLFX_ERR_HIP.  The grid is at most one workgroup per CU
+// and is launched with hipLaunchCooperativeKernel, which rejects a grid that cannot be co-resident.
+constexpr int SMOW_BLOCK = 256;
+constexpr int SMOW_WAVES = SMOW_BLOCK / 64;
+constexpr int SMOW_CHUNK = 8192;   // iterations per launch
+constexpr int SMOW_RMAX = 8;       // rows per thread; above this the problem goes to k_smo
+constexpr uint64_t SMOW_SPIN_TICKS = 200000000ull;   // 2 s
+constexpr int SMOW_A = 4, SMOW_B = 8;                // 8-byte words of the i and j records
+
+typedef __attribute__((address_space(1))) unsigned long long smow_gu64;
+
+struct SmoWideArgs {
+    const double *X;
+    int d, n, nwg;
+    const int32_t *row;     // [n] row of X in libsvm's order
+    const int8_t *yi;       // [n] internal labels
+    const double *qd, *xsq; // [n]
+    double *alpha, *G;      // [n]
+    int32_t *st;            // [2] iterations, state
+    unsigned long long *xch;   // [nwg * (SMOW_A + SMOW_B) + 2]: records, then the error word
+    double C, g, tol;
+    int maxit, chunk;
+};
+
+__device__ inline void smow_st(unsigned long long *p, unsigned long long v)
+{
+    __hip_atomic_store((smow_gu64 *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline unsigned long long smow_ld(const unsigned long long *p)
+{
+    return __hip_atomic_load((smow_gu64 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline unsigned long long smow_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
+__device__ inline double smow_dbl(unsigned long long v) { return __longlong_as_double((long long)v); }
+
+// publish one record (the calling lane only): payload words, drain, then the tag word
+__device__ inline void smow_publish(unsigned long long *rec, const double *w, int nw, int idx, unsigned epoch)
+{
+    for (int k = 0; k < nw; k++) smow_st(rec + k, smow_bits(w[k]));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    smow_st(rec + nw, ((unsigned long long)epoch << 32) | (unsigned)idx);
+}
+
+// wave 0: wait until the tag word (offset tagw) of every record carries epoch; false on timeout or a foreign error
+__device__ inline bool smow_wait(const SmoWideArgs &a, const unsigned long long *base, int stride, int tagw, unsigned epoch,
+                                 int lane)
+{
+    unsigned long long *err = a.xch + (size_t)a.nwg * (SMOW_A + SMOW_B);
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    for (;;) {
+        bool ok = true;
+        for (int w = lane; w < a.nwg; w += 64) ok &= (unsigned)(smow_ld(base + (size_t)w * stride + tagw) >> 32) == epoch;
+        if (__all(ok)) break;
+        if (smow_ld(err) != 0) return false;
+        if (__builtin_amdgcn_s_memrealtime() - t0 > SMOW_SPIN_TICKS) {
+            if (lane == 0) smow_st(err, 1);
+            return false;
+        }
+        __builtin_amdgcn_s_sleep(2);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // every load of the records below is an sc1 load
+    return true;
+}
+
+template <int R, int D>
+__global__ void __launch_bounds__(SMOW_BLOCK, 1) k_smo_wide(SmoWideArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ SmoSlotA sa[SMOW_WAVES];
+    __shared__ SmoSlotB sb[SMOW_WAVES];
+    __shared__ int bad;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wg = blockIdx.x;
+    const int k0 = (wg * SMOW_BLOCK + tid) * R;
+    const double C = a.C, g = a.g, tol = a.tol;
+    const int d = a.d, n = a.n;
+    const double INF = __builtin_huge_val();
+    unsigned long long *recA = a.xch, *recB = a.xch + (size_t)a.nwg * SMOW_A;
+
+    double x[R][D], al[R], G[R], xsq[R], qd[R];
+    float qr[R];
+    int yv[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const int k = k0 + r;
+        const bool own = k < n;
+        const int rr = own ? a.row[k] : 0;
+#pragma unroll
+        for (int f = 0; f < D; f++) x[r][f] = own && f < d ? a.X[(size_t)rr * d + f] : 0.;
+        al[r] = own ? a.alpha[k] : 0.;
+        G[r] = own ? a.G[k] : 0.;
+        xsq[r] = own ? a.xsq[k] : 0.;
+        qd[r] = own ? a.qd[k] : 0.;
+        yv[r] = own ? a.yi[k] : 0;   // label 0: a row that is not there is never a candidate
+        qr[r] = 0.f;
+    }
+    if (tid == 0) bad = 0;
+
+    double av = -INF, aa = 0.;
+    int ai = -1;
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if (yv[r] != 0) smo_cand_i(yv[r], al[r], G[r], C, k0 + r, av, ai, aa);
+    int iter = a.st[0], state = 0;
+    const int maxit = a.maxit;
+    bool fault = false;
+    for (int step = 0;; step++) {
+        if (iter >= maxit) {
+            state = 2;
+            break;
+        }
+        if (step == a.chunk) break;
+        const unsigned epA = 2u * (unsigned)step + 1u, epB = epA + 1u;
+        // ---- selection of i: workgroup, then grid
+        {
+            double v = av;
+            int ix = ai;
+            smo_wave_max(v, ix);
+            if ((ix >= 0 && ai == ix) || (ix < 0 && lane == 0)) sa[wave] = SmoSlotA{v, aa, ix};
+        }
+        __syncthreads();
+        if (wave == 0) {
+            if (lane == 0) {
+                double Gm = -INF, ali = 0.;
+                int ii = -1;
+                smo_merge_a<SMOW_WAVES>(sa, SMOW_WAVES, Gm, ii, ali);
+                const double w[2] = {Gm, ali};
+                smow_publish(recA + (size_t)wg * SMOW_A, w, 2, ii, epA);
+            }
+            if (smow_wait(a, recA, SMOW_A, 2, epA, lane)) {
+                // every lane takes the records w = lane, lane + 64, ... (merge order is immaterial: the result is exact)
+                double v = -INF, al2 = 0.;
+                int ix = -1;
+                for (int w = lane; w < a.nwg; w += 64) {
+                    const unsigned long long *r = recA + (size_t)w * SMOW_A;
+                    const SmoSlotA t{smow_dbl(smow_ld(r)), smow_dbl(smow_ld(r + 1)), (int)(unsigned)smow_ld(r + 2)};
+                    smo_merge_a<1>(&t, 1, v, ix, al2);
+                }
+                double vv = v;
+                int iw = ix;
+                smo_wave_max(vv, iw);
+                if ((iw >= 0 && ix == iw) || (iw < 0 && lane == 0)) sa[0] = SmoSlotA{vv, al2, iw};
+            } else if (lane == 0) {
+                bad = 1;
+            }
+        }
+        __syncthreads();
+        if (bad) {
+            fault = true;
+            break;
+        }
+        const double Gmax = sa[0].v, alpha_i = sa[0].a;
+        int i = sa[0].idx;
+        if (i < 0) {
+            state = 1;
+            break;
+        }
+        i = __builtin_amdgcn_readfirstlane(i);
+        const int y_i = a.yi[i];
+        const double G_i = y_i > 0 ? -Gmax : Gmax, qd_i = a.qd[i], xsq_i = a.xsq[i];
+        double xi[SMO_DMAX];
+        smo_load_x(a.X, d, a.row[i], xi);
+
+        // ---- row i, candidate for j and Gmax2
+        double bv = INF, ba = 0., bg = 0., bq = 0., g2 = -INF;
+        int bj = -1;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (yv[r] == 0) continue;
+            const float q = smo_qdot(smo_dot<D>(xi, x[r], d), xsq_i, xsq[r], y_i * yv[r], g);
+            qr[r] = q;
+            smo_cand_j(yv[r], al[r], G[r], qd[r], q, k0 + r, C, Gmax, y_i, qd_i, bv, bj, ba, bg, bq, g2);
+        }
+        {
+            double v = bv, m2 = g2;
+            int ix = bj;
+            smo_wave_min(v, ix, m2);
+            if ((ix >= 0 && bj == ix) || (ix < 0 && lane == 0)) sb[wave] = SmoSlotB{v, ba, bg, bq, m2, ix};
+        }
+        __syncthreads();
+        if (wave == 0) {
+            if (lane == 0) {
+                double om = INF, alj = 0., gj = 0., qij = 0., gm2 = -INF;
+                int jj = -1;
+                smo_merge_b<SMOW_WAVES>(sb, SMOW_WAVES, om, jj, alj, gj, qij, gm2);
+                const double w[5] = {om, alj, gj, qij, gm2};
+                smow_publish(recB + (size_t)wg * SMOW_B, w, 5, jj, epB);
+            }
+            if (smow_wait(a, recB, SMOW_B, 5, epB, lane)) {
+                double v = INF, alj = 0., gj = 0., qij = 0., gm2 = -INF;
+                int ix = -1;
+                for (int w = lane; w < a.nwg; w += 64) {
+                    const unsigned long long *r = recB + (size_t)w * SMOW_B;
+                    const SmoSlotB t{smow_dbl(smow_ld(r)),     smow_dbl(smow_ld(r + 1)), smow_dbl(smow_ld(r + 2)),
+                                     smow_dbl(smow_ld(r + 3)), smow_dbl(smow_ld(r + 4)), (int)(unsigned)smow_ld(r + 5)};
+                    smo_merge_b<1>(&t, 1, v, ix, alj, gj, qij, gm2);
+                }
+                double vv = v, mm = gm2;
+                int iw = ix;
+                smo_wave_min(vv, iw, mm);
+                if ((iw >= 0 && ix == iw) || (iw < 0 && lane == 0)) sb[0] = SmoSlotB{vv, alj, gj, qij, mm, iw};
+            } else if (lane == 0) {
+                bad = 1;
+            }
+        }
+        __syncthreads();
+        if (bad) {
+            fault = true;
+            break;
+        }
+        const double alpha_j = sb[0].a, G_j = sb[0].g, Q_ij = sb[0].q, Gmax2 = sb[0].g2;
+        int j = sb[0].idx;
+        if (Gmax + Gmax2 < tol || j < 0) {
+            state = 1;
+            break;
+        }
+        ++iter;
+        j = __builtin_amdgcn_readfirstlane(j);
+
+        // ---- the two-variable update, G from both rows, the new a, the candidate for the next i
+        const int y_j = a.yi[j];
+        const double qd_j = a.qd[j];
+        double ni, nj;
+        smo_pair(y_i, y_j, qd_i, qd_j, Q_ij, G_i, G_j, alpha_i, alpha_j, C, ni, nj);
+        const double dai = ni - alpha_i, daj = nj - alpha_j, xsq_j = a.xsq[j];
+        double xj[SMO_DMAX];
+        smo_load_x(a.X, d, a.row[j], xj);
+        av = -INF, ai = -1, aa = 0.;
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            if (yv[r] == 0) continue;
+            const float qj = smo_qdot(smo_dot<D>(xj, x[r], d), xsq_j, xsq[r], y_j * yv[r], g);
+            G[r] = smo_g_update(G[r], qr[r], qj, dai, daj);
+            if (k0 + r == i) al[r] = ni;
+            if (k0 + r == j) al[r] = nj;
+            smo_cand_i(yv[r], al[r], G[r], C, k0 + r, av, ai, aa);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        if (k0 + r < n) {
+            a.alpha[k0 + r] = al[r];
+            a.G[k0 + r] = G[r];
+        }
+    if (wg == 0 && tid == 0 && !fault) {
+        a.st[0] = iter;
+        a.st[1] = state;
     }
 }
 
@@ -454,6 +786,140 @@ int svc_fit_batch_impl(plfx_ctx *c, int n, int d, const double *X, const double 
         status[p] = hst[2 * p + 1] == 2 ? 1 : 0;
         for (int k = o; k < o + np; k++) alpha[hpos[k]] = hal[k];
     }
+    return PLFX_OK;
+}
+
+template <int R, int D>
+hipError_t smow_launch(int nwg, SmoWideArgs &a, hipStream_t s)
+{
+    void *args[] = {&a};
+    return hipLaunchCooperativeKernel(reinterpret_cast<const void *>(&k_smo_wide<R, D>), dim3(nwg), dim3(SMOW_BLOCK), args, 0, s);
+}
+
+template <int R, int D>
+int smow_resident(plfx_ctx *c)
+{
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, &k_smo_wide<R, D>, SMOW_BLOCK, 0) != hipSuccess) return 0;
+    return nb;
+}
+
+// one problem over all rows of X on nwg workgroups (0: automatic); falls back to k_smo (plfx_svc_fit_batch) when the rows
+// exceed SMOW_RMAX per thread of the largest grid
+int svc_fit_wide_impl(plfx_ctx *c, int n, int d, const double *X, const double *y, double C, double gamma, double tol,
+                      int64_t max_iter, int nwg, double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (n < 1 || !X || !y || !alpha || !rho || !iters || !status) return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: null or empty argument");
+    if (nwg < 0) return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: nwg = %d, must be >= 0 (0: automatic)", nwg);
+    const int32_t off[2] = {0, n};
+    std::vector<int32_t> idx(n);
+    for (int k = 0; k < n; k++) idx[k] = k;
+    const int cus = c->prop.multiProcessorCount;
+    const int D = d <= 8 ? 8 : 16;
+    int resident = 0;
+    switch (D) {   // workgroups per CU the kernel admits (1 at most is used); R does not change the register budget class
+    case 8: resident = smow_resident<SMOW_RMAX, 8>(c); break;
+    default: resident = smow_resident<SMOW_RMAX, 16>(c); break;
+    }
+    const int gmax = std::min(cus, cus * std::max(resident, 0));
+    const int64_t per_wg = (int64_t)SMOW_BLOCK * SMOW_RMAX;
+    if (gmax < 1 || (nwg == 0 && (int64_t)n > per_wg * gmax))   // too many rows for registers: the one-workgroup solver
+        return svc_fit_batch_impl(c, n, d, X, y, 1, off, idx.data(), &C, &gamma, tol, max_iter, alpha, rho, obj, iters, status);
+    SVMCHK(svm_check_rows(c, "plfx_svc_fit_wide", n, d, X, 1, off, idx.data(), &gamma));
+    if (!(C > 0.) || !std::isfinite(C)) return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: C must be > 0 (got %g)", C);
+    if (!(tol > 0.) || !std::isfinite(tol)) return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: tol must be > 0 (got %g)", tol);
+    if (nwg > gmax)
+        return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: nwg = %d exceeds the %d co-resident workgroups (one per CU)", nwg, gmax);
+    if (nwg == 0) nwg = (int)std::max<int64_t>(1, (n + per_wg - 1) / per_wg);   // grows with n: fewest workgroups
+    int R = 1;
+    while ((int64_t)R * SMOW_BLOCK * nwg < n) R *= 2;
+    if (R > SMOW_RMAX)
+        return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: %d rows need more than %d rows per thread on %d workgroups", n,
+                    SMOW_RMAX, nwg);
+    std::vector<int32_t> hrow(n), hpos(n);
+    std::vector<int8_t> hy(n);
+    int m = 0;
+    for (int pass = 0; pass < 2; pass++)   // libsvm's order: label -1 first (internal +1)
+        for (int k = 0; k < n; k++) {
+            if (y[k] != 1. && y[k] != -1.)
+                return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: label %g at row %d; binary labels -1 / +1 expected", y[k], k);
+            if ((y[k] < 0.) == (pass == 0)) hrow[m] = k, hpos[m] = k, hy[m] = pass == 0 ? 1 : -1, m++;
+        }
+    int nneg = 0;
+    for (int k = 0; k < n; k++) nneg += hy[k] > 0;
+    if (nneg == 0 || nneg == n) return fail(c, PLFX_ERR_ARG, "plfx_svc_fit_wide: the problem holds only one class");
+    const int hmax = (int)std::min<int64_t>(max_iter > 0 ? max_iter : std::max<int64_t>(10000000, 100 * (int64_t)n), INT32_MAX);
+    int coop = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device));
+    if (!coop) return fail(c, PLFX_ERR_HIP, "plfx_svc_fit_wide: the device does not support cooperative launches");
+    SvmBuffers B;
+    SmoArgs ia;
+    double *dX, *dC, *dg;
+    int32_t *doff, *drow, *dmax;
+    int8_t *dy;
+    unsigned long long *dx;
+    const size_t nxch = (size_t)nwg * (SMOW_A + SMOW_B) + 2;
+    SVMCHK(B.get(c, &dX, (size_t)n * d));
+    SVMCHK(B.get(c, &doff, 2));
+    SVMCHK(B.get(c, &drow, n));
+    SVMCHK(B.get(c, &dy, n));
+    SVMCHK(B.get(c, &dC, 1));
+    SVMCHK(B.get(c, &dg, 1));
+    SVMCHK(B.get(c, &dmax, 1));
+    SVMCHK(B.get(c, &ia.alpha, n));
+    SVMCHK(B.get(c, &ia.G, n));
+    SVMCHK(B.get(c, &ia.qd, n));
+    SVMCHK(B.get(c, &ia.xsq, n));
+    SVMCHK(B.get(c, &ia.st, 2));
+    SVMCHK(B.get(c, &dx, nxch));
+    HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)n * d * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(doff, off, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(drow, hrow.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dy, hy.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dC, &C, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dg, &gamma, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dmax, &hmax, 4, hipMemcpyHostToDevice, c->stream));
+    ia.X = dX, ia.d = d, ia.off = doff, ia.row = drow, ia.yi = dy, ia.C = dC, ia.gam = dg, ia.maxit = dmax, ia.tol = tol;
+    ia.qrow = nullptr;
+    hipLaunchKernelGGL(k_smo_init, dim3(1), dim3(256), 0, c->stream, ia);   // a = 0, G = -1, |x|^2, Q_ii, st = 0
+    HIPCHK(c, hipGetLastError());
+    SmoWideArgs a;
+    a.X = dX, a.d = d, a.n = n, a.nwg = nwg, a.row = drow, a.yi = dy, a.qd = ia.qd, a.xsq = ia.xsq, a.alpha = ia.alpha;
+    a.G = ia.G, a.st = ia.st, a.xch = dx, a.C = C, a.g = gamma, a.tol = tol, a.maxit = hmax, a.chunk = SMOW_CHUNK;
+    int32_t hst[2] = {0, 0};
+    unsigned long long herr = 0;
+    for (;;) {
+        HIPCHK(c, hipMemsetAsync(dx, 0, nxch * 8, c->stream));   // records and the error word, before every launch
+        hipError_t e = hipSuccess;
+#define SMOW_CASE(RR, DD) \
+    if (R == RR && D == DD) e = smow_launch<RR, DD>(nwg, a, c->stream);
+        SMOW_CASE(1, 8) SMOW_CASE(2, 8) SMOW_CASE(4, 8) SMOW_CASE(8, 8)
+        SMOW_CASE(1, 16) SMOW_CASE(2, 16) SMOW_CASE(4, 16) SMOW_CASE(8, 16)
+#undef SMOW_CASE
+        HIPCHK(c, e);
+        HIPCHK(c, hipMemcpyAsync(hst, ia.st, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&herr, dx + nxch - 2, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (herr)
+            return fail(c, PLFX_ERR_HIP, "plfx_svc_fit_wide: a grid-wide exchange timed out after %.1f s on %d workgroups "
+                                         "(iteration %d); the fit was abandoned", SMOW_SPIN_TICKS * 1e-8, nwg, hst[0]);
+        if (hst[1] != 0) break;
+    }
+    std::vector<double> hal(n), hG(n);
+    HIPCHK(c, hipMemcpyAsync(hal.data(), ia.alpha, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hG.data(), ia.G, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rho[0] = -smo_rho(n, hal.data(), hG.data(), hy.data(), C);
+    if (obj) {
+        double v = 0.;
+        for (int k = 0; k < n; k++) v += hal[k] * (hG[k] - 1.);
+        obj[0] = v / 2;
+    }
+    iters[0] = hst[0];
+    status[0] = hst[1] == 2 ? 1 : 0;
+    for (int k = 0; k < n; k++) alpha[hpos[k]] = hal[k];
     return PLFX_OK;
 }
 

@@ -779,10 +779,91 @@ class Material(object):
             lo, hi = np.where(f > 0., lo, mid), np.where(f > 0., mid, hi)
         return 0.5 * (lo + hi)
 
+    # fields of Data.mat_data that the msparam branch of train_SVC reads
+    _MSPARAM_KEYS = ('Nlc', 'sdim', 'wh_data', 'sy_av', 'peeq_max')
+
+    def from_data(self, param):
+        """Define the material from one data set of ``Data`` (material.py:2596-2680): ``param`` is ``Data.mat_data``
+        (or a list holding one).  Sets msparam, Nset, whdat, epc, Ndof (6, or 15 with work-hardening data; 2 for
+        sdim = 3) and ind_wh; elastic constants from ``elast_const`` (a warning when the data has none) and
+        ``plasticity(sy=sy_av, sdim)``.  Several data sets (textures) and work-hardening data with sdim = 3 are refused."""
+        ms = list(param) if isinstance(param, (list, tuple, np.ndarray)) else [param]
+        if len(ms) != 1:
+            raise NotImplementedError('from_data: %d data sets (texture variants) are not supported; pass one '
+                                      'Data.mat_data' % len(ms))
+        md = ms[0]
+        if md.get('tx_data', False):
+            raise NotImplementedError('from_data: texture data (tx_data) is not supported')
+        if md.get('tx_descriptor') == 'VF':
+            raise NotImplementedError('from_data: texture descriptor VF is not supported')
+        sdim = md['sdim']
+        if sdim not in (3, 6):
+            raise ValueError('Value of sdim must be either 3 or 6')
+        whdat = bool(md['wh_data'])
+        if whdat and sdim == 3:
+            raise NotImplementedError('from_data: work-hardening data with sdim = 3 (8 features) is not supported; '
+                                      'no kernel evaluates those features')
+        if self.sdim is not None and self.sdim != sdim:
+            warnings.warn('from_data: Microstructure has changed definition of sdim. New value={}'.format(sdim))
+        self.sdim = sdim
+        self.msparam = np.array(ms, ndmin=1)
+        self._msparam_from_data = self.msparam   # marker: train_SVC accepts this msparam
+        self.Nset = 1
+        self.whdat = whdat
+        self.txdat = False
+        self.tdim = None
+        self.epc = md.get('epc')
+        self.Ndof = 2 if sdim == 3 else 6
+        if whdat:
+            self.ind_wh = self.Ndof
+            self.Ndof += sdim + 3
+        if md.get('elast_const') is None:
+            print('WARNING: No data on elastic properties in data.')
+        else:
+            self.elasticity(CV=md['elast_const'])
+        self.plasticity(sy=md['sy_av'], sdim=sdim)
+        self._version += 1
+
+    def _msparam_ok(self):
+        """True when msparam is one data set that from_data installed and that holds the fields training reads"""
+        ms = getattr(self, 'msparam', None)
+        if ms is None or getattr(self, '_msparam_from_data', None) is not ms or len(ms) != 1:
+            return False
+        md = ms[0]
+        need = self._MSPARAM_KEYS + (('flow_stress', 'plastic_strain') if md.get('wh_data') else ('sig_ideal',))
+        return isinstance(md, dict) and all(k in md for k in need)
+
     def _svc_refuse(self, what):
-        if getattr(self, 'msparam', None) is not None or getattr(self, 'txdat', False) or getattr(self, 'whdat', False):
-            raise NotImplementedError('%s: training from microstructure data (msparam / Data / texture / work hardening) '
-                                      'is not supported; train from mat_ref or sdata' % what)
+        ms = getattr(self, 'msparam', None) is not None
+        if (ms and not self._msparam_ok()) or getattr(self, 'txdat', False) or (getattr(self, 'whdat', False) and not ms):
+            raise NotImplementedError('%s: training from this microstructure data (msparam / texture / work hardening) '
+                                      'is not supported; train from mat_ref or sdata, or from one data set installed '
+                                      'by from_data' % what)
+
+    def _create_data_for_ms(self, Ce, Fe, Nseq, extend, idx_ms=0):
+        """Training rows of one data set (material.py:1734-1820): row i + j Ndinp is flow stress i (``sig_ideal`` without
+        work-hardening data) scaled by the j-th factor of create_sig_data, with its plastic strain in the columns
+        ind_wh .. ind_wh + 5 and the three reversal columns zero.  Returns (Nlc, N0, xt, yt)."""
+        md = self.msparam[idx_ms]
+        Nlc = md['Nlc']
+        if self.whdat:
+            src = np.asarray(md['flow_stress'], dtype=float)
+            Nlc -= md.get('Ncyl', 0)
+        else:
+            src = np.asarray(md['sig_ideal'], dtype=float)
+        Ndinp = len(src)
+        Nsdata = 2 * Nseq + 4 if extend else 2 * Nseq
+        N0 = Nlc * Nsdata
+        sig_train, yt = self.create_sig_data(sdata=src, Nseq=Nseq, Fe=Fe, Ce=Ce, extend=extend)
+        xt = np.zeros((Ndinp * Nsdata, self.Ndof))
+        xt[:, 0:self.sdim] = sig_train
+        if self.whdat:
+            if 'normalized_accumulated_strain' in md:
+                raise NotImplementedError('train_SVC: data with strain reversals (normalized_accumulated_strain) '
+                                          'is not supported')
+            iw = self.ind_wh
+            xt[:, iw:iw + self.sdim] = np.tile(np.asarray(md['plastic_strain'], dtype=float), (Nsdata, 1))
+        return Nlc, N0, xt, yt
 
     def _svc_fit(self, X, y, C, gamma, gridsearch, cvals, gvals, dflt_c, dflt_g, metric):
         """fit the SVC on the GPU (with grid search: all candidates x 5 folds in one batched call, then the refit) and
@@ -826,14 +907,27 @@ class Material(object):
             raise NotImplementedError('setup_yf_SVM_6D: plotting is not supported')
         if self.sdim != 6:
             raise ValueError('setup_yf_SVM_6D: material must have sdim=6')
-        self.scale_seq = self.sy
-        self.Ndof, self.whdat = 6, False
-        X_train = self.create_scaled_input(np.asarray(x, dtype=float)[:, 0:6])
-        X_test = None if x_test is None else self.create_scaled_input(np.asarray(x_test, dtype=float)[:, 0:6])
+        scale_wh = None
+        if getattr(self, 'msparam', None) is None:
+            self.scale_seq = self.sy
+            self.Ndof, self.whdat = 6, False
+        else:   # scaling from the data set (material.py:1160-1172); Nset = 1
+            self.scale_seq = float(self.msparam[0]['sy_av'])
+            scale_wh = float(self.msparam[0]['peeq_max']) if self.whdat else 1.
+            self.scale_wh = scale_wh
+        x = np.asarray(x, dtype=float)
+
+        def feat(v):
+            if not self.whdat:
+                return self.create_scaled_input(v[:, 0:6])
+            iw = self.ind_wh
+            return self.create_scaled_input(v[:, 0:6], v[:, iw:iw + 6], v[:, iw + 6], v[:, iw + 7], v[:, iw + 8])
+        X_train = feat(x)
+        X_test = None if x_test is None else feat(np.asarray(x_test, dtype=float))
         train_sc, m = self._svc_fit(X_train, y_train, C, gamma, gridsearch, cvals, gvals,
                                     [1, 2, 4, 10], [0.5, 1, 1.5, 2, 2.5, 3], metric)
         self.set_svc(m.support_vectors_, m.dual_coef_[0], m.intercept_[0], m.gamma, self.scale_seq, dev_only=self.dev_only,
-                     C=m.C)
+                     C=m.C, scale_wh=scale_wh if self.whdat else None)
         return train_sc, self._svc_score(m, X_test, y_test, metric)
 
     def setup_yf_SVM_3D(self, x, y_train, x_test=None, y_test=None, C=10., gamma=1., fs=0.1, plot=False, cyl=False,
@@ -887,7 +981,9 @@ class Material(object):
             raise NotImplementedError('train_SVC: plotting is not supported')
         if reversal is not None:
             print('WARNING in "train_SVC": Parameter "reversal" is depracted and will be ignored.')
-        if sdata is None:
+        if getattr(self, 'msparam', None) is not None:   # one data set from from_data (material.py:1624-1636)
+            Nlc, N0, xt, yt = self._create_data_for_ms(Ce=Ce, Fe=Fe, Nseq=Nseq, extend=extend)
+        elif sdata is None:
             if mat_ref is None:
                 raise ValueError('create_data_sig: Neither sdata nor mat_ref are provided, cannot generate training data')
             self.elasticity(CV=mat_ref.CV)
@@ -981,9 +1077,16 @@ class SVCModel(object):
             warnings.warn('Solver terminated early (max_iter=%d).  Consider pre-processing your data with '
                           'StandardScaler or MinMaxScaler.' % n_iter)
 
+    # rows from which a single fit runs on the many-workgroup solver (plfx_svc_fit_wide) instead of one workgroup; the
+    # crossover measured with tools/svc_data_train_bench.py.  Both give the same fit bit for bit.
+    WIDE_MIN_ROWS = 4096
+
     @classmethod
     def fit(cls, ctx, X, y, C, gamma, tol=1e-3, max_iter=-1):
-        r = ctx.svc_fit_batch(X, y, [np.arange(len(y))], C, gamma, tol=tol, max_iter=max_iter)[0]
+        if len(y) >= cls.WIDE_MIN_ROWS:
+            r = ctx.svc_fit_wide(X, y, C, gamma, tol=tol, max_iter=max_iter)
+        else:
+            r = ctx.svc_fit_batch(X, y, [np.arange(len(y))], C, gamma, tol=tol, max_iter=max_iter)[0]
         return cls(ctx, X, y, C, gamma, r['alpha'], r['rho'], r['n_iter'], r['status'], r['obj'])
 
     def decision_function(self, X):
