@@ -11,8 +11,15 @@ schedule: elastic predictor solve + K-iterations of {assemble, PCG solve, materi
 update + homogenisation, everything resident in HBM.  The first PREROLL increments (elastic regime)
 are run untimed as set-up so that warm-up and timed steps lie in the plastic regime.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up (model, engine, pre-roll), the W warm-up and K timed steps, the
+--dump-outputs arrays, and the result line; its roofline objects come from the HIP events of the timed steps and the
+committed profiles.  Every leg that takes a run of its own is behind --full: the back-to-back V-cycle timing (`vcycle`), the
+config-5 leg, `roofline_2048`, `inclusion_variant`, `roofline_svc`, the PLFX_REUSE=0 window (`reuse_off`,
+`roofline_mg_smooth`) and the CPU baselines (`cpu_baseline`, `vs_cpu_baseline`); the --no-* options skip single legs of a
+--full run.
 
 N>1 (one rank per GPU over RCCL), default: STRONG scaling of the SAME workload -- the 1024 x 1024 mesh of config 3 cut into
 N cost-balanced x-strips of whole element columns (Model.strip_plan; element and node numbering are x-major in the
@@ -656,7 +663,7 @@ def main():
     ap.add_argument('--weak', action='store_true',
                     help='N>1: weak scaling (N strips of mesh x mesh elements side by side) instead of strong scaling of the same mesh')
     ap.add_argument('--config5-leg-mesh', type=int, default=2048,
-                    help='config 3: also time two load steps of BASELINE config 5 (the sweep-dominated workload: where element '
+                    help='config 3, --full: also time two load steps of BASELINE config 5 (the sweep-dominated workload: where element '
                          'strips pay) on this mesh -- 2048 = BASELINE configs[4] itself, at every N so that the driver can form the ratio -- '
                          'reported as `config5_leg` of the same JSON line; 0 = skip (also skipped with --no-svc at N = 1)')
     ap.add_argument('--cpu-mesh', type=int, default=0, help='mesh of the CPU leg (cpu_baseline.all_cores) and of the GPU run beside it; 0 = --mesh')
@@ -676,9 +683,17 @@ def main():
                          'costs about 0.1 ms per load step')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the timed solve returns after its last step as DIR/<name>.npy (see the top of this file)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every leg that takes a run of its own (the --no-* options skip single ones): '
+                         'V-cycle tight loop, config-5 leg, 2048^2 roofline, inclusion variant, SVC sample, reuse-off window, '
+                         'CPU baselines')
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit('--steps must be >= 1 and --warmup >= 0')
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the result line -- every other leg is skipped
+        args.no_cpu = args.no_svc = args.no_inclusion = args.no_2048 = args.no_reuse_off = args.no_tight_loop = True
+        args.config5_leg_mesh = 0
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -931,8 +946,8 @@ def main():
                                 'of %d (after %d untimed elastic pre-roll steps); %s'
                                 % ('%dx%d' % (fe._NX, fe._NY), ninc, pre + W, pre + W + K, ninc, pre,
                                    ('0 PCG iterations in the window: every one of its %d solves is answered by the previous identical solve or by the '
-                                    'interpolation of the last two solutions, which already satisfies the tolerance (see ms_per_step_reuse_off / '
-                                    'ms_per_step_inclusion_variant for what a computed window costs)' % len(its)) if int(np.sum(its)) == 0 else
+                                    'interpolation of the last two solutions, which already satisfies the tolerance (a --full run gives '
+                                    'ms_per_step_reuse_off / ms_per_step_inclusion_variant: what a computed window costs)' % len(its)) if int(np.sum(its)) == 0 else
                                    ('%d PCG iterations in the window' % int(np.sum(its))))) if args.config == 3 else
                                ('%s Q4 two-phase laminate [2,1,2,1,2] (BASELINE config 5): J2 (sy=150, khard=500) + SVC yield function '
                                 'trained on Barlat Yld2004-18p / Goss (%d support vectors), plane strain, uniaxial tension eps=0.003, '

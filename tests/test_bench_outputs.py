@@ -81,3 +81,20 @@ def test_bench_dump_is_what_the_solve_returns(tmp_path):
     for k in NAMES:
         assert got[k].dtype == np.float64 and got[k].shape == want[k].shape, k
         assert np.max(np.abs(got[k] - want[k])) <= 1e-12 * max(np.max(np.abs(want[k])), 1e-300), k
+
+
+@pytest.mark.gpu
+def test_plain_bench_runs_the_headline_only():
+    """bench.py without --full: the result line of the timed steps, and none of the legs that take a run of their own"""
+    K, W, n = 2, 1, 128
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(K), '--warmup', str(W),
+                        '--mesh', str(n)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d['steps'] == K and d['warmup'] == W and d['ms_per_step'] > 0. and d['value'] > 0. and d['sweeps'] > 0
+    assert d['unit'] == 'element-updates/s' and d['higher_is_better'] is True and d['dtype'] == 'f64'
+    assert d['config']['elements'] == n * n
+    for k in ('config5_leg', 'roofline_2048', 'inclusion_variant', 'roofline_svc', 'reuse_off', 'roofline_mg_smooth', 'vs_cpu_baseline'):
+        assert k not in d, k
+    assert d['cpu_baseline'] is None and d['ms_per_step_reuse_off'] is None and d['ms_per_step_inclusion_variant'] is None
+    assert 'plfx_precond_bench' not in d.get('vcycle', {}).get('note', '')     # no V-cycle tight loop either

@@ -309,8 +309,8 @@ def test_bench_one_rank_with_rccl_collectives_forced():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ['--steps', '3', '--warmup', '1', '--mesh', '256', '--no-cpu', '--svc-mesh', '16', '--no-inclusion', '--no-2048', '--no-reuse-off',
-              '--config5-leg-mesh', '128']
+    common = ['--full', '--steps', '3', '--warmup', '1', '--mesh', '256', '--no-cpu', '--svc-mesh', '16', '--no-inclusion', '--no-2048',
+              '--no-reuse-off', '--config5-leg-mesh', '128']
     env = dict(os.environ, PLFX_FORCE_DIST='1', PLFX_STRIP_FORCE_COLL='1', RANK='0', WORLD_SIZE='1', LOCAL_RANK='0',
                MASTER_ADDR='127.0.0.1', MASTER_PORT=str(free_port()), PLFX_COLL_TIMEOUT='120')
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1'] + common, env=env, capture_output=True,
@@ -351,7 +351,7 @@ def test_bench_two_ranks(tmp_path, mode):
     mode = 'strong' if mode == 'strong4' else mode
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(nr), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(nr), '--steps', '3', '--warmup', '1',
-           '--mesh', str(mesh), '--config5-leg-mesh', '256' if nr == 2 else '0'] + (['--weak'] if mode == 'weak' else [])
+           '--mesh', str(mesh), '--full', '--config5-leg-mesh', '256' if nr == 2 else '0'] + (['--weak'] if mode == 'weak' else [])
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('{')][-1]
