@@ -240,7 +240,7 @@ int plfx_sweep_info(plfx_ctx *ctx, int64_t *sweeps, int64_t *tangents_rewritten)
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read
  * from device memory otherwise -- no limit on the number of 6-feature SVC materials or of their support vectors;
  * bit k of *thread_materials = material k runs one thread per element / point (only when the row kernels are switched off
- * by PLFX_SVC_POLY / PLFX_SVC_WAVE).  Launch counters of the sweep kernels of either form since plfx_create. */
+ * by PLFX_SVC_WAVE).  Launch counters of the sweep kernels of either form since plfx_create. */
 int plfx_svc_info(plfx_ctx *ctx, int *row_materials, int *thread_materials, int64_t *row_launches, int64_t *thread_launches);
 /* B matrices of element e at its 4 Gauss points, [4*6*8] (Element.calc_Bmat, model.py:439) */
 int plfx_get_bmat(plfx_ctx *ctx, int e, double *B);
@@ -430,9 +430,9 @@ int plfx_svc_decision_batch(plfx_ctx *ctx, int n, int d, const double *X, int np
 
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
- * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_wave<0>), 1 spmv(+dot), 2 cg vector
+ * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
- *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_wave<1>),
+ *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time
  *          includes the wait for the slowest peer) */
 int plfx_timing_get(plfx_ctx *ctx, int which, double *ms, int64_t *launches);

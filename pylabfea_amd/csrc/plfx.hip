@@ -143,11 +143,10 @@ struct plfx_ctx {
     bool has_svcwh = false;      // SVC with work-hardening features (PLFX_SVC_WH)
     int n_noflow = 0;            // materials without a flow rule (Tresca, Barlat without the native normal)
     int svc_lds_need = 0;
-    int svc_wave_mat = -1;       // first 6-feature SVC material whose tables fit the LDS (-1: none): the one the wave-per-element kernels of rounds 1-4 run
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
     unsigned svc6_mask = 0;      // bit k: material k is a 6-feature SVC
-    int svc_wave_lds = 0;        // bytes of its SoA tables (7 x nsv padded to 64)
+    int svc_wave_lds = 0;        // dynamic LDS bytes of the row kernels with their tables in LDS (k_*_row<..., true>)
     int n_svc6 = 0;              // number of 6-feature SVC materials
     int want_svc_wave = 1;       // PLFX_SVC_WAVE
 
@@ -1297,11 +1296,7 @@ int mg_down_level(plfx_ctx *c, int l)
     (void)ev;  // the head of the cycle is enqueued speculatively (may return at once): family 5 times the post-smoothing
                // launches of k_mg_smooth<1, .> only
     const bool march = l == 0 && mf && march_mg(c);
-    // experiment (PLFX_MG_OMEGA2=w1,w2): two Chebyshev weights instead of one damping factor -- pre-smoothing w1 then w2, post-smoothing
-    // w2 then w1 (the adjoint order: the cycle stays symmetric); separate launches per sweep, for iteration counts only
-    static const char *om2s = getenv("PLFX_MG_OMEGA2");
-    static const double om2a = om2s ? atof(om2s) : 0., om2b = (om2s && strchr(om2s, ',')) ? atof(strchr(om2s, ',') + 1) : 0.;
-    if (nu == 2 && !(om2a > 0. && om2b > 0.)) {  // both sweeps in one pass over the operator
+    if (nu == 2) {  // both sweeps in one pass over the operator
         if (march)
             hipLaunchKernelGGL(k_mg_smooth2_zero_march, dim3(L.grid), dim3(BLOCK), 0, c->stream, L.op, (const double2 *)L.dinv,
                                (const double2 *)L.b, (double2 *)L.x, om, c->sc);
@@ -1316,10 +1311,10 @@ int mg_down_level(plfx_ctx *c, int l)
         for (int k = 0; k < nu; k++) {
             if (l == 0)
                 LAUNCH_OP2(k_mg_smooth, 1, mf, dim3(L.grid), L.op, (const double2 *)L.dinv, (const double2 *)L.b,
-                           (const double2 *)src, (double2 *)dst, (om2a > 0. && om2b > 0. && nu == 2) ? (k == 0 ? om2a : om2b) : om, k == 0, c->sc);
+                           (const double2 *)src, (double2 *)dst, om, k == 0, c->sc);
             else
                 LAUNCH_OP2R(k_mg_smooth, 0, mf, L.op, dim3(L.grid), L.op, (const double2 *)L.dinv, (const double2 *)L.b,
-                           (const double2 *)src, (double2 *)dst, (om2a > 0. && om2b > 0. && nu == 2) ? (k == 0 ? om2a : om2b) : om, k == 0, c->sc);
+                           (const double2 *)src, (double2 *)dst, om, k == 0, c->sc);
             src = dst;
             dst = (dst == L.x) ? L.t : L.x;
         }
@@ -1350,11 +1345,7 @@ int mg_up_level(plfx_ctx *c, int l)
     hipLaunchKernelGGL(k_mg_prolong_add, dim3(grid_for(L.nnode)), dim3(BLOCK), 0, c->stream, L.nx + 1, L.ny + 1,
                        C.ny + 1, (const double2 *)C.x, (const double2 *)L.dinv, (double2 *)L.x, L.rx, L.ry);
     double *src = L.x, *dst = L.t;
-    static const char *om2s = getenv("PLFX_MG_OMEGA2");
-    static const double om2a = om2s ? atof(om2s) : 0., om2b = (om2s && strchr(om2s, ',')) ? atof(strchr(om2s, ',') + 1) : 0.;
-    const double om_base = om;
     for (int k = 0; k < nu; k++) {
-        const double om = (om2a > 0. && om2b > 0. && nu == 2) ? (k == 0 ? om2b : om2a) : om_base;
         EvPair *ev = nullptr;
         if (l == 0) tim_begin(c, 5, &ev);  // family 5: fine-level smoother launches
         DotOut dot{};
@@ -1834,19 +1825,6 @@ int plfx_sync(plfx_ctx *c)
     return PLFX_OK;
 }
 
-// Sampled-ray form of the SVC ray search (YfSvcT::ray_sample; PLFX_SVC_POLY=0: the FP32-screened evaluations of rounds 2-4)
-// 2 (default): 16 lanes per element (k_sweep_svc_row); 1: one wave per element; 0: the FP32-screened evaluations of rounds 2-4
-static int svc_poly()
-{
-    static const int v = getenv("PLFX_SVC_POLY") ? atoi(getenv("PLFX_SVC_POLY")) : 2;
-    return v;
-}
-// materials that run on the row kernels (mode 2: every 6-feature SVC that fits the LDS) or on the wave kernels (modes 0, 1: the first)
-static unsigned svc_fast_mask(const plfx_ctx *c)
-{
-    if (svc_poly() == 2) return c->svc_row_all;
-    return c->svc_wave_mat < 0 ? 0u : (1u << c->svc_wave_mat);
-}
 // launch a row kernel for material k: tables in LDS when they fit, else read from device memory (no dynamic LDS)
 #define LAUNCH_ROW1(c, k, kern, grid, ...)                                                                                 \
     do {                                                                                                                 \
@@ -1881,12 +1859,12 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     c->has_svcwh = false;
     c->n_noflow = 0;
     c->svc_lds_need = 0;
-    c->svc_wave_mat = -1;
     c->svc_row_all = c->svc_row_lds = c->svc6_mask = 0;
     c->svc_wave_lds = 0;
     c->n_svc6 = 0;
     c->nonlin = false;
     c->hmat.resize(nmat);
+    bool wave_pad = false;
     for (int k = 0; k < nmat; k++) {
         const plfx_material &s = mats[k];
         MatDev &m = c->hmat[k];
@@ -1960,10 +1938,9 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
             if (s.kind == PLFX_SVC6) c->has_svc = true; else if (s.kind == PLFX_SVC3) c->has_svc3 = true; else c->has_svcwh = true;
             if (s.kind == PLFX_SVC6) {
                 c->n_svc6++;
-                const int npad = (s.nsv + 255) & ~255;  // padded for 4 vectors per lane and trip
                 c->svc6_mask |= 1u << k;
                 if (c->want_svc_wave) {
-                    // the tables of the row kernels in device memory, in the layout of their LDS copy (stage_svc_wave): read from
+                    // the tables of the row kernels in device memory, in the layout of their LDS copy (stage_svc_row): read from
                     // there by the kernels when the material has more support vectors than the LDS of a CU holds
                     const int rp = (s.nsv + 63) & ~63;
                     std::vector<double> T((size_t)9 * rp + SVC_WAVE_EXTRA, 0.);
@@ -1992,14 +1969,16 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
                     m.rowtab = dT;
                     m.rowpad = rp;
                     c->svc_row_all |= 1u << k;
-                    // v[6], dual, |v|^2 in FP64 + (dual, g |v|^2) pairs in FP32 + the tables of the sampled-ray form: the row kernels
-                    // pad the vectors to 64 (up to 2176 vectors fit the 160 KB of a CU), the wave kernels of rounds 1-4 to 256
+                    // v[6], dual, |v|^2, one unused slot + the tables of the sampled-ray form, the vectors padded to 64 (up to
+                    // 2176 vectors fit the 160 KB of a CU)
                     if (9 * rp + SVC_WAVE_EXTRA <= c->lds_doubles) {
                         c->svc_row_lds |= 1u << k;
                         c->svc_wave_lds = std::max(c->svc_wave_lds, (9 * rp + SVC_WAVE_EXTRA) * 8);
                     }
-                    if (9 * npad + SVC_WAVE_EXTRA <= c->lds_doubles && npad <= 2048 && c->svc_wave_mat < 0) {
-                        c->svc_wave_mat = k;
+                    // kept from the removed wave kernels (tables padded to 256, first fitting material): shrinking it changes the launch
+                    const int npad = (s.nsv + 255) & ~255;
+                    if (9 * npad + SVC_WAVE_EXTRA <= c->lds_doubles && npad <= 2048 && !wave_pad) {
+                        wave_pad = true;
                         c->svc_wave_lds = std::max(c->svc_wave_lds, (9 * npad + SVC_WAVE_EXTRA) * 8);
                     }
                 }
@@ -2012,12 +1991,6 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     HIPCHK(c, hipMemcpyAsync(c->dmat, c->hmat.data(), sizeof(MatDev) * nmat, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, stream_sync(c));
     if (c->svc_wave_lds > 0) {
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_wave<0, false>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_wave<1, false>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_full_yf_wave<false>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_wave<0, true>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_wave<1, true>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_full_yf_wave<true>, c->svc_wave_lds));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<0, true>, c->svc_wave_lds));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<1, true>, c->svc_wave_lds));
         HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true>, c->svc_wave_lds));
@@ -2069,17 +2042,10 @@ static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, 
     }
     if (status) HIPCHK(c, hipMalloc((void **)&dst, (size_t)n * 4));
     static const bool wave_full = !(getenv("PLFX_FULL_YF_WAVE") && atoi(getenv("PLFX_FULL_YF_WAVE")) == 0);
-    if (what == 3 && wave_full && ((svc_fast_mask(c) >> mat) & 1u)) {  // ML_full_yf of a row / wave-kernel SVC material
-        if (svc_poly() == 2)
-            LAUNCH_ROW1(c, mat, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
-                       c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
-        else if (svc_poly())
-            hipLaunchKernelGGL(k_full_yf_wave<true>, dim3(std::max(1, std::min((n + 7) / 8, 2048))), dim3(512), (size_t)c->svc_wave_lds, c->stream,
-                               c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
-        else
-            hipLaunchKernelGGL(k_full_yf_wave<false>, dim3(std::max(1, std::min((n + 7) / 8, 2048))), dim3(512), (size_t)c->svc_wave_lds, c->stream,
-                               c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
-    } else
+    if (what == 3 && wave_full && ((c->svc_row_all >> mat) & 1u))  // ML_full_yf of a row-kernel SVC material
+        LAUNCH_ROW1(c, mat, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
+                   c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
+    else
         hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
                            c->dmat, c->nmat, c->svc_lds_need, what, mat, n, dsig, depl, dld, dout, dst);
     HIPCHK(c, hipGetLastError());
@@ -2184,7 +2150,7 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
     if (c->has_barlat)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<5>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, RB_ARGS(0), RB_TAIL);
     const bool resp_row = !(getenv("PLFX_RESPONSE_ROW") && atoi(getenv("PLFX_RESPONSE_ROW")) == 0);   // read per call: tests compare the two forms
-    const unsigned rmask = (resp_row && svc_poly() == 2) ? svc_fast_mask(c) : 0u;
+    const unsigned rmask = resp_row ? c->svc_row_all : 0u;
     if (c->has_svc && (c->svc6_mask & ~rmask))
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<3>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
                            c->stream, RB_ARGS(c->svc_lds_need), (const double *)nullptr, (double *)nullptr, rmask, c->resp_maxit);
@@ -3041,9 +3007,8 @@ int plfx_sweep_info(plfx_ctx *c, int64_t *sweeps, int64_t *tangents_rewritten)
 int plfx_svc_info(plfx_ctx *c, int *row_materials, int *thread_materials, int64_t *row_launches, int64_t *thread_launches)
 {
     if (!c) return PLFX_ERR_ARG;
-    const unsigned fast = (svc_poly() == 2) ? svc_fast_mask(c) : 0u;
-    if (row_materials) *row_materials = (int)fast;
-    if (thread_materials) *thread_materials = (int)(c->svc6_mask & ~svc_fast_mask(c));
+    if (row_materials) *row_materials = (int)c->svc_row_all;
+    if (thread_materials) *thread_materials = (int)(c->svc6_mask & ~c->svc_row_all);
     if (row_launches) *row_launches = c->n_svc_row_launches;
     if (thread_launches) *thread_launches = c->n_svc_thread_launches;
     return PLFX_OK;
@@ -4142,7 +4107,6 @@ int surrogate_build(plfx_ctx *c, long long *replaced)
 }
 
 constexpr int GMRES_BLK = 32;  // basis vectors per allocation
-constexpr int GMRES_M_CGS2 = 400;  // restart length of rounds 3-5 (PLFX_GMRES_ORTH=cgs2)
 constexpr int GMRES_M = 1200;      // restart length (round 6): restarts stall on indefinite K -- a solve that needs 500 iterations took three cycles of
                                    // 400 (1176 iterations) or none at all (residual stuck at 1e-6 after the first restart, profiles/r07e_*); with
                                    // the basis read twice instead of four times per iteration a cycle three times as long costs what it cost,
@@ -4161,8 +4125,7 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
     if (c->gm_m == 0) {
         size_t fr = 0, tot = 0;
         HIPCHK(c, hipMemGetInfo(&fr, &tot));
-        static const bool cgs2_len = getenv("PLFX_GMRES_ORTH") && !strcmp(getenv("PLFX_GMRES_ORTH"), "cgs2");
-        c->gm_m = getenv("PLFX_GMRES_M") ? std::max(25, atoi(getenv("PLFX_GMRES_M"))) : (cgs2_len ? GMRES_M_CGS2 : GMRES_M);
+        c->gm_m = getenv("PLFX_GMRES_M") ? std::max(25, atoi(getenv("PLFX_GMRES_M"))) : GMRES_M;
         c->gm_m = std::min(c->gm_m, 40 * GMRES_BLK - 1);
         while (c->gm_m > 25 && (size_t)(c->gm_m + 1) * nd * 8 > fr / 3) c->gm_m = (c->gm_m * 2) / 3;
         if (comm_active(c)) {  // every rank must run the same cycle length (paired collectives of a strip; identical iterates of a replicated solve)
@@ -4202,10 +4165,7 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
     int itn = 0, cycles = 0, poor = 0;
     double rl = 0., rr_prev = -1.;
     std::vector<double> H((size_t)(M + 1) * M), cs(M), sn(M), g(M + 1), hcol(M + 2);
-    // PLFX_GMRES_ORTH=cgs2 restores the orthogonalisation of rounds 3-5 (classical Gram-Schmidt twice: four sweeps over the basis
-    // per iteration, a host round trip per eight vectors); default: delayed re-orthogonalisation, two sweeps, two round trips
-    static const bool dcgs2 = !(getenv("PLFX_GMRES_ORTH") && !strcmp(getenv("PLFX_GMRES_ORTH"), "cgs2"));
-    std::vector<double> Hraw(dcgs2 ? (size_t)(M + 1) * M : 0);
+    std::vector<double> Hraw((size_t)(M + 1) * M);
     static const bool gm_dbg = getenv("PLFX_GMRES_DEBUG") != nullptr;
     while (true) {
         // r0 = P (b - K x) -> c->r; beta = |r0|
@@ -4234,192 +4194,126 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
         std::fill(g.begin(), g.end(), 0.);
         g[0] = beta;
         int k = 0;  // columns built in this cycle
-        if (dcgs2) {
-            // ---- Arnoldi with delayed re-orthogonalisation (plfx_mg.hpp: k_gmres_dots2 / k_gmres_update2).
-            // State at the top of iteration j >= 1: q_0 .. q_{j-1} final in V_0 .. V_{j-1}; u = V_j the once-projected candidate
-            // for q_j (u = w_{j-1} - Q_j h1, h1 = the first-pass coefficients kept in h1p); column j-1 of the Hessenberg matrix
-            // still open.  One operator application z = A u, one dots pass (s = Q_j^T u, t = Q_j^T z, u.u, u.z), then on the host
-            //   alpha^2 = u.u - s.s                      (q_j = (u - Q_j s) / alpha: the delayed second pass of vector j)
-            //   column j-1 of H:  h1 + s  over  alpha    -> Givens, residual estimate, convergence test (one iteration late)
-            //   w_j = A q_j = (z - A Q_j s) / alpha,  A Q_j s = Q_j (H s) + q_j rho,  rho = alpha s_{j-1}     (Arnoldi relation)
-            //   first pass of w_j:  c = Q_j^T w_j = (t - H s) / alpha,   d = q_j^T w_j = ((u.z - s.t) / alpha - rho) / alpha
-            //   next candidate      w_j - Q_j c - q_j d = (z - Q_j t) / alpha - e (u - Q_j s),   e = (rho / alpha + d) / alpha
-            // and one update pass over Q_j that writes q_j into V_j and the next candidate into V_{j+1}.
-            std::vector<double> h1p, sv(M + 2), tv(M + 2), cf(2 * (size_t)M + 4), red(2 * (size_t)M + 4);
-            const int ncolmax = 2 * M + 4;
-            if (!c->gm_part2 && (rc = dalloc(c, &c->gm_part2, (size_t)ncolmax * MAXPART))) return rc;
-            if (!c->gm_red && (rc = dalloc(c, &c->gm_red, (size_t)ncolmax))) return rc;
-            if (!c->gm_coef && (rc = dalloc(c, &c->gm_coef, (size_t)ncolmax))) return rc;
-            GmBlocks GB;
-            auto fill_blocks = [&]() { for (int q = 0; q < 40; q++) GB.blk[q] = q < (int)c->gm_blk.size() ? c->gm_blk[q] : c->gm_blk[0]; };
-            // sums over the basis: columns 2k (V_k . a), 2k+1 (V_k . b), then a.a, a.b -- one reduction kernel, one host round trip
-            auto dots = [&](int j, const double *a, const double *bvec) -> int {
-                fill_blocks();
-                const int gd = std::min(gn, std::max(1, (ohi - olo + 2 * BLOCK - 1) / (2 * BLOCK)));   // tiles of 512 nodes
-                for (int b0 = 0; b0 < j; b0 += GM_KC)
-                    hipLaunchKernelGGL(k_gmres_dots3, dim3(gd), dim3(BLOCK), 0, c->stream, olo, ohi, b0, std::min(GM_KC, j - b0), GB, nd,
-                                       (const double2 *)a, (const double2 *)bvec, b0 == 0 ? 2 * j : -1, c->gm_part2);
-                const int ncol = 2 * j + 2;
-                hipLaunchKernelGGL(k_gmres_reduce, dim3((ncol + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, ncol, gd,
-                                   (const double *)c->gm_part2, c->gm_red);
-                HIPCHK(c, hipGetLastError());
-                int e;
-                if (comm_active(c) && c->strip.on && (e = allreduce(c, c->gm_red, (size_t)ncol, NCCL_FLOAT64, NCCL_SUM, "GMRES sums"))) return e;
-                return fetch_results(c, c->gm_red, ncol, red.data());
-            };
-            // first step: w_0 = A q_0; h1 = q_0 . w_0; candidate u_1 = w_0 - q_0 h1 -> V_1
-            itn++;
-            hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)Vj(0),
-                               (double2 *)c->r, (double2 *)nullptr);
-            if ((rc = apply_B())) return rc;
-            LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
-                       (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            if ((rc = need(1))) return rc;
-            if ((rc = dots(1, c->q, nullptr))) return rc;
-            h1p.assign(1, red[0]);
-            cf[0] = red[0];
-            HIPCHK(c, hipMemcpyAsync(c->gm_coef + ncolmax / 2, cf.data(), 8, hipMemcpyHostToDevice, c->stream));
+        // ---- Arnoldi with delayed re-orthogonalisation (plfx_mg.hpp: k_gmres_dots3 / k_gmres_update2).
+        // State at the top of iteration j >= 1: q_0 .. q_{j-1} final in V_0 .. V_{j-1}; u = V_j the once-projected candidate
+        // for q_j (u = w_{j-1} - Q_j h1, h1 = the first-pass coefficients kept in h1p); column j-1 of the Hessenberg matrix
+        // still open.  One operator application z = A u, one dots pass (s = Q_j^T u, t = Q_j^T z, u.u, u.z), then on the host
+        //   alpha^2 = u.u - s.s                      (q_j = (u - Q_j s) / alpha: the delayed second pass of vector j)
+        //   column j-1 of H:  h1 + s  over  alpha    -> Givens, residual estimate, convergence test (one iteration late)
+        //   w_j = A q_j = (z - A Q_j s) / alpha,  A Q_j s = Q_j (H s) + q_j rho,  rho = alpha s_{j-1}     (Arnoldi relation)
+        //   first pass of w_j:  c = Q_j^T w_j = (t - H s) / alpha,   d = q_j^T w_j = ((u.z - s.t) / alpha - rho) / alpha
+        //   next candidate      w_j - Q_j c - q_j d = (z - Q_j t) / alpha - e (u - Q_j s),   e = (rho / alpha + d) / alpha
+        // and one update pass over Q_j that writes q_j into V_j and the next candidate into V_{j+1}.
+        std::vector<double> h1p, sv(M + 2), tv(M + 2), cf(2 * (size_t)M + 4), red(2 * (size_t)M + 4);
+        const int ncolmax = 2 * M + 4;
+        if (!c->gm_part2 && (rc = dalloc(c, &c->gm_part2, (size_t)ncolmax * MAXPART))) return rc;
+        if (!c->gm_red && (rc = dalloc(c, &c->gm_red, (size_t)ncolmax))) return rc;
+        if (!c->gm_coef && (rc = dalloc(c, &c->gm_coef, (size_t)ncolmax))) return rc;
+        GmBlocks GB;
+        auto fill_blocks = [&]() { for (int q = 0; q < 40; q++) GB.blk[q] = q < (int)c->gm_blk.size() ? c->gm_blk[q] : c->gm_blk[0]; };
+        // sums over the basis: columns 2k (V_k . a), 2k+1 (V_k . b), then a.a, a.b -- one reduction kernel, one host round trip
+        auto dots = [&](int j, const double *a, const double *bvec) -> int {
             fill_blocks();
-            hipLaunchKernelGGL(k_gmres_update2, dim3(gn), dim3(BLOCK), 0, c->stream, nn, nd, 1, GB, (const double *)c->gm_coef,
-                               (const double *)(c->gm_coef + ncolmax / 2), 1., 0., (const double2 *)c->q, (const double2 *)nullptr,
-                               (double2 *)nullptr, (double2 *)Vj(1));
+            const int gd = std::min(gn, std::max(1, (ohi - olo + 2 * BLOCK - 1) / (2 * BLOCK)));   // tiles of 512 nodes
+            for (int b0 = 0; b0 < j; b0 += GM_KC)
+                hipLaunchKernelGGL(k_gmres_dots3, dim3(gd), dim3(BLOCK), 0, c->stream, olo, ohi, b0, std::min(GM_KC, j - b0), GB, nd,
+                                   (const double2 *)a, (const double2 *)bvec, b0 == 0 ? 2 * j : -1, c->gm_part2);
+            const int ncol = 2 * j + 2;
+            hipLaunchKernelGGL(k_gmres_reduce, dim3((ncol + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, ncol, gd,
+                               (const double *)c->gm_part2, c->gm_red);
             HIPCHK(c, hipGetLastError());
-            for (int j = 1; j <= M; j++) {
-                const bool more = j < M && itn < maxit;   // another basis vector may still be built after this one
-                // z = A u -> c->q   (the operator application of iteration j + 1, on the candidate: one ahead of the finished basis)
-                itn++;
-                hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)Vj(j),
-                                   (double2 *)c->r, (double2 *)nullptr);
-                if ((rc = apply_B())) return rc;
-                LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
-                           (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
-                HIPCHK(c, hipGetLastError());
-                if ((rc = dots(j, Vj(j), c->q))) return rc;
-                double ss = 0., st = 0.;
-                for (int q = 0; q < j; q++) {
-                    sv[q] = red[2 * q];
-                    tv[q] = red[2 * q + 1];
-                    ss += sv[q] * sv[q];
-                    st += sv[q] * tv[q];
-                }
-                const double uu = red[2 * j], uz = red[2 * j + 1];
-                const double a2 = uu - ss;
-                const double alpha = (a2 > 0. && std::isfinite(a2)) ? std::sqrt(a2) : 0.;
-                if (gm_dbg) {
-                    double smax = 0.;
-                    for (int q = 0; q < j; q++) smax = std::max(smax, std::fabs(sv[q]));
-                    fprintf(stderr, "[gmres-d] j %d u.u %.6e s.s %.3e max|s| %.3e alpha %.6e |g| %.3e\n", j, uu, ss, smax, alpha, std::fabs(g[j - 1]));
-                }
-                // column j-1 of the Hessenberg matrix is complete: first-pass coefficients + the delayed second pass, alpha below
-                std::fill(hcol.begin(), hcol.end(), 0.);
-                for (int q = 0; q < j; q++) hcol[q] = h1p[q] + sv[q];
-                hcol[j] = alpha;
-                for (int q = 0; q <= j; q++) Hraw[(size_t)q * M + (j - 1)] = hcol[q];
-                for (int q = 0; q < j - 1; q++) {
-                    const double t = cs[q] * hcol[q] + sn[q] * hcol[q + 1];
-                    hcol[q + 1] = -sn[q] * hcol[q] + cs[q] * hcol[q + 1];
-                    hcol[q] = t;
-                }
-                const double den = std::hypot(hcol[j - 1], hcol[j]);
-                cs[j - 1] = den > 0. ? hcol[j - 1] / den : 1.;
-                sn[j - 1] = den > 0. ? hcol[j] / den : 0.;
-                hcol[j - 1] = den;
-                hcol[j] = 0.;
-                g[j] = -sn[j - 1] * g[j - 1];
-                g[j - 1] = cs[j - 1] * g[j - 1];
-                for (int q = 0; q < j; q++) H[(size_t)q * M + (j - 1)] = hcol[q];
-                k = j;
-                if (std::fabs(g[j]) <= tol || !(alpha > 0.) || !more) break;
-                // first pass of the next vector, from the sums at hand
-                const double ia = 1. / alpha;
-                const double rho = alpha * sv[j - 1];
-                const double d = ((uz - st) * ia - rho) * ia;
-                const double e = (rho * ia + d) * ia;
-                h1p.assign(j + 1, 0.);
-                for (int q = 0; q < j; q++) {
-                    double r = 0.;   // (H s)_q over the finished columns (upper Hessenberg: column p reaches row p + 1)
-                    for (int p2 = (q > 0 ? q - 1 : 0); p2 < j; p2++) r += Hraw[(size_t)q * M + p2] * sv[p2];
-                    h1p[q] = (tv[q] - r) * ia;
-                    cf[q] = sv[q];
-                    cf[ncolmax / 2 + q] = tv[q] * ia - e * sv[q];
-                }
-                h1p[j] = d;
-                if ((rc = need(j + 1))) return rc;
-                fill_blocks();
-                HIPCHK(c, hipMemcpyAsync(c->gm_coef, cf.data(), (size_t)8 * j, hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->gm_coef + ncolmax / 2, cf.data() + ncolmax / 2, (size_t)8 * j, hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(k_gmres_update2, dim3(gn), dim3(BLOCK), 0, c->stream, nn, nd, j, GB, (const double *)c->gm_coef,
-                                   (const double *)(c->gm_coef + ncolmax / 2), ia, e, (const double2 *)Vj(j), (const double2 *)c->q,
-                                   (double2 *)Vj(j), (double2 *)Vj(j + 1));
-                HIPCHK(c, hipGetLastError());
-            }
-            c->n_gmres_its += k;
-        } else {
-        for (int j = 0; j < M && itn < maxit; j++) {
+            int e;
+            if (comm_active(c) && c->strip.on && (e = allreduce(c, c->gm_red, (size_t)ncol, NCCL_FLOAT64, NCCL_SUM, "GMRES sums"))) return e;
+            return fetch_results(c, c->gm_red, ncol, red.data());
+        };
+        // first step: w_0 = A q_0; h1 = q_0 . w_0; candidate u_1 = w_0 - q_0 h1 -> V_1
+        itn++;
+        hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)Vj(0),
+                           (double2 *)c->r, (double2 *)nullptr);
+        if ((rc = apply_B())) return rc;
+        LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
+                   (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = need(1))) return rc;
+        if ((rc = dots(1, c->q, nullptr))) return rc;
+        h1p.assign(1, red[0]);
+        cf[0] = red[0];
+        HIPCHK(c, hipMemcpyAsync(c->gm_coef + ncolmax / 2, cf.data(), 8, hipMemcpyHostToDevice, c->stream));
+        fill_blocks();
+        hipLaunchKernelGGL(k_gmres_update2, dim3(gn), dim3(BLOCK), 0, c->stream, nn, nd, 1, GB, (const double *)c->gm_coef,
+                           (const double *)(c->gm_coef + ncolmax / 2), 1., 0., (const double2 *)c->q, (const double2 *)nullptr,
+                           (double2 *)nullptr, (double2 *)Vj(1));
+        HIPCHK(c, hipGetLastError());
+        for (int j = 1; j <= M; j++) {
+            const bool more = j < M && itn < maxit;   // another basis vector may still be built after this one
+            // z = A u -> c->q   (the operator application of iteration j + 1, on the candidate: one ahead of the finished basis)
             itn++;
-            // w = P K B V_j  -> c->q
             hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)Vj(j),
                                (double2 *)c->r, (double2 *)nullptr);
             if ((rc = apply_B())) return rc;
             LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
                        (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
             HIPCHK(c, hipGetLastError());
-            // classical Gram-Schmidt, twice: h = V^T w; w -= V h
-            std::fill(hcol.begin(), hcol.end(), 0.);
-            double wnorm2 = 0.;
-            for (int pass = 0; pass < 2; pass++) {
-                std::vector<double> hp(j + 1, 0.);
-                for (int b0 = 0; b0 <= j; b0 += 8) {
-                    const int n8 = std::min(8, j + 1 - b0);
-                    Ptr8 V8;
-                    for (int q = 0; q < 8; q++) V8.p[q] = (const double2 *)Vj(b0 + std::min(q, n8 - 1));
-                    hipLaunchKernelGGL(k_gmres_dots, dim3(gn), dim3(BLOCK), 0, c->stream, olo, ohi, n8, (const double2 *)c->q, V8,
-                                       c->gm_part);
-                    HIPCHK(c, hipGetLastError());
-                    double o8[8];
-                    if ((rc = host_sums(c, c->gm_part, n8, gn, o8))) return rc;
-                    for (int q = 0; q < n8; q++) hp[b0 + q] = o8[q];
-                }
-                for (int b0 = 0; b0 <= j; b0 += 8) {
-                    const int n8 = std::min(8, j + 1 - b0);
-                    Ptr8 V8;
-                    Coef8 C8;
-                    for (int q = 0; q < 8; q++) {
-                        V8.p[q] = (const double2 *)Vj(b0 + std::min(q, n8 - 1));
-                        C8.c[q] = q < n8 ? -hp[b0 + q] : 0.;
-                    }
-                    const bool last = b0 + 8 > j;
-                    hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, n8, (double2 *)c->q, V8, C8,
-                                       last ? c->gm_part : (double *)nullptr, olo, ohi);
-                    HIPCHK(c, hipGetLastError());
-                    if (last && (rc = host_sums(c, c->gm_part, 1, gn, &wnorm2))) return rc;
-                }
-                for (int q = 0; q <= j; q++) hcol[q] += hp[q];
-            }
-            const double hn = std::sqrt(std::max(wnorm2, 0.));
-            hcol[j + 1] = hn;
-            // Givens rotations: previous ones on the new column, then the new one
+            if ((rc = dots(j, Vj(j), c->q))) return rc;
+            double ss = 0., st = 0.;
             for (int q = 0; q < j; q++) {
+                sv[q] = red[2 * q];
+                tv[q] = red[2 * q + 1];
+                ss += sv[q] * sv[q];
+                st += sv[q] * tv[q];
+            }
+            const double uu = red[2 * j], uz = red[2 * j + 1];
+            const double a2 = uu - ss;
+            const double alpha = (a2 > 0. && std::isfinite(a2)) ? std::sqrt(a2) : 0.;
+            if (gm_dbg) {
+                double smax = 0.;
+                for (int q = 0; q < j; q++) smax = std::max(smax, std::fabs(sv[q]));
+                fprintf(stderr, "[gmres-d] j %d u.u %.6e s.s %.3e max|s| %.3e alpha %.6e |g| %.3e\n", j, uu, ss, smax, alpha, std::fabs(g[j - 1]));
+            }
+            // column j-1 of the Hessenberg matrix is complete: first-pass coefficients + the delayed second pass, alpha below
+            std::fill(hcol.begin(), hcol.end(), 0.);
+            for (int q = 0; q < j; q++) hcol[q] = h1p[q] + sv[q];
+            hcol[j] = alpha;
+            for (int q = 0; q <= j; q++) Hraw[(size_t)q * M + (j - 1)] = hcol[q];
+            for (int q = 0; q < j - 1; q++) {
                 const double t = cs[q] * hcol[q] + sn[q] * hcol[q + 1];
                 hcol[q + 1] = -sn[q] * hcol[q] + cs[q] * hcol[q + 1];
                 hcol[q] = t;
             }
-            const double den = std::hypot(hcol[j], hcol[j + 1]);
-            cs[j] = den > 0. ? hcol[j] / den : 1.;
-            sn[j] = den > 0. ? hcol[j + 1] / den : 0.;
-            hcol[j] = den;
-            hcol[j + 1] = 0.;
-            g[j + 1] = -sn[j] * g[j];
-            g[j] = cs[j] * g[j];
-            for (int q = 0; q <= j; q++) H[(size_t)q * M + j] = hcol[q];
-            k = j + 1;
-            if (std::fabs(g[j + 1]) <= tol || !(hn > 0.)) break;
+            const double den = std::hypot(hcol[j - 1], hcol[j]);
+            cs[j - 1] = den > 0. ? hcol[j - 1] / den : 1.;
+            sn[j - 1] = den > 0. ? hcol[j] / den : 0.;
+            hcol[j - 1] = den;
+            hcol[j] = 0.;
+            g[j] = -sn[j - 1] * g[j - 1];
+            g[j - 1] = cs[j - 1] * g[j - 1];
+            for (int q = 0; q < j; q++) H[(size_t)q * M + (j - 1)] = hcol[q];
+            k = j;
+            if (std::fabs(g[j]) <= tol || !(alpha > 0.) || !more) break;
+            // first pass of the next vector, from the sums at hand
+            const double ia = 1. / alpha;
+            const double rho = alpha * sv[j - 1];
+            const double d = ((uz - st) * ia - rho) * ia;
+            const double e = (rho * ia + d) * ia;
+            h1p.assign(j + 1, 0.);
+            for (int q = 0; q < j; q++) {
+                double r = 0.;   // (H s)_q over the finished columns (upper Hessenberg: column p reaches row p + 1)
+                for (int p2 = (q > 0 ? q - 1 : 0); p2 < j; p2++) r += Hraw[(size_t)q * M + p2] * sv[p2];
+                h1p[q] = (tv[q] - r) * ia;
+                cf[q] = sv[q];
+                cf[ncolmax / 2 + q] = tv[q] * ia - e * sv[q];
+            }
+            h1p[j] = d;
             if ((rc = need(j + 1))) return rc;
-            hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1. / hn, (const double2 *)c->q,
-                               (double2 *)Vj(j + 1), (double2 *)nullptr);
+            fill_blocks();
+            HIPCHK(c, hipMemcpyAsync(c->gm_coef, cf.data(), (size_t)8 * j, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->gm_coef + ncolmax / 2, cf.data() + ncolmax / 2, (size_t)8 * j, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_gmres_update2, dim3(gn), dim3(BLOCK), 0, c->stream, nn, nd, j, GB, (const double *)c->gm_coef,
+                               (const double *)(c->gm_coef + ncolmax / 2), ia, e, (const double2 *)Vj(j), (const double2 *)c->q,
+                               (double2 *)Vj(j), (double2 *)Vj(j + 1));
+            HIPCHK(c, hipGetLastError());
         }
-        }
+        c->n_gmres_its += k;
         // y = H^-1 g (upper triangular); t = V y -> c->r; x += B t
         std::vector<double> y(k, 0.);
         for (int q = k - 1; q >= 0; q--) {
@@ -4436,7 +4330,7 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
                 V8.p[q] = (const double2 *)Vj(b0 + std::min(q, n8 - 1));
                 C8.c[q] = q < n8 ? y[b0 + q] : 0.;
             }
-            hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, n8, (double2 *)c->r, V8, C8, (double *)nullptr, olo, ohi);
+            hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, n8, (double2 *)c->r, V8, C8);
         }
         if ((rc = apply_B())) return rc;
         {
@@ -4446,7 +4340,7 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
                 V8.p[q] = (const double2 *)c->z;
                 C8.c[q] = q == 0 ? 1. : 0.;
             }
-            hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, 1, (double2 *)c->x, V8, C8, (double *)nullptr, olo, ohi);
+            hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, 1, (double2 *)c->x, V8, C8);
         }
         HIPCHK(c, hipGetLastError());
         // next cycle starts from the true residual of x (and ends the solve if it is small enough)
@@ -4853,12 +4747,11 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
             done = hs.done;
         }
     }
-    static const bool fuse_dot = !(getenv("PLFX_FUSE_DOT") && atoi(getenv("PLFX_FUSE_DOT")) == 0);
     if (mg && pred_site >= 0 && pred_active) c->first_test_hint[pred_site] = pred_first_passed;
     if (mg && !done) {
-        c->fuse_rz = fuse_dot ? P_rz[1] : nullptr;  // r.z partials from the last post-smoothing launch of the cycle
+        c->fuse_rz = P_rz[1];  // r.z partials from the last post-smoothing launch of the cycle
         rc = mg_vcycle_rest(c);
-        const bool fused = fuse_dot && c->fuse_rz == nullptr;
+        const bool fused = c->fuse_rz == nullptr;
         c->fuse_rz = nullptr;
         if (rc) return rc;
         if (!fused)
@@ -4936,9 +4829,9 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
                     it++;
                     break;
                 }
-                c->fuse_rz = fuse_dot ? P_rz[cur] : nullptr;
+                c->fuse_rz = P_rz[cur];
                 rc = mg_vcycle_rest(c);
-                const bool fused = fuse_dot && c->fuse_rz == nullptr;
+                const bool fused = c->fuse_rz == nullptr;
                 c->fuse_rz = nullptr;
                 tim_end(c, evv);
                 if (rc) return rc;
@@ -5174,13 +5067,10 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                         c->res_sig, c->res_depl, c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     // phase 1 per material kind present (the first launched instantiation also clears fyn of elastic elements)
     int first = 1;
-    const int wm = c->svc_wave_mat;  // modes 0 / 1: this SVC material runs wave-per-element
-    const unsigned fast = svc_fast_mask(c);   // these materials run on the row (wave) kernels, the thread-per-element kernels skip them
+    const unsigned fast = c->svc_row_all;   // these materials run on the row kernels, the thread-per-element kernels skip them
     const bool svc_thread = c->has_svc && (c->svc6_mask & ~fast);
-    // one wave per element, one block per CU and round (the tables fill most of the LDS): 4 waves x 1024 blocks
-    const int grid_w = std::max(1, std::min((c->nel + 3) / 4, 1024));
     const int grid_r = std::max(1, std::min((c->nel + 31) / 32, 1024));   // 16 lanes per element: 32 elements per block and round
-#define WAVE_ARGS c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,  \
+#define ROW_ARGS c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,  \
                   c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,       \
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh)) {
@@ -5205,20 +5095,12 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         c->n_svc_thread_launches++;
     }
     if (c->has_svc && fast) {
-        if (svc_poly() == 2) {
-            for (int k = 0; k < c->nmat; k++)   // one launch per material: its tables fill the LDS
-                if ((fast >> k) & 1u) {
-                    LAUNCH_ROW2(c, k, k_sweep_svc_row, 0, dim3(grid_r), WAVE_ARGS, first, k);
-                    first = 0;
-                    c->n_svc_row_launches++;
-                }
-        } else if (svc_poly())
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_svc_wave<0, true>), dim3(grid_w), dim3(512), (size_t)c->svc_wave_lds,
-                               c->stream, WAVE_ARGS, first, wm);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_svc_wave<0, false>), dim3(grid_w), dim3(512), (size_t)c->svc_wave_lds,
-                               c->stream, WAVE_ARGS, first, wm);
-        first = 0;
+        for (int k = 0; k < c->nmat; k++)   // one launch per material: its tables fill the LDS
+            if ((fast >> k) & 1u) {
+                LAUNCH_ROW2(c, k, k_sweep_svc_row, 0, dim3(grid_r), ROW_ARGS, first, k);
+                first = 0;
+                c->n_svc_row_launches++;
+            }
     }
     if (c->has_svc3) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
@@ -5256,17 +5138,9 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     if (svc_thread)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
                            c->stream, SWEEP_ARGS(c->svc_lds_need), fast);
-    if (c->has_svc && fast) {
-        if (svc_poly() == 2) {
-            for (int k = 0; k < c->nmat; k++)
-                if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, k_sweep_svc_row, 1, dim3(grid_r), WAVE_ARGS, 0, k);
-        } else if (svc_poly())
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_svc_wave<1, true>), dim3(grid_w), dim3(PLFX_HEAVY_THREADS), (size_t)c->svc_wave_lds,
-                               c->stream, WAVE_ARGS, 0, wm);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_svc_wave<1, false>), dim3(grid_w), dim3(PLFX_HEAVY_THREADS), (size_t)c->svc_wave_lds,
-                               c->stream, WAVE_ARGS, 0, wm);
-    }
+    if (c->has_svc && fast)
+        for (int k = 0; k < c->nmat; k++)
+            if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
     if (c->has_svc3)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
                            c->stream, SWEEP_ARGS(c->svc_lds_need), 0u);
@@ -5281,7 +5155,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                            c->stream, SWEEP_ARGS(c->svc_lds_need), 0u, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
                            wh_seq ? c->kh_touch : (int32_t *)nullptr);
 #undef SWEEP_ARGS
-#undef WAVE_ARGS
+#undef ROW_ARGS
     tim_end(c, ev);
     int h[4];
     const bool spec = c->spec_arm && !comm_active(c) && c->mbox && c->mb_cap >= 2 && matfree(c) && !c->strip.on && c->assembled;
@@ -5488,7 +5362,7 @@ int plfx_wh_carry(plfx_ctx *c, int mat, const double *set, double *get)
 // calc_scf per element: hh and multiplicity of every owned element into scf_hh / scf_mult (sld at small + 32)
 static void launch_scf_elements(plfx_ctx *c)
 {
-    const unsigned fast = (svc_poly() == 2) ? svc_fast_mask(c) : 0u;
+    const unsigned fast = c->svc_row_all;
     hipLaunchKernelGGL(k_scf_elements, dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
                        c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn,
                        c->dcls_id, (const double2 *)c->du, c->sig, c->epl, tan_store(c),

@@ -23,7 +23,7 @@ namespace plfx {
 
 extern __shared__ double dyn_lds[];
 
-// Region timers of the wave-per-element SVC kernels (probe builds only: hipcc ... -DPLFX_PROF_REGIONS -o libplfx_prof.so, loaded
+// Region timers of the row-per-element SVC kernels (probe builds only: hipcc ... -DPLFX_PROF_REGIONS -o libplfx_prof.so, loaded
 // through PLFX_LIB): lane 0 of every wave adds the shader-clock ticks it spent in a region; plfx_destroy prints the totals.
 // CAVEAT (measured, round 5): s_memtime waits for all outstanding memory operations, which serialises the software-pipelined
 // LDS reads -- the instrumented corrector runs 4x slower and the shares are distorted; the scaling probe
@@ -110,7 +110,7 @@ constexpr double LOG2E = 1.4426950408889634;
 #ifndef PLFX_RAY_BOUND
 #define PLFX_RAY_BOUND 1.e-7
 #endif
-constexpr double RAY_BOUND = PLFX_RAY_BOUND;   // rigorous bound on |f - p| the sampled-ray interval is shrunk to (see ray_sample)
+constexpr double RAY_BOUND = PLFX_RAY_BOUND;   // rigorous bound on |f - p| the sampled-ray interval is shrunk to (see YfSvcRow::ray_sample)
 
 // sum over the 64 lanes of a wave, result in every lane (and wave-uniform for the compiler: scalar branches).
 // Four DPP butterfly steps inside each row of 16 lanes (quad xor 1, xor 2, half-row mirror, row mirror: no LDS
@@ -155,7 +155,7 @@ struct MatDev {
     double E, nu;
     double gamma, intercept, scale_seq;
     double scale_wh;     // SVC with work-hardening features: scaling of the plastic-strain features (material.py:2343)
-    double svc_sabs, svc_vvmax;  // sum |dual_k| and max |v_k|^2 over the support vectors (error bounds of YfSvcT::ray_sample)
+    double svc_sabs, svc_vvmax;  // sum |dual_k| and max |v_k|^2 over the support vectors (error bounds of YfSvcRow::ray_sample)
     const double *rowtab;        // 6-feature SVC: the tables of the row kernels in device memory, laid out like their LDS copy
                                  // (v[6][rowpad], dual, |v|^2, -, RAYPOLY_MT, 0.98^i, 1.02^i) -- read from here (L2) when the
                                  // tables do not fit the LDS of a CU (k_*_row<..., false>)
@@ -759,383 +759,31 @@ struct BrentState {
     }
 };
 
-// Yield-function policy: RBF-SVC (ML_yf) on NF = 6 stress features (sdim 6) or NF = 2 (sdim 3).
-// calc_seq of an ML material is J2 (hill = ones), on Voigt or on principal stresses.
-// WAVE = NC > 0 (NF = 6): one wave works on ONE material point; every lane carries the same point (the scalar part of the
-// algorithm runs redundantly in lock-step, as cheap as running it once) and the support-vector sums are split over the
-// lanes: lane L takes the vectors L, L+64, ... from the SoA tables in dynamic LDS (stride-1 across lanes: conflict-free
-// ds_read_b64, no dependent flat loads), followed by one wave reduction.  npad = vectors padded to a multiple of 64 NC
-// with dual = 0.  Tables: v[6][npad] at dyn_lds[0], dual[npad] at dyn_lds[6*npad].
-template <int NF, int WAVE = 0, bool POLY = false>
+// Yield-function policy: RBF-SVC (ML_yf) on NF = 6 stress features (sdim 6) or NF = 2 (sdim 3), one thread per point
+// (entry points, calc_scf, the thread sweeps).  calc_seq of an ML material is J2 (hill = ones), on Voigt or on principal stresses.
+template <int NF>
 struct YfSvcT {
     const MatDev &m;
     const double *sv;
     const double *dual;
-    int npad;
-    __device__ YfSvcT(const MatDev &mm, const double *s, const double *d, int np = 0) : m(mm), sv(s), dual(d), npad(np) {}
+    __device__ YfSvcT(const MatDev &mm, const double *s, const double *d) : m(mm), sv(s), dual(d) {}
     __device__ __forceinline__ double seq(const double *s) const { return NF == 6 ? hill_seq(m, s) : princ_seq(m, s); }
-    // NC = WAVE support vectors per lane and trip (k, k + 64, ...): all 7 NC LDS reads are issued before the first use
-    // (the empty asm pins them: otherwise the scheduler re-uses one register pair and waits after every read), and the
-    // NC independent distance / exp chains give the one or two resident waves of a SIMD instruction-level parallelism.
-    // npad is a multiple of 64 NC.
-    static constexpr int NC = WAVE > 0 ? WAVE : 1;
-    // LDS reads of one trip: issued as a batch (the sched_barrier keeps the scheduler from sinking them to their uses) ...
-    __device__ __forceinline__ static void issue(int npad, int k, double (*v)[7])
-    {
-#pragma unroll
-        for (int i = 0; i < 7; i++)
-#pragma unroll
-            for (int c = 0; c < NC; c++) v[c][i] = dyn_lds[i * npad + k + 64 * c];
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    // ... and awaited together, one trip later (software pipeline: the reads of trip t+1 fly during the arithmetic of t)
-    __device__ __forceinline__ static void pin(double (*v)[7])
-    {
-#pragma unroll
-        for (int c = 0; c < NC; c++)
-            asm volatile("" : "+v"(v[c][0]), "+v"(v[c][1]), "+v"(v[c][2]), "+v"(v[c][3]), "+v"(v[c][4]), "+v"(v[c][5]),
-                         "+v"(v[c][6]));
-    }
-    // body(v) consumes one trip of NC vectors per lane.  (Ping-pong prefetching of the next trip's reads was measured:
-    // no gain, the loop is bound by FP64 issue, not by LDS latency.)
-    template <class BODY>
-    __device__ __forceinline__ void for_trips(BODY body) const
-    {
-        for (int k = threadIdx.x & 63; k < npad; k += 64 * NC) {
-            double A[NC][7];
-            issue(npad, k, A);
-            pin(A);
-            body(A);
-        }
-    }
-    // ---- evaluations along a ray x = t su (ML_full_yf evaluates ~12 points on the same ray): the feature vector is
-    // linear in t, X(t) = t D with D = features(su), so |X - v_k|^2 = t^2 |D|^2 - 2 t (D.v_k) + |v_k|^2.  D.v_k is
-    // computed once per ray and kept in registers (one value per vector of this lane), |v_k|^2 is the 8th LDS table:
-    // 2 fused multiply-adds and 2 LDS reads per vector and evaluation instead of 12 operations and 7 reads.
-    static constexpr int MAXTRIP = 2048 / (64 * NC);   // 64 NC MAXTRIP >= npad: up to 2048 support vectors
-    // FP32 sign screen of the marching bracket (ray_screen): in the corrector kernel (4 vectors per lane and trip, one wave
-    // per SIMD, registers to spare); the streaming kernel (2 waves per SIMD, 256 VGPRs) has no room for the FP32 copies
-    static constexpr bool SCREEN = WAVE >= 4 && NF == 6 && !POLY;
-    struct RaySetup {
-        double DD;
-        double ck[WAVE > 0 ? MAXTRIP : 1][NC];
-        float ck32[SCREEN ? MAXTRIP : 1][NC];    // the same in FP32 for the sign screen of the marching bracket
-        float ckmax, gvvmax;                     // bounds of |D.v_k| and gamma log2(e) |v_k|^2 over the vectors (error margin)
-    };
-    __device__ __forceinline__ void ray_setup(const double *su, RaySetup &r) const
-    {
-        if (WAVE == 0 || NF != 6) return;
-        double D[6];
-        svc_features(m, su, D);
-        r.DD = 0.;
-#pragma unroll
-        for (int i = 0; i < 6; i++) r.DD = fma(D[i], D[i], r.DD);
-        const int lane = threadIdx.x & 63;
-        float ckm = 0.f;
-#pragma unroll
-        for (int t = 0; t < MAXTRIP; t++) {
-            if (t * 64 * NC < npad) {  // wave-uniform
-                double v[NC][7];
-                issue(npad, lane + t * 64 * NC, v);
-                pin(v);
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    double a = 0.;
-#pragma unroll
-                    for (int i = 0; i < 6; i++) a = fma(D[i], v[c][i], a);
-                    r.ck[t][c] = a;
-                    if (SCREEN) {
-                        r.ck32[t][c] = (float)a;
-                        ckm = fmaxf(ckm, fabsf((float)a));
-                    }
-                }
-            }
-        }
-        if (!SCREEN) return;
-        // bounds for the error margin of ray_screen (wave maxima; |v_k|^2 table * gamma log2 e)
-        float gm = 0.f;
-        const float2 *t32 = reinterpret_cast<const float2 *>(dyn_lds + 8 * npad);
-        for (int k = lane; k < npad; k += 64) gm = fmaxf(gm, fabsf(t32[k].y));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            ckm = fmaxf(ckm, __shfl_xor(ckm, off, 64));
-            gm = fmaxf(gm, __shfl_xor(gm, off, 64));
-        }
-        r.ckmax = ckm;
-        r.gvvmax = gm;
-    }
-    // FP32 estimate of the decision function at x su with a rigorous error margin: the marching bracket of ML_full_yf
-    // (material.py:475-486, ten to thirty-five 2 % steps per call) only needs the SIGN of the yield function at the
-    // intermediate points -- wherever |estimate| > margin the FP64 evaluation is skipped; the points where the march stops,
-    // and every point the estimate cannot decide, are evaluated in FP64 as before, so bracket ends, brentq iterates and the
-    // result are unchanged.  Per vector: arg = (g t^2 |D|^2) + (-2 g t)(D.v_k) + g |v_k|^2 in FP32, v_exp_f32, two
-    // multiply-adds (sum and sum of magnitudes S): 5 FP32 instructions against 21 FP64 ones.
-    // Error of the estimate <= S (ln 2 * d_arg + e_exp + e_sum) with d_arg <= 6 * 2^-24 * M, M = |g t^2 DD| + |2 g t| max|D.v| +
-    // max g|v|^2 (three roundings + the FP32 representation of the three inputs), e_exp <= 2^-22 (v_exp_f32: 1 ulp, table
-    // entry 0.5 ulp), e_sum <= (npad / 64 + 7) 2^-24 (sequential partial sums per lane + wave reduction).  The margin used is
-    // S (1e-6 M + 1e-5): four to five times that bound.
-    __device__ __forceinline__ double ray_screen(const RaySetup &r, double x, double &margin) const
-    {
-        const double g = -m.gamma * LOG2E;
-        const float A = (float)(g * x * x * r.DD), B = (float)(-2. * g * x);
-        const int lane = threadIdx.x & 63;
-        const float2 *t32 = reinterpret_cast<const float2 *>(dyn_lds + 8 * npad);
-        float f[NC], sa[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) f[c] = 0.f, sa[c] = 0.f;
-#pragma unroll
-        for (int t = 0; t < MAXTRIP; t++) {
-            if (t * 64 * NC < npad) {
-                const int k = lane + t * 64 * NC;
-                float2 tv[NC];
-#pragma unroll
-                for (int c = 0; c < NC; c++) tv[c] = t32[k + 64 * c];
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    const float e = __builtin_amdgcn_exp2f(fmaf(B, r.ck32[SCREEN ? t : 0][c], A) + tv[c].y);
-                    f[c] = fmaf(tv[c].x, e, f[c]);
-                    sa[c] = fmaf(fabsf(tv[c].x), e, sa[c]);
-                }
-            }
-        }
-        float fs = f[0], ss = sa[0];
-#pragma unroll
-        for (int c = 1; c < NC; c++) fs += f[c], ss += sa[c];
-        const double F = wave_allsum((double)fs), S = wave_allsum((double)ss);
-        const double M = fabs((double)A) + fabs((double)B) * (double)r.ckmax + (double)r.gvvmax;
-        margin = S * (1.e-6 * M + 1.e-5) + 1.e-300;
-        return F + m.intercept;
-    }
-    __device__ __forceinline__ double ray_eval(const double *su, const RaySetup &r, double x) const
-    {
-        if (WAVE == 0 || NF != 6) {
-            double xs[6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) xs[i] = x * su[i];
-            return decision(xs);
-        }
-        const double g = -m.gamma * LOG2E;
-        const int lane = threadIdx.x & 63;
-        const double tt = x * x * r.DD, m2t = -2. * x;
-        double f[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) f[c] = 0.;
-#pragma unroll
-        for (int t = 0; t < MAXTRIP; t++) {
-            if (t * 64 * NC < npad) {
-                const int k = lane + t * 64 * NC;
-                double du[NC], vv[NC];
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    du[c] = dyn_lds[6 * npad + k + 64 * c];
-                    vv[c] = dyn_lds[7 * npad + k + 64 * c];
-                }
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    const double h = fma(m2t, r.ck[t][c], tt) + vv[c];
-                    f[c] = fma(du[c], exp2_neg(g * h), f[c]);
-                }
-            }
-        }
-        double tsum = f[0];
-#pragma unroll
-        for (int c = 1; c < NC; c++) tsum += f[c];
-        return wave_allsum(tsum) + m.intercept;
-    }
-    // ---- sampled-ray form of the ray search (round 5; POLY, wave mode, 6 stress features).  Along x = t su every kernel
-    // term is a Gaussian in t, d_k exp(-gamma (DD t^2 - 2 c_k t + |v_k|^2)), so on equally spaced points t_j = lo + j dl
-    //   term_k(t_j) = [d_k e^{-gamma h_k(lo)}] rho_k^j e^{-gamma DD dl^2 j^2},   rho_k = e^{2 gamma dl (c_k - DD lo)}:
-    // ONE pass over the support vectors (two exp per vector, then one multiply and one add per sample) yields NS samples
-    // of the decision function, the fixed matrix RAYPOLY_MT turns them into the Chebyshev coefficients of the
-    // interpolating polynomial p on [lo, hi], and the 2 % marching bracket of ML_full_yf (material.py:468-486) and the
-    // brentq iterates (:501-503) are evaluated on p -- 32 instructions per point in lock-step instead of a pass over the
-    // vectors (~10 FP64 + ~20 FP32 passes per call before).  f along a ray is entire with length scale 1/sqrt(2 gamma DD):
-    //   |f - p| <= sum|d_k| K sqrt(NS!) / (4 NS) (sqrt(2 gamma DD) dl)^NS          (K = 1.0865: Cramer's bound on Hermite functions)
-    // on the whole interval; the interval is shrunk about the start of the march until that bound is <= 1e-7 (a root shift of
-    // <= 2e-6 MPa at the decision function's slope; measured |f - p| ~ 4e-11, the conditioning of the equispaced samples).  March
-    // decisions use p only where |p| exceeds the bound + a round-off allowance, and any point outside [lo, hi] or closer to zero
-    // than that is evaluated as before (decision_wave on x su): the bracket is the reference's, the root the one brentq finds on p.
-    static constexpr int NS = RAYPOLY_N;
-    struct RayPoly {
-        double c[NS];              // Chebyshev coefficients (wave-uniform)
-        double lo, hi, ua, ub;     // u = ua x + ub maps [lo, hi] to [-1, 1]
-        double margin;             // |p| <= margin: the sign of f is not decided by p
-        bool ok;
-        __device__ __forceinline__ bool covers(double x) const { return ok && x >= lo && x <= hi; }
-        __device__ __forceinline__ double eval(double x) const   // Clenshaw
-        {
-            const double u = fma(ua, x, ub), u2 = u + u;
-            double b1 = 0., b2 = 0.;
-#pragma unroll
-            for (int k = NS - 1; k >= 1; k--) {
-                const double t = fma(u2, b1, c[k] - b2);
-                b2 = b1;
-                b1 = t;
-            }
-            return fma(u, b1, c[0] - b2);
-        }
-    };
-    // tables behind the support-vector tables in dynamic LDS (stage_svc_wave): RAYPOLY_MT, 0.98^i, 1.02^i (i < 64)
-    __device__ __forceinline__ const double *poly_tab() const { return dyn_lds + 9 * npad; }
-    __device__ __forceinline__ void ray_sample(const double *su, double x0, bool halved, RayPoly &P) const
-    {
-        P.ok = false;
-        if (!(WAVE > 0 && NF == 6 && POLY)) return;
-        double D[6];
-        svc_features(m, su, D);
-        double DD = 0.;
-#pragma unroll
-        for (int i = 0; i < 6; i++) DD = fma(D[i], D[i], DD);
-        // the march starts at x0 = sflow and goes down or up, or at x0 = sflow / 2 (material.py:468-473) and goes up
-        double lo = halved ? 0.94 * x0 : 0.72 * x0, hi = halved ? 2.7 * x0 : 1.30 * x0;
-        double dl = (hi - lo) * (1. / (NS - 1));
-        const double q = sqrt(2. * m.gamma * DD);
-        constexpr double KN = 1.0865 * 4574143.623 / (4. * NS);   // K sqrt(16!) / (4 N)
-        static_assert(NS == 16, "KN and the 16th power below are written for 16 samples");
-        double b = q * dl;
-        b *= b; b *= b; b *= b; b *= b;
-        double bound = m.svc_sabs * KN * b;
-        if (!(bound <= RAY_BOUND)) {
-            if (!(bound < 1.e300)) return;
-            const double sh = sqrt(sqrt(sqrt(sqrt(RAY_BOUND / bound))));   // (RAY_BOUND / bound)^(1/16)
-            lo = x0 - (x0 - lo) * sh;
-            hi = x0 + (hi - x0) * sh;
-            dl = (hi - lo) * (1. / (NS - 1));
-            bound = RAY_BOUND;
-        }
-        // the recurrence multiplies by rho_k up to NS - 1 times: keep its exponent range harmless
-        const double sD = sqrt(DD);
-        if (!(2. * m.gamma * dl * (NS - 1) * sD * (sqrt(m.svc_vvmax) + sD * hi) < 60.) || !(hi > lo)) return;
-        const double g = -m.gamma * LOG2E;
-        const double A0 = g * DD * lo * lo, A1 = -2. * g * lo;   // log2(w_k / d_k) = A0 + A1 c_k + g |v_k|^2
-        const double R1 = -2. * g * dl, R0 = -R1 * DD * lo;      // log2 rho_k = R1 c_k + R0
-        double acc[NS];
-#pragma unroll
-        for (int j = 0; j < NS; j++) acc[j] = 0.;
-        PROF_T0(a);
-        for (int k = threadIdx.x & 63; k < npad; k += 64 * NC) {
-            double v[NC][8];
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-#pragma unroll
-                for (int c = 0; c < NC; c++) v[c][i] = dyn_lds[i * npad + k + 64 * c];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int c = 0; c < NC; c++)
-                asm volatile("" : "+v"(v[c][0]), "+v"(v[c][1]), "+v"(v[c][2]), "+v"(v[c][3]), "+v"(v[c][4]), "+v"(v[c][5]),
-                             "+v"(v[c][6]), "+v"(v[c][7]));
-            double w[NC], rho[NC], ea[2 * NC], eo[2 * NC];
-#pragma unroll
-            for (int c = 0; c < NC; c++) {
-                double ck = 0.;
-#pragma unroll
-                for (int i = 0; i < 6; i++) ck = fma(D[i], v[c][i], ck);
-                ea[c] = fma(g, v[c][7], fma(A1, ck, A0));
-                ea[NC + c] = fma(R1, ck, R0);
-            }
-            exp2_neg_n<2 * NC>(ea, eo);
-#pragma unroll
-            for (int c = 0; c < NC; c++) {
-                w[c] = v[c][6] * eo[c];
-                rho[c] = eo[NC + c];
-            }
-#pragma unroll
-            for (int j = 0; j < NS; j++)
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    acc[j] += w[c];
-                    if (j < NS - 1) w[c] *= rho[c];
-                }
-        }
-        PROF_ADD(2, a);
-        // f_j = b + G_j sum_k (...), G_j = 2^(g DD dl^2 j^2) by recurrence: G_{j+1} = G_j t_j, t_{j+1} = t_j G_1^2
-        PROF_T0(b);
-        const double G1 = exp2_neg(g * DD * dl * dl);
-        double G = 1., t = G1;
-        const double r = G1 * G1;
-        const double *tab = poly_tab();
-        const int li = threadIdx.x & (NS - 1);
-        double ci = 0.;   // lane i (mod NS): Chebyshev coefficient i
-#pragma unroll
-        for (int j = 0; j < NS; j++) {
-            const double fj = fma(G, wave_allsum(acc[j]), m.intercept);
-            ci = fma(tab[j * NS + li], fj, ci);
-            G *= t;
-            t *= r;
-        }
-#pragma unroll
-        for (int i = 0; i < NS; i++) P.c[i] = readlane_f64(ci, i);
-        P.lo = lo;
-        P.hi = hi;
-        P.ua = 2. / (hi - lo);
-        P.ub = -(hi + lo) / (hi - lo);
-        P.margin = bound + 4.e-12 * m.svc_sabs;
-        P.ok = true;
-        PROF_ADD(3, b);
-    }
-    __device__ __forceinline__ double decision_wave(const double *s) const
-    {
-        double x[6];
-        svc_features(m, s, x);
-        const double g = -m.gamma * LOG2E;
-        double f[NC];
-#pragma unroll
-        for (int c = 0; c < NC; c++) f[c] = 0.;
-        for_trips([&](double (*v)[7]) {
-            double h[NC];
-#pragma unroll
-            for (int c = 0; c < NC; c++) h[c] = 0.;
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    const double d = x[i] - v[c][i];
-                    h[c] = fma(d, d, h[c]);
-                }
-#pragma unroll
-            for (int c = 0; c < NC; c++) f[c] = fma(v[c][6], exp2_neg(g * h[c]), f[c]);
-        });
-        double t = f[0];
-#pragma unroll
-        for (int c = 1; c < NC; c++) t += f[c];
-        return wave_allsum(t) + m.intercept;
-    }
-    __device__ __forceinline__ void fgrad_wave(const double *s, double *a) const
-    {
-        double x[6], acc[6] = {0., 0., 0., 0., 0., 0.};
-        svc_features(m, s, x);
-        const double g = -m.gamma * LOG2E;
-        for_trips([&](double (*v)[7]) {
-            double h[NC];
-#pragma unroll
-            for (int c = 0; c < NC; c++) h[c] = 0.;
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int c = 0; c < NC; c++) {
-                    v[c][i] = x[i] - v[c][i];
-                    h[c] = fma(v[c][i], v[c][i], h[c]);
-                }
-#pragma unroll
-            for (int c = 0; c < NC; c++) {
-                const double w = v[c][6] * exp2_neg(g * h[c]);
-#pragma unroll
-                for (int i = 0; i < 6; i++) acc[i] = fma(w, v[c][i], acc[i]);
-            }
-        });
-        const double sc = -2. * m.gamma / m.scale_seq;
-#pragma unroll
-        for (int i = 0; i < 6; i++) a[i] = wave_allsum(acc[i]) * sc;
-    }
     __device__ __forceinline__ double decision(const double *s) const
     {
-        if (WAVE) return decision_wave(s);
         return NF == 6 ? svc_decision(m, sv, dual, s) : svc3_decision(m, sv, dual, s);
     }
     __device__ __forceinline__ double plain(const double *s, const double *epl) const
     {
         (void)epl;
         return decision(s);
+    }
+    // decision function at the point x su of the ray
+    __device__ __forceinline__ double ray_eval(const double *su, double x) const
+    {
+        double xs[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) xs[i] = x * su[i];
+        return decision(xs);
     }
     // ML_full_yf (material.py:414-516): distance to the yield locus along the ray through s
     // (ld == nullptr) or along the loading direction ld.
@@ -1166,71 +814,18 @@ struct YfSvcT {
             }
         }
         // find_yloc_scalar (material.py:547-574): f(x) = calc_yf(x*su).  The marching bracket (:468-486) and the
-        // brentq search (:501-503) are driven as one state machine so that f has a single call site (the wave-mode
-        // evaluation is a long unrolled loop).  Evaluation order and arithmetic are those of the straight-line form.
-        RaySetup ray;
-        if (!POLY) ray_setup(su, ray);
+        // brentq search (:501-503) are driven as one state machine so that f has a single call site.  Evaluation order
+        // and arithmetic are those of the straight-line form.
         double x0 = sflow;
         const bool halved = su[0] * su[1] < -1.e-5;
         if (halved) x0 *= 0.5;  // material.py:468-473
-        RayPoly P;
-        ray_sample(su, x0, halved, P);
-#ifdef PLFX_PROF_REGIONS
-        unsigned long long prof_m = __builtin_readcyclecounter();
-#endif
         double x1 = x0, f0 = 0., f1 = 0., xs = 0.;
         bool conv = true;
         BrentState br;
         int phase = 0;  // 0 first point, 1 marching down (:475-480), 2 marching up (:481-486), 3 brentq
         double xq = x0;
         for (;;) {
-            if (POLY && P.ok && (phase == 1 || phase == 2)) {
-                // lane i looks at the i-th next point of the march (i = 0: xq itself): the leading run of points at which
-                // p decides that the march goes on is skipped; the products are then repeated one by one so that the point
-                // the march stops at (a bracket end) carries the reference's rounding
-                const double fac = (phase == 1) ? 0.98 : 1.02;
-                const double z = xq * poly_tab()[NS * NS + (phase == 1 ? 0 : 64) + (threadIdx.x & 63)];
-                const double pv = P.eval(z);
-                const bool on = z >= P.lo && z <= P.hi &&
-                                ((phase == 1) ? (pv > P.margin && z > 0.010000001) : (pv < -P.margin && z < 4.9999999 * sflow));
-                const unsigned long long stop = ~__ballot(on);
-                const int k = stop ? __ffsll((long long)stop) - 1 : 64;
-                double xx = xq;
-                for (int i = 0; i < k; i++) xx *= fac;
-                if (phase == 1) x0 = xx; else x1 = xx;
-                xq = xx;
-                if (k == 64) continue;
-            }
-            if (SCREEN && (phase == 1 || phase == 2)) {  // marching: the sign alone decides whether it goes on
-                double mg;
-                const double fe = ray_screen(ray, xq, mg);
-                if (phase == 1 && fe - mg > 0. && x0 > 0.01) {  // certainly f >= 0: :475-480 marches on
-                    x0 *= 0.98;
-                    xq = x0;
-                    continue;
-                }
-                if (phase == 2 && fe + mg < 0. && x1 < 5. * sflow) {  // certainly f < 0: :481-486 marches on
-                    x1 *= 1.02;
-                    xq = x1;
-                    continue;
-                }
-            }
-            double fq;
-            if (POLY) {
-                bool direct = true;
-                if (P.covers(xq)) {
-                    fq = P.eval(xq);
-                    direct = phase < 3 && fabs(fq) <= P.margin;
-                }
-                if (direct) {
-                    double xs6[6];
-#pragma unroll
-                    for (int i = 0; i < 6; i++) xs6[i] = xq * su[i];
-                    fq = decision(xs6);
-                }
-            } else {
-                fq = ray_eval(su, ray, xq);
-            }
+            const double fq = ray_eval(su, xq);
             if (phase == 0) {
                 f0 = f1 = fq;
                 phase = 1;
@@ -1260,18 +855,11 @@ struct YfSvcT {
                     return seqv - 0.85 * sflow;
                 }
                 phase = 3;
-#ifdef PLFX_PROF_REGIONS
-                if ((threadIdx.x & 63) == 0) atomicAdd(&g_prof[4], (unsigned long long)__builtin_readcyclecounter() - prof_m);
-                prof_m = __builtin_readcyclecounter();
-#endif
                 if (!br.start(x0, x1, f0, f1)) break;
             }
             if (!br.next(1.e-5, 4. * 2.220446049250313e-16, 100)) break;
             xq = br.xcur;
         }
-#ifdef PLFX_PROF_REGIONS
-        if ((threadIdx.x & 63) == 0) atomicAdd(&g_prof[5], (unsigned long long)__builtin_readcyclecounter() - prof_m);
-#endif
         xs = br.root;
         conv = br.converged;
         if (conv && xs < 4. * sflow) return seqv - xs * seq(su);  // material.py:507
@@ -1291,9 +879,7 @@ struct YfSvcT {
     }
     __device__ __forceinline__ void fgrad(const double *s, double *a) const
     {
-        if (WAVE)
-            fgrad_wave(s, a);
-        else if (NF == 6)
+        if (NF == 6)
             svc_fgrad(m, sv, dual, s, a);
         else
             svc3_fgrad(m, sv, dual, s, a);
@@ -1468,16 +1054,14 @@ struct YfSvcWhT {
 };
 
 // ---------------------------------------------------------------------------------------------
-// 6-feature RBF-SVC, SIXTEEN LANES PER MATERIAL POINT (round 5, k_sweep_svc_row / k_full_yf_row).  The wave-per-point
-// form above runs the scalar part of response() -- predictor / corrector algebra, the ray search's control flow, the
-// polynomial evaluations of the sampled-ray form -- redundantly in all 64 lanes, and once the ray search needs one pass over
-// the support vectors instead of thirty that part is half of the instructions of a sub-step.  Here a DPP row (16 lanes)
-// carries one point and a wave four: the support-vector sums cost what they cost before (lane L of a row takes the vectors
-// L, L + 16, ...; the four rows read the same LDS addresses), the scalar part a quarter.  A row is also exactly what the
+// 6-feature RBF-SVC, SIXTEEN LANES PER MATERIAL POINT (round 5, k_sweep_svc_row / k_full_yf_row).  A DPP row (16 lanes)
+// carries one point and a wave four: lane L of a row takes the support vectors L, L + 16, ... (the four rows read the same
+// LDS addresses), and the scalar part of response() -- predictor / corrector algebra, the ray search's control flow, the
+// polynomial evaluations of the sampled-ray form -- runs redundantly in the 16 lanes of a row only.  A row is also exactly what the
 // cross-lane hardware offers without LDS: sums by four DPP butterfly steps inside the row, broadcasts of one lane's value
 // to its row by v_mov_b64_dpp row_newbcast.  Every value that steers control flow is bit-identical in the 16 lanes of a row
 // (same inputs, same operations, commutative butterfly), so rows diverge from each other but never inside.
-// The ray search is the sampled-ray form (see YfSvcT::ray_sample): NS = 16 samples, lane i of the row computes and keeps
+// The ray search is the sampled-ray form (see ray_sample): NS = 16 samples, lane i of the row computes and keeps
 // Chebyshev coefficient i; p(x) is Clenshaw's recurrence with the coefficients broadcast from their lanes.  With 16 lanes a
 // row looks at 16 points per polynomial evaluation:
 //  * the 2 % marching bracket (material.py:475-486): lane i tests the (i+1)-th next point of the march; the leading run of
@@ -1495,7 +1079,7 @@ struct YfSvcRow {
     const MatDev &m;
     int npad;
     __device__ YfSvcRow(const MatDev &mm, int np) : m(mm), npad(np) {}
-    // the tables: dynamic LDS (staged by stage_svc_wave), or the material's copy in device memory (INLDS = false: more support
+    // the tables: dynamic LDS (staged by stage_svc_row), or the material's copy in device memory (INLDS = false: more support
     // vectors than the LDS holds; the 16 lanes of a row read 128 consecutive bytes, the four rows of a wave the same ones)
     __device__ __forceinline__ const double *tabs() const { return INLDS ? dyn_lds : m.rowtab; }
     __device__ __forceinline__ double seq(const double *s) const { return hill_seq(m, s); }
@@ -1644,7 +1228,18 @@ struct YfSvcRow {
         (void)epl;
         return fgrad_impl<true>(s, s2, a);
     }
-    // ---- sampled ray (see YfSvcT::ray_sample for the mathematics and the error bound)
+    // ---- sampled ray.  Along x = t su every kernel term is a Gaussian in t, d_k exp(-gamma (DD t^2 - 2 c_k t + |v_k|^2)), so on
+    // equally spaced points t_j = lo + j dl
+    //   term_k(t_j) = [d_k e^{-gamma h_k(lo)}] rho_k^j e^{-gamma DD dl^2 j^2},   rho_k = e^{2 gamma dl (c_k - DD lo)}:
+    // ONE pass over the support vectors (two exp per vector, then one multiply and one add per sample) yields NS samples of the
+    // decision function, the fixed matrix RAYPOLY_MT turns them into the Chebyshev coefficients of the interpolating polynomial
+    // p on [lo, hi], and the 2 % marching bracket of ML_full_yf (material.py:468-486) and the brentq iterates (:501-503) are
+    // evaluated on p.  f along a ray is entire with length scale 1/sqrt(2 gamma DD):
+    //   |f - p| <= sum|d_k| K sqrt(NS!) / (4 NS) (sqrt(2 gamma DD) dl)^NS          (K = 1.0865: Cramer's bound on Hermite functions)
+    // on the whole interval; the interval is shrunk about the start of the march until that bound is <= RAY_BOUND (a root shift
+    // of <= 2e-6 MPa at the decision function's slope; measured |f - p| ~ 4e-11, the conditioning of the equispaced samples).
+    // March decisions use p only where |p| exceeds the bound + a round-off allowance; any point outside [lo, hi] or closer to
+    // zero than that is evaluated directly.
     struct RowPoly {
         double ci;                 // Chebyshev coefficient (lane & 15) of the interpolant on [lo, hi]
         double lo, hi, ua, ub, margin;
@@ -1893,8 +1488,6 @@ struct YfSvcRow {
 typedef YfSvcWhT<0> YfSvcWh;
 typedef YfSvcT<6> YfSvc;
 typedef YfSvcT<2> YfSvc3;
-template <int NC, bool POLY = false>
-using YfSvcWave = YfSvcT<6, NC, POLY>;
 
 // ---------------------------------------------------------------------------------------------
 // Material.response (material.py:207-346) for one point, in two phases so that the sweep can run

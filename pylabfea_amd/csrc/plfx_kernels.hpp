@@ -19,9 +19,6 @@ constexpr int BLOCK = 256;
 constexpr int MAXMAT = 16;
 constexpr int MAXCLS = 16;
 constexpr int MAXPART = 1024;  // max blocks of a reducing kernel (partials per scalar)
-#ifndef PLFX_HEAVY_THREADS
-#define PLFX_HEAVY_THREADS 512  // threads per workgroup of the wave-per-element SVC corrector: two waves per SIMD at 256 VGPRs + 592 B of scratch beat one wave per SIMD at 424 registers (766 -> 589 ms per 16 x 16384 element updates)
-#endif
 #ifndef PLFX_SWEEP_WAVES
 #define PLFX_SWEEP_WAVES 1  // min waves per SIMD the sweep kernel is compiled for (register budget)
 #endif
@@ -552,7 +549,7 @@ __device__ __forceinline__ void stage_tables(SweepTables &t, const MatDev *gmat,
 // Result flags of a sweep without atomics on one address (4096 per-wave atomics on one cache line cost ~40 us of the
 // streaming sweep): every block adds its counts to its own slot of `bflags` (blocks of consecutive launches on the stream
 // share slots, memset once per sweep), k_sweep_flags reduces the slots after the last launch of the sweep.
-constexpr int SWEEP_SLOTS = 1024;  // >= every sweep grid (grid_xcd / grid_w cap their grids at MAXPART = 1024)
+constexpr int SWEEP_SLOTS = 1024;  // >= every sweep grid (grid_xcd / grid_r cap their grids at MAXPART = 1024)
 static_assert(SWEEP_SLOTS >= MAXPART, "one slot per block of a sweep grid");
 
 __device__ __forceinline__ void post_block_flags(int changed, int nconv, int *__restrict__ bflags)
@@ -767,14 +764,14 @@ k_sweep_heavy(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Wave-per-element variants of the two sweep phases for the 6-feature SVC material `wave_mat` (YfSvcWave): the
-// support-vector sums dominate an SVC update (1585 vectors x tens of yield-function evaluations), so one wave
-// works on one element and splits every sum over its lanes.  Lane 0 stores.  The 50-sub-step list is shared with
-// the thread-per-element kernels (flags[2]).
-__device__ __forceinline__ int stage_svc_wave(const MatDev *smat, int wave_mat, int nc)
+// Support-vector tables of the 6-feature SVC material `mat` in dynamic LDS for the row kernels (YfSvcRow), vectors padded to 64
+// with dual = 0: v[6][npad] at 0, dual[npad] at 6 npad, |v_k|^2 at 7 npad, an unused slot at 8 npad, then the tables of the
+// sampled-ray form at 9 npad (samples -> Chebyshev coefficients, and the march factors 0.98^i / 1.02^i as sequential products).
+// The device-memory copy MatDev::rowtab has the same layout.
+__device__ __forceinline__ int stage_svc_row(const MatDev *smat, int mat)
 {
-    const MatDev &m = smat[wave_mat];
-    const int n = m.nsv, npad = (n + 64 * nc - 1) / (64 * nc) * (64 * nc);
+    const MatDev &m = smat[mat];
+    const int n = m.nsv, npad = (n + 63) / 64 * 64;
     for (int i = threadIdx.x; i < npad; i += blockDim.x) {
 #pragma unroll
         for (int c = 0; c < 6; c++) dyn_lds[c * npad + i] = (i < n) ? m.sv[6 * (size_t)i + c] : 0.;
@@ -784,13 +781,8 @@ __device__ __forceinline__ int stage_svc_wave(const MatDev *smat, int wave_mat, 
 #pragma unroll
             for (int c = 0; c < 6; c++) vv = fma(m.sv[6 * (size_t)i + c], m.sv[6 * (size_t)i + c], vv);
         }
-        dyn_lds[7 * npad + i] = vv;  // |v_k|^2 for the evaluations along a ray (YfSvcT::ray_eval)
-        // FP32 pair (dual, -gamma log2(e) |v_k|^2) for the sign screen of the marching bracket (YfSvcT::ray_screen)
-        reinterpret_cast<float2 *>(dyn_lds + 8 * npad)[i] =
-            make_float2((i < n) ? (float)m.dual[i] : 0.f, (float)(-m.gamma * LOG2E * vv));
+        dyn_lds[7 * npad + i] = vv;
     }
-    // tables of the sampled-ray form (YfSvcT::ray_sample): samples -> Chebyshev coefficients, and the march factors
-    // 0.98^i / 1.02^i as sequential products
     double *ext = dyn_lds + 9 * npad;
     for (int i = threadIdx.x; i < RAYPOLY_N * RAYPOLY_N; i += blockDim.x) ext[i] = RAYPOLY_MT[i];
     if (threadIdx.x < 64) {
@@ -806,100 +798,10 @@ __device__ __forceinline__ int stage_svc_wave(const MatDev *smat, int wave_mat, 
 }
 constexpr int SVC_WAVE_EXTRA = RAYPOLY_N * RAYPOLY_N + 128;   // doubles behind the 9 npad of the support-vector tables
 
-// ML_full_yf on N points, one WAVE per point (round 4): the ray search of YfSvcWave<4> -- support-vector sums split over the
-// lanes, FP32 sign screen of the marching bracket -- on its own needs 210 VGPRs and no scratch at two waves per SIMD (inside the
-// sub-stepping corrector it shares 256 registers + 720 B of scratch with the loop state).  Entry point of plfx_full_yf_batch for the
-// model's 6-feature SVC material (f3's callers: find_yloc / calc_properties / yield-locus grids call it on (N, 6) arrays).
-template <bool POLY>
-__global__ void __launch_bounds__(512)
-k_full_yf_wave(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const double *__restrict__ sig_in,
-               const double *__restrict__ epl_in, const double *__restrict__ ld, double *__restrict__ out, int32_t *__restrict__ status)
-{
-    __shared__ MatDev smat[MAXMAT];
-    stage_materials(smat, gmat, nmat);
-    __syncthreads();
-    const int npad = stage_svc_wave(smat, mat, 4);
-    __syncthreads();
-    const MatDev &m = smat[mat];
-    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
-    double ldv[6];
-    if (ld) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) ldv[c] = ld[c];
-    }
-    for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < n; i += gridDim.x * wpb) {  // wave-uniform
-        double s[6], e[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-            s[c] = sig_in[6 * (size_t)i + c];
-            e[c] = epl_in ? epl_in[6 * (size_t)i + c] : 0.;
-        }
-        const YfSvcWave<4, POLY> yf(m, nullptr, nullptr, npad);
-        int st = 0;
-        const double f = yf.full_ld(s, e, ld ? ldv : nullptr, &st);
-        if (lane == 0) {
-            out[i] = f;
-            if (status) status[i] = st;
-        }
-    }
-}
 
-// Both phases run 512-thread workgroups (8 waves share the LDS tables: 2 waves per SIMD, 256 VGPRs).  HEAVY = 0: 2 vectors per
-// lane and trip; HEAVY = 1: 4, with the FP32 sign screen of the marching bracket -- the sub-stepping loop wants 424 registers
-// and ran one wave per SIMD in round 1; two waves per SIMD with 592 B of scratch are 1.3x faster (PLFX_HEAVY_THREADS).
-template <int HEAVY, bool POLY>
-__global__ void __launch_bounds__(HEAVY ? PLFX_HEAVY_THREADS : 512)
-k_sweep_svc_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
-                 int nel, int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls,
-                 const double2 *__restrict__ du2, const double *__restrict__ sig, const double *__restrict__ epl,
-                 TanStore ts, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
-                 int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, int wave_mat)
-{
-    const int count = HEAVY ? flags[2] : nel;
-    if (count == 0) return;
-    __shared__ SweepTables tb;
-    stage_tables(tb, gmat, nmat, gcls, ncls);
-    __syncthreads();
-    constexpr int NC = HEAVY ? 4 : 2;
-    const int npad = stage_svc_wave(tb.smat, wave_mat, NC);
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wpb = blockDim.x >> 6;
-    const int w = blockIdx.x * wpb + (threadIdx.x >> 6), nw = gridDim.x * wpb;
-    int changed = 0, nconv = 0;
-    for (int i = w; i < count; i += nw) {  // wave-uniform
-        const int e = HEAVY ? list[i] : i;
-        const ClassDev &c = tb.scls[cls[e]];
-        const MatDev &m = tb.smat[c.mat];
-        if (!HEAVY && m.kind == 0 && first_kind && lane == 0) fyn[e] = 0.;  // elastic: skipped by the reference
-        if (c.mat != wave_mat) continue;
-        const size_t ge = (size_t)e + e_off;
-        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
-        class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], deps);
-#pragma unroll
-        for (int k = 0; k < 6; k++) {
-            s[k] = sig[(size_t)k * nel + e];
-            ep[k] = epl[(size_t)k * nel + e];
-        }
-        const YfSvcWave<NC, POLY> yf(m, nullptr, nullptr, npad);
-        const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
-        if (HEAVY) {
-            response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
-            if (lane == 0)
-                sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, Mel, mel_stride, res_sig,
-                               res_depl, fyn, max_steps, nit, changed, nconv);
-        } else if (st == 2) {
-            if (lane == 0) list[atomicAdd(&flags[2], 1)] = e;
-        } else if (lane == 0) {
-            sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, Mel, mel_stride, res_sig, res_depl, fyn,
-                           max_steps, nit, changed, nconv);
-        }
-    }
-    post_block_flags(lane == 0 ? changed : 0, lane == 0 ? nconv : 0, bflags);
-}
-
-// Row-per-element variants (round 5; YfSvcRow): 16 lanes = one DPP row per element, four elements per wave, the ray search in
-// its sampled form.  Same tables in LDS, same two phases, same list and flags as k_sweep_svc_wave; lane 0 of a row stores.
+// Row-per-element variants (round 5; YfSvcRow) for one 6-feature SVC material: 16 lanes = one DPP row per element, four
+// elements per wave, the ray search in its sampled form.  The two sweep phases of k_sweep_svc_row share the 50-sub-step list
+// and the flags with the thread-per-element kernels (flags[2]); lane 0 of a row stores.
 template <bool INLDS>
 __global__ void __launch_bounds__(512)
 k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const double *__restrict__ sig_in,
@@ -908,7 +810,7 @@ k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const d
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
-    const int npad = INLDS ? stage_svc_wave(smat, mat, 1) : smat[mat].rowpad;   // rows take 16 x 4 vectors per trip: padded to 64
+    const int npad = INLDS ? stage_svc_row(smat, mat) : smat[mat].rowpad;   // rows take 16 x 4 vectors per trip: padded to 64
     __syncthreads();
     const MatDev &m = smat[mat];
     const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;
@@ -946,7 +848,7 @@ k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const 
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
-    const int npad = INLDS ? stage_svc_wave(smat, mat, 1) : smat[mat].rowpad;
+    const int npad = INLDS ? stage_svc_row(smat, mat) : smat[mat].rowpad;
     __syncthreads();
     const MatDev &m = smat[mat];
     const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;
@@ -994,7 +896,7 @@ k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
 #define PLFX_ROW_NC 4
 #endif
     constexpr int NC = PLFX_ROW_NC;   // (2: measured 0 % -- see DESIGN 11.5)
-    const int npad = INLDS ? stage_svc_wave(tb.smat, wave_mat, 1) : tb.smat[wave_mat].rowpad;   // rows take 16 x 4 vectors per trip: padded to 64
+    const int npad = INLDS ? stage_svc_row(tb.smat, wave_mat) : tb.smat[wave_mat].rowpad;   // rows take 16 x 4 vectors per trip: padded to 64
     __syncthreads();
     const int l16 = threadIdx.x & 15;
     const int rpb = blockDim.x >> 4;
@@ -2704,7 +2606,7 @@ k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict_
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
-    const int npad = INLDS ? stage_svc_wave(smat, mat, 1) : smat[mat].rowpad;
+    const int npad = INLDS ? stage_svc_row(smat, mat) : smat[mat].rowpad;
     __syncthreads();
     const MatDev &m = smat[mat];
     const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;

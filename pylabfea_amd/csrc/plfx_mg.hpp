@@ -574,8 +574,7 @@ k_sqmr_update_x(int nn, double cd, double cq, const double2 *__restrict__ q, dou
 // ---------------------------------------------------------------------------------------------- GMRES
 // Restarted GMRES with the V-cycle as RIGHT preconditioner: the solver of last resort for indefinite tangent stiffness when
 // the V-cycle built on such an operator is not positive definite either (MINRES needs an SPD preconditioner, GMRES needs
-// nothing).  Minimises the true residual |P(b - K x)|_2, the quantity PCG's stopping test uses.  Classical Gram-Schmidt
-// with re-orthogonalisation, eight basis vectors per pass (coefficients by value).
+// nothing).  Minimises the true residual |P(b - K x)|_2, the quantity PCG's stopping test uses.
 struct Coef8 {
     double c[8];
 };
@@ -583,35 +582,10 @@ struct Ptr8 {
     const double2 *p[8];
 };
 
-// partials of w . V_k, k < n (<= 8), over [own_lo, own_hi): part[k * MAXPART + block]
+// w += sum_k c_k V_k, k < n (<= 8): the solution update at the end of a cycle (coefficients by value)
 __global__ void __launch_bounds__(BLOCK)
-k_gmres_dots(int own_lo, int own_hi, int n, const double2 *__restrict__ w, Ptr8 V, double *__restrict__ part)
+k_gmres_axpy(int nn, int n, double2 *__restrict__ w, Ptr8 V, Coef8 C)
 {
-    __shared__ double sh[BLOCK / 64];
-    double acc[8] = {0., 0., 0., 0., 0., 0., 0., 0.};
-    for (int i = own_lo + blockIdx.x * BLOCK + threadIdx.x; i < own_hi; i += gridDim.x * BLOCK) {
-        const double2 wi = w[i];
-#pragma unroll
-        for (int k = 0; k < 8; k++)
-            if (k < n) {
-                const double2 v = V.p[k][i];
-                acc[k] = fma(wi.x, v.x, fma(wi.y, v.y, acc[k]));
-            }
-    }
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        if (k >= n) break;
-        const double t = block_sum(acc[k], sh);
-        if (threadIdx.x == 0) part[(size_t)k * MAXPART + blockIdx.x] = t;
-    }
-}
-
-// w += sum_k c_k V_k, k < n (<= 8); with norm_part: partials of |w|^2 over [own_lo, own_hi) after the update
-__global__ void __launch_bounds__(BLOCK)
-k_gmres_axpy(int nn, int n, double2 *__restrict__ w, Ptr8 V, Coef8 C, double *__restrict__ norm_part, int own_lo, int own_hi)
-{
-    __shared__ double sh[BLOCK / 64];
-    double acc = 0.;
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < nn; i += gridDim.x * BLOCK) {
         double2 wi = w[i];
 #pragma unroll
@@ -622,11 +596,6 @@ k_gmres_axpy(int nn, int n, double2 *__restrict__ w, Ptr8 V, Coef8 C, double *__
                 wi.y = fma(C.c[k], v.y, wi.y);
             }
         w[i] = wi;
-        if (norm_part && i >= own_lo && i < own_hi) acc = fma(wi.x, wi.x, fma(wi.y, wi.y, acc));
-    }
-    if (norm_part) {
-        const double t = block_sum(acc, sh);
-        if (threadIdx.x == 0) norm_part[blockIdx.x] = t;
     }
 }
 
@@ -642,10 +611,10 @@ k_scale_copy(int nn, double s, const double2 *__restrict__ src, double2 *__restr
     }
 }
 
-// ---- GMRES with delayed re-orthogonalisation (round 6): the basis is read TWICE per iteration instead of four
-// times.  Classical Gram-Schmidt twice (above) makes two projection passes per new vector, each a dots pass + an update pass
-// over the j basis vectors.  Here the second pass of vector j is delayed by one iteration and shares its two sweeps over the
-// basis with the first pass of vector j + 1 (Swirydowicz, Langou, Ananthan, Yang, Thomas 2020; Bielich et al. 2022: "DCGS-2"):
+// ---- Arnoldi with delayed re-orthogonalisation (round 6): the basis is read TWICE per iteration.  Classical
+// Gram-Schmidt twice would make two projection passes per new vector, each a dots pass + an update pass over the j basis
+// vectors; here the second pass of vector j is delayed by one iteration and shares its two sweeps over the basis with the
+// first pass of vector j + 1 (Swirydowicz, Langou, Ananthan, Yang, Thomas 2020; Bielich et al. 2022: "DCGS-2"):
 // with u = the once-projected candidate for q_j and z = A u, ONE dots pass yields s = Q^T u, t = Q^T z, u.u, u.z, and ONE update
 // pass writes q_j = (u - Q s) / alpha and the next candidate (z - Q t) / alpha - e alpha q_j (plfx.hip: gmres_solve has the
 // algebra).  Up to 128 basis vectors per dots launch, all of them in one update launch.

@@ -1,4 +1,4 @@
-"""ML_full_yf on N points: one wave per point (k_full_yf_wave) against one thread per point (k_point_eval, PLFX_FULL_YF_WAVE=0);
+"""ML_full_yf on N points: 16 lanes per point (k_full_yf_row; one wave per point, k_full_yf_wave, before round 5) against one thread per point (k_point_eval, PLFX_FULL_YF_WAVE=0);
 states = the corrector's: stresses on rays through the yield locus, 0.9 ... 1.3 of the yield stress.  python tools/probes/full_yf_probe.py [N]"""
 import os, sys, time, numpy as np
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..')

@@ -2,10 +2,12 @@
 """Two builds of libplfx.so on the same solves, compared BIT FOR BIT (u, sig, epl, sgl, PCG iterations per solve) -- for
 changes that must not move a number (a kernel rewritten with the same sums in the same order).
 
-    python tools/probes/lib_ab.py pylabfea_amd/libplfx_prev.so pylabfea_amd/libplfx.so
+    python tools/probes/lib_ab.py [--more] pylabfea_amd/libplfx_prev.so pylabfea_amd/libplfx.so
 
 Cases: even mesh with a soft inclusion (fine + coarse generators, the whole V-cycle), odd mesh 201 x 199 (levels with a wider
-last column / row: area-scaled diagonal, k_mg_coarsen_M), non-proportional laminate (per-column widths)."""
+last column / row: area-scaled diagonal, k_mg_coarsen_M), non-proportional laminate (per-column widths).  --more adds config 4's
+6-feature SVC material on 32 x 32 (the row kernels and their 50-sub-step corrector), config 5's J2 + SVC laminate on 128 x 64,
+and a solve on 64 x 64 with three indefinite element tangents that GMRES completes."""
 import hashlib
 import os
 import subprocess
@@ -15,7 +17,7 @@ import warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def child():
+def child(more):
     sys.path.insert(0, ROOT)
     import numpy as np
     import pylabfea_amd as FE
@@ -44,6 +46,61 @@ def child():
             fe.solve(min_step=min_step)
         return digest(fe)
 
+    def svc(name, num=1):
+        z = np.load(os.path.join(ROOT, 'tests', 'golden', 'svc_%s.npz' % name))
+        m = FE.Material(name='ML-' + name, num=num)
+        m.elasticity(CV=z['par_CV'])
+        m.plasticity(sy=float(z['par_sy']), sdim=int(z['par_sdim']))
+        m.set_svc(z['par_sv'], z['par_dual'], float(z['par_intercept']), float(z['par_gamma']),
+                  float(z['par_scale_seq']), dev_only=bool(z['par_dev_only']))
+        return m
+
+    def solve_tension(fe, eps, min_step):
+        fe.bcleft(0.)
+        fe.bcbot(0.)
+        fe.bcright(0., 'force')
+        fe.bctop(eps * fe.leny, 'disp')
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            fe.solve(min_step=min_step)
+        return digest(fe)
+
+    def gmres_case():
+        # three element tangents with negative eigenvalues (one of config 5's, tests/test_gpu_random.py): PCG gives up, GMRES
+        # with the V-cycle of the indefinite operator finishes the solve
+        from pylabfea_amd import _lib
+        os.environ['PLFX_INDEFINITE_SOLVER'] = 'gmres'
+        t = [3.06119e+05, 2.30987e+05, 2.44365e+05, -7.10713e+02, 8.16221e+02, -3.89722e+01, -5.30574e+05, -2.01886e+05,
+             8.08981e+02, -9.29004e+02, 4.43106e+01, 2.03386e+05, -4.23220e+01, 4.86228e+01, -2.33304e+00, 5.81516e+04,
+             1.14637e+01, -5.47451e-01, 5.81484e+04, 6.34734e-01, 5.81615e+04]
+        nx = ny = 64
+        mat = FE.Material()
+        mat.elasticity(E=151220., nu=0.3)
+        fe = FE.Model(dim=2, planestress=False)
+        fe.geom([4.], LY=4.)
+        fe.assign([mat])
+        fe.bcleft(0.)
+        fe.bcbot(0.)
+        fe.bcright(0., 'force')
+        fe.bctop(0.002 * fe.leny, 'disp')
+        fe.mesh(NX=nx, NY=ny)
+        eng = fe._ensure_engine()
+        D = np.tile(fe._element_CV(mat), (fe.Nel, 1, 1))
+        bad = np.zeros((6, 6))
+        bad[np.triu_indices(6)] = t
+        bad = bad + bad.T - np.diag(np.diag(bad))
+        for cx, cy in ((nx // 3, ny // 2), (2 * nx // 3, ny // 4), (nx // 2, (3 * ny) // 4)):
+            D[cx * ny + cy] = bad
+        eng.state_set(_lib.ST_ELSTIFF, D.reshape(fe.Nel, 36))
+        eng.assemble()
+        z, d = np.zeros(2), np.array([0., 0.002 * fe.leny])
+        eng.apply_bc(*fe._bc_data(z, z, z, d, None))
+        it, rr, ok = eng.solve(1e-10, 20000, False)
+        del os.environ['PLFX_INDEFINITE_SOLVER']
+        assert ok and eng.indefinite_info()['by_gmres'] == 1
+        h = hashlib.sha256(np.ascontiguousarray(eng.state_get(_lib.ST_DU), dtype=np.float64).tobytes()).hexdigest()[:16]
+        return h, [it]
+
     out = []
     fe = FE.Model(dim=2, planestress=False)   # three sections, the middle one soft: heterogeneous tangents
     fe.geom([2, 1, 2], LY=5.)
@@ -58,18 +115,39 @@ def child():
     fe.geom([3, 1, 2, 1, 2], LY=9. * 256 / 320)
     fe.assign([ma, mb, ma, mb, ma])
     out.append(('laminate 320x256', finish(fe, 320, 256, 6, 20)))
+    if more:
+        fe = FE.Model(dim=2, planestress=False)   # config 4's schedule: the SVC corrector on every element of the last step
+        fe.geom([4.], LY=4.)
+        fe.assign([svc('hill')])
+        fe.mesh(NX=32, NY=32)
+        d = solve_tension(fe, 0.001, 10)
+        assert fe._engine.svc_info()[0] == 1 and int(np.max(fe._state('max_steps'))) == 49
+        out.append(('svc6 32x32', d))
+        ma = FE.Material(num=1)
+        ma.elasticity(E=200.e3, nu=0.3)
+        ma.plasticity(sy=150., khard=500., sdim=6)
+        fe = FE.Model(dim=2, planestress=False)   # config 5's laminate: J2 and the SVC trained on Barlat / Goss
+        fe.geom([2, 1, 2, 1, 2], LY=8.)
+        mb = svc('gossbarlat', 2)
+        fe.assign([ma, mb, ma, mb, ma])
+        fe.mesh(NX=128, NY=64)
+        out.append(('config 5 laminate 128x64', solve_tension(fe, 0.003, 20)))
+        out.append(('indefinite K 64x64, GMRES', gmres_case()))
     for name, (d, its) in out:
         print('%s|%s|%s' % (name, d, ','.join(map(str, its))))
 
 
 if __name__ == '__main__':
-    if len(sys.argv) == 2 and sys.argv[1] == '--child':
-        child()
+    more = '--more' in sys.argv
+    args = [a for a in sys.argv[1:] if a != '--more']
+    if args == ['--child']:
+        child(more)
         sys.exit(0)
     res = []
-    for lib in sys.argv[1:3]:
+    for lib in args[:2]:
         env = dict(os.environ, PLFX_LIB=os.path.abspath(lib))
-        o = subprocess.run([sys.executable, os.path.abspath(__file__), '--child'], env=env, capture_output=True, text=True)
+        o = subprocess.run([sys.executable, os.path.abspath(__file__), '--child'] + (['--more'] if more else []), env=env,
+                           capture_output=True, text=True)
         if o.returncode:
             print(o.stdout, o.stderr)
             sys.exit(1)
