@@ -188,25 +188,15 @@ int plfx_precond_apply(plfx_ctx *ctx, const double *r, double *z);
  * vectors are written.  Single-GPU hierarchies (no strip). */
 int plfx_precond_bench(plfx_ctx *ctx, int reps, double *us_per_cycle, double *us_coarse);
 /* number of plfx_solve calls so far that PCG could not finish: a direction of negative curvature was met (the tangents of
- * Material.response are not always positive semi-definite, material.py:324-338) and the indefinite-system solver completed
- * the solve from the last iterate (right-preconditioned GMRES by default; PLFX_INDEFINITE_SOLVER=surrogate / minres:
- * preconditioned MINRES, see plfx_indefinite_info) -- the reference's LU does not need definiteness either -- or multigrid-PCG did not
+ * Material.response are not always positive semi-definite, material.py:324-338) and right-preconditioned GMRES completed
+ * the solve from the last iterate -- the reference's LU does not need definiteness either -- or multigrid-PCG did not
  * converge within 300 iterations and Jacobi-PCG took over */
 int plfx_solve_fallbacks(plfx_ctx *ctx, int64_t *count);
-/* The solves with an indefinite tangent stiffness among them (p.Kp <= 0 met by PCG): how many there were, how many were
- * completed by MINRES with the V-cycle of the SPD surrogate operator (PLFX_INDEFINITE_SOLVER=surrogate: every indefinite
- * element matrix -- Kel is PSD iff the 3 x 3 matrix of its stiffness generators is -- shifted by its most negative
- * eigenvalue; uniform structured grids, one GPU or a replicated solve), how many by GMRES (the default; strips; MINRES not
- * converged), the number of surrogate hierarchies built (one per operator that needed it) and the elements shifted in the
- * last one.  Any pointer may be NULL. */
+/* The solves with an indefinite tangent stiffness among them (p.Kp <= 0 met by PCG): how many there were and how many GMRES
+ * completed.  by_minres_surrogate, surrogates_built and elements_shifted are always 0: they counted the MINRES solver on an
+ * SPD surrogate operator, which was removed; the signature is kept.  Any pointer may be NULL. */
 int plfx_indefinite_info(plfx_ctx *ctx, int64_t *solves, int64_t *by_minres_surrogate, int64_t *by_gmres,
                          int64_t *surrogates_built, int64_t *elements_shifted);
-/* PLFX_INDEFINITE_SOLVER=sqmr (round 5, not the default): SQMR (simplified QMR for symmetric indefinite systems, Freund &
- * Nachtigal 1994) completes such a solve from PCG's last iterate -- the recurrences of preconditioned CG without its positivity
- * requirements plus a quasi-minimal-residual smoothing of the iterates, preconditioned by the V-cycle of the operator as it is
- * (symmetric, not necessarily definite); no Krylov basis.  GMRES continues from SQMR's iterate on a breakdown or when the true
- * residual stalls.  *by_sqmr: solves SQMR completed on its own. */
-int plfx_sqmr_info(plfx_ctx *ctx, int64_t *by_sqmr);
 /* Form of the stiffness operator in plfx_solve / plfx_update_state / plfx_apply_bc: kind 1 (default) applies
  * K matrix-free from the element stiffness generators (Element.calc_Kel never materialised, Model.setupK reduced to
  * the diagonal) wherever plfx_set_grid found a structured grid with one element shape; kind 0 always assembles the

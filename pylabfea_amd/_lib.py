@@ -52,7 +52,7 @@ SYMBOLS = [
     'plfx_load_step', 'plfx_set_strip', 'plfx_strip_info', 'plfx_allreduce_host',
     'plfx_response_batch_kh', 'plfx_fgrad_batch_wh', 'plfx_timing_sample', 'plfx_solve_fallbacks', 'plfx_comm_selftest',
     'plfx_indefinite_info', 'plfx_pattern_selftest', 'plfx_precond_bench', 'plfx_set_wh_mode', 'plfx_wh_info', 'plfx_wh_carry', 'plfx_set_mesh_structured',
-    'plfx_svc_info', 'plfx_sqmr_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
+    'plfx_svc_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide',
 ]
@@ -439,12 +439,6 @@ class Context(object):
         self._chk(self.lib.plfx_sweep_info(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def sqmr_info(self):
-        """solves with an indefinite tangent stiffness that SQMR completed on its own (plfx_indefinite_info counts all of them)"""
-        a = C.c_int64()
-        self._chk(self.lib.plfx_sqmr_info(self.h, C.byref(a)))
-        return a.value
-
     def svc_info(self):
         """(bit mask of the 6-feature SVC materials on the 16-lanes-per-element kernels, mask of those run one thread per
         element, sweep launches of either form) since the context was created"""
@@ -512,8 +506,8 @@ class Context(object):
         return n.value
 
     def indefinite_info(self):
-        """dict: solves with an indefinite tangent stiffness, how they were completed (MINRES with the surrogate V-cycle /
-        GMRES), surrogate hierarchies built, elements replaced in the last one (plfx_indefinite_info)"""
+        """dict: solves with an indefinite tangent stiffness and how many GMRES completed (plfx_indefinite_info;
+        by_minres_surrogate, surrogates_built and elements_shifted are always 0)"""
         v = [C.c_int64() for _ in range(5)]
         self._chk(self.lib.plfx_indefinite_info(self.h, *[C.byref(x) for x in v]))
         return dict(zip(('solves', 'by_minres_surrogate', 'by_gmres', 'surrogates_built', 'elements_shifted'),

@@ -290,24 +290,13 @@ struct plfx_ctx {
     int fin_pin_n = 0;
     int fin_defer = -1;             // slot the next plfx_finish_step posts into instead of waiting
     int mg_fallbacks = 0; // solves that fell back from multigrid- to Jacobi-PCG
-    int n_minres = 0;     // solves completed by MINRES (indefinite tangent stiffness)
-    double *mr_r1 = nullptr, *mr_w = nullptr;  // MINRES work vectors (allocated on first use)
+    int n_indefinite = 0; // solves with an indefinite tangent stiffness (PCG met negative curvature, GMRES completed them)
     std::vector<double *> gm_blk;                // GMRES: Krylov basis in blocks of GMRES_BLK vectors, allocated as a cycle grows into them
     double *gm_part = nullptr;                   //        partial sums, on first use
     double *gm_part2 = nullptr, *gm_red = nullptr, *gm_coef = nullptr;   // delayed re-orthogonalisation: partials of all columns, their sums, coefficients
     long long n_gmres_its = 0;
     int n_gmres = 0, gm_m = 0;
     double *fuse_rz = nullptr;  // != null during a V-cycle of the PCG loop: the last fine-level post-smoothing launch writes the r.z partials here
-    // SPD surrogate of an indefinite operator (k_make_surrogate): generators with every indefinite element's 3 x 3 generator
-    // matrix shifted by its most negative eigenvalue, the diagonal / Jacobi scaling of that operator; while sur_active the V-cycle (level 0 and every level
-    // below it) is built on the surrogate, the Krylov method applies the true operator
-    double *Msur = nullptr, *diag_sur = nullptr, *dinv_sur = nullptr;
-    int *sur_cnt = nullptr;
-    bool sur_active = false;
-    int n_sur = 0;             // surrogate hierarchies built
-    long long sur_replaced = 0; // elements replaced in the last one
-    int n_sur_minres = 0;      // solves MINRES completed with the surrogate V-cycle
-    int n_sqmr = 0;            // solves SQMR completed (the default indefinite-system solver)
     bool strip_jacobi = false;  // strip-local engine during such a fall-back: the V-cycle is replaced by z = D^-1 r
     int grid_nodes = 0, grid_el = 0;
 
@@ -817,7 +806,6 @@ bool build_pattern(int nnode, const int32_t *conn, int el_begin, int el_end, std
 void mg_graph_drop(plfx_ctx *c);
 int strip_coarse(plfx_ctx *c);
 void strip_free(plfx_ctx *c);
-void surrogate_drop(plfx_ctx *c);
 
 void free_mesh(plfx_ctx *c)
 {
@@ -863,8 +851,6 @@ void free_mesh(plfx_ctx *c)
     dfree(c->pred_x);
     dfree(c->pred_d);
     c->pred_valid = false;
-    dfree(c->mr_r1);
-    dfree(c->mr_w);
     for (auto &b : c->gm_blk) dfree(b);
     c->gm_blk.clear();
     c->gm_m = 0;
@@ -872,11 +858,6 @@ void free_mesh(plfx_ctx *c)
     dfree(c->gm_part2);
     dfree(c->gm_red);
     dfree(c->gm_coef);
-    dfree(c->Msur);
-    dfree(c->diag_sur);
-    dfree(c->dinv_sur);
-    dfree(c->sur_cnt);
-    c->sur_active = false;
     dfree(c->p[0]);
     dfree(c->p[1]);
     for (auto &L : c->mg) {
@@ -2720,7 +2701,6 @@ int plfx_set_grid(plfx_ctx *c, int nx, int ny)
         return fail(c, PLFX_ERR_ARG, "grid %dx%d does not match the mesh", nx, ny);
     if (c->strip.on)  // the hierarchy, halo analysis and coarse child context of a strip belong to the grid they were set up for
         return fail(c, PLFX_ERR_STATE, "plfx_set_grid after plfx_set_strip: call plfx_set_mesh again");
-    c->sur_active = false;  // the levels are rebuilt below: level 0 points at the true operator again
     const int nrow = ny + 1;
     const bool known = c->hint_nx == nx && c->hint_ny == ny;   // written by plfx_set_mesh_structured: nothing to verify
     for (int e = 0; e < c->nel_total && !known; e++) {  // model.py:935-948
@@ -3161,22 +3141,15 @@ int plfx_precond_info(plfx_ctx *c, int *kind, int *levels)
     return PLFX_OK;
 }
 
-int plfx_sqmr_info(plfx_ctx *c, int64_t *by_sqmr)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (by_sqmr) *by_sqmr = c->n_sqmr;
-    return PLFX_OK;
-}
-
 int plfx_indefinite_info(plfx_ctx *c, int64_t *solves, int64_t *by_minres_surrogate, int64_t *by_gmres, int64_t *surrogates_built,
                          int64_t *elements_shifted)
 {
     if (!c) return PLFX_ERR_ARG;
-    if (solves) *solves = c->n_minres;
-    if (by_minres_surrogate) *by_minres_surrogate = c->n_sur_minres;
+    if (solves) *solves = c->n_indefinite;
+    if (by_minres_surrogate) *by_minres_surrogate = 0;
     if (by_gmres) *by_gmres = c->n_gmres;
-    if (surrogates_built) *surrogates_built = c->n_sur;
-    if (elements_shifted) *elements_shifted = c->sur_replaced;
+    if (surrogates_built) *surrogates_built = 0;
+    if (elements_shifted) *elements_shifted = 0;
     return PLFX_OK;
 }
 
@@ -3253,7 +3226,7 @@ int plfx_precond_bench(plfx_ctx *c, int reps, double *us_per_cycle, double *us_c
 int plfx_solve_fallbacks(plfx_ctx *c, int64_t *count)
 {
     if (!c || !count) return PLFX_ERR_ARG;
-    *count = (int64_t)c->mg_fallbacks + c->n_minres;
+    *count = (int64_t)c->mg_fallbacks + c->n_indefinite;
     return PLFX_OK;
 }
 
@@ -3430,7 +3403,6 @@ int plfx_assemble(plfx_ctx *c)
         c->n_reuse_assemble++;
         return PLFX_OK;
     }
-    surrogate_drop(c);  // the hierarchy is rebuilt from the new generators below
     EvPair *ev;
     tim_begin(c, 3, &ev);
     if (matfree(c)) {  // operators are applied from the generators: only the diagonal is formed
@@ -3618,13 +3590,11 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
                        fext ? c->fext : nullptr, c->kw, c->diag, c->is_presc, c->rhs, c->dinv);
     HIPCHK(c, hipGetLastError());
     if (fext) HIPCHK(c, stream_sync(c));
-    if (c->sur_active)  // level 0 of the V-cycle runs on the surrogate operator: its Jacobi scaling with the new mask
-        hipLaunchKernelGGL(k_dinv_masked, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->diag_sur, c->dinv, c->dinv_sur);
     if (mg_active(c)) {
         if (c->mg_pending)
-            c->mg_pending_same = c->mg_pending_same && same_set && !c->sur_active;
+            c->mg_pending_same = c->mg_pending_same && same_set;
         else {
-            rc = mg_update_dinv(c, same_set && !c->sur_active);
+            rc = mg_update_dinv(c, same_set);
             if (rc) return rc;
         }
     }
@@ -4051,61 +4021,6 @@ int host_sums(plfx_ctx *c, double *part, int nslots, int gn, double *out)
 
 // Right-preconditioned restarted GMRES on P K P x = P b from the iterate in c->x (see plfx_mg.hpp): x = x0 + B t with t in the
 // Krylov space of K B.  Returns 0 = |P(b - K x)| <= rtol |b|, 1 = iteration limit, < 0 = error.
-// Level 0 of the V-cycle back on the true operator (called before the hierarchy is rebuilt from new generators)
-void surrogate_drop(plfx_ctx *c)
-{
-    if (!c->sur_active) return;
-    auto &L0 = c->mg[0];
-    L0.op.M = c->Mop;
-    L0.diag = c->diag;
-    L0.dinv = c->dinv;
-    c->sur_active = false;
-}
-
-// Rebuild the multigrid hierarchy on the SPD surrogate of the current operator (see k_make_surrogate).  *replaced = number
-// of elements whose generators were shifted (0: the operator's element matrices are all PSD -- nothing was changed).
-int surrogate_build(plfx_ctx *c, long long *replaced)
-{
-    *replaced = 0;
-    if (!matfree(c) || !mg_active(c) || c->strip.on || !c->assembled) return 0;
-    int rc;
-    const size_t ne = c->nel_total, nd = c->ndof;
-    const int g = grid_for(ne);
-    if (!c->Msur && (rc = dalloc(c, &c->Msur, 6 * ne))) return rc;
-    if (!c->diag_sur && (rc = dalloc(c, &c->diag_sur, nd))) return rc;
-    if (!c->dinv_sur && (rc = dalloc(c, &c->dinv_sur, nd))) return rc;
-    if (!c->sur_cnt && (rc = dalloc(c, &c->sur_cnt, (size_t)1024))) return rc;
-    hipLaunchKernelGGL(k_make_surrogate, dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->dcls, (int)ne, c->dcls_all, c->Mop,
-                       c->Msur, c->sur_cnt);
-    HIPCHK(c, hipGetLastError());
-    std::vector<int> h(g);
-    HIPCHK(c, hipMemcpyAsync(h.data(), c->sur_cnt, (size_t)4 * g, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    long long nb = 0;
-    for (int v : h) nb += v;
-    *replaced = nb;
-    if (nb == 0) return 0;
-    auto &L0 = c->mg[0];
-    KOp sop = c->op;
-    sop.M = c->Msur;
-    // diagonal of the surrogate + generators of level 1, then the coarser levels, Jacobi scalings and the coarse inverse
-    LAUNCH_SETUP(1, sop,
-                       (double2 *)c->diag_sur, (double *)nullptr, level_plain(c->mg[0]) ? c->mg[1].Mel : (double *)nullptr,
-                       (const double2 *)nullptr, 0, 0, (double2 *)nullptr);
-    hipLaunchKernelGGL(k_dinv_masked, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->diag_sur, c->dinv, c->dinv_sur);
-    HIPCHK(c, hipGetLastError());
-    L0.op.M = c->Msur;
-    L0.diag = c->diag_sur;
-    L0.dinv = c->dinv_sur;
-    c->sur_active = true;
-    c->mg_pending = false;   // (set up right here, on the surrogate)
-    if ((rc = mg_assemble(c))) return rc;
-    if ((rc = mg_update_dinv(c, false))) return rc;
-    c->n_sur++;
-    c->sur_replaced = nb;
-    return 0;
-}
-
 constexpr int GMRES_BLK = 32;  // basis vectors per allocation
 constexpr int GMRES_M = 1200;      // restart length (round 6): restarts stall on indefinite K -- a solve that needs 500 iterations took three cycles of
                                    // 400 (1176 iterations) or none at all (residual stuck at 1e-6 after the first restart, profiles/r07e_*); with
@@ -4344,253 +4259,6 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
         }
         HIPCHK(c, hipGetLastError());
         // next cycle starts from the true residual of x (and ends the solve if it is small enough)
-    }
-}
-
-// Preconditioned MINRES on P K P x = P b from the iterate in c->x (see plfx_mg.hpp).  Returns 0 = converged to
-// |r| <= rtol |b| (true residual, checked whenever the recurrence says so), 1 = iteration limit, 2 = the preconditioner is
-// not positive definite on this system or the recurrences stalled (the caller continues with GMRES), < 0 = error.
-int minres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
-{
-    const size_t nd = c->ndof;
-    const int nn = c->nnode, gn = c->grid_nodes;
-    const int olo = own_lo(c), ohi = own_hi(c);
-    int rc;
-    if (!c->mr_r1 && (rc = dalloc(c, &c->mr_r1, nd))) return rc;
-    if (!c->mr_w && (rc = dalloc(c, &c->mr_w, nd))) return rc;
-    double *P0 = c->part, *P_rz = c->part + 3 * MAXPART, *P_rr = c->part + 4 * MAXPART, *P_bb = c->part + 5 * MAXPART;
-    bool use_mg = mg_active(c);
-    int itn = 0;
-    double bb = 0., rr = 0.;
-    auto precond = [&](double *rz_out) -> int {  // z = M^-1 r, r.z
-        int e;
-        if (c->strip.on && (e = halo_refresh(c, c->r))) return e;
-        if (use_mg) {
-            if ((e = mg_vcycle(c))) return e;
-        } else {
-            hipLaunchKernelGGL(k_jacobi_z, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, (const double2 *)c->dinv,
-                               (const double2 *)c->r, (double2 *)c->z, c->sc);
-        }
-        hipLaunchKernelGGL(k_dot_rz, dim3(gn), dim3(BLOCK), 0, c->stream, olo, ohi, (const double2 *)c->r, (const double2 *)c->z, P0);
-        HIPCHK(c, hipGetLastError());
-        return host_sums(c, P0, 1, gn, rz_out);
-    };
-    auto true_resid = [&](double *out) -> int {
-        LAUNCH_OP1(k_resid_norm, matfree(c), dim3(gn), c->op, nn, (const double2 *)c->x, (const double2 *)c->rhs,
-                   (const double2 *)c->dinv, P0, olo, ohi);
-        HIPCHK(c, hipGetLastError());
-        return host_sums(c, P0, 1, gn, out);
-    };
-restart:
-    // r2 = P (b - K x) in c->r
-    LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
-               (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, P_rz, P_rr, P_bb, olo, ohi);
-    HIPCHK(c, hipGetLastError());
-    {
-        double o[3];
-        if ((rc = host_sums(c, P_rz, 3, gn, o))) return rc;
-        rr = o[1];
-        bb = o[2];
-    }
-    hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, P_bb, gn, rtol, c->sc);  // clears the sticky done flag
-    const double tol2 = rtol * rtol * bb;
-    double rl = bb > 0. ? std::sqrt(rr / bb) : 0.;
-    if (rr <= tol2) {
-        if (iters) *iters = itn;
-        if (relres) *relres = rl;
-        return 0;
-    }
-    double rz;
-    if ((rc = precond(&rz))) return rc;
-    if (!(rz > 0.)) {  // the preconditioner built on this operator is not positive definite: GMRES does not need that
-        if (getenv("PLFX_SOLVE_DEBUG")) fprintf(stderr, "[minres] r.Br = %.3e <= 0 at the start\n", rz);
-        if (iters) *iters = itn;
-        if (relres) *relres = rl;
-        return 2;
-    }
-    {
-        HIPCHK(c, hipMemsetAsync(c->mr_w, 0, 8 * nd, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->p[1], 0, 8 * nd, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->mr_r1, 0, 8 * nd, c->stream));
-        const double beta1 = std::sqrt(rz), rr0 = rr;
-        double beta = beta1, oldb = 0., dbar = 0., epsln = 0., phibar = beta1, cs = -1., sn = 0.;
-        double *v = c->p[0], *w1 = c->mr_w, *w2 = c->p[1];  // w1 = oldest direction
-        double last_rl = 1e300;
-        int stalled = 0;
-        double check_at = 1.;  // true-residual check once the estimate (phibar / beta1) sqrt(rr0) falls below check_at * rtol |b|
-        int first = 1;
-        while (itn < maxit) {
-            itn++;
-            double o2[2];
-            LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1. / beta, (const double2 *)c->z, (const double2 *)c->dinv,
-                       (const double2 *)c->mr_r1, (double2 *)v, (double2 *)c->q, P0, P0 + MAXPART, olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            if ((rc = host_sums(c, P0, 2, gn, o2))) return rc;
-            const double c1 = first ? 0. : beta / oldb;
-            const double alfa = o2[0] - c1 * o2[1];
-            hipLaunchKernelGGL(k_minres_update1, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, alfa / beta, c1,
-                               (const double2 *)c->q, (double2 *)c->r, (double2 *)c->mr_r1);
-            first = 0;
-            if ((rc = precond(&rz))) return rc;
-            if (rz < 0. && rz < -1e-14 * beta * beta) {  // preconditioner not positive definite on this Krylov space
-                if (getenv("PLFX_SOLVE_DEBUG")) fprintf(stderr, "[minres] r.Br = %.3e < 0 in iteration %d\n", rz, itn);
-                if (iters) *iters = itn;
-                if (relres) *relres = rl;
-                return 2;  // the iterate so far is kept: GMRES continues from it
-            }
-            oldb = beta;
-            beta = std::sqrt(std::max(rz, 0.));
-            const double oldeps = epsln;
-            const double delta = cs * dbar + sn * alfa;
-            const double gbar = sn * dbar - cs * alfa;
-            epsln = sn * beta;
-            dbar = -cs * beta;
-            double gamma = std::sqrt(gbar * gbar + beta * beta);
-            if (!(gamma > 0.)) gamma = 1e-300;
-            cs = gbar / gamma;
-            sn = beta / gamma;
-            const double phi = cs * phibar;
-            phibar = sn * phibar;
-            hipLaunchKernelGGL(k_minres_update2, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, oldeps, delta, 1. / gamma, phi,
-                               (const double2 *)v, (double2 *)w1, (const double2 *)w2, (double2 *)c->x);
-            std::swap(w1, w2);  // the direction just written is the newest one: next w2
-            HIPCHK(c, hipGetLastError());
-            const double est2 = (phibar / beta1) * (phibar / beta1) * rr0;
-            if (est2 <= check_at * check_at * tol2 || beta == 0. || itn == maxit) {
-                if ((rc = true_resid(&rr))) return rc;
-                rl = bb > 0. ? std::sqrt(rr / bb) : 0.;
-                if (rr <= tol2) {
-                    if (iters) *iters = itn;
-                    if (relres) *relres = rl;
-                    return 0;
-                }
-                if (getenv("PLFX_SOLVE_DEBUG")) fprintf(stderr, "[minres] iteration %d (%s): estimate %.3e, true relative residual %.3e\n", itn, use_mg ? "V-cycle" : "Jacobi", std::sqrt(est2 / (bb > 0. ? bb : 1.)), rl);
-                if (beta == 0.) goto restart;  // Krylov space exhausted short of the tolerance (rounding): again from here
-                if (rl > 0.7 * last_rl && ++stalled >= 2) {  // the recurrences have lost their orthogonality: no further progress
-                    if (iters) *iters = itn;
-                    if (relres) *relres = rl;
-                    return 2;
-                }
-                last_rl = rl;
-                check_at = 0.5 * std::sqrt(est2 / tol2);  // the norms differ: ask for half of the present estimate
-            }
-        }
-    }
-    if (iters) *iters = itn;
-    if (relres) *relres = rl;
-    return 1;
-}
-
-// Preconditioned SQMR on P K P x = P b from the iterate in c->x (see plfx_mg.hpp).  Returns 0 = converged to |r| <= rtol |b|
-// (true residual), 1 = iteration limit, 2 = breakdown (p.Kp = 0 or r.Br = 0) or the recurrences stalled short of the tolerance
-// (the caller continues with GMRES from the iterate), < 0 = error.
-int sqmr_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
-{
-    const size_t nd = c->ndof;
-    const int nn = c->nnode, gn = c->grid_nodes;
-    const int olo = own_lo(c), ohi = own_hi(c);
-    int rc;
-    if (!c->mr_w && (rc = dalloc(c, &c->mr_w, nd))) return rc;
-    double *P0 = c->part, *P_rz = c->part + 3 * MAXPART, *P_rr = c->part + 4 * MAXPART, *P_bb = c->part + 5 * MAXPART;
-    const bool use_mg = mg_active(c);
-    const bool dbg = getenv("PLFX_SOLVE_DEBUG") != nullptr;
-    int itn = 0, restarts = 0;
-    double bb = 0., rr = 0., rl = 0., last_rl = 1e300;
-    auto precond = [&](double *rz_out) -> int {  // z = B r, r.z
-        int e;
-        if (c->strip.on && (e = halo_refresh(c, c->r))) return e;
-        if (use_mg) {
-            if ((e = mg_vcycle(c))) return e;
-        } else {
-            hipLaunchKernelGGL(k_jacobi_z, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, (const double2 *)c->dinv,
-                               (const double2 *)c->r, (double2 *)c->z, c->sc);
-        }
-        hipLaunchKernelGGL(k_dot_rz, dim3(gn), dim3(BLOCK), 0, c->stream, olo, ohi, (const double2 *)c->r, (const double2 *)c->z, P0);
-        HIPCHK(c, hipGetLastError());
-        return host_sums(c, P0, 1, gn, rz_out);
-    };
-    auto finish = [&](int code) {
-        if (iters) *iters = itn;
-        if (relres) *relres = rl;
-        return code;
-    };
-    for (;;) {
-        // r = P (b - K x) in c->r
-        LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
-                   (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, P_rz, P_rr, P_bb, olo, ohi);
-        HIPCHK(c, hipGetLastError());
-        double o[3];
-        if ((rc = host_sums(c, P_rz, 3, gn, o))) return rc;
-        rr = o[1];
-        bb = o[2];
-        hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, P_bb, gn, rtol, c->sc);  // clears the sticky done flag
-        const double tol2 = rtol * rtol * bb;
-        rl = bb > 0. ? std::sqrt(rr / bb) : 0.;
-        if (dbg) fprintf(stderr, "[sqmr] (re)start %d at iteration %d: true relative residual %.3e\n", restarts, itn, rl);
-        if (rr <= tol2) return finish(0);
-        if (itn >= maxit) return finish(1);
-        if (restarts > 0 && rl > 0.5 * last_rl) return finish(2);   // a whole leg bought less than a factor of two
-        last_rl = rl;
-        double rho;
-        if ((rc = precond(&rho))) return rc;
-        if (!(rho != 0.) || !std::isfinite(rho)) return finish(2);
-        HIPCHK(c, hipMemsetAsync(c->mr_w, 0, 8 * nd, c->stream));   // d
-        double tau = std::sqrt(rr), theta = 0., beta = 0.;
-        double *qo = c->p[1], *qn = c->p[0];   // (beta = 0 in the first iteration: qo is read but does not contribute)
-        HIPCHK(c, hipMemsetAsync(qo, 0, 8 * nd, c->stream));
-        double check_at = 1.;
-        int leg = 0, worse = 0;
-        double best_tau = tau;
-        bool again = false;
-        while (itn < maxit) {
-            itn++;
-            leg++;
-            double sigma, rr_n;
-            LAUNCH_OP1(k_sqmr_apply, matfree(c), dim3(gn), c->op, nn, beta, (const double2 *)c->z, (const double2 *)qo,
-                       (const double2 *)c->dinv, (double2 *)qn, (double2 *)c->q, P0, olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            if ((rc = host_sums(c, P0, 1, gn, &sigma))) return rc;
-            if (!(sigma != 0.) || !std::isfinite(sigma)) return finish(2);
-            const double alpha = rho / sigma;
-            hipLaunchKernelGGL(k_sqmr_update_r, dim3(gn), dim3(BLOCK), 0, c->stream, nn, alpha, (const double2 *)c->q, (double2 *)c->r, P0, olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            if ((rc = host_sums(c, P0, 1, gn, &rr_n))) return rc;
-            if (!std::isfinite(rr_n)) return finish(2);
-            const double theta_n = std::sqrt(rr_n) / tau;
-            const double cn2 = 1. / (1. + theta_n * theta_n);
-            tau = tau * theta_n * std::sqrt(cn2);
-            hipLaunchKernelGGL(k_sqmr_update_x, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, cn2 * theta * theta, cn2 * alpha,
-                               (const double2 *)qn, (double2 *)c->mr_w, (double2 *)c->x);
-            HIPCHK(c, hipGetLastError());
-            theta = theta_n;
-            std::swap(qo, qn);
-            // |r_qmr| <= sqrt(leg + 1) tau: look at the true residual when that bound reaches the tolerance (or stops falling)
-            const double est2 = (leg + 1.) * tau * tau;
-            if (tau < best_tau) best_tau = tau, worse = 0;
-            else worse++;
-            if (est2 <= check_at * check_at * tol2 || itn == maxit || worse >= 50) {
-                LAUNCH_OP1(k_resid_norm, matfree(c), dim3(gn), c->op, nn, (const double2 *)c->x, (const double2 *)c->rhs,
-                           (const double2 *)c->dinv, P0, olo, ohi);
-                HIPCHK(c, hipGetLastError());
-                double rt;
-                if ((rc = host_sums(c, P0, 1, gn, &rt))) return rc;
-                rl = bb > 0. ? std::sqrt(rt / bb) : 0.;
-                if (dbg) fprintf(stderr, "[sqmr] iteration %d: bound %.3e, true relative residual %.3e\n", itn, std::sqrt(est2 / (bb > 0. ? bb : 1.)), rl);
-                if (rt <= tol2) return finish(0);
-                if (worse >= 50 || rt > 100. * est2) {   // the recurrences have drifted from the true residual: start again from it
-                    again = true;
-                    break;
-                }
-                check_at = 0.5 * std::sqrt(est2 / tol2);
-            }
-            double rho_n;
-            if ((rc = precond(&rho_n))) return rc;
-            if (!(rho_n != 0.) || !std::isfinite(rho_n)) return finish(2);
-            beta = rho_n / rho;
-            rho = rho_n;
-        }
-        if (!again) return finish(1);
-        if (++restarts > 6) return finish(2);
     }
 }
 
@@ -4923,63 +4591,15 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
     }
     if (done != 1 && hs.done == 2) {
         // negative curvature met (p.K p <= 0) or a NaN residual: the tangent stiffness is not positive definite (lstsq
-        // correction of Material.response, material.py:324-338) -- the reference's LU solves such systems, so does MINRES
+        // correction of Material.response, material.py:324-338) -- the reference's LU solves such systems, and so does
+        // right-preconditioned GMRES with the V-cycle of the operator as it is (need not be SPD), from PCG's last iterate
         int itm = 0;
         double rl = 0.;
-        // PLFX_INDEFINITE_SOLVER selects what completes such a solve from PCG's last iterate:
-        //   gmres (default)  right-preconditioned GMRES(400) with the V-cycle of the operator as it is (need not be SPD)
-        //   surrogate        the V-cycle rebuilt on the SPD surrogate of the operator (every indefinite element matrix shifted
-        //                    by its most negative eigenvalue, k_make_surrogate) + preconditioned MINRES on the TRUE operator:
-        //                    short recurrences, no Krylov basis; GMRES takes over if MINRES has not converged after 600
-        //                    iterations.  Measured on config 5 at 2048^2: same wall-clock (203 vs 198 s),
-        //                    GMRES still needed in 6 of 63 such solves (48 of 48 with gmres), 22.5 k instead of 16.6 k
-        //                    iterations in total -- an SPD preconditioner leaves the negative eigenvalues of K on the other
-        //                    side of zero, which costs MINRES about a factor of two -- hence not the default
-        //   minres           MINRES with the V-cycle of the indefinite operator itself (not positive definite in about half
-        //                    of config 5's solves: hands over to GMRES after a few wasted iterations)
-        const char *isv = getenv("PLFX_INDEFINITE_SOLVER");
-        //   sqmr (round 5)   simplified QMR with the V-cycle of the operator as it is (symmetric, need not be definite): CG-like
-        //                    short recurrences, no Krylov basis; GMRES takes over from its iterate on a breakdown or stall.
-        //                    Measured on config 5 at 2048^2: 38.2 k instead of 15.9 k iterations (one solve
-        //                    9314), 77.2 instead of 75.1 s, and the stress history leaves the other meshes' in the fifth digit
-        //                    (144.123 against 144.134; reference 8 x 4: 144.135) -- not the default
-        const int imode = !isv ? 1 : (!strcmp(isv, "surrogate") ? 0 : (!strcmp(isv, "minres") ? 2 : (!strcmp(isv, "sqmr") ? 3 : 1)));
-        int rcm = 2;
-        if (imode == 0) {
-            long long nrep = c->sur_replaced;
-            if (!c->sur_active && (rc = surrogate_build(c, &nrep))) return rc;
-            if (solve_debug) fprintf(stderr, "[plfx_solve] surrogate preconditioner %s: %lld indefinite element matrices shifted\n",
-                                    c->sur_active ? "active" : "not built", nrep);
-            if (c->sur_active) {
-                // capped: GMRES takes over from MINRES's iterate when the short recurrences do not get there
-                static const int sur_cap = getenv("PLFX_SURROGATE_MAXIT") ? std::max(1, atoi(getenv("PLFX_SURROGATE_MAXIT"))) : 600;
-                rcm = minres_solve(c, rtol, std::min(maxit_all, sur_cap), &itm, &rl);
-                if (rcm < 0) return rcm;
-                if (rcm == 0) c->n_sur_minres++;
-                else rcm = 2;
-                if (solve_debug) fprintf(stderr, "[plfx_solve] MINRES (surrogate V-cycle): rc %d, %d iterations, relative residual %.3e\n", rcm, itm, rl);
-            }
-        } else if (imode == 2) {
-            rcm = minres_solve(c, rtol, maxit_all, &itm, &rl);
-            if (rcm < 0) return rcm;
-            if (solve_debug) fprintf(stderr, "[plfx_solve] MINRES: rc %d, %d iterations, relative residual %.3e\n", rcm, itm, rl);
-        }
-        else if (imode == 3) {
-            rcm = sqmr_solve(c, rtol, maxit_all, &itm, &rl);
-            if (rcm < 0) return rcm;
-            if (rcm == 0) c->n_sqmr++;
-            else rcm = 2;   // iteration limit or stall: GMRES continues from the iterate
-            if (solve_debug) fprintf(stderr, "[plfx_solve] SQMR: rc %d, %d iterations, relative residual %.3e\n", rcm, itm, rl);
-        }
-        c->n_minres++;
-        if (rcm == 2) {
-            int itg = 0;
-            rcm = gmres_solve(c, rtol, maxit_all, &itg, &rl);
-            if (rcm < 0) return rcm;
-            c->n_gmres++;
-            itm += itg;
-            if (solve_debug) fprintf(stderr, "[plfx_solve] GMRES(%d): rc %d, %d iterations, relative residual %.3e\n", c->gm_m, rcm, itg, rl);
-        }
+        c->n_indefinite++;
+        const int rcm = gmres_solve(c, rtol, maxit_all, &itm, &rl);
+        if (rcm < 0) return rcm;
+        c->n_gmres++;
+        if (solve_debug) fprintf(stderr, "[plfx_solve] GMRES(%d): rc %d, %d iterations, relative residual %.3e\n", c->gm_m, rcm, itm, rl);
         if (c->strip.on && (rc = halo_refresh(c, c->x))) return rc;
         hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du);
         HIPCHK(c, hipGetLastError());

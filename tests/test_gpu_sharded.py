@@ -448,7 +448,7 @@ def test_bench_config5_option(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# indefinite tangent stiffness on strips: the GMRES / MINRES fall-backs with owned-only sums and halo exchanges
+# indefinite tangent stiffness on strips: the GMRES fall-back with owned-only sums and halo exchanges
 BAD_TANGENT_21 = [3.06119e+05, 2.30987e+05, 2.44365e+05, -7.10713e+02, 8.16221e+02, -3.89722e+01, -5.30574e+05, -2.01886e+05,
                   8.08981e+02, -9.29004e+02, 4.43106e+01, 2.03386e+05, -4.23220e+01, 4.86228e+01, -2.33304e+00, 5.81516e+04,
                   1.14637e+01, -5.47451e-01, 5.81484e+04, 6.34734e-01, 5.81615e+04]
@@ -489,11 +489,10 @@ def indefinite_solve(rank=None, world=None, dist=None):
     return fe, it, fe._nodal(eng.state_get(_lib.ST_DU))
 
 
-def _indef_worker(rank, world, port, solver, q):
+def _indef_worker(rank, world, port, q):
     import torch.distributed as dist
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
-    os.environ['PLFX_INDEFINITE_SOLVER'] = solver
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
         fe, it, du = indefinite_solve(rank, world, dist)
@@ -506,21 +505,20 @@ def _indef_worker(rank, world, port, solver, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('solver', ['gmres', 'minres'])
-def test_strip_indefinite_tangent(solver, monkeypatch):
+# the id keeps the name of the former solver option ('gmres'), so that the history of this case stays comparable
+@pytest.mark.parametrize('world', [2], ids=['gmres'])
+def test_strip_indefinite_tangent(world):
     import torch.multiprocessing as mp
-    world = 2
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = free_port()
-    procs = [ctx.Process(target=_indef_worker, args=(r, world, port, solver, q)) for r in range(world)]
+    procs = [ctx.Process(target=_indef_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
     res = collect(q, procs, world, 300.)
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
-    monkeypatch.setenv('PLFX_INDEFINITE_SOLVER', solver)
     fe, it1, du1 = indefinite_solve()
     nyn = fe.NnodeY
     for r in range(world):

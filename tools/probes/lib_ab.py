@@ -69,7 +69,6 @@ def child(more):
         # three element tangents with negative eigenvalues (one of config 5's, tests/test_gpu_random.py): PCG gives up, GMRES
         # with the V-cycle of the indefinite operator finishes the solve
         from pylabfea_amd import _lib
-        os.environ['PLFX_INDEFINITE_SOLVER'] = 'gmres'
         t = [3.06119e+05, 2.30987e+05, 2.44365e+05, -7.10713e+02, 8.16221e+02, -3.89722e+01, -5.30574e+05, -2.01886e+05,
              8.08981e+02, -9.29004e+02, 4.43106e+01, 2.03386e+05, -4.23220e+01, 4.86228e+01, -2.33304e+00, 5.81516e+04,
              1.14637e+01, -5.47451e-01, 5.81484e+04, 6.34734e-01, 5.81615e+04]
@@ -96,7 +95,6 @@ def child(more):
         z, d = np.zeros(2), np.array([0., 0.002 * fe.leny])
         eng.apply_bc(*fe._bc_data(z, z, z, d, None))
         it, rr, ok = eng.solve(1e-10, 20000, False)
-        del os.environ['PLFX_INDEFINITE_SOLVER']
         assert ok and eng.indefinite_info()['by_gmres'] == 1
         h = hashlib.sha256(np.ascontiguousarray(eng.state_get(_lib.ST_DU), dtype=np.float64).tobytes()).hexdigest()[:16]
         return h, [it]
