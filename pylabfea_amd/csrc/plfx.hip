@@ -2374,6 +2374,10 @@ static int set_mesh_impl(plfx_ctx *c, int nel, int nnode, const int32_t *conn, c
     HIPCHK(c, stream_sync(c));
     c->grid_nodes = grid_xcd(nnode);
     c->grid_el = grid_xcd(nown);
+    // PLFX_SWEEP_BLOCKS=<n> (tests): at most n blocks in the grid of the sweeps and of calc_scf, so that a small mesh runs several passes of the
+    // sweep's tile loop (read per mesh, not once per process)
+    if (const char *cap = getenv("PLFX_SWEEP_BLOCKS"))
+        if (atoi(cap) > 0 && c->grid_el > atoi(cap)) c->grid_el = atoi(cap);
     c->grid_ok = false;
     c->val_valid = false;
     c->op = make_op(c, nnode, nslot, c->dcol, c->dval, 0, 0, nel, c->Mel);
@@ -3893,8 +3897,8 @@ int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
         hipLaunchKernelGGL(k_axpy_uf, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->q, c->u, c->f);
     }
     const int g = grid_for(c->nel, SUMPART);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->dcls, c->nel,
-                       c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
+                       c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
                        c->eps, tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, c->part_g,
                        c->strip.on ? c->strip.eown_lo : 0, c->strip.on ? c->strip.eown_hi : 0x7fffffff);
     const int n = c->fin_n;
@@ -5082,7 +5086,7 @@ int plfx_update_state(plfx_ctx *c)
         hipLaunchKernelGGL(k_axpy_uf, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->q, c->u, c->f);
     }
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
-                       c->dmat, c->dcls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
+                       c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
                        (const double2 *)c->u, c->sig, c->epl, c->eps, tan_store(c), c->res_sig,
                        c->res_depl, c->nonlin ? 1 : 0, (double *)nullptr);
     HIPCHK(c, hipGetLastError());

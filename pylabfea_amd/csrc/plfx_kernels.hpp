@@ -476,13 +476,28 @@ __device__ __forceinline__ void tan_load(const TanStore &ts, int nel, int e, con
     }
 }
 
+// form tag of the stored tangent of element e, with its factors in f[0..6] when the form is TAN_FAC (what sweep_epilogue takes
+// as the old tangent; the 21 entries of a TAN_FULL element are loaded there)
+__device__ __forceinline__ int tan_load_fac(const TanStore &ts, int nel, int e, double *f)
+{
+    const int form = ts.tag[e];
+    if (form == TAN_FAC) {
+#pragma unroll
+        for (int k = 0; k < 7; k++) f[k] = ts.fac[(size_t)k * nel + e];
+    }
+    return form;
+}
+
 // Tail of the per-element sweep (model.py:1343-1357): store the response, yield-function ratio,
 // tangent test ||elstiff - Ct||_F > 1e-3 and tangent / stiffness-generator refresh.
 // The new tangent Ct comes in form `form` (response_light<true>: TAN_CV for st 0 with Ct unused, TAN_FAC for st 1 with the
-// factors in Ct[0..6]; the corrector: TAN_FULL).
+// factors in Ct[0..6]; the corrector: TAN_FULL).  The stored tangent comes as its form tag `oform` and, for TAN_FAC, its
+// factors ofac[0..6], so that a streaming caller can have them in flight long before (k_sweep_light); the 21 entries of a
+// TAN_FULL element (cold path) are loaded here.  omax: the element's max_steps so far.
 __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &m, int e, int nel,
                                                const double *s, const double *ep, const double *depl,
                                                int form, const double *Ct, double fy, int ns, const TanStore &ts,
+                                               int oform, const double *ofac, int omax,
                                                double *Mel, int mel_stride, double *res_sig,
                                                double *res_depl, double *fyn, int32_t *max_steps, int nit,
                                                int &changed, int &nconv, double kh = -1.)
@@ -497,7 +512,12 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
     if (!(f <= YF_TOL * 1.0001)) nconv = 1;  // model.py:1361
     // Frobenius norm of the tangent change over the full 6x6 (model.py:1346)
     double Dold[21], Dnew[21];
-    tan_load(ts, nel, e, m.CV, Dold);
+    if (oform == TAN_FULL) {
+#pragma unroll
+        for (int k = 0; k < 21; k++) Dold[k] = ts.full[(size_t)k * nel + e];
+    } else {
+        tan_expand(oform, m.CV, ofac, Dold);
+    }
     tan_expand(form, m.CV, Ct, Dnew);
     double hh = 0.;
 #pragma unroll
@@ -528,7 +548,39 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
         for (int k = 0; k < 6; k++) Mel[(size_t)k * mel_stride + e] = M[k];
         changed += 1;  // counts the elements whose tangent (and generator) this thread rewrote
     }
-    if (ns > max_steps[e]) max_steps[e] = ns;  // stat_nlin['max_steps'] (model.py:1356)
+    if (ns > omax) max_steps[e] = ns;  // stat_nlin['max_steps'] (model.py:1356)
+}
+
+// What k_sweep_light reads of one element at addresses that depend on the element index alone: class, connectivity, state
+// max_steps, and the stored tangent's tag and factors (loaded whatever the tag says: an unused value is dropped).  All of it is issued
+// in one go, a tile ahead of its use; only the gather of du waits for a load (conn).
+struct SweepIn {
+    int cl, n[4], form, ms;
+    double s[6], ep[6], fac[7];
+};
+
+// e < nel is the predicate of every load: no address beyond the arrays is formed for the tile past the end
+__device__ __forceinline__ void sweep_in_load(SweepIn &in, long long e, int nel, int e_off, const int32_t *__restrict__ cls,
+                                              const int32_t *__restrict__ conn, const double *__restrict__ sig,
+                                              const double *__restrict__ epl, const TanStore &ts,
+                                              const int32_t *max_steps)
+{
+    in = SweepIn{};
+    if (e < nel) {
+        const size_t ge = (size_t)e + e_off;
+        in.cl = cls[e];
+#pragma unroll
+        for (int k = 0; k < 4; k++) in.n[k] = conn[ge * 4 + k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            in.s[k] = sig[(size_t)k * nel + e];
+            in.ep[k] = epl[(size_t)k * nel + e];
+        }
+        in.form = ts.tag[e];
+        in.ms = max_steps[e];
+#pragma unroll
+        for (int k = 0; k < 7; k++) in.fac[k] = ts.fac[(size_t)k * nel + e];
+    }
 }
 
 struct SweepTables {
@@ -641,9 +693,10 @@ __global__ void __launch_bounds__(BLOCK) k_sweep_flags(int *__restrict__ bflags,
 // Material / class tables are staged in LDS (wave-uniform addresses -> broadcast reads); holding them
 // in SGPRs instead (scalar loads + waterfall over classes) was measured 35 % slower (SGPR spills).
 // (KIND 2, principal-stress Hill: two waves per SIMD as before the out-of-line LAPACK replay of sig_princ_general was
-// added -- the call must not cost the streaming path its occupancy; the spills it takes sit on the cold side of that branch)
+// added -- the call must not cost the streaming path its occupancy; the spills it takes sit on the cold side of that branch;
+// KIND 1: 256 VGPRs with the next tile's streams in registers -- the budget of two waves is pinned, not left to chance)
 template <int KIND>
-__global__ void __launch_bounds__(BLOCK, (KIND == 2 && PLFX_SWEEP_WAVES < 2) ? 2 : PLFX_SWEEP_WAVES)
+__global__ void __launch_bounds__(BLOCK, (KIND <= 2 && PLFX_SWEEP_WAVES < 2) ? 2 : PLFX_SWEEP_WAVES)
 k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
               int lds_doubles, int nel, int e_off, const int32_t *__restrict__ conn,
               const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
@@ -665,22 +718,34 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
     }
     int changed = 0, nconv = 0;
     const int nb = gridDim.x;
-    for (int t = xcd_tile(blockIdx.x, nb); t * BLOCK < nel; t += nb) {
+    // The next tile's streams are kept in registers only by the analytic Hill sweep (KIND 1: HBM-bound, 256 VGPRs at two
+    // waves per SIMD); the other kinds, compute-bound or already spilling, load the current tile's at the top of the pass.
+    constexpr bool PREFETCH = (KIND == 1);
+    int t = xcd_tile(blockIdx.x, nb);
+    SweepIn nx;
+    if (PREFETCH) sweep_in_load(nx, (long long)t * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+    for (; t * BLOCK < nel; t += nb) {
         const int e = t * BLOCK + threadIdx.x;
         bool heavy = false;
+        // PREFETCH: the streams of this tile are in flight since the previous pass; those of the thread's next tile go out
+        // now, ahead of the gather of du and the return mapping.  The empty asm statement keeps what follows below the loads
+        // and keeps them from sinking to their first use.  Only the gather waits for a load (conn).
+        if (!PREFETCH) sweep_in_load(nx, (long long)t * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+        const SweepIn in = nx;
+        if (PREFETCH) sweep_in_load(nx, (long long)(t + nb) * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+        asm volatile("" ::: "memory");
         if (e < nel) {
-            const ClassDev &c = tb.scls[cls[e]];
+            const ClassDev &c = tb.scls[in.cl];
             const MatDev &m = tb.smat[c.mat];
             if (m.kind == 0) {  // elastic material: skipped by the reference (model.py:1341, 1358)
                 if (first_kind) fyn[e] = 0.;
             } else if (m.kind == KIND && !((skip_mask >> c.mat) & 1u)) {  // skip_mask: materials handled by the row / wave kernels
-                const size_t ge = (size_t)e + e_off;
                 double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
-                class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], deps);
+                class_strain(c, du2, in.n[0], in.n[1], in.n[2], in.n[3], deps);
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
-                    s[k] = sig[(size_t)k * nel + e];
-                    ep[k] = epl[(size_t)k * nel + e];
+                    s[k] = in.s[k];
+                    ep[k] = in.ep[k];
                 }
                 const bool staged = (c.mat == svc_mat);
                 const typename YfOf<KIND>::type yf =
@@ -689,7 +754,7 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
                 if (st == 2)
                     heavy = true;  // (the corrector kernel repeats the prelude from the same entry modulus)
                 else {
-                    sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, Mel, mel_stride, res_sig,
+                    sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, in.ms, Mel, mel_stride, res_sig,
                                    res_depl, fyn, max_steps, nit, changed, nconv, KIND == 7 ? yf.kh() : -1.);
                     if (KIND == 7 && kh_el) {
                         (kh_out ? kh_out : kh_el)[e] = yf.kh();
@@ -741,7 +806,7 @@ k_sweep_heavy(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
         const MatDev &m = tb.smat[c.mat];
         if (m.kind != KIND || ((skip_mask >> c.mat) & 1u)) continue;
         const size_t ge = (size_t)e + e_off;
-        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
+        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], ofac[7], fy, st_scal;
         class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], deps);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -753,7 +818,7 @@ k_sweep_heavy(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
             make_policy<KIND>(m, staged ? sv : nullptr, staged ? dual : nullptr, (KIND == 7 && kh_el) ? kh_el[e] : m.khard);
         response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);  // recompute the prelude
         response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
-        sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, Mel, mel_stride, res_sig,
+        sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, tan_load_fac(ts, nel, e, ofac), ofac, max_steps[e], Mel, mel_stride, res_sig,
                        res_depl, fyn, max_steps, nit, changed, nconv, KIND == 7 ? yf.kh() : -1.);
         if (KIND == 7 && kh_el) {
             (kh_out ? kh_out : kh_el)[e] = yf.kh();
@@ -909,7 +974,7 @@ k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
         if (!HEAVY && m.kind == 0 && first_kind && l16 == 0) fyn[e] = 0.;  // elastic: skipped by the reference
         if (c.mat != wave_mat) continue;
         const size_t ge = (size_t)e + e_off;
-        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
+        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], ofac[7], fy, st_scal;
         class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], deps);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -921,12 +986,12 @@ k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
         if (HEAVY) {
             response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
             if (l16 == 0)
-                sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, Mel, mel_stride, res_sig,
+                sweep_epilogue(c, m, e, nel, s, ep, depl, TAN_FULL, Ct, fy, MAXIT - 1, ts, tan_load_fac(ts, nel, e, ofac), ofac, max_steps[e], Mel, mel_stride, res_sig,
                                res_depl, fyn, max_steps, nit, changed, nconv);
         } else if (st == 2) {
             if (l16 == 0) list[atomicAdd(&flags[2], 1)] = e;
         } else if (l16 == 0) {
-            sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, Mel, mel_stride, res_sig, res_depl, fyn,
+            sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, tan_load_fac(ts, nel, e, ofac), ofac, max_steps[e], Mel, mel_stride, res_sig, res_depl, fyn,
                            max_steps, nit, changed, nconv);
         }
     }
@@ -966,7 +1031,7 @@ k_sweep_wh_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
         if (!HEAVY && m.kind == 0 && first_kind && lane == 0) fyn[e] = 0.;  // elastic: skipped by the reference
         if (m.kind != 7) continue;
         const size_t ge = (size_t)e + e_off;
-        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
+        double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], ofac[7], fy, st_scal;
         class_strain(c, du2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], deps);
 #pragma unroll
         for (int k = 0; k < 6; k++) {
@@ -982,7 +1047,7 @@ k_sweep_wh_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
             continue;
         }
         if (lane == 0) {
-            sweep_epilogue(c, m, e, nel, s, ep, depl, HEAVY ? TAN_FULL : st, Ct, fy, HEAVY ? MAXIT - 1 : 0, ts, Mel, mel_stride, res_sig, res_depl, fyn,
+            sweep_epilogue(c, m, e, nel, s, ep, depl, HEAVY ? TAN_FULL : st, Ct, fy, HEAVY ? MAXIT - 1 : 0, ts, tan_load_fac(ts, nel, e, ofac), ofac, max_steps[e], Mel, mel_stride, res_sig, res_depl, fyn,
                            max_steps, nit, changed, nconv, yf.kh());
             if (kh_el) {
                 (kh_out ? kh_out : kh_el)[e] = yf.kh();
@@ -2360,48 +2425,69 @@ k_axpy_uf(size_t ndof, const double *__restrict__ du, const double *__restrict__
 }
 
 // element state update at the end of a load step (model.py:1385-1392); u already updated
+// Latency structure as in k_sweep_light: tables in LDS, every stream whose address depends on the element index alone issued
+// at the top of the pass (res_sig / res_depl whenever the step was non-linear, whatever the element's material turns out to
+// be), the gathers of u and du behind conn, and the stores after the last load.
 template <int SUMS>
 __global__ void __launch_bounds__(BLOCK)
-k_update_state(const MatDev *__restrict__ gmat, const ClassDev *__restrict__ gcls, int nel, int e_off, const int32_t *__restrict__ conn,
+k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off, const int32_t *__restrict__ conn,
                const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
                double *__restrict__ eps, TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
                int nonlin, double *__restrict__ part /* SUMS: [18][gridDim.x] volume-weighted sums of the new sig, eps, epl */,
                int sum_lo = 0, int sum_hi = 0x7fffffff /* elements that enter the sums (strip: owned columns) */)
 {
+    __shared__ SweepTables tb;
+    stage_tables(tb, gmat, nmat, gcls, ncls);
+    __syncthreads();
     // SUMS = 1 fuses calc_global's element sums (k_global_partials: same grid, same order -> identical numbers)
     double acc[18];
 #pragma unroll
     for (int k = 0; k < 18; k++) acc[k] = 0.;
     for (int e = blockIdx.x * BLOCK + threadIdx.x; e < nel; e += gridDim.x * BLOCK) {
-        const ClassDev &c = gcls[cls[e]];
-        const MatDev &m = gmat[c.mat];
         const size_t ge = (size_t)e + e_off;
+        const int cl = cls[e];
         const int n0 = conn[ge * 4], n1 = conn[ge * 4 + 1], n2 = conn[ge * 4 + 2], n3 = conn[ge * 4 + 3];
-        double sn[6], pn[6];
+        double po[6], rd[6] = {}, rs[6] = {};
+#pragma unroll
+        for (int k = 0; k < 6; k++) po[k] = epl[(size_t)k * nel + e];
+        if (nonlin) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) {
+                rd[k] = res_depl[(size_t)k * nel + e];
+                rs[k] = res_sig[(size_t)k * nel + e];
+            }
+        }
+        asm volatile("" ::: "memory");  // the loads above may not sink behind the table look-up to their first use
+        const ClassDev &c = tb.scls[cl];
+        const MatDev &m = tb.smat[c.mat];
+        double et[6], sn[6], pn[6];
+        class_strain(c, u2, n0, n1, n2, n3, et);  // el.eps = el.eps_t() (model.py:1392)
         if (m.kind != 0 && nonlin) {  // el.res_sig is set (model.py:1390-1391)
 #pragma unroll
             for (int k = 0; k < 6; k++) {
-                pn[k] = epl[(size_t)k * nel + e] + res_depl[(size_t)k * nel + e];
-                sn[k] = res_sig[(size_t)k * nel + e];
-                epl[(size_t)k * nel + e] = pn[k];
-                sig[(size_t)k * nel + e] = sn[k];
+                pn[k] = po[k] + rd[k];
+                sn[k] = rs[k];
             }
+#pragma unroll
+            for (int k = 0; k < 6; k++) epl[(size_t)k * nel + e] = pn[k];
         } else {  // el.sig += elstiff @ deps ; depl = 0 for elastic materials (model.py:1387-1388)
-            double de[6], D[21], ds[6];
+            double de[6], D[21], ds[6], so[6];
             class_strain(c, du2, n0, n1, n2, n3, de);
+#pragma unroll
+            for (int k = 0; k < 6; k++) so[k] = sig[(size_t)k * nel + e];
             tan_load(ts, nel, e, m.CV, D);
             symv(D, de, ds);
 #pragma unroll
             for (int k = 0; k < 6; k++) {
-                sn[k] = sig[(size_t)k * nel + e] + ds[k];
-                sig[(size_t)k * nel + e] = sn[k];
-                if (SUMS) pn[k] = epl[(size_t)k * nel + e];
+                sn[k] = so[k] + ds[k];
+                pn[k] = po[k];
             }
         }
-        double et[6];
-        class_strain(c, u2, n0, n1, n2, n3, et);  // el.eps = el.eps_t() (model.py:1392)
 #pragma unroll
-        for (int k = 0; k < 6; k++) eps[(size_t)k * nel + e] = et[k];
+        for (int k = 0; k < 6; k++) {
+            sig[(size_t)k * nel + e] = sn[k];
+            eps[(size_t)k * nel + e] = et[k];
+        }
         if (SUMS && e >= sum_lo && e < sum_hi) {
             const double v = c.vel;
 #pragma unroll
