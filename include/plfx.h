@@ -147,6 +147,12 @@ int plfx_response_batch_kh(plfx_ctx *ctx, int n, const int32_t *mat_id, const do
 /* calc_fgrad(sig, epl) of a PLFX_SVC_WH material on n points: gradient w.r.t. the stress and, per point, the raw value
  * -sum_k dK/dx[6+k] * scale_seq / scale_wh whose mean over the points, clipped at 0, the reference stores in khard */
 int plfx_fgrad_batch_wh(plfx_ctx *ctx, int mat, int n, const double *sig, const double *epl, double *fgrad, double *khard_raw);
+/* Material.calc_hessian (material.py:860-972) of an SVC material on n points: the 6x6 block of the feature-space
+ * Hessian of the decision function w.r.t. the stress features, hess[n*36] row-major, symmetric.  epl: NULL or [n*6]
+ * (PLFX_SVC_WH only; NULL = zeros).  The scaling to stress units is the caller's (the reference divides by
+ * scale_seq ONCE, :962).  PLFX_ERR_UNSUPPORTED for every other kind (the reference raises for Hill / Tresca /
+ * Barlat :965-970, NotImplementedError for sdim = 3 :950). */
+int plfx_hessian_batch(plfx_ctx *ctx, int mat, int n, const double *sig, const double *epl, double *hess);
 
 /* Index products of Model.mesh for the reference's structured NX x NY grid, computed on the host (no context, no GPU):
  * conn[NX*NY*4] = [n1, n1+1, n1+NnodeY, n1+NnodeY+1] with n1 = (ih / NY) * NnodeY + ih % NY for element ih = j*NY + k
@@ -420,7 +426,8 @@ int plfx_svc_decision_batch(plfx_ctx *ctx, int n, int d, const double *X, int np
 
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
- * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>), 1 spmv(+dot), 2 cg vector
+ * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

@@ -54,7 +54,7 @@ SYMBOLS = [
     'plfx_indefinite_info', 'plfx_pattern_selftest', 'plfx_precond_bench', 'plfx_set_wh_mode', 'plfx_wh_info', 'plfx_wh_carry', 'plfx_set_mesh_structured',
     'plfx_svc_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
-    'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide',
+    'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
 ]
 
 _lib = None
@@ -274,6 +274,17 @@ class Context(object):
         kh = np.empty(len(sig))
         self._chk(self.lib.plfx_fgrad_batch_wh(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(out), _dp(kh)))
         return out, kh
+
+    def hessian(self, mat, sig, epl=None):
+        """calc_hessian of an SVC material in feature space: (N,6,6), the stress-feature block (plfx_hessian_batch);
+        epl (N,6) enters the features of a work-hardening material only (None: zeros)"""
+        sig = _f64(sig).reshape(-1, 6)
+        epl = None if epl is None else _f64(epl).reshape(-1, 6)
+        if epl is not None and len(epl) != len(sig):
+            raise ValueError('hessian: one plastic strain per stress expected')
+        out = np.empty((len(sig), 6, 6))
+        self._chk(self.lib.plfx_hessian_batch(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(out)))
+        return out
 
     def yf(self, mat, sig, epl=None):
         sig = _f64(sig).reshape(-1, 6)

@@ -1993,6 +1993,8 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_heavy<7>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_wh_wave<0>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_wh_wave<1>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<6>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<15>, bytes));
     }
     c->M_dirty = true;
     c->memo.valid = false;
@@ -2023,12 +2025,15 @@ static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, 
     }
     if (status) HIPCHK(c, hipMalloc((void **)&dst, (size_t)n * 4));
     static const bool wave_full = !(getenv("PLFX_FULL_YF_WAVE") && atoi(getenv("PLFX_FULL_YF_WAVE")) == 0);
+    EvPair *ev;
+    tim_begin(c, 0, &ev);   // family 0 like plfx_response_batch: the kernel alone, without the copies
     if (what == 3 && wave_full && ((c->svc_row_all >> mat) & 1u))  // ML_full_yf of a row-kernel SVC material
         LAUNCH_ROW1(c, mat, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
                    c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
     else
         hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
                            c->dmat, c->nmat, c->svc_lds_need, what, mat, n, dsig, depl, dld, dout, dst);
+    tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 8 * wout, hipMemcpyDeviceToHost, c->stream));
     if (status) HIPCHK(c, hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2198,8 +2203,11 @@ int plfx_fgrad_batch_wh(plfx_ctx *c, int mat, int n, const double *sig, const do
         HIPCHK(c, hipMalloc((void **)&depl, (size_t)n * 48));
         HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
     }
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
     hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat,
                        c->svc_lds_need, 1, mat, n, dsig, depl, (const double *)nullptr, dout, (int32_t *)nullptr, dkh);
+    tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(fgrad, dout, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
     if (khard_raw) HIPCHK(c, hipMemcpyAsync(khard_raw, dkh, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -2207,6 +2215,45 @@ int plfx_fgrad_batch_wh(plfx_ctx *c, int mat, int n, const double *sig, const do
     hipFree(dsig);
     hipFree(dout);
     hipFree(dkh);
+    if (depl) hipFree(depl);
+    return PLFX_OK;
+}
+
+// Material.calc_hessian of an SVC material: sibling of point_eval with 36 numbers per point and the row kernel
+int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *hess)
+{
+    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
+    if (mat < 0 || mat >= c->nmat || n < 0 || !sig || !hess) return fail(c, PLFX_ERR_ARG, "bad argument");
+    const int kind = c->hmat[mat].kind;
+    if (kind != PLFX_SVC6 && kind != PLFX_SVC_WH)
+        return fail(c, PLFX_ERR_UNSUPPORTED, kind == PLFX_SVC3 ? "calc_hessian: not implemented for 3D stress (material.py:950)"
+                    : "calc_hessian: no analytical hessian for this Hill / Tresca / Barlat material (material.py:965-970)");
+    if (n == 0) return PLFX_OK;
+    double *dsig = nullptr, *depl = nullptr, *dout = nullptr;
+    HIPCHK(c, hipMalloc((void **)&dsig, (size_t)n * 48));
+    HIPCHK(c, hipMalloc((void **)&dout, (size_t)n * 288));
+    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+    if (epl && kind == PLFX_SVC_WH) {
+        HIPCHK(c, hipMalloc((void **)&depl, (size_t)n * 48));
+        HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+    }
+    // 64 points per block; a block stages the tables once, so no more blocks than keep every CU busy for a few rounds
+    const int rpb = HESS_BLOCK / 16;
+    const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    if (kind == PLFX_SVC6)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hessian_row<6>), grid, dim3(HESS_BLOCK), dyn_lds_bytes(c), c->stream,
+                           c->dmat, c->nmat, c->svc_lds_need, mat, n, dsig, depl, dout);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hessian_row<15>), grid, dim3(HESS_BLOCK), dyn_lds_bytes(c), c->stream,
+                           c->dmat, c->nmat, c->svc_lds_need, mat, n, dsig, depl, dout);
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(hess, dout, (size_t)n * 288, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    hipFree(dsig);
+    hipFree(dout);
     if (depl) hipFree(depl);
     return PLFX_OK;
 }

@@ -3,6 +3,7 @@
 // Kernels (one wavefront = 64 lanes, blocks of 256 threads = 4 waves, one per SIMD):
 //   k_response_batch  Material.response on N independent points (AoS in/out; façade + parity entry)
 //   k_point_eval      calc_seq / calc_fgrad / calc_yf / ML_full_yf on N points
+//   k_hessian_row     calc_hessian of an SVC material on N points, 16 lanes per point
 //   k_sweep           model.py:1340-1359: strain gather + response + tangent test/refresh, SoA state
 //   k_assemble        model.py:954-977 as a deterministic gather into the block-ELL matrix
 //   k_spmv            q = K p (block-ELL, one thread per node = two rows) [+ fused p update + p.q]
@@ -146,14 +147,14 @@ __device__ __forceinline__ void stage_materials(MatDev *smat, const MatDev *gmat
     for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
 }
 
-// stage the support vectors of the first SVC material into dynamic LDS (if they fit)
+// stage the support vectors of the first SVC material into dynamic LDS (if they fit); only >= 0: of that material or none
 __device__ __forceinline__ void stage_svc(const MatDev *smat, int nmat, double *lds, int lds_doubles,
-                                          int &svc_mat, const double *&sv, const double *&dual, int kind = 0)
+                                          int &svc_mat, const double *&sv, const double *&dual, int kind = 0, int only = -1)
 {
     svc_mat = -1;
     sv = dual = nullptr;
     for (int k = 0; k < nmat; k++)
-        if ((kind ? smat[k].kind == kind : kind_is_svc(smat[k].kind)) &&
+        if ((only < 0 || k == only) && (kind ? smat[k].kind == kind : kind_is_svc(smat[k].kind)) &&
             smat[k].nsv * (smat[k].nfeat + 1) <= lds_doubles) {
             svc_mat = k;
             break;
@@ -389,6 +390,96 @@ k_point_eval(const MatDev *gmat, int nmat, int lds_doubles, int what, int mat, i
             }
             if (status) status[i] = st;
         }
+    }
+}
+
+// Material.calc_hessian (material.py:860-972) of the SVC material `mat` (NF = 6: PLFX_SVC6, NF = 15: PLFX_SVC_WH) on n points:
+// the 6 x 6 block of the Hessian of the decision function w.r.t. the stress features,
+//   Hx[a][b] = sum_i c_i k_i (4 gamma^2 d_i[a] d_i[b] - 2 gamma delta_ab),  d_i = v_i - x,  k_i = exp(-gamma |d_i|^2) over ALL features
+// (the plastic-strain features epl / scale_wh enter the distance; the three trailing ones are zero as everywhere on the path).
+// Lane mapping of the row kernels: 16 lanes (one DPP row) per point, four points per wave, lane L of a row takes the support
+// vectors L, L + 16, ... two per trip (two independent exp2 chains); the 21 unique sums are closed by the DPP butterfly and
+// lanes 0..5 of the row store one matrix row each.  Per vector the loop accumulates w d_a d_b (a < b) and w (d_a^2 - 1/(2 gamma))
+// -- each diagonal term in one piece, as the reference forms it, so that the error stays within a few ulps of the sum of the
+// ABSOLUTE terms (the gauge the tests hold it to) -- and 4 gamma^2 is applied once at the end.  dev_only materials: the
+// features are the deviator's and, like the reference, no chain rule through the projection is applied.
+// Kernel values below 2^-1020 are flushed to zero (the reference keeps subnormals down to 2^-1074).
+constexpr int HESS_BLOCK = 512;   // one block per CU when the tables fill its LDS: 8 waves = 2 per SIMD, two exp2 chains each
+template <int NF>
+__global__ void __launch_bounds__(HESS_BLOCK)
+k_hessian_row(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int mat, int n, const double *__restrict__ sig_in,
+              const double *__restrict__ epl_in, double *__restrict__ out)
+{
+    static_assert(NF == 6 || NF == 15, "6 stress features, or 15 with the work-hardening ones");
+    constexpr int NX = (NF == 15) ? 12 : 6;   // features that vary from point to point
+    __shared__ MatDev smat[MAXMAT];
+    stage_materials(smat, gmat, nmat);
+    __syncthreads();
+    int svc_mat;
+    const double *sv, *dual;
+    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
+    __syncthreads();
+    const MatDev &m = smat[mat];
+    const double *psv = (mat == svc_mat) ? sv : m.sv;
+    const double *pdu = (mat == svc_mat) ? dual : m.dual;
+    const int nsv = m.nsv;
+    const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;
+    const double g = -m.gamma * LOG2E, q = 0.5 / m.gamma, c4 = 4. * m.gamma * m.gamma;
+    for (int i = blockIdx.x * rpb + (threadIdx.x >> 4); i < n; i += gridDim.x * rpb) {  // row-uniform
+        double s[6], x[NX], acc[21];
+#pragma unroll
+        for (int c = 0; c < 6; c++) s[c] = sig_in[6 * (size_t)i + c];
+        svc_features(m, s, x);
+        if (NF == 15) {
+#pragma unroll
+            for (int c = 0; c < 6; c++) x[6 + c] = (epl_in ? epl_in[6 * (size_t)i + c] : 0.) / m.scale_wh;
+        }
+#pragma unroll
+        for (int c = 0; c < 21; c++) acc[c] = 0.;
+        for (int k = l16; k < nsv; k += 32) {
+            const bool two = (k + 16 < nsv);   // the second vector of the trip exists (else: the first again, with weight 0)
+            const int kk[2] = {k, two ? k + 16 : k};
+            double d[2][6], ea[2], eo[2];
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const double *v = psv + (size_t)NF * kk[c];
+                double hh = 0.;
+#pragma unroll
+                for (int f = 0; f < 6; f++) {
+                    d[c][f] = v[f] - x[f];
+                    hh = fma(d[c][f], d[c][f], hh);
+                }
+#pragma unroll
+                for (int f = 6; f < NX; f++) {
+                    const double t = v[f] - x[f];
+                    hh = fma(t, t, hh);
+                }
+#pragma unroll
+                for (int f = NX; f < NF; f++) hh = fma(v[f], v[f], hh);
+                ea[c] = g * hh;
+            }
+            exp2_neg_n<2>(ea, eo);
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const double w = (ea[c] < -1020. || (c == 1 && !two)) ? 0. : pdu[kk[c]] * eo[c];
+#pragma unroll
+                for (int a = 0; a < 6; a++) {
+                    acc[sym_idx(a, a)] = fma(w, fma(d[c][a], d[c][a], -q), acc[sym_idx(a, a)]);
+                    const double wa = w * d[c][a];
+#pragma unroll
+                    for (int b = a + 1; b < 6; b++) acc[sym_idx(a, b)] = fma(wa, d[c][b], acc[sym_idx(a, b)]);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 21; c++) acc[c] = c4 * YfSvcRow<1>::row_allsum(acc[c]);
+        double *H = out + 36 * (size_t)i;
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+            if (l16 == r) {
+#pragma unroll
+                for (int c = 0; c < 6; c++) H[6 * r + c] = acc[sym_idx(r, c)];
+            }
     }
 }
 

@@ -634,6 +634,55 @@ class Material(object):
         a = a[:, :nout]
         return a[0] if single else a
 
+    def calc_hessian(self, sig, epl=None, seq=None, accumulated_strain=0.0, max_stress=0.0, flag=0.0, tex=None, ana=False):
+        """Hessian of the SVC yield function at (6,) or (N,6) stresses, shape (N,6,6) (material.py:860-972).
+
+        With x the scaled features, v_i the support vectors, c_i the dual coefficients and d_i = v_i - x, the device
+        evaluates ``Hx[a][b] = sum_i c_i exp(-gamma |d_i|^2) (4 gamma^2 d_i[a] d_i[b] - 2 gamma delta_ab)`` -- the distance
+        over all features (the plastic strain of a work-hardening material included), a and b over the stress features --
+        and, like the reference, this returns ``Hx / scale_seq`` with ONE power of ``scale_seq`` (:962).  The mathematical
+        second derivative in stress units is ``Hx / scale_seq**2``; ``hessian * scale_seq`` of the returned array is the
+        feature-space Hessian ``Hx``.  For ``dev_only`` materials the features are the deviator's components and, again
+        like the reference, no chain rule through the deviator projection is applied.  Analytic yield functions have no
+        Hessian in the reference (``ValueError``), nor have sdim = 3 ML materials (``NotImplementedError``).
+        Unlike ``calc_fgrad`` this touches neither ``khard`` nor ``msg``."""
+        if tex is not None or getattr(self, 'txdat', False):
+            raise NotImplementedError('calc_hessian: texture features are outside this engine')
+        if getattr(self, 'ML_grad', False) and not ana:
+            raise NotImplementedError('calc_hessian: analytical gradient for SVR not implemented')
+        s = np.asarray(sig, dtype=float)
+        if s.shape in ((3,), (6,)):
+            s = s[None, :]
+        elif s.ndim == 0 or s.shape != (len(s), self.sdim):
+            raise ValueError('Unknown format of stress in calc_fgrad')
+        if not (self.ML_yf and not ana):
+            if self.barlat:
+                raise ValueError('calc_hessian: analytical hessian for Barlat not implemented')
+            if self.tresca:
+                raise ValueError('calc_hessian: analytical hessian for Tresca not implemented')
+            if self.hill is not None and len(self.hill):
+                raise ValueError('calc_hessian: analytical hessian for Hill not implemented')
+            return np.zeros((len(s), self.sdim, self.sdim))   # an elastic material: the reference's zeros (:907, 972)
+        if self.sdim == 3:
+            raise NotImplementedError('calc_hessian: not  implemented for 3D stress')
+        if s.shape[1] != 6:
+            raise ValueError('Unknown format of stress in calc_fgrad')
+        e = None
+        if getattr(self, 'whdat', False):
+            if accumulated_strain or max_stress or flag:
+                raise NotImplementedError('calc_hessian: the accumulated-strain, max-stress and flag features are zero '
+                                          'on every path of this engine')
+            if epl is not None:
+                if type(epl) in (float, np.float64):   # PEEQ -> a plastic strain along the stress (:889-892)
+                    e = epl * s / sig_eq_j2(s).reshape(-1, 1)
+                else:
+                    e = np.asarray(epl, dtype=float)
+                    if e.shape == (6,):
+                        e = np.tile(e, (len(s), 1))
+                    elif e.shape != s.shape:
+                        raise ValueError('Parameter sig and epl must have the same shape.')
+        return self._load().hessian(0, np.ascontiguousarray(s), e) / self.scale_seq
+
     def response(self, sig, epl, deps, CV, maxit=50):
         """Elastic-predictor / plastic-corrector update of one material point (material.py:207-346).
         Returns ``fy1, sig, depl, grad_stiff``; ``msg['nsteps']`` is set as in the reference."""
