@@ -424,10 +424,28 @@ int plfx_svc_decision_batch(plfx_ctx *ctx, int n, int d, const double *X, int np
                             const int32_t *sv_idx, const double *coef, const double *intercept, const double *gamma,
                             const int32_t *q_off, const int32_t *q_idx, double *dec);
 
+/* ---------------------------------------------------------------- SVR flow rule (Material.setup_fgrad_SVM, material.py:2058-2131)
+ * RBF epsilon-SVR fits by libsvm's non-shrinking SMO (solve_epsilon_svr), many problems in one call.  X [n*d] row-major
+ * features shared by all problems (1 <= d <= 16); problem p trains on the rows idx[off[p] .. off[p+1]) of X, in that order,
+ * with the targets t[off[p] .. off[p+1]) (one per entry of idx), C[p] > 0, gamma[p] > 0 and epsilon[p] >= 0; tol: stopping
+ * tolerance (scikit-learn's SVR default 1e-3); max_iter <= 0: max(10^7, 200 l_p).  Out: coef[off[nprob]] in the order of
+ * idx (alpha - alpha*, |coef| <= C; scikit-learn's dual_coef_ over coef != 0), rho[nprob] with prediction(x) =
+ * sum_k coef_k exp(-gamma |x - x_k|^2) - rho (intercept_ = -rho), obj[nprob] (NULL allowed) the dual objective,
+ * iters[nprob], status[nprob] 0 converged, 1 max_iter reached.  Rejects C or gamma <= 0, epsilon < 0 and d > 16. */
+int plfx_svr_fit_batch(plfx_ctx *ctx, int n, int d, const double *X, int nprob, const int32_t *off, const int32_t *idx,
+                       const double *t, const double *C, const double *gamma, const double *epsilon, double tol,
+                       int64_t max_iter, double *coef, double *rho, double *obj, int32_t *iters, int32_t *status);
+/* Predictions of m <= 8 RBF models that share the training rows X [n*d] and gamma, on nq points Q [nq*d] in one pass:
+ * out[q*m + k] = sum_r coef[r*m + k] exp(-gamma |Q_q - X_r|^2) + intercept[k], every kernel value computed once and
+ * the rows summed in order; coef [n*m] holds 0 where row r is no support vector of model k (an exact zero term leaves
+ * the sum as it is, so a column is the sum over its support vectors in their order). */
+int plfx_svr_predict_multi(plfx_ctx *ctx, int n, int d, const double *X, double gamma, int m, const double *coef,
+                           const double *intercept, int nq, const double *Q, double *out);
+
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
- *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch), 1 spmv(+dot), 2 cg vector
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

@@ -55,6 +55,7 @@ SYMBOLS = [
     'plfx_svc_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
+    'plfx_svr_fit_batch', 'plfx_svr_predict_multi',
 ]
 
 _lib = None
@@ -377,6 +378,51 @@ class Context(object):
         self._chk(self.lib.plfx_svc_decision_batch(self.h, len(X), X.shape[1], _dp(X), npb, _dp(so), _dp(si), _dp(cf),
                                                    _dp(ic), _dp(gs), _dp(qo), _dp(qi), _dp(out)))
         return [out[qo[p]:qo[p + 1]] for p in range(npb)]
+
+    # -- SVR flow rule (plfx_svm.hpp)
+    def svr_fit_batch(self, X, problems, targets, C, gamma, epsilon=0.1, tol=1e-3, max_iter=-1):
+        """Fit one RBF epsilon-SVR per problem (libsvm's non-shrinking SMO) in one batched call.
+        X (n, d) shared features, problems: list of row-index arrays into X, targets: one array per problem in the order
+        of its index array; C, gamma, epsilon: scalars or one per problem.  Returns a list of dicts (coef = alpha - alpha*
+        in the order of the index array, rho with prediction = sum coef K - rho, obj, n_iter, status 0 converged / 1
+        max_iter reached)."""
+        import ctypes   # (the argument C shadows this module's ctypes alias)
+        X = _f64(X)
+        if X.ndim != 2:
+            raise ValueError('svr_fit_batch: X must be (n, d)')
+        off, idx = self._lists(problems, 'svr_fit_batch')
+        npb = len(off) - 1
+        if len(targets) != npb:
+            raise ValueError('svr_fit_batch: one target array per problem expected')
+        t = _f64(np.concatenate([np.asarray(v, dtype=float).reshape(-1) for v in targets]))
+        if len(t) != len(idx) or any(len(np.reshape(v, -1)) != off[p + 1] - off[p] for p, v in enumerate(targets)):
+            raise ValueError('svr_fit_batch: one target per row of every problem expected')
+        Cs = _f64(np.broadcast_to(np.asarray(C, dtype=float), (npb,)))
+        gs = _f64(np.broadcast_to(np.asarray(gamma, dtype=float), (npb,)))
+        es = _f64(np.broadcast_to(np.asarray(epsilon, dtype=float), (npb,)))
+        coef = np.empty(len(idx))
+        rho, obj = np.empty(npb), np.empty(npb)
+        it, st = np.empty(npb, dtype=np.int32), np.empty(npb, dtype=np.int32)
+        self._chk(self.lib.plfx_svr_fit_batch(self.h, len(X), X.shape[1], _dp(X), npb, _dp(off), _dp(idx), _dp(t), _dp(Cs),
+                                              _dp(gs), _dp(es), ctypes.c_double(tol), ctypes.c_int64(int(max_iter)),
+                                              _dp(coef), _dp(rho), _dp(obj), _dp(it), _dp(st)))
+        return [dict(coef=coef[off[p]:off[p + 1]], rho=float(rho[p]), obj=float(obj[p]), n_iter=int(it[p]),
+                     status=int(st[p])) for p in range(npb)]
+
+    def svr_predict_multi(self, X, coef, intercepts, gamma, Q):
+        """Predictions of m <= 8 RBF models on the shared training rows X (n, d): coef (n, m) with zeros where a row is
+        no support vector of a model, intercepts (m,), query points Q (nq, d).  Returns (nq, m)."""
+        X, Q = _f64(X), _f64(Q)
+        coef = _f64(coef)
+        ic = _f64(intercepts).reshape(-1)
+        if X.ndim != 2 or Q.ndim != 2 or Q.shape[1] != X.shape[1]:
+            raise ValueError('svr_predict_multi: X (n, d) and Q (nq, d) expected')
+        if coef.ndim != 2 or coef.shape[0] != len(X) or coef.shape[1] != len(ic):
+            raise ValueError('svr_predict_multi: coef must be (n, m) with one intercept per column')
+        out = np.empty((len(Q), len(ic)))
+        self._chk(self.lib.plfx_svr_predict_multi(self.h, len(X), X.shape[1], _dp(X), C.c_double(float(gamma)), len(ic),
+                                                  _dp(coef), _dp(ic), len(Q), _dp(Q), _dp(out)))
+        return out
 
     def set_response_maxit(self, maxit=50):
         self._chk(self.lib.plfx_set_response_maxit(self.h, int(maxit)))

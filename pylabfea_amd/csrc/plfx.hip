@@ -3083,6 +3083,19 @@ int plfx_svc_decision_batch(plfx_ctx *c, int n, int d, const double *X, int npro
     return svc_decision_batch_impl(c, n, d, X, nprob, sv_off, sv_idx, coef, intercept, gamma, q_off, q_idx, dec);
 }
 
+int plfx_svr_fit_batch(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *off, const int32_t *idx,
+                       const double *t, const double *C, const double *gamma, const double *epsilon, double tol,
+                       int64_t max_iter, double *coef, double *rho, double *obj, int32_t *iters, int32_t *status)
+{
+    return svr_fit_batch_impl(c, n, d, X, nprob, off, idx, t, C, gamma, epsilon, tol, max_iter, coef, rho, obj, iters, status);
+}
+
+int plfx_svr_predict_multi(plfx_ctx *c, int n, int d, const double *X, double gamma, int m, const double *coef,
+                           const double *intercept, int nq, const double *Q, double *out)
+{
+    return svr_predict_multi_impl(c, n, d, X, gamma, m, coef, intercept, nq, Q, out);
+}
+
 int plfx_set_response_maxit(plfx_ctx *c, int maxit)
 {
     if (!c) return PLFX_ERR_ARG;

@@ -965,6 +965,344 @@ int svc_decision_batch_impl(plfx_ctx *c, int n, int d, const double *X, int npro
     return PLFX_OK;
 }
 
+// ---- epsilon-SVR (Material.setup_fgrad_SVM, material.py:2058-2131): libsvm's solve_epsilon_svr on the same solver rules.
+// A problem of l rows has 2l variables: k < l with sign +1 and linear term eps - t_k, k + l with sign -1 and eps + t_k;
+// Q_ab = s_a s_b K(a mod l, b mod l); a = 0, G = p.  Selection, update, clipping, tie-break and stopping rule are the
+// functions above, with the sign of a variable in the place of the internal label.  The rows stay in the caller's order
+// (scikit-learn does not reorder regression rows).  k_svr is a sibling of k_smo, which is left as it was: thread t owns
+// the ROWS t, t + 512, ... and with each row both of its variables, so the kernel entry K(i mod l, r) is computed once
+// per row (libsvm's SVR_Q::get_Q: (Qfloat)K, then the two signs, which are exact) and serves r and r + l.  A thread
+// keeps one candidate per half; the upper half wins ties, as its indices are the larger ones, which is the order in which
+// libsvm's loop over 0 .. 2l - 1 meets them.  Reductions, LDS slots and barriers are those of k_smo.
+struct SvrArgs {
+    const double *X;        // [n*d] shared features
+    int d;
+    const int32_t *off;     // [nprob+1] row range of each problem
+    const int32_t *row;     // [total] row of X, in the caller's order
+    const double *t;        // [total] targets in that order
+    const double *C, *gam, *eps;   // [nprob]
+    const int32_t *maxit;   // [nprob]
+    double *alpha, *G;      // [2*total]: problem p at 2 off[p]; variable k < l, then k + l
+    double *qd, *xsq;       // [total]
+    float *krow;            // [total] FP32 K(i mod l, r) of the current i
+    int32_t *st;            // [2*nprob] iterations, state (0 running, 1 optimal, 2 max_iter reached)
+    double tol;
+};
+
+__global__ void __launch_bounds__(256) k_svr_init(SvrArgs a)
+{
+#pragma clang fp contract(off)
+    const int p = blockIdx.x;
+    const int o = a.off[p], l = a.off[p + 1] - o;
+    const double g = a.gam[p], eps = a.eps[p];
+    double *al = a.alpha + 2 * (size_t)o, *G = a.G + 2 * (size_t)o;
+    for (int k = threadIdx.x; k < l; k += blockDim.x) {
+        const int r = a.row[o + k];
+        double s = 0.;
+        for (int f = 0; f < a.d; f++) s = s + a.X[(size_t)r * a.d + f] * a.X[(size_t)r * a.d + f];
+        a.xsq[o + k] = s;
+        a.qd[o + k] = exp(-g * ((s + s) - 2. * s));
+        al[k] = al[k + l] = 0.;
+        G[k] = eps - a.t[o + k];
+        G[k + l] = eps + a.t[o + k];
+    }
+    if (threadIdx.x == 0) a.st[2 * p] = a.st[2 * p + 1] = 0;
+}
+
+// 512 threads: a thread carries two variables per row, so this is the work per thread of k_smo's 1024, and the 256
+// registers a thread may then use hold both halves' candidates and the 16 feature loads in flight without scratch
+constexpr int SVR_BLOCK = 512;
+constexpr int SVR_WAVES = SVR_BLOCK / 64;
+
+__global__ void __launch_bounds__(SVR_BLOCK) k_svr(SvrArgs a, const int32_t *active, int chunk)
+{
+#pragma clang fp contract(off)
+    __shared__ SmoSlotA sa[SVR_WAVES];
+    __shared__ SmoSlotB sb[SVR_WAVES];
+    const int p = active[blockIdx.x];
+    if (a.st[2 * p + 1] != 0) return;
+    const int o = a.off[p], l = a.off[p + 1] - o;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double C = a.C[p], g = a.gam[p], tol = a.tol;
+    const int d = a.d, maxit = a.maxit[p];
+    double *al = a.alpha + 2 * (size_t)o, *G = a.G + 2 * (size_t)o;
+    const double *qd = a.qd + o, *xsq = a.xsq + o;
+    float *kr = a.krow + o;
+    const int32_t *row = a.row + o;
+    const double INF = __builtin_huge_val();
+
+    double av = -INF, aa = 0.;
+    int ai = -1;
+    {
+        double av2 = -INF, aa2 = 0.;
+        int ai2 = -1;
+        for (int r = tid; r < l; r += SVR_BLOCK) {
+            smo_cand_i(1, al[r], G[r], C, r, av, ai, aa);
+            smo_cand_i(-1, al[r + l], G[r + l], C, r + l, av2, ai2, aa2);
+        }
+        if (ai2 >= 0 && av2 >= av) av = av2, ai = ai2, aa = aa2;
+    }
+    int iter = a.st[2 * p], state = 0;
+    for (int step = 0;; step++) {
+        if (iter >= maxit) {
+            state = 2;
+            break;
+        }
+        if (step == chunk) break;
+        // ---- reduction for i
+        {
+            double v = av;
+            int ix = ai;
+            smo_wave_max(v, ix);
+            if ((ix >= 0 && ai == ix) || (ix < 0 && lane == 0)) sa[wave] = SmoSlotA{v, aa, ix};
+        }
+        __syncthreads();
+        double Gmax = -INF, alpha_i = 0.;
+        int i = -1;
+        smo_merge_a<SVR_WAVES>(sa, SVR_WAVES, Gmax, i, alpha_i);
+        if (i < 0) {
+            state = 1;
+            break;
+        }
+        i = __builtin_amdgcn_readfirstlane(i);
+        const int s_i = i < l ? 1 : -1, ri = i < l ? i : i - l;
+        const double G_i = s_i > 0 ? -Gmax : Gmax, qd_i = qd[ri], xsq_i = xsq[ri];
+        double xi[SMO_DMAX];
+        smo_load_x(a.X, d, row[ri], xi);
+
+        // ---- row i mod l once per row, candidates for j in both halves, Gmax2
+        double bv = INF, ba = 0., bg = 0., bq = 0., g2 = -INF;
+        int bj = -1;
+        {
+            double bv2 = INF, ba2 = 0., bg2 = 0., bq2 = 0.;
+            int bj2 = -1;
+            for (int r = tid; r < l; r += SVR_BLOCK) {
+                const float K = smo_q(xi, xsq_i, 1, a.X, d, row[r], xsq[r], g);
+                kr[r] = K;
+                const float q = s_i > 0 ? K : -K;
+                smo_cand_j(1, al[r], G[r], qd[r], q, r, C, Gmax, s_i, qd_i, bv, bj, ba, bg, bq, g2);
+                smo_cand_j(-1, al[r + l], G[r + l], qd[r], -q, r + l, C, Gmax, s_i, qd_i, bv2, bj2, ba2, bg2, bq2, g2);
+            }
+            if (bj2 >= 0 && bv2 <= bv) bv = bv2, bj = bj2, ba = ba2, bg = bg2, bq = bq2;
+        }
+        {
+            double v = bv, m2 = g2;
+            int ix = bj;
+            smo_wave_min(v, ix, m2);
+            if ((ix >= 0 && bj == ix) || (ix < 0 && lane == 0)) sb[wave] = SmoSlotB{v, ba, bg, bq, m2, ix};
+        }
+        __syncthreads();
+        double omin = INF, alpha_j = 0., G_j = 0., Q_ij = 0., Gmax2 = -INF;
+        int j = -1;
+        smo_merge_b<SVR_WAVES>(sb, SVR_WAVES, omin, j, alpha_j, G_j, Q_ij, Gmax2);
+        if (Gmax + Gmax2 < tol || j < 0) {
+            state = 1;
+            break;
+        }
+        ++iter;
+        j = __builtin_amdgcn_readfirstlane(j);
+
+        // ---- the two-variable update, G of both halves from the two rows, the candidate for the next i
+        const int s_j = j < l ? 1 : -1, rj = j < l ? j : j - l;
+        const double qd_j = qd[rj];
+        double ni, nj;
+        smo_pair(s_i, s_j, qd_i, qd_j, Q_ij, G_i, G_j, alpha_i, alpha_j, C, ni, nj);
+        const double dai = ni - alpha_i, daj = nj - alpha_j, xsq_j = xsq[rj];
+        double xj[SMO_DMAX];
+        smo_load_x(a.X, d, row[rj], xj);
+        av = -INF, ai = -1, aa = 0.;
+        double av2 = -INF, aa2 = 0.;
+        int ai2 = -1;
+        for (int r = tid; r < l; r += SVR_BLOCK) {
+            const float Kj = smo_q(xj, xsq_j, 1, a.X, d, row[r], xsq[r], g), Ki = kr[r];
+            const float qi = s_i > 0 ? Ki : -Ki, qj = s_j > 0 ? Kj : -Kj;
+            const double gl = smo_g_update(G[r], qi, qj, dai, daj), gu = smo_g_update(G[r + l], -qi, -qj, dai, daj);
+            G[r] = gl;
+            G[r + l] = gu;
+            double ak = al[r], au = al[r + l];
+            if (r == i) al[r] = ak = ni;
+            if (r == j) al[r] = ak = nj;
+            if (r + l == i) al[r + l] = au = ni;
+            if (r + l == j) al[r + l] = au = nj;
+            smo_cand_i(1, ak, gl, C, r, av, ai, aa);
+            smo_cand_i(-1, au, gu, C, r + l, av2, ai2, aa2);
+        }
+        if (ai2 >= 0 && av2 >= av) av = av2, ai = ai2, aa = aa2;
+    }
+    if (tid == 0) {
+        a.st[2 * p] = iter;
+        a.st[2 * p + 1] = state;
+    }
+}
+
+// predictions of up to SVR_MMAX RBF models that share their training rows and gamma: K(x_q, x_r) once per pair, one
+// accumulator per model, coef [n][SVR_MMAX] with zeros where a row is no support vector of a model (and in the unused
+// columns).  Rows in order: adding an exact 0 K leaves an FP64 sum as it is, so every column is libsvm's sum over its
+// support vectors in their order.  One thread per query point; the row loop is uniform, so the row and its coefficients
+// are scalar loads shared by the wave.
+constexpr int SVR_MMAX = 8;
+
+__global__ void __launch_bounds__(256) k_svr_predict(const double *__restrict__ X, int n, int d, double g,
+                                                     const double *__restrict__ coef, const double *__restrict__ icpt, int m,
+                                                     const double *__restrict__ Q, int nq, double *__restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nq) return;
+    double xq[SMO_DMAX];
+    smo_load_x(Q, d, t, xq);
+    double s[SVR_MMAX];
+#pragma unroll
+    for (int c = 0; c < SVR_MMAX; c++) s[c] = 0.;
+    for (int r = 0; r < n; r++) {
+        double ss = 0.;
+#pragma unroll
+        for (int f = 0; f < SMO_DMAX; f++)
+            if (f < d) {
+                const double df = xq[f] - X[(size_t)r * d + f];
+                ss = ss + df * df;
+            }
+        const double k = exp(-g * ss);
+#pragma unroll
+        for (int c = 0; c < SVR_MMAX; c++) s[c] = s[c] + coef[(size_t)r * SVR_MMAX + c] * k;
+    }
+#pragma unroll
+    for (int c = 0; c < SVR_MMAX; c++)
+        if (c < m) out[(size_t)t * m + c] = s[c] + icpt[c];
+}
+
+int svr_fit_batch_impl(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *off, const int32_t *idx,
+                       const double *t, const double *C, const double *gamma, const double *epsilon, double tol,
+                       int64_t max_iter, double *coef, double *rho, double *obj, int32_t *iters, int32_t *status)
+{
+    SVMCHK(svm_check_rows(c, "plfx_svr_fit_batch", n, d, X, nprob, off, idx, gamma));
+    if (!t || !C || !epsilon || !coef || !rho || !iters || !status)
+        return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: null argument");
+    if (!(tol > 0.) || !std::isfinite(tol)) return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: tol must be > 0 (got %g)", tol);
+    const int total = off[nprob];
+    if ((int64_t)total * 2 > INT32_MAX) return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: too many rows (%d)", total);
+    std::vector<int32_t> hmax(nprob);
+    for (int p = 0; p < nprob; p++) {
+        if (!(C[p] > 0.) || !std::isfinite(C[p]))
+            return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: C of problem %d must be > 0 (got %g)", p, C[p]);
+        if (!(epsilon[p] >= 0.) || !std::isfinite(epsilon[p]))
+            return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: epsilon of problem %d must be >= 0 (got %g)", p, epsilon[p]);
+        const int l = off[p + 1] - off[p];
+        if (l < 1) return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: problem %d holds no row", p);
+        // libsvm counts the 2l variables of the solver
+        hmax[p] = (int)std::min<int64_t>(max_iter > 0 ? max_iter : std::max<int64_t>(10000000, 200 * (int64_t)l), INT32_MAX);
+    }
+    for (int k = 0; k < total; k++)
+        if (!std::isfinite(t[k])) return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: target %d is not finite", k);
+    HIPCHK(c, hipSetDevice(c->device));
+    SvmBuffers B;
+    SvrArgs a;
+    double *dX, *dC, *dg, *de, *dt;
+    int32_t *doff, *drow, *dmax, *dact;
+    SVMCHK(B.get(c, &dX, (size_t)n * d));
+    SVMCHK(B.get(c, &doff, nprob + 1));
+    SVMCHK(B.get(c, &drow, total));
+    SVMCHK(B.get(c, &dt, total));
+    SVMCHK(B.get(c, &dC, nprob));
+    SVMCHK(B.get(c, &dg, nprob));
+    SVMCHK(B.get(c, &de, nprob));
+    SVMCHK(B.get(c, &dmax, nprob));
+    SVMCHK(B.get(c, &dact, nprob));
+    SVMCHK(B.get(c, &a.alpha, 2 * (size_t)total));
+    SVMCHK(B.get(c, &a.G, 2 * (size_t)total));
+    SVMCHK(B.get(c, &a.qd, total));
+    SVMCHK(B.get(c, &a.xsq, total));
+    SVMCHK(B.get(c, &a.krow, total));
+    SVMCHK(B.get(c, &a.st, 2 * nprob));
+    HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)n * d * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(doff, off, (size_t)(nprob + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(drow, idx, (size_t)total * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dt, t, (size_t)total * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dC, C, (size_t)nprob * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dg, gamma, (size_t)nprob * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(de, epsilon, (size_t)nprob * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dmax, hmax.data(), (size_t)nprob * 4, hipMemcpyHostToDevice, c->stream));
+    a.X = dX, a.d = d, a.off = doff, a.row = drow, a.t = dt, a.C = dC, a.gam = dg, a.eps = de, a.maxit = dmax, a.tol = tol;
+    hipLaunchKernelGGL(k_svr_init, dim3(nprob), dim3(256), 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    std::vector<int32_t> act(nprob), hst(2 * nprob, 0);
+    for (int p = 0; p < nprob; p++) act[p] = p;
+    std::stable_sort(act.begin(), act.end(), [&](int u, int v) { return off[u + 1] - off[u] > off[v + 1] - off[v]; });
+    while (!act.empty()) {
+        HIPCHK(c, hipMemcpyAsync(dact, act.data(), act.size() * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_svr, dim3((unsigned)act.size()), dim3(SVR_BLOCK), 0, c->stream, a, (const int32_t *)dact, SMO_CHUNK);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(hst.data(), a.st, (size_t)nprob * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        std::vector<int32_t> next;
+        for (int p : act)
+            if (hst[2 * p + 1] == 0) next.push_back(p);
+        act.swap(next);
+    }
+    std::vector<double> hal(2 * (size_t)total), hG(2 * (size_t)total);
+    HIPCHK(c, hipMemcpyAsync(hal.data(), a.alpha, hal.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hG.data(), a.G, hG.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int8_t> sgn;
+    for (int p = 0; p < nprob; p++) {
+        const int o = off[p], l = off[p + 1] - o;
+        const double *al = &hal[2 * (size_t)o], *G = &hG[2 * (size_t)o];
+        sgn.assign(2 * (size_t)l, 1);
+        std::fill(sgn.begin() + l, sgn.end(), (int8_t)-1);
+        rho[p] = smo_rho(2 * l, al, G, sgn.data(), C[p]);   // libsvm's rho: prediction = sum_k coef_k K(x, x_k) - rho
+        if (obj) {
+            double v = 0.;
+            for (int k = 0; k < l; k++) v += al[k] * (G[k] + (epsilon[p] - t[o + k]));
+            for (int k = 0; k < l; k++) v += al[k + l] * (G[k + l] + (epsilon[p] + t[o + k]));
+            obj[p] = v / 2;
+        }
+        iters[p] = hst[2 * p];
+        status[p] = hst[2 * p + 1] == 2 ? 1 : 0;
+        for (int k = 0; k < l; k++) coef[o + k] = al[k] - al[k + l];
+    }
+    return PLFX_OK;
+}
+
+int svr_predict_multi_impl(plfx_ctx *c, int n, int d, const double *X, double gamma, int m, const double *coef,
+                           const double *intercept, int nq, const double *Q, double *out)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (n < 1 || !X || !coef || !intercept || nq < 0 || (nq > 0 && (!Q || !out)))
+        return fail(c, PLFX_ERR_ARG, "plfx_svr_predict_multi: null or empty argument");
+    if (d < 1 || d > SMO_DMAX)
+        return fail(c, PLFX_ERR_ARG, "plfx_svr_predict_multi: d = %d features, 1 <= d <= %d supported", d, SMO_DMAX);
+    if (m < 1 || m > SVR_MMAX)
+        return fail(c, PLFX_ERR_ARG, "plfx_svr_predict_multi: m = %d models, 1 <= m <= %d supported", m, SVR_MMAX);
+    if (!(gamma > 0.) || !std::isfinite(gamma))
+        return fail(c, PLFX_ERR_ARG, "plfx_svr_predict_multi: gamma must be > 0 (got %g)", gamma);
+    if (nq == 0) return PLFX_OK;
+    std::vector<double> hc((size_t)n * SVR_MMAX, 0.), hi(SVR_MMAX, 0.);
+    for (int r = 0; r < n; r++)
+        for (int k = 0; k < m; k++) hc[(size_t)r * SVR_MMAX + k] = coef[(size_t)r * m + k];
+    for (int k = 0; k < m; k++) hi[k] = intercept[k];
+    HIPCHK(c, hipSetDevice(c->device));
+    SvmBuffers B;
+    double *dX, *dc, *di, *dQ, *dout;
+    SVMCHK(B.get(c, &dX, (size_t)n * d));
+    SVMCHK(B.get(c, &dc, hc.size()));
+    SVMCHK(B.get(c, &di, hi.size()));
+    SVMCHK(B.get(c, &dQ, (size_t)nq * d));
+    SVMCHK(B.get(c, &dout, (size_t)nq * m));
+    HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)n * d * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dc, hc.data(), hc.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(di, hi.data(), hi.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dQ, Q, (size_t)nq * d * 8, hipMemcpyHostToDevice, c->stream));
+    EvPair *ev;
+    tim_begin(c, 0, &ev);   // family 0, like the other batched point kernels: the kernel alone, without the copies
+    hipLaunchKernelGGL(k_svr_predict, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream, (const double *)dX, n, d,
+                       gamma, (const double *)dc, (const double *)di, m, (const double *)dQ, nq, dout);
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)nq * m * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PLFX_OK;
+}
+
 #undef SVMCHK
 
 }  // namespace

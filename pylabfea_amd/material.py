@@ -404,6 +404,12 @@ class Material(object):
         if self.tresca:
             raise ValueError('calc_fgrad: analytical gradient for Tresca not implemented')
 
+    def _no_svr_gradient(self, what):
+        """the device's return mapping follows the gradient of the SVC yield function; it cannot follow an SVR gradient"""
+        if getattr(self, 'ML_grad', False):
+            raise NotImplementedError('%s: ML_grad is set, and the SVR gradient of setup_fgrad_SVM is evaluated by calc_fgrad '
+                                      '(and epl_dot / C_tan) only; set ML_grad = False to run with the SVC gradient' % what)
+
     def _content_key(self, CV=None, ana=False, rec=None, parameters_only=False):
         """Digest of everything the device evaluates for this material: the packed ``plfx_material`` record (kind, elastic
         and plastic parameters, Hill / Barlat coefficients, SVC scalars) and the support-vector / dual-coefficient tables.
@@ -599,6 +605,8 @@ class Material(object):
         nd = self.sdim if self.sdim is not None else 6
         if s0.shape not in ((3,), (6,)) and not (s0.ndim == 2 and s0.shape[1] == nd):
             raise ValueError('Unknown format of stress in calc_fgrad')
+        if getattr(self, 'ML_grad', False) and not ana:
+            return self._fgrad_svr(s0, epl)
         if not (self.ML_yf and not ana):
             self._no_flow_rule()
         s, single = self._voigt(s0, 'calc_fgrad')
@@ -632,6 +640,70 @@ class Material(object):
                 self.msg['gradient'] = ('analytical, J2 isotropic, princ. stress' if np.all(h == 1.)
                                         else 'analytical, 3-parameter Hill, princ. stress')
         a = a[:, :nout]
+        return a[0] if single else a
+
+    # ------------------------------------------------------------------ SVR flow rule
+    SVR_EPSILON, SVR_TOL = 0.01, 1e-4   # the reference's SVR settings (material.py:2076-2089)
+
+    def setup_fgrad_SVM(self):
+        """Train the SVR flow rule on the work-hardening data of ``from_data`` (material.py:2058-2131): seven RBF
+        epsilon-SVRs on the standardised features [flow_stress | plastic_strain], six for the components of the plastic
+        strain direction eps / peeq and one for the local hardening rate d seq / d peeq, all with C_yf, gam_yf,
+        epsilon 0.01 and tol 1e-4, fitted in one batched call on the GPU (libsvm's epsilon-SVR without shrinking).  Sets
+        svm_grad0 .. svm_grad5, svm_khard, sc_feat, sc_grad, sc_khard and ML_grad = True."""
+        if not getattr(self, 'whdat', False):
+            raise ValueError('No strain hardening data available.')
+        if not self._msparam_ok():
+            raise NotImplementedError('setup_fgrad_SVM: the work-hardening data must be one data set installed by from_data')
+        if self.C_yf is None or self.gam_yf is None:
+            raise ValueError('setup_fgrad_SVM: C_yf and gam_yf are not set; train_SVC sets them')
+        eps = np.asarray(self.msparam[0]['plastic_strain'], dtype=float)
+        sig = np.asarray(self.msparam[0]['flow_stress'], dtype=float)
+        # seq from the principal stresses, as the reference's sig_eq_j2 forms it: the hardening rate divides differences of
+        # seq, which keep the last bits the direct Voigt form of basic.sig_eq_j2 rounds differently
+        peeq, seq = eps_eq(eps), sig_eq_j2(sig_princ(sig)[0])
+        ndata = len(seq)
+        X_gt = np.concatenate((sig, eps), axis=1)
+        ok = peeq > 1.e-12
+        y_gt = np.zeros((ndata, 6))
+        y_gt[ok] = eps[ok] / peeq[ok, None]
+        y_kh = np.zeros(ndata)   # forward difference along the rows; the last row has no successor
+        hh = peeq[1:] - peeq[:-1]
+        step = np.abs(hh) > 1.e-12
+        y_kh[:-1][step] = (seq[1:] - seq[:-1])[step] / hh[step]
+        self.sc_feat, self.sc_grad, self.sc_khard = StdScaler(X_gt), StdScaler(y_gt), StdScaler(y_kh.reshape(-1, 1))
+        x_sc = self.sc_feat.transform(X_gt)
+        y_sc = np.concatenate((self.sc_grad.transform(y_gt), self.sc_khard.transform(y_kh.reshape(-1, 1))), axis=1)
+        ctx = _ctx()
+        rows = np.arange(ndata)
+        fits = ctx.svr_fit_batch(x_sc, [rows] * 7, [y_sc[:, m] for m in range(7)], self.C_yf, self.gam_yf,
+                                 epsilon=self.SVR_EPSILON, tol=self.SVR_TOL)
+        svr = [SVRModel(ctx, x_sc, r, self.C_yf, self.gam_yf, self.SVR_EPSILON) for r in fits]
+        (self.svm_grad0, self.svm_grad1, self.svm_grad2, self.svm_grad3, self.svm_grad4, self.svm_grad5,
+         self.svm_khard) = svr
+        self._svr = dict(X=x_sc, coef=np.ascontiguousarray(np.stack([m.coef_ for m in svr], axis=1)),
+                         intercept=np.array([m.intercept_[0] for m in svr]), gamma=float(self.gam_yf))
+        self.ML_grad = True
+
+    def _fgrad_svr(self, sig, epl):
+        """the ML_grad branch of calc_fgrad (material.py:752-764): the six SVR predictions on [sig | epl], standardised and
+        scaled back, all points and all seven models in one kernel pass; khard from the hardening SVR at the LAST point
+        (a float; the reference leaves a (1,) array)"""
+        if not hasattr(self, '_svr'):
+            raise AttributeError('calc_fgrad: ML_grad is set, but setup_fgrad_SVM has not trained the SVR gradient')
+        single = sig.shape == (6,)
+        if not single and not (sig.ndim == 2 and sig.shape[1] == 6):
+            raise ValueError('Unknown format of stress in calc_fgrad')
+        s = sig.reshape(-1, 6)
+        e = np.zeros_like(s) if epl is None else np.asarray(epl, dtype=float).reshape(-1, 6)
+        if len(s) == 0:
+            return np.zeros((0, 6))
+        v = self._svr
+        out = _ctx().svr_predict_multi(v['X'], v['coef'], v['intercept'], v['gamma'],
+                                       self.sc_feat.transform(np.concatenate((s, e), axis=1)))
+        a = self.sc_grad.inverse_transform(out[:, :6])
+        self.khard = float(self.sc_khard.inverse_transform(out[-1:, 6:7])[0, 0])
+        self.msg['gradient'] = 'SVR gradient'
         return a[0] if single else a
 
     def calc_hessian(self, sig, epl=None, seq=None, accumulated_strain=0.0, max_stress=0.0, flag=0.0, tex=None, ana=False):
@@ -693,6 +765,7 @@ class Material(object):
                              'Shape of argument is {}'.format(sh))
         if sh == (3,):
             raise NotImplementedError('response: pass the Voigt stress (6,); (3,) principal input is not supported')
+        self._no_svr_gradient('response')
         self._no_flow_rule()
         maxit = int(maxit)
         if maxit < 1:
@@ -713,6 +786,7 @@ class Material(object):
 
     def response_batch(self, sig, epl, deps, CV):
         """``response`` on (N,6) arrays in one launch (extension; same numbers point by point)."""
+        self._no_svr_gradient('response_batch')
         fy, so, dp, ct, ns = self._load(CV).response(sig, epl, deps)
         return fy, so, dp, ct.reshape(-1, 6, 6), ns
 
@@ -1060,6 +1134,7 @@ class Material(object):
         """Stress-strain curves of a 2x2 plane-stress model under four load cases
         (material.py:3062-3166); the harness of the reference's plasticity tests."""
         from .model import Model
+        self._no_svr_gradient('calc_properties')
 
         def calc_strength(vbc1, nbc1, vbc2, nbc2, sel):
             fe = Model(dim=2, planestress=True)
@@ -1151,6 +1226,54 @@ class SVCModel(object):
 
     def score(self, X, y):
         return float(np.mean(self.predict(X) == np.asarray(y)))
+
+
+class StdScaler(object):
+    """scikit-learn's ``StandardScaler`` arithmetic (``mean_``, ``var_``, ``scale_``, ``transform``,
+    ``inverse_transform``): population standard deviation per column; a column whose variance is zero (within
+    rounding: var <= n eps var + (n mean eps)^2, scikit-learn's test for a constant feature) gets scale 1."""
+
+    def __init__(self, X):
+        X = np.asarray(X, dtype=float)
+        n = len(X)
+        self.n_samples_seen_ = n
+        self.mean_ = np.mean(X, axis=0)
+        self.var_ = np.var(X, axis=0)
+        fe = np.finfo(np.float64).eps
+        const = self.var_ <= n * fe * self.var_ + (n * self.mean_ * fe) ** 2
+        self.scale_ = np.where(const, 1., np.sqrt(self.var_))
+
+    def transform(self, X):
+        return (np.asarray(X, dtype=float) - self.mean_) / self.scale_
+
+    def inverse_transform(self, X):
+        return np.asarray(X, dtype=float) * self.scale_ + self.mean_
+
+
+class SVRModel(object):
+    """A fitted RBF epsilon-SVR in scikit-learn's layout (``support_``, ``support_vectors_``, ``dual_coef_`` (1, nSV),
+    ``intercept_`` (1,), ``n_iter_`` (1,), ``C``, ``gamma``, ``epsilon``): what ``Material.svm_grad0`` .. ``svm_khard``
+    hold after ``setup_fgrad_SVM``.  ``coef_`` holds alpha - alpha* of every training row.  Fitted by plfx_svr_fit_batch and
+    evaluated by plfx_svr_predict_multi."""
+
+    def __init__(self, ctx, X, fit, C, gamma, epsilon):
+        self._ctx, self._X = ctx, X
+        self.C, self.gamma, self._gamma, self.epsilon = float(C), float(gamma), float(gamma), float(epsilon)
+        self.coef_ = np.array(fit['coef'])
+        self.support_ = np.nonzero(np.abs(self.coef_) > 0.)[0].astype(np.int32)
+        self.support_vectors_ = X[self.support_]
+        self.dual_coef_ = self.coef_[self.support_][None, :]
+        self.intercept_ = np.array([-fit['rho']])
+        self.n_iter_ = np.array([fit['n_iter']], dtype=np.int32)
+        self.fit_status_ = int(fit['status'])
+        self.dual_objective_ = float(fit['obj'])
+        if self.fit_status_:
+            warnings.warn('Solver terminated early (max_iter=%d).  Consider pre-processing your data with '
+                          'StandardScaler or MinMaxScaler.' % fit['n_iter'])
+
+    def predict(self, X):
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        return self._ctx.svr_predict_multi(self._X, self.coef_[:, None], self.intercept_, self.gamma, X)[:, 0]
 
 
 def svc_grid_search(ctx, X, y, candidates, folds):

@@ -936,6 +936,8 @@ class Model(object):
         co_nconv`` and ``element[i].sig/eps/epl``."""
         if self.Nnode is None:
             raise AttributeError('Attributes for mesh not set, but required by solver.')
+        for m in self.mat:
+            m._no_svr_gradient('Model.solve')
         eng = self._ensure_engine()
         eng.set_wh_mode(self.wh_carry != 'per_point')
         self._cache = {}

@@ -5,7 +5,8 @@ This is the debugging aid for the device solver: libsvm's non-shrinking C-SVC so
 selection, the analytic two-variable update, G from both kernel rows), with kernel rows computed in FP64 and stored as FP32
 like libsvm's ``Qfloat``.  It can print the working pair (i, j) of every iteration, so the first iteration where the device
 and this replay (or libsvm) part can be found.  It is also the reference of tests/test_gpu_svc_smo.py (pinned to libsvm by
-tests/test_svc_replay_cpu.py), together with the FP64 checks ``kkt_gap`` and ``dual_obj``.
+tests/test_svc_replay_cpu.py), together with the FP64 checks ``kkt_gap`` and ``dual_obj``.  ``svr`` is the same for the epsilon-SVR dual (k_svr, Material.setup_fgrad_SVM), the reference of
+tests/test_gpu_svr.py, pinned to libsvm by tests/test_svr_replay_cpu.py.
 
 The problem is laid out as libsvm sees it inside scikit-learn: the classes are sorted, so the rows of label -1 come first
 (internal y = +1) and the rows of label +1 follow (internal y = -1).  Results are returned in scikit-learn's convention
@@ -124,6 +125,119 @@ def smo(X, y, C, gamma, tol=1e-3, max_iter=-1, trace=0):
     sv = np.nonzero(alpha > 0)[0]
     return dict(support_=perm[sv], dual_coef_=-(yd[sv] * alpha[sv]), intercept_=rho, n_iter_=it,
                 obj=0.5 * float(np.sum(alpha * (G - 1.))), alpha=alpha, perm=perm, status=int(it >= max_iter))
+
+
+def svr(X, t, C, gamma, epsilon=0.1, tol=1e-3, max_iter=-1, trace=0):
+    """non-shrinking libsvm SMO for the epsilon-SVR dual (solve_epsilon_svr) on (X, targets t), rows in the order given:
+    2l variables, k < l with sign +1 and linear term epsilon - t_k, k + l with sign -1 and epsilon + t_k,
+    Q_ab = s_a s_b K(a mod l, b mod l) from FP32 kernel rows, alpha = 0 and G = p at the start; selection, update and rho as in
+    ``smo``.  Returns dict(support_, dual_coef_ (over the support), intercept_ (= -rho), n_iter_, obj, coef (l,), alpha
+    (2l,), G (2l,), status) in scikit-learn's convention (prediction = sum coef K + intercept_).  max_iter <= 0 (or None)
+    means libsvm's default max(10 000 000, 100 * 2l)."""
+    X = np.ascontiguousarray(X, dtype=float)
+    t = np.asarray(t, dtype=float).reshape(-1)
+    l = len(X)
+    n = 2 * l
+    if max_iter is None or max_iter <= 0:
+        max_iter = max(10000000, 100 * n)
+    xsq = np.zeros(l)
+    for f in range(X.shape[1]):
+        xsq = xsq + X[:, f] * X[:, f]
+    yi = np.concatenate([np.ones(l, dtype=np.int8), -np.ones(l, dtype=np.int8)])
+    yd = yi.astype(float)
+    p = np.concatenate([epsilon - t, epsilon + t])
+
+    def row(i):   # SVR_Q::get_Q: (Qfloat)K(i mod l, .) once, then the signs (exact)
+        k = np.exp(-gamma * (xsq[i % l] + xsq - 2 * dot_seq(X, X[i % l]))).astype(np.float32)
+        return (yd[i] * yd).astype(np.float32) * np.concatenate([k, k])
+
+    qd = np.exp(-gamma * (xsq + xsq - 2 * xsq))
+    QD = np.concatenate([qd, qd])
+    alpha = np.zeros(n)
+    G = p.copy()
+    it = 0
+    while it < max_iter:
+        up = alpha >= C
+        lo = alpha <= 0
+        v = np.where(yi > 0, np.where(~up, -G, -np.inf), np.where(~lo, G, -np.inf))
+        Gmax = v.max()
+        if Gmax == -np.inf:
+            break
+        i = n - 1 - int(np.argmax(v[::-1]))
+        Qi = row(i)
+        cand = np.where(yi > 0, ~lo, ~up)
+        g2 = np.where(yi > 0, G, -G)
+        Gmax2 = np.max(np.where(cand, g2, -np.inf))
+        gd = np.where(yi > 0, Gmax + G, Gmax - G)
+        quad = QD[i] + QD - np.where(yi > 0, 1., -1.) * (2.0 * yd[i] * Qi.astype(float))
+        quad = np.where(quad > 0, quad, TAU)
+        od = np.where(cand & (gd > 0), -(gd * gd) / quad, np.inf)
+        if Gmax + Gmax2 < tol or not np.any(cand & (gd > 0)):
+            break
+        j = n - 1 - int(np.argmin(od[::-1]))
+        it += 1
+        if trace and it <= trace:
+            print('iter %d  i=%d j=%d  Gmax=%.17g' % (it, i, j, Gmax))
+        Qj = row(j)
+        ai, aj = alpha[i], alpha[j]
+        if yi[i] != yi[j]:
+            q = QD[i] + QD[j] + 2 * float(Qi[j])
+            if q <= 0:
+                q = TAU
+            delta = (-G[i] - G[j]) / q
+            diff = ai - aj
+            ni, nj = ai + delta, aj + delta
+            if diff > 0:
+                if nj < 0:
+                    nj, ni = 0., diff
+            elif ni < 0:
+                ni, nj = 0., -diff
+            if diff > 0:
+                if ni > C:
+                    ni, nj = C, C - diff
+            elif nj > C:
+                nj, ni = C, C + diff
+        else:
+            q = QD[i] + QD[j] - 2 * float(Qi[j])
+            if q <= 0:
+                q = TAU
+            delta = (G[i] - G[j]) / q
+            s = ai + aj
+            ni, nj = ai - delta, aj + delta
+            if s > C:
+                if ni > C:
+                    ni, nj = C, s - C
+            elif nj < 0:
+                nj, ni = 0., s
+            if s > C:
+                if nj > C:
+                    nj, ni = C, s - C
+            elif ni < 0:
+                ni, nj = 0., s
+        alpha[i], alpha[j] = ni, nj
+        G += Qi.astype(float) * (ni - ai) + Qj.astype(float) * (nj - aj)
+    rho = calc_rho(alpha, G, yi, C)
+    coef = alpha[:l] - alpha[l:]
+    sv = np.nonzero(np.abs(coef) > 0)[0]
+    return dict(support_=sv, dual_coef_=coef[sv], intercept_=-rho, n_iter_=it, obj=0.5 * float(np.sum(alpha * (G + p))),
+                coef=coef, alpha=alpha, G=G, status=int(it >= max_iter))
+
+
+def svr_kkt_gap(X, t, coef, alpha, C, gamma, epsilon):
+    """m(a) - M(a) of an epsilon-SVR fit in FP64: G = s (K coef) + p over the 2l variables (alpha as ``svr`` returns it
+    decides which variables sit at a bound); -inf when one of the two index sets is empty"""
+    X, t = np.asarray(X, dtype=float), np.asarray(t, dtype=float)
+    l = len(X)
+    f = kernel_fp64(X, X, gamma) @ np.asarray(coef, dtype=float)
+    y = np.concatenate([np.ones(l), -np.ones(l)])
+    G = y * np.concatenate([f, f]) + np.concatenate([epsilon - t, epsilon + t])
+    a = np.asarray(alpha, dtype=float)
+    v = -y * G
+    up = ((y > 0) & (a < C)) | ((y < 0) & (a > 0))
+    low = ((y > 0) & (a > 0)) | ((y < 0) & (a < C))
+    if not np.any(up) or not np.any(low):
+        return -np.inf
+    return np.max(v[up]) - np.min(v[low])
 
 
 def calc_rho(alpha, G, yi, C):
