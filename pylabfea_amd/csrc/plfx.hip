@@ -4394,9 +4394,23 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
         }
     } else
         c->pred_valid = false;   // a cold start or another solver: the history starts again
-    // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
-    LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, warm ? 1 : 0, (const double2 *)c->x, (const double2 *)c->rhs,
-               (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, P_rz[1], P_rr[1], P_bb, olo, ohi);
+    // A solve that may be answered by x + alpha d needs K d as well as K x: where the plain start is not expected to pass its
+    // test, both come from ONE pass over the generators (k_cg_start_pred) instead of k_cg_start and k_spmv<0>.  A site
+    // whose last solve was answered by the plain start (the predictor solve of a load step) keeps k_cg_start: it would pay for a
+    // K d that nobody reads.  Matrix-free operator with cells all alike, one GPU, no strip.  If the plain start passes after
+    // all, pred_d and p[0] hold a d and a K d that nothing reads: pred_d_ready stays false, the next solve forms its own.
+    const bool pred_fused = pred_active && matfree(c) && !c->op.colr && !c->strip.on && !comm_active(c) && solve_site_in >= 0 &&
+                            !c->first_test_hint[solve_site_in];
+    if (pred_fused) {
+        // d = x - (solution before) first (k_pred_diff without the flag: the test of this solve has not run yet), then
+        // r = P(b - K x) and K d -> p[0]; partials of r.r and b.b -> slot 1 (z and r.z: written by the V-cycle if there is one)
+        hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d,
+                           (const CgScalars *)nullptr);
+        hipLaunchKernelGGL(k_cg_start_pred, dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, (const double2 *)c->x, (const double2 *)c->pred_d,
+                           (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], P_rr[1], P_bb);
+    } else   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
+        LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, warm ? 1 : 0, (const double2 *)c->x, (const double2 *)c->rhs,
+                   (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, P_rz[1], P_rr[1], P_bb, olo, ohi);
     if (c->strip.on) {  // sums of the whole grid; r valid on every local column (the V-cycle reads the halo)
         if ((rc = part_allreduce(c, P_rz[1], (size_t)3 * MAXPART))) return rc;
         if ((rc = halo_refresh(c, c->r))) return rc;
@@ -4427,9 +4441,11 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
             // (the reference repeats solves of one system: x satisfies the tolerance as it is); the host waits ONCE, for the second
             // test (round 6: three round trips -> one).  d = x - (solution before), K d, the two sums, alpha on the device
             // (k_pred_alpha), | P (r - alpha K d) |^2 into the free slot P_rr[0] without touching x, r, z, the test on it.
-            hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
-            LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)c->pred_d, nullptr, nullptr, (double2 *)c->p[0],
-                       nullptr, nullptr, nullptr, 0, nullptr, c->sc, 0, 0, 0);
+            if (!pred_fused) {   // (the fused start has left d in pred_d and K d in p[0])
+                hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
+                LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)c->pred_d, nullptr, nullptr, (double2 *)c->p[0],
+                           nullptr, nullptr, nullptr, 0, nullptr, c->sc, 0, 0, 0);
+            }
             const int gp = MAXPART;   // (one size on every rank: the all-reduce of the partial sums pairs up)
             hipLaunchKernelGGL(k_pred_dots, dim3(gp), dim3(BLOCK), 0, c->stream, (size_t)2 * olo, (size_t)2 * ohi, c->dinv, c->r, c->p[0],
                                c->part, c->sc);

@@ -1624,6 +1624,76 @@ __device__ __forceinline__ double2 op_apply(const KOp &o, int i, XF xf)
     return bell_apply(o.nnode, o.nslot, o.col, o.val, i, xf);
 }
 
+// the row pair of a node from its 3 x 3 window u of vector entries and its four elements' generators m: the arithmetic of
+// grid_apply_pairs_jk<false> behind its loads, expression for expression
+__device__ __forceinline__ double2 stencil_rows(const double2 (&u)[3][3], const double (&m)[4][6], const double *tab)
+{
+    double qx = 0., qy = 0.;
+#pragma unroll
+    for (int pj = 0; pj < 2; pj++)
+#pragma unroll
+        for (int pk = 0; pk < 2; pk++) {
+            const int p = pj * 2 + pk;
+            const double *T = tab + p * 16;  // wave-uniform -> scalar loads
+            double A1 = 0., A2 = 0., A3 = 0., A4 = 0., A5 = 0., A6 = 0., A7 = 0., A8 = 0.;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const double2 ub = u[pj + (b >> 1)][pk + (b & 1)];
+                const double sxx = T[b * 4 + 0], syy = T[b * 4 + 1], sxy = T[b * 4 + 2], syx = T[b * 4 + 3];
+                A1 = fma(sxx, ub.x, A1);
+                A2 = fma(sxx, ub.y, A2);
+                A3 = fma(syy, ub.x, A3);
+                A4 = fma(syy, ub.y, A4);
+                A5 = fma(sxy, ub.x, A5);
+                A6 = fma(sxy, ub.y, A6);
+                A7 = fma(syx, ub.x, A7);
+                A8 = fma(syx, ub.y, A8);
+            }
+            const double Mxx = m[p][0], Mxy = m[p][1], Mxs = m[p][2], Myy = m[p][3], Mys = m[p][4], Mss = m[p][5];
+            qx = fma(Mxx, A1, fma(Mxs, A5 + A7 + A2, fma(Mss, A3 + A8, fma(Mxy, A6, fma(Mys, A4, qx)))));
+            qy = fma(Mxy, A7, fma(Mys, A3 + A8 + A6, fma(Mxs, A1, fma(Mss, A5 + A2, fma(Myy, A4, qy)))));
+        }
+    return make_double2(qx, qy);
+}
+
+// Row pair i of the matrix-free operator (all cells alike: GRID 1) times TWO vectors, the generators loaded once: xf2(node, a, b)
+// gives the entries of both at a node.  qa and qb are, bit for bit, what op_apply<1> returns for either vector alone: nothing is
+// shared between the two sums but the registers that hold m.
+template <class XF2>
+__device__ __forceinline__ void op_apply2(const KOp &g, int i, XF2 xf2, double2 &qa, double2 &qb)
+{
+    const double2 *M2 = reinterpret_cast<const double2 *>(g.M);
+    const int nyn = g.nyn, nel = g.nel, nye = nyn - 1, nxe = g.nxn - 1;
+    const int j = i / nyn, k = i - j * nyn;
+    double2 ua[3][3], ub[3][3];
+#pragma unroll
+    for (int dj = 0; dj < 3; dj++) {
+        const int jj = min(max(j + dj - 1, 0), nxe);
+#pragma unroll
+        for (int dk = 0; dk < 3; dk++) {
+            const int kk = min(max(k + dk - 1, 0), nye);
+            xf2(jj * nyn + kk, ua[dj][dk], ub[dj][dk]);
+        }
+    }
+    double m[4][6];
+#pragma unroll
+    for (int pj = 0; pj < 2; pj++)
+#pragma unroll
+        for (int pk = 0; pk < 2; pk++) {
+            const int ej = j - 1 + pj, ek = k - 1 + pk;
+            const bool ok = ej >= 0 && ej < nxe && ek >= 0 && ek < nye;
+            const int e = min(max(ej, 0), nxe - 1) * nye + min(max(ek, 0), nye - 1);
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double2 v = M2[c * nel + e];
+                m[pj * 2 + pk][2 * c] = ok ? v.x : 0.;
+                m[pj * 2 + pk][2 * c + 1] = ok ? v.y : 0.;
+            }
+        }
+    qa = stencil_rows(ua, m, g.tab);
+    qb = stencil_rows(ub, m, g.tab);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The same operator, MARCHING along x with the 3 x 3 stencil window in registers (round 3).  Measured with rocprofv3 at
 // 2048^2 -- one pass = 470 MB, beyond the 256 MiB Infinity Cache -- the gather form above moves 1.15x (smoother) and 1.38x
@@ -2156,6 +2226,48 @@ k_cg_start(KOp op, int nnode, int warm, const double2 *__restrict__ x, const dou
     }
 }
 
+// k_cg_start of a warm-started multigrid-PCG solve that will try the interpolated start x + alpha d (plfx_solve):
+// the same r and the same partial sums of r.r and b.b, and from the same load of the generators K d (k_spmv<0>'s arithmetic on
+// the d that k_pred_diff has just written).  No z and no r.z: the V-cycle that follows a failed test starts from a zero guess
+// and writes every entry of z, and its last smoothing launch (or k_dot_rz) writes the r.z partials.  One GPU, no strip: the
+// sums run over all nodes.
+__global__ void __launch_bounds__(BLOCK)
+k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 *__restrict__ d, const double2 *__restrict__ b,
+                const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ kd,
+                double *__restrict__ part_rr_out, double *__restrict__ part_bb_out)
+{
+    __shared__ double sh[BLOCK / 64];
+    double a_rr = 0., a_bb = 0.;
+    const int nb = gridDim.x;
+    for (int t = xcd_tile(blockIdx.x, nb); t * BLOCK < nnode; t += nb) {
+        const int i = t * BLOCK + threadIdx.x;
+        if (i >= nnode) continue;
+        double2 qi, qd;
+        op_apply2(
+            op, i,
+            [&](int j, double2 &xj, double2 &dj) {
+                xj = x[j];
+                dj = d[j];
+            },
+            qi, qd);
+        const double2 bi = b[i], di = dinv[i];
+        double2 ri;
+        ri.x = (di.x != 0.) ? bi.x - qi.x : 0.;
+        ri.y = (di.y != 0.) ? bi.y - qi.y : 0.;
+        r[i] = ri;
+        kd[i] = qd;
+        a_rr = fma(ri.x, ri.x, fma(ri.y, ri.y, a_rr));
+        const double bx = (di.x != 0.) ? bi.x : 0., by = (di.y != 0.) ? bi.y : 0.;
+        a_bb = fma(bx, bx, fma(by, by, a_bb));
+    }
+    const double t2 = block_sum(a_rr, sh);
+    const double t3 = block_sum(a_bb, sh);
+    if (threadIdx.x == 0) {
+        part_rr_out[blockIdx.x] = t2;
+        part_bb_out[blockIdx.x] = t3;
+    }
+}
+
 // r = mask (b - q), z = dinv r, partial r.z, r.r   (initial residual; q = K x0)
 __global__ void __launch_bounds__(BLOCK)
 k_cg_init(int nnode, const double2 *__restrict__ b, const double2 *__restrict__ q, const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ z,
@@ -2411,7 +2523,8 @@ __global__ void __launch_bounds__(BLOCK)
 k_pred_diff(size_t ndof, const double *__restrict__ x, const double *__restrict__ xprev, const double *__restrict__ dinv,
             double *__restrict__ d, const CgScalars *__restrict__ sc)
 {
-    if (sc->done) return;   // the plain start satisfies the tolerance: nothing to interpolate (enqueued before the host knows)
+    if (sc && sc->done) return;   // the plain start satisfies the tolerance: nothing to interpolate (enqueued before the host knows;
+                                  // sc == nullptr: in front of the fused start, where that test has not run yet)
     for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK)
         d[i] = (dinv[i] != 0.) ? x[i] - xprev[i] : 0.;   // (the Dirichlet set may have changed since xprev was a solution)
 }
