@@ -235,10 +235,9 @@ struct plfx_ctx {
     // plfx_load_step, single GPU: the set-up pass of the next stiffness iteration and the K du of the end of the load step are
     // enqueued behind k_sweep_flags with device-side predicates, before the host has read the flags
     bool spec_arm = false, spec_setup = false, spec_kdu = false, spec_was_clean = false;
-    // plfx_load_step tells plfx_solve which of its two solves this is (0 predictor of the load step, 1 stiffness iteration;
+    // plfx_load_step tells the solver which of its two solves this is (site 0 predictor of the load step, 1 stiffness iteration;
     // -1 any other caller); first_test_hint[site]: the last solve of that kind was answered by the test of the plain warm start
     // -- the next one waits for that test before it enqueues the six launches of the interpolated start behind it
-    int solve_site = -1;
     bool first_test_hint[2] = {false, false};
     int spec_h0 = 0, spec_h1 = 0;
     CgScalars *spec_sc = nullptr;
@@ -296,7 +295,6 @@ struct plfx_ctx {
     double *gm_part2 = nullptr, *gm_red = nullptr, *gm_coef = nullptr;   // delayed re-orthogonalisation: partials of all columns, their sums, coefficients
     long long n_gmres_its = 0;
     int n_gmres = 0, gm_m = 0;
-    double *fuse_rz = nullptr;  // != null during a V-cycle of the PCG loop: the last fine-level post-smoothing launch writes the r.z partials here
     bool strip_jacobi = false;  // strip-local engine during such a fall-back: the V-cycle is replaced by z = D^-1 r
     int grid_nodes = 0, grid_el = 0;
 
@@ -1315,8 +1313,9 @@ int mg_down_level(plfx_ctx *c, int l)
     return 0;
 }
 
-// one level of the up leg: prolongation from level l+1, nu post-smoothing sweeps
-int mg_up_level(plfx_ctx *c, int l)
+// one level of the up leg: prolongation from level l+1, nu post-smoothing sweeps.  rz_part (level 0, may be null): the last
+// post-smoothing launch writes the r.z partials there if it can, and *wrote says whether it did
+int mg_up_level(plfx_ctx *c, int l, double *rz_part, bool *wrote)
 {
     const double om = c->mg_omega;
     auto &L = c->mg[l];
@@ -1330,12 +1329,12 @@ int mg_up_level(plfx_ctx *c, int l)
         EvPair *ev = nullptr;
         if (l == 0) tim_begin(c, 5, &ev);  // family 5: fine-level smoother launches
         DotOut dot{};
-        if (l == 0 && k == nu - 1 && c->fuse_rz && !(nu & 1) && L.grid <= c->grid_nodes) {  // (even nu: the last launch writes L.x = z)
-            dot.part = c->fuse_rz;
+        if (l == 0 && k == nu - 1 && rz_part && !(nu & 1) && L.grid <= c->grid_nodes) {  // (even nu: the last launch writes L.x = z)
+            dot.part = rz_part;
             dot.nslots = c->grid_nodes;
             dot.own_lo = own_lo(c);
             dot.own_hi = own_hi(c);
-            c->fuse_rz = nullptr;  // consumed: the caller launches k_dot_rz itself if this is still set
+            *wrote = true;  // (otherwise the caller launches k_dot_rz itself)
         }
         if (l == 0 && mf && march_mg(c))
             hipLaunchKernelGGL(k_mg_smooth_march, dim3(L.grid), dim3(BLOCK), 0, c->stream, L.op, (const double2 *)L.dinv,
@@ -1374,7 +1373,7 @@ int mg_coarse_part(plfx_ctx *c)
                 if (leg == 0)
                     for (int l = 1; l < lt && !rc; l++) rc = mg_down_level(c, l);
                 else
-                    for (int l = lt - 1; l >= 1 && !rc; l--) rc = mg_up_level(c, l);
+                    for (int l = lt - 1; l >= 1 && !rc; l--) rc = mg_up_level(c, l, nullptr, nullptr);
                 const hipError_t e = hipStreamEndCapture(c->stream, &g);
                 if (rc) return rc;
                 if (e != hipSuccess || !g) return fail(c, PLFX_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
@@ -1438,7 +1437,7 @@ int mg_coarse_part(plfx_ctx *c)
                                4 * L.nnode + 20, 1.e-10, c->sc);
     }
     for (int l = lt - 1; l >= 1; l--)
-        if ((rc = mg_up_level(c, l))) return rc;
+        if ((rc = mg_up_level(c, l, nullptr, nullptr))) return rc;
     return 0;
 }
 
@@ -1492,7 +1491,8 @@ int mg_vcycle_head(plfx_ctx *c)
 // INVARIANT: only the finest level's kernels test sc->done.  The levels >= 1, the hipGraph replay and a strip's
 // child context (which shares c->sc) must therefore never be enqueued speculatively or while the flag is sticky: every caller
 // of mg_vcycle_rest has either seen done == 0 from cg_check_wait or has just cleared it (k_cg_setup, plfx_precond_bench).
-int mg_vcycle_rest(plfx_ctx *c)
+// rz_part (may be null): where the last fine-level post-smoothing launch writes the r.z partials if it can; *wrote: whether it did
+int mg_vcycle_rest(plfx_ctx *c, double *rz_part, bool *wrote)
 {
     if (c->strip_jacobi) {  // Jacobi fall-back of a strip: same PCG loop, same exchanges, z = D^-1 r on the local grid
         hipLaunchKernelGGL(k_jacobi_z, dim3(grid_for(c->nnode)), dim3(BLOCK), 0, c->stream, c->nnode, (const double2 *)c->dinv,
@@ -1521,7 +1521,7 @@ int mg_vcycle_rest(plfx_ctx *c)
         if ((rc = mg_coarse_part(c))) return rc;
     }
     if (lt >= 1) {
-        if ((rc = mg_up_level(c, 0))) return rc;
+        if ((rc = mg_up_level(c, 0, rz_part, wrote))) return rc;
     }
     HIPCHK(c, hipGetLastError());
     return 0;
@@ -1533,7 +1533,7 @@ int mg_vcycle(plfx_ctx *c)
     if (rc) return rc;
     rc = mg_vcycle_head(c);
     if (rc) return rc;
-    return mg_vcycle_rest(c);
+    return mg_vcycle_rest(c, nullptr, nullptr);
 }
 
 
@@ -3263,7 +3263,7 @@ int plfx_precond_bench(plfx_ctx *c, int reps, double *us_per_cycle, double *us_c
         const int lt = (c->mg_tail > 0) ? c->mg_tail : nl - 1;
         auto coarse_only = [&]() -> int {
             if (lt < 2 || !c->want_mg_graph) return mg_coarse_part(c);
-            if (!c->mg_graph_exec) return mg_vcycle_rest(c);  // (captures the graph; not reached after the cycles above)
+            if (!c->mg_graph_exec) return mg_vcycle_rest(c, nullptr, nullptr);  // (captures the graph; not reached after the cycles above)
             return hipGraphLaunch(c->mg_graph_exec, c->stream) == hipSuccess ? 0 : PLFX_ERR_HIP;
         };
         auto &L = c->mg[0];
@@ -3795,6 +3795,8 @@ int plfx_set_bc_sources(plfx_ctx *c, int nseg, const int32_t *src, const int32_t
 
 namespace {
 
+int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *iters, double *relres);
+
 // calc_BC through the registered plan for the current increments; returns the first inconsistent entry or -1
 int step_apply_bc(plfx_ctx *c, const plfx_step *st, const double *dbcr, const double *dbct, const double *dbcn, int *bad)
 {
@@ -3821,11 +3823,12 @@ int step_apply_bc(plfx_ctx *c, const plfx_step *st, const double *dbcr, const do
     return rc;
 }
 
-int step_solve(plfx_ctx *c, plfx_step *st, int warm)
+// site: which of the two solves of a load step this is (0 predictor, 1 stiffness iteration; plfx_ctx::first_test_hint)
+int step_solve(plfx_ctx *c, plfx_step *st, int warm, int site)
 {
     int it = 0;
     double rr = 0.;
-    const int rc = plfx_solve(c, st->rtol, st->maxit, warm, &it, &rr);
+    const int rc = solve_impl(c, st->rtol, st->maxit, warm, site, &it, &rr);
     if (rc < 0) return rc;
     if (st->nsolves < 40) {
         st->its[st->nsolves] = it;
@@ -3851,8 +3854,7 @@ int plfx_load_step(plfx_ctx *c, plfx_step *st, double *u_at, double *f_at, doubl
     double *dbcn = st->max_dbcn;  // the reference's dbcn IS max_dbcn (alias, model.py:1285)
     // elastic predictor with the stiffness of the previous step (model.py:1290-1291)
     if ((rc = step_apply_bc(c, st, dbcr, dbct, dbcn, &st->inconsistent_entry))) return rc;
-    c->solve_site = 0;
-    if ((rc = step_solve(c, st, st->warm))) return rc;
+    if ((rc = step_solve(c, st, st->warm, 0))) return rc;
     if (st->nonlin) {
         if (st->il < 10) {  // calc_scf (model.py:1036-1067, 1296)
             int64_t cnt = 0;
@@ -3890,8 +3892,7 @@ int plfx_load_step(plfx_ctx *c, plfx_step *st, double *u_at, double *f_at, doubl
             }
             if ((rc = plfx_assemble(c))) return rc;  // updated tangent stiffness (model.py:1333)
             if ((rc = step_apply_bc(c, st, dbcr, dbct, dbcn, &st->inconsistent_entry))) return rc;
-            c->solve_site = 1;
-            if ((rc = step_solve(c, st, 1))) return rc;
+            if ((rc = step_solve(c, st, 1, 1))) return rc;
             // (the loop goes on after this sweep only if nit + 1 <= 15: then -- and only then -- what follows the flags is decided
             // by the flags alone and can be enqueued behind them with device-side predicates)
             c->spec_arm = (nit + 1 <= 15) && c->reuse && !wh_sequential(c);
@@ -4205,14 +4206,19 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
             if (comm_active(c) && c->strip.on && (e = allreduce(c, c->gm_red, (size_t)ncol, NCCL_FLOAT64, NCCL_SUM, "GMRES sums"))) return e;
             return fetch_results(c, c->gm_red, ncol, red.data());
         };
+        // c->q = K B v (through c->r, c->z).  Defined behind the cycle's k_cg_start, as the launches it replaces were: the kernel
+        // templates appear in the code object in the order of their first use, and that order is kept
+        auto apply_A = [&](const double *v) -> int {
+            hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)v, (double2 *)c->r, (double2 *)nullptr);
+            if (const int e = apply_B()) return e;
+            LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
+                       (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
+            HIPCHK(c, hipGetLastError());
+            return 0;
+        };
         // first step: w_0 = A q_0; h1 = q_0 . w_0; candidate u_1 = w_0 - q_0 h1 -> V_1
         itn++;
-        hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)Vj(0),
-                           (double2 *)c->r, (double2 *)nullptr);
-        if ((rc = apply_B())) return rc;
-        LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
-                   (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
-        HIPCHK(c, hipGetLastError());
+        if ((rc = apply_A(Vj(0)))) return rc;
         if ((rc = need(1))) return rc;
         if ((rc = dots(1, c->q, nullptr))) return rc;
         h1p.assign(1, red[0]);
@@ -4227,12 +4233,7 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
             const bool more = j < M && itn < maxit;   // another basis vector may still be built after this one
             // z = A u -> c->q   (the operator application of iteration j + 1, on the candidate: one ahead of the finished basis)
             itn++;
-            hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)Vj(j),
-                               (double2 *)c->r, (double2 *)nullptr);
-            if ((rc = apply_B())) return rc;
-            LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
-                       (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
-            HIPCHK(c, hipGetLastError());
+            if ((rc = apply_A(Vj(j)))) return rc;
             if ((rc = dots(j, Vj(j), c->q))) return rc;
             double ss = 0., st = 0.;
             for (int q = 0; q < j; q++) {
@@ -4326,37 +4327,75 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
     }
 }
 
-}  // namespace
-
-int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double *relres)
-{
-    if (!c || !c->bc_set) return c ? fail(c, PLFX_ERR_STATE, "apply_bc first") : PLFX_ERR_STATE;
-    c->spec_setup = c->spec_kdu = false;   // (a solve overwrites c->q: nothing enqueued behind a sweep's flags is valid beyond it)
-    const int solve_site_in = c->solve_site;
-    c->solve_site = -1;
-    if (maxit < 1) maxit = 1;
-    if (c->reuse && warm && c->x_is_du && c->memo.valid && c->memo.rtol == rtol) {
-        // the system of the previous converged solve (no assembly, no other boundary values since): du is its solution
-        c->n_reuse_solve++;
-        if (iters) *iters = 0;
-        if (relres) *relres = c->memo.relres;
-        return PLFX_OK;
-    }
-    const size_t nd = c->ndof;
-    const int nn = c->nnode;
-    const int gn = c->grid_nodes;
+// What one solve carries from phase to phase (solve_impl and the functions it calls): a plain aggregate on the stack.
+struct SolveRun {
     // partial-sum slots; r.z[1], r.r[1], b.b (written together by k_cg_start) are contiguous: one all-reduce in a strip
-    double *P_pq = c->part, *P_rz[2] = {c->part + MAXPART, c->part + 3 * MAXPART},
-           *P_rr[2] = {c->part + 2 * MAXPART, c->part + 4 * MAXPART}, *P_bb = c->part + 5 * MAXPART;
-    const int olo = own_lo(c), ohi = own_hi(c);
-    if (c->strip.on && !mg_active(c)) return fail(c, PLFX_ERR_STATE, "a strip solves with the multigrid preconditioner only");
-    // Sharded run with the assembled operator: every rank applies its own rows, one all-reduce of the global vector per
-    // CG step.  With the matrix-free operator every rank holds all generators and a full K p costs ~50 us at 1024^2 --
-    // several times less than all-reducing 16.8 MB over xGMI -- so the product is computed redundantly and the solve has
-    // no collective at all (PLFX_SHARD_SPMV=1 restores the sharded rows + all-reduce).
-    static const bool force_shard_spmv = getenv("PLFX_SHARD_SPMV") && atoi(getenv("PLFX_SHARD_SPMV")) != 0;
-    const bool multi = comm_active(c) && (!matfree(c) || force_shard_spmv);
-    // x0
+    double *P_pq, *P_rz[2], *P_rr[2], *P_bb;
+    int olo, ohi, gn, nn;
+    size_t nd;
+    bool multi, mg;   // sharded SpMV (one all-reduce of q per CG step); multigrid-PCG (a strip's Jacobi fall-back included)
+    CgScalars hs;
+    int done, it;
+    bool pred_active, pred_fused;    // a history exists: this solve may be answered by x + alpha d; K d came with the start kernel's pass
+    bool pred_d_ready, pred_moved;   // (d = x - pred_x is in pred_d; the start x + alpha d was accepted as the solution)
+    bool pred_finished;              // (... and k_pred_finish has composed du and advanced the history already)
+};
+
+bool solve_debug_on() { static const bool on = getenv("PLFX_SOLVE_DEBUG") && atoi(getenv("PLFX_SOLVE_DEBUG")) != 0; return on; }
+
+// z = (the rest of the V-cycle)(r) and the partials of r.z in `slot`: written by the last post-smoothing launch of the cycle
+// where that can be done, by k_dot_rz otherwise; all-reduced in a strip.  `vcycle_ev` (may be null) closes the timing of the cycle.
+int precondition_rz(plfx_ctx *c, double *slot, EvPair *vcycle_ev = nullptr)
+{
+    bool fused = false;
+    const int rc = mg_vcycle_rest(c, slot, &fused);
+    tim_end(c, vcycle_ev);
+    if (rc) return rc;
+    if (!fused)
+        hipLaunchKernelGGL(k_dot_rz, dim3(c->grid_nodes), dim3(BLOCK), 0, c->stream, own_lo(c), own_hi(c), (const double2 *)c->r,
+                           (const double2 *)c->z, slot);
+    return part_allreduce(c, slot, c->grid_nodes);
+}
+
+// p = z + beta p_old and q = K p of iteration `it`, partials of p.q
+void launch_direction(plfx_ctx *c, const SolveRun &s, int it)
+{
+    const int cur = it & 1, prev = cur ^ 1;  // (cur: the partial slot written by this iteration's update kernel)
+    const double2 *pold = (const double2 *)c->p[prev];
+    double2 *pnew = (double2 *)c->p[cur];
+    if (!s.multi && march_pcg(c)) {  // marching form of the matrix-free operator (bit-identical q, p)
+        if (it == 0)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_march<2>), dim3(s.gn), dim3(BLOCK), 0, c->stream, c->op, pold, (const double2 *)c->z,
+                               pnew, (double2 *)c->q, s.P_rz[prev], s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_march<1>), dim3(s.gn), dim3(BLOCK), 0, c->stream, c->op, pold, (const double2 *)c->z,
+                               pnew, (double2 *)c->q, s.P_rz[prev], s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
+    } else if (it == 0 && !s.multi)  // first iteration: p = z, p_old untouched
+        LAUNCH_OP2(k_spmv, 2, matfree(c), dim3(s.gn), c->op, 0, s.nn, pold, (const double2 *)c->z, pnew, (double2 *)c->q, s.P_rz[prev],
+                   s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
+    else
+        LAUNCH_OP2(k_spmv, 1, matfree(c), dim3(s.gn), c->op, s.multi ? c->own_n0 : 0, s.multi ? c->own_n1 : s.nn, pold, (const double2 *)c->z,
+                   pnew, (double2 *)c->q, s.P_rz[prev], s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
+}
+
+// du = x on the free DOFs, the prescribed values elsewhere (strip: x is valid on owned + 2 columns: complete the halo first)
+int compose_du(plfx_ctx *c)
+{
+    int rc;
+    if (c->strip.on && (rc = halo_refresh(c, c->x))) return rc;
+    hipLaunchKernelGGL(k_compose_du, dim3(grid_for(c->ndof)), dim3(BLOCK), 0, c->stream, c->ndof, c->x, c->dup, c->is_presc, c->du);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// the system just solved, for the shortcut at the top of solve_impl
+void remember(plfx_ctx *c, double rtol, double relres, bool valid) { c->memo = {valid, rtol, relres}; }
+
+// x0, the history of the initial guess, r0 (and z0 or K d), the scalars of a Jacobi-PCG solve
+int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
+{
+    const size_t nd = s.nd;
+    const int nn = s.nn, gn = s.gn;
     // x0: the previous solution restricted to the free DOFs is still in c->x when neither du nor the Dirichlet set changed
     const bool x_kept = warm && c->x_is_du;
     if (!x_kept)
@@ -4377,17 +4416,14 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
     // than the extra passes and the host round trips (>= 16384 nodes; the reference traces of the parity tests, <= 32 x 32
     // elements, run the plain warm start).  Strips: x and the solution before it are valid on the halo columns, the sums are
     // taken over the owned columns and all-reduced (host_sums / part_allreduce).  PLFX_PREDICT=0 at plfx_create switches it off.
-    bool pred_d_ready = false, pred_moved = false;   // (d = x - pred_x is in pred_d; the start x + alpha d was accepted as the solution)
-    bool pred_finished = false;                      // (... and k_pred_finish has composed du and advanced the history already)
     // (every rank of a communicator takes the same decisions: the global node count and -- through the all-reduced sums -- alpha
     // and the test are the same everywhere; a replicated solve computes everything redundantly)
     const long long nn_global = c->strip.on ? (long long)(c->strip.gnx + 1) * (c->gy + 1) : (long long)c->nnode;
-    bool pred_active = false;   // a history exists: this solve may be answered by x + alpha d
-    if (c->predict && warm && !multi && mg_active(c) && nn_global >= 16384) {
+    if (c->predict && warm && !s.multi && mg_active(c) && nn_global >= 16384) {
         if (!c->pred_x && (rc = dalloc(c, &c->pred_x, nd))) return rc;
         if (!c->pred_d && (rc = dalloc(c, &c->pred_d, nd))) return rc;
         if (c->pred_valid)
-            pred_active = true;
+            s.pred_active = true;
         else {
             HIPCHK(c, hipMemcpyAsync(c->pred_x, c->x, 8 * nd, hipMemcpyDeviceToDevice, c->stream));
             c->pred_valid = true;
@@ -4399,129 +4435,117 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
     // whose last solve was answered by the plain start (the predictor solve of a load step) keeps k_cg_start: it would pay for a
     // K d that nobody reads.  Matrix-free operator with cells all alike, one GPU, no strip.  If the plain start passes after
     // all, pred_d and p[0] hold a d and a K d that nothing reads: pred_d_ready stays false, the next solve forms its own.
-    const bool pred_fused = pred_active && matfree(c) && !c->op.colr && !c->strip.on && !comm_active(c) && solve_site_in >= 0 &&
-                            !c->first_test_hint[solve_site_in];
-    if (pred_fused) {
+    s.pred_fused = s.pred_active && matfree(c) && !c->op.colr && !c->strip.on && !comm_active(c) && site >= 0 && !c->first_test_hint[site];
+    if (s.pred_fused) {
         // d = x - (solution before) first (k_pred_diff without the flag: the test of this solve has not run yet), then
         // r = P(b - K x) and K d -> p[0]; partials of r.r and b.b -> slot 1 (z and r.z: written by the V-cycle if there is one)
         hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d,
                            (const CgScalars *)nullptr);
         hipLaunchKernelGGL(k_cg_start_pred, dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, (const double2 *)c->x, (const double2 *)c->pred_d,
-                           (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], P_rr[1], P_bb);
+                           (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], s.P_rr[1], s.P_bb);
     } else   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
         LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, warm ? 1 : 0, (const double2 *)c->x, (const double2 *)c->rhs,
-                   (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, P_rz[1], P_rr[1], P_bb, olo, ohi);
+                   (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, s.olo, s.ohi);
     if (c->strip.on) {  // sums of the whole grid; r valid on every local column (the V-cycle reads the halo)
-        if ((rc = part_allreduce(c, P_rz[1], (size_t)3 * MAXPART))) return rc;
+        if ((rc = part_allreduce(c, s.P_rz[1], (size_t)3 * MAXPART))) return rc;
         if ((rc = halo_refresh(c, c->r))) return rc;
     }
-    const double rtol_eff = rtol;
-    const bool mg = mg_active(c);
-    if (!mg) hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, P_bb, gn, rtol_eff, c->sc);
-    CgScalars hs{};
-    int done = 0;
-    int pred_site = -1;
-    bool pred_first_passed = false;
-    if (mg) {  // z0 = V-cycle(r0) replaces the Jacobi z of k_cg_init -- unless x0 already satisfies the tolerance
-        unsigned long long seq = cg_setup_check_post(c, P_bb, P_rr[1], gn, rtol_eff);   // (scalars set up and first test: one launch)
-        const int site = pred_site = solve_site_in;
-        bool first_passed = false;
-        static const bool wait_first = !(getenv("PLFX_WAIT_FIRST") && atoi(getenv("PLFX_WAIT_FIRST")) == 0);   // (0: always speculate, as before)
-        if (wait_first && pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on) {
-            // the predictor solve of a load step repeats the system of the solve before it up to the last bits of its boundary
-            // values: x passes the first test.  Learn that before enqueuing what would return at once (six launches, 28 us)
-            if ((rc = cg_check_wait(c, seq, &hs))) return rc;
-            done = hs.done;
-            first_passed = done != 0;
-        }
-        if (first_passed) {
-            pred_first_passed = true;   // (nothing to do: done, hs as the chain below would have left them)
-        } else if (pred_active) {
-            // Everything the interpolated start needs is enqueued behind the first test and returns at once if that test passed
-            // (the reference repeats solves of one system: x satisfies the tolerance as it is); the host waits ONCE, for the second
-            // test (round 6: three round trips -> one).  d = x - (solution before), K d, the two sums, alpha on the device
-            // (k_pred_alpha), | P (r - alpha K d) |^2 into the free slot P_rr[0] without touching x, r, z, the test on it.
-            if (!pred_fused) {   // (the fused start has left d in pred_d and K d in p[0])
-                hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
-                LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)c->pred_d, nullptr, nullptr, (double2 *)c->p[0],
-                           nullptr, nullptr, nullptr, 0, nullptr, c->sc, 0, 0, 0);
-            }
-            const int gp = MAXPART;   // (one size on every rank: the all-reduce of the partial sums pairs up)
-            hipLaunchKernelGGL(k_pred_dots, dim3(gp), dim3(BLOCK), 0, c->stream, (size_t)2 * olo, (size_t)2 * ohi, c->dinv, c->r, c->p[0],
-                               c->part, c->sc);
-            HIPCHK(c, hipGetLastError());
-            if (c->strip.on && (rc = part_allreduce(c, c->part, (size_t)2 * MAXPART))) return rc;
-            hipLaunchKernelGGL(k_pred_try, dim3(gn), dim3(BLOCK), 0, c->stream, nn, c->sc, (const double *)c->part, gp, (const double2 *)c->r,
-                               (const double2 *)c->p[0], (const double2 *)c->dinv, P_rr[0], olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            if (c->strip.on && (rc = part_allreduce(c, P_rr[0], gn))) return rc;
-            seq = cg_check_post(c, P_rr[0], gn, -2);   // (iters = -2 marks "converged by the interpolated start")
-            if (!c->strip.on)   // x, du and the history in one pass -- behind the test, before the host has seen it (no-op unless accepted)
-                hipLaunchKernelGGL(k_pred_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x,
-                                   (const double *)c->pred_d, c->pred_x, (const double *)c->dup, (const double *)c->is_presc, c->du);
-            if ((rc = cg_check_wait(c, seq, &hs))) return rc;
-            done = hs.done;
-            if (done == 1 && hs.iters == -2) {   // it is the solution: commit x (r, z are not read again: the loop below is skipped)
-                if (!c->strip.on)
-                    pred_finished = true;
-                else
-                    hipLaunchKernelGGL(k_pred_commit, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x, c->pred_d);
-                HIPCHK(c, hipGetLastError());
-                hs.iters = 0;
-                c->n_pred++;
-                pred_d_ready = true;
-                pred_moved = true;
-            } else if (!done) {
-                pred_d_ready = true;
-                if (hs.aux > 0.) c->n_pred_rejected++;
-                else c->n_pred_skipped++;
-            }
-            if (!done) {
-                if ((rc = mg_ensure(c))) return rc;
-                if ((rc = mg_vcycle_head(c))) return rc;
-            }
-            pred_first_passed = done == 1 && !pred_moved;
-        } else if (c->mg_pending) {
-            // the coarse levels are stale (mg_ensure): learn first whether a V-cycle is needed at all
-            if ((rc = cg_check_wait(c, seq, &hs))) return rc;
-            done = hs.done;
-            if (!done) {
-                if ((rc = mg_ensure(c))) return rc;
-                if ((rc = mg_vcycle_head(c))) return rc;
-            }
-        } else {
-            if ((rc = mg_vcycle_head(c))) return rc;  // speculative: its kernels return at once if the flag says converged
-            if ((rc = cg_check_wait(c, seq, &hs))) return rc;
-            done = hs.done;
-        }
-    }
-    if (mg && pred_site >= 0 && pred_active) c->first_test_hint[pred_site] = pred_first_passed;
-    if (mg && !done) {
-        c->fuse_rz = P_rz[1];  // r.z partials from the last post-smoothing launch of the cycle
-        rc = mg_vcycle_rest(c);
-        const bool fused = c->fuse_rz == nullptr;
-        c->fuse_rz = nullptr;
-        if (rc) return rc;
-        if (!fused)
-            hipLaunchKernelGGL(k_dot_rz, dim3(gn), dim3(BLOCK), 0, c->stream, olo, ohi, (const double2 *)c->r,
-                               (const double2 *)c->z, P_rz[1]);
-        if ((rc = part_allreduce(c, P_rz[1], gn))) return rc;
-    }
-    // beta of the first iteration is 0 (k_spmv<1> takes p = z for it == 0 without touching p_old); only the sharded
-    // k_p_update_outside path still derives it from the partials: rz_old = +inf, p_old = 0
-    if (multi) {
-        hipLaunchKernelGGL(k_fill, dim3(1), dim3(BLOCK), 0, c->stream, P_rz[0], (size_t)gn, (double)INFINITY);
-        HIPCHK(c, hipMemsetAsync(c->p[1], 0, 8 * nd, c->stream));
-    }
-    HIPCHK(c, hipGetLastError());
+    if (!s.mg) hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, s.P_bb, gn, rtol, c->sc);
+    return 0;
+}
 
+// multigrid-PCG: z0 = V-cycle(r0) replaces the Jacobi z of k_cg_init -- unless x0 already satisfies the tolerance.  Leaves
+// s.done / s.hs as the host saw them and, while not done, the head of the V-cycle enqueued.
+int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
+{
+    const size_t nd = s.nd;
+    const int nn = s.nn, gn = s.gn, olo = s.olo, ohi = s.ohi;
+    int rc;
+    bool first_passed = false, pred_first_passed = false;
+    unsigned long long seq = cg_setup_check_post(c, s.P_bb, s.P_rr[1], gn, rtol);   // (scalars set up and first test: one launch)
+    static const bool wait_first = !(getenv("PLFX_WAIT_FIRST") && atoi(getenv("PLFX_WAIT_FIRST")) == 0);   // (0: always speculate, as before)
+    if (wait_first && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on) {
+        // the predictor solve of a load step repeats the system of the solve before it up to the last bits of its boundary
+        // values: x passes the first test.  Learn that before enqueuing what would return at once (six launches, 28 us)
+        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
+        s.done = s.hs.done;
+        first_passed = s.done != 0;
+    }
+    if (first_passed) {
+        pred_first_passed = true;   // (nothing to do: done, hs as the chain below would have left them)
+    } else if (s.pred_active) {
+        // Everything the interpolated start needs is enqueued behind the first test and returns at once if that test passed
+        // (the reference repeats solves of one system: x satisfies the tolerance as it is); the host waits ONCE, for the second
+        // test (round 6: three round trips -> one).  d = x - (solution before), K d, the two sums, alpha on the device
+        // (k_pred_alpha), | P (r - alpha K d) |^2 into the free slot P_rr[0] without touching x, r, z, the test on it.
+        if (!s.pred_fused) {   // (the fused start has left d in pred_d and K d in p[0])
+            hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
+            LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)c->pred_d, nullptr, nullptr, (double2 *)c->p[0],
+                       nullptr, nullptr, nullptr, 0, nullptr, c->sc, 0, 0, 0);
+        }
+        const int gp = MAXPART;   // (one size on every rank: the all-reduce of the partial sums pairs up)
+        hipLaunchKernelGGL(k_pred_dots, dim3(gp), dim3(BLOCK), 0, c->stream, (size_t)2 * olo, (size_t)2 * ohi, c->dinv, c->r, c->p[0],
+                           c->part, c->sc);
+        HIPCHK(c, hipGetLastError());
+        if (c->strip.on && (rc = part_allreduce(c, c->part, (size_t)2 * MAXPART))) return rc;
+        hipLaunchKernelGGL(k_pred_try, dim3(gn), dim3(BLOCK), 0, c->stream, nn, c->sc, (const double *)c->part, gp, (const double2 *)c->r,
+                           (const double2 *)c->p[0], (const double2 *)c->dinv, s.P_rr[0], olo, ohi);
+        HIPCHK(c, hipGetLastError());
+        if (c->strip.on && (rc = part_allreduce(c, s.P_rr[0], gn))) return rc;
+        seq = cg_check_post(c, s.P_rr[0], gn, -2);   // (iters = -2 marks "converged by the interpolated start")
+        if (!c->strip.on)   // x, du and the history in one pass -- behind the test, before the host has seen it (no-op unless accepted)
+            hipLaunchKernelGGL(k_pred_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x,
+                               (const double *)c->pred_d, c->pred_x, (const double *)c->dup, (const double *)c->is_presc, c->du);
+        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
+        s.done = s.hs.done;
+        if (s.done == 1 && s.hs.iters == -2) {   // it is the solution: commit x (r, z are not read again: the loop is skipped)
+            if (!c->strip.on)
+                s.pred_finished = true;
+            else
+                hipLaunchKernelGGL(k_pred_commit, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x, c->pred_d);
+            HIPCHK(c, hipGetLastError());
+            s.hs.iters = 0;
+            c->n_pred++;
+            s.pred_d_ready = true;
+            s.pred_moved = true;
+        } else if (!s.done) {
+            s.pred_d_ready = true;
+            if (s.hs.aux > 0.) c->n_pred_rejected++;
+            else c->n_pred_skipped++;
+        }
+        if (!s.done) {
+            if ((rc = mg_ensure(c))) return rc;
+            if ((rc = mg_vcycle_head(c))) return rc;
+        }
+        pred_first_passed = s.done == 1 && !s.pred_moved;
+    } else if (c->mg_pending) {
+        // the coarse levels are stale (mg_ensure): learn first whether a V-cycle is needed at all
+        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
+        s.done = s.hs.done;
+        if (!s.done) {
+            if ((rc = mg_ensure(c))) return rc;
+            if ((rc = mg_vcycle_head(c))) return rc;
+        }
+    } else {
+        if ((rc = mg_vcycle_head(c))) return rc;  // speculative: its kernels return at once if the flag says converged
+        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
+        s.done = s.hs.done;
+    }
+    if (site >= 0 && s.pred_active) c->first_test_hint[site] = pred_first_passed;
+    return 0;
+}
+
+// the PCG loop: at most `maxit` iterations from s.it = 0, until the flag says done
+int pcg_iterate(plfx_ctx *c, SolveRun &s, int maxit)
+{
+    const int nn = s.nn, gn = s.gn, olo = s.olo, ohi = s.ohi;
+    const bool mg = s.mg, multi = s.multi;
+    double *const P_pq = s.P_pq, *const *P_rz = s.P_rz, *const *P_rr = s.P_rr;
+    CgScalars &hs = s.hs;
+    int rc;
     const int chunk = mg ? 1 : 50;  // multigrid: the flag is polled inside the iteration, before the V-cycle
-    const int maxit_all = maxit;
-    // multigrid-PCG converges in tens of iterations or not at all (PLFX_MG_MAXIT: the cap, for tests of the fall-back)
-    const int mg_cap = getenv("PLFX_MG_MAXIT") ? std::max(1, atoi(getenv("PLFX_MG_MAXIT"))) : 300;
-    if (mg && !c->strip_jacobi) maxit = std::min(maxit, mg_cap);
-    int it = 0;
-    while (it < maxit && !done) {
+    int &it = s.it;
+    while (it < maxit && !s.done) {
         const int stop = std::min(maxit, it + chunk);
         for (; it < stop; it++) {
             const int cur = it & 1;  // partial slot written by this iteration's update kernel
@@ -4529,29 +4553,14 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
             double *pold = c->p[prev], *pnew = c->p[cur];
             EvPair *ev;
             tim_begin(c, 1, &ev);
-            if (!multi && march_pcg(c)) {  // marching form of the matrix-free operator (bit-identical q, p)
-                if (it == 0)
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_march<2>), dim3(gn), dim3(BLOCK), 0, c->stream, c->op, (const double2 *)pold,
-                                       (const double2 *)c->z, (double2 *)pnew, (double2 *)c->q, P_rz[prev], P_rz[cur], P_rr[prev], gn,
-                                       P_pq, c->sc, it, olo, ohi);
-                else
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_march<1>), dim3(gn), dim3(BLOCK), 0, c->stream, c->op, (const double2 *)pold,
-                                       (const double2 *)c->z, (double2 *)pnew, (double2 *)c->q, P_rz[prev], P_rz[cur], P_rr[prev], gn,
-                                       P_pq, c->sc, it, olo, ohi);
-            } else if (it == 0 && !multi)  // first iteration: p = z, p_old untouched
-                LAUNCH_OP2(k_spmv, 2, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)pold, (const double2 *)c->z,
-                           (double2 *)pnew, (double2 *)c->q, P_rz[prev], P_rz[cur], P_rr[prev], gn, P_pq, c->sc, it, olo, ohi);
-            else
-                LAUNCH_OP2(k_spmv, 1, matfree(c), dim3(gn), c->op, multi ? c->own_n0 : 0, multi ? c->own_n1 : nn,
-                           (const double2 *)pold, (const double2 *)c->z, (double2 *)pnew, (double2 *)c->q, P_rz[prev],
-                           P_rz[cur], P_rr[prev], gn, P_pq, c->sc, it, olo, ohi);
+            launch_direction(c, s, it);
             tim_end(c, ev);
             if ((rc = part_allreduce(c, P_pq, gn))) return rc;
             if (multi) {
                 hipLaunchKernelGGL(k_p_update_outside, dim3(gn), dim3(BLOCK), 0, c->stream, nn, c->own_n0,
                                    c->own_n1, (const double2 *)pold, (const double2 *)c->z, (double2 *)pnew,
                                    (double2 *)c->q, P_rz[prev], P_rz[cur], P_rr[prev], gn, c->sc);
-                if ((rc = allreduce(c, c->q, nd, NCCL_FLOAT64, NCCL_SUM, "q"))) return rc;
+                if ((rc = allreduce(c, c->q, s.nd, NCCL_FLOAT64, NCCL_SUM, "q"))) return rc;
                 hipLaunchKernelGGL(k_dot_pq, dim3(gn), dim3(BLOCK), 0, c->stream, nn, (const double2 *)pnew,
                                    (const double2 *)c->q, P_pq, c->sc);
             }
@@ -4577,16 +4586,7 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
                     it++;
                     break;
                 }
-                c->fuse_rz = P_rz[cur];
-                rc = mg_vcycle_rest(c);
-                const bool fused = c->fuse_rz == nullptr;
-                c->fuse_rz = nullptr;
-                tim_end(c, evv);
-                if (rc) return rc;
-                if (!fused)
-                    hipLaunchKernelGGL(k_dot_rz, dim3(gn), dim3(BLOCK), 0, c->stream, olo, ohi, (const double2 *)c->r,
-                                       (const double2 *)c->z, P_rz[cur]);
-                if ((rc = part_allreduce(c, P_rz[cur], gn))) return rc;
+                if ((rc = precondition_rz(c, P_rz[cur], evv))) return rc;
             } else {
                 tim_begin(c, 2, &ev);
                 hipLaunchKernelGGL(k_cg_update, dim3(gn), dim3(BLOCK), 0, c->stream, nn, (const double2 *)pnew,
@@ -4601,159 +4601,207 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
             HIPCHK(c, hipMemcpyAsync(&hs, c->sc, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, stream_sync(c));
         }
-        done = hs.done;
+        s.done = hs.done;
     }
-    static const bool solve_debug = getenv("PLFX_SOLVE_DEBUG") && atoi(getenv("PLFX_SOLVE_DEBUG")) != 0;
-    if (solve_debug && mg && done != 1) {  // what made multigrid-PCG give up: sums of the last iteration, NaN census
-        stream_sync(c);
-        std::vector<double> hp((size_t)6 * MAXPART), hv(nd);
-        hipMemcpy(hp.data(), c->part, hp.size() * 8, hipMemcpyDeviceToHost);
-        auto psum = [&](int slot) { double t = 0.; for (int i = 0; i < gn; i++) t += hp[(size_t)slot * MAXPART + i]; return t; };
-        auto census = [&](const double *dev, const char *name) {
-            hipMemcpy(hv.data(), dev, nd * 8, hipMemcpyDeviceToHost);
-            size_t nan = 0, neg = 0; double mx = 0., mn = 1e300;
-            for (size_t i = 0; i < nd; i++) { const double v = hv[i]; if (!(v == v)) nan++; else { if (v < 0.) neg++; mx = std::max(mx, std::fabs(v)); if (v != 0.) mn = std::min(mn, std::fabs(v)); } }
-            fprintf(stderr, "    %-5s nan %zu  negative %zu  max|.| %.3e  min nonzero|.| %.3e\n", name, nan, neg, mx, mn);
-        };
-        fprintf(stderr, "[plfx_solve] multigrid-PCG gave up after %d iterations: done %d rr_final %.3e thresh2 %.3e | p.q %.6e  r.z %.6e / %.6e  r.r %.6e / %.6e  b.b %.6e\n",
-                it, hs.done, hs.rr_final, hs.thresh2, psum(0), psum(1), psum(3), psum(2), psum(4), psum(5));
-        census(c->dinv, "dinv"); census(c->r, "r"); census(c->z, "z"); census(c->x, "x"); census(c->q, "q");
-        {
-            std::vector<double> hm((size_t)6 * c->nel_total);
-            hipMemcpy(hm.data(), matfree(c) ? c->Mop : c->Mel, hm.size() * 8, hipMemcpyDeviceToHost);
-            size_t nan = 0; double mx = 0.;
-            for (double v : hm) { if (!(v == v)) nan++; else mx = std::max(mx, std::fabs(v)); }
-            fprintf(stderr, "    generators nan %zu  max|.| %.3e\n", nan, mx);
-            // per element: smallest eigenvalue of the 3 x 3 generator matrix [XX XY XS; XY YY YS; XS YS SS] (PSD for a PSD tangent)
-            const size_t ne = c->nel_total;
-            size_t nneg = 0, worst = 0; double wv = 0.;
-            for (size_t e = 0; e < ne; e++) {
-                const bool pr = matfree(c);  // layout of the array read above
-                const double a = hm[gen_index(pr, 0, ne, e)], b = hm[gen_index(pr, 1, ne, e)], cc = hm[gen_index(pr, 2, ne, e)],
-                             d = hm[gen_index(pr, 3, ne, e)], f = hm[gen_index(pr, 4, ne, e)], g = hm[gen_index(pr, 5, ne, e)];
-                // Sylvester: leading minors
-                const double m1 = a, m2 = a * d - b * b, m3 = a * (d * g - f * f) - b * (b * g - f * cc) + cc * (b * f - d * cc);
-                const double sc1 = std::fabs(a) + std::fabs(d) + std::fabs(g);
-                const double bad = std::min(m1 / sc1, std::min(m2 / (sc1 * sc1), m3 / (sc1 * sc1 * sc1)));
-                if (bad < -1e-9) { nneg++; if (bad < wv) { wv = bad; worst = e; } }
-            }
-            fprintf(stderr, "    elements with an indefinite generator matrix: %zu of %zu (worst scaled minor %.3e at element %zu)\n", nneg, ne, wv, worst);
-            if (nneg && worst >= (size_t)c->e0 && worst < (size_t)c->e0 + c->nel) {
-                const size_t e = worst - c->e0, n = c->nel;
-                double v[21]; int ms = 0; double fy = 0.;
-                fprintf(stderr, "      class %d material %d kind %d  M =", (int)c->hcls_id[worst], c->hcls[c->hcls_id[worst]].mat, (int)c->hmat[c->hcls[c->hcls_id[worst]].mat].kind);
-                for (int k = 0; k < 6; k++) fprintf(stderr, " %.6e", hm[gen_index(matfree(c), k, ne, worst)]);
-                for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->sig + k * n + e, 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "\n      sig = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-                for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_sig + k * n + e, 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "\n      res_sig = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-                for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->epl + k * n + e, 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "\n      epl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-                for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_depl + k * n + e, 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "\n      res_depl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-                {
-                    double *tmp = nullptr;
-                    if (!dalloc(c, &tmp, 21 * n)) {
-                        hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), tmp, 0);
-                        hipStreamSynchronize(c->stream);
-                        for (int k = 0; k < 21; k++) hipMemcpy(&v[k], tmp + k * n + e, 8, hipMemcpyDeviceToHost);
-                        dfree(tmp);
-                    }
+    return 0;
+}
+
+// PLFX_SOLVE_DEBUG: what made multigrid-PCG give up: sums of the last iteration, NaN census
+void solve_debug_dump(plfx_ctx *c, const SolveRun &s)
+{
+    const size_t nd = s.nd;
+    const int gn = s.gn, it = s.it;
+    const CgScalars &hs = s.hs;
+    stream_sync(c);
+    std::vector<double> hp((size_t)6 * MAXPART), hv(nd);
+    hipMemcpy(hp.data(), c->part, hp.size() * 8, hipMemcpyDeviceToHost);
+    auto psum = [&](int slot) { double t = 0.; for (int i = 0; i < gn; i++) t += hp[(size_t)slot * MAXPART + i]; return t; };
+    auto census = [&](const double *dev, const char *name) {
+        hipMemcpy(hv.data(), dev, nd * 8, hipMemcpyDeviceToHost);
+        size_t nan = 0, neg = 0; double mx = 0., mn = 1e300;
+        for (size_t i = 0; i < nd; i++) { const double v = hv[i]; if (!(v == v)) nan++; else { if (v < 0.) neg++; mx = std::max(mx, std::fabs(v)); if (v != 0.) mn = std::min(mn, std::fabs(v)); } }
+        fprintf(stderr, "    %-5s nan %zu  negative %zu  max|.| %.3e  min nonzero|.| %.3e\n", name, nan, neg, mx, mn);
+    };
+    fprintf(stderr, "[plfx_solve] multigrid-PCG gave up after %d iterations: done %d rr_final %.3e thresh2 %.3e | p.q %.6e  r.z %.6e / %.6e  r.r %.6e / %.6e  b.b %.6e\n",
+            it, hs.done, hs.rr_final, hs.thresh2, psum(0), psum(1), psum(3), psum(2), psum(4), psum(5));
+    census(c->dinv, "dinv"); census(c->r, "r"); census(c->z, "z"); census(c->x, "x"); census(c->q, "q");
+    {
+        std::vector<double> hm((size_t)6 * c->nel_total);
+        hipMemcpy(hm.data(), matfree(c) ? c->Mop : c->Mel, hm.size() * 8, hipMemcpyDeviceToHost);
+        size_t nan = 0; double mx = 0.;
+        for (double v : hm) { if (!(v == v)) nan++; else mx = std::max(mx, std::fabs(v)); }
+        fprintf(stderr, "    generators nan %zu  max|.| %.3e\n", nan, mx);
+        // per element: smallest eigenvalue of the 3 x 3 generator matrix [XX XY XS; XY YY YS; XS YS SS] (PSD for a PSD tangent)
+        const size_t ne = c->nel_total;
+        size_t nneg = 0, worst = 0; double wv = 0.;
+        for (size_t e = 0; e < ne; e++) {
+            const bool pr = matfree(c);  // layout of the array read above
+            const double a = hm[gen_index(pr, 0, ne, e)], b = hm[gen_index(pr, 1, ne, e)], cc = hm[gen_index(pr, 2, ne, e)],
+                         d = hm[gen_index(pr, 3, ne, e)], f = hm[gen_index(pr, 4, ne, e)], g = hm[gen_index(pr, 5, ne, e)];
+            // Sylvester: leading minors
+            const double m1 = a, m2 = a * d - b * b, m3 = a * (d * g - f * f) - b * (b * g - f * cc) + cc * (b * f - d * cc);
+            const double sc1 = std::fabs(a) + std::fabs(d) + std::fabs(g);
+            const double bad = std::min(m1 / sc1, std::min(m2 / (sc1 * sc1), m3 / (sc1 * sc1 * sc1)));
+            if (bad < -1e-9) { nneg++; if (bad < wv) { wv = bad; worst = e; } }
+        }
+        fprintf(stderr, "    elements with an indefinite generator matrix: %zu of %zu (worst scaled minor %.3e at element %zu)\n", nneg, ne, wv, worst);
+        if (nneg && worst >= (size_t)c->e0 && worst < (size_t)c->e0 + c->nel) {
+            const size_t e = worst - c->e0, n = c->nel;
+            double v[21]; int ms = 0; double fy = 0.;
+            fprintf(stderr, "      class %d material %d kind %d  M =", (int)c->hcls_id[worst], c->hcls[c->hcls_id[worst]].mat, (int)c->hmat[c->hcls[c->hcls_id[worst]].mat].kind);
+            for (int k = 0; k < 6; k++) fprintf(stderr, " %.6e", hm[gen_index(matfree(c), k, ne, worst)]);
+            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->sig + k * n + e, 8, hipMemcpyDeviceToHost);
+            fprintf(stderr, "\n      sig = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
+            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_sig + k * n + e, 8, hipMemcpyDeviceToHost);
+            fprintf(stderr, "\n      res_sig = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
+            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->epl + k * n + e, 8, hipMemcpyDeviceToHost);
+            fprintf(stderr, "\n      epl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
+            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_depl + k * n + e, 8, hipMemcpyDeviceToHost);
+            fprintf(stderr, "\n      res_depl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
+            {
+                double *tmp = nullptr;
+                if (!dalloc(c, &tmp, 21 * n)) {
+                    hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
+                                       c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), tmp, 0);
+                    hipStreamSynchronize(c->stream);
+                    for (int k = 0; k < 21; k++) hipMemcpy(&v[k], tmp + k * n + e, 8, hipMemcpyDeviceToHost);
+                    dfree(tmp);
                 }
-                fprintf(stderr, "\n      elstiff(21) =");
-                for (int k = 0; k < 21; k++) fprintf(stderr, " %.5e", v[k]);
-                hipMemcpy(&ms, c->max_steps + e, 4, hipMemcpyDeviceToHost);
-                hipMemcpy(&fy, c->fyn + e, 8, hipMemcpyDeviceToHost);
-                fprintf(stderr, "\n      max_steps %d  fyn %.6e\n", ms, fy);
             }
+            fprintf(stderr, "\n      elstiff(21) =");
+            for (int k = 0; k < 21; k++) fprintf(stderr, " %.5e", v[k]);
+            hipMemcpy(&ms, c->max_steps + e, 4, hipMemcpyDeviceToHost);
+            hipMemcpy(&fy, c->fyn + e, 8, hipMemcpyDeviceToHost);
+            fprintf(stderr, "\n      max_steps %d  fyn %.6e\n", ms, fy);
         }
     }
-    if (done != 1 && hs.done == 2) {
-        // negative curvature met (p.K p <= 0) or a NaN residual: the tangent stiffness is not positive definite (lstsq
-        // correction of Material.response, material.py:324-338) -- the reference's LU solves such systems, and so does
-        // right-preconditioned GMRES with the V-cycle of the operator as it is (need not be SPD), from PCG's last iterate
-        int itm = 0;
-        double rl = 0.;
-        c->n_indefinite++;
-        const int rcm = gmres_solve(c, rtol, maxit_all, &itm, &rl);
-        if (rcm < 0) return rcm;
-        c->n_gmres++;
-        if (solve_debug) fprintf(stderr, "[plfx_solve] GMRES(%d): rc %d, %d iterations, relative residual %.3e\n", c->gm_m, rcm, itm, rl);
-        if (c->strip.on && (rc = halo_refresh(c, c->x))) return rc;
-        hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du);
-        HIPCHK(c, hipGetLastError());
-        c->x_is_du = true;
-        if (iters) *iters = it + itm;
-        if (relres) *relres = rl;
-        c->memo.valid = rcm == 0;
-        c->pred_valid = false;   // (not a plain PCG solve: the history of the initial guess starts again)
-        c->memo.rtol = rtol;
-        c->memo.relres = rl;
-        return rcm == 0 ? PLFX_OK : 1;
-    }
-    if (mg && done != 1 && c->strip.on && !c->strip_jacobi) {
-        // every rank sees the same all-reduced sums and takes this branch together: Jacobi-PCG through the same loop
-        // (owned-only sums, halo refresh of r per iteration), warm-started from the last iterate
-        if ((rc = halo_refresh(c, c->x))) return rc;
-        hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du);
-        HIPCHK(c, hipGetLastError());
-        c->strip_jacobi = true;
-        c->mg_fallbacks++;
-        int it2 = 0;
-        const int rc2 = plfx_solve(c, rtol, maxit_all, 1, &it2, relres);
-        c->strip_jacobi = false;
-        if (iters) *iters = it + it2;
-        return rc2;
-    }
-    if (mg && done != 1 && !c->strip.on) {
-        // breakdown (indefinite tangent, preconditioner not SPD) or stagnation: fall back to Jacobi-PCG,
-        // warm-started from the last iterate
-        hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du);
-        HIPCHK(c, hipGetLastError());
-        const int saved = c->precond;
-        c->precond = 0;
-        c->mg_fallbacks++;
-        int it2 = 0;
-        const int rc2 = plfx_solve(c, rtol, maxit_all, 1, &it2, relres);
-        c->precond = saved;
-        if (solve_debug) fprintf(stderr, "[plfx_solve] Jacobi fall-back: rc %d, %d iterations, relative residual %.3e\n", rc2, it2, relres ? *relres : -1.);
-        if (iters) *iters = it + it2;
-        return rc2;
-    }
+}
+
+// negative curvature met (p.K p <= 0) or a NaN residual: the tangent stiffness is not positive definite (lstsq
+// correction of Material.response, material.py:324-338) -- the reference's LU solves such systems, and so does
+// right-preconditioned GMRES with the V-cycle of the operator as it is (need not be SPD), from PCG's last iterate
+int finish_by_gmres(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, int *iters, double *relres)
+{
+    int itm = 0, rc;
+    double rl = 0.;
+    c->n_indefinite++;
+    const int rcm = gmres_solve(c, rtol, maxit_all, &itm, &rl);
+    if (rcm < 0) return rcm;
+    c->n_gmres++;
+    if (solve_debug_on()) fprintf(stderr, "[plfx_solve] GMRES(%d): rc %d, %d iterations, relative residual %.3e\n", c->gm_m, rcm, itm, rl);
+    if ((rc = compose_du(c))) return rc;
+    c->x_is_du = true;
+    if (iters) *iters = s.it + itm;
+    if (relres) *relres = rl;
+    c->pred_valid = false;   // (not a plain PCG solve: the history of the initial guess starts again)
+    remember(c, rtol, rl, rcm == 0);
+    return rcm == 0 ? PLFX_OK : 1;
+}
+
+// breakdown (indefinite tangent, preconditioner not SPD) or stagnation of multigrid-PCG: Jacobi-PCG, warm-started from the
+// last iterate.  Strip: every rank sees the same all-reduced sums and comes here together; Jacobi-PCG runs through the same
+// loop (owned-only sums, halo refresh of r per iteration) with z = D^-1 r in place of the V-cycle (strip_jacobi).
+int fall_back_to_jacobi(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, int *iters, double *relres)
+{
+    int rc;
+    if ((rc = compose_du(c))) return rc;
+    const int saved = c->precond;   // (changed and restored off a strip only)
+    if (c->strip.on) c->strip_jacobi = true;
+    else c->precond = 0;
+    c->mg_fallbacks++;
+    int it2 = 0;
+    const int rc2 = solve_impl(c, rtol, maxit_all, 1, -1, &it2, relres);
+    if (c->strip.on) c->strip_jacobi = false;
+    else c->precond = saved;
+    // (the strip branch never printed this line: kept so, every rank would print it)
+    if (!c->strip.on && solve_debug_on()) fprintf(stderr, "[plfx_solve] Jacobi fall-back: rc %d, %d iterations, relative residual %.3e\n", rc2, it2, relres ? *relres : -1.);
+    if (iters) *iters = s.it + it2;
+    return rc2;
+}
+
+// the last residual if no test has seen it, du, the history of the initial guess, the memo
+int solve_finish(plfx_ctx *c, SolveRun &s, double rtol, int *iters, double *relres)
+{
+    const size_t nd = s.nd;
+    CgScalars &hs = s.hs;
+    int rc, done = s.done;
+    const int it = s.it;
     if (done == 2) done = 0;  // Jacobi-PCG breakdown: report as not converged
     if (!done) {
         // the convergence test of iteration `it` has not run yet: evaluate the last residual
-        hipLaunchKernelGGL(k_cg_final, dim3(1), dim3(BLOCK), 0, c->stream, P_rr[(it - 1) & 1], gn, c->sc);
+        hipLaunchKernelGGL(k_cg_final, dim3(1), dim3(BLOCK), 0, c->stream, s.P_rr[(it - 1) & 1], s.gn, c->sc);
         HIPCHK(c, hipMemcpyAsync(&hs, c->sc, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, stream_sync(c));
     }
-    if (!pred_finished) {
-        if (c->strip.on && (rc = halo_refresh(c, c->x))) return rc;  // x is valid on owned + 2 columns: complete the halo
-        hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du);
-        HIPCHK(c, hipGetLastError());
-    }
+    if (!s.pred_finished && (rc = compose_du(c))) return rc;
     c->x_is_du = true;  // x = du on the free DOFs, 0 on the prescribed ones: the next warm start
     const int its_done = (done && hs.iters >= 0) ? hs.iters : it;
     // history of the initial guess: the solution this solve started from becomes "the one before" -- only if this solve moved
     // away from it (the reference repeats solves of one system: such a solve ends where it started and must not erase d)
-    if (pred_d_ready && !pred_finished && (pred_moved || its_done > 0))
+    if (s.pred_d_ready && !s.pred_finished && (s.pred_moved || its_done > 0))
         hipLaunchKernelGGL(k_pred_advance, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->pred_x, c->pred_d);
-    if (iters) *iters = (done && hs.iters >= 0) ? hs.iters : it;
+    if (iters) *iters = its_done;
     if (c->tim.on && done) {  // launches after convergence are no-ops: keep them out of the averages
         c->tim.noop[1] += it - hs.iters;
         c->tim.noop[2] += it - hs.iters;
-
     }
-    {
-        const double bb = hs.thresh2 / (rtol_eff * rtol_eff);
-        const double rl = (bb > 0. && hs.rr_final >= 0.) ? std::sqrt(hs.rr_final / bb) : 0.;
-        if (relres) *relres = rl;
-        c->memo.valid = done == 1;
-        c->memo.rtol = rtol;
-        c->memo.relres = rl;
-    }
+    const double bb = hs.thresh2 / (rtol * rtol);
+    const double rl = (bb > 0. && hs.rr_final >= 0.) ? std::sqrt(hs.rr_final / bb) : 0.;
+    if (relres) *relres = rl;
+    remember(c, rtol, rl, done == 1);
     return done ? PLFX_OK : 1;  // 1 = iteration limit reached (soft failure, like co_nconv)
+}
+
+// The solve behind plfx_solve and plfx_load_step.  The caller guarantees c != null and c->bc_set (plfx_solve checks them;
+// step_solve runs behind a successful step_apply_bc).  site: see plfx_ctx::first_test_hint, -1 = no site.
+int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *iters, double *relres)
+{
+    c->spec_setup = c->spec_kdu = false;   // (a solve overwrites c->q: nothing enqueued behind a sweep's flags is valid beyond it)
+    if (maxit < 1) maxit = 1;
+    if (c->reuse && warm && c->x_is_du && c->memo.valid && c->memo.rtol == rtol) {
+        // the system of the previous converged solve (no assembly, no other boundary values since): du is its solution
+        c->n_reuse_solve++;
+        if (iters) *iters = 0;
+        if (relres) *relres = c->memo.relres;
+        return PLFX_OK;
+    }
+    SolveRun s{c->part, {c->part + MAXPART, c->part + 3 * MAXPART}, {c->part + 2 * MAXPART, c->part + 4 * MAXPART}, c->part + 5 * MAXPART,
+               own_lo(c), own_hi(c), c->grid_nodes, c->nnode, (size_t)c->ndof};   // (the rest: false / zero)
+    if (c->strip.on && !mg_active(c)) return fail(c, PLFX_ERR_STATE, "a strip solves with the multigrid preconditioner only");
+    // Sharded run with the assembled operator: every rank applies its own rows, one all-reduce of the global vector per
+    // CG step.  With the matrix-free operator every rank holds all generators and a full K p costs ~50 us at 1024^2 --
+    // several times less than all-reducing 16.8 MB over xGMI -- so the product is computed redundantly and the solve has
+    // no collective at all (PLFX_SHARD_SPMV=1 restores the sharded rows + all-reduce).
+    static const bool force_shard_spmv = getenv("PLFX_SHARD_SPMV") && atoi(getenv("PLFX_SHARD_SPMV")) != 0;
+    s.multi = comm_active(c) && (!matfree(c) || force_shard_spmv);
+    s.mg = mg_active(c);
+    int rc;
+    if ((rc = solve_start(c, s, rtol, warm, site))) return rc;
+    if (s.mg && (rc = solve_first_test(c, s, rtol, site))) return rc;
+    if (s.mg && !s.done && (rc = precondition_rz(c, s.P_rz[1]))) return rc;
+    // beta of the first iteration is 0 (k_spmv<1> takes p = z for it == 0 without touching p_old); only the sharded
+    // k_p_update_outside path still derives it from the partials: rz_old = +inf, p_old = 0
+    if (s.multi) {
+        hipLaunchKernelGGL(k_fill, dim3(1), dim3(BLOCK), 0, c->stream, s.P_rz[0], (size_t)s.gn, (double)INFINITY);
+        HIPCHK(c, hipMemsetAsync(c->p[1], 0, 8 * s.nd, c->stream));
+    }
+    HIPCHK(c, hipGetLastError());
+    // multigrid-PCG converges in tens of iterations or not at all (PLFX_MG_MAXIT: the cap, for tests of the fall-back)
+    const int mg_cap = getenv("PLFX_MG_MAXIT") ? std::max(1, atoi(getenv("PLFX_MG_MAXIT"))) : 300;
+    const int maxit_pcg = (s.mg && !c->strip_jacobi) ? std::min(maxit, mg_cap) : maxit;
+    if ((rc = pcg_iterate(c, s, maxit_pcg))) return rc;
+    if (solve_debug_on() && s.mg && s.done != 1) solve_debug_dump(c, s);
+    if (s.done != 1 && s.hs.done == 2) return finish_by_gmres(c, s, rtol, maxit, iters, relres);
+    if (s.mg && s.done != 1 && !c->strip_jacobi) return fall_back_to_jacobi(c, s, rtol, maxit, iters, relres);
+    return solve_finish(c, s, rtol, iters, relres);
+}
+
+}  // namespace
+
+int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double *relres)
+{
+    if (!c || !c->bc_set) return c ? fail(c, PLFX_ERR_STATE, "apply_bc first") : PLFX_ERR_STATE;
+    return solve_impl(c, rtol, maxit, warm, -1, iters, relres);
 }
 
 // ------------------------------------------------------------------------------ non-linear driver pieces

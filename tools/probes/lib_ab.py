@@ -7,7 +7,8 @@ changes that must not move a number (a kernel rewritten with the same sums in th
 Cases: even mesh with a soft inclusion (fine + coarse generators, the whole V-cycle), odd mesh 201 x 199 (levels with a wider
 last column / row: area-scaled diagonal, k_mg_coarsen_M), non-proportional laminate (per-column widths).  --more adds config 4's
 6-feature SVC material on 32 x 32 (the row kernels and their 50-sub-step corrector), config 5's J2 + SVC laminate on 128 x 64,
-and a solve on 64 x 64 with three indefinite element tangents that GMRES completes."""
+a solve on 64 x 64 with three indefinite element tangents that GMRES completes, and 32 x 32 with PLFX_MG_MAXIT=2, where
+the single-GPU Jacobi-PCG fall-back completes the solves."""
 import hashlib
 import os
 import subprocess
@@ -131,6 +132,17 @@ def child(more):
         fe.mesh(NX=128, NY=64)
         out.append(('config 5 laminate 128x64', solve_tension(fe, 0.003, 20)))
         out.append(('indefinite K 64x64, GMRES', gmres_case()))
+        os.environ['PLFX_MG_MAXIT'] = '2'   # (read by every solve) multigrid-PCG gives up after two iterations: Jacobi-PCG finishes
+        fe = FE.Model(dim=2, planestress=False)
+        fe.geom([4.], LY=4.)
+        fe.assign([hill()])
+        try:
+            d = finish(fe, 32, 32, 4, 6)
+        finally:
+            del os.environ['PLFX_MG_MAXIT']
+        assert fe._engine.precond_info()[0] == 1 and fe._engine.precond_info()[1] >= 2   # multigrid-PCG is what gave up
+        assert fe._engine.solve_fallbacks() > 0 and fe._engine.indefinite_info()['by_gmres'] == 0   # ... Jacobi, not GMRES
+        out.append(('32x32, multigrid capped at 2: Jacobi fall-back', d))
     for name, (d, its) in out:
         print('%s|%s|%s' % (name, d, ','.join(map(str, its))))
 
