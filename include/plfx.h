@@ -442,6 +442,23 @@ int plfx_svr_fit_batch(plfx_ctx *ctx, int n, int d, const double *X, int nprob, 
 int plfx_svr_predict_multi(plfx_ctx *ctx, int n, int d, const double *X, double gamma, int m, const double *coef,
                            const double *intercept, int nq, const double *Q, double *out);
 
+/* SVR flow rule of Material.response (material.py:207-346 with ML_grad set; opt-in).  Attaches to material `mat` of the
+ * loaded set -- a work-hardening SVC material (PLFX_SVC_WH), anything else is PLFX_ERR_UNSUPPORTED -- the seven models of
+ * setup_fgrad_SVM: X [l*12] the standardised training rows, coef [l*7] as plfx_svr_predict_multi takes it (0 where a row
+ * is no support vector of a model), intercept[7], gamma, the feature scaler feat_mean[12] / feat_scale[12] and the output
+ * scaler out_mean[7] / out_scale[7] (six gradient components, then the hardening rate).  plfx_response_batch(_kh) then
+ * runs the points of this material with every gradient evaluation taken from the SVRs: a = predictions 0-5 * out_scale +
+ * out_mean (not normalised), and the point's hardening modulus is REPLACED by prediction 6 * out_scale[6] + out_mean[6] (not
+ * clipped), as calc_fgrad overwrites Material.khard (:752-764); the predictions are those of plfx_svr_predict_multi on
+ * ([sig | epl] - feat_mean) / feat_scale, bit for bit.  Sweeps and solves do not follow the rule.  l = 0 detaches;
+ * plfx_set_materials detaches every rule.  The tables are copied to device memory owned by the context. */
+int plfx_set_svr_flow(plfx_ctx *ctx, int mat, int l, const double *X, const double *coef, const double *intercept,
+                      double gamma, const double *feat_mean, const double *feat_scale, const double *out_mean,
+                      const double *out_scale);
+/* rows of the rule attached to material `mat` (0: none) and the response launches that took the SVR kernel for it since
+ * it was attached (either pointer may be NULL) */
+int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
+
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point

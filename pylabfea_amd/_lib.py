@@ -55,7 +55,7 @@ SYMBOLS = [
     'plfx_svc_info', 'plfx_fgrad_seq_batch', 'plfx_precond_apply', 'plfx_predict_info',
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
-    'plfx_svr_fit_batch', 'plfx_svr_predict_multi',
+    'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
 ]
 
 _lib = None
@@ -423,6 +423,34 @@ class Context(object):
         self._chk(self.lib.plfx_svr_predict_multi(self.h, len(X), X.shape[1], _dp(X), C.c_double(float(gamma)), len(ic),
                                                   _dp(coef), _dp(ic), len(Q), _dp(Q), _dp(out)))
         return out
+
+    def set_svr_flow(self, mat, X=None, coef=None, intercepts=None, gamma=0., feat_mean=None, feat_scale=None, out_mean=None,
+                     out_scale=None):
+        """Attach an SVR flow rule to the work-hardening SVC material ``mat`` of the loaded set (plfx_set_svr_flow):
+        X (l, 12) standardised training rows, coef (l, 7) with zeros where a row is no support vector of a model,
+        intercepts (7,), gamma, the feature scaler (12,) / (12,) and the output scaler (7,) / (7,): six gradient components,
+        then the hardening rate.  ``response`` then takes every gradient evaluation of this material's points from the
+        SVRs.  ``X=None`` (or no row) detaches; ``set_materials`` detaches every rule."""
+        if X is None or len(X) == 0:
+            self._chk(self.lib.plfx_set_svr_flow(self.h, int(mat), 0, None, None, None, C.c_double(0.), None, None, None, None))
+            return
+        X, coef = _f64(X), _f64(coef)
+        ic = _f64(intercepts).reshape(-1)
+        fm, fs = _f64(feat_mean).reshape(-1), _f64(feat_scale).reshape(-1)
+        om, osc = _f64(out_mean).reshape(-1), _f64(out_scale).reshape(-1)
+        if X.ndim != 2 or X.shape[1] != 12 or coef.shape != (len(X), 7) or len(ic) != 7:
+            raise ValueError('set_svr_flow: X (l, 12), coef (l, 7) and 7 intercepts expected')
+        if len(fm) != 12 or len(fs) != 12 or len(om) != 7 or len(osc) != 7:
+            raise ValueError('set_svr_flow: 12 feature means / scales and 7 output means / scales expected')
+        self._chk(self.lib.plfx_set_svr_flow(self.h, int(mat), len(X), _dp(X), _dp(coef), _dp(ic), C.c_double(float(gamma)),
+                                             _dp(fm), _dp(fs), _dp(om), _dp(osc)))
+
+    def svr_flow_info(self, mat=0):
+        """(rows of the SVR flow rule attached to material ``mat`` -- 0: none --, response launches that took the SVR kernel
+        for it since it was attached)"""
+        rows, launches = C.c_int(0), C.c_int64(0)
+        self._chk(self.lib.plfx_svr_flow_info(self.h, int(mat), C.byref(rows), C.byref(launches)))
+        return rows.value, launches.value
 
     def set_response_maxit(self, maxit=50):
         self._chk(self.lib.plfx_set_response_maxit(self.h, int(maxit)))

@@ -141,11 +141,15 @@ struct plfx_ctx {
     bool has_svc = false, has_svc3 = false, has_analytic = false, has_elastic = false, has_princ = false;
     bool has_barlat = false;     // Barlat material with the native normal (plfx_material.barlat_normal)
     bool has_svcwh = false;      // SVC with work-hardening features (PLFX_SVC_WH)
+    SvrFlowDev svr_flow[MAXMAT] = {}; // SVR flow rule of material k (plfx_set_svr_flow); l == 0: none; X and coef are owned device memory
+    unsigned svr_mask = 0;       // bit k: material k has a rule attached (its points run on k_response_svr)
+    int64_t svr_launches[MAXMAT] = {0};   // response launches of k_response_svr per material since the rule was attached
     int n_noflow = 0;            // materials without a flow rule (Tresca, Barlat without the native normal)
     int svc_lds_need = 0;
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
     unsigned svc6_mask = 0;      // bit k: material k is a 6-feature SVC
+    unsigned svcwh_mask = 0;     // bit k: material k is an SVC with work-hardening features
     int svc_wave_lds = 0;        // dynamic LDS bytes of the row kernels with their tables in LDS (k_*_row<..., true>)
     int n_svc6 = 0;              // number of 6-feature SVC materials
     int want_svc_wave = 1;       // PLFX_SVC_WAVE
@@ -899,8 +903,19 @@ void free_mesh(plfx_ctx *c)
     c->bc_nrows = 0;
 }
 
+void free_svr_flow(plfx_ctx *c, int k)
+{
+    SvrFlowDev &f = c->svr_flow[k];
+    if (f.X) hipFree((void *)f.X);
+    if (f.coef) hipFree((void *)f.coef);
+    f = SvrFlowDev();
+    c->svr_mask &= ~(1u << k);
+    c->svr_launches[k] = 0;
+}
+
 void free_materials(plfx_ctx *c)
 {
+    for (int k = 0; k < MAXMAT; k++) free_svr_flow(c, k);   // a rule belongs to the material it was attached to
     for (double *p : c->dsv) hipFree(p);
     c->dsv.clear();
     dfree(c->dmat);
@@ -1840,7 +1855,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     c->has_svcwh = false;
     c->n_noflow = 0;
     c->svc_lds_need = 0;
-    c->svc_row_all = c->svc_row_lds = c->svc6_mask = 0;
+    c->svc_row_all = c->svc_row_lds = c->svc6_mask = c->svcwh_mask = 0;
     c->svc_wave_lds = 0;
     c->n_svc6 = 0;
     c->nonlin = false;
@@ -1916,7 +1931,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
                 m.svc_sabs += std::fabs(s.dual[i]);
             }
             if (s.nsv * (nf + 1) <= c->lds_doubles) c->svc_lds_need = std::max(c->svc_lds_need, s.nsv * (nf + 1));
-            if (s.kind == PLFX_SVC6) c->has_svc = true; else if (s.kind == PLFX_SVC3) c->has_svc3 = true; else c->has_svcwh = true;
+            if (s.kind == PLFX_SVC6) c->has_svc = true; else if (s.kind == PLFX_SVC3) c->has_svc3 = true; else c->has_svcwh = true, c->svcwh_mask |= 1u << k;
             if (s.kind == PLFX_SVC6) {
                 c->n_svc6++;
                 c->svc6_mask |= 1u << k;
@@ -1989,6 +2004,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_heavy<3>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_scf_elements, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_response_batch<7>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_response_svr, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_light<7>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_heavy<7>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_wh_wave<0>, bytes));
@@ -2147,9 +2163,16 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
     if (c->has_svc3)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<6>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
                            c->stream, RB_ARGS(c->svc_lds_need), RB_TAIL);
-    if (c->has_svcwh)
+    if (c->has_svcwh && (c->svcwh_mask & ~c->svr_mask))
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<7>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, RB_ARGS(c->svc_lds_need), (const double *)d_kh, d_kh + N, 0u, c->resp_maxit);
+                           c->stream, RB_ARGS(c->svc_lds_need), (const double *)d_kh, d_kh + N, c->svr_mask, c->resp_maxit);
+    for (int k = 0; k < c->nmat; k++)   // work-hardening SVC materials with an SVR flow rule attached: one launch per material
+        if ((c->svr_mask >> k) & 1u) {
+            hipLaunchKernelGGL(k_response_svr, dim3(grid_for(N)), dim3(SVR_FLOW_BLOCK), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat,
+                               c->svc_lds_need, k, c->svr_flow[k], c->svr_flow[k].X, c->svr_flow[k].coef, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so,
+                               d_dp, d_ct, d_ns, (const double *)d_kh, d_kh + N, c->resp_maxit);
+            c->svr_launches[k]++;
+        }
 #undef RB_ARGS
 #undef RB_TAIL
     tim_end(c, ev);
@@ -3088,6 +3111,22 @@ int plfx_svr_fit_batch(plfx_ctx *c, int n, int d, const double *X, int nprob, co
                        int64_t max_iter, double *coef, double *rho, double *obj, int32_t *iters, int32_t *status)
 {
     return svr_fit_batch_impl(c, n, d, X, nprob, off, idx, t, C, gamma, epsilon, tol, max_iter, coef, rho, obj, iters, status);
+}
+
+int plfx_set_svr_flow(plfx_ctx *c, int mat, int l, const double *X, const double *coef, const double *intercept, double gamma,
+                      const double *feat_mean, const double *feat_scale, const double *out_mean, const double *out_scale)
+{
+    return set_svr_flow_impl(c, mat, l, X, coef, intercept, gamma, feat_mean, feat_scale, out_mean, out_scale);
+}
+
+int plfx_svr_flow_info(plfx_ctx *c, int mat, int *rows, int64_t *launches)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
+    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "plfx_svr_flow_info: material %d out of range", mat);
+    if (rows) *rows = c->svr_flow[mat].l;
+    if (launches) *launches = c->svr_launches[mat];
+    return PLFX_OK;
 }
 
 int plfx_svr_predict_multi(plfx_ctx *c, int n, int d, const double *X, double gamma, int m, const double *coef,

@@ -166,6 +166,18 @@ struct MatDev {
     int32_t kind, sdim, nsv, dev_only, nfeat, barlat_normal;  // barlat_normal: the native Barlat normal is enabled (extension)
 };
 
+// SVR flow rule attached to a work-hardening SVC material (plfx_set_svr_flow): the tables k_response_svr evaluates
+constexpr int SVR_FLOW_M = 8;   // accumulators of the prediction loop (plfx_svm.hpp: SVR_MMAX); seven are used
+struct SvrFlowDev {
+    const double *X;      // [l*12] standardised training rows
+    const double *coef;   // [l*SVR_FLOW_M], zero where a row is no support vector of a model (and in column 7)
+    int l;
+    double gamma;
+    double icpt[SVR_FLOW_M];
+    double fmean[12], fscale[12];               // StdScaler of the features [sig | epl]
+    double omean[SVR_FLOW_M], oscale[SVR_FLOW_M];   // ... of the outputs: six gradient components, hardening rate
+};
+
 // y = C x for a symmetric 21-entry matrix
 __device__ __forceinline__ void symv(const double *C, const double *x, double *y)
 {

@@ -1142,18 +1142,13 @@ __global__ void __launch_bounds__(SVR_BLOCK) k_svr(SvrArgs a, const int32_t *act
 // are scalar loads shared by the wave.
 constexpr int SVR_MMAX = 8;
 
-__global__ void __launch_bounds__(256) k_svr_predict(const double *__restrict__ X, int n, int d, double g,
-                                                     const double *__restrict__ coef, const double *__restrict__ icpt, int m,
-                                                     const double *__restrict__ Q, int nq, double *__restrict__ out)
+// the row loop of the prediction, shared by k_svr_predict and k_response_svr (same code, same bits): one pass over the rows
+// in row order, the distance formed feature by feature, one accumulator per model; s must come in zeroed
+__device__ __forceinline__ void svr_row_sums(const double *__restrict__ X, int n, int d, double g,
+                                             const double *__restrict__ coef, const double (&xq)[SMO_DMAX],
+                                             double (&s)[SVR_MMAX])
 {
 #pragma clang fp contract(off)
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nq) return;
-    double xq[SMO_DMAX];
-    smo_load_x(Q, d, t, xq);
-    double s[SVR_MMAX];
-#pragma unroll
-    for (int c = 0; c < SVR_MMAX; c++) s[c] = 0.;
     for (int r = 0; r < n; r++) {
         double ss = 0.;
 #pragma unroll
@@ -1166,9 +1161,137 @@ __global__ void __launch_bounds__(256) k_svr_predict(const double *__restrict__ 
 #pragma unroll
         for (int c = 0; c < SVR_MMAX; c++) s[c] = s[c] + coef[(size_t)r * SVR_MMAX + c] * k;
     }
+}
+
+__global__ void __launch_bounds__(256) k_svr_predict(const double *__restrict__ X, int n, int d, double g,
+                                                     const double *__restrict__ coef, const double *__restrict__ icpt, int m,
+                                                     const double *__restrict__ Q, int nq, double *__restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nq) return;
+    double xq[SMO_DMAX];
+    smo_load_x(Q, d, t, xq);
+    double s[SVR_MMAX];
+#pragma unroll
+    for (int c = 0; c < SVR_MMAX; c++) s[c] = 0.;
+    svr_row_sums(X, n, d, g, coef, xq, s);
 #pragma unroll
     for (int c = 0; c < SVR_MMAX; c++)
         if (c < m) out[(size_t)t * m + c] = s[c] + icpt[c];
+}
+
+// ---- Material.response under the SVR flow rule (plfx_set_svr_flow; material.py:207-346 with ML_grad set).  The update is
+// k_response_batch<7>'s (response_point on the work-hardening SVC policy); only the gradient source differs: every gradient
+// evaluation standardises [sig | epl], takes the seven predictions from svr_row_sums -- k_svr_predict's loop, hence its bits --
+// and scales them back: six components of the normal (not normalised) and the hardening modulus (not clipped), which
+// replaces the point's modulus as calc_fgrad overwrites Material.khard (:752-764).  One launch per material with a rule:
+// the tables are kernel arguments, the row loop is uniform across the wave and its loads are scalar.
+static_assert(SVR_FLOW_M == SVR_MMAX, "SvrFlowDev carries one slot per accumulator of svr_row_sums");
+
+struct YfSvrFlow : YfSvcWhT<0> {
+    const SvrFlowDev &r;
+    const double *__restrict__ X, *__restrict__ coef;   // r.X, r.coef as the kernel's own restrict arguments (scalar loads)
+    __device__ YfSvrFlow(const MatDev &mm, const double *s, const double *d, double k0, const SvrFlowDev &rr,
+                         const double *__restrict__ xx, const double *__restrict__ cc)
+        : YfSvcWhT<0>(mm, s, d, k0), r(rr), X(xx), coef(cc) {}
+    __device__ inline void fgrad(const double *s, const double *epl, double *a) const
+    {
+#pragma clang fp contract(off)
+        double xq[SMO_DMAX], acc[SVR_MMAX];
+#pragma unroll
+        for (int f = 0; f < 6; f++) {   // StdScaler.transform: (x - mean) / scale
+            xq[f] = (s[f] - r.fmean[f]) / r.fscale[f];
+            xq[6 + f] = (epl[f] - r.fmean[6 + f]) / r.fscale[6 + f];
+        }
+#pragma unroll
+        for (int f = 12; f < SMO_DMAX; f++) xq[f] = 0.;
+#pragma unroll
+        for (int c = 0; c < SVR_MMAX; c++) acc[c] = 0.;
+        svr_row_sums(X, r.l, 12, r.gamma, coef, xq, acc);
+#pragma unroll
+        for (int c = 0; c < 6; c++) a[c] = (acc[c] + r.icpt[c]) * r.oscale[c] + r.omean[c];   // inverse_transform
+        K = (acc[6] + r.icpt[6]) * r.oscale[6] + r.omean[6];
+        touch = 1;
+    }
+    // ML_full_yf once a gradient evaluation of this call has overwritten khard.  The reference's khard is then a (1,) ARRAY
+    // (sc_khard.inverse_transform(...)[0], :763), and so is get_sflow's result; in ML_full_yf `x0 = sflow` and `x1 = x0`
+    // (:467, :474) are then ONE array that the in-place `*=` of both marches (:480, :486) and of the pure-shear correction
+    // (:473) work on.  The march down to a negative and up to a non-negative yield function therefore ends with x0 = x1 =
+    // sflow, `x1 < 5 sflow` (:484) never ends the second march, f0 = f1 fails the bracket test (:495) and the function
+    // returns its conservative estimate seq - 0.85 sflow with the MARCHED value -- the first 2 % step outside the yield locus
+    // along the ray -- instead of the root.  Every ML_full_yf of a call after its first gradient evaluation takes this path
+    // (with a float khard, i.e. before it, the root search of YfSvcWhT::full_ld); reproduced as it is.
+    __device__ inline double full(const double *s, const double *epl) const
+    {
+#pragma clang fp contract(off)
+        if (!touch) return YfSvcWhT<0>::full(s, epl);
+        const double seqv = seq(s);
+        double x = sflow(epl);
+        if (seqv < 0.01) return seqv - 0.85 * x;
+        double su[6], xs[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) su[i] = s[i] / seqv;
+        if (su[0] * su[1] < -1.e-5) x *= 0.5;
+        auto f = [&](double v) {
+#pragma unroll
+            for (int i = 0; i < 6; i++) xs[i] = v * su[i];
+            return plain(xs, epl);
+        };
+        double fx = f(x);
+        while (fx >= 0. && x > 0.01) {   // :475-480
+            x *= 0.98;
+            fx = f(x);
+        }
+        while (fx < 0. && x < 5. * x) {  // :481-486: x1 < 5 sflow on the one array; false only once x has overflowed
+            x *= 1.02;
+            fx = f(x);
+        }
+        return seqv - 0.85 * x;          // f0 = f1: "could not bracket" (:495-499); an exact zero of f is not distinguished
+    }
+};
+
+constexpr int SVR_FLOW_BLOCK = BLOCK;
+
+__global__ void __launch_bounds__(SVR_FLOW_BLOCK)
+k_response_svr(const MatDev *gmat, int nmat, int lds_doubles, int mat, const SvrFlowDev flow,
+               const double *__restrict__ svr_X /* flow.X */, const double *__restrict__ svr_coef /* flow.coef */, int n, const int32_t *mat_id,
+               const double *sig_in, const double *epl_in, const double *deps_in, double *fy, double *sig_out,
+               double *depl_out, double *ct_out, int32_t *nsteps, const double *kh_in, double *kh_out, int maxit)
+{
+    __shared__ MatDev smat[MAXMAT];
+    stage_materials(smat, gmat, nmat);
+    __syncthreads();
+    int svc_mat = -1;
+    const double *sv = nullptr, *dual = nullptr;
+    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 7, mat);   // this launch's material, if its tables fit
+    __syncthreads();
+    const MatDev &m = smat[mat];
+    const bool staged = (mat == svc_mat);
+    for (int i = blockIdx.x * SVR_FLOW_BLOCK + threadIdx.x; i < n; i += gridDim.x * SVR_FLOW_BLOCK) {
+        if ((mat_id ? mat_id[i] : 0) != mat) continue;  // another material's launch
+        double sig[6], epl[6], deps[6], depl[6], Ct[21], f = 0.;
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            sig[c] = sig_in[6 * (size_t)i + c];
+            epl[c] = epl_in[6 * (size_t)i + c];
+            deps[c] = deps_in[6 * (size_t)i + c];
+        }
+        const YfSvrFlow yf(m, staged ? sv : m.sv, staged ? dual : m.dual, kh_in[i], flow, svr_X, svr_coef);
+        const int ns = response_point(m, yf, sig, epl, deps, f, depl, Ct, maxit);
+        kh_out[i] = yf.kh();
+        fy[i] = f;
+        nsteps[i] = ns;
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            sig_out[6 * (size_t)i + c] = sig[c];
+            depl_out[6 * (size_t)i + c] = depl[c];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int c = 0; c < 6; c++) ct_out[36 * (size_t)i + r * 6 + c] = Ct[sym_idx(r, c)];
+    }
 }
 
 int svr_fit_batch_impl(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *off, const int32_t *idx,
@@ -1300,6 +1423,56 @@ int svr_predict_multi_impl(plfx_ctx *c, int n, int d, const double *X, double ga
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)nq * m * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PLFX_OK;
+}
+
+int set_svr_flow_impl(plfx_ctx *c, int mat, int l, const double *X, const double *coef, const double *intercept, double gamma,
+                      const double *feat_mean, const double *feat_scale, const double *out_mean, const double *out_scale)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
+    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "plfx_set_svr_flow: material %d out of range", mat);
+    if (l < 0) return fail(c, PLFX_ERR_ARG, "plfx_set_svr_flow: l = %d rows", l);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, stream_sync(c));   // no launch may still read the tables that go
+    if (l == 0) {
+        free_svr_flow(c, mat);
+        return PLFX_OK;
+    }
+    if (c->hmat[mat].kind != PLFX_SVC_WH)
+        return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_set_svr_flow: material %d is of kind %d; an SVR flow rule attaches to a "
+                    "6-feature work-hardening SVC material (PLFX_SVC_WH) only", mat, c->hmat[mat].kind);
+    if (!X || !coef || !intercept || !feat_mean || !feat_scale || !out_mean || !out_scale)
+        return fail(c, PLFX_ERR_ARG, "plfx_set_svr_flow: null argument");
+    if (!(gamma > 0.) || !std::isfinite(gamma)) return fail(c, PLFX_ERR_ARG, "plfx_set_svr_flow: gamma must be > 0 (got %g)", gamma);
+    for (int f = 0; f < 12; f++)
+        if (!std::isfinite(feat_mean[f]) || !std::isfinite(feat_scale[f]) || feat_scale[f] == 0.)
+            return fail(c, PLFX_ERR_ARG, "plfx_set_svr_flow: feature %d has no finite mean and non-zero scale", f);
+    for (int k = 0; k < 7; k++)
+        if (!std::isfinite(out_mean[k]) || !std::isfinite(out_scale[k]) || !std::isfinite(intercept[k]))
+            return fail(c, PLFX_ERR_ARG, "plfx_set_svr_flow: output %d has no finite intercept, mean and scale", k);
+    SvrFlowDev f = SvrFlowDev();
+    std::vector<double> hc((size_t)l * SVR_MMAX, 0.);
+    for (int r = 0; r < l; r++)
+        for (int k = 0; k < 7; k++) hc[(size_t)r * SVR_MMAX + k] = coef[(size_t)r * 7 + k];
+    double *dX = nullptr, *dc = nullptr;
+    HIPCHK(c, hipMalloc((void **)&dX, (size_t)l * 12 * 8));
+    if (hipMalloc((void **)&dc, hc.size() * 8) != hipSuccess) {
+        hipFree(dX);
+        return fail(c, PLFX_ERR_HIP, "plfx_set_svr_flow: out of device memory");
+    }
+    if (hipMemcpy(dX, X, (size_t)l * 12 * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dc, hc.data(), hc.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(dX);
+        hipFree(dc);
+        return fail(c, PLFX_ERR_HIP, "plfx_set_svr_flow: copy to the device failed");
+    }
+    f.X = dX, f.coef = dc, f.l = l, f.gamma = gamma;
+    for (int k = 0; k < 7; k++) f.icpt[k] = intercept[k], f.omean[k] = out_mean[k], f.oscale[k] = out_scale[k];
+    for (int k = 0; k < 12; k++) f.fmean[k] = feat_mean[k], f.fscale[k] = feat_scale[k];
+    free_svr_flow(c, mat);
+    c->svr_flow[mat] = f;
+    c->svr_mask |= 1u << mat;
     return PLFX_OK;
 }
 

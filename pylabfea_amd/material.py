@@ -404,8 +404,41 @@ class Material(object):
         if self.tresca:
             raise ValueError('calc_fgrad: analytical gradient for Tresca not implemented')
 
+    def enable_svr_flow(self, on=True):
+        """EXTENSION (the reference follows the SVR flow rule wherever ``ML_grad`` is set; this engine does so on request,
+        and in the point functions only): with ``on`` and ``ML_grad`` set, ``response`` and ``response_batch`` run on the
+        device with every gradient evaluation -- the normal and the hardening modulus of ``epl_dot`` / ``C_tan`` -- taken
+        from the seven SVRs of ``setup_fgrad_SVM`` (material.py:207-346, 752-764), and ``response`` leaves
+        ``khard`` at the value of the call's last gradient evaluation.  ``calc_properties`` and ``Model.solve`` keep
+        refusing an SVR gradient.  Without this call nothing changes: while ``ML_grad`` is set, all four refuse."""
+        if not hasattr(self, '_svr'):
+            raise AttributeError('enable_svr_flow: setup_fgrad_SVM has not trained the SVR gradient')
+        self.svr_flow = bool(on)
+        self._version += 1
+        return self
+
+    def _svr_flow_on(self):
+        """the point functions follow the SVR flow rule: enabled, trained, ML_grad still set, and the material is still the
+        work-hardening SVC the rule attaches to (else the refusals of _no_svr_gradient hold as before)"""
+        return bool(getattr(self, 'svr_flow', False) and getattr(self, 'ML_grad', False) and hasattr(self, '_svr')
+                    and self.ML_yf and getattr(self, 'whdat', False))   # the record _load sends is SVC_WH: the rule attaches
+
+    def _svr_flow_tables(self):
+        """what plfx_set_svr_flow takes, in its argument order after the material index"""
+        v = self._svr
+        return (v['X'], v['coef'], v['intercept'], v['gamma'], self.sc_feat.mean_, self.sc_feat.scale_,
+                np.concatenate((self.sc_grad.mean_, self.sc_khard.mean_)),
+                np.concatenate((self.sc_grad.scale_, self.sc_khard.scale_)))
+
     def _no_svr_gradient(self, what):
-        """the device's return mapping follows the gradient of the SVC yield function; it cannot follow an SVR gradient"""
+        """the device's return mapping follows the gradient of the SVC yield function; only the point functions can follow
+        an SVR gradient instead, and only on request (enable_svr_flow)"""
+        if getattr(self, 'ML_grad', False) and self._svr_flow_on():
+            if what in ('response', 'response_batch'):
+                return
+            raise NotImplementedError('%s: ML_grad is set, and the SVR gradient of setup_fgrad_SVM is followed by calc_fgrad, '
+                                      'epl_dot / C_tan and, with enable_svr_flow, by the point functions response and '
+                                      'response_batch only; set ML_grad = False to run with the SVC gradient' % what)
         if getattr(self, 'ML_grad', False):
             raise NotImplementedError('%s: ML_grad is set, and the SVR gradient of setup_fgrad_SVM is evaluated by calc_fgrad '
                                       '(and epl_dot / C_tan) only; set ML_grad = False to run with the SVC gradient' % what)
@@ -431,6 +464,11 @@ class Material(object):
         m.sv, m.dual, m.khard = sv_ptr, dual_ptr, kh
         for a in keep:
             h.update(_table_digest(np.ascontiguousarray(a)))
+        if m.kind == _lib.SVC_WH and self._svr_flow_on():
+            # the SVR flow rule is attached to this record (_load): its tables and scalers are evaluated by the device too
+            h.update(b'svr_flow')
+            for a in self._svr_flow_tables():
+                h.update(_table_digest(np.ascontiguousarray(a, dtype=float).reshape(-1)))
         return h.digest()
 
     def _load(self, CV=None, ana=False):
@@ -445,6 +483,8 @@ class Material(object):
         if getattr(ctx, '_point_key', None) != key:
             ctx._point_key = None          # a failing set_materials must not leave a stale key behind
             ctx.set_materials([rec])
+            if rec[0].kind == _lib.SVC_WH and self._svr_flow_on():
+                ctx.set_svr_flow(0, *self._svr_flow_tables())
             ctx._point_key = key
         return ctx
 
@@ -778,15 +818,25 @@ class Material(object):
                                                                np.asarray(deps, dtype=float)[None, :],
                                                                khard_in=[self.khard], return_khard=True, maxit=maxit)
             self.khard = float(kout[0])
+            if self._svr_flow_on():
+                self.msg['gradient'] = 'SVR gradient'
         else:
             fy, so, dp, ct, ns = self._load(CV).response(sig[None, :], np.asarray(epl, dtype=float)[None, :],
                                                          np.asarray(deps, dtype=float)[None, :], maxit=maxit)
         self.msg['nsteps'] = int(ns[0])
         return fy[0], so[0], dp[0], ct[0].reshape(6, 6)
 
-    def response_batch(self, sig, epl, deps, CV):
-        """``response`` on (N,6) arrays in one launch (extension; same numbers point by point)."""
+    def response_batch(self, sig, epl, deps, CV, khard_in=None, return_khard=False):
+        """``response`` on (N,6) arrays in one launch (extension; same numbers point by point).  ``khard_in`` /
+        ``return_khard``: for a material that follows the SVR flow rule (``enable_svr_flow``), the hardening modulus of
+        every point on entry (default: ``khard``) and, appended to the result, on exit; ``khard`` itself is left alone."""
         self._no_svr_gradient('response_batch')
+        if khard_in is not None or return_khard:
+            if not self._svr_flow_on():
+                raise ValueError('response_batch: khard_in / return_khard are for a material that follows the SVR flow rule '
+                                 '(enable_svr_flow)')
+            fy, so, dp, ct, ns, kout = self._load(CV).response(sig, epl, deps, khard_in=khard_in, return_khard=True)
+            return (fy, so, dp, ct.reshape(-1, 6, 6), ns) + ((kout,) if return_khard else ())
         fy, so, dp, ct, ns = self._load(CV).response(sig, epl, deps)
         return fy, so, dp, ct.reshape(-1, 6, 6), ns
 
