@@ -231,6 +231,10 @@ int plfx_predict_info(plfx_ctx *ctx, int64_t *applied, int64_t *skipped, int64_t
  * Kel refreshed, only where it changed by more than 1e-3) -- whole mesh in sharded runs.  A sweep moves 412 B per element
  * plus 216 B per rewritten tangent. */
 int plfx_sweep_info(plfx_ctx *ctx, int64_t *sweeps, int64_t *tangents_rewritten);
+/* Single GPU with the mailbox: a sweep that follows one whose list of sub-stepped elements was empty leaves the corrector
+ * launches out (heavy_skipped counts such sweeps); if its own list is not empty after all, the launches and a second flags
+ * kernel follow after one more round trip (heavy_recovered).  Results are the same either way. */
+int plfx_sweep_launch_info(plfx_ctx *ctx, int64_t *heavy_skipped, int64_t *heavy_recovered);
 /* Which kernels run the 6-feature SVC materials (Material.response with an ML yield function, material.py:398-405 evaluates
  * any trained svm_yf): bit k of *row_materials = material k runs with 16 lanes per element / point (one launch per material
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read

@@ -56,6 +56,7 @@ SYMBOLS = [
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
     'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
+    'plfx_sweep_launch_info',
 ]
 
 _lib = None
@@ -522,6 +523,13 @@ class Context(object):
         """(sweeps, element tangents rewritten by them) since the context was created"""
         a, b = C.c_int64(), C.c_int64()
         self._chk(self.lib.plfx_sweep_info(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def sweep_launch_info(self):
+        """(sweeps that left the corrector launches out because the previous sweep's list was empty, those among them that
+        had to launch the corrector after all) since the context was created"""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_sweep_launch_info(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def svc_info(self):

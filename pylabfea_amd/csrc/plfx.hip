@@ -178,6 +178,10 @@ struct plfx_ctx {
 
     // element state (owned)
     double *sig = nullptr, *epl = nullptr, *eps = nullptr, *res_sig = nullptr, *res_depl = nullptr;
+    // End of a load step.  res_is_sig: the last finish exchanged sig and res_sig instead of copying one into the
+    // other -- c->sig holds both fields, the res_sig buffer is scratch until the next sweep writes it.  res_fresh: a sweep wrote
+    // res_sig since the last exchange.  eps_stale: the stored eps is behind u; the wanted field is class_strain(u) (ensure_eps).
+    bool res_is_sig = false, res_fresh = false, eps_stale = false;
     double *Mel = nullptr, *fyn = nullptr, *scf_hh = nullptr;
     // element tangents (TanStore, plfx_kernels.hpp): one allocation tan_buf = [21][nel] full entries (elstiff), [7][nel] factors
     // (elfac), [nel] form tags (eltag)
@@ -225,7 +229,8 @@ struct plfx_ctx {
     int32_t *bc_rows = nullptr;     // nodes whose matrix rows touch a prescribed node (rows of K w that can be non-zero)
     int bc_nrows = 0;
     double *kw = nullptr;           // K w, zero outside bc_rows
-    int last_heavy = 0;  // elements that needed the sub-divided corrector in the last sweep
+    int last_heavy = -1;  // elements that needed the sub-divided corrector in the last sweep (-1: no sweep yet)
+    long long n_heavy_skipped = 0, n_heavy_recovered = 0;   // sweeps that left the corrector launches out / had to add them after all
     bool x_is_du = false;  // c->x still holds the last solution on the free DOFs (0 on the prescribed ones) = the warm start
     // initial guess from the last two solutions (plfx_solve): the solution before the one in c->x, scratch for the difference,
     // whether pred_x is that vector (same mesh, same Dirichlet set, c->x untouched since), counters
@@ -1838,11 +1843,18 @@ int plfx_sync(plfx_ctx *c)
     } while (0)
 
 // ------------------------------------------------------------------------------ materials
+static int ensure_eps(plfx_ctx *c);
+static int split_res_sig(plfx_ctx *c);
+
 int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
 {
     if (!c || !c->stream) return PLFX_ERR_STATE;
     if (nmat < 1 || nmat > MAXMAT || !mats) return fail(c, PLFX_ERR_ARG, "nmat must be in 1..%d", MAXMAT);
     if (c->tan_buf && c->dmat && c->nel > 0) {
+        // eps and res_sig as stored fields before the tables they were deferred under go away
+        int rcs;
+        if ((rcs = ensure_eps(c)) || (rcs = split_res_sig(c))) return rcs;
+        c->res_fresh = false;
         // the tangent store refers to the CV of the current materials: hold every stored tangent in full form first
         hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
                            c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->elstiff, 1);
@@ -3058,6 +3070,14 @@ int plfx_sweep_info(plfx_ctx *c, int64_t *sweeps, int64_t *tangents_rewritten)
     return PLFX_OK;
 }
 
+int plfx_sweep_launch_info(plfx_ctx *c, int64_t *heavy_skipped, int64_t *heavy_recovered)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (heavy_skipped) *heavy_skipped = c->n_heavy_skipped;
+    if (heavy_recovered) *heavy_recovered = c->n_heavy_recovered;
+    return PLFX_OK;
+}
+
 int plfx_svc_info(plfx_ctx *c, int *row_materials, int *thread_materials, int64_t *row_launches, int64_t *thread_launches)
 {
     if (!c) return PLFX_ERR_ARG;
@@ -3366,18 +3386,62 @@ int plfx_state_reset(plfx_ctx *c)
     HIPCHK(c, hipGetLastError());
     c->assembled = false, c->M_dirty = true;
     c->x_is_du = false;
+    c->res_is_sig = c->res_fresh = c->eps_stale = false;
+    c->last_heavy = -1;   // the next sweep launches its corrector kernels whatever the one before found
     return PLFX_OK;
+}
+
+// the stored eps field, brought up to date: eps = class_strain(u) (k_update_state forms it for the sums and does not store it)
+static int ensure_eps(plfx_ctx *c)
+{
+    if (!c->eps_stale) return 0;
+    hipLaunchKernelGGL(k_eps_from_u, dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
+                       c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->u, c->eps);
+    HIPCHK(c, hipGetLastError());
+    c->eps_stale = false;
+    return 0;
+}
+
+// res_sig as a field of its own again (after an exchange c->sig holds both): copy, then the two buffers are independent
+static int split_res_sig(plfx_ctx *c)
+{
+    if (!c->res_is_sig) return 0;
+    HIPCHK(c, hipMemcpyAsync(c->res_sig, c->sig, (size_t)48 * c->nel, hipMemcpyDeviceToDevice, c->stream));
+    c->res_is_sig = false;
+    return 0;
+}
+
+// what the end of a load step does with sig: exchange it with res_sig (true) or run the kernel as ever (false)
+static int finish_mode(plfx_ctx *c, bool *swap)
+{
+    *swap = c->nonlin && !c->has_elastic && c->res_fresh;
+    if (*swap) return 0;
+    return split_res_sig(c);   // no sweep since the last exchange: res_sig == sig, as the kernel will read it
+}
+
+static void finish_done(plfx_ctx *c, bool swap)
+{
+    if (swap) {
+        std::swap(c->sig, c->res_sig);
+        c->res_is_sig = true;
+        c->res_fresh = false;
+    }
+    c->eps_stale = true;
 }
 
 static int state_ptr(plfx_ctx *c, int which, double **p, size_t *comps, size_t *n, bool *soa)
 {
     *soa = true;
     *n = c->nel;
+    if (which == 1 || which == 6) {   // eps is read, or eps / u is about to be overwritten: the stored field first
+        const int rce = ensure_eps(c);
+        if (rce) return rce;
+    }
     switch (which) {
     case 0: *p = c->sig; *comps = 6; break;
     case 1: *p = c->eps; *comps = 6; break;
     case 2: *p = c->epl; *comps = 6; break;
-    case 3: *p = c->res_sig; *comps = 6; break;
+    case 3: *p = c->res_is_sig ? c->sig : c->res_sig; *comps = 6; break;
     case 4: *p = c->res_depl; *comps = 6; break;
     case 5: *p = c->elstiff; *comps = 21; break;
     case 6: *p = c->u; *comps = 1; *n = c->ndof; *soa = false; break;
@@ -3445,7 +3509,9 @@ int plfx_state_set(plfx_ctx *c, int which, const double *in)
     double *p;
     size_t comps, n;
     bool soa;
-    int rc = state_ptr(c, which, &p, &comps, &n, &soa);
+    int rc = (which == 0 || which == 3) ? split_res_sig(c) : 0;   // sig / res_sig written from outside: two buffers first
+    if (rc) return rc;
+    rc = state_ptr(c, which, &p, &comps, &n, &soa);
     if (rc) return rc;
     if (!soa) {
         c->x_is_du = false;  // u / f / du written from outside
@@ -3997,10 +4063,13 @@ int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
         hipLaunchKernelGGL(k_axpy_uf, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->q, c->u, c->f);
     }
     const int g = grid_for(c->nel, SUMPART);
+    bool swap;
+    if ((rc = finish_mode(c, &swap))) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
                        c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
-                       c->eps, tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, c->part_g,
+                       tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, c->part_g,
                        c->strip.on ? c->strip.eown_lo : 0, c->strip.on ? c->strip.eown_hi : 0x7fffffff);
+    finish_done(c, swap);
     const int n = c->fin_n;
     const int tot = 2 * n + 18;
     const int sl = c->fin_defer;  // >= 0: post into that pinned slot and return without waiting (plfx_finish_fetch collects)
@@ -4025,11 +4094,9 @@ int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
     static const bool direct_ok = !(getenv("PLFX_FINISH_DIRECT") && atoi(getenv("PLFX_FINISH_DIRECT")) == 0);
     const bool direct = sl >= 0 && direct_ok && !comm_active(c);
     double *out = direct ? c->fin_pin[sl] : c->fin_dev;
-    if (n > 0) {
-        hipLaunchKernelGGL(k_gather2, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, n, c->fin_idx, (const double *)c->u,
-                           (const double *)c->f, out, out + n);
-    }
-    hipLaunchKernelGGL(k_reduce_rows, dim3(18), dim3(BLOCK), 0, c->stream, c->part_g, 18, g, out + 2 * (size_t)n);
+    // boundary values of u and f and the 18 row sums: independent, one launch (the first blocks gather, the last 18 reduce)
+    hipLaunchKernelGGL(k_finish_out, dim3((n + BLOCK - 1) / BLOCK + 18), dim3(BLOCK), 0, c->stream, n, c->fin_idx, (const double *)c->u,
+                       (const double *)c->f, out, out + n, (const double *)c->part_g, 18, g, out + 2 * (size_t)n);
     HIPCHK(c, hipGetLastError());
     if (comm_active(c) &&  // element sums of the whole mesh (calc_global, model.py:1473-1511)
         (rc = allreduce(c, c->fin_dev + 2 * (size_t)n, 18, NCCL_FLOAT64, NCCL_SUM, "sums")))
@@ -4847,6 +4914,9 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
 static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq)
 {
     // (flags / bflags are left zeroed by the k_sweep_flags of the previous sweep)
+    // every plastic element's res_sig is written below: the buffer is a field of its own again, whatever it held
+    c->res_is_sig = false;
+    c->res_fresh = true;
     EvPair *ev;
     tim_begin(c, 0, &ev);
 #define SWEEP_ARGS(lds) c->dmat, c->nmat, c->dcls, c->ncls, lds, c->nel, c->e0, c->dconn, c->dcls_id,          \
@@ -4911,47 +4981,57 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         first = 0;
     }
     tim_end(c, ev);  // family 0: the streaming phase (one launch per material kind present)
-    tim_begin(c, 6, &ev);  // family 6: the compacted 50-sub-step corrector
-    // phase 2 reads the list length from the device; an empty list costs one empty launch
-    if (c->has_analytic)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), 0u);
-    if (c->has_princ)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<2>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), 0u);
-    if (c->has_barlat)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<5>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), 0u);
-    if (svc_thread)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), fast);
-    if (c->has_svc && fast)
-        for (int k = 0; k < c->nmat; k++)
-            if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
-    if (c->has_svc3)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), 0u);
-    if (c->has_svcwh && wh_wave)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_wh_wave<1>), dim3(grid_wh), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
-                           c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn, c->dcls_id,
-                           (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
-                           c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list, 0, c->kh_el,
-                           wh_seq ? c->kh_out : (double *)nullptr, wh_seq ? c->kh_touch : (int32_t *)nullptr);
-    else if (c->has_svcwh)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<7>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), 0u, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
-                           wh_seq ? c->kh_touch : (int32_t *)nullptr);
+    // phase 2 reads the list length from the device; an empty list costs one empty launch per kind.  Single GPU with the mailbox:
+    // after a sweep whose list was empty the launches are left out, k_sweep_flags reports a list that turned up after all, and
+    // the launches follow then (one more round trip, in the first sweep that grows a list: DESIGN 22)
+    const bool mb_flags = !comm_active(c) && c->mbox && c->mb_cap >= 2;
+    const bool skip_heavy = mb_flags && !c->strip.on && c->last_heavy == 0;
+    auto launch_phase2 = [&]() {
+        tim_begin(c, 6, &ev);  // family 6: the compacted 50-sub-step corrector
+        if (c->has_analytic)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
+                               SWEEP_ARGS(0), 0u);
+        if (c->has_princ)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<2>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
+                               SWEEP_ARGS(0), 0u);
+        if (c->has_barlat)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<5>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
+                               SWEEP_ARGS(0), 0u);
+        if (svc_thread)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
+                               c->stream, SWEEP_ARGS(c->svc_lds_need), fast);
+        if (c->has_svc && fast)
+            for (int k = 0; k < c->nmat; k++)
+                if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
+        if (c->has_svc3)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
+                               c->stream, SWEEP_ARGS(c->svc_lds_need), 0u);
+        if (c->has_svcwh && wh_wave)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_wh_wave<1>), dim3(grid_wh), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
+                               c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn, c->dcls_id,
+                               (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
+                               c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list, 0, c->kh_el,
+                               wh_seq ? c->kh_out : (double *)nullptr, wh_seq ? c->kh_touch : (int32_t *)nullptr);
+        else if (c->has_svcwh)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<7>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
+                               c->stream, SWEEP_ARGS(c->svc_lds_need), 0u, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
+                               wh_seq ? c->kh_touch : (int32_t *)nullptr);
+        tim_end(c, ev);
+    };
 #undef SWEEP_ARGS
 #undef ROW_ARGS
-    tim_end(c, ev);
+    if (skip_heavy)
+        c->n_heavy_skipped++;
+    else
+        launch_phase2();
     int h[4];
     const bool spec = c->spec_arm && !comm_active(c) && c->mbox && c->mb_cap >= 2 && matfree(c) && !c->strip.on && c->assembled;
     c->spec_arm = false;
-    if (!comm_active(c) && c->mbox && c->mb_cap >= 2) {   // single GPU: the flags kernel posts its results itself
+    if (mb_flags) {   // single GPU: the flags kernel posts its results itself
         const unsigned long long seq = ++c->mbox_seq;
         hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4,
                            reinterpret_cast<int *>(c->mb_buf), c->mbox, seq, spec ? c->flags + 8 : (int *)nullptr,
-                           spec ? c->spec_sc : (CgScalars *)nullptr);
+                           spec ? c->spec_sc : (CgScalars *)nullptr, skip_heavy ? 1 : 0);
         if (spec) {
             // what the host would enqueue after reading the flags, enqueued now (the round trip overlaps it): the set-up pass of
             // plfx_assemble if a tangent changed, else -- if every element converged as well -- the K du of plfx_finish_step
@@ -4970,6 +5050,20 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         const int rcw = mbox_wait(c, seq);
         if (rcw) return rcw;
         memcpy(h, c->mb_buf, sizeof(h));
+        if (skip_heavy && h[0] < 0) {
+            // elements need the corrector after all: the flags kernel left its inputs alone and told the two speculative kernels to
+            // do nothing; the corrector launches and an unarmed flags kernel follow, and their results are the sweep's
+            c->n_heavy_recovered++;
+            c->spec_setup = c->spec_kdu = false;
+            launch_phase2();
+            const unsigned long long seq2 = ++c->mbox_seq;
+            hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4,
+                               reinterpret_cast<int *>(c->mb_buf), c->mbox, seq2, (int *)nullptr, (CgScalars *)nullptr, 0);
+            HIPCHK(c, hipGetLastError());
+            const int rcw2 = mbox_wait(c, seq2);
+            if (rcw2) return rcw2;
+            memcpy(h, c->mb_buf, sizeof(h));
+        }
         c->spec_h0 = h[0];
         c->spec_h1 = h[1];
     } else {
@@ -5248,11 +5342,14 @@ int plfx_update_state(plfx_ctx *c)
         if ((rc = plain_spmv(c, c->du, c->q))) return rc;
         hipLaunchKernelGGL(k_axpy_uf, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->q, c->u, c->f);
     }
+    bool swap;
+    if ((rc = finish_mode(c, &swap))) return rc;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
                        c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                       (const double2 *)c->u, c->sig, c->epl, c->eps, tan_store(c), c->res_sig,
-                       c->res_depl, c->nonlin ? 1 : 0, (double *)nullptr);
+                       (const double2 *)c->u, c->sig, c->epl, tan_store(c), c->res_sig,
+                       c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, (double *)nullptr);
     HIPCHK(c, hipGetLastError());
+    finish_done(c, swap);
     return PLFX_OK;
 }
 
@@ -5275,6 +5372,8 @@ int plfx_global_sums(plfx_ctx *c, double *out18)
     if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
     if (!out18) return fail(c, PLFX_ERR_ARG, "null output");
     const int g = grid_for(c->nel, SUMPART);  // same grid as the fused sums of plfx_finish_step: identical numbers
+    const int rce = ensure_eps(c);
+    if (rce) return rce;
     hipLaunchKernelGGL(k_global_partials, dim3(g), dim3(BLOCK), 0, c->stream, c->dcls, c->nel, c->dcls_id,
                        c->sig, c->eps, c->epl, c->part_g);
     hipLaunchKernelGGL(k_reduce_rows, dim3(18), dim3(BLOCK), 0, c->stream, c->part_g, 18, g, c->small);

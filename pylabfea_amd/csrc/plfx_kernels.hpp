@@ -735,9 +735,32 @@ struct CgScalars;
 __device__ void spec_set(CgScalars *spec, int done);
 __global__ void __launch_bounds__(BLOCK) k_sweep_flags(int *__restrict__ bflags, int *__restrict__ flags, int *__restrict__ out,
                                                        int *__restrict__ pin = nullptr, CgMbox *mb = nullptr, unsigned long long seq = 0ull,
-                                                       int *__restrict__ skip_setup = nullptr, CgScalars *spec = nullptr)
+                                                       int *__restrict__ skip_setup = nullptr, CgScalars *spec = nullptr,
+                                                       int heavy_skipped = 0)
 {
     __shared__ int sc[BLOCK / 64], sn[BLOCK / 64];
+    // heavy_skipped: the host left the corrector launches out (the previous sweep's list was empty).  If this sweep's list is not
+    // empty, nothing is consumed: slots and list length stay for the corrector kernels, the two speculative kernels are told to do
+    // nothing, and out[0] = -1 with the length in out[2] asks the host for the launches and a second flags kernel.
+    const int pending = heavy_skipped ? flags[2] : 0;   // (uniform; no thread writes flags[2] on this path)
+    if (pending > 0) {
+        if (threadIdx.x == 0) {
+            out[0] = -1;
+            out[1] = 0;
+            out[2] = pending;
+            out[3] = 0;
+            if (skip_setup) *skip_setup = 1;
+            if (spec) spec_set(spec, 1);
+            if (pin) {
+                pin[0] = -1;
+                pin[1] = 0;
+                pin[2] = pending;
+                pin[3] = 0;
+                mbox_publish(mb, seq);
+            }
+        }
+        return;
+    }
     int cw = 0, nw = 0;
     for (int b = threadIdx.x; b < SWEEP_SLOTS; b += BLOCK) {
         cw += bflags[2 * b];
@@ -2456,19 +2479,6 @@ k_scatter_bc_plan(int n, const int32_t *__restrict__ idx, const int32_t *__restr
     if (flag) m[i] = 1.;
 }
 
-// va[k] = a[idx[k]], vb[k] = b[idx[k]]   (boundary values of u and f at the end of a load step: one launch)
-__global__ void __launch_bounds__(BLOCK)
-k_gather2(int n, const int32_t *__restrict__ idx, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ va,
-          double *__restrict__ vb)
-{
-    const int k = blockIdx.x * BLOCK + threadIdx.x;
-    if (k < n) {
-        const int i = idx[k];
-        va[k] = a[i];
-        vb[k] = b[i];
-    }
-}
-
 __global__ void __launch_bounds__(BLOCK) k_gather(int n, const int32_t *idx, const double *y, double *v)
 {
     const int k = blockIdx.x * BLOCK + threadIdx.x;
@@ -2632,12 +2642,15 @@ k_axpy_uf(size_t ndof, const double *__restrict__ du, const double *__restrict__
 // Latency structure as in k_sweep_light: tables in LDS, every stream whose address depends on the element index alone issued
 // at the top of the pass (res_sig / res_depl whenever the step was non-linear, whatever the element's material turns out to
 // be), the gathers of u and du behind conn, and the stores after the last load.
+// eps = class_strain(u) is formed for the sums only and not stored: k_eps_from_u writes the field when somebody asks for it
+// (ensure_eps, plfx.hip).  swap != 0 (every material plastic, a sweep wrote res_sig for every element since the last
+// exchange): the new sig IS res_sig, so it is only read for the sums and the host exchanges the two pointers behind the launch.
 template <int SUMS>
 __global__ void __launch_bounds__(BLOCK)
 k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off, const int32_t *__restrict__ conn,
                const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
-               double *__restrict__ eps, TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
-               int nonlin, double *__restrict__ part /* SUMS: [18][gridDim.x] volume-weighted sums of the new sig, eps, epl */,
+               TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
+               int nonlin, int swap, double *__restrict__ part /* SUMS: [18][gridDim.x] volume-weighted sums of the new sig, eps, epl */,
                int sum_lo = 0, int sum_hi = 0x7fffffff /* elements that enter the sums (strip: owned columns) */)
 {
     __shared__ SweepTables tb;
@@ -2687,10 +2700,9 @@ k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
                 pn[k] = po[k];
             }
         }
+        if (!swap) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) {
-            sig[(size_t)k * nel + e] = sn[k];
-            eps[(size_t)k * nel + e] = et[k];
+            for (int k = 0; k < 6; k++) sig[(size_t)k * nel + e] = sn[k];
         }
         if (SUMS && e >= sum_lo && e < sum_hi) {
             const double v = c.vel;
@@ -2703,6 +2715,25 @@ k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
         }
     }
     if (SUMS) block_sums_to_partials(acc, part);
+}
+
+// eps = class_strain(u) of every element: the stored field behind Element.eps and plfx_global_sums, written on demand (the
+// same inline function on the same staged class tables as k_update_state: the same bits as the sums saw)
+__global__ void __launch_bounds__(BLOCK)
+k_eps_from_u(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off,
+             const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ u2, double *__restrict__ eps)
+{
+    __shared__ SweepTables tb;
+    stage_tables(tb, gmat, nmat, gcls, ncls);
+    __syncthreads();
+    for (int e = blockIdx.x * BLOCK + threadIdx.x; e < nel; e += gridDim.x * BLOCK) {
+        const size_t ge = (size_t)e + e_off;
+        const ClassDev &c = tb.scls[cls[e]];
+        double et[6];
+        class_strain(c, u2, conn[ge * 4], conn[ge * 4 + 1], conn[ge * 4 + 2], conn[ge * 4 + 3], et);
+#pragma unroll
+        for (int k = 0; k < 6; k++) eps[(size_t)k * nel + e] = et[k];
+    }
 }
 
 // calc_global sums (model.py:1500-1507): partials of sum(x*Vel) for the 18 components
@@ -2731,6 +2762,31 @@ __global__ void __launch_bounds__(BLOCK) k_reduce_rows(const double *part, int n
     __shared__ double sh[BLOCK / 64];
     const int k = blockIdx.x;
     if (k >= nrows) return;
+    double v = 0.;
+    for (int i = threadIdx.x; i < npart; i += BLOCK) v += part[(size_t)k * npart + i];
+    const double t = block_sum(v, sh);
+    if (threadIdx.x == 0) out[k] = t;
+}
+
+// The two independent tails of plfx_finish_step in one launch: the first gridDim.x - nrows blocks gather the boundary values of
+// u and f (va[k] = a[idx[k]], vb[k] = b[idx[k]]), the last nrows blocks sum the rows of part (k_reduce_rows: the same per-thread order and block_sum, so
+// the same numbers).  No block reads what another one writes.
+__global__ void __launch_bounds__(BLOCK)
+k_finish_out(int n, const int32_t *__restrict__ idx, const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ va,
+             double *__restrict__ vb, const double *__restrict__ part, int nrows, int npart, double *__restrict__ out)
+{
+    __shared__ double sh[BLOCK / 64];
+    const int gb = (int)gridDim.x - nrows;   // gather blocks
+    if ((int)blockIdx.x < gb) {
+        const int k = blockIdx.x * BLOCK + threadIdx.x;
+        if (k < n) {
+            const int i = idx[k];
+            va[k] = a[i];
+            vb[k] = b[i];
+        }
+        return;
+    }
+    const int k = (int)blockIdx.x - gb;
     double v = 0.;
     for (int i = threadIdx.x; i < npart; i += BLOCK) v += part[(size_t)k * npart + i];
     const double t = block_sum(v, sh);

@@ -17,10 +17,10 @@ ends = [i for i, r in enumerate(rows) if r[2].startswith('k_update_state')]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 a, b = ends[-k - 1] + 1, ends[-k] + 1
 # extend to the post of that step
-while b < len(rows) and rows[b][2] in ('k_gather', 'k_reduce_rows', 'k_mbox_post'):
+while b < len(rows) and rows[b][2] in ('k_gather', 'k_gather2', 'k_reduce_rows', 'k_finish_out', 'k_mbox_post'):
     b += 1
 a0 = a
-while rows[a0][2] in ('k_gather', 'k_reduce_rows', 'k_mbox_post'):
+while rows[a0][2] in ('k_gather', 'k_gather2', 'k_reduce_rows', 'k_finish_out', 'k_mbox_post'):
     a0 += 1
 seg = rows[a0:b]
 t0 = seg[0][0]
