@@ -259,6 +259,36 @@ int plfx_state_reset(plfx_ctx *ctx);
 /* gather entries of u (which=6), f (7) or du (8) at idx[n] */
 int plfx_gather(plfx_ctx *ctx, int which, int n, const int32_t *idx, double *out);
 
+/* Element result fields: per owned element the value the closures of Model.plot compute (model.py:1591-1677).
+ * STRAIN* = eps[0], eps[1], eps[5] times 100; STRESS* = sig[0], sig[1], sig[5]; PLASTIC* = epl[0], epl[1], epl[5] times 100;
+ * SEQ = calc_seq of the element's own material (material.py:576-676); SEQJ2 = sig_eq_j2(sig); PEEQ / ETOT = eps_eq(epl) /
+ * eps_eq(eps) times 100; UX / UY = mean of the four nodal displacements (summed in the order of the element's nodes).
+ * The reference's sixteenth field, the material number, is the caller's own map and no selector of the library. */
+enum {
+    PLFX_FIELD_STRAIN1 = 0,
+    PLFX_FIELD_STRAIN2 = 1,
+    PLFX_FIELD_STRAIN12 = 2,
+    PLFX_FIELD_STRESS1 = 3,
+    PLFX_FIELD_STRESS2 = 4,
+    PLFX_FIELD_STRESS12 = 5,
+    PLFX_FIELD_PLASTIC1 = 6,
+    PLFX_FIELD_PLASTIC2 = 7,
+    PLFX_FIELD_PLASTIC12 = 8,
+    PLFX_FIELD_SEQ = 9,
+    PLFX_FIELD_SEQJ2 = 10,
+    PLFX_FIELD_PEEQ = 11,
+    PLFX_FIELD_ETOT = 12,
+    PLFX_FIELD_UX = 13,
+    PLFX_FIELD_UY = 14
+};
+/* nsel selectors sel[] (any order, repeats allowed) in one device pass; columns several selectors share are read once.
+ * out: [nsel * nel_owned], selector-major (row k = selector sel[k]), or NULL; range: [2 * nsel], minimum and maximum of
+ * every row, reduced on the device (both NaN when the row holds a NaN), or NULL.  The call reads the state and changes
+ * neither it nor its flags: the stress is the current one also right after a load step, and the strain selectors are
+ * formed from u whenever the stored eps is behind it, without writing the stored field.  The device rows live in a buffer
+ * of the context that later calls reuse.  Unknown selector: PLFX_ERR_ARG; before set_mesh: PLFX_ERR_STATE; nsel = 0: PLFX_OK. */
+int plfx_element_fields(plfx_ctx *ctx, int nsel, const int32_t *sel, double *out, double *range);
+
 /* ---------------------------------------------------------------- assembly (Model.setupK, model.py:954-977) */
 int plfx_assemble(plfx_ctx *ctx);
 /* export the assembled matrix as CSR (scalar rows, sorted columns).  Call with NULL arrays to get nnz. */

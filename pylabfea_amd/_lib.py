@@ -18,6 +18,11 @@ ELASTIC, HILL6, PRINC3, SVC6, TRESCA, BARLAT, SVC3, SVC_WH = 0, 1, 2, 3, 4, 5, 6
 # state ids of plfx_state_get/_set
 ST_SIG, ST_EPS, ST_EPL, ST_RES_SIG, ST_RES_DEPL, ST_ELSTIFF, ST_U, ST_F, ST_DU, ST_FYN, ST_MAXSTEPS, ST_KHARD = range(12)
 
+# selectors of plfx_element_fields (PLFX_FIELD_* of include/plfx.h), in the order of their values
+FIELD_NAMES = ('strain1', 'strain2', 'strain12', 'stress1', 'stress2', 'stress12', 'plastic1', 'plastic2', 'plastic12',
+               'seq', 'seqJ2', 'peeq', 'etot', 'ux', 'uy')
+FIELD_ID = {n: i for i, n in enumerate(FIELD_NAMES)}
+
 # timing families
 T_SWEEP, T_SPMV, T_CGUPD, T_ASSEMBLE, T_VCYCLE, T_SMOOTH, T_SWEEP_HEAVY, T_COMM = range(8)
 
@@ -56,7 +61,7 @@ SYMBOLS = [
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
     'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
-    'plfx_sweep_launch_info',
+    'plfx_sweep_launch_info', 'plfx_element_fields',
 ]
 
 _lib = None
@@ -651,6 +656,15 @@ class Context(object):
 
     def state_reset(self):
         self._chk(self.lib.plfx_state_reset(self.h))
+
+    def element_fields(self, sel, want_out=True, want_range=False):
+        """plfx_element_fields: (rows[len(sel), nel_owned] or None, range[len(sel), 2] or None) of the selector ids ``sel``
+        from one device pass"""
+        sel = _i32(sel).reshape(-1)
+        out = np.empty((len(sel), self.nel_owned)) if want_out else None
+        rng = np.empty((len(sel), 2)) if want_range else None
+        self._chk(self.lib.plfx_element_fields(self.h, len(sel), _dp(sel), _dp(out), _dp(rng)))
+        return out, rng
 
     def gather(self, which, idx):
         idx = _i32(idx)

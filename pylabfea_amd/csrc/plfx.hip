@@ -182,6 +182,11 @@ struct plfx_ctx {
     // other -- c->sig holds both fields, the res_sig buffer is scratch until the next sweep writes it.  res_fresh: a sweep wrote
     // res_sig since the last exchange.  eps_stale: the stored eps is behind u; the wanted field is class_strain(u) (ensure_eps).
     bool res_is_sig = false, res_fresh = false, eps_stale = false;
+    // plfx_element_fields: the rows of the last call (grown when a call asks for more rows than any before it, else reused) and
+    // the per-block minimum / maximum partials with their host mirror
+    double *fld_buf = nullptr, *fld_part = nullptr;
+    size_t fld_cap = 0;
+    std::vector<double> fld_host;
     double *Mel = nullptr, *fyn = nullptr, *scf_hh = nullptr;
     // element tangents (TanStore, plfx_kernels.hpp): one allocation tan_buf = [21][nel] full entries (elstiff), [7][nel] factors
     // (elfac), [nel] form tags (eltag)
@@ -830,6 +835,9 @@ void free_mesh(plfx_ctx *c)
     dfree(c->eps);
     dfree(c->res_sig);
     dfree(c->res_depl);
+    dfree(c->fld_buf);
+    dfree(c->fld_part);
+    c->fld_cap = 0;
     tan_free(c);
     dfree(c->Mel);
     dfree(c->fyn);
@@ -5380,6 +5388,100 @@ int plfx_global_sums(plfx_ctx *c, double *out18)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out18, c->small, 18 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+// Element result fields (Model.field / fields / field_range): reads the state, changes none of it and none of its flags
+int plfx_element_fields(plfx_ctx *c, int nsel, const int32_t *sel, double *out, double *range)
+{
+    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
+    if (nsel < 0 || (nsel > 0 && !sel)) return fail(c, PLFX_ERR_ARG, "bad selector list");
+    for (int k = 0; k < nsel; k++)
+        if (sel[k] < 0 || sel[k] >= FLD_COUNT) return fail(c, PLFX_ERR_ARG, "unknown field selector %d (sel[%d])", sel[k], k);
+    if (nsel == 0 || (!out && !range)) return PLFX_OK;
+    const size_t ne = c->nel;
+    FieldPlan pl{};
+    int first[FLD_COUNT];   // first position of a selector in the list: the row the kernel writes
+    for (int id = 0; id < FLD_COUNT; id++) first[id] = -1;
+    for (int k = 0; k < nsel; k++)
+        if (first[sel[k]] < 0) first[sel[k]] = k;
+    bool disp = false, strain = false, all_kinds = false;
+    for (int id = 0; id < FLD_COUNT; id++) {
+        if (first[id] < 0) continue;
+        pl.want |= 1u << id;
+        pl.row[id] = first[id];
+        switch (id) {
+        case FLD_STRAIN1: pl.eps_cols |= 1u; strain = true; break;
+        case FLD_STRAIN2: pl.eps_cols |= 2u; strain = true; break;
+        case FLD_STRAIN12: pl.eps_cols |= 32u; strain = true; break;
+        case FLD_ETOT: pl.eps_cols |= 63u; strain = true; break;
+        case FLD_STRESS1: pl.sig_cols |= 1u; break;
+        case FLD_STRESS2: pl.sig_cols |= 2u; break;
+        case FLD_STRESS12: pl.sig_cols |= 32u; break;
+        case FLD_SEQ: case FLD_SEQJ2: pl.sig_cols |= 63u; break;
+        case FLD_PLASTIC1: pl.epl_cols |= 1u; break;
+        case FLD_PLASTIC2: pl.epl_cols |= 2u; break;
+        case FLD_PLASTIC12: pl.epl_cols |= 32u; break;
+        case FLD_PEEQ: pl.epl_cols |= 63u; break;
+        default: disp = true; break;   // ux, uy
+        }
+    }
+    pl.eps_from_u = (strain && c->eps_stale) ? 1 : 0;   // never a stale c->eps; eps_stale and the stored field stay as they are
+    if (pl.eps_from_u) pl.eps_cols = 0;
+    pl.need_u = (disp || pl.eps_from_u) ? 1 : 0;
+    pl.store = out ? 1 : 0;
+    if ((pl.want >> FLD_SEQ) & 1u)
+        for (int m = 0; m < c->nmat; m++) {
+            const int kd = c->hmat[m].kind;
+            if (kd == 2 || kd == 4 || kd == 5 || kd == 6) all_kinds = true;
+        }
+    int rc;
+    if (out && c->fld_cap < (size_t)nsel * ne) {
+        if ((rc = dalloc(c, &c->fld_buf, (size_t)nsel * ne))) return rc;
+        c->fld_cap = (size_t)nsel * ne;
+    }
+    if (range && !c->fld_part && (rc = dalloc(c, &c->fld_part, (size_t)2 * FLD_COUNT * MAXPART))) return rc;
+    const int g = grid_for(ne, MAXPART);
+    EvPair *ev;
+    tim_begin(c, 0, &ev);   // family 0, like the batched point kernels: the kernel alone, without the copies
+    // sig through c->sig at launch time: after an exchange it holds the current stress, the other buffer is scratch
+#define PLFX_FLD_LAUNCH(A, R)                                                                                                  \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_element_fields<A, R>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls,  \
+                       c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->u, c->sig, c->epl, c->eps, pl,        \
+                       c->fld_buf, c->fld_part)
+    if (all_kinds) {
+        if (range) PLFX_FLD_LAUNCH(1, 1); else PLFX_FLD_LAUNCH(1, 0);
+    } else {
+        if (range) PLFX_FLD_LAUNCH(0, 1); else PLFX_FLD_LAUNCH(0, 0);
+    }
+#undef PLFX_FLD_LAUNCH
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    if (out) {
+        for (int k = 0; k < nsel; k++)   // a selector named again: its row once more
+            if (first[sel[k]] != k)
+                HIPCHK(c, hipMemcpyAsync(c->fld_buf + (size_t)k * ne, c->fld_buf + (size_t)first[sel[k]] * ne, 8 * ne,
+                                         hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, c->fld_buf, (size_t)nsel * ne * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (range) {
+        c->fld_host.resize((size_t)2 * FLD_COUNT * g);
+        HIPCHK(c, hipMemcpyAsync(c->fld_host.data(), c->fld_part, (size_t)2 * FLD_COUNT * g * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, stream_sync(c));
+    if (range)   // at most MAXPART partials per scalar: the last stage on the host
+        for (int k = 0; k < nsel; k++) {
+            const double *pmin = c->fld_host.data() + (size_t)(2 * sel[k]) * g, *pmax = pmin + g;
+            double lo = pmin[0], hi = pmax[0];
+            bool isnan_ = false;
+            for (int b = 0; b < g; b++) {
+                isnan_ = isnan_ || pmin[b] != pmin[b] || pmax[b] != pmax[b];
+                lo = std::min(lo, pmin[b]);
+                hi = std::max(hi, pmax[b]);
+            }
+            range[2 * k] = isnan_ ? std::nan("") : lo;
+            range[2 * k + 1] = isnan_ ? std::nan("") : hi;
+        }
     return PLFX_OK;
 }
 

@@ -2736,6 +2736,163 @@ k_eps_from_u(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restri
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Element result fields (plfx_element_fields): the values the closures of the reference's Model.plot compute per element
+// (model.py:1591-1677), one (nel,) row per selector, and their minimum / maximum.
+enum : int {
+    FLD_STRAIN1 = 0, FLD_STRAIN2, FLD_STRAIN12, FLD_STRESS1, FLD_STRESS2, FLD_STRESS12, FLD_PLASTIC1, FLD_PLASTIC2,
+    FLD_PLASTIC12, FLD_SEQ, FLD_SEQJ2, FLD_PEEQ, FLD_ETOT, FLD_UX, FLD_UY, FLD_COUNT   // = PLFX_FIELD_* of plfx.h
+};
+struct FieldPlan {          // passed by value: every member is wave-uniform, every branch on it scalar
+    int32_t row[FLD_COUNT]; // output row of a selector (read where want has its bit)
+    uint32_t want;          // bit id: selector id is asked for
+    uint32_t sig_cols, epl_cols, eps_cols;   // bit k: SoA column k of the field is read
+    int32_t need_u;         // conn and u are read (displacements, or strain formed from u)
+    int32_t eps_from_u;     // the stored eps is behind u: the strain selectors take class_strain(u)
+    int32_t store;          // write the rows
+};
+
+// minimum / maximum over the 64 lanes of a wave, result in every lane: the DPP butterfly of wave_allsum
+__device__ __forceinline__ double wave_allmin(double v)
+{
+    v = fmin(v, dpp_f64<0xB1>(v));
+    v = fmin(v, dpp_f64<0x4E>(v));
+    v = fmin(v, dpp_f64<0x141>(v));
+    v = fmin(v, dpp_f64<0x140>(v));
+    return fmin(fmin(readlane_f64(v, 0), readlane_f64(v, 16)), fmin(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+__device__ __forceinline__ double wave_allmax(double v)
+{
+    v = fmax(v, dpp_f64<0xB1>(v));
+    v = fmax(v, dpp_f64<0x4E>(v));
+    v = fmax(v, dpp_f64<0x141>(v));
+    v = fmax(v, dpp_f64<0x140>(v));
+    return fmax(fmax(readlane_f64(v, 0), readlane_f64(v, 16)), fmax(readlane_f64(v, 32), readlane_f64(v, 48)));
+}
+
+// basic.py:30-65 sig_eq_j2 on the Voigt components
+__device__ __forceinline__ double j2_seq(const double *s)
+{
+    const double d12 = s[0] - s[1], d23 = s[1] - s[2], d31 = s[2] - s[0];
+    const double sj2 = 0.5 * (d12 * d12 + d23 * d23 + d31 * d31) + 3. * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]);
+    return sqrt(sj2);
+}
+
+// One thread per element, latency structure of k_update_state: tables in LDS, the streams whose address depends on the
+// element index alone (class, conn, the columns of sig / epl / eps the selectors need) issued at the top of the pass, the
+// gathers of u behind conn, the stores (one coalesced row per selector) after the last load.  The material of an element
+// comes from its class.  ALLKINDS = 0: every material of the table takes hill_seq (elastic, Hill-6, the SVC kinds -- J2 or
+// Hill on the Voigt stress); 1: the dispatch of k_point_eval (what = 0) with the principal-stress, Tresca and Barlat forms.
+// RANGE: minimum and maximum of every row per block (DPP butterfly, then the BLOCK / 64 wave results through LDS) into
+// part[(2 id + ismax) * gridDim.x + block]; a NaN anywhere in the block's part of a row makes both of its partials NaN
+// (fmin / fmax alone would drop it, np.amin / np.amax do not).  No floating-point atomics.
+template <int ALLKINDS, int RANGE>
+__global__ void __launch_bounds__(BLOCK)
+k_element_fields(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off,
+                 const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ u2,
+                 const double *__restrict__ sig, const double *__restrict__ epl, const double *__restrict__ eps, FieldPlan pl,
+                 double *__restrict__ out, double *__restrict__ part)
+{
+    __shared__ SweepTables tb;
+    stage_tables(tb, gmat, nmat, gcls, ncls);
+    __syncthreads();
+    double mn[FLD_COUNT], mx[FLD_COUNT];
+    unsigned nanbits = 0;
+#pragma unroll
+    for (int k = 0; k < FLD_COUNT; k++) {
+        mn[k] = __builtin_huge_val();
+        mx[k] = -__builtin_huge_val();
+    }
+#define PLFX_FLD_EMIT(ID, VAL)                                                  \
+    if ((pl.want >> (ID)) & 1u) {                                               \
+        const double v_ = (VAL);                                                \
+        if (pl.store) out[(size_t)pl.row[ID] * nel + e] = v_;                   \
+        if (RANGE) {                                                            \
+            mn[ID] = fmin(mn[ID], v_);                                          \
+            mx[ID] = fmax(mx[ID], v_);                                          \
+            nanbits |= (v_ != v_) ? (1u << (ID)) : 0u;                          \
+        }                                                                       \
+    }
+    for (int e = blockIdx.x * BLOCK + threadIdx.x; e < nel; e += gridDim.x * BLOCK) {
+        const size_t ge = (size_t)e + e_off;
+        const int cl = cls[e];
+        int n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+        if (pl.need_u) {
+            n0 = conn[ge * 4], n1 = conn[ge * 4 + 1], n2 = conn[ge * 4 + 2], n3 = conn[ge * 4 + 3];
+        }
+        double s[6] = {}, p[6] = {}, et[6] = {};
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            if ((pl.sig_cols >> k) & 1u) s[k] = sig[(size_t)k * nel + e];
+            if ((pl.epl_cols >> k) & 1u) p[k] = epl[(size_t)k * nel + e];
+            if ((pl.eps_cols >> k) & 1u) et[k] = eps[(size_t)k * nel + e];
+        }
+        asm volatile("" ::: "memory");  // the loads above may not sink behind the table look-up to their first use
+        const ClassDev &c = tb.scls[cl];
+        double ux = 0., uy = 0.;
+        if (pl.need_u) {
+            // the stored eps is behind u: the same inline function on the same staged tables as k_eps_from_u (the same bits)
+            if (pl.eps_from_u) class_strain(c, u2, n0, n1, n2, n3, et);
+            if ((pl.want >> FLD_UX) & 3u) {   // model.py:1656-1672: hh += u[node] * 0.25 over el.nodes in their order
+                const double2 a0 = u2[n0], a1 = u2[n1], a2 = u2[n2], a3 = u2[n3];
+                ux = ((a0.x * 0.25 + a1.x * 0.25) + a2.x * 0.25) + a3.x * 0.25;
+                uy = ((a0.y * 0.25 + a1.y * 0.25) + a2.y * 0.25) + a3.y * 0.25;
+            }
+        }
+        PLFX_FLD_EMIT(FLD_STRAIN1, et[0] * 100.)
+        PLFX_FLD_EMIT(FLD_STRAIN2, et[1] * 100.)
+        PLFX_FLD_EMIT(FLD_STRAIN12, et[5] * 100.)
+        PLFX_FLD_EMIT(FLD_STRESS1, s[0])
+        PLFX_FLD_EMIT(FLD_STRESS2, s[1])
+        PLFX_FLD_EMIT(FLD_STRESS12, s[5])
+        PLFX_FLD_EMIT(FLD_PLASTIC1, p[0] * 100.)
+        PLFX_FLD_EMIT(FLD_PLASTIC2, p[1] * 100.)
+        PLFX_FLD_EMIT(FLD_PLASTIC12, p[5] * 100.)
+        if ((pl.want >> FLD_SEQ) & 1u) {   // Stress(el.sig).seq(el.Mat): calc_seq of the element's own material
+            const MatDev &m = tb.smat[c.mat];
+            const int kd = m.kind;
+            double q;
+            if (ALLKINDS)
+                q = (kd == 2 || kd == 6) ? princ_seq(m, s) : kd == 4 ? tresca_seq(s) : kd == 5 ? barlat_seq(m, s) : hill_seq(m, s);
+            else
+                q = hill_seq(m, s);
+            PLFX_FLD_EMIT(FLD_SEQ, q)
+        }
+        PLFX_FLD_EMIT(FLD_SEQJ2, j2_seq(s))
+        PLFX_FLD_EMIT(FLD_PEEQ, eps_eq(p) * 100.)
+        PLFX_FLD_EMIT(FLD_ETOT, eps_eq(et) * 100.)
+        PLFX_FLD_EMIT(FLD_UX, ux)
+        PLFX_FLD_EMIT(FLD_UY, uy)
+    }
+#undef PLFX_FLD_EMIT
+    if (RANGE) {
+        __shared__ double shr[2 * FLD_COUNT][BLOCK / 64];
+        __shared__ unsigned shnan;
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        if (threadIdx.x == 0) shnan = 0u;
+        __syncthreads();
+        if (nanbits) atomicOr(&shnan, nanbits);
+#pragma unroll
+        for (int k = 0; k < FLD_COUNT; k++)
+            if ((pl.want >> k) & 1u) {
+                const double a = wave_allmin(mn[k]), b = wave_allmax(mx[k]);
+                if (lane == 0) {
+                    shr[2 * k][w] = a;
+                    shr[2 * k + 1][w] = b;
+                }
+            }
+        __syncthreads();
+        const int t = threadIdx.x;
+        if (t < 2 * FLD_COUNT && ((pl.want >> (t >> 1)) & 1u)) {
+            double v = shr[t][0];
+#pragma unroll
+            for (int i = 1; i < BLOCK / 64; i++) v = (t & 1) ? fmax(v, shr[t][i]) : fmin(v, shr[t][i]);
+            if ((shnan >> (t >> 1)) & 1u) v = __builtin_nan("");
+            part[(size_t)t * gridDim.x + blockIdx.x] = v;
+        }
+    }
+}
+
 // calc_global sums (model.py:1500-1507): partials of sum(x*Vel) for the 18 components
 __global__ void __launch_bounds__(BLOCK)
 k_global_partials(const ClassDev *__restrict__ gcls, int nel, const int32_t *__restrict__ cls, const double *__restrict__ sig,

@@ -133,6 +133,26 @@ class _ElementList(object):
             yield _ElementView(self._m, k)
 
 
+FIELD_SELECTORS = _lib.FIELD_NAMES + ('mat',)
+"""selectors of ``Model.field`` / ``fields`` / ``field_range``: the keys of the reference's ``Model.plot`` (model.py:1679-1696)"""
+
+
+def autoscale_range(vmin, vmax, auto_scale=True):
+    """Colour-bar limits of the reference's ``Model.plot`` from a field's minimum and maximum (model.py:1700-1716): with
+    ``auto_scale`` (neither limit given by the caller) a range narrower than 0.1, or than 4 % of ``vmax``, is widened --
+    by 0.05 either way when ``|vmax| < 0.1``, else by 2 % of either limit, outwards for a positive ``vmax``."""
+    delta = np.abs(vmax - vmin)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if auto_scale and (delta < 0.1 or np.float64(delta) / vmax < 0.04):
+            if np.abs(vmax) < 0.1:
+                vmax, vmin = vmax + 0.05, vmin - 0.05
+            elif vmax > 0.:
+                vmax, vmin = vmax * 1.02, vmin * 0.98
+            else:
+                vmax, vmin = vmax * 0.98, vmin * 1.02
+    return float(vmin), float(vmax)
+
+
 class Model(object):
     """Finite-element model (2-d, Q4) with the reference's attributes: ``dim, planestress, Nsec, LS,
     lenx, leny, thick, nonlin, mat, Nnode, NnodeX, NnodeY, Nel, Ndof, npos, noleft, noright, nobot,
@@ -1207,6 +1227,71 @@ class Model(object):
             return   # the homogenised values of the last load step are current (element sums over strips need the halo masks)
         self._calc_global_device(eng)
 
+    # ------------------------------------------------------------------ element result fields
+    def _field_rows(self, names):
+        """rows of the device fields ``names`` (no 'mat') that are not cached yet: ONE device pass, placed into full-size
+        arrays like ``_state`` does"""
+        miss = [n for n in dict.fromkeys(names) if ('field', n) not in self._cache]
+        if not miss:
+            return
+        rows, _ = self._ensure_engine().element_fields([_lib.FIELD_ID[n] for n in miss])
+        for n, a in zip(miss, rows):
+            if self._strip is not None:
+                full = np.zeros(self.Nel)
+                o = self._e0 - self._strip['state_el0']
+                full[self._e0:self._e1] = a[o:o + self._e1 - self._e0]
+                a = full
+            elif self._shard is not None:
+                full = np.zeros(self.Nel)
+                full[self._e0:self._e1] = a
+                a = full
+            self._cache[('field', n)] = np.ascontiguousarray(a)
+
+    def _field_mat(self):
+        """el.Mat.num of every element (model.py:1674-1677), from the material map on the host"""
+        return np.array([m.num for m in self.mat], dtype=np.float64)[np.asarray(self._mat_id)]
+
+    def fields(self, fsel):
+        """Element result fields as arrays: dict ``{selector: (Nel,) float64 array in element order}`` of the values the
+        reference's ``Model.plot`` colours its elements with (model.py:1591-1677; selectors: ``FIELD_SELECTORS``), all of
+        them from one device pass over the state in HBM.  Unknown selector: ``KeyError``.  Before the first solve the
+        fields are those of the zero state; on a sharded or strip model this rank's owned elements are filled and the rest
+        is zero.  Cached until the next solve, like the element results."""
+        names = list(fsel)
+        for n in names:
+            if n not in FIELD_SELECTORS:
+                raise KeyError(n)
+        self._field_rows([n for n in names if n != 'mat'])
+        return {n: (self._field_mat() if n == 'mat' else self._cache[('field', n)]) for n in names}
+
+    def field(self, fsel):
+        """One element result field, see ``fields``."""
+        return self.fields([fsel])[fsel]
+
+    def field_range(self, fsel, vmin=None, vmax=None):
+        """``(vmin, vmax)`` of the colour bar the reference's ``Model.plot(fsel, vmin=, vmax=)`` shows (model.py:1700-1716):
+        the field's minimum / maximum where an argument is None -- reduced on the device, no field is downloaded; a NaN in
+        the field gives NaN like ``np.amin`` / ``np.amax`` -- and, with both None, the reference's widening of a narrow range."""
+        if fsel not in FIELD_SELECTORS:
+            raise KeyError(fsel)
+        key = ('range', fsel)
+        if (vmin is None or vmax is None) and key not in self._cache:
+            if fsel == 'mat':
+                a = self._field_mat()
+                lo, hi = float(np.amin(a)), float(np.amax(a))
+            else:
+                _, r = self._ensure_engine().element_fields([_lib.FIELD_ID[fsel]], want_out=False, want_range=True)
+                lo, hi = float(r[0, 0]), float(r[0, 1])
+                if self._shard is not None:   # owned elements of every rank: op 3 is min, the maximum goes in negated
+                    nan = np.isnan(lo) or np.isnan(hi)
+                    g = self._host_reduce(np.array([np.inf if nan else lo, np.inf if nan else -hi, -1. if nan else 0.]), 3)
+                    lo, hi = (np.nan, np.nan) if g[2] < 0. else (float(g[0]), -float(g[1]))
+            self._cache[key] = (lo, hi)
+        return autoscale_range(self._cache[key][0] if vmin is None else vmin, self._cache[key][1] if vmax is None else vmax,
+                               vmin is None and vmax is None)
+
     def plot(self, *args, **kw):
+        """Refuses: plotting is out of scope.  The arrays a plot needs come from ``field`` / ``fields`` (the sixteen element
+        fields of the reference's ``plot``) and ``field_range`` (its colour-bar limits)."""
         raise NotImplementedError('plotting is out of scope of pylabfea_amd (SURVEY.md §2); '
                                   'use the reference package on the arrays u, npos, element[i].sig')
