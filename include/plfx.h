@@ -235,6 +235,13 @@ int plfx_sweep_info(plfx_ctx *ctx, int64_t *sweeps, int64_t *tangents_rewritten)
  * launches out (heavy_skipped counts such sweeps); if its own list is not empty after all, the launches and a second flags
  * kernel follow after one more round trip (heavy_recovered).  Results are the same either way. */
 int plfx_sweep_launch_info(plfx_ctx *ctx, int64_t *heavy_skipped, int64_t *heavy_recovered);
+/* Between the boundary values and the first operator pass (one GPU, no strip; PLFX_BC_ROWS=0 or
+ * PLFX_REUSE=0 at plfx_create: all four stay 0).  apply_bc calls that rewrote rhs on the rows next to prescribed nodes only
+ * (same Dirichlet set, no force vector) instead of passing over all DOFs (rhs_rows_only); those among them that kept the
+ * Jacobi scaling because the diagonal had not been rewritten (dinv_kept) / formed it again on its own (dinv_refreshed);
+ * solves whose du was composed behind the first convergence test, under the host's wait for it (du_early).  Results are
+ * the same bit for bit either way. */
+int plfx_bc_info(plfx_ctx *ctx, int64_t *rhs_rows_only, int64_t *dinv_kept, int64_t *dinv_refreshed, int64_t *du_early);
 /* Which kernels run the 6-feature SVC materials (Material.response with an ML yield function, material.py:398-405 evaluates
  * any trained svm_yf): bit k of *row_materials = material k runs with 16 lanes per element / point (one launch per material
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read

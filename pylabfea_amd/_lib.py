@@ -61,7 +61,7 @@ SYMBOLS = [
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
     'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
-    'plfx_sweep_launch_info', 'plfx_element_fields',
+    'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info',
 ]
 
 _lib = None
@@ -536,6 +536,13 @@ class Context(object):
         a, b = C.c_int64(), C.c_int64()
         self._chk(self.lib.plfx_sweep_launch_info(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def bc_info(self):
+        """(apply_bc calls that rewrote rhs on the boundary rows only, those among them that kept dinv, those that formed it
+        again on its own, solves whose du was composed under the wait for the first test) since the context was created"""
+        a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_bc_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
+        return a.value, b.value, r.value, d.value
 
     def svc_info(self):
         """(bit mask of the 6-feature SVC materials on the 16-lanes-per-element kernels, mask of those run one thread per

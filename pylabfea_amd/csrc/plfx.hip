@@ -234,6 +234,15 @@ struct plfx_ctx {
     int32_t *bc_rows = nullptr;     // nodes whose matrix rows touch a prescribed node (rows of K w that can be non-zero)
     int bc_nrows = 0;
     double *kw = nullptr;           // K w, zero outside bc_rows
+    // Between "the boundary values are known" and the first operator pass (PLFX_BC_ROWS=0 or PLFX_REUSE=0: off;
+    // never with a strip or inside a communicator).  rhs_rows_ok: the last full k_bc_finish ran with this Dirichlet set and
+    // this row list and without a force vector, and nothing has made rhs dense since -- rhs is +0.0 off bc_rows and
+    // k_spmv_rows rewrites it on them.  dinv_ok: c->dinv was formed from the present (diag, is_presc); cleared at every launch
+    // that writes c->diag.  A plain flag, not op_epoch: the set-up pass enqueued behind a sweep's flags writes diag before
+    // plfx_assemble counts it, and assemble_fine_val on behalf of plfx_get_csr never counts.
+    bool bc_rows_on = true;
+    bool rhs_rows_ok = false, dinv_ok = false;
+    long long n_rhs_rows = 0, n_dinv_kept = 0, n_dinv_refreshed = 0, n_du_early = 0;   // plfx_bc_info
     int last_heavy = -1;  // elements that needed the sub-divided corrector in the last sweep (-1: no sweep yet)
     long long n_heavy_skipped = 0, n_heavy_recovered = 0;   // sweeps that left the corrector launches out / had to add them after all
     bool x_is_du = false;  // c->x still holds the last solution on the free DOFs (0 on the prescribed ones) = the warm start
@@ -914,6 +923,7 @@ void free_mesh(plfx_ctx *c)
     dfree(c->kw);
     dfree(c->bc_rows);
     c->bc_nrows = 0;
+    c->rhs_rows_ok = c->dinv_ok = false;
 }
 
 void free_svr_flow(plfx_ctx *c, int k)
@@ -1220,6 +1230,7 @@ int assemble_fine_val(plfx_ctx *c)
                        (matfree(c) && c->assembled) ? c->Mop : c->Mel, c->dcol, c->dval, c->diag,
                        (matfree(c) && c->assembled) ? 1 : 0);  // the snapshot is in pair layout, the live array SoA
     HIPCHK(c, hipGetLastError());
+    c->dinv_ok = false;   // (c->diag rewritten)
     c->val_valid = true;
     return 0;
 }
@@ -1718,6 +1729,7 @@ int plfx_create(int device, plfx_ctx **out)
     if (const char *e4 = getenv("PLFX_COLL_TIMEOUT")) c->coll_timeout_s = atof(e4);
     if (const char *e4 = getenv("PLFX_MG_GRAPH")) c->want_mg_graph = atoi(e4) ? 1 : 0;
     if (const char *e8 = getenv("PLFX_REUSE")) c->reuse = atoi(e8) != 0;
+    if (const char *e9 = getenv("PLFX_BC_ROWS")) c->bc_rows_on = atoi(e9) != 0;
     if (const char *e9 = getenv("PLFX_PREDICT")) c->predict = atoi(e9) != 0;
     {
         const char *e5 = getenv("PLFX_MAILBOX");
@@ -3009,6 +3021,7 @@ int plfx_set_strip(plfx_ctx *c, int own_col0, int own_col1, int global_col0, int
     c->assembled = false, c->M_dirty = true;
     c->bc_set = false;
     c->bc_valid = false;
+    c->rhs_rows_ok = c->dinv_ok = false;
     c->x_is_du = false;
     c->memo.valid = false;
     return PLFX_OK;
@@ -3075,6 +3088,16 @@ int plfx_sweep_info(plfx_ctx *c, int64_t *sweeps, int64_t *tangents_rewritten)
     if (!c) return PLFX_ERR_ARG;
     if (sweeps) *sweeps = c->n_sweeps;
     if (tangents_rewritten) *tangents_rewritten = c->n_tangents_rewritten;
+    return PLFX_OK;
+}
+
+int plfx_bc_info(plfx_ctx *c, int64_t *rhs_rows_only, int64_t *dinv_kept, int64_t *dinv_refreshed, int64_t *du_early)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (rhs_rows_only) *rhs_rows_only = c->n_rhs_rows;
+    if (dinv_kept) *dinv_kept = c->n_dinv_kept;
+    if (dinv_refreshed) *dinv_refreshed = c->n_dinv_refreshed;
+    if (du_early) *du_early = c->n_du_early;
     return PLFX_OK;
 }
 
@@ -3394,6 +3417,7 @@ int plfx_state_reset(plfx_ctx *c)
     HIPCHK(c, hipGetLastError());
     c->assembled = false, c->M_dirty = true;
     c->x_is_du = false;
+    c->rhs_rows_ok = c->dinv_ok = false;   // (a new history starts with one full k_bc_finish)
     c->res_is_sig = c->res_fresh = c->eps_stale = false;
     c->last_heavy = -1;   // the next sweep launches its corrector kernels whatever the one before found
     return PLFX_OK;
@@ -3591,6 +3615,7 @@ int plfx_assemble(plfx_ctx *c)
             LAUNCH_SETUP(0, live, (double2 *)c->diag,
                                c->Mop, (mg_active(c) && level_plain(c->mg[0])) ? c->mg[1].Mel : (double *)nullptr, (const double2 *)nullptr, 0, 0,
                                (double2 *)nullptr);
+        c->dinv_ok = false;   // (c->diag rewritten, here or by the pass behind the sweep's flags)
         c->val_valid = false;
     } else {
         int rc = assemble_fine_val(c);
@@ -3706,9 +3731,11 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
                 HIPCHK(c, hipMemcpyAsync(c->bc_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, c->stream));
             if (!c->kw && (rc = dalloc(c, &c->kw, nd))) return rc;
             HIPCHK(c, hipMemsetAsync(c->kw, 0, 8 * nd, c->stream));
+            c->rhs_rows_ok = false;   // another row list, kw rebuilt: rhs needs one full pass
             HIPCHK(c, stream_sync(c));  // `rows` goes out of scope
         }
         c->bc_valid = true;
+        c->rhs_rows_ok = c->dinv_ok = false;   // (another mask: dinv and the zeros of rhs belong to the old one)
     }
     if (c->reuse && seg4 && same_set && c->bc_set && c->bc_memo && c->bc_epoch == c->op_epoch && !fext && !c->bc_memo_fext &&
         memcmp(&c->bc_last, segv, sizeof(BcSegVals)) == 0) {
@@ -3751,20 +3778,39 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
         HIPCHK(c, hipGetLastError());
     }
     if (fext) HIPCHK(c, hipMemcpyAsync(c->fext, fext, 8 * nd, hipMemcpyHostToDevice, c->stream));
+    // rhs = fext - K w and dinv.  Without a force vector rhs can differ from what it was on bc_rows only, and dinv is a function
+    // of (diag, is_presc): with the set and the row list of the last full pass, k_spmv_rows writes rhs on its rows and dinv is
+    // formed again only if the diagonal was rewritten since.  One GPU, no strip; the full pass otherwise.
+    const bool rows_only = c->bc_rows_on && c->reuse && !c->strip.on && !comm_active(c) && c->rhs_rows_ok && same_set && !fext &&
+                           c->bc_nrows > 0;
+    const double2 *rm = rows_only ? (const double2 *)c->is_presc : nullptr;
+    double2 *rr = rows_only ? (double2 *)c->rhs : nullptr;
     if (c->bc_nrows > 0)  // K w on the few rows where it can be non-zero
     {
         if (matfree(c) && c->op.colr)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_rows<2>), dim3((c->bc_nrows + BLOCK - 1) / BLOCK), dim3(BLOCK), 0,
-                               c->stream, c->bc_nrows, c->bc_rows, c->op, (const double2 *)c->wv, (double2 *)c->kw);
+                               c->stream, c->bc_nrows, c->bc_rows, c->op, (const double2 *)c->wv, (double2 *)c->kw, rm, rr);
         else if (matfree(c))
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_rows<1>), dim3((c->bc_nrows + BLOCK - 1) / BLOCK), dim3(BLOCK), 0,
-                               c->stream, c->bc_nrows, c->bc_rows, c->op, (const double2 *)c->wv, (double2 *)c->kw);
+                               c->stream, c->bc_nrows, c->bc_rows, c->op, (const double2 *)c->wv, (double2 *)c->kw, rm, rr);
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_rows<0>), dim3((c->bc_nrows + BLOCK - 1) / BLOCK), dim3(BLOCK), 0,
-                               c->stream, c->bc_nrows, c->bc_rows, c->op, (const double2 *)c->wv, (double2 *)c->kw);
+                               c->stream, c->bc_nrows, c->bc_rows, c->op, (const double2 *)c->wv, (double2 *)c->kw, rm, rr);
     }
-    hipLaunchKernelGGL(k_bc_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd,
-                       fext ? c->fext : nullptr, c->kw, c->diag, c->is_presc, c->rhs, c->dinv);
+    if (rows_only) {
+        c->n_rhs_rows++;
+        if (c->dinv_ok)
+            c->n_dinv_kept++;
+        else {
+            hipLaunchKernelGGL(k_dinv, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->diag, c->is_presc, c->dinv);
+            c->n_dinv_refreshed++;
+        }
+    } else {
+        hipLaunchKernelGGL(k_bc_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd,
+                           fext ? c->fext : nullptr, c->kw, c->diag, c->is_presc, c->rhs, c->dinv);
+        c->rhs_rows_ok = !fext;
+    }
+    c->dinv_ok = true;
     HIPCHK(c, hipGetLastError());
     if (fext) HIPCHK(c, stream_sync(c));
     if (mg_active(c)) {
@@ -4453,6 +4499,7 @@ struct SolveRun {
     bool pred_active, pred_fused;    // a history exists: this solve may be answered by x + alpha d; K d came with the start kernel's pass
     bool pred_d_ready, pred_moved;   // (d = x - pred_x is in pred_d; the start x + alpha d was accepted as the solution)
     bool pred_finished;              // (... and k_pred_finish has composed du and advanced the history already)
+    bool du_early;                   // the gated k_compose_du behind the first test has composed du (that test passed)
 };
 
 bool solve_debug_on() { static const bool on = getenv("PLFX_SOLVE_DEBUG") && atoi(getenv("PLFX_SOLVE_DEBUG")) != 0; return on; }
@@ -4581,9 +4628,20 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
     if (wait_first && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on) {
         // the predictor solve of a load step repeats the system of the solve before it up to the last bits of its boundary
         // values: x passes the first test.  Learn that before enqueuing what would return at once (six launches, 28 us)
+        // du of a passed test is composed under the round trip: gated on the flag the test just wrote, a no-op otherwise
+        const bool early = c->bc_rows_on && c->reuse && !comm_active(c);
+        if (early) {
+            hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du,
+                               (const CgScalars *)c->sc);
+            HIPCHK(c, hipGetLastError());
+        }
         if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
         s.done = s.hs.done;
         first_passed = s.done != 0;
+        if (early && s.done == 1) {
+            s.du_early = true;
+            c->n_du_early++;
+        }
     }
     if (first_passed) {
         pred_first_passed = true;   // (nothing to do: done, hs as the chain below would have left them)
@@ -4847,7 +4905,7 @@ int solve_finish(plfx_ctx *c, SolveRun &s, double rtol, int *iters, double *relr
         HIPCHK(c, hipMemcpyAsync(&hs, c->sc, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, stream_sync(c));
     }
-    if (!s.pred_finished && (rc = compose_du(c))) return rc;
+    if (!s.pred_finished && !s.du_early && (rc = compose_du(c))) return rc;
     c->x_is_du = true;  // x = du on the free DOFs, 0 on the prescribed ones: the next warm start
     const int its_done = (done && hs.iters >= 0) ? hs.iters : it;
     // history of the initial guess: the solution this solve started from becomes "the one before" -- only if this solve moved
@@ -5074,6 +5132,9 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         }
         c->spec_h0 = h[0];
         c->spec_h1 = h[1];
+        // the speculative set-up pass rewrote c->diag exactly if the flags kernel it sits behind reported a changed tangent
+        // (its predicate flags[8] is "h[0] == 0" of that kernel; after a recovery it was told to skip, and plfx_assemble launches)
+        if (spec && h[0]) c->dinv_ok = false;
     } else {
         hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4);
         HIPCHK(c, hipGetLastError());

@@ -2490,12 +2490,19 @@ __global__ void __launch_bounds__(BLOCK) k_gather(int n, const int32_t *idx, con
 template <int GRID>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_rows(int nlist, const int32_t *__restrict__ list, KOp op, const double2 *__restrict__ w,
-            double2 *__restrict__ q)
+            double2 *__restrict__ q, const double2 *__restrict__ is_presc = nullptr, double2 *__restrict__ rhs = nullptr)
 {
     const int k = blockIdx.x * BLOCK + threadIdx.x;
     if (k >= nlist) return;
     const int i = list[k];
-    q[i] = op_apply<GRID>(op, i, [&](int j) { return w[j]; });
+    const double2 kw = op_apply<GRID>(op, i, [&](int j) { return w[j]; });
+    q[i] = kw;
+    // rhs of these rows as k_bc_finish forms it without a force vector (0. - kw, not -kw: +0.0 where kw is +0.0); off the
+    // listed rows K w is zero and rhs is the +0.0 the last full k_bc_finish left there (apply_bc_impl)
+    if (rhs) {
+        const double2 m = is_presc[i];
+        rhs[i] = make_double2((m.x == 0.) ? 0. - kw.x : 0., (m.y == 0.) ? 0. - kw.y : 0.);
+    }
 }
 
 // rhs = fext - K w (q holds K w);  dinv = free ? 1/|diag| : 0
@@ -2511,10 +2518,24 @@ k_bc_finish(size_t ndof, const double *__restrict__ fext, const double *__restri
     }
 }
 
-// du = x (free) + du_presc (prescribed)
+// dinv alone, as k_bc_finish forms it: where the diagonal or the Dirichlet mask changed and rhs comes from k_spmv_rows
 __global__ void __launch_bounds__(BLOCK)
-k_compose_du(size_t ndof, const double *__restrict__ x, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du)
+k_dinv(size_t ndof, const double *__restrict__ diag, const double *__restrict__ is_presc, double *__restrict__ dinv)
 {
+    for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK) {
+        const bool free_dof = (is_presc[i] == 0.);
+        const double d = fabs(diag[i]);
+        dinv[i] = free_dof ? (d > 1e-300 ? 1. / d : 1.) : 0.;
+    }
+}
+
+// du = x (free) + du_presc (prescribed).  gate != null: enqueued behind a convergence test the host has not seen yet --
+// a no-op unless that test passed (done == 1), in which case x is the solution
+__global__ void __launch_bounds__(BLOCK)
+k_compose_du(size_t ndof, const double *__restrict__ x, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du,
+             const CgScalars *__restrict__ gate = nullptr)
+{
+    if (gate && gate->done != 1) return;
     for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK)
         du[i] = (is_presc[i] != 0.) ? dup[i] : x[i];
 }
