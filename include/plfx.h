@@ -153,6 +153,19 @@ int plfx_fgrad_batch_wh(plfx_ctx *ctx, int mat, int n, const double *sig, const 
  * scale_seq ONCE, :962).  PLFX_ERR_UNSUPPORTED for every other kind (the reference raises for Hill / Tresca /
  * Barlat :965-970, NotImplementedError for sdim = 3 :950). */
 int plfx_hessian_batch(plfx_ctx *ctx, int mat, int n, const double *sig, const double *epl, double *hess);
+/* Material.yield_scale: the factor x[n] with calc_yf(x su, epl) = 0 along n unit stresses su[n*6] -- the root search behind
+ * the reference's polar_plot_yl (material.py:3290-3293), kept on the device ray by ray.  epl: NULL or [n*6]; x0: NULL or [n]
+ * start values, default sflow(epl) / seq_J2(su).
+ * SVC kinds: the root that the marching bracket of ML_full_yf (material.py:468-486) isolates, made symmetric: from x0 down by
+ * factors 0.98 while f >= 0 (to 0.01 x0), else up by factors 1.02 while f < 0 (to 5 x0); the bracket f(lo) < 0 <= f(hi) is
+ * bisected until lo and hi are neighbouring doubles.  Analytic kinds (homogeneous of degree one): sflow(epl) / seq(su); the
+ * value of x0 is not used there, but a given x0 that is <= 0 or not finite makes the ray degenerate as for the SVC kinds.
+ * Rays of the principal-stress kinds (PLFX_PRINC3, PLFX_SVC3) with out-of-plane shear are reduced to their principal stresses
+ * on the host (plfx_sig_princ_host).  PLFX_ERR_ARG for an elastic material.
+ * status[n]: 0 root found; 1 no bracket in [0.01 x0, 5 x0]; 2 refinement cap reached; 3 degenerate ray (su = 0, seq(su) = 0
+ * where x follows from it -- analytic kinds, or no x0 given --, a non-finite input, x0 <= 0).  x is NaN unless status is 0. */
+int plfx_yield_scale(plfx_ctx *ctx, int mat, int n, const double *su, const double *epl, const double *x0, double *x,
+                     int32_t *status);
 
 /* Index products of Model.mesh for the reference's structured NX x NY grid, computed on the host (no context, no GPU):
  * conn[NX*NY*4] = [n1, n1+1, n1+NnodeY, n1+NnodeY+1] with n1 = (ih / NY) * NnodeY + ih % NY for element ih = j*NY + k
@@ -503,7 +516,7 @@ int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
- *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

@@ -61,7 +61,7 @@ SYMBOLS = [
     'plfx_set_response_maxit', 'plfx_sig_princ_host', 'plfx_eig3_host',
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
     'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
-    'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info',
+    'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info', 'plfx_yield_scale',
 ]
 
 _lib = None
@@ -292,6 +292,23 @@ class Context(object):
         out = np.empty((len(sig), 6, 6))
         self._chk(self.lib.plfx_hessian_batch(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(out)))
         return out
+
+    def yield_scale(self, mat, su, epl=None, x0=None):
+        """(x (N,), status (N,) int32): the factor with calc_yf(x su, epl) = 0 along N unit stresses su (N,6), searched on
+        the device ray by ray (plfx_yield_scale).  epl (N,6) or None (zeros); x0 (N,) start values or None
+        (sflow(epl) / seq_J2(su)).  status 0 root found, 1 no bracket in [0.01 x0, 5 x0], 2 refinement cap, 3 degenerate ray;
+        x is NaN where status is not 0."""
+        su = _f64(su).reshape(-1, 6)
+        epl = None if epl is None else _f64(epl).reshape(-1, 6)
+        x0 = None if x0 is None else _f64(x0).reshape(-1)
+        if epl is not None and len(epl) != len(su):
+            raise ValueError('yield_scale: one plastic strain per unit stress expected')
+        if x0 is not None and len(x0) != len(su):
+            raise ValueError('yield_scale: one start value per unit stress expected')
+        x = np.empty(len(su))
+        st = np.zeros(len(su), dtype=np.int32)
+        self._chk(self.lib.plfx_yield_scale(self.h, int(mat), len(su), _dp(su), _dp(epl), _dp(x0), _dp(x), _dp(st)))
+        return x, st
 
     def yf(self, mat, sig, epl=None):
         sig = _f64(sig).reshape(-1, 6)

@@ -2043,6 +2043,9 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         HIPCHK(c, set_dyn_lds((const void *)k_sweep_wh_wave<1>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<6>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<15>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<6>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<2>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<15>, bytes));
     }
     c->M_dirty = true;
     c->memo.valid = false;
@@ -2310,6 +2313,86 @@ int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const dou
     hipFree(dsig);
     hipFree(dout);
     if (depl) hipFree(depl);
+    return PLFX_OK;
+}
+
+// Material.yield_scale: the factor x with calc_yf(x su) = 0 along n unit stresses.  SVC kinds: the search of k_yield_scale,
+// one launch; analytic kinds: the closed form sflow / seq(su).
+int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double *epl, const double *x0, double *x,
+                     int32_t *status)
+{
+    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
+    if (mat < 0 || mat >= c->nmat || n < 0 || !su || !x || !status) return fail(c, PLFX_ERR_ARG, "bad argument");
+    const int kind = c->hmat[mat].kind;
+    if (kind == PLFX_ELASTIC) return fail(c, PLFX_ERR_ARG, "yield_scale: material %d has no yield strength", mat);
+    if (n == 0) return PLFX_OK;
+    SvmBuffers B;   // device buffers of this call, released on every exit path
+    double *dsu = nullptr, *depl = nullptr, *dx0 = nullptr, *dx = nullptr;
+    int32_t *dst = nullptr;
+    if (int rc = B.get(c, &dsu, (size_t)n * 6)) return rc;
+    if (int rc = B.get(c, &dx, (size_t)n)) return rc;
+    if (int rc = B.get(c, &dst, (size_t)n)) return rc;
+    // principal-stress kinds (2-feature SVC, Hill-3 / J2 on principal stresses): rays with out-of-plane shear are reduced to
+    // their principal stresses here, by the LAPACK replay that the device runs for such states (plfx_sig_princ_host); the order
+    // of the principal stresses does not change along a ray.  The kernels then need the closed form of plane states only.
+    // (Material.yield_scale has done the same through _princ_rows, material.py, and nothing is left to reduce for its rays;
+    // this pass serves callers of the C-ABI.)
+    std::vector<double> red;
+    if (kind == PLFX_SVC3 || kind == PLFX_PRINC3)
+        for (int i = 0; i < n; i++) {
+            const double *s = su + 6 * (size_t)i;
+            bool fin = true;
+            for (int k = 0; k < 6; k++) fin = fin && std::isfinite(s[k]);
+            if (!fin || (s[3] == 0. && s[4] == 0.)) continue;
+            if (red.empty()) red.assign(su, su + 6 * (size_t)n);
+            double *r = red.data() + 6 * (size_t)i;
+            lapack3::sig_princ_lapack3(s, r);
+            r[3] = r[4] = r[5] = 0.;
+        }
+    HIPCHK(c, hipMemcpyAsync(dsu, red.empty() ? su : red.data(), (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+    if (epl) {
+        if (int rc = B.get(c, &depl, (size_t)n * 6)) return rc;
+        HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+    }
+    if (x0) {
+        if (int rc = B.get(c, &dx0, (size_t)n)) return rc;
+        HIPCHK(c, hipMemcpyAsync(dx0, x0, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    // a block stages the tables once; the fewest rays per block (4 per wave) that still leave no more than a few blocks per
+    // CU, so that a short batch spreads over the device.  The result does not depend on the choice.
+    int block = 64;
+    while (block < YS_BLOCK && (n + block / 16 - 1) / (block / 16) > 2 * c->prop.multiProcessorCount) block *= 2;
+    const int rpb = block / 16;
+    const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+#define YS_LAUNCH(NF)                                                                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_yield_scale<NF>), grid, dim3(block), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat, \
+                       c->svc_lds_need, mat, n, dsu, depl, dx0, dx, dst)
+    if (kind == PLFX_SVC6)
+        YS_LAUNCH(6);
+    else if (kind == PLFX_SVC3)
+        YS_LAUNCH(2);
+    else if (kind == PLFX_SVC_WH)
+        YS_LAUNCH(15);
+#undef YS_LAUNCH
+#define YS_LAUNCH(KD)                                                                                                       \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_yield_scale_analytic<KD>), dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->dmat, mat, n, \
+                       dsu, depl, dx0, dx, dst)
+    else if (kind == PLFX_PRINC3)
+        YS_LAUNCH(2);
+    else if (kind == PLFX_TRESCA)
+        YS_LAUNCH(4);
+    else if (kind == PLFX_BARLAT)
+        YS_LAUNCH(5);
+    else
+        YS_LAUNCH(1);
+#undef YS_LAUNCH
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(x, dx, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
     return PLFX_OK;
 }
 

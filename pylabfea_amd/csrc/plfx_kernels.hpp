@@ -483,6 +483,221 @@ k_hessian_row(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
     }
 }
 
+// Material.yield_scale of the SVC material `mat` on n rays: the factor x with calc_yf(x su) = 0 along the unit stress su, the
+// whole search of a ray on the device.  The root is the one the marching bracket of ML_full_yf
+// (material.py:468-486) isolates, made symmetric: from x0 (default sflow(epl) / seq_J2(su)) down by factors 0.98 while
+// f >= 0 (to 0.01 x0) or up by factors 1.02 while f < 0 (to 5 x0), then bisection of the bracket f(lo) < 0 <= f(hi) until lo
+// and hi are neighbouring doubles; of the two the one with the smaller |f| is returned.  Every loop is capped.
+// status: 0 root found, 1 no bracket in [0.01 x0, 5 x0], 2 refinement cap reached, 3 degenerate ray (su = 0, seq_J2(su) = 0 with
+// no x0 given, a non-finite input, x0 <= 0); x = NaN unless status is 0.
+// Only x moves along a ray, so the features are set up once per ray: NF = 6 / 15 x u with u the (deviatoric) stress features of
+// su, the plastic-strain features of NF = 15 fixed; NF = 2 (seq_J2(su) / scale_seq) x - 1 and the constant polar angle.  Every
+// difference x u_j - v_ij is ONE fma, so the sums are at least as accurate as the point functions'.
+// Lane mapping of k_hessian_row: 16 lanes (one DPP row) per ray, four rays per wave, lane L takes the vectors L, L + 16, ...
+// two per trip (two exp2 chains, two accumulators), closed by the DPP butterfly: every lane of a row holds the same f, control
+// flow is row-uniform, rows of a wave diverge freely (the butterfly stays inside the row).  The order of a ray's sum depends on
+// nsv alone -- not on n, the ray's place in the batch, the block size or the grid.
+constexpr int YS_BLOCK = 512;
+constexpr int YS_CAP_DOWN = 240, YS_CAP_UP = 90, YS_CAP_BISECT = 80;   // 0.98^228 = 0.01, 1.02^82 = 5, 2 % of x in ulps: 2^47
+template <int NF>
+__global__ void __launch_bounds__(YS_BLOCK)
+k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int mat, int n, const double *__restrict__ su_in,
+              const double *__restrict__ epl_in, const double *__restrict__ x0_in, double *__restrict__ x_out,
+              int32_t *__restrict__ status)
+{
+    static_assert(NF == 6 || NF == 15 || NF == 2, "6 stress features, 15 with the work-hardening ones, or the 2 of sdim = 3");
+    constexpr int NU = (NF == 2) ? 1 : 6;     // features that move with x
+    constexpr int NW = (NF == 15) ? 6 : 0;    // plastic-strain features
+    __shared__ MatDev smat[MAXMAT];
+    stage_materials(smat, gmat, nmat);
+    __syncthreads();
+    int svc_mat;
+    const double *sv, *dual;
+    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
+    __syncthreads();
+    const MatDev &m = smat[mat];
+    const double *psv = (mat == svc_mat) ? sv : m.sv;
+    const double *pdu = (mat == svc_mat) ? dual : m.dual;
+    const int nsv = m.nsv;
+    const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;
+    const double g = -m.gamma * LOG2E;
+    for (int i = blockIdx.x * rpb + (threadIdx.x >> 4); i < n; i += gridDim.x * rpb) {  // row-uniform
+        double s[6], e[6], u[NU], w[NW > 0 ? NW : 1], th = 0.;
+        bool fin = true, zero = true;
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            s[c] = su_in[6 * (size_t)i + c];
+            e[c] = epl_in ? epl_in[6 * (size_t)i + c] : 0.;
+            fin = fin && isfinite(s[c]) && isfinite(e[c]);
+            zero = zero && s[c] == 0.;
+        }
+        double x0 = x0_in ? x0_in[i] : 0., sj2;
+        if constexpr (NF == 2) {
+            // principal stresses in the closed form of plane states (sig_princ_dev's first branch): plfx_yield_scale has reduced
+            // the rays with out-of-plane shear on the host, so the LAPACK replay (a call, scratch) stays out of this kernel
+            double sp[3], xf[2];
+            fin = fin && s[3] == 0. && s[4] == 0.;
+            const double mean = 0.5 * (s[0] + s[1]), hd = 0.5 * (s[0] - s[1]);
+            const double R = sqrt(hd * hd + s[5] * s[5]);
+            sp[0] = (s[5] == 0.) ? s[0] : (s[0] >= s[1]) ? mean + R : mean - R;
+            sp[1] = (s[5] == 0.) ? s[1] : (s[0] >= s[1]) ? mean - R : mean + R;
+            sp[2] = s[2];
+            svc3_features(m, sp, xf);
+            const double d12 = sp[0] - sp[1], d23 = sp[1] - sp[2], d31 = sp[2] - sp[0];
+            sj2 = sqrt(0.5 * (d12 * d12 + d23 * d23 + d31 * d31));
+            u[0] = sj2 / m.scale_seq;
+            th = xf[1];
+        } else {
+            double xf[6];
+            svc_features(m, s, xf);
+#pragma unroll
+            for (int c = 0; c < NU; c++) u[c] = xf[c];
+            const double d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
+            sj2 = sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3. * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]));
+        }
+#pragma unroll
+        for (int c = 0; c < NW; c++) w[c] = e[c] / m.scale_wh;
+        if (!x0_in) x0 = sflow_of(m, e) / sj2;   // (sj2 = 0: inf, refused below)
+        int st = 0;
+        double root = __builtin_nan("");
+        if (!fin || zero || !isfinite(x0) || !(x0 > 0.)) st = 3;
+        if (st == 0) {
+            int phase = 0, cnt = 0;   // 0 first point, 1 marching down, 2 marching up, 3 bracket found, 4 bisection
+            double x = x0, lo = 0., hi = 0., flo = 0., fhi = 0.;
+            for (;;) {
+                // ---- f(x): the decision function at x su (the only evaluation site)
+                double acc[2] = {0., 0.};
+                for (int k = l16; k < nsv; k += 32) {
+                    const bool two = (k + 16 < nsv);   // the second vector of the trip exists (else: the first again, with weight 0)
+                    const int kk[2] = {k, two ? k + 16 : k};
+                    double ea[2], eo[2];
+#pragma unroll
+                    for (int c = 0; c < 2; c++) {
+                        const double *v = psv + (size_t)NF * kk[c];
+                        double hh = 0.;
+                        if constexpr (NF == 2) {
+                            const double h0 = fma(x, u[0], -1.) - v[0], h1 = th - v[1];
+                            hh = fma(h0, h0, h1 * h1);
+                        } else {
+#pragma unroll
+                            for (int f = 0; f < 6; f++) {
+                                const double d = fma(x, u[f], -v[f]);
+                                hh = fma(d, d, hh);
+                            }
+#pragma unroll
+                            for (int f = 0; f < NW; f++) {
+                                const double d = w[f] - v[6 + f];
+                                hh = fma(d, d, hh);
+                            }
+#pragma unroll
+                            for (int f = 6 + NW; f < NF; f++) hh = fma(v[f], v[f], hh);
+                        }
+                        ea[c] = g * hh;
+                    }
+                    exp2_neg_n<2>(ea, eo);
+                    acc[0] = fma((ea[0] < -1020.) ? 0. : pdu[kk[0]], eo[0], acc[0]);
+                    acc[1] = fma((ea[1] < -1020. || !two) ? 0. : pdu[kk[1]], eo[1], acc[1]);
+                }
+                const double f = YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + m.intercept;   // the same bits in the 16 lanes
+                // ---- the search
+                if (!(f == f)) {
+                    st = 1;
+                    break;
+                }
+                if (phase == 0) phase = (f >= 0.) ? 1 : 2;
+                if (phase == 1) {
+                    if (f < 0.) {
+                        lo = x, flo = f, phase = 3;
+                    } else {
+                        hi = x, fhi = f;
+                        if (x < 0.01 * x0 || ++cnt > YS_CAP_DOWN) {
+                            st = 1;
+                            break;
+                        }
+                        x *= 0.98;
+                        continue;
+                    }
+                } else if (phase == 2) {
+                    if (f >= 0.) {
+                        hi = x, fhi = f, phase = 3;
+                    } else {
+                        lo = x, flo = f;
+                        if (x > 5. * x0 || ++cnt > YS_CAP_UP) {
+                            st = 1;
+                            break;
+                        }
+                        x *= 1.02;
+                        continue;
+                    }
+                } else if (f < 0.) {
+                    lo = x, flo = f;
+                } else {
+                    hi = x, fhi = f;
+                }
+                if (phase == 3) phase = 4, cnt = 0;
+                const double mid = lo + 0.5 * (hi - lo);
+                if (!(mid > lo && mid < hi)) {   // lo and hi are neighbours
+                    root = (-flo < fhi) ? lo : hi;
+                    break;
+                }
+                if (++cnt > YS_CAP_BISECT) {
+                    st = 2;
+                    break;
+                }
+                x = mid;
+            }
+        }
+        if (l16 == 0) {
+            x_out[i] = root;
+            status[i] = st;
+        }
+    }
+}
+
+// the analytic kinds (Hill / J2 / Drucker on Voigt or principal stresses, Tresca, Barlat) are homogeneous of degree one:
+// x = sflow(epl) / seq(su), status 0 where seq(su) > 0 and the inputs are finite (a given x0: finite and > 0), else 3 and NaN
+template <int KD>   // 1 Hill / J2 / Drucker on Voigt stresses, 2 on principal stresses, 4 Tresca, 5 Barlat: one form per instantiation
+__global__ void __launch_bounds__(BLOCK)
+k_yield_scale_analytic(const MatDev *__restrict__ gmat, int mat, int n, const double *__restrict__ su_in,
+                       const double *__restrict__ epl_in, const double *__restrict__ x0_in, double *__restrict__ x_out,
+                       int32_t *__restrict__ status)
+{
+    const MatDev &m = gmat[mat];
+    constexpr int kd = KD;
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        double s[6], e[6];
+        bool fin = true;
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            s[c] = su_in[6 * (size_t)i + c];
+            e[c] = epl_in ? epl_in[6 * (size_t)i + c] : 0.;
+            fin = fin && isfinite(s[c]) && isfinite(e[c]);
+        }
+        double x = __builtin_nan("");
+        int st = 3;
+        if (x0_in) fin = fin && isfinite(x0_in[i]) && x0_in[i] > 0.;   // the value is not used, but a bad one is a degenerate ray
+        if (kd == 2) fin = fin && s[3] == 0. && s[4] == 0.;            // plfx_yield_scale has reduced the other states
+        if (fin) {
+            double seq;
+            if constexpr (kd == 2) {   // principal stresses in the closed form of plane states (sig_princ_dev's first branch): no LAPACK call
+                double sp[3];
+                const double mean = 0.5 * (s[0] + s[1]), hd = 0.5 * (s[0] - s[1]);
+                const double R = sqrt(hd * hd + s[5] * s[5]);
+                sp[0] = (s[5] == 0.) ? s[0] : (s[0] >= s[1]) ? mean + R : mean - R;
+                sp[1] = (s[5] == 0.) ? s[1] : (s[0] >= s[1]) ? mean - R : mean + R;
+                sp[2] = s[2];
+                seq = princ_seq_sp(m, sp, s[0] + s[1] + s[2]);
+            } else {
+                seq = kd == 4 ? tresca_seq(s) : kd == 5 ? barlat_seq(m, s) : hill_seq(m, s);
+            }
+            const double r = sflow_of(m, e) / seq;
+            if (seq > 0. && isfinite(r)) x = r, st = 0;
+        }
+        x_out[i] = x;
+        status[i] = st;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // element strain from nodal values: (sum_gp B) u_e   (model.py:387-411)
 __device__ __forceinline__ void class_strain(const ClassDev &c, const double2 *u2, int n0, int n1,

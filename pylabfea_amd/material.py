@@ -7,7 +7,9 @@ the path named by BASELINE.json: ``elasticity`` (:2401), ``plasticity`` (:2466),
 (:974), ``epl_dot`` (:1009), ``C_tan`` (:1057) and the test harness ``calc_properties`` (:3062).
 Same names, argument meaning and error behaviour; arguments are never mutated.
 
-Out of scope here: data import, plotting, texture/work-hardening features.  A trained SVC enters through
+Out of scope here: data import, plotting, texture/work-hardening features.  What the yield-locus plots
+compute comes back as arrays (``yield_scale``, ``polar_yield_locus``, ``polar_field``, ``yield_slices``).
+A trained SVC enters through
 :meth:`Material.train_SVC` (trained on the GPU), :meth:`Material.set_svc` or :meth:`Material.from_sklearn`.
 sdim=3 flow rules use the reference's axis-tracking principal stresses (exact for plane states);
 Tresca and Barlat Yld2004-18p are equivalent stresses only (the reference has no normal for them).
@@ -951,6 +953,193 @@ class Material(object):
             f = self.find_yloc(mid, su)
             lo, hi = np.where(f > 0., lo, mid), np.where(f > 0., mid, hi)
         return 0.5 * (lo + hi)
+
+    # ------------------------------------------------------------------ yield loci as arrays
+    def _epl_rows(self, epl, n, name):
+        """epl as calc_yf takes it -- None, a PEEQ scalar, (6,) or (N,6) -- as (N,6) rows or None"""
+        if epl is None:
+            return None
+        if np.ndim(epl) == 0:   # PEEQ -> an arbitrary plastic strain tensor of that equivalent strain (material.py:381-383)
+            return np.tile(float(epl) * np.array([1., -0.5, -0.5, 0., 0., 0.]), (n, 1))
+        e = np.asarray(epl, dtype=float)
+        if e.shape == (6,):
+            e = np.tile(e, (n, 1))
+        if e.shape != (n, 6):
+            raise ValueError('%s: epl must be None, a PEEQ value, (6,) or (N,6) with one row per stress; got shape %s'
+                             % (name, e.shape))
+        return e
+
+    def yield_scale(self, su, epl=None, x0=None, return_status=False):
+        """Factor ``x`` with ``calc_yf(x * su, epl) = 0`` along unit stresses ``su`` -- (sdim,), (N,3) or (N,6) -- i.e. where
+        the yield locus lies along these directions: the root search behind the reference's ``polar_plot_yl``
+        (material.py:3290-3293, one ``fsolve`` over all N unknowns there), done on the device ray by ray in one launch.
+        ``epl`` as ``calc_yf`` takes it (None, PEEQ, (6,), (N,6)); ``x0`` start values (scalar or (N,)), default
+        ``get_sflow(epl) / seq_J2(su)``.
+
+        Rays of an ML yield function have more than one root; returned is the one the marching bracket of ``ML_full_yf``
+        (material.py:468-486) isolates: from ``x0`` down in steps of 2 % while the yield function is >= 0 (to 0.01 x0), else
+        up in steps of 2 % while it is < 0 (to 5 x0), refined until the bracket is two neighbouring doubles.  Analytic
+        yield functions (Hill / J2 / Drucker, Tresca, Barlat) are homogeneous: ``get_sflow(epl) / calc_seq(su)``, whatever the
+        value of ``x0`` (a given ``x0 <= 0`` still makes the ray degenerate).
+        A single stress returns a float.  Rays without a root come back as NaN (one warning names their count);
+        ``return_status`` adds the status per ray: 0 root, 1 no bracket, 2 refinement cap reached, 3 degenerate ray (zero or
+        hydrostatic direction without ``x0``, non-finite input, ``x0 <= 0``)."""
+        if self.sy is None:
+            raise ValueError('yield_scale: the material has no yield strength')
+        s, single = self._voigt(su, 'yield_scale')
+        e = self._epl_rows(epl, len(s), 'yield_scale')
+        if x0 is not None:
+            x0 = np.asarray(x0, dtype=float)
+            if x0.ndim == 0:
+                x0 = np.full(len(s), float(x0))
+            if x0.shape != (len(s),):
+                raise ValueError('yield_scale: x0 must be a scalar or hold one start value per stress; got shape %s'
+                                 % (x0.shape,))
+        ml = self.ML_yf
+        # (_princ_rows: principal-stress materials see general states through the host's LAPACK call; plfx_yield_scale does the
+        # same for callers of the C-ABI, csrc/plfx.hip, and finds nothing left to reduce in these rows)
+        x, st = self._load(ana=not ml).yield_scale(0, self._princ_rows(s), e, x0)
+        bad = int(np.sum(st != 0))
+        if bad:
+            warnings.warn('yield_scale: no point of the yield locus found along %d of %d direction(s); NaN returned there'
+                          % (bad, len(s)))
+        if single:
+            return (float(x[0]), int(st[0])) if return_status else float(x[0])
+        return (x, st) if return_status else x
+
+    def yield_stress(self, su, epl=None):
+        """Stresses on the yield locus along the unit stresses ``su``: ``su * yield_scale(su, epl)[:, None]`` (NaN rows where
+        no point of the locus was found)."""
+        s = np.asarray(su, dtype=float)
+        x = self.yield_scale(s, epl=epl)
+        return s * x if s.ndim == 1 else s * x[:, None]
+
+    def polar_yield_locus(self, Na=72, cmat=None, scaling=None, sJ2=False):
+        """The curves that the reference's ``polar_plot_yl`` draws (material.py:3290-3309), as arrays: ``(theta, s_yld)``
+        with ``theta = linspace(0, 2 pi, Na)`` and ``s_yld`` of shape (1 + len(cmat), Na) -- the equivalent stress of this
+        material's yield locus along ``snorm = sig_cyl2princ([sy sqrt(1.5), theta])``, searched from ``x0 = 1``, then one row
+        per material of ``cmat`` along the same directions.  Like the reference (:3308), the curves of ``cmat`` are put through
+        THIS material's ``calc_seq`` (``sig_eq_j2`` with ``sJ2``), not their own.  ``scaling`` divides the stresses."""
+        if self.sy is None:
+            raise ValueError('polar_yield_locus: the material has no yield strength')
+        sf = 1. if scaling is None else 1. / scaling
+        theta = np.linspace(0., 2. * np.pi, Na)
+        snorm = sig_cyl2princ(np.array([self.sy * np.ones(Na) * np.sqrt(1.5), theta]).T)
+        rows = []
+        for mat in [self] + list(cmat or []):
+            sig = snorm * mat.yield_scale(snorm, x0=np.ones(Na))[:, None]
+            ok = np.all(np.isfinite(sig), axis=1)
+            seq = np.full(Na, np.nan)
+            if np.any(ok):
+                seq[ok] = sig_eq_j2(sig[ok]) if sJ2 else self.calc_seq(sig[ok])
+            rows.append(seq * sf)
+        return theta, np.array(rows)
+
+    @staticmethod
+    def _symmetrise(Z):
+        """colour range of the reference's field plots (material.py:2817-2823, 3276-3282): the longer tail is cut"""
+        Z = np.array(Z, dtype=float)
+        zmin, zmax = np.amin(Z), np.amax(Z)
+        if -zmin < zmax:
+            Z[Z > -zmin] = -zmin
+        else:
+            Z[Z < -zmax] = -zmax
+        return Z
+
+    def polar_field(self, Np=100, predict=False):
+        """The field that ``polar_plot_yl(field=True)`` draws under the yield locus (material.py:3261-3285), as arrays:
+        ``(theta_grid, r_grid, Z)``, each (Np, Np) -- the decision function (``predict``: its sign as -1 / +1) of a 2-feature
+        (sdim = 3) ML yield function on the feature grid [-1, 1] x [-1, 1], symmetrised like the reference's colour range, at
+        the polar angles ``theta_grid`` and the equivalent stresses ``r_grid = (feature + 1) * scale_seq``."""
+        if not self.ML_yf:
+            raise AttributeError('polar_field: material has no trained ML yield function')
+        if self.Ndof != 2:
+            raise ValueError('"polar_plot_yl" currently does not support texture as degree of freedom for field plots.')
+        xx, yy = np.meshgrid(np.linspace(-1., 1., Np), np.linspace(-1, 1., Np))
+        feat = np.c_[yy.ravel(), xx.ravel()]
+        sv = self.svc['sv']
+        nsv = len(sv)
+        ctx = _ctx()
+        Z = ctx.svc_decision_batch(np.vstack((sv, feat)), [np.arange(nsv)], [self.svc['dual']], [self.svc['intercept']],
+                                   [self.gam_yf], [nsv + np.arange(len(feat))])[0]
+        if predict:
+            Z = np.where(Z > 0., 1., -1.)
+        return xx * np.pi, (yy + 1.) * self.scale_seq, self._symmetrise(Z).reshape(xx.shape)
+
+    @staticmethod
+    def ellipsis(a=1., b=1. / np.sqrt(3.), n=72):
+        """Points (x, y) of an ellipse with its long half-axis ``a`` along the 45 degree line and short half-axis ``b``: the
+        plane-stress yield locus of an isotropic J2 material in units of its yield strength (material.py:2772-2792)."""
+        t = np.arange(0., 2.1 * np.pi, np.pi / n)
+        return a * np.cos(t) - b * np.sin(t), a * np.cos(t) + b * np.sin(t)
+
+    @staticmethod
+    def _slice_stress(c1, c2, xa, ya):
+        """principal stresses (N,3) of the points (xa, ya) of a slice with axis codes c1, c2 (material.py:2915-3008):
+        0, 1, 2: sigma_1, sigma_2, sigma_3; 3: p = sigma_1 = sigma_2 on the first axis, sigma_3 on the second"""
+        s = [None, None, None]
+        if c1 == 3:
+            s[0] = s[1] = xa
+        elif c1 in (0, 1, 2):
+            s[c1] = xa
+        else:
+            warnings.warn('yield_slices: axis1 not defined properly, set to sig_1: {}'.format(c1))
+            s[0] = xa
+        if c2 in (0, 1):
+            s[c2] = ya
+        elif c2 in (2, 3):
+            s[2] = ya
+        else:
+            warnings.warn('yield_slices: axis2 not defined properly, set to sig_2: {}'.format(c2))
+            s[1] = ya
+        z = np.zeros(len(xa))
+        return np.c_[tuple(z if v is None else v for v in s)]
+
+    def yield_slices(self, axis1=[0], axis2=[1], peeq=0., xstart=None, xend=None, Nmesh=100, scaling=True, ref_mat=None,
+                     iso=False, Na=180):
+        """What the reference's ``plot_yield_locus`` draws (material.py:2835-3060), as arrays: one dict per slice
+        ``(axis1[j], axis2[j])`` through the principal stress space (codes 0, 1, 2: sigma_1, sigma_2, sigma_3; 3:
+        p = sigma_1 = sigma_2 against sigma_3) with
+
+        * ``xx``, ``yy`` (Nmesh, Nmesh): the mesh, in units of ``sy`` with ``scaling``;
+        * ``Z``: ``calc_yf(sig, epl=peeq, pred=True)`` on the mesh (``/ sy`` with ``scaling``) after the symmetrisation of
+          ``plot_data`` (:2817-2824) -- what the reference contours at level 0;
+        * ``Z_ref``: the same of ``ref_mat``, when given (not for slices with code 3, which the reference cannot draw with a
+          reference material);
+        * ``ellipsis``: ``(x, y)`` of the isotropic J2 locus with ``iso``;
+        * ``locus`` (Na, 2): the zero contour itself, traced by ``yield_scale`` along ``Na`` in-plane rays from the origin at
+          the angles ``linspace(0, 2 pi, Na)``; NaN rows where a ray meets no yield locus (hydrostatic rays of code 3).
+
+        The caller's ``axis1`` / ``axis2`` lists are not modified (the reference rewrites code 3 in place)."""
+        if self.sy is None:
+            raise ValueError('yield_slices: the material has no yield strength')
+        if len(axis1) != len(axis2):
+            raise ValueError('Error in plot_yield_locus: mismatch in dimensions of ax1 and ax2')
+        if xstart is None:
+            xstart = -2. if scaling else -2. * self.sy
+        if xend is None:
+            xend = 2. if scaling else 2. * self.sy
+        xx, yy = np.meshgrid(np.linspace(xstart, xend, Nmesh), np.linspace(xstart, xend, Nmesh))
+        unit = self.sy if scaling else 1.    # stress per plot unit
+        sf = 1. / unit
+        phi = np.linspace(0., 2. * np.pi, Na)
+        out = []
+        for c1, c2 in zip(axis1, axis2):
+            sig = self._slice_stress(c1, c2, xx.ravel(), yy.ravel()) * unit
+            d = dict(axis1=c1, axis2=c2, xx=xx, yy=yy)
+            d['Z'] = self._symmetrise(self.calc_yf(sig, epl=float(peeq), pred=True) * sf).reshape(xx.shape)
+            if ref_mat is not None and c1 != 3:
+                d['Z_ref'] = self._symmetrise(ref_mat.calc_yf(sig, epl=float(peeq), pred=True) * sf).reshape(xx.shape)
+            if iso:
+                x0, y0 = self.ellipsis()
+                d['ellipsis'] = (x0, y0) if scaling else (x0 * self.sy, y0 * self.sy)
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')     # axis codes were reported above; rays without a locus are NaN rows
+                su = self._slice_stress(c1, c2, np.cos(phi), np.sin(phi)) * self.sy
+                x = self.yield_scale(su, epl=float(peeq))
+            d['locus'] = np.c_[np.cos(phi), np.sin(phi)] * (x * self.sy * sf)[:, None]
+            out.append(d)
+        return out
 
     # fields of Data.mat_data that the msparam branch of train_SVC reads
     _MSPARAM_KEYS = ('Nlc', 'sdim', 'wh_data', 'sy_av', 'peeq_max')
