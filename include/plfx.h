@@ -167,6 +167,25 @@ int plfx_hessian_batch(plfx_ctx *ctx, int mat, int n, const double *sig, const d
 int plfx_yield_scale(plfx_ctx *ctx, int mat, int n, const double *su, const double *epl, const double *x0, double *x,
                      int32_t *status);
 
+/* A committee of SVC yield functions on n shared unit stresses su[n*6] (query by committee): member k is
+ * material mats[k] of the context, 1 <= nmem <= 16, duplicates allowed, each a 6-feature SVC on Voigt stresses (PLFX_SVC6,
+ * dev_only or not), with its own stress scale scale[k] (finite, > 0).  One launch of k_committee_yf, whatever nmem is:
+ *   yf[nmem*n]  member-major: y[k, i] = calc_yf(su_i * scale[k]) of member k -- create_scaled_input and decision_function
+ *               of the reference (material.py:398-405, 2336-2339), roundings in its order: su * scale, (deviator), / scale_seq
+ *   mean[n]     (sum_k y[k, i]) / nmem, summed in member order
+ *   var[n]      (sum_k (y[k, i] - mean_i)^2) / nmem, summed in member order (np.var, ddof = 0, as a fixed two-pass formula)
+ *   best        index of the largest variance, best_var its value: NaN variances are skipped, equal variances resolve to the
+ *               smaller index; -1 and NaN when no point has a variance that is not NaN
+ * yf, mean, var, best and best_var may each be NULL.  A non-finite component of su_i makes y[:, i], mean_i and var_i NaN and
+ * nothing else.  A member's row of yf does not depend on n, the place of the point, or the other members.
+ * PLFX_ERR_UNSUPPORTED for a member of any other kind (the message names it); PLFX_ERR_ARG for nmem out of range, a material
+ * index out of range, a scale that is not finite or <= 0; n = 0 is PLFX_OK with nothing launched. */
+int plfx_committee_yf(plfx_ctx *ctx, int nmem, const int32_t *mats, const double *scale, int n, const double *su, double *yf,
+                      double *mean, double *var, int32_t *best, double *best_var);
+/* launches: k_committee_yf launches of this context so far (one per plfx_committee_yf call with n > 0); staged_members: bit k
+ * set when member k of the last such call had its tables staged in LDS (clear: read from device memory) */
+int plfx_committee_info(plfx_ctx *ctx, int64_t *launches, int32_t *staged_members);
+
 /* Index products of Model.mesh for the reference's structured NX x NY grid, computed on the host (no context, no GPU):
  * conn[NX*NY*4] = [n1, n1+1, n1+NnodeY, n1+NnodeY+1] with n1 = (ih / NY) * NnodeY + ih % NY for element ih = j*NY + k
  * (model.py:935-948); node sets noleft (j = 0), noright (j = NX), nobot (k = 0), notop (k = NY) in ascending node order
@@ -516,7 +535,7 @@ int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
- *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_committee_yf, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

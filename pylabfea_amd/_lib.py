@@ -62,6 +62,7 @@ SYMBOLS = [
     'plfx_svc_fit_batch', 'plfx_svc_decision_batch', 'plfx_svc_fit_wide', 'plfx_hessian_batch',
     'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
     'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info', 'plfx_yield_scale',
+    'plfx_committee_yf', 'plfx_committee_info',
 ]
 
 _lib = None
@@ -309,6 +310,40 @@ class Context(object):
         st = np.zeros(len(su), dtype=np.int32)
         self._chk(self.lib.plfx_yield_scale(self.h, int(mat), len(su), _dp(su), _dp(epl), _dp(x0), _dp(x), _dp(st)))
         return x, st
+
+    def committee_yf(self, mats, scale, su, want_yf=True, want_mean=False, want_var=False, want_best=False):
+        """A committee of 6-feature SVC materials on N shared unit stresses su (N,6) in one launch (plfx_committee_yf):
+        member k is material mats[k] of this context with the stress scale scale[k].  Returns a dict with the requested
+        entries: 'yf' (M,N) = calc_yf(su * scale[k]) per member, 'mean' (N,), 'var' (N,) (np.var over the members, ddof = 0),
+        'best' = (index of the largest variance or -1, its value or NaN)."""
+        mats = _i32(mats).reshape(-1)
+        scale = _f64(scale).reshape(-1)
+        if len(scale) != len(mats):
+            raise ValueError('committee_yf: one scale per member expected')
+        su = _f64(su).reshape(-1, 6)
+        n, M = len(su), len(mats)
+        yf = np.empty((M, n)) if want_yf else None
+        mean = np.empty(n) if want_mean else None
+        var = np.empty(n) if want_var else None
+        best, bvar = C.c_int32(-1), C.c_double(float('nan'))
+        self._chk(self.lib.plfx_committee_yf(self.h, M, _dp(mats), _dp(scale), n, _dp(su), _dp(yf), _dp(mean), _dp(var),
+                                             C.byref(best) if want_best else None, C.byref(bvar) if want_best else None))
+        out = {}
+        if want_yf:
+            out['yf'] = yf
+        if want_mean:
+            out['mean'] = mean
+        if want_var:
+            out['var'] = var
+        if want_best:
+            out['best'] = (int(best.value), float(bvar.value))
+        return out
+
+    def committee_info(self):
+        """(launches of k_committee_yf so far, bit mask of the last call's members whose tables were staged in LDS)"""
+        n, st = C.c_int64(), C.c_int32()
+        self._chk(self.lib.plfx_committee_info(self.h, C.byref(n), C.byref(st)))
+        return int(n.value), int(st.value)
 
     def yf(self, mat, sig, epl=None):
         sig = _f64(sig).reshape(-1, 6)

@@ -124,6 +124,29 @@ def sig_cyl2princ(s_cyl):
     return sp[0] if single else sp
 
 
+def sig_spherical_to_cartesian(angles, seq=1.0):
+    """Voigt stress (6,) of norm ``seq`` from 5 spherical angles in radians (basic.py:280-301): x1 = cos a0,
+    x2 = sin a0 cos a1, ..., x6 = sin a0 sin a1 sin a2 sin a3 sin a4, the products taken from the left as there.
+    (N,5) angles give (N,6); ``seq`` is then a scalar or (N,)."""
+    a = np.asarray(angles, dtype=float)
+    single = a.ndim == 1
+    if single:
+        a = a[None, :]
+    if a.ndim != 2 or a.shape[1] != 5:
+        raise ValueError('sig_spherical_to_cartesian: 5 angles, (5,) or (N,5), expected')
+    s, c = np.sin(a), np.cos(a)
+    x = np.empty((len(a), 6))
+    p = np.ones(len(a))
+    x[:, 0] = c[:, 0]
+    for k in range(1, 5):
+        p = s[:, k - 1] if k == 1 else p * s[:, k - 1]
+        x[:, k] = p * c[:, k]
+    x[:, 5] = p * s[:, 4]
+    sq = np.asarray(seq, dtype=float)
+    x = sq * x if sq.ndim == 0 else sq.reshape(-1, 1) * x
+    return x[0] if single else x
+
+
 class Stress(object):
     """A Voigt stress with its tensor, principal values (axis-tracking order), hydrostatic and deviatoric parts
     (basic.py:366-484); ``seq(mat)`` is the material's equivalent stress (evaluated on the GPU through

@@ -145,6 +145,8 @@ struct plfx_ctx {
     unsigned svr_mask = 0;       // bit k: material k has a rule attached (its points run on k_response_svr)
     int64_t svr_launches[MAXMAT] = {0};   // response launches of k_response_svr per material since the rule was attached
     int n_noflow = 0;            // materials without a flow rule (Tresca, Barlat without the native normal)
+    int64_t committee_launches = 0;   // k_committee_yf launches of this context (plfx_committee_info)
+    int32_t committee_staged = 0;     // bit k: member k of the last plfx_committee_yf call had its tables staged in LDS
     int svc_lds_need = 0;
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
@@ -2046,6 +2048,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<6>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<2>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<15>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_committee_yf, bytes));
     }
     c->M_dirty = true;
     c->memo.valid = false;
@@ -2393,6 +2396,89 @@ int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double
     HIPCHK(c, hipMemcpyAsync(x, dx, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+// A committee of SVC yield functions on n shared unit stresses: all members in ONE launch of k_committee_yf, mean and
+// variance over the members per point, and the point of largest variance (the blocks' partials are closed here, in block
+// order: a strictly larger variance replaces, so equal variances resolve to the smaller index).
+int plfx_committee_yf(plfx_ctx *c, int nmem, const int32_t *mats, const double *scale, int n, const double *su, double *yf,
+                      double *mean, double *var, int32_t *best, double *best_var)
+{
+    static const char *const kind_names[] = {"elastic", "Hill / J2 on Voigt stresses", "Hill / J2 on principal stresses",
+                                             "6-feature SVC", "Tresca", "Barlat", "2-feature SVC on principal stresses",
+                                             "SVC with work-hardening features"};
+    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
+    if (nmem < 1 || nmem > MAXMAT) return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: nmem = %d, must be in 1..%d", nmem, MAXMAT);
+    if (!mats || !scale || n < 0 || n > INT32_MAX - CY_BLOCK || (n > 0 && !su)) return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: bad argument");
+    CommitteeArgs a = {};
+    int32_t staged = 0;
+    for (int k = 0; k < nmem; k++) {
+        if (mats[k] < 0 || mats[k] >= c->nmat)
+            return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: member %d is material %d, the context holds %d", k, mats[k], c->nmat);
+        const MatDev &m = c->hmat[mats[k]];
+        if (m.kind != PLFX_SVC6)
+            return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_committee_yf: member %d (material %d) is of kind %d (%s); only 6-feature SVC "
+                        "materials on Voigt stresses form a committee", k, mats[k], m.kind, kind_names[m.kind]);
+        if (!std::isfinite(scale[k]) || !(scale[k] > 0.))
+            return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: scale of member %d must be finite and positive", k);
+        a.mat[k] = mats[k];
+        a.scale[k] = scale[k];
+        if (m.nsv * (m.nfeat + 1) <= c->svc_lds_need) staged |= 1 << k;   // the test of stage_svc
+    }
+    if (n == 0) return PLFX_OK;
+    // a block stages each member's tables once: the fewest points per block (one per 16 lanes) that still leave no more than a few
+    // blocks per CU, so that a short batch spreads over the device.  The result does not depend on the choice.
+    int block = 64;
+    while (block < CY_BLOCK && (n + block / 16 - 1) / (block / 16) > 2 * c->prop.multiProcessorCount) block *= 2;
+    const int rpb = block / 16, nblk = (n + rpb - 1) / rpb;
+    const bool query = best || best_var;
+    SvmBuffers B;   // device buffers of this call, released on every exit path: [su | yf | mean | var | partial variances], partial indices
+    double *dbuf = nullptr;
+    int32_t *dpi = nullptr;
+    const size_t nn = (size_t)n, o_yf = 6 * nn, o_mean = o_yf + (yf ? (size_t)nmem * nn : 0), o_var = o_mean + (mean ? nn : 0),
+                 o_pv = o_var + (var ? nn : 0);
+    if (int rc = B.get(c, &dbuf, o_pv + (query ? (size_t)nblk : 0))) return rc;
+    if (query)
+        if (int rc = B.get(c, &dpi, (size_t)nblk)) return rc;
+    HIPCHK(c, hipMemcpyAsync(dbuf, su, nn * 48, hipMemcpyHostToDevice, c->stream));
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    hipLaunchKernelGGL(k_committee_yf, dim3(nblk), dim3(block), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat, c->svc_lds_need, nmem,
+                       a, n, (const double *)dbuf, yf ? dbuf + o_yf : nullptr, mean ? dbuf + o_mean : nullptr,
+                       var ? dbuf + o_var : nullptr, query ? dbuf + o_pv : nullptr, dpi);
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->committee_launches++;
+    c->committee_staged = staged;
+    if (yf) HIPCHK(c, hipMemcpyAsync(yf, dbuf + o_yf, (size_t)nmem * nn * 8, hipMemcpyDeviceToHost, c->stream));
+    if (mean) HIPCHK(c, hipMemcpyAsync(mean, dbuf + o_mean, nn * 8, hipMemcpyDeviceToHost, c->stream));
+    if (var) HIPCHK(c, hipMemcpyAsync(var, dbuf + o_var, nn * 8, hipMemcpyDeviceToHost, c->stream));
+    std::vector<double> pv;
+    std::vector<int32_t> pi;
+    if (query) {
+        pv.resize(nblk);
+        pi.resize(nblk);
+        HIPCHK(c, hipMemcpyAsync(pv.data(), dbuf + o_pv, (size_t)nblk * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(pi.data(), dpi, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, stream_sync(c));
+    if (query) {
+        double bv = std::nan("");
+        int32_t bi = -1;
+        for (int b = 0; b < nblk; b++)
+            if (pi[b] >= 0 && (bi < 0 || pv[b] > bv)) bv = pv[b], bi = pi[b];
+        if (best) *best = bi;
+        if (best_var) *best_var = bv;
+    }
+    return PLFX_OK;
+}
+
+int plfx_committee_info(plfx_ctx *c, int64_t *launches, int32_t *staged_members)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (launches) *launches = c->committee_launches;
+    if (staged_members) *staged_members = c->committee_staged;
     return PLFX_OK;
 }
 

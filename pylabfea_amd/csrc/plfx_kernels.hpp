@@ -698,6 +698,137 @@ k_yield_scale_analytic(const MatDev *__restrict__ gmat, int mat, int n, const do
     }
 }
 
+// A committee of SVC yield functions on n shared unit stresses: y[m, i] = calc_yf(su_i * scale_m) of
+// member m -- material a.mat[m] of the context, a 6-feature SVC on Voigt stresses -- then per point the mean and the variance
+// (np.var, ddof = 0) over the members, and per block the point of largest variance.  The features are the reference's
+// create_scaled_input (material.py:2336-2339) with its roundings in its order: su * scale_m first, the deviator where the
+// member is dev_only, then the division by scale_seq_m.
+// Lane mapping of k_hessian_row / k_yield_scale: 16 lanes (one DPP row) per point, ONE point per row and block pass, lane L
+// takes the vectors L, L + 16, ... of the current member two per trip, closed by the DPP butterfly, so the 16 lanes of a row
+// hold the same bits.  The members are looped inside the row (su is read once per point), their tables staged in LDS one
+// member at a time where they fit (stage_svc; two block barriers per member), read from device memory otherwise.  The order
+// of a point's sum for member m depends on that member's nsv alone -- not on n, the point's place, the block size, the
+// grid or the other members.  Lane m of the row keeps y_m (nmem <= MAXMAT = 16 = lanes of a row), so no register array is
+// indexed by the member; after the last member the 16 values are broadcast through the row (row_newbcast) and
+//     mean = (sum_m y_m) / M,   var = (sum_m (y_m - mean)^2) / M,   both summed in member order, no contraction.
+// A non-finite component of su_i makes y[:, i], mean_i and var_i NaN and nothing else.
+// Query: part_var / part_idx[block] = largest variance among the block's points and its index (NaN variances skipped; the
+// rows are scanned in index order and only a strictly larger variance replaces, so ties go to the smaller index); NaN / -1
+// when the block has none.  The host closes the reduction over the blocks in block order (plfx_committee_yf).
+constexpr int CY_BLOCK = 512;
+struct CommitteeArgs {
+    double scale[MAXMAT];
+    int32_t mat[MAXMAT];
+};
+template <int N>
+__device__ __forceinline__ void row_gather16(double y, double (&v)[16])   // v[L] = y of lane L of the row, in every lane
+{
+    v[N] = YfSvcRow<1>::row_bcast<N>(y);
+    if constexpr (N < 15) row_gather16<N + 1>(y, v);
+}
+__global__ void __launch_bounds__(CY_BLOCK)
+k_committee_yf(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int nmem, const CommitteeArgs a, int n,
+               const double *__restrict__ su_in, double *__restrict__ yf, double *__restrict__ mean_out,
+               double *__restrict__ var_out, double *__restrict__ part_var, int32_t *__restrict__ part_idx)
+{
+    __shared__ MatDev smat[MAXMAT];
+    __shared__ double red_var[CY_BLOCK / 16];
+    __shared__ int32_t red_idx[CY_BLOCK / 16];
+    stage_materials(smat, gmat, nmat);
+    const int l16 = threadIdx.x & 15, row = threadIdx.x >> 4, rpb = blockDim.x >> 4;
+    const int i = blockIdx.x * rpb + row;
+    const bool active = i < n;   // row-uniform
+    double s[6];
+    bool fin = true;
+#pragma unroll
+    for (int c = 0; c < 6; c++) {
+        s[c] = active ? su_in[6 * (size_t)i + c] : 0.;
+        fin = fin && isfinite(s[c]);
+    }
+    double y = 0.;   // lane m of the row: y of member m
+    for (int mm = 0; mm < nmem; mm++) {   // block-uniform
+        const int mat = a.mat[mm];
+        __syncthreads();   // first trip: smat is complete; later trips: the readers of the previous member's tables are done
+        int svc_mat;
+        const double *sv, *dual;
+        stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
+        __syncthreads();
+        if (!active) continue;
+        const MatDev &m = smat[mat];
+        const double *psv = (mat == svc_mat) ? sv : m.sv;
+        const double *pdu = (mat == svc_mat) ? dual : m.dual;
+        const int nsv = m.nsv;
+        const double g = -m.gamma * LOG2E, sc = a.scale[mm];
+        double sx[6], x[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) sx[c] = s[c] * sc;
+        svc_features(m, sx, x);
+        double acc[2] = {0., 0.};
+        for (int k = l16; k < nsv; k += 32) {
+            const bool two = (k + 16 < nsv);   // the second vector of the trip exists (else: the first again, with weight 0)
+            const int kk[2] = {k, two ? k + 16 : k};
+            double ea[2], eo[2];
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const double *v = psv + (size_t)6 * kk[c];
+                double hh = 0.;
+#pragma unroll
+                for (int f = 0; f < 6; f++) {
+                    const double d = x[f] - v[f];
+                    hh = fma(d, d, hh);
+                }
+                ea[c] = g * hh;
+            }
+            exp2_neg_n<2>(ea, eo);
+            acc[0] = fma((ea[0] < -1020.) ? 0. : pdu[kk[0]], eo[0], acc[0]);
+            acc[1] = fma((ea[1] < -1020. || !two) ? 0. : pdu[kk[1]], eo[1], acc[1]);
+        }
+        double f = YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + m.intercept;   // the same bits in the 16 lanes
+        if (!fin) f = __builtin_nan("");
+        if (l16 == mm) y = f;
+    }
+    double var = __builtin_nan("");
+    if (active) {
+#pragma clang fp contract(off)
+        double v[16];
+        row_gather16<0>(y, v);
+        const double M = (double)nmem;
+        double sum = 0., sq = 0.;
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if (k < nmem) sum += v[k];
+        const double mean = sum / M;
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            if (k < nmem) {
+                const double d = v[k] - mean;
+                sq += d * d;
+            }
+        var = sq / M;
+        if (yf && l16 < nmem) yf[(size_t)l16 * n + i] = y;
+        if (l16 == 0) {
+            if (mean_out) mean_out[i] = mean;
+            if (var_out) var_out[i] = var;
+        }
+    }
+    if (part_var) {   // block-uniform
+        if (l16 == 0) {
+            const bool ok = active && var == var;
+            red_var[row] = ok ? var : 0.;
+            red_idx[row] = ok ? i : -1;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double bv = __builtin_nan("");
+            int bi = -1;
+            for (int r = 0; r < rpb; r++)
+                if (red_idx[r] >= 0 && (bi < 0 || red_var[r] > bv)) bv = red_var[r], bi = red_idx[r];
+            part_var[blockIdx.x] = bv;
+            part_idx[blockIdx.x] = bi;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // element strain from nodal values: (sum_gp B) u_e   (model.py:387-411)
 __device__ __forceinline__ void class_strain(const ClassDev &c, const double2 *u2, int n0, int n1,
