@@ -443,6 +443,30 @@ void dfree(T *&p)
     p = nullptr;
 }
 
+// device buffers of one call, released on every exit path
+struct CallBuffers {
+    std::vector<void *> p;
+    template <class T>
+    int get(plfx_ctx *c, T **q, size_t n)
+    {
+        HIPCHK(c, hipMalloc((void **)q, std::max<size_t>(n, 1) * sizeof(T)));
+        p.push_back(*q);
+        return 0;
+    }
+    // get + upload of n elements on c->stream (host stays valid until the stream is synchronised)
+    template <class T>
+    int put(plfx_ctx *c, T **q, const T *host, size_t n)
+    {
+        if (int rc = get(c, q, n)) return rc;
+        HIPCHK(c, hipMemcpyAsync(*q, host, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }
+    ~CallBuffers()
+    {
+        for (void *q : p) hipFree(q);
+    }
+};
+
 // doubles of the tangent store of n elements: 21 entries + 7 factors + one tag byte per element
 inline size_t tan_words(size_t n) { return 28 * n + (n + 7) / 8; }
 
@@ -2057,27 +2081,40 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
 
 
 // ------------------------------------------------------------------------------ batched point evaluation
+// the opening check of a point function of one material; args_ok: what the function asks of its other arguments
+static int point_check(plfx_ctx *c, int mat, bool args_ok)
+{
+    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
+    if (mat < 0 || mat >= c->nmat || !args_ok) return fail(c, PLFX_ERR_ARG, "bad argument");
+    return PLFX_OK;
+}
+
+// Block size of a kernel with 16 lanes per point whose blocks stage the tables once: the fewest points per block that still
+// leave no more than a few blocks per CU, so that a short batch spreads over the device.  No result depends on the choice.
+static int row16_block(const plfx_ctx *c, int n, int cap)
+{
+    int block = 64;
+    while (block < cap && (n + block / 16 - 1) / (block / 16) > 2 * c->prop.multiProcessorCount) block *= 2;
+    return block;
+}
+
 static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, const double *epl,
                       const double *ld, double *out, int32_t *status)
 {
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat || n < 0 || !sig || !out) return fail(c, PLFX_ERR_ARG, "bad argument");
+    if (int rc = point_check(c, mat, n >= 0 && sig && out)) return rc;
     if (n == 0) return PLFX_OK;
-    const int wout = (what == 1) ? 6 : 1;
+    const size_t N = n, wout = (what == 1) ? 6 : 1;
+    CallBuffers B;
     double *dsig = nullptr, *depl = nullptr, *dout = nullptr, *dld = nullptr;
     int32_t *dst = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dsig, (size_t)n * 48));
-    HIPCHK(c, hipMalloc((void **)&dout, (size_t)n * 8 * wout));
-    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    if (epl) {
-        HIPCHK(c, hipMalloc((void **)&depl, (size_t)n * 48));
-        HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    }
-    if (ld) {
-        HIPCHK(c, hipMalloc((void **)&dld, 48));
-        HIPCHK(c, hipMemcpyAsync(dld, ld, 48, hipMemcpyHostToDevice, c->stream));
-    }
-    if (status) HIPCHK(c, hipMalloc((void **)&dst, (size_t)n * 4));
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.get(c, &dout, N * wout)) return rc;
+    if (epl)
+        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
+    if (ld)
+        if (int rc = B.put(c, &dld, ld, 6)) return rc;
+    if (status)
+        if (int rc = B.get(c, &dst, N)) return rc;
     static const bool wave_full = !(getenv("PLFX_FULL_YF_WAVE") && atoi(getenv("PLFX_FULL_YF_WAVE")) == 0);
     EvPair *ev;
     tim_begin(c, 0, &ev);   // family 0 like plfx_response_batch: the kernel alone, without the copies
@@ -2089,14 +2126,9 @@ static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, 
                            c->dmat, c->nmat, c->svc_lds_need, what, mat, n, dsig, depl, dld, dout, dst);
     tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, dout, (size_t)n * 8 * wout, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout, N * wout * 8, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
-    hipFree(dsig);
-    hipFree(dout);
-    if (depl) hipFree(depl);
-    if (dld) hipFree(dld);
-    if (dst) hipFree(dst);
     return PLFX_OK;
 }
 
@@ -2113,25 +2145,21 @@ int plfx_fgrad_batch(plfx_ctx *c, int mat, int n, const double *sig, double *a)
 }
 int plfx_fgrad_seq_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *seq, double *a)
 {
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat || n < 0 || !sig || !seq || !a) return fail(c, PLFX_ERR_ARG, "bad argument");
+    if (int rc = point_check(c, mat, n >= 0 && sig && seq && a)) return rc;
     const int kind = c->hmat[mat].kind;
     if (kind != PLFX_HILL6 && kind != PLFX_PRINC3)
         return fail(c, PLFX_ERR_UNSUPPORTED, "calc_fgrad(seq=...): analytic Hill materials only (material.py:822-847)");
     if (n == 0) return PLFX_OK;
+    const size_t N = n;
+    CallBuffers B;
     double *dsig = nullptr, *dseq = nullptr, *dout = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dsig, (size_t)n * 48));
-    HIPCHK(c, hipMalloc((void **)&dseq, (size_t)n * 8));
-    HIPCHK(c, hipMalloc((void **)&dout, (size_t)n * 48));
-    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dseq, seq, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.put(c, &dseq, seq, N)) return rc;
+    if (int rc = B.get(c, &dout, 6 * N)) return rc;
     hipLaunchKernelGGL(k_fgrad_seq, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->dmat, mat, n, dsig, dseq, dout);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(a, dout, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(a, dout, N * 48, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
-    hipFree(dsig);
-    hipFree(dseq);
-    hipFree(dout);
     return PLFX_OK;
 }
 int plfx_yf_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *yf)
@@ -2156,23 +2184,22 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
     if (mat_id)
         for (int i = 0; i < n; i++)
             if (mat_id[i] < 0 || mat_id[i] >= c->nmat) return fail(c, PLFX_ERR_ARG, "mat_id[%d] out of range", i);
+    CallBuffers B;
     double *d_in = nullptr, *d_out = nullptr;
     int32_t *d_mid = nullptr, *d_ns = nullptr;
     const size_t N = n;
-    HIPCHK(c, hipMalloc((void **)&d_in, N * 18 * 8));
-    HIPCHK(c, hipMalloc((void **)&d_out, N * (1 + 6 + 6 + 36) * 8));
-    HIPCHK(c, hipMalloc((void **)&d_ns, N * 4));
+    if (int rc = B.get(c, &d_in, N * 18)) return rc;
+    if (int rc = B.get(c, &d_out, N * (1 + 6 + 6 + 36))) return rc;
+    if (int rc = B.get(c, &d_ns, N)) return rc;
     HIPCHK(c, hipMemcpyAsync(d_in, sig, N * 48, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_in + 6 * N, epl, N * 48, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_in + 12 * N, deps, N * 48, hipMemcpyHostToDevice, c->stream));
-    if (mat_id) {
-        HIPCHK(c, hipMalloc((void **)&d_mid, N * 4));
-        HIPCHK(c, hipMemcpyAsync(d_mid, mat_id, N * 4, hipMemcpyHostToDevice, c->stream));
-    }
+    if (mat_id)
+        if (int rc = B.put(c, &d_mid, mat_id, N)) return rc;
     double *d_fy = d_out, *d_so = d_out + N, *d_dp = d_out + 7 * N, *d_ct = d_out + 13 * N;
     double *d_kh = nullptr;   // [2N]: entry / exit hardening modulus of the work-hardening SVC points
     if (c->has_svcwh) {
-        HIPCHK(c, hipMalloc((void **)&d_kh, N * 16));
+        if (int rc = B.get(c, &d_kh, 2 * N)) return rc;
         std::vector<double> k0(N);
         for (size_t i = 0; i < N; i++) k0[i] = kh_in ? kh_in[i] : c->hmat[mat_id ? mat_id[i] : 0].khard;
         HIPCHK(c, hipMemcpyAsync(d_kh, k0.data(), N * 8, hipMemcpyHostToDevice, c->stream));
@@ -2227,11 +2254,6 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
             for (size_t i = 0; i < N; i++) kh_out[i] = kh_in ? kh_in[i] : c->hmat[mat_id ? mat_id[i] : 0].khard;
     }
     HIPCHK(c, stream_sync(c));
-    hipFree(d_in);
-    hipFree(d_out);
-    hipFree(d_ns);
-    if (d_mid) hipFree(d_mid);
-    if (d_kh) hipFree(d_kh);
     return PLFX_OK;
 }
 
@@ -2251,53 +2273,45 @@ int plfx_response_batch_kh(plfx_ctx *c, int n, const int32_t *mat_id, const doub
 
 int plfx_fgrad_batch_wh(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *fgrad, double *khard_raw)
 {
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat || n < 0 || !sig || !fgrad) return fail(c, PLFX_ERR_ARG, "bad argument");
+    if (int rc = point_check(c, mat, n >= 0 && sig && fgrad)) return rc;
     if (c->hmat[mat].kind != PLFX_SVC_WH) return fail(c, PLFX_ERR_ARG, "material %d has no work-hardening features", mat);
     if (n == 0) return PLFX_OK;
+    const size_t N = n;
+    CallBuffers B;
     double *dsig = nullptr, *depl = nullptr, *dout = nullptr, *dkh = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dsig, (size_t)n * 48));
-    HIPCHK(c, hipMalloc((void **)&dout, (size_t)n * 48));
-    HIPCHK(c, hipMalloc((void **)&dkh, (size_t)n * 8));
-    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    if (epl) {
-        HIPCHK(c, hipMalloc((void **)&depl, (size_t)n * 48));
-        HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    }
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.get(c, &dout, 6 * N)) return rc;
+    if (int rc = B.get(c, &dkh, N)) return rc;
+    if (epl)
+        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
     EvPair *ev;
     tim_begin(c, 0, &ev);
     hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat,
                        c->svc_lds_need, 1, mat, n, dsig, depl, (const double *)nullptr, dout, (int32_t *)nullptr, dkh);
     tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(fgrad, dout, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
-    if (khard_raw) HIPCHK(c, hipMemcpyAsync(khard_raw, dkh, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(fgrad, dout, N * 48, hipMemcpyDeviceToHost, c->stream));
+    if (khard_raw) HIPCHK(c, hipMemcpyAsync(khard_raw, dkh, N * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
-    hipFree(dsig);
-    hipFree(dout);
-    hipFree(dkh);
-    if (depl) hipFree(depl);
     return PLFX_OK;
 }
 
 // Material.calc_hessian of an SVC material: sibling of point_eval with 36 numbers per point and the row kernel
 int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *hess)
 {
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat || n < 0 || !sig || !hess) return fail(c, PLFX_ERR_ARG, "bad argument");
+    if (int rc = point_check(c, mat, n >= 0 && sig && hess)) return rc;
     const int kind = c->hmat[mat].kind;
     if (kind != PLFX_SVC6 && kind != PLFX_SVC_WH)
         return fail(c, PLFX_ERR_UNSUPPORTED, kind == PLFX_SVC3 ? "calc_hessian: not implemented for 3D stress (material.py:950)"
                     : "calc_hessian: no analytical hessian for this Hill / Tresca / Barlat material (material.py:965-970)");
     if (n == 0) return PLFX_OK;
+    const size_t N = n;
+    CallBuffers B;
     double *dsig = nullptr, *depl = nullptr, *dout = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dsig, (size_t)n * 48));
-    HIPCHK(c, hipMalloc((void **)&dout, (size_t)n * 288));
-    HIPCHK(c, hipMemcpyAsync(dsig, sig, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    if (epl && kind == PLFX_SVC_WH) {
-        HIPCHK(c, hipMalloc((void **)&depl, (size_t)n * 48));
-        HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    }
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.get(c, &dout, 36 * N)) return rc;
+    if (epl && kind == PLFX_SVC_WH)
+        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
     // 64 points per block; a block stages the tables once, so no more blocks than keep every CU busy for a few rounds
     const int rpb = HESS_BLOCK / 16;
     const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
@@ -2311,11 +2325,8 @@ int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const dou
                            c->dmat, c->nmat, c->svc_lds_need, mat, n, dsig, depl, dout);
     tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hess, dout, (size_t)n * 288, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hess, dout, N * 288, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
-    hipFree(dsig);
-    hipFree(dout);
-    if (depl) hipFree(depl);
     return PLFX_OK;
 }
 
@@ -2324,17 +2335,17 @@ int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const dou
 int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double *epl, const double *x0, double *x,
                      int32_t *status)
 {
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat || n < 0 || !su || !x || !status) return fail(c, PLFX_ERR_ARG, "bad argument");
+    if (int rc = point_check(c, mat, n >= 0 && su && x && status)) return rc;
     const int kind = c->hmat[mat].kind;
     if (kind == PLFX_ELASTIC) return fail(c, PLFX_ERR_ARG, "yield_scale: material %d has no yield strength", mat);
     if (n == 0) return PLFX_OK;
-    SvmBuffers B;   // device buffers of this call, released on every exit path
+    const size_t N = n;
+    CallBuffers B;
     double *dsu = nullptr, *depl = nullptr, *dx0 = nullptr, *dx = nullptr;
     int32_t *dst = nullptr;
-    if (int rc = B.get(c, &dsu, (size_t)n * 6)) return rc;
-    if (int rc = B.get(c, &dx, (size_t)n)) return rc;
-    if (int rc = B.get(c, &dst, (size_t)n)) return rc;
+    if (int rc = B.get(c, &dsu, 6 * N)) return rc;
+    if (int rc = B.get(c, &dx, N)) return rc;
+    if (int rc = B.get(c, &dst, N)) return rc;
     // principal-stress kinds (2-feature SVC, Hill-3 / J2 on principal stresses): rays with out-of-plane shear are reduced to
     // their principal stresses here, by the LAPACK replay that the device runs for such states (plfx_sig_princ_host); the order
     // of the principal stresses does not change along a ray.  The kernels then need the closed form of plane states only.
@@ -2352,20 +2363,12 @@ int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double
             lapack3::sig_princ_lapack3(s, r);
             r[3] = r[4] = r[5] = 0.;
         }
-    HIPCHK(c, hipMemcpyAsync(dsu, red.empty() ? su : red.data(), (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    if (epl) {
-        if (int rc = B.get(c, &depl, (size_t)n * 6)) return rc;
-        HIPCHK(c, hipMemcpyAsync(depl, epl, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    }
-    if (x0) {
-        if (int rc = B.get(c, &dx0, (size_t)n)) return rc;
-        HIPCHK(c, hipMemcpyAsync(dx0, x0, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    // a block stages the tables once; the fewest rays per block (4 per wave) that still leave no more than a few blocks per
-    // CU, so that a short batch spreads over the device.  The result does not depend on the choice.
-    int block = 64;
-    while (block < YS_BLOCK && (n + block / 16 - 1) / (block / 16) > 2 * c->prop.multiProcessorCount) block *= 2;
-    const int rpb = block / 16;
+    HIPCHK(c, hipMemcpyAsync(dsu, red.empty() ? su : red.data(), N * 48, hipMemcpyHostToDevice, c->stream));
+    if (epl)
+        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
+    if (x0)
+        if (int rc = B.put(c, &dx0, x0, N)) return rc;
+    const int block = row16_block(c, n, YS_BLOCK), rpb = block / 16;
     const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
     EvPair *ev;
     tim_begin(c, 0, &ev);
@@ -2393,8 +2396,8 @@ int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double
 #undef YS_LAUNCH
     tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(x, dx, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, dst, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(x, dx, N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
     return PLFX_OK;
 }
@@ -2427,13 +2430,9 @@ int plfx_committee_yf(plfx_ctx *c, int nmem, const int32_t *mats, const double *
         if (m.nsv * (m.nfeat + 1) <= c->svc_lds_need) staged |= 1 << k;   // the test of stage_svc
     }
     if (n == 0) return PLFX_OK;
-    // a block stages each member's tables once: the fewest points per block (one per 16 lanes) that still leave no more than a few
-    // blocks per CU, so that a short batch spreads over the device.  The result does not depend on the choice.
-    int block = 64;
-    while (block < CY_BLOCK && (n + block / 16 - 1) / (block / 16) > 2 * c->prop.multiProcessorCount) block *= 2;
-    const int rpb = block / 16, nblk = (n + rpb - 1) / rpb;
+    const int block = row16_block(c, n, CY_BLOCK), rpb = block / 16, nblk = (n + rpb - 1) / rpb;
     const bool query = best || best_var;
-    SvmBuffers B;   // device buffers of this call, released on every exit path: [su | yf | mean | var | partial variances], partial indices
+    CallBuffers B;   // [su | yf | mean | var | partial variances], partial indices
     double *dbuf = nullptr;
     int32_t *dpi = nullptr;
     const size_t nn = (size_t)n, o_yf = 6 * nn, o_mean = o_yf + (yf ? (size_t)nmem * nn : 0), o_var = o_mean + (mean ? nn : 0),

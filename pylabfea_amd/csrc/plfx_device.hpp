@@ -321,6 +321,17 @@ __device__ inline void sig_princ_dev(const double *s, double *sp)
     sig_princ_general(s, sp);
 }
 
+// The closed form above for callers that have seen to s[3] == s[4] == 0 themselves (the yield-scale kernels): no call, no
+// scratch.  sig_princ_dev keeps its own branches: written through this function the sweep kernels compile to other code.
+__device__ __forceinline__ void plane_princ(const double *s, double *sp)
+{
+    const double mean = 0.5 * (s[0] + s[1]), hd = 0.5 * (s[0] - s[1]);
+    const double R = sqrt(hd * hd + s[5] * s[5]);
+    sp[0] = (s[5] == 0.) ? s[0] : (s[0] >= s[1]) ? mean + R : mean - R;
+    sp[1] = (s[5] == 0.) ? s[1] : (s[0] >= s[1]) ? mean - R : mean + R;
+    sp[2] = s[2];
+}
+
 // 3-parameter Hill / J2 on principal stresses (material.py:662-673); I1 from the Voigt normal components
 __device__ __forceinline__ double princ_seq_sp(const MatDev &m, const double *sp, double tr)
 {

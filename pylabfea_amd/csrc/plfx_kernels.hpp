@@ -167,6 +167,48 @@ __device__ __forceinline__ void stage_svc(const MatDev *smat, int nmat, double *
     dual = lds + nf * n;
 }
 
+// ---- The row sum over the support vectors of an SVC material: k_yield_scale, k_committee_yf, and
+// k_hessian_row, which writes the trips out.  The tables of material `mat`: staged in dynamic LDS where they fit (stage_svc),
+// read from device memory otherwise.  Called by every thread of the block after a barrier that closes the writes to smat and
+// the reads of the tables staged before; ends with the barrier that publishes the new ones.
+__device__ __forceinline__ void svc_row_tables(const MatDev *smat, int nmat, int lds_doubles, int mat, const double *&psv,
+                                               const double *&pdu)
+{
+    int svc_mat;
+    const double *sv, *dual;
+    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
+    __syncthreads();
+    psv = (mat == svc_mat) ? sv : smat[mat].sv;
+    pdu = (mat == svc_mat) ? dual : smat[mat].dual;
+}
+
+// The trips of one row -- 16 lanes, one DPP row, per point -- over the nsv vectors.  The contract, held here for every user:
+//   lanes   lane L of the row takes the vectors L, L + 16, L + 32, ... two per trip: slot 0 the vector k, slot 1 the vector
+//           k + 16, k = L, L + 32, ...; two independent exp2 chains (exp2_neg_n<2>), and the callers keep one accumulator per slot.
+//   order   a lane's terms arrive in increasing k, slot 0 before slot 1, and the caller closes the row with the DPP butterfly
+//           (YfSvcRow<1>::row_allsum), after which the 16 lanes hold the same bits.  So the order of a point's sum depends on
+//           nsv alone -- not on the number of points, the point's place, the block size or the grid.  Rows of a wave diverge freely.
+//   tail    where the vector k + 16 does not exist, slot 1 takes the vector k again with the coefficient 0: an exact +0 enters.
+//   flush   kernel values below 2^-1020 enter with the coefficient 0 (the reference keeps subnormals down to 2^-1074).
+// dist2(v, c): the squared distance of the point to the vector at v (NF doubles), for slot c; add(c, d, e): the term of slot c,
+// d the coefficient (0 by tail and flush), e = exp(-gamma dist2).  g = -gamma log2(e).
+// e is always a finite number >= 0 (exp2_neg_n clamps its argument at -1020, a NaN or -inf argument included), so a term
+// with d = 0 is an exact +0.
+template <int NF, class D2, class ADD>
+__device__ __forceinline__ void svc_row_trips(const double *psv, const double *pdu, int nsv, double g, D2 &&dist2, ADD &&add)
+{
+    for (int k = threadIdx.x & 15; k < nsv; k += 32) {
+        const bool two = (k + 16 < nsv);
+        const int kk[2] = {k, two ? k + 16 : k};
+        double ea[2], eo[2];
+#pragma unroll
+        for (int c = 0; c < 2; c++) ea[c] = g * dist2(psv + (size_t)NF * kk[c], c);
+        exp2_neg_n<2>(ea, eo);
+#pragma unroll
+        for (int c = 0; c < 2; c++) add(c, (ea[c] < -1020. || (c == 1 && !two)) ? 0. : pdu[kk[c]], eo[c]);
+    }
+}
+
 // One material kind per kernel instantiation (KIND = 1 Hill-6p/J2 on Voigt, 2 Hill-3p/J2 on principal
 // stresses, 3 RBF-SVC): the analytic kernels do not carry the SVC code (and its registers); every
 // instantiation skips the elements of the other kinds.
@@ -397,13 +439,13 @@ k_point_eval(const MatDev *gmat, int nmat, int lds_doubles, int what, int mat, i
 // the 6 x 6 block of the Hessian of the decision function w.r.t. the stress features,
 //   Hx[a][b] = sum_i c_i k_i (4 gamma^2 d_i[a] d_i[b] - 2 gamma delta_ab),  d_i = v_i - x,  k_i = exp(-gamma |d_i|^2) over ALL features
 // (the plastic-strain features epl / scale_wh enter the distance; the three trailing ones are zero as everywhere on the path).
-// Lane mapping of the row kernels: 16 lanes (one DPP row) per point, four points per wave, lane L of a row takes the support
-// vectors L, L + 16, ... two per trip (two independent exp2 chains); the 21 unique sums are closed by the DPP butterfly and
-// lanes 0..5 of the row store one matrix row each.  Per vector the loop accumulates w d_a d_b (a < b) and w (d_a^2 - 1/(2 gamma))
+// The lanes, order, tail and flush of svc_row_trips, 16 lanes per point and four points per wave, but with the trips written
+// out in the kernel: through the helper's lambdas the 15-feature instantiation schedules its loads differently and measured
+// 1.3 % slower.  The 21 unique sums are closed by the DPP butterfly and lanes 0..5 of the row store one
+// matrix row each.  Per vector the loop accumulates w d_a d_b (a < b) and w (d_a^2 - 1/(2 gamma))
 // -- each diagonal term in one piece, as the reference forms it, so that the error stays within a few ulps of the sum of the
 // ABSOLUTE terms (the gauge the tests hold it to) -- and 4 gamma^2 is applied once at the end.  dev_only materials: the
 // features are the deviator's and, like the reference, no chain rule through the projection is applied.
-// Kernel values below 2^-1020 are flushed to zero (the reference keeps subnormals down to 2^-1074).
 constexpr int HESS_BLOCK = 512;   // one block per CU when the tables fill its LDS: 8 waves = 2 per SIMD, two exp2 chains each
 template <int NF>
 __global__ void __launch_bounds__(HESS_BLOCK)
@@ -415,13 +457,9 @@ k_hessian_row(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
-    int svc_mat;
-    const double *sv, *dual;
-    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
-    __syncthreads();
+    const double *psv, *pdu;
+    svc_row_tables(smat, nmat, lds_doubles, mat, psv, pdu);
     const MatDev &m = smat[mat];
-    const double *psv = (mat == svc_mat) ? sv : m.sv;
-    const double *pdu = (mat == svc_mat) ? dual : m.dual;
     const int nsv = m.nsv;
     const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;
     const double g = -m.gamma * LOG2E, q = 0.5 / m.gamma, c4 = 4. * m.gamma * m.gamma;
@@ -436,8 +474,8 @@ k_hessian_row(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
         }
 #pragma unroll
         for (int c = 0; c < 21; c++) acc[c] = 0.;
-        for (int k = l16; k < nsv; k += 32) {
-            const bool two = (k + 16 < nsv);   // the second vector of the trip exists (else: the first again, with weight 0)
+        for (int k = l16; k < nsv; k += 32) {   // the trips of svc_row_trips, written out: see the comment above the kernel
+            const bool two = (k + 16 < nsv);
             const int kk[2] = {k, two ? k + 16 : k};
             double d[2][6], ea[2], eo[2];
 #pragma unroll
@@ -493,10 +531,8 @@ k_hessian_row(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
 // Only x moves along a ray, so the features are set up once per ray: NF = 6 / 15 x u with u the (deviatoric) stress features of
 // su, the plastic-strain features of NF = 15 fixed; NF = 2 (seq_J2(su) / scale_seq) x - 1 and the constant polar angle.  Every
 // difference x u_j - v_ij is ONE fma, so the sums are at least as accurate as the point functions'.
-// Lane mapping of k_hessian_row: 16 lanes (one DPP row) per ray, four rays per wave, lane L takes the vectors L, L + 16, ...
-// two per trip (two exp2 chains, two accumulators), closed by the DPP butterfly: every lane of a row holds the same f, control
-// flow is row-uniform, rows of a wave diverge freely (the butterfly stays inside the row).  The order of a ray's sum depends on
-// nsv alone -- not on n, the ray's place in the batch, the block size or the grid.
+// f is the row sum of svc_row_trips, 16 lanes per ray and four rays per wave: every lane of a row holds the same f, so the
+// search is row-uniform.
 constexpr int YS_BLOCK = 512;
 constexpr int YS_CAP_DOWN = 240, YS_CAP_UP = 90, YS_CAP_BISECT = 80;   // 0.98^228 = 0.01, 1.02^82 = 5, 2 % of x in ulps: 2^47
 template <int NF>
@@ -511,13 +547,9 @@ k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
-    int svc_mat;
-    const double *sv, *dual;
-    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
-    __syncthreads();
+    const double *psv, *pdu;
+    svc_row_tables(smat, nmat, lds_doubles, mat, psv, pdu);
     const MatDev &m = smat[mat];
-    const double *psv = (mat == svc_mat) ? sv : m.sv;
-    const double *pdu = (mat == svc_mat) ? dual : m.dual;
     const int nsv = m.nsv;
     const int l16 = threadIdx.x & 15, rpb = blockDim.x >> 4;
     const double g = -m.gamma * LOG2E;
@@ -533,15 +565,11 @@ k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
         }
         double x0 = x0_in ? x0_in[i] : 0., sj2;
         if constexpr (NF == 2) {
-            // principal stresses in the closed form of plane states (sig_princ_dev's first branch): plfx_yield_scale has reduced
-            // the rays with out-of-plane shear on the host, so the LAPACK replay (a call, scratch) stays out of this kernel
+            // principal stresses in the closed form of plane states: plfx_yield_scale has reduced the rays with out-of-plane
+            // shear on the host, so the LAPACK replay (a call, scratch) stays out of this kernel
             double sp[3], xf[2];
             fin = fin && s[3] == 0. && s[4] == 0.;
-            const double mean = 0.5 * (s[0] + s[1]), hd = 0.5 * (s[0] - s[1]);
-            const double R = sqrt(hd * hd + s[5] * s[5]);
-            sp[0] = (s[5] == 0.) ? s[0] : (s[0] >= s[1]) ? mean + R : mean - R;
-            sp[1] = (s[5] == 0.) ? s[1] : (s[0] >= s[1]) ? mean - R : mean + R;
-            sp[2] = s[2];
+            plane_princ(s, sp);
             svc3_features(m, sp, xf);
             const double d12 = sp[0] - sp[1], d23 = sp[1] - sp[2], d31 = sp[2] - sp[0];
             sj2 = sqrt(0.5 * (d12 * d12 + d23 * d23 + d31 * d31));
@@ -567,13 +595,9 @@ k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
             for (;;) {
                 // ---- f(x): the decision function at x su (the only evaluation site)
                 double acc[2] = {0., 0.};
-                for (int k = l16; k < nsv; k += 32) {
-                    const bool two = (k + 16 < nsv);   // the second vector of the trip exists (else: the first again, with weight 0)
-                    const int kk[2] = {k, two ? k + 16 : k};
-                    double ea[2], eo[2];
-#pragma unroll
-                    for (int c = 0; c < 2; c++) {
-                        const double *v = psv + (size_t)NF * kk[c];
+                svc_row_trips<NF>(
+                    psv, pdu, nsv, g,
+                    [&](const double *v, int) {
                         double hh = 0.;
                         if constexpr (NF == 2) {
                             const double h0 = fma(x, u[0], -1.) - v[0], h1 = th - v[1];
@@ -592,12 +616,9 @@ k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
 #pragma unroll
                             for (int f = 6 + NW; f < NF; f++) hh = fma(v[f], v[f], hh);
                         }
-                        ea[c] = g * hh;
-                    }
-                    exp2_neg_n<2>(ea, eo);
-                    acc[0] = fma((ea[0] < -1020.) ? 0. : pdu[kk[0]], eo[0], acc[0]);
-                    acc[1] = fma((ea[1] < -1020. || !two) ? 0. : pdu[kk[1]], eo[1], acc[1]);
-                }
+                        return hh;
+                    },
+                    [&](int c, double du, double e) { acc[c] = fma(du, e, acc[c]); });
                 const double f = YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + m.intercept;   // the same bits in the 16 lanes
                 // ---- the search
                 if (!(f == f)) {
@@ -679,13 +700,9 @@ k_yield_scale_analytic(const MatDev *__restrict__ gmat, int mat, int n, const do
         if (kd == 2) fin = fin && s[3] == 0. && s[4] == 0.;            // plfx_yield_scale has reduced the other states
         if (fin) {
             double seq;
-            if constexpr (kd == 2) {   // principal stresses in the closed form of plane states (sig_princ_dev's first branch): no LAPACK call
+            if constexpr (kd == 2) {   // principal stresses in the closed form of plane states: no LAPACK call
                 double sp[3];
-                const double mean = 0.5 * (s[0] + s[1]), hd = 0.5 * (s[0] - s[1]);
-                const double R = sqrt(hd * hd + s[5] * s[5]);
-                sp[0] = (s[5] == 0.) ? s[0] : (s[0] >= s[1]) ? mean + R : mean - R;
-                sp[1] = (s[5] == 0.) ? s[1] : (s[0] >= s[1]) ? mean - R : mean + R;
-                sp[2] = s[2];
+                plane_princ(s, sp);
                 seq = princ_seq_sp(m, sp, s[0] + s[1] + s[2]);
             } else {
                 seq = kd == 4 ? tresca_seq(s) : kd == 5 ? barlat_seq(m, s) : hill_seq(m, s);
@@ -703,12 +720,11 @@ k_yield_scale_analytic(const MatDev *__restrict__ gmat, int mat, int n, const do
 // (np.var, ddof = 0) over the members, and per block the point of largest variance.  The features are the reference's
 // create_scaled_input (material.py:2336-2339) with its roundings in its order: su * scale_m first, the deviator where the
 // member is dev_only, then the division by scale_seq_m.
-// Lane mapping of k_hessian_row / k_yield_scale: 16 lanes (one DPP row) per point, ONE point per row and block pass, lane L
-// takes the vectors L, L + 16, ... of the current member two per trip, closed by the DPP butterfly, so the 16 lanes of a row
-// hold the same bits.  The members are looped inside the row (su is read once per point), their tables staged in LDS one
-// member at a time where they fit (stage_svc; two block barriers per member), read from device memory otherwise.  The order
-// of a point's sum for member m depends on that member's nsv alone -- not on n, the point's place, the block size, the
-// grid or the other members.  Lane m of the row keeps y_m (nmem <= MAXMAT = 16 = lanes of a row), so no register array is
+// y[m, i] is the row sum of svc_row_trips over member m's vectors, 16 lanes per point, ONE point per row and block pass.  The
+// members are looped inside the row (su is read once per point), their tables staged in LDS one member at a time where they
+// fit (svc_row_tables; two block barriers per member), read from device memory otherwise.  The order of a point's sum for
+// member m depends on that member's nsv alone, and not on the other members either.
+// Lane m of the row keeps y_m (nmem <= MAXMAT = 16 = lanes of a row), so no register array is
 // indexed by the member; after the last member the 16 values are broadcast through the row (row_newbcast) and
 //     mean = (sum_m y_m) / M,   var = (sum_m (y_m - mean)^2) / M,   both summed in member order, no contraction.
 // A non-finite component of su_i makes y[:, i], mean_i and var_i NaN and nothing else.
@@ -749,14 +765,10 @@ k_committee_yf(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int n
     for (int mm = 0; mm < nmem; mm++) {   // block-uniform
         const int mat = a.mat[mm];
         __syncthreads();   // first trip: smat is complete; later trips: the readers of the previous member's tables are done
-        int svc_mat;
-        const double *sv, *dual;
-        stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 0, mat);
-        __syncthreads();
+        const double *psv, *pdu;
+        svc_row_tables(smat, nmat, lds_doubles, mat, psv, pdu);
         if (!active) continue;
         const MatDev &m = smat[mat];
-        const double *psv = (mat == svc_mat) ? sv : m.sv;
-        const double *pdu = (mat == svc_mat) ? dual : m.dual;
         const int nsv = m.nsv;
         const double g = -m.gamma * LOG2E, sc = a.scale[mm];
         double sx[6], x[6];
@@ -764,25 +776,18 @@ k_committee_yf(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int n
         for (int c = 0; c < 6; c++) sx[c] = s[c] * sc;
         svc_features(m, sx, x);
         double acc[2] = {0., 0.};
-        for (int k = l16; k < nsv; k += 32) {
-            const bool two = (k + 16 < nsv);   // the second vector of the trip exists (else: the first again, with weight 0)
-            const int kk[2] = {k, two ? k + 16 : k};
-            double ea[2], eo[2];
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const double *v = psv + (size_t)6 * kk[c];
+        svc_row_trips<6>(
+            psv, pdu, nsv, g,
+            [&](const double *v, int) {
                 double hh = 0.;
 #pragma unroll
                 for (int f = 0; f < 6; f++) {
                     const double d = x[f] - v[f];
                     hh = fma(d, d, hh);
                 }
-                ea[c] = g * hh;
-            }
-            exp2_neg_n<2>(ea, eo);
-            acc[0] = fma((ea[0] < -1020.) ? 0. : pdu[kk[0]], eo[0], acc[0]);
-            acc[1] = fma((ea[1] < -1020. || !two) ? 0. : pdu[kk[1]], eo[1], acc[1]);
-        }
+                return hh;
+            },
+            [&](int c, double du, double e) { acc[c] = fma(du, e, acc[c]); });
         double f = YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + m.intercept;   // the same bits in the 16 lanes
         if (!fin) f = __builtin_nan("");
         if (l16 == mm) y = f;

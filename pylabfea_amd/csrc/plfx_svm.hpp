@@ -629,22 +629,6 @@ __global__ void __launch_bounds__(256) k_svc_decision(const double *X, int d, co
     out[q0 + t] = s + icpt[p];
 }
 
-// device buffers of one call, released on every exit path
-struct SvmBuffers {
-    std::vector<void *> p;
-    template <class T>
-    int get(plfx_ctx *c, T **q, size_t n)
-    {
-        HIPCHK(c, hipMalloc((void **)q, std::max<size_t>(n, 1) * sizeof(T)));
-        p.push_back(*q);
-        return 0;
-    }
-    ~SvmBuffers()
-    {
-        for (void *q : p) hipFree(q);
-    }
-};
-
 #define SVMCHK(call)           \
     do {                       \
         const int rc_ = (call); \
@@ -725,7 +709,7 @@ int svc_fit_batch_impl(plfx_ctx *c, int n, int d, const double *X, const double 
         hmax[p] = (int)std::min<int64_t>(max_iter > 0 ? max_iter : std::max<int64_t>(10000000, 100 * (int64_t)np), INT32_MAX);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    SvmBuffers B;
+    CallBuffers B;
     SmoArgs a;
     double *dX, *dC, *dg;
     int32_t *doff, *drow, *dmax, *dact;
@@ -854,7 +838,7 @@ int svc_fit_wide_impl(plfx_ctx *c, int n, int d, const double *X, const double *
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, c->device));
     if (!coop) return fail(c, PLFX_ERR_HIP, "plfx_svc_fit_wide: the device does not support cooperative launches");
-    SvmBuffers B;
+    CallBuffers B;
     SmoArgs ia;
     double *dX, *dC, *dg;
     int32_t *doff, *drow, *dmax;
@@ -935,7 +919,7 @@ int svc_decision_batch_impl(plfx_ctx *c, int n, int d, const double *X, int npro
     int qmax = 0;
     for (int p = 0; p < nprob; p++) qmax = std::max(qmax, q_off[p + 1] - q_off[p]);
     HIPCHK(c, hipSetDevice(c->device));
-    SvmBuffers B;
+    CallBuffers B;
     double *dX, *dcoef, *dic, *dg, *dout;
     int32_t *dsvo, *dsvi, *dqo, *dqi;
     SVMCHK(B.get(c, &dX, (size_t)n * d));
@@ -1318,7 +1302,7 @@ int svr_fit_batch_impl(plfx_ctx *c, int n, int d, const double *X, int nprob, co
     for (int k = 0; k < total; k++)
         if (!std::isfinite(t[k])) return fail(c, PLFX_ERR_ARG, "plfx_svr_fit_batch: target %d is not finite", k);
     HIPCHK(c, hipSetDevice(c->device));
-    SvmBuffers B;
+    CallBuffers B;
     SvrArgs a;
     double *dX, *dC, *dg, *de, *dt;
     int32_t *doff, *drow, *dmax, *dact;
@@ -1404,7 +1388,7 @@ int svr_predict_multi_impl(plfx_ctx *c, int n, int d, const double *X, double ga
         for (int k = 0; k < m; k++) hc[(size_t)r * SVR_MMAX + k] = coef[(size_t)r * m + k];
     for (int k = 0; k < m; k++) hi[k] = intercept[k];
     HIPCHK(c, hipSetDevice(c->device));
-    SvmBuffers B;
+    CallBuffers B;
     double *dX, *dc, *di, *dQ, *dout;
     SVMCHK(B.get(c, &dX, (size_t)n * d));
     SVMCHK(B.get(c, &dc, hc.size()));

@@ -173,6 +173,15 @@ def synthetic(nsv, seed):
     return m
 
 
+def check_rows(m, sig, H, what):
+    """H of the rows sig against the np.longdouble restatement, allowed 4 max(r_ref, 1) units with r_ref measured on these rows"""
+    Hl, A = restate(m, features(m, sig))
+    Hd, _ = restate(m, features(m, sig), L=np.float64)
+    r_ref = float(np.max(np.abs(Hd.astype(np.longdouble) - Hl)[A > 0] / (A[A > 0] * U)))
+    print('%s: r_ref of the FP64 evaluation on these rows %.3f' % (what, r_ref))
+    check(H, Hl, A, 4. * max(r_ref, 1.), what)
+
+
 @pytest.mark.parametrize('nsv', [3000, 17])   # tables read from device memory / fewer vectors than lanes in a row
 def test_shapes_of_the_lane_mapping(fx, nsv):
     """No reference run exists for a synthetic table, so r_ref is formed here by the procedure of the module docstring: the
@@ -191,13 +200,23 @@ def test_shapes_of_the_lane_mapping(fx, nsv):
         if n == 0:
             continue
         pick = np.arange(n) if n < 2000 else np.sort(rng.choice(n, size=2000, replace=False))
-        Hl, A = restate(m, features(m, sig[pick]))
-        Hd, _ = restate(m, features(m, sig[pick]), L=np.float64)
-        r_ref = float(np.max(np.abs(Hd.astype(np.longdouble) - Hl)[A > 0] / (A[A > 0] * U)))
-        print('nsv = %d, n = %d: r_ref of the FP64 evaluation on these rows %.3f' % (nsv, n, r_ref))
-        check(H[pick], Hl, A, 4. * max(r_ref, 1.), 'nsv = %d, n = %d' % (nsv, n))
+        check_rows(m, sig[pick], H[pick], 'nsv = %d, n = %d' % (nsv, n))
         if n > 2000:   # rows outside the sample: at least finite and symmetric
             assert np.all(np.isfinite(H)) and np.array_equal(H, H.transpose(0, 2, 1))
+
+
+@pytest.mark.parametrize('nsv', [1, 16, 32, 33])
+def test_remainders_of_the_row_sum(nsv):
+    """The trip loop that calc_hessian shares with yield_scale and the committee (svc_row_trips: 16 lanes per point, two vectors
+    per lane and trip) at its remainders: one vector (15 lanes make no trip, lane 0's second slot is absent), 16 (every lane one
+    trip, no second slot), 32 (every slot filled), 33 (lane 0 alone makes a second trip, its second slot absent).  n = 67 is no
+    multiple of the 4 rows of a wave nor of the 32 rows of a block.  Allowance: the procedure of
+    test_shapes_of_the_lane_mapping, 4 max(r_ref, 1) units with r_ref of the FP64 NumPy evaluation on the same rows."""
+    m = synthetic(nsv, nsv)
+    sig = np.random.default_rng(11).normal(size=(67, 6)) * 35.
+    H = m.calc_hessian(sig)
+    assert H.shape == (67, 6, 6)
+    check_rows(m, sig, H, 'nsv = %d, n = 67' % nsv)
 
 
 # ------------------------------------------------------------------------------------------------ 5: C-ABI

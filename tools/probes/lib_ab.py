@@ -2,13 +2,14 @@
 """Two builds of libplfx.so on the same solves, compared BIT FOR BIT (u, sig, epl, sgl, PCG iterations per solve) -- for
 changes that must not move a number (a kernel rewritten with the same sums in the same order).
 
-    python tools/probes/lib_ab.py [--more] pylabfea_amd/libplfx_prev.so pylabfea_amd/libplfx.so
+    python tools/probes/lib_ab.py [--more] [--points] pylabfea_amd/libplfx_prev.so pylabfea_amd/libplfx.so
 
 Cases: even mesh with a soft inclusion (fine + coarse generators, the whole V-cycle), odd mesh 201 x 199 (levels with a wider
 last column / row: area-scaled diagonal, k_mg_coarsen_M), non-proportional laminate (per-column widths).  --more adds config 4's
 6-feature SVC material on 32 x 32 (the row kernels and their 50-sub-step corrector), config 5's J2 + SVC laminate on 128 x 64,
 a solve on 64 x 64 with three indefinite element tangents that GMRES completes, and 32 x 32 with PLFX_MG_MAXIT=2, where
-the single-GPU Jacobi-PCG fall-back completes the solves."""
+the single-GPU Jacobi-PCG fall-back completes the solves.  --points adds the batched point functions of the C-ABI (function
+points below): every output array of a call digested, inputs from a fixed-seed generator, n = 67 and 1025 points."""
 import hashlib
 import os
 import subprocess
@@ -18,7 +19,120 @@ import warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def child(more):
+def points(out):
+    """hessian and yield_scale (tables as trained, cut to the remainders of the 16-lane trip loop, padded past the LDS),
+    committee_yf (as trained and with cut members) and, once each, seq / fgrad / fgrad_seq / fgrad_wh / yf / full_yf / response / the analytic yield_scale on principal stresses:
+    name|digest of all outputs|n (yield_scale: n, rays with a root)"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import numpy as np
+    import committee_cases as CC
+    import pylabfea_amd as FE
+    from pylabfea_amd import _lib
+
+    def record(name, nsv=None, pad=0):
+        """The trained SVC of tests/golden/svc_<name>.npz: its first nsv vectors, then `pad` more with a zero coefficient.  A
+        cut table keeps vectors of the inner class only (negative coefficients); its intercept is set to half of what they
+        sum to at zero stress, so that the function still changes sign along a ray and yield_scale returns roots."""
+        z = np.load(os.path.join(ROOT, 'tests', 'golden', 'svc_%s.npz' % name))
+        sv, dual, icpt = z['par_sv'][:nsv], z['par_dual'][:nsv], float(z['par_intercept'])
+        if nsv:
+            x0 = np.array([-1., 0.]) if sv.shape[1] == 2 else np.zeros(sv.shape[1])
+            icpt = 0.5 * abs(float(np.sum(dual * np.exp(-float(z['par_gamma']) * np.sum((sv - x0) ** 2, axis=1)))))
+        sv, dual = np.vstack((sv, np.tile(sv[:1], (pad, 1)))), np.concatenate((dual, np.zeros(pad)))
+        m = FE.Material(name='ML-' + name)
+        m.elasticity(CV=z['par_CV'])
+        m.plasticity(sy=float(z['par_sy']), sdim=int(z['par_sdim']))
+        m.set_svc(sv, dual, icpt, float(z['par_gamma']), float(z['par_scale_seq']),
+                  dev_only=bool(z['par_dev_only']), scale_wh=float(z['par_scale_wh']) if 'par_scale_wh' in z else None)
+        return m._record(np.asarray(m.CV)), m.sy, getattr(m, 'scale_wh', 1.)
+
+    def emit(name, n, arrays, *info):
+        h = hashlib.sha256()
+        for a in arrays:
+            h.update(np.ascontiguousarray(a).tobytes())
+        out.append((name, (h.hexdigest()[:16], [n] + list(info))))
+
+    def emit_ys(name, n, xs):
+        emit(name, n, xs, int(np.sum(xs[1] == 0)))
+
+    def inputs(n, sy, scale_wh):
+        rng = np.random.default_rng(1000 + n)
+        u = rng.normal(size=(n, 6))
+        su = u / np.linalg.norm(u, axis=1)[:, None]
+        return dict(su=su, sig=su * (sy * rng.uniform(0.3, 2.0, size=n))[:, None], epl=rng.normal(size=(n, 6)) * 0.3 * scale_wh,
+                    x0=sy * rng.uniform(0.5, 1.5, size=n), deps=rng.normal(size=(n, 6)) * 1e-3)
+
+    def with_context(records, fn):
+        ctx = _lib.Context(0)
+        try:
+            ctx.set_materials(records)
+            for n in (67, 1025):
+                fn(ctx, n)
+        finally:
+            ctx.close()
+
+    # more doubles than the LDS of a CU holds (160 KiB = 20480): the tables of such a material are read from device memory
+    past_lds = {'hill': 3200, 'workhard': 1400, 'hill3d': 7000}
+    trained = {'hill': 1585, 'workhard': 1018, 'hill3d': 166}
+    for name in ('hill', 'workhard', 'hill3d'):
+        wh = name == 'workhard'
+        for tag, kw in [('', {})] + [(' nsv %d' % k, dict(nsv=k)) for k in (1, 16, 17, 32, 33)] + \
+                       [(' padded to %d' % past_lds[name], dict(pad=past_lds[name] - trained[name]))]:
+            rec, sy, swh = record(name, **kw)
+            assert rec[0].nsv == (kw.get('nsv') or past_lds[name] if kw else trained[name])
+            assert 'pad' not in kw or rec[0].nsv * (rec[0].nfeat + 1) > 20480
+
+            def fn(ctx, n):
+                q = inputs(n, sy, swh)
+                if name != 'hill3d':
+                    emit('hessian %s%s' % (name, tag), n, [ctx.hessian(0, q['sig'], q['epl'] if wh else None)])
+                emit_ys('yield_scale %s%s' % (name, tag), n, ctx.yield_scale(0, q['su'], q['epl'] if wh else None))
+                emit_ys('yield_scale %s%s, x0' % (name, tag), n, ctx.yield_scale(0, q['su'], q['epl'] if wh else None, q['x0']))
+            with_context([rec], fn)
+
+    z = CC.load()
+    members = [CC.member_params(z, k) for k in range(5)]
+
+    for tag, cuts in (('', [None] * 5), (', members cut to nsv 1, 16, 17, 32, 33', [1, 16, 17, 32, 33])):
+        mem = [CC.cut(p, k) for p, k in zip(members, cuts)]
+
+        def fn(ctx, n):
+            q = inputs(n, 1., 1.)
+            r = ctx.committee_yf(list(range(5)), [0.5 * p['sy'] for p in mem], q['su'], True, True, True, True)
+            emit('committee_yf yf, mean, var, best' + tag, n, [r['yf'], r['mean'], r['var'], np.array(r['best'])])
+        with_context([CC.facade(p)._record(np.asarray(CC.facade(p).CV)) for p in mem], fn)
+
+    hill, sy, _ = record('hill')
+    wh, sy_wh, swh = record('workhard')
+    CV = np.load(os.path.join(ROOT, 'tests', 'golden', 'svc_hill.npz'))['par_CV']
+    hill6 = _lib.pack_material(_lib.HILL6, CV, E=200.e3, nu=0.3, sy=sy, khard=100., hill=[0.7, 1., 1.4, 1., 1.2, 0.8])
+    princ3 = _lib.pack_material(_lib.PRINC3, CV, E=200.e3, nu=0.3, sy=sy, khard=100., hill=[0.7, 1., 1.4])
+
+    def fn(ctx, n):
+        q = inputs(n, sy, swh)
+        ld = np.array([0.3, 1., -0.2, 0.1, 0., 0.4])
+        for k, what in ((0, 'hill6'), (1, 'svc6'), (2, 'svc_wh')):
+            emit('seq %s' % what, n, [ctx.seq(k, q['sig'])])
+            emit('yf %s' % what, n, [ctx.yf(k, q['sig'], q['epl'])])
+        emit('fgrad hill6', n, [ctx.fgrad(0, q['sig'])])
+        emit('fgrad svc6', n, [ctx.fgrad(1, q['sig'])])
+        emit('fgrad_seq hill6', n, [ctx.fgrad_seq(0, q['sig'], ctx.seq(0, q['sig']))])
+        emit('fgrad_wh svc_wh', n, ctx.fgrad_wh(2, q['sig'], q['epl']))
+        emit('full_yf svc6, ld', n, ctx.full_yf(1, q['sig'], q['epl'], ld))
+        emit('full_yf svc_wh, ld', n, ctx.full_yf(2, q['sig'], q['epl'], ld))
+        plane = q['su'] * np.array([1., 1., 1., 0., 0., 1.])   # the closed form of the principal stresses on the device
+        emit_ys('yield_scale princ3 (analytic), plane and general states', n, ctx.yield_scale(3, np.vstack((plane, q['su']))))
+        mid = np.arange(n, dtype=np.int32) % 3
+        emit('response hill6 / svc6 / svc_wh', n, ctx.response(q['sig'], np.abs(q['epl']) * 0.01, q['deps'], mid, return_khard=True))
+        os.environ['PLFX_RESPONSE_ROW'] = '0'   # (read by every call) the 6-feature SVC points in the thread kernel
+        try:
+            emit('response, PLFX_RESPONSE_ROW=0', n, ctx.response(q['sig'], np.abs(q['epl']) * 0.01, q['deps'], mid, return_khard=True))
+        finally:
+            del os.environ['PLFX_RESPONSE_ROW']
+    with_context([hill6, hill, wh, princ3], fn)
+
+
+def child(more, pts=False):
     sys.path.insert(0, ROOT)
     import numpy as np
     import pylabfea_amd as FE
@@ -143,20 +257,22 @@ def child(more):
         assert fe._engine.precond_info()[0] == 1 and fe._engine.precond_info()[1] >= 2   # multigrid-PCG is what gave up
         assert fe._engine.solve_fallbacks() > 0 and fe._engine.indefinite_info()['by_gmres'] == 0   # ... Jacobi, not GMRES
         out.append(('32x32, multigrid capped at 2: Jacobi fall-back', d))
+    if pts:
+        points(out)
     for name, (d, its) in out:
         print('%s|%s|%s' % (name, d, ','.join(map(str, its))))
 
 
 if __name__ == '__main__':
-    more = '--more' in sys.argv
-    args = [a for a in sys.argv[1:] if a != '--more']
+    flags = [a for a in ('--more', '--points') if a in sys.argv]
+    args = [a for a in sys.argv[1:] if a not in flags]
     if args == ['--child']:
-        child(more)
+        child('--more' in flags, '--points' in flags)
         sys.exit(0)
     res = []
     for lib in args[:2]:
         env = dict(os.environ, PLFX_LIB=os.path.abspath(lib))
-        o = subprocess.run([sys.executable, os.path.abspath(__file__), '--child'] + (['--more'] if more else []), env=env,
+        o = subprocess.run([sys.executable, os.path.abspath(__file__), '--child'] + flags, env=env,
                            capture_output=True, text=True)
         if o.returncode:
             print(o.stdout, o.stderr)
