@@ -186,6 +186,33 @@ int plfx_committee_yf(plfx_ctx *ctx, int nmem, const int32_t *mats, const double
  * set when member k of the last such call had its tables staged in LDS (clear: read from device memory) */
 int plfx_committee_info(plfx_ctx *ctx, int64_t *launches, int32_t *staged_members);
 
+/* The texture-dependent SVC yield function (train_SVC on a txdat material, material.py:1186-1196,
+ * 2347-2361): an RBF C-SVC on 6 + tdim features [Voigt stress | texture descriptor], every column standardised,
+ * f_j = (x_j - mean[j]) / scale[j], the stress taken as its deviator first when dev_only.  A table set of its own, owned by the
+ * context: plfx_set_materials leaves it alone, a second call replaces it, nsv = 0 releases it, plfx_destroy frees it.
+ * sv[nsv*(6+tdim)] row-major, dual[nsv].  PLFX_ERR_ARG for tdim outside 1..10, a scale that is <= 0 or not finite,
+ * gamma <= 0, a non-finite table entry. */
+int plfx_tex_svc_set(plfx_ctx *ctx, int nsv, int tdim, const double *sv, const double *dual, double intercept, double gamma,
+                     const double *mean, const double *scale, int dev_only);
+/* yf[n] = calc_yf(sig_i, tex=) at n stresses sig[n*6] in one launch; tex[ntex*tdim] row-major.  The texture of point i is row
+ * tex_id[i] (each in 0..ntex-1); with tex_id NULL it is row 0 (ntex == 1, shared) or row i (ntex == n), anything else is
+ * PLFX_ERR_ARG.  A point's value does not depend on n, its place, or how its texture was addressed; a non-finite stress or
+ * texture component makes that point NaN and nothing else.  n = 0 is PLFX_OK with nothing launched; PLFX_ERR_STATE before
+ * plfx_tex_svc_set. */
+int plfx_tex_svc_yf(plfx_ctx *ctx, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *yf);
+/* Yield loci over textures: x[t*nray + r] with calc_yf(x su_r, tex_t) = 0 for nray unit stresses su[nray*6] and ntex textures
+ * tex[ntex*tdim], all ntex * nray rays in ONE launch, output texture-major.  x0: NULL or [ntex*nray] start values; NULL starts
+ * ray (t, r) at 1 / seq_J2(su_r), a J2 stress of one stress unit, so callers that know the yield strength pass x0.  The search
+ * and the status values are exactly those of plfx_yield_scale: march by 0.98 / 1.02 from x0 (caps 240 / 90), bisection to
+ * neighbouring doubles (cap 80); status 0 root found, 1 no bracket in [0.01 x0, 5 x0], 2 refinement cap reached, 3 degenerate
+ * ray (su = 0, a non-finite input, x0 <= 0 or not finite); x is NaN unless status is 0.  nray = 0 or ntex = 0 is PLFX_OK with
+ * nothing launched; PLFX_ERR_STATE before plfx_tex_svc_set. */
+int plfx_tex_svc_yield_scale(plfx_ctx *ctx, int nray, const double *su, int ntex, const double *tex, const double *x0, double *x,
+                             int32_t *status);
+/* the set (nsv = 0: none), launches of k_tex_yf / k_tex_yield_scale since it was set, and whether its tables are staged in LDS
+ * (0: read from device memory) */
+int plfx_tex_svc_info(plfx_ctx *ctx, int *nsv, int *tdim, int64_t *yf_launches, int64_t *ray_launches, int *staged);
+
 /* Index products of Model.mesh for the reference's structured NX x NY grid, computed on the host (no context, no GPU):
  * conn[NX*NY*4] = [n1, n1+1, n1+NnodeY, n1+NnodeY+1] with n1 = (ih / NY) * NnodeY + ih % NY for element ih = j*NY + k
  * (model.py:935-948); node sets noleft (j = 0), noright (j = NX), nobot (k = 0), notop (k = NY) in ascending node order
@@ -535,7 +562,7 @@ int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
- *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_committee_yf, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_committee_yf, plfx_tex_svc_yf, plfx_tex_svc_yield_scale, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

@@ -5,7 +5,8 @@ the per-element return mapping, the B^T D B assembly and the linear solve run as
 HIP kernels (gfx950) in ``libplfx.so`` behind the reference's own ``Model`` / ``Material`` API.
 See DESIGN.md for the scope table and INTEGRATION.md for the C-ABI.
 """
-from .basic import (Strain, Stress, eps_eq, sig_cyl2princ, sig_dev, sig_eq_j2, sig_polar_ang, sig_princ, sig_spherical_to_cartesian,
+from .basic import (Strain, Stress, eps_eq, sig_cyl2princ, sig_dev, sig_eq_j2, sig_polar_ang, sig_princ, sig_princ2cyl,
+                    sig_spherical_to_cartesian,
                     yf_tolerance)
 from .committee import Committee, active_learning, train_committee
 from .data import Data
@@ -17,4 +18,4 @@ from ._dist import host_transport
 __version__ = '0.1.0'
 __all__ = ['Data', 'Material', 'Model', 'host_transport', 'Stress', 'Strain', 'eps_eq', 'sig_dev', 'sig_eq_j2', 'sig_polar_ang', 'sig_princ',
            'yf_tolerance', 'sig_cyl2princ', 'load_cases', 'training_score', 'Committee', 'train_committee', 'active_learning',
-           'sig_spherical_to_cartesian']
+           'sig_spherical_to_cartesian', 'sig_princ2cyl']

@@ -63,6 +63,7 @@ SYMBOLS = [
     'plfx_svr_fit_batch', 'plfx_svr_predict_multi', 'plfx_set_svr_flow', 'plfx_svr_flow_info',
     'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info', 'plfx_yield_scale',
     'plfx_committee_yf', 'plfx_committee_info',
+    'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
 ]
 
 _lib = None
@@ -344,6 +345,61 @@ class Context(object):
         n, st = C.c_int64(), C.c_int32()
         self._chk(self.lib.plfx_committee_info(self.h, C.byref(n), C.byref(st)))
         return int(n.value), int(st.value)
+
+    # -- texture SVC: a table set of the context, independent of its materials
+    def tex_svc_set(self, sv, dual, intercept, gamma, mean, scale, dev_only=False):
+        """install the texture SVC: sv (nsv, 6 + tdim) standardised support vectors, dual (nsv,), the scaler's mean and
+        scale per column (plfx_tex_svc_set); sv=None releases the set"""
+        if sv is None:
+            self._chk(self.lib.plfx_tex_svc_set(self.h, 0, 0, None, None, C.c_double(0.), C.c_double(0.), None, None, 0))
+            return
+        sv = _f64(sv)
+        dual = _f64(dual).reshape(-1)
+        mean, scale = _f64(mean).reshape(-1), _f64(scale).reshape(-1)
+        if sv.ndim != 2 or len(dual) != len(sv) or len(mean) != sv.shape[1] or len(scale) != sv.shape[1]:
+            raise ValueError('tex_svc_set: sv (nsv, d), dual (nsv,), mean (d,) and scale (d,) expected')
+        self._chk(self.lib.plfx_tex_svc_set(self.h, len(sv), sv.shape[1] - 6, _dp(sv), _dp(dual), C.c_double(float(intercept)),
+                                            C.c_double(float(gamma)), _dp(mean), _dp(scale), int(bool(dev_only))))
+
+    def tex_svc_yf(self, sig, tex, tex_id=None):
+        """calc_yf(sig, tex=) of the texture SVC at N stresses sig (N,6) in one launch (plfx_tex_svc_yf): tex (T, tdim);
+        tex_id (N,) picks a row per point, None means one shared texture (T = 1) or one per point (T = N)"""
+        sig = _f64(sig).reshape(-1, 6)
+        tex = _f64(tex)
+        if tex.ndim != 2:
+            raise ValueError('tex_svc_yf: tex (T, tdim) expected')
+        tid = None if tex_id is None else _i32(tex_id).reshape(-1)
+        if tid is not None and len(tid) != len(sig):
+            raise ValueError('tex_svc_yf: one texture index per stress expected')
+        yf = np.empty(len(sig))
+        self._chk(self.lib.plfx_tex_svc_yf(self.h, len(sig), _dp(sig), len(tex), _dp(tex), _dp(tid), _dp(yf)))
+        return yf
+
+    def tex_svc_yield_scale(self, su, tex, x0=None):
+        """(x (T,N), status (T,N) int32): calc_yf(x[t, r] su_r, tex_t) = 0 for N unit stresses su (N,6) and T textures
+        tex (T, tdim), all T N rays searched in one launch (plfx_tex_svc_yield_scale); x0 (T,N) start values or None.
+        Status as in yield_scale."""
+        su = _f64(su).reshape(-1, 6)
+        tex = _f64(tex)
+        if tex.ndim != 2:
+            raise ValueError('tex_svc_yield_scale: tex (T, tdim) expected')
+        T, N = len(tex), len(su)
+        if x0 is not None:
+            x0 = _f64(x0)
+            if x0.shape != (T, N):
+                raise ValueError('tex_svc_yield_scale: x0 of shape (T, N) expected')
+        x = np.empty((T, N))
+        st = np.zeros((T, N), dtype=np.int32)
+        self._chk(self.lib.plfx_tex_svc_yield_scale(self.h, N, _dp(su), T, _dp(tex), _dp(x0), _dp(x), _dp(st)))
+        return x, st
+
+    def tex_svc_info(self):
+        """dict(nsv, tdim, yf_launches, ray_launches, staged) of the texture SVC of this context (nsv = 0: none)"""
+        nsv, td, st = C.c_int(), C.c_int(), C.c_int()
+        ny, nr = C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_tex_svc_info(self.h, C.byref(nsv), C.byref(td), C.byref(ny), C.byref(nr), C.byref(st)))
+        return dict(nsv=int(nsv.value), tdim=int(td.value), yf_launches=int(ny.value), ray_launches=int(nr.value),
+                    staged=bool(st.value))
 
     def yf(self, mat, sig, epl=None):
         sig = _f64(sig).reshape(-1, 6)

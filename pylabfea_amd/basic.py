@@ -124,6 +124,24 @@ def sig_cyl2princ(s_cyl):
     return sp[0] if single else sp
 
 
+def sig_princ2cyl(sig, mat=None):
+    """Cylindrical stresses (seq, theta, p) of principal (3,)/(N,3) or Voigt (6,)/(N,6) stresses (basic.py:236-277): the
+    equivalent stress -- J2, or ``mat.calc_seq`` of the stress when a material is given --, the polar angle in the
+    deviatoric plane and the hydrostatic stress.  Voigt stresses go through ``sig_princ``."""
+    s, single = _as2d(sig, 'sig_princ2cyl')
+    if s.shape[1] == 3:
+        sp = s
+        sv = np.concatenate((s, np.zeros((len(s), 3))), axis=1)
+    else:
+        sp = sig_princ(s)[0].reshape(-1, 3)
+        sv = s
+    sc = np.zeros((len(s), 3))
+    sc[:, 0] = sig_eq_j2(sp) if mat is None else mat.calc_seq(sv)
+    sc[:, 1] = sig_polar_ang(sp)
+    sc[:, 2] = np.sum(sp, axis=1) / 3.
+    return sc[0] if single else sc
+
+
 def sig_spherical_to_cartesian(angles, seq=1.0):
     """Voigt stress (6,) of norm ``seq`` from 5 spherical angles in radians (basic.py:280-301): x1 = cos a0,
     x2 = sin a0 cos a1, ..., x6 = sin a0 sin a1 sin a2 sin a3 sin a4, the products taken from the left as there.

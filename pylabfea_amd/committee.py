@@ -35,13 +35,15 @@ class Committee(object):
     array, or None for the example's ``0.5 * m.sy``.
 
     ValueError for an untrained member, a member with sdim = 3, a work-hardening member, a member with ``ML_grad`` set, and
-    for 0 or more than 16 members."""
+    for 0 or more than 16 members; NotImplementedError for a texture material."""
 
     def __init__(self, members, scale=None):
         members = list(members)
         if not 1 <= len(members) <= MAX_MEMBERS:
             raise ValueError('Committee: %d members, 1 to %d are supported' % (len(members), MAX_MEMBERS))
         for k, m in enumerate(members):
+            if isinstance(m, Material) and getattr(m, 'txdat', False):
+                m._tex_refuse('Committee')
             if not isinstance(m, Material) or not m.ML_yf or m.svc is None:
                 raise ValueError('Committee: member %d has no trained SVC yield function' % k)
             if m.sdim != 6:

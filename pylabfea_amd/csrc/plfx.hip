@@ -11,6 +11,7 @@
 #include "../../include/plfx.h"
 #include "plfx_kernels.hpp"
 #include "plfx_mg.hpp"
+#include "plfx_tex.hpp"
 
 #include <dlfcn.h>
 #include <algorithm>
@@ -147,6 +148,11 @@ struct plfx_ctx {
     int n_noflow = 0;            // materials without a flow rule (Tresca, Barlat without the native normal)
     int64_t committee_launches = 0;   // k_committee_yf launches of this context (plfx_committee_info)
     int32_t committee_staged = 0;     // bit k: member k of the last plfx_committee_yf call had its tables staged in LDS
+    // texture SVC (plfx_tex_svc_set): a table set of its own, owned by the context; plfx_set_materials leaves it alone
+    TexSvcPar tex = {};               // tex.nsv == 0: no set
+    double *tex_sv = nullptr, *tex_dual = nullptr;   // [nsv * tex_stride(tex_nfp)] padded vectors, [nsv] coefficients
+    int tex_nfp = 0;                  // padded feature slots of the set: 8, 12 or 16
+    int64_t tex_yf_launches = 0, tex_ray_launches = 0;
     int svc_lds_need = 0;
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
@@ -1811,6 +1817,8 @@ void plfx_destroy(plfx_ctx *c)
     }
     free_mesh(c);
     free_materials(c);
+    dfree(c->tex_sv);
+    dfree(c->tex_dual);
     dfree(c->part);
     dfree(c->part_g);
     dfree(c->sc);
@@ -2478,6 +2486,193 @@ int plfx_committee_info(plfx_ctx *c, int64_t *launches, int32_t *staged_members)
     if (!c) return PLFX_ERR_ARG;
     if (launches) *launches = c->committee_launches;
     if (staged_members) *staged_members = c->committee_staged;
+    return PLFX_OK;
+}
+
+// ------------------------------------------------------------------------------ texture SVC
+// The set: vectors padded to NFP = 8 / 12 / 16 slots at a row stride of NFP + 2 doubles (plfx_tex.hpp), coefficients, the
+// scaler's mean and scale per column.  nsv = 0 releases the set; a second call replaces it.
+int plfx_tex_svc_set(plfx_ctx *c, int nsv, int tdim, const double *sv, const double *dual, double intercept, double gamma,
+                     const double *mean, const double *scale, int dev_only)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (nsv < 0) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: nsv = %d", nsv);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (nsv == 0) {
+        HIPCHK(c, stream_sync(c));
+        dfree(c->tex_sv);
+        dfree(c->tex_dual);
+        c->tex = TexSvcPar();
+        c->tex_nfp = 0;
+        c->tex_yf_launches = c->tex_ray_launches = 0;
+        return PLFX_OK;
+    }
+    if (tdim < 1 || tdim > TEX_TMAX)
+        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: tdim = %d texture coefficients, 1 <= tdim <= %d supported", tdim, TEX_TMAX);
+    if (!sv || !dual || !mean || !scale) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: null argument");
+    if (!(gamma > 0.) || !std::isfinite(gamma)) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: gamma must be > 0 (got %g)", gamma);
+    if (!std::isfinite(intercept)) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: the intercept is not finite");
+    const int d = 6 + tdim, nfp = d <= 8 ? 8 : d <= 12 ? 12 : 16, st = tex_stride(nfp);
+    if ((int64_t)nsv * (st + 1) > INT32_MAX) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: nsv = %d is too large", nsv);
+    TexSvcPar P = {};
+    for (int j = 0; j < TEX_DMAX; j++) P.mean[j] = 0., P.scale[j] = 1.;
+    for (int j = 0; j < d; j++) {
+        if (!(scale[j] > 0.) || !std::isfinite(scale[j]))
+            return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: scale of column %d must be finite and > 0 (got %g)", j, scale[j]);
+        if (!std::isfinite(mean[j])) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: mean of column %d is not finite", j);
+        P.mean[j] = mean[j], P.scale[j] = scale[j];
+    }
+    std::vector<double> tab((size_t)nsv * st, 0.);
+    for (int k = 0; k < nsv; k++) {
+        if (!std::isfinite(dual[k])) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: coefficient %d is not finite", k);
+        for (int j = 0; j < d; j++) {
+            const double v = sv[(size_t)k * d + j];
+            if (!std::isfinite(v)) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: vector %d holds a non-finite value", k);
+            tab[(size_t)k * st + j] = v;
+        }
+    }
+    P.gamma = gamma, P.intercept = intercept, P.nsv = nsv, P.tdim = tdim, P.dev_only = dev_only ? 1 : 0;
+    P.staged = (int64_t)nsv * (st + 1) <= c->lds_doubles ? 1 : 0;
+    HIPCHK(c, stream_sync(c));   // no launch of the previous set is in flight when its tables go
+    c->tex = TexSvcPar();
+    c->tex_nfp = 0;
+    if (int rc = dalloc(c, &c->tex_sv, tab.size())) return rc;
+    if (int rc = dalloc(c, &c->tex_dual, (size_t)nsv)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->tex_sv, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->tex_dual, dual, (size_t)nsv * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, stream_sync(c));
+    if (P.staged) {
+        const int bytes = nsv * (st + 1) * 8;
+        HIPCHK(c, set_dyn_lds((const void *)k_tex_yf<8>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_tex_yf<12>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_tex_yf<16>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_tex_yield_scale<8>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_tex_yield_scale<12>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_tex_yield_scale<16>, bytes));
+    }
+    c->tex = P;
+    c->tex_nfp = nfp;
+    c->tex_yf_launches = c->tex_ray_launches = 0;
+    return PLFX_OK;
+}
+
+static size_t tex_lds_bytes(const plfx_ctx *c)
+{
+    return c->tex.staged ? (size_t)c->tex.nsv * (tex_stride(c->tex_nfp) + 1) * 8 : 0;
+}
+
+// calc_yf(sig, tex=) of the set at n points, one launch of k_tex_yf
+int plfx_tex_svc_yf(plfx_ctx *c, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *yf)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (c->tex.nsv == 0) return fail(c, PLFX_ERR_STATE, "plfx_tex_svc_yf: plfx_tex_svc_set first");
+    if (n < 0 || n > INT32_MAX / 2 || (n > 0 && (!sig || !tex || !yf || ntex < 1)))
+        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yf: bad argument");
+    if (n == 0) return PLFX_OK;
+    if (!tex_id && ntex != 1 && ntex != n)
+        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yf: %d textures for %d points; without tex_id one shared texture or one per "
+                    "point is expected", ntex, n);
+    if (tex_id)
+        for (int i = 0; i < n; i++)
+            if (tex_id[i] < 0 || tex_id[i] >= ntex)
+                return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yf: tex_id[%d] = %d, the call holds %d textures", i, tex_id[i], ntex);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = n, td = c->tex.tdim;
+    CallBuffers B;
+    double *dsig = nullptr, *dtex = nullptr, *dyf = nullptr;
+    int32_t *did = nullptr;
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
+    if (tex_id)
+        if (int rc = B.put(c, &did, tex_id, N)) return rc;
+    if (int rc = B.get(c, &dyf, N)) return rc;
+    const int block = row16_block(c, n, TEX_BLOCK), rpb = block / 16;
+    const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 8 * c->prop.multiProcessorCount)));
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+#define TEX_LAUNCH(NFP)                                                                                                  \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yf<NFP>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,           \
+                       (const double *)c->tex_sv, (const double *)c->tex_dual, n, (const double *)dsig, ntex,            \
+                       (const double *)dtex, (const int32_t *)did, dyf)
+    if (c->tex_nfp == 8)
+        TEX_LAUNCH(8);
+    else if (c->tex_nfp == 12)
+        TEX_LAUNCH(12);
+    else
+        TEX_LAUNCH(16);
+#undef TEX_LAUNCH
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->tex_yf_launches++;
+    HIPCHK(c, hipMemcpyAsync(yf, dyf, N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+// yield_scale(su, tex=) of the set: ntex x nray rays, texture-major, one launch of k_tex_yield_scale.  x0 NULL: the search of
+// ray (t, r) starts at 1 / seq_J2(su_r), the factor that brings the ray to a J2 stress of one stress unit
+int plfx_tex_svc_yield_scale(plfx_ctx *c, int nray, const double *su, int ntex, const double *tex, const double *x0, double *x,
+                             int32_t *status)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (c->tex.nsv == 0) return fail(c, PLFX_ERR_STATE, "plfx_tex_svc_yield_scale: plfx_tex_svc_set first");
+    if (nray < 0 || ntex < 0 || (int64_t)nray * ntex > INT32_MAX / 2)
+        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yield_scale: bad argument");
+    if (nray == 0 || ntex == 0) return PLFX_OK;
+    if (!su || !tex || !x || !status) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yield_scale: null argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int nq = nray * ntex;
+    const size_t Q = nq, td = c->tex.tdim;
+    std::vector<double> start;
+    if (!x0) {
+        start.resize(Q);
+        for (int r = 0; r < nray; r++) {
+            const double *s = su + 6 * (size_t)r;
+            const double d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
+            const double sj2 = std::sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3. * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]));
+            for (int t = 0; t < ntex; t++) start[(size_t)t * nray + r] = 1. / sj2;   // (sj2 = 0: inf, status 3)
+        }
+    }
+    CallBuffers B;
+    double *dsu = nullptr, *dtex = nullptr, *dx0 = nullptr, *dx = nullptr;
+    int32_t *dst = nullptr;
+    if (int rc = B.put(c, &dsu, su, 6 * (size_t)nray)) return rc;
+    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
+    if (int rc = B.put(c, &dx0, x0 ? x0 : start.data(), Q)) return rc;
+    if (int rc = B.get(c, &dx, Q)) return rc;
+    if (int rc = B.get(c, &dst, Q)) return rc;
+    const int block = row16_block(c, nq, TEX_BLOCK), rpb = block / 16;
+    const dim3 grid(std::max(1, std::min((nq + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+#define TEX_LAUNCH(NFP)                                                                                                    \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yield_scale<NFP>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,    \
+                       (const double *)c->tex_sv, (const double *)c->tex_dual, nray, (const double *)dsu, ntex,            \
+                       (const double *)dtex, (const double *)dx0, dx, dst)
+    if (c->tex_nfp == 8)
+        TEX_LAUNCH(8);
+    else if (c->tex_nfp == 12)
+        TEX_LAUNCH(12);
+    else
+        TEX_LAUNCH(16);
+#undef TEX_LAUNCH
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->tex_ray_launches++;
+    HIPCHK(c, hipMemcpyAsync(x, dx, Q * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, dst, Q * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+int plfx_tex_svc_info(plfx_ctx *c, int *nsv, int *tdim, int64_t *yf_launches, int64_t *ray_launches, int *staged)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (nsv) *nsv = c->tex.nsv;
+    if (tdim) *tdim = c->tex.tdim;
+    if (yf_launches) *yf_launches = c->tex_yf_launches;
+    if (ray_launches) *ray_launches = c->tex_ray_launches;
+    if (staged) *staged = c->tex.staged;
     return PLFX_OK;
 }
 

@@ -1,5 +1,6 @@
-"""Stress-strain data for training work-hardening SVC yield functions (pylabfea/data.py of the reference, the part without
-texture descriptors), in NumPy only: no SciPy, no scikit-learn.
+"""Stress-strain data for training SVC yield functions with work hardening or texture (pylabfea/data.py of the reference;
+of its texture descriptors the GSH coefficients, not the PCA-reduced address vectors), in NumPy only: no SciPy, no
+scikit-learn.
 
 ``Data`` reads a JSON database of virtual or physical mechanical tests (both record layouts of the reference), takes
 load-case dictionaries as ``examples/train_hardening.py`` builds them, or yield stresses alone, and leaves in
@@ -12,7 +13,7 @@ import warnings
 
 import numpy as np
 
-from .basic import eps_eq, sig_eq_j2
+from .basic import eps_eq, sig_eq_j2, sig_princ
 
 _COMP = ('11', '22', '33', '23', '13', '12')
 
@@ -116,15 +117,22 @@ class Data(object):
     'Stress', 'Eq_Stress', 'Strain_Plastic', 'Eq_Strain_Plastic', 'Strain_Total'), or an (N, sdim) array of yield
     stresses.  ``mat_data`` then holds, among others, ``flow_stress`` / ``plastic_strain`` (the training data of
     work hardening), ``sig_ideal`` (stresses at yield onset), ``sy_av``, ``elast_const``, ``epc``, ``peeq_max`` and
-    ``Nlc``.  Texture descriptors (``tx_data=True``) and plotting are not supported."""
+    ``Nlc``.  With ``tx_data=True`` and ``tx_descriptor='GSH_n'`` (n = 3, 7, 12 or 37) a JSON database's ``Texture`` entry
+    gives ``texture`` (its ``gsh_coeff_reconstructed_random[1:1 + n]``) and ``tdim = n`` (data.py:522-545); the address-vector
+    descriptors ``ADV_*`` (reduced by a PCA in training) and ``VF`` (not implemented in the reference either) are refused,
+    and so is plotting."""
 
     def __init__(self, source, path_data='./', name='Dataset', mat_name="Simulanium", sdim=6, epl_crit=None,
                  epl_start=None, epl_max=None, depl=0., plot=False, wh_data=True, tx_data=False,
                  texture_name='Random', tx_descriptor='GSH_3', mode='RS'):
         if sdim != 3 and sdim != 6:
             raise ValueError('Value of sdim must be either 3 or 6')
+        self._gsh_dim = None
         if tx_data:
-            raise NotImplementedError('Data: texture descriptors (tx_data=True) are not supported')
+            self._gsh_dim = self._descriptor_dim(tx_descriptor)
+            if not isinstance(source, str):
+                raise NotImplementedError('Data: tx_data=True needs a JSON database with a "Texture" entry; stress arrays '
+                                          'and load-case dictionaries carry no texture descriptor')
         if plot:
             raise NotImplementedError('Data: plotting is not supported')
         self.lc_data = None
@@ -144,6 +152,33 @@ class Data(object):
             self.convert_data(np.array(source))
         else:
             raise ValueError('Only sources of type "str" or "dict" are supported.')
+
+    @staticmethod
+    def _descriptor_dim(tx_descriptor):
+        """number of GSH coefficients of a descriptor name 'GSH_n' (data.py:531-537); other descriptors are refused"""
+        tx_descriptor = str(tx_descriptor)
+        if 'GSH' in tx_descriptor:
+            gsh_dim = int(tx_descriptor.split('_')[-1])
+            if gsh_dim not in (3, 7, 12, 37):
+                raise ValueError(f"GSH with {gsh_dim} not valid. Must be 3, 7, 12, ")
+            return gsh_dim
+        if 'ADV' in tx_descriptor:
+            raise NotImplementedError('Data: address-vector descriptors (%s) are reduced by a PCA in the reference\'s '
+                                      'training, which is not supported; use GSH_3, GSH_7, GSH_12 or GSH_37' % tx_descriptor)
+        if tx_descriptor == 'VF':
+            raise NotImplementedError('Data: the volume-fraction descriptor VF is not implemented (nor is it in the reference)')
+        raise ValueError('Data: unknown texture descriptor %r; GSH_3, GSH_7, GSH_12 or GSH_37 expected' % tx_descriptor)
+
+    def _seq(self, sig):
+        """J2 equivalent stress of Voigt stresses.  Data sets with texture descriptors are stacked by train_SVC into rows
+        that are held to the reference's bit for bit, so for them the reference's own form is taken: through the principal
+        stresses of ``sig_princ`` (the same LAPACK call), which rounds differently from the direct Voigt form in the last
+        place."""
+        if self.mat_data['tx_data']:
+            sig = np.asarray(sig, dtype=float)
+            sp = sig_princ(sig)[0]
+            return sig_eq_j2(sp)
+        return sig_eq_j2(sig)
 
     def key_parser(self, key):
         parameters = key.split('_')
@@ -198,7 +233,12 @@ class Data(object):
             if key == 'Texture':
                 self.mat_data['tx_name'] = val['name']
                 self.mat_data['tx_index'] = val.get('texture_index', 0)
-                warnings.warn("WARNING: tx_data was set to false. I will just include qualitative texture info.")
+                if not self.mat_data['tx_data']:
+                    warnings.warn("WARNING: tx_data was set to false. I will just include qualitative texture info.")
+                else:
+                    self.mat_data['texture'] = np.array(val['gsh_coeff_reconstructed_random'],
+                                                        dtype=float)[1:1 + self._gsh_dim]
+                    self.mat_data['tdim'] = len(self.mat_data['texture'])
                 continue
             if 'Results' in val.keys():
                 res = val['Results']
@@ -228,7 +268,7 @@ class Data(object):
                 strain_t = np.array(tens).T
                 strain_p = np.array(self._layout(val['plastic_strain'], tens)).T if "plastic_strain" in val.keys() \
                     else None
-            seq_full = sig_eq_j2(stress)
+            seq_full = self._seq(stress)
             if strain_p is not None:
                 peeq_plastic = eps_eq(strain_p)
                 e_plastic = True
@@ -327,7 +367,7 @@ class Data(object):
             idx = i_ideal[-1]
             s_crit = interpolate_stress(s0=val['Eq_Stress'][idx], s1=val['Eq_Stress'][idx + 1], e0=peeq[idx],
                                         e1=peeq[idx + 1], et=epc_lc)
-            sig_ideal.append(val['Stress'][idx] * s_crit / sig_eq_j2(val['Stress'][idx]))
+            sig_ideal.append(val['Stress'][idx] * s_crit / self._seq(val['Stress'][idx]))
             if peeq[ipl[-1]] > peeq_max:
                 peeq_max = peeq[ipl[-1]]
             eps = -depl
@@ -348,7 +388,7 @@ class Data(object):
                 self.mat_data['tx_key'] = 'unknown'
             ct += 1
         C = get_elastic_coefficients(elstrain, elstress, method='least_square')
-        sy_av = np.mean(sig_eq_j2(np.array(sig_ideal)))
+        sy_av = np.mean(self._seq(np.array(sig_ideal)))
         nreal = Nlc - Ncyl
         md = self.mat_data
         md['flow_stress'] = np.array(sig)

@@ -7,8 +7,10 @@ the path named by BASELINE.json: ``elasticity`` (:2401), ``plasticity`` (:2466),
 (:974), ``epl_dot`` (:1009), ``C_tan`` (:1057) and the test harness ``calc_properties`` (:3062).
 Same names, argument meaning and error behaviour; arguments are never mutated.
 
-Out of scope here: data import, plotting, texture/work-hardening features.  What the yield-locus plots
-compute comes back as arrays (``yield_scale``, ``polar_yield_locus``, ``polar_field``, ``yield_slices``).
+Out of scope here: plotting.  What the yield-locus plots compute comes back as arrays (``yield_scale``,
+``polar_yield_locus``, ``polar_field``, ``yield_slices``; ``texture_loci`` for a texture material, §28).
+Texture materials (``from_data`` on data sets with ``tx_data``) are trained and evaluated as yield functions --
+``train_SVC``, ``calc_yf``, ``find_yloc``, ``yield_scale``, ``texture_loci`` -- and, like in the reference, nothing past that.
 A trained SVC enters through
 :meth:`Material.train_SVC` (trained on the GPU), :meth:`Material.set_svc` or :meth:`Material.from_sklearn`.
 sdim=3 flow rules use the reference's axis-tracking principal stresses (exact for plane states);
@@ -264,6 +266,7 @@ class Material(object):
         scale_wh, C22, C33, C13, C23, C55, C66, dev_only flag, Nset, scale_text), dual coefficients from slot 29,
         then the support vectors row by row -- and ``file-svm_meta.json``."""
         import datetime, getpass, json, platform
+        self._tex_refuse('export_MLparam')
         if not self.ML_yf:
             raise AttributeError('export_MLparam: No ML flow rule defined.')
         if descr is not None and param is not None and len(descr) != len(param):
@@ -372,6 +375,7 @@ class Material(object):
         if self.sy is None:
             return _lib.pack_material(_lib.ELASTIC, CV, E=self.E, nu=self.nu)
         if self.ML_yf and not ana:
+            self._tex_refuse('Model.assign')
             svc = dict(sv=self.svc['sv'], dual=self.svc['dual'], intercept=self.svc['intercept'],
                        gamma=self.gam_yf, scale_seq=self.scale_seq, dev_only=self.dev_only,
                        scale_wh=getattr(self, 'scale_wh', None))
@@ -399,6 +403,88 @@ class Material(object):
         self.barlat_normal = bool(on)
         self._version += 1
         return self
+
+    # ------------------------------------------------------------------ texture materials
+    # what the reference does where this engine refuses a texture material
+    _TEX_REFUSALS = {
+        'calc_fgrad': 'the reference raises AttributeError there (self.self.scale_seq, material.py:811)',
+        'ML_full_yf': "the reference raises ValueError there: its calls of calc_yf pass no texture (material.py:475-491)",
+        'response': 'the reference raises ValueError in its first calc_yf call, which passes no texture (material.py:252)',
+        'response_batch': 'the reference has no response for a texture material: its calc_yf calls pass no texture (material.py:252)',
+        'calc_hessian': 'the reference rescales the Hessian of the scaler-standardised features by 1 / scale_seq**2, and '
+                        'scale_seq is not a feature scale of a texture material (material.py:952-960)',
+        'calc_properties': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343)',
+        'setup_fgrad_SVM': 'the reference needs work-hardening data, which a texture material cannot carry here',
+        'export_MLparam': "the reference's file has no slots for the scaler's mean and scale (material.py:2130-2271)",
+        'polar_yield_locus': 'the reference\'s polar_plot_yl calls find_yloc without a texture and raises ValueError '
+                             '(material.py:3292); texture_loci traces the loci',
+        'yield_slices': "the reference's plot_yield_locus calls calc_yf without a texture and raises ValueError (material.py:3017)",
+        'Committee': 'the reference example forms committees of texture-free yield functions only',
+        'Model.assign': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343)',
+    }
+
+    def _is_tex(self):
+        """a texture material: txdat set by from_data, msparam still the one it installed"""
+        ms = getattr(self, 'msparam', None)
+        return bool(getattr(self, 'txdat', False)) and ms is not None and getattr(self, '_tex_from_data', None) is ms
+
+    def _tex_refuse(self, what):
+        if getattr(self, 'txdat', False):
+            raise NotImplementedError('%s: not offered for a texture material (txdat); %s'
+                                      % (what, self._TEX_REFUSALS.get(what, 'the reference does not support it either')))
+
+    def _tex_rows(self, tex, n, name):
+        """tex as calc_yf takes it -- (tdim,) or (N, tdim) -- as a C-contiguous (1, tdim) or (n, tdim) array"""
+        t = np.asarray(tex, dtype=float)
+        if t.ndim == 1:
+            t = t[None, :]
+        if t.ndim != 2 or t.shape[1] != self.tdim or len(t) not in (1, n):
+            raise ValueError('%s: tex must be (%d,) or (N, %d) with one row per stress; got shape %s'
+                             % (name, self.tdim, self.tdim, np.shape(tex)))
+        return np.ascontiguousarray(t)
+
+    def _tex_key(self):
+        """digest of the tables the device evaluates for the texture SVC (cf. _content_key)"""
+        h = hashlib.blake2b(b'tex_svc', digest_size=16)
+        sc = self.std_scaler
+        for a in (self.svc['sv'], self.svc['dual'], sc.mean_, sc.scale_,
+                  np.array([self.svc['intercept'], self.gam_yf, 1. if self.dev_only else 0.])):
+            h.update(_table_digest(np.ascontiguousarray(a, dtype=float).reshape(-1)))
+        return h.digest()
+
+    def _load_tex(self):
+        """Make the texture SVC the table set of the shared point context; re-sent only when its content differs."""
+        if not self.ML_yf or self.svc is None or getattr(self, 'std_scaler', None) is None:
+            raise AttributeError('texture material has no trained ML yield function; train_SVC trains it')
+        ctx = _ctx()
+        key = self._tex_key()
+        if getattr(ctx, '_tex_key', None) != key:
+            ctx._tex_key = None
+            ctx.tex_svc_set(self.svc['sv'], self.svc['dual'], self.svc['intercept'], self.gam_yf, self.std_scaler.mean_,
+                            self.std_scaler.scale_, dev_only=self.dev_only)
+            ctx._tex_key = key
+        return ctx
+
+    def set_tex_svc(self, support_vectors, dual_coef, intercept, gamma, mean, scale, dev_only=False, C=None):
+        """Install a trained texture SVC on a material that ``from_data`` made a texture material: standardised support
+        vectors (nsv, 6 + tdim), ``dual_coef_[0]``, ``intercept_[0]``, gamma and the scaler's ``mean_`` / ``scale_`` (what
+        ``train_SVC`` leaves in ``svm_yf`` and ``std_scaler``)."""
+        if not self._is_tex():
+            raise ValueError('set_tex_svc: from_data must have installed texture data sets first')
+        sv = np.ascontiguousarray(support_vectors, dtype=float)
+        dual = np.ascontiguousarray(dual_coef, dtype=float).reshape(-1)
+        mean, scale = np.array(mean, dtype=float).reshape(-1), np.array(scale, dtype=float).reshape(-1)
+        if sv.ndim != 2 or sv.shape[1] != self.Ndof or len(dual) != len(sv) or len(mean) != self.Ndof or len(scale) != self.Ndof:
+            raise ValueError('set_tex_svc: support vectors (nsv, %d), dual_coef (nsv,), mean and scale (%d,) expected'
+                             % (self.Ndof, self.Ndof))
+        sc = StdScaler.__new__(StdScaler)
+        sc.mean_, sc.scale_, sc.var_, sc.n_samples_seen_ = mean, scale, scale ** 2, None
+        self.std_scaler = sc
+        self.svc = dict(sv=sv, dual=dual, intercept=float(intercept))
+        self.gam_yf, self.C_yf = float(gamma), C
+        self.dev_only = bool(dev_only)
+        self.ML_yf = True
+        self._version += 1
 
     def _no_flow_rule(self):
         if self.barlat and not getattr(self, 'barlat_normal', False):
@@ -559,8 +645,19 @@ class Material(object):
         work-hardening features — the ones this engine evaluates): principal-stress cylinder coordinates for sdim=3,
         (deviatoric) Voigt stress / scale_seq for sdim=6.  Host-side helper for scripts; the kernels build the same
         features in registers."""
+        if self._is_tex():   # material.py:2347-2361 (no PCA): unscaled features through the fitted scaler
+            if tex is None:
+                raise ValueError('create_scaled_input: a texture material needs tex')
+            if getattr(self, 'std_scaler', None) is None:
+                raise AttributeError('create_scaled_input: no scaler fitted; train_SVC fits it')
+            s, _ = self._voigt(sig, 'create_scaled_input')
+            x = np.zeros((len(s), self.Ndof))
+            x[:, 0:6] = sig_dev(s) if self.dev_only else s
+            x[:, self.ind_tx:] = self._tex_rows(tex, len(s), 'create_scaled_input')
+            return self.std_scaler.transform(x)
         if tex is not None or getattr(self, 'txdat', False):
-            raise NotImplementedError('create_scaled_input: texture features are outside this engine')
+            raise NotImplementedError('create_scaled_input: texture features need a texture material (from_data on data '
+                                      'sets with tx_data)')
         s, _ = self._voigt(sig, 'create_scaled_input')
         x = np.zeros((len(s), self.Ndof))
         if self.sdim == 3:
@@ -583,9 +680,26 @@ class Material(object):
         peeq = epl if type(epl) in (float, np.float64) else eps_eq(epl)
         return self.sy + peeq * self.khard
 
-    def calc_yf(self, sig, epl=None, ana=False, pred=False, **kw):
-        """Yield function: analytic ``calc_seq - sflow`` or the SVC decision function (material.py:348-412)."""
+    def calc_yf(self, sig, epl=None, ana=False, pred=False, tex=None, **kw):
+        """Yield function: analytic ``calc_seq - sflow`` or the SVC decision function (material.py:348-412).  A texture
+        material takes ``tex``, one descriptor (tdim,) or one per stress (N, tdim), and raises the reference's ValueError
+        without it."""
         s, single = self._voigt(sig, 'calc_yf')
+        if self.ML_yf and not ana and getattr(self, 'txdat', False):
+            if tex is None:
+                raise ValueError("SVM is trained on texture data but no texture data is given to evaluate yf!")
+            if not self._is_tex():
+                self._svc_refuse('calc_yf')
+            t = self._tex_rows(tex, len(s), 'calc_yf')
+            f = self._load_tex().tex_svc_yf(s, t)
+            if pred:   # svm_yf.predict: decision >= 0 -> +1 (libsvm)
+                f = np.where(f >= 0., 1., -1.)
+                self.msg['yield_fct'] = 'ML_yf-predict'
+            else:
+                self.msg['yield_fct'] = 'ML_yf-decision-fct'
+            return f[0] if single else f
+        if tex is not None and not (getattr(self, 'txdat', False)):
+            raise NotImplementedError('calc_yf: tex needs a texture material (from_data on data sets with tx_data)')
         if epl is None:
             e = np.zeros((len(s), 6))
         elif type(epl) in (float, np.float64):
@@ -606,21 +720,26 @@ class Material(object):
             self.msg['yield_fct'] = 'analytical'
         return f[0] if single else f
 
-    def find_yloc(self, x, su, epl=None, **kw):
+    def find_yloc(self, x, su, epl=None, tex=None, **kw):
         """Yield function at ``sig = x[:, None] * su`` for N unit stresses at once (material.py:518-545): the objective
         that the reference's training / plotting scripts hand to ``scipy.optimize.fsolve`` to trace yield loci
         (``plot_yield_locus`` :3017, ``calc_yf`` on (N, sdim) grids); one batched GPU evaluation per call."""
+        if getattr(self, 'txdat', False) and tex is None:
+            raise ValueError("SVM is trained on texture data but no texture data was provided to this function.")
         x = np.asarray(x, dtype=float)
         su = np.asarray(su, dtype=float)
-        return self.calc_yf(x[:, None] * su, epl=epl)
+        return self.calc_yf(x[:, None] * su, epl=epl, tex=tex)
 
-    def find_yloc_scalar(self, x, su, epl=None, **kw):
+    def find_yloc_scalar(self, x, su, epl=None, tex=None, **kw):
         """scalar form of `find_yloc` (material.py:547-574): ``calc_yf(x * su)``"""
-        return self.calc_yf(float(x) * np.asarray(su, dtype=float), epl=epl)
+        if getattr(self, 'txdat', False) and tex is None:
+            raise ValueError("SVM is trained on texture data but no texture data was provided to this function.")
+        return self.calc_yf(float(x) * np.asarray(su, dtype=float), epl=epl, tex=tex)
 
     def ML_full_yf(self, sig, epl=None, ld=None, verb=True, **kw):
         """Distance of a stress to the ML yield locus along its ray / the loading direction
         (material.py:414-516).  Accepts a single stress like the reference, or (N,6)."""
+        self._tex_refuse('ML_full_yf')
         if not self.ML_yf:
             raise AttributeError('ML_full_yf: material has no trained ML yield function')
         s = np.asarray(sig, dtype=float)
@@ -641,6 +760,8 @@ class Material(object):
 
     def calc_fgrad(self, sig, epl=None, seq=None, ana=False, **kw):
         """Gradient of the yield function w.r.t. stress (material.py:704-858)."""
+        if self.ML_yf and not ana:
+            self._tex_refuse('calc_fgrad')
         s0 = np.asarray(sig, dtype=float)
         if epl is not None and np.shape(epl) != s0.shape:
             raise ValueError('Parameter sig and epl must have the same shape.')
@@ -693,6 +814,7 @@ class Material(object):
         strain direction eps / peeq and one for the local hardening rate d seq / d peeq, all with C_yf, gam_yf,
         epsilon 0.01 and tol 1e-4, fitted in one batched call on the GPU (libsvm's epsilon-SVR without shrinking).  Sets
         svm_grad0 .. svm_grad5, svm_khard, sc_feat, sc_grad, sc_khard and ML_grad = True."""
+        self._tex_refuse('setup_fgrad_SVM')
         if not getattr(self, 'whdat', False):
             raise ValueError('No strain hardening data available.')
         if not self._msparam_ok():
@@ -760,8 +882,9 @@ class Material(object):
         like the reference, no chain rule through the deviator projection is applied.  Analytic yield functions have no
         Hessian in the reference (``ValueError``), nor have sdim = 3 ML materials (``NotImplementedError``).
         Unlike ``calc_fgrad`` this touches neither ``khard`` nor ``msg``."""
-        if tex is not None or getattr(self, 'txdat', False):
-            raise NotImplementedError('calc_hessian: texture features are outside this engine')
+        self._tex_refuse('calc_hessian')
+        if tex is not None:
+            raise NotImplementedError('calc_hessian: texture features are outside this engine; ' + self._TEX_REFUSALS['calc_hessian'])
         if getattr(self, 'ML_grad', False) and not ana:
             raise NotImplementedError('calc_hessian: analytical gradient for SVR not implemented')
         s = np.asarray(sig, dtype=float)
@@ -807,6 +930,7 @@ class Material(object):
                              'Shape of argument is {}'.format(sh))
         if sh == (3,):
             raise NotImplementedError('response: pass the Voigt stress (6,); (3,) principal input is not supported')
+        self._tex_refuse('response')
         self._no_svr_gradient('response')
         self._no_flow_rule()
         maxit = int(maxit)
@@ -832,6 +956,7 @@ class Material(object):
         """``response`` on (N,6) arrays in one launch (extension; same numbers point by point).  ``khard_in`` /
         ``return_khard``: for a material that follows the SVR flow rule (``enable_svr_flow``), the hardening modulus of
         every point on entry (default: ``khard``) and, appended to the result, on exit; ``khard`` itself is left alone."""
+        self._tex_refuse('response_batch')
         self._no_svr_gradient('response_batch')
         if khard_in is not None or return_khard:
             if not self._svr_flow_on():
@@ -969,7 +1094,7 @@ class Material(object):
                              % (name, e.shape))
         return e
 
-    def yield_scale(self, su, epl=None, x0=None, return_status=False):
+    def yield_scale(self, su, epl=None, x0=None, return_status=False, tex=None):
         """Factor ``x`` with ``calc_yf(x * su, epl) = 0`` along unit stresses ``su`` -- (sdim,), (N,3) or (N,6) -- i.e. where
         the yield locus lies along these directions: the root search behind the reference's ``polar_plot_yl``
         (material.py:3290-3293, one ``fsolve`` over all N unknowns there), done on the device ray by ray in one launch.
@@ -983,10 +1108,17 @@ class Material(object):
         value of ``x0`` (a given ``x0 <= 0`` still makes the ray degenerate).
         A single stress returns a float.  Rays without a root come back as NaN (one warning names their count);
         ``return_status`` adds the status per ray: 0 root, 1 no bracket, 2 refinement cap reached, 3 degenerate ray (zero or
-        hydrostatic direction without ``x0``, non-finite input, ``x0 <= 0``)."""
+        hydrostatic direction without ``x0``, non-finite input, ``x0 <= 0``).
+
+        A texture material takes ``tex``, one descriptor (tdim,) shared by the rays or one per ray (N, tdim); the default
+        ``x0`` is ``sy / seq_J2(su)`` (no plastic strain enters its features)."""
         if self.sy is None:
             raise ValueError('yield_scale: the material has no yield strength')
         s, single = self._voigt(su, 'yield_scale')
+        if self.ML_yf and getattr(self, 'txdat', False):
+            return self._yield_scale_tex(s, single, tex, x0, return_status)
+        if tex is not None:
+            raise NotImplementedError('yield_scale: tex needs a texture material (from_data on data sets with tx_data)')
         e = self._epl_rows(epl, len(s), 'yield_scale')
         if x0 is not None:
             x0 = np.asarray(x0, dtype=float)
@@ -1007,12 +1139,88 @@ class Material(object):
             return (float(x[0]), int(st[0])) if return_status else float(x[0])
         return (x, st) if return_status else x
 
-    def yield_stress(self, su, epl=None):
+    def yield_stress(self, su, epl=None, tex=None):
         """Stresses on the yield locus along the unit stresses ``su``: ``su * yield_scale(su, epl)[:, None]`` (NaN rows where
-        no point of the locus was found)."""
+        no point of the locus was found); ``tex`` for a texture material."""
         s = np.asarray(su, dtype=float)
-        x = self.yield_scale(s, epl=epl)
+        x = self.yield_scale(s, epl=epl, tex=tex)
         return s * x if s.ndim == 1 else s * x[:, None]
+
+    def _tex_x0(self, s, x0, shape, name):
+        """start values of the ray search of a texture material: given (scalar or of `shape`), else sy / seq_J2(su)"""
+        if x0 is None:
+            with np.errstate(divide='ignore'):
+                return np.broadcast_to(self.sy / sig_eq_j2(s), shape)
+        x0 = np.asarray(x0, dtype=float)
+        if x0.ndim == 0:
+            return np.full(shape, float(x0))
+        if x0.shape != shape:
+            raise ValueError('%s: x0 must be a scalar or of shape %s; got %s' % (name, shape, x0.shape))
+        return x0
+
+    def _yield_scale_tex(self, s, single, tex, x0, return_status):
+        """yield_scale of a texture material through plfx_tex_svc_yield_scale: one launch for a shared texture, one per
+        distinct texture when every ray has its own"""
+        if tex is None:
+            raise ValueError("SVM is trained on texture data but no texture data was provided to this function.")
+        if not self._is_tex():
+            self._svc_refuse('yield_scale')
+        n = len(s)
+        t = self._tex_rows(tex, n, 'yield_scale')
+        x0 = self._tex_x0(s, x0, (n,), 'yield_scale')
+        ctx = self._load_tex()
+        if len(t) == 1 or n == 1:
+            x, st = ctx.tex_svc_yield_scale(s, t[:1], np.ascontiguousarray(x0[None, :]))
+            x, st = x[0], st[0]
+        else:   # one texture per ray: the rays grouped by texture, one launch per distinct texture
+            ut, inv = np.unique(t, axis=0, return_inverse=True)
+            inv = np.asarray(inv).reshape(-1)
+            x, st = np.empty(n), np.empty(n, dtype=np.int32)
+            for k in range(len(ut)):
+                sel = np.nonzero(inv == k)[0]
+                xx, ss = ctx.tex_svc_yield_scale(s[sel], ut[k:k + 1], np.ascontiguousarray(x0[None, sel]))
+                x[sel], st[sel] = xx[0], ss[0]
+        bad = int(np.sum(st != 0))
+        if bad:
+            warnings.warn('yield_scale: no point of the yield locus found along %d of %d direction(s); NaN returned there'
+                          % (bad, n))
+        if single:
+            return (float(x[0]), int(st[0])) if return_status else float(x[0])
+        return (x, st) if return_status else x
+
+    def texture_loci(self, tex=None, Na=72, return_status=False):
+        """The yield loci that the reference's ``examples/Texture/train_texture.py`` computes before it draws them, one per
+        texture: ``(theta, seq_yld)`` with ``theta = linspace(-pi, pi, Na)`` and ``seq_yld`` of shape (T, Na) -- along
+        ``snorm = sig_cyl2princ([1, theta])`` (padded to six components) the root ``x`` of ``find_yloc(x, snorm, tex=tex_t)``,
+        searched from ``x0 = sy / seq_J2(snorm)`` like ``yield_scale``, then ``sig_eq_j2(snorm * x)``.  ``tex`` (T, tdim),
+        default: the textures of the data sets of ``from_data``, in order.  All T * Na rays are searched in ONE launch
+        (the example solves one coupled ``fsolve`` per texture).  NaN where a ray has no root; ``return_status`` adds the
+        (T, Na) status array of ``yield_scale``."""
+        if not getattr(self, 'txdat', False):
+            raise NotImplementedError('texture_loci: needs a texture material (from_data on data sets with tx_data)')
+        if not self._is_tex():
+            self._svc_refuse('texture_loci')
+        if tex is None:
+            tex = np.array([np.asarray(md['texture'], dtype=float) for md in self.msparam])
+        t = np.asarray(tex, dtype=float)
+        if t.ndim == 1:
+            t = t[None, :]
+        if t.ndim != 2 or t.shape[1] != self.tdim:
+            raise ValueError('texture_loci: tex must be (T, %d); got shape %s' % (self.tdim, t.shape))
+        theta = np.linspace(-np.pi, np.pi, Na)
+        snorm = np.zeros((Na, 6))
+        snorm[:, 0:3] = sig_cyl2princ(np.array([np.ones(Na), theta]).T)
+        x0 = np.ascontiguousarray(self._tex_x0(snorm, None, (len(t), Na), 'texture_loci'))
+        x, st = self._load_tex().tex_svc_yield_scale(snorm, np.ascontiguousarray(t), x0)
+        seq = np.full(x.shape, np.nan)
+        ok = st == 0
+        if np.any(ok):
+            seq[ok] = sig_eq_j2((snorm[None, :, :] * x[:, :, None])[ok])
+        bad = int(np.sum(~ok))
+        if bad:
+            warnings.warn('texture_loci: no point of the yield locus found along %d of %d ray(s); NaN returned there'
+                          % (bad, x.size))
+        return (theta, seq, st) if return_status else (theta, seq)
 
     def polar_yield_locus(self, Na=72, cmat=None, scaling=None, sJ2=False):
         """The curves that the reference's ``polar_plot_yl`` draws (material.py:3290-3309), as arrays: ``(theta, s_yld)``
@@ -1020,6 +1228,7 @@ class Material(object):
         material's yield locus along ``snorm = sig_cyl2princ([sy sqrt(1.5), theta])``, searched from ``x0 = 1``, then one row
         per material of ``cmat`` along the same directions.  Like the reference (:3308), the curves of ``cmat`` are put through
         THIS material's ``calc_seq`` (``sig_eq_j2`` with ``sJ2``), not their own.  ``scaling`` divides the stresses."""
+        self._tex_refuse('polar_yield_locus')
         if self.sy is None:
             raise ValueError('polar_yield_locus: the material has no yield strength')
         sf = 1. if scaling is None else 1. / scaling
@@ -1111,6 +1320,7 @@ class Material(object):
           the angles ``linspace(0, 2 pi, Na)``; NaN rows where a ray meets no yield locus (hydrostatic rays of code 3).
 
         The caller's ``axis1`` / ``axis2`` lists are not modified (the reference rewrites code 3 in place)."""
+        self._tex_refuse('yield_slices')
         if self.sy is None:
             raise ValueError('yield_slices: the material has no yield strength')
         if len(axis1) != len(axis2):
@@ -1148,16 +1358,21 @@ class Material(object):
         """Define the material from one data set of ``Data`` (material.py:2596-2680): ``param`` is ``Data.mat_data``
         (or a list holding one).  Sets msparam, Nset, whdat, epc, Ndof (6, or 15 with work-hardening data; 2 for
         sdim = 3) and ind_wh; elastic constants from ``elast_const`` (a warning when the data has none) and
-        ``plasticity(sy=sy_av, sdim)``.  Several data sets (textures) and work-hardening data with sdim = 3 are refused."""
+        ``plasticity(sy=sy_av, sdim)``.  One or several data sets of ``Data(..., tx_data=True)`` make a texture material:
+        ``txdat``, ``tdim``, ``ind_tx = 6`` and ``Ndof = 6 + tdim``, elasticity and ``sy`` from set 0 as in the reference.
+        Refused: several data sets without texture data, texture together with work-hardening data (more features than the
+        kernels take), texture with sdim = 3, more than 10 texture coefficients, work-hardening data with sdim = 3."""
         ms = list(param) if isinstance(param, (list, tuple, np.ndarray)) else [param]
-        if len(ms) != 1:
-            raise NotImplementedError('from_data: %d data sets (texture variants) are not supported; pass one '
-                                      'Data.mat_data' % len(ms))
+        if len(ms) < 1:
+            raise ValueError('from_data: no data set given')
         md = ms[0]
-        if md.get('tx_data', False):
-            raise NotImplementedError('from_data: texture data (tx_data) is not supported')
         if md.get('tx_descriptor') == 'VF':
             raise NotImplementedError('from_data: texture descriptor VF is not supported')
+        if md.get('tx_data', False):
+            return self._from_data_tex(ms)
+        if len(ms) != 1:
+            raise NotImplementedError('from_data: %d data sets need texture data (Data(..., tx_data=True)) to tell them '
+                                      'apart; pass one Data.mat_data' % len(ms))
         sdim = md['sdim']
         if sdim not in (3, 6):
             raise ValueError('Value of sdim must be either 3 or 6')
@@ -1170,6 +1385,7 @@ class Material(object):
         self.sdim = sdim
         self.msparam = np.array(ms, ndmin=1)
         self._msparam_from_data = self.msparam   # marker: train_SVC accepts this msparam
+        self._tex_from_data = None
         self.Nset = 1
         self.whdat = whdat
         self.txdat = False
@@ -1186,10 +1402,65 @@ class Material(object):
         self.plasticity(sy=md['sy_av'], sdim=sdim)
         self._version += 1
 
+    def _from_data_tex(self, ms):
+        """from_data for data sets with texture descriptors (material.py:2618-2681)"""
+        md = ms[0]
+        tdim = md.get('tdim')
+        if not tdim:
+            raise NotImplementedError('from_data: texture data without a descriptor (tdim); Data(json, tx_data=True, '
+                                      "tx_descriptor='GSH_n') reads one")
+        sdim = md['sdim']
+        if sdim not in (3, 6):
+            raise ValueError('Value of sdim must be either 3 or 6')
+        if sdim == 3:
+            raise NotImplementedError('from_data: texture data with sdim = 3; the reference trains texture on full Voigt '
+                                      'stresses only (create_scaled_input asserts sdim == 6)')
+        if md['wh_data']:
+            raise NotImplementedError('from_data: texture together with work-hardening data (15 + tdim features) exceeds '
+                                      'the 16 features of the training kernels; read the data with wh_data=False')
+        if tdim > 10:
+            raise NotImplementedError('from_data: %d texture coefficients; at most 10 (16 features) are supported' % tdim)
+        for i, other in enumerate(ms[1:], 1):   # material.py:2652-2661
+            if (other['Ntext'] != md['Ntext'] or other['sdim'] != sdim or other.get('tdim') != tdim
+                    or not other.get('tx_data', False) or bool(other['wh_data'])):
+                print('Error: Structure of data set #', i, ' is inconsistent:', md['Nlc'], md['Ntext'], sdim)
+                raise ValueError('Inconsistent data structure')
+        for other in ms:
+            if np.shape(other.get('texture')) != (tdim,):
+                raise ValueError('Inconsistent data structure')
+        if self.sdim is not None and self.sdim != sdim:
+            warnings.warn('from_data: Microstructure has changed definition of sdim. New value={}'.format(sdim))
+        if getattr(self, 'tdim', None) not in (None, tdim):
+            warnings.warn('from_data: Microstructure has changed definition of tdim. New value={}'.format(tdim))
+        self.sdim = sdim
+        self.msparam = np.array(ms, ndmin=1)
+        self._msparam_from_data = self.msparam
+        self._tex_from_data = self.msparam       # marker: the texture paths accept this msparam
+        self.Nset = len(ms)
+        self.whdat = False
+        self.txdat = True
+        self.tdim = int(tdim)
+        self.epc = md.get('epc')
+        self.Ndof = 6
+        self.ind_tx = self.Ndof
+        self.Ndof += self.tdim
+        self.std_scaler = None
+        if md.get('elast_const') is None:
+            print('WARNING: No data on elastic properties in data.')
+        else:
+            self.elasticity(CV=md['elast_const'])
+        self.plasticity(sy=md['sy_av'], sdim=sdim)
+        self._version += 1
+
     def _msparam_ok(self):
         """True when msparam is one data set that from_data installed and that holds the fields training reads"""
         ms = getattr(self, 'msparam', None)
-        if ms is None or getattr(self, '_msparam_from_data', None) is not ms or len(ms) != 1:
+        if ms is None or getattr(self, '_msparam_from_data', None) is not ms:
+            return False
+        if self._is_tex():
+            need = self._MSPARAM_KEYS + ('sig_ideal', 'texture')
+            return all(isinstance(md, dict) and all(k in md for k in need) for md in ms)
+        if len(ms) != 1:
             return False
         md = ms[0]
         need = self._MSPARAM_KEYS + (('flow_stress', 'plastic_strain') if md.get('wh_data') else ('sig_ideal',))
@@ -1197,7 +1468,8 @@ class Material(object):
 
     def _svc_refuse(self, what):
         ms = getattr(self, 'msparam', None) is not None
-        if (ms and not self._msparam_ok()) or getattr(self, 'txdat', False) or (getattr(self, 'whdat', False) and not ms):
+        if ((ms and not self._msparam_ok()) or (getattr(self, 'txdat', False) and not self._is_tex())
+                or (getattr(self, 'whdat', False) and not ms)):
             raise NotImplementedError('%s: training from this microstructure data (msparam / texture / work hardening) '
                                       'is not supported; train from mat_ref or sdata, or from one data set installed '
                                       'by from_data' % what)
@@ -1225,6 +1497,8 @@ class Material(object):
                                           'is not supported')
             iw = self.ind_wh
             xt[:, iw:iw + self.sdim] = np.tile(np.asarray(md['plastic_strain'], dtype=float), (Nsdata, 1))
+        if self._is_tex():   # material.py:1813-1817
+            xt[:, self.ind_tx:] = np.asarray(md['texture'], dtype=float)
         return Nlc, N0, xt, yt
 
     def _svc_fit(self, X, y, C, gamma, gridsearch, cvals, gvals, dflt_c, dflt_g, metric):
@@ -1336,13 +1610,19 @@ class Material(object):
         plasticity from ``mat_ref`` (or sy = mean J2 stress of ``sdata``), training data from ``create_sig_data``, the fit
         by the batched SMO solver on the GPU (libsvm's C-SVC).  Returns (train score, test score)."""
         self._svc_refuse('train_SVC')
-        if scaler is not None or pca is not None or train_index is not None or test_index is not None:
-            raise NotImplementedError('train_SVC: scaler / pca / train_index / test_index belong to the texture path, '
-                                      'which is not supported')
+        if scaler is not None or pca is not None:
+            raise NotImplementedError('train_SVC: scaler / pca (a given scaler, the PCA of address-vector descriptors) are '
+                                      'not supported; a texture material fits its own StdScaler')
+        if (train_index is not None or test_index is not None) and not self._is_tex():
+            raise NotImplementedError('train_SVC: train_index / test_index select data sets of a texture material '
+                                      '(from_data on data sets with tx_data)')
         if plot:
             raise NotImplementedError('train_SVC: plotting is not supported')
         if reversal is not None:
             print('WARNING in "train_SVC": Parameter "reversal" is depracted and will be ignored.')
+        if self._is_tex():
+            return self._train_SVC_tex(C, gamma, Nseq, extend, Fe, Ce, gridsearch, cvals, gvals, train_index, test_index,
+                                       metric, verbose)
         if getattr(self, 'msparam', None) is not None:   # one data set from from_data (material.py:1624-1636)
             Nlc, N0, xt, yt = self._create_data_for_ms(Ce=Ce, Fe=Fe, Nseq=Nseq, extend=extend)
         elif sdata is None:
@@ -1367,12 +1647,136 @@ class Material(object):
             print(f"Training completed with score: {train_sc}")
         return train_sc, test_sc
 
+    # ------------------------------------------------------------------ texture training
+    def _tex_data(self, index, Ce, Fe, Nseq, extend):
+        """unscaled training rows [stress | texture] and labels of the data sets `index`, stacked (material.py:1631-1640)"""
+        xs, ys = [], []
+        for i in index:
+            _, _, xt, yt = self._create_data_for_ms(Ce=Ce, Fe=Fe, Nseq=Nseq, extend=extend, idx_ms=int(i))
+            xs.append(xt)
+            ys.append(yt)
+        return np.concatenate(xs, axis=0), np.concatenate(ys, axis=0)
+
+    def _tex_features(self, scaler, x):
+        """create_scaled_input on unscaled rows: the deviator where dev_only, then the scaler (material.py:2347-2361)"""
+        x = np.array(x, dtype=float)
+        if self.dev_only:
+            x[:, 0:6] = sig_dev(x[:, 0:6])
+        return scaler.transform(x)
+
+    @staticmethod
+    def _score(y, dec, metric):
+        pred = np.where(dec >= 0., 1., -1.)
+        return 100. * float(np.mean(pred == y)) if metric == 'acc' else _mcc(y, pred)
+
+    def _train_SVC_tex(self, C, gamma, Nseq, extend, Fe, Ce, gridsearch, cvals, gvals, train_index, test_index, metric,
+                       verbose):
+        """train_SVC of a texture material (material.py:1523-1593, 1624-1668, 1160-1258): rows of the data sets in
+        ``train_index`` (default: all), a StdScaler fitted to the unscaled rows, the fit on the standardised ones;
+        ``test_index`` names held-out sets for the test score.  ``gridsearch``: the reference's search over the textures --
+        KFold(5, shuffle, random_state 42) over the data sets, a scaler per fold, the mean test score per candidate, the
+        best by strict ``>`` in ParameterGrid order, then the refit on all sets -- with every fold x candidate fit in
+        one batched device call."""
+        if metric not in ('acc', 'mcc'):
+            raise ValueError(f"{metric} must be acc or mcc")
+        ctx = _ctx()
+        kw = dict(Ce=Ce, Fe=Fe, Nseq=Nseq, extend=extend)
+        if gridsearch:
+            from .training import param_grid, texture_folds
+            if cvals is None:
+                cvals = [1, 5, 10, 20, 50] + ([] if C in (1, 5, 10, 20, 50) else [C])
+            if gvals is None:
+                gvals = [0.3, 0.5, 1, 5, 10] + ([] if gamma in (0.3, 0.5, 1, 5, 10) else [gamma])
+            cand = param_grid(cvals, gvals)
+            folds = texture_folds(self.Nset)
+            # the shared X: per fold its training rows, then its held-out rows, both through the fold's own scaler
+            blocks, ys, tr_rows, te_rows, off = [], [], [], [], 0
+            for tr, te in folds:
+                xtr, ytr = self._tex_data(tr, **kw)
+                xte, yte = self._tex_data(te, **kw)
+                sc = StdScaler(xtr)
+                blocks += [self._tex_features(sc, xtr), self._tex_features(sc, xte)]
+                ys += [ytr, yte]
+                tr_rows.append(off + np.arange(len(ytr)))
+                te_rows.append(off + len(ytr) + np.arange(len(yte)))
+                off += len(ytr) + len(yte)
+            X, y = np.concatenate(blocks, axis=0), np.concatenate(ys)
+            probs = [tr_rows[k] for _ in cand for k in range(len(folds))]
+            Cs = np.array([float(c) for c, _ in cand for _ in folds])
+            gs = np.array([float(g) for _, g in cand for _ in folds])
+            fits = ctx.svc_fit_batch(X, y, probs, Cs, gs)
+            svl, coefs, icpt = [], [], []
+            for k, r in enumerate(fits):
+                rows = probs[k]
+                yt = y[rows]
+                order = np.concatenate([np.nonzero(yt < 0)[0], np.nonzero(yt > 0)[0]])
+                sv = order[r['alpha'][order] > 0.]
+                svl.append(rows[sv])
+                coefs.append(yt[sv] * r['alpha'][sv])
+                icpt.append(-r['rho'])
+            nf = len(folds)
+            q = [te_rows[k % nf] for k in range(len(fits))] + [tr_rows[k % nf] for k in range(len(fits))]
+            dec = ctx.svc_decision_batch(X, svl + svl, coefs + coefs, icpt + icpt, np.concatenate((gs, gs)), q)
+            test = np.array([self._score(y[q[k]], dec[k], metric) for k in range(len(fits))]).reshape(len(cand), nf)
+            train = np.array([self._score(y[q[len(fits) + k]], dec[len(fits) + k], metric)
+                              for k in range(len(fits))]).reshape(len(cand), nf)
+            best, best_score = -1, 0
+            for i in range(len(cand)):   # strict >, from 0 (material.py:1536, 1573)
+                cv = np.mean(test[i])
+                if cv > best_score:
+                    best, best_score = i, cv
+            self.grid = dict(params=[{'C': c, 'gamma': g} for c, g in cand], folds=[(tr, te) for tr, te in folds],
+                             split_test_scores=test, split_train_scores=train, mean_test_score=test.mean(axis=1),
+                             best_index_=best, best_params_=None if best < 0 else {'C': cand[best][0], 'gamma': cand[best][1]},
+                             n_iter=np.array([r['n_iter'] for r in fits]).reshape(len(cand), nf))
+            if best < 0:
+                raise ValueError('train_SVC: no candidate of the grid search reached a mean test score above 0; the '
+                                 'reference would refit with C = 0 and fail')
+            C, gamma = cand[best]
+            train_index = test_index = None   # the refit runs on all sets (material.py:1583-1586)
+            print(80 * "+")
+            print(f"Grid Search is finished :) \n Best HP: C={C}, gamma={gamma}")
+            print(80 * "+")
+        if not (C > 0 and gamma > 0):
+            raise ValueError('train_SVC: C and gamma must be > 0 (got C=%r, gamma=%r)' % (C, gamma))
+        if train_index is None:
+            train_index = range(self.Nset)
+        for i in list(train_index) + list(test_index if test_index is not None else []):
+            if not 0 <= int(i) < self.Nset:
+                raise IndexError('train_SVC: data set %r out of range (%d sets)' % (i, self.Nset))
+        xt, yt = self._tex_data(train_index, **kw)
+        if np.any((yt != 1.) & (yt != -1.)):
+            raise NotImplementedError('train_SVC: only binary labels -1 / +1 are supported (got %s)' % np.unique(yt))
+        print('Using {} full Voigt yield stresses for training.'.format(xt.shape))
+        if self.dev_only:
+            print('Only deviatoric part of stress tensors is considered.')
+        self.gam_yf, self.C_yf = gamma, C
+        self.scale_seq = sum(float(md['sy_av']) / self.Nset for md in self.msparam)   # not a feature scale (material.py:1164-1172)
+        self.scale_wh = 1.
+        self.std_scaler = StdScaler(xt)
+        X_train = self._tex_features(self.std_scaler, xt)
+        model = SVCModel.fit(ctx, X_train, yt, C, gamma)
+        self.svm_yf = model
+        self.svc = dict(sv=np.ascontiguousarray(model.support_vectors_), dual=np.ascontiguousarray(model.dual_coef_[0]),
+                        intercept=float(model.intercept_[0]))
+        self.ML_yf = True
+        self._version += 1
+        train_sc = self._score(yt, model.decision_function(X_train), metric)
+        test_sc = None
+        if test_index is not None:
+            xte, yte = self._tex_data(test_index, **kw)
+            test_sc = self._score(yte, model.decision_function(self._tex_features(self.std_scaler, xte)), metric)
+        if not gridsearch:
+            print(f"Training completed with score: {train_sc}")
+        return train_sc, test_sc
+
     # ------------------------------------------------------------------ harness
     def calc_properties(self, size=2, Nel=2, verb=False, eps=0.005, min_step=None, sigeps=False,
                         load_cases=['stx', 'sty', 'et2', 'ect']):
         """Stress-strain curves of a 2x2 plane-stress model under four load cases
         (material.py:3062-3166); the harness of the reference's plasticity tests."""
         from .model import Model
+        self._tex_refuse('calc_properties')
         self._no_svr_gradient('calc_properties')
 
         def calc_strength(vbc1, nbc1, vbc2, nbc2, sel):

@@ -242,6 +242,9 @@ class Model(object):
         if len(mats) != self.Nsec:
             raise ValueError('Numer of materials ({}) does not match number of sections ({})'
                              .format(len(mats), self.Nsec))
+        for mat in mats:
+            if getattr(mat, 'txdat', False):   # no response exists for a texture material, here or in the reference
+                mat._tex_refuse('Model.assign')
         self.mat = mats
         self.nonlin = False
         for mat in mats:

@@ -6,6 +6,7 @@ cross-validation bookkeeping of its grid search, in NumPy only (no SciPy, no sci
 reference calls, so the directions agree with the reference's to rounding.  ``stratified_folds`` and ``param_grid`` reproduce
 the fold assignment of ``StratifiedKFold(5)`` without shuffling and the candidate order of ``ParameterGrid`` that the
 reference's ``GridSearchCV`` uses; the fits themselves run on the GPU (``_lib.Context.svc_fit_batch``).
+``texture_folds`` gives the shuffled ``KFold`` over data sets of the reference's grid search over textures.
 """
 import math
 
@@ -172,3 +173,23 @@ def stratified_folds(y, n_splits=5):
 def param_grid(cvals, gvals):
     """candidates of ``ParameterGrid({'C': cvals, 'gamma': gvals})``: C outer, gamma inner, lists in the given order"""
     return [(c, g) for c in cvals for g in gvals]
+
+
+def texture_folds(nset, n_splits=5, seed=42):
+    """(train, test) index arrays of the texture grid search (material.py:1551-1552): scikit-learn's
+    ``KFold(n_splits, shuffle=True, random_state=seed).split`` over ``nset`` data sets.  The indices 0 .. nset - 1 are
+    shuffled by ``numpy.random.RandomState(seed)``, cut into ``n_splits`` consecutive test folds of which the first
+    ``nset % n_splits`` hold one index more, and every fold's train and test indices come back in ascending order."""
+    if n_splits > nset:
+        raise ValueError('Cannot have number of splits n_splits={0} greater than the number of samples: '
+                         'n_samples={1}.'.format(n_splits, nset))
+    idx = np.arange(nset)
+    np.random.RandomState(seed).shuffle(idx)
+    sizes = np.full(n_splits, nset // n_splits, dtype=int)
+    sizes[:nset % n_splits] += 1
+    out, start = [], 0
+    for sz in sizes:
+        test = np.sort(idx[start:start + sz])
+        out.append((np.setdiff1d(np.arange(nset), test), test))
+        start += sz
+    return out
