@@ -24,6 +24,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace plfx;
@@ -2106,6 +2107,29 @@ static int row16_block(const plfx_ctx *c, int n, int cap)
     return block;
 }
 
+// Grid of such a kernel: a block per block / 16 points, but no more than `rounds` blocks per CU, since every block stages the
+// tables again
+static dim3 row16_grid(const plfx_ctx *c, int n, int block, int rounds)
+{
+    const int rpb = block / 16;
+    return dim3(std::max(1, std::min((n + rpb - 1) / rpb, rounds * c->prop.multiProcessorCount)));
+}
+
+// f(std::integral_constant<int, NFP>) for the padded width nfp of a texture set (plfx_tex.hpp): the one place that lists the
+// instantiations of its kernels
+extern "C++" {
+template <class F>
+static void tex_for_nfp(int nfp, F &&f)
+{
+    if (nfp == 8)
+        f(std::integral_constant<int, 8>());
+    else if (nfp == 12)
+        f(std::integral_constant<int, 12>());
+    else
+        f(std::integral_constant<int, 16>());
+}
+}
+
 static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, const double *epl,
                       const double *ld, double *out, int32_t *status)
 {
@@ -2320,9 +2344,7 @@ int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const dou
     if (int rc = B.get(c, &dout, 36 * N)) return rc;
     if (epl && kind == PLFX_SVC_WH)
         if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
-    // 64 points per block; a block stages the tables once, so no more blocks than keep every CU busy for a few rounds
-    const int rpb = HESS_BLOCK / 16;
-    const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
+    const dim3 grid = row16_grid(c, n, HESS_BLOCK, 4);   // 64 points per block
     EvPair *ev;
     tim_begin(c, 0, &ev);
     if (kind == PLFX_SVC6)
@@ -2376,8 +2398,8 @@ int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double
         if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
     if (x0)
         if (int rc = B.put(c, &dx0, x0, N)) return rc;
-    const int block = row16_block(c, n, YS_BLOCK), rpb = block / 16;
-    const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
+    const int block = row16_block(c, n, YS_BLOCK);
+    const dim3 grid = row16_grid(c, n, block, 4);
     EvPair *ev;
     tim_begin(c, 0, &ev);
 #define YS_LAUNCH(NF)                                                                                                      \
@@ -2543,12 +2565,13 @@ int plfx_tex_svc_set(plfx_ctx *c, int nsv, int tdim, const double *sv, const dou
     HIPCHK(c, stream_sync(c));
     if (P.staged) {
         const int bytes = nsv * (st + 1) * 8;
-        HIPCHK(c, set_dyn_lds((const void *)k_tex_yf<8>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_tex_yf<12>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_tex_yf<16>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_tex_yield_scale<8>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_tex_yield_scale<12>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_tex_yield_scale<16>, bytes));
+        hipError_t e = hipSuccess;
+        for (int width : {8, 12, 16})   // every width, as the attribute is only ever raised (set_dyn_lds)
+            tex_for_nfp(width, [&](auto w) {
+                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_yf<decltype(w)::value>, bytes);
+                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_yield_scale<decltype(w)::value>, bytes);
+            });
+        HIPCHK(c, e);
     }
     c->tex = P;
     c->tex_nfp = nfp;
@@ -2586,21 +2609,15 @@ int plfx_tex_svc_yf(plfx_ctx *c, int n, const double *sig, int ntex, const doubl
     if (tex_id)
         if (int rc = B.put(c, &did, tex_id, N)) return rc;
     if (int rc = B.get(c, &dyf, N)) return rc;
-    const int block = row16_block(c, n, TEX_BLOCK), rpb = block / 16;
-    const dim3 grid(std::max(1, std::min((n + rpb - 1) / rpb, 8 * c->prop.multiProcessorCount)));
+    const int block = row16_block(c, n, TEX_BLOCK);
+    const dim3 grid = row16_grid(c, n, block, 8);
     EvPair *ev;
     tim_begin(c, 0, &ev);
-#define TEX_LAUNCH(NFP)                                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yf<NFP>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,           \
-                       (const double *)c->tex_sv, (const double *)c->tex_dual, n, (const double *)dsig, ntex,            \
-                       (const double *)dtex, (const int32_t *)did, dyf)
-    if (c->tex_nfp == 8)
-        TEX_LAUNCH(8);
-    else if (c->tex_nfp == 12)
-        TEX_LAUNCH(12);
-    else
-        TEX_LAUNCH(16);
-#undef TEX_LAUNCH
+    tex_for_nfp(c->tex_nfp, [&](auto w) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yf<decltype(w)::value>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,
+                           (const double *)c->tex_sv, (const double *)c->tex_dual, n, (const double *)dsig, ntex,
+                           (const double *)dtex, (const int32_t *)did, dyf);
+    });
     tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
     c->tex_yf_launches++;
@@ -2641,21 +2658,15 @@ int plfx_tex_svc_yield_scale(plfx_ctx *c, int nray, const double *su, int ntex, 
     if (int rc = B.put(c, &dx0, x0 ? x0 : start.data(), Q)) return rc;
     if (int rc = B.get(c, &dx, Q)) return rc;
     if (int rc = B.get(c, &dst, Q)) return rc;
-    const int block = row16_block(c, nq, TEX_BLOCK), rpb = block / 16;
-    const dim3 grid(std::max(1, std::min((nq + rpb - 1) / rpb, 4 * c->prop.multiProcessorCount)));
+    const int block = row16_block(c, nq, TEX_BLOCK);
+    const dim3 grid = row16_grid(c, nq, block, 4);
     EvPair *ev;
     tim_begin(c, 0, &ev);
-#define TEX_LAUNCH(NFP)                                                                                                    \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yield_scale<NFP>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,    \
-                       (const double *)c->tex_sv, (const double *)c->tex_dual, nray, (const double *)dsu, ntex,            \
-                       (const double *)dtex, (const double *)dx0, dx, dst)
-    if (c->tex_nfp == 8)
-        TEX_LAUNCH(8);
-    else if (c->tex_nfp == 12)
-        TEX_LAUNCH(12);
-    else
-        TEX_LAUNCH(16);
-#undef TEX_LAUNCH
+    tex_for_nfp(c->tex_nfp, [&](auto w) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yield_scale<decltype(w)::value>), grid, dim3(block), tex_lds_bytes(c), c->stream,
+                           c->tex, (const double *)c->tex_sv, (const double *)c->tex_dual, nray, (const double *)dsu, ntex,
+                           (const double *)dtex, (const double *)dx0, dx, dst);
+    });
     tim_end(c, ev);
     HIPCHK(c, hipGetLastError());
     c->tex_ray_launches++;

@@ -13,6 +13,7 @@
 // bitwise reproducible run to run.
 #pragma once
 #include "plfx_device.hpp"
+#include "plfx_rayroot.hpp"
 
 namespace plfx {
 
@@ -167,10 +168,11 @@ __device__ __forceinline__ void stage_svc(const MatDev *smat, int nmat, double *
     dual = lds + nf * n;
 }
 
-// ---- The row sum over the support vectors of an SVC material: k_yield_scale, k_committee_yf, and
-// k_hessian_row, which writes the trips out.  The tables of material `mat`: staged in dynamic LDS where they fit (stage_svc),
-// read from device memory otherwise.  Called by every thread of the block after a barrier that closes the writes to smat and
-// the reads of the tables staged before; ends with the barrier that publishes the new ones.
+// ---- The row sum over the support vectors of an SVC material: k_yield_scale, k_committee_yf, the
+// texture kernels of plfx_tex.hpp, and k_hessian_row, which writes the trips out.  The tables of material `mat`: staged in
+// dynamic LDS where they fit (stage_svc), read from device memory otherwise.  Called by every thread of the block after a
+// barrier that closes the writes to smat and the reads of the tables staged before; ends with the barrier that publishes the
+// new ones.
 __device__ __forceinline__ void svc_row_tables(const MatDev *smat, int nmat, int lds_doubles, int mat, const double *&psv,
                                                const double *&pdu)
 {
@@ -207,6 +209,19 @@ __device__ __forceinline__ void svc_row_trips(const double *psv, const double *p
 #pragma unroll
         for (int c = 0; c < 2; c++) add(c, (ea[c] < -1020. || (c == 1 && !two)) ? 0. : pdu[kk[c]], eo[c]);
     }
+}
+
+// The decision function of one row: the trips above with one FMA per term into the slot's accumulator, the row closed by the
+// DPP butterfly, then the intercept.  The same bits in the 16 lanes.  STRIDE: doubles from one vector to the next.
+// The intercept comes by reference: where it lies in LDS (smat) it is then read after the trips, where it is used; taken by
+// value it is read before them and holds two VGPRs through the loop (k_yield_scale<6>: 82 instead of 78).
+template <int STRIDE, class D2>
+__device__ __forceinline__ double svc_row_decision(const double *psv, const double *pdu, int nsv, double g,
+                                                   const double &intercept, D2 &&dist2)
+{
+    double acc[2] = {0., 0.};
+    svc_row_trips<STRIDE>(psv, pdu, nsv, g, dist2, [&](int c, double du, double e) { acc[c] = fma(du, e, acc[c]); });
+    return YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + intercept;
 }
 
 // One material kind per kernel instantiation (KIND = 1 Hill-6p/J2 on Voigt, 2 Hill-3p/J2 on principal
@@ -522,19 +537,15 @@ k_hessian_row(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
 }
 
 // Material.yield_scale of the SVC material `mat` on n rays: the factor x with calc_yf(x su) = 0 along the unit stress su, the
-// whole search of a ray on the device.  The root is the one the marching bracket of ML_full_yf
-// (material.py:468-486) isolates, made symmetric: from x0 (default sflow(epl) / seq_J2(su)) down by factors 0.98 while
-// f >= 0 (to 0.01 x0) or up by factors 1.02 while f < 0 (to 5 x0), then bisection of the bracket f(lo) < 0 <= f(hi) until lo
-// and hi are neighbouring doubles; of the two the one with the smaller |f| is returned.  Every loop is capped.
-// status: 0 root found, 1 no bracket in [0.01 x0, 5 x0], 2 refinement cap reached, 3 degenerate ray (su = 0, seq_J2(su) = 0 with
-// no x0 given, a non-finite input, x0 <= 0); x = NaN unless status is 0.
+// whole search of a ray on the device: ray_root (plfx_rayroot.hpp: the search, its caps and the status
+// values 0 / 1 / 2) from x0, default sflow(epl) / seq_J2(su).  Status 3, a degenerate ray, is decided here: su = 0,
+// seq_J2(su) = 0 with no x0 given, a non-finite input, x0 <= 0.  x = NaN unless status is 0.
 // Only x moves along a ray, so the features are set up once per ray: NF = 6 / 15 x u with u the (deviatoric) stress features of
 // su, the plastic-strain features of NF = 15 fixed; NF = 2 (seq_J2(su) / scale_seq) x - 1 and the constant polar angle.  Every
 // difference x u_j - v_ij is ONE fma, so the sums are at least as accurate as the point functions'.
-// f is the row sum of svc_row_trips, 16 lanes per ray and four rays per wave: every lane of a row holds the same f, so the
-// search is row-uniform.
+// f is svc_row_decision, 16 lanes per ray and four rays per wave: every lane of a row holds the same f, so the search is
+// row-uniform.
 constexpr int YS_BLOCK = 512;
-constexpr int YS_CAP_DOWN = 240, YS_CAP_UP = 90, YS_CAP_BISECT = 80;   // 0.98^228 = 0.01, 1.02^82 = 5, 2 % of x in ulps: 2^47
 template <int NF>
 __global__ void __launch_bounds__(YS_BLOCK)
 k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int mat, int n, const double *__restrict__ su_in,
@@ -589,15 +600,11 @@ k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
         int st = 0;
         double root = __builtin_nan("");
         if (!fin || zero || !isfinite(x0) || !(x0 > 0.)) st = 3;
-        if (st == 0) {
-            int phase = 0, cnt = 0;   // 0 first point, 1 marching down, 2 marching up, 3 bracket found, 4 bisection
-            double x = x0, lo = 0., hi = 0., flo = 0., fhi = 0.;
-            for (;;) {
-                // ---- f(x): the decision function at x su (the only evaluation site)
-                double acc[2] = {0., 0.};
-                svc_row_trips<NF>(
-                    psv, pdu, nsv, g,
-                    [&](const double *v, int) {
+        if (st == 0)   // (x by reference: taken by value the search's bookkeeping compiles otherwise, +0.8 % at 72 rays, section 29)
+            st = ray_root(
+                x0,
+                [&](const double &x) {   // the decision function at x su
+                    return svc_row_decision<NF>(psv, pdu, nsv, g, m.intercept, [&](const double *v, int) {
                         double hh = 0.;
                         if constexpr (NF == 2) {
                             const double h0 = fma(x, u[0], -1.) - v[0], h1 = th - v[1];
@@ -617,57 +624,9 @@ k_yield_scale(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int ma
                             for (int f = 6 + NW; f < NF; f++) hh = fma(v[f], v[f], hh);
                         }
                         return hh;
-                    },
-                    [&](int c, double du, double e) { acc[c] = fma(du, e, acc[c]); });
-                const double f = YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + m.intercept;   // the same bits in the 16 lanes
-                // ---- the search
-                if (!(f == f)) {
-                    st = 1;
-                    break;
-                }
-                if (phase == 0) phase = (f >= 0.) ? 1 : 2;
-                if (phase == 1) {
-                    if (f < 0.) {
-                        lo = x, flo = f, phase = 3;
-                    } else {
-                        hi = x, fhi = f;
-                        if (x < 0.01 * x0 || ++cnt > YS_CAP_DOWN) {
-                            st = 1;
-                            break;
-                        }
-                        x *= 0.98;
-                        continue;
-                    }
-                } else if (phase == 2) {
-                    if (f >= 0.) {
-                        hi = x, fhi = f, phase = 3;
-                    } else {
-                        lo = x, flo = f;
-                        if (x > 5. * x0 || ++cnt > YS_CAP_UP) {
-                            st = 1;
-                            break;
-                        }
-                        x *= 1.02;
-                        continue;
-                    }
-                } else if (f < 0.) {
-                    lo = x, flo = f;
-                } else {
-                    hi = x, fhi = f;
-                }
-                if (phase == 3) phase = 4, cnt = 0;
-                const double mid = lo + 0.5 * (hi - lo);
-                if (!(mid > lo && mid < hi)) {   // lo and hi are neighbours
-                    root = (-flo < fhi) ? lo : hi;
-                    break;
-                }
-                if (++cnt > YS_CAP_BISECT) {
-                    st = 2;
-                    break;
-                }
-                x = mid;
-            }
-        }
+                    });
+                },
+                root);
         if (l16 == 0) {
             x_out[i] = root;
             status[i] = st;
@@ -788,6 +747,7 @@ k_committee_yf(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int n
                 return hh;
             },
             [&](int c, double du, double e) { acc[c] = fma(du, e, acc[c]); });
+        // (svc_row_decision written out: through it the code after the row sum compiles otherwise)
         double f = YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + m.intercept;   // the same bits in the 16 lanes
         if (!fin) f = __builtin_nan("");
         if (l16 == mm) y = f;

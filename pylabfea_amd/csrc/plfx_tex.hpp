@@ -9,8 +9,8 @@
 // consecutive vectors with ds_read_b64, fall on 16 different bank pairs (strides of 8 / 12 / 16 doubles would be 4-, 2- and
 // 8-way conflicts).  Slots 6 + tdim .. NFP - 1 hold 0 in the table and in the point: their difference is an exact 0 and
 // fma(0, 0, hh) = hh, so no result depends on the padding.  The two stride slots are never read.
-// Lane contract of DESIGN section 27: 16 lanes per point / ray, svc_row_trips, row_allsum; the order of a point's sum depends
-// on nsv alone.
+// Lane contract of DESIGN section 27: 16 lanes per point / ray, svc_row_decision; the order of a point's sum depends on nsv
+// alone.
 #pragma once
 
 namespace plfx {
@@ -77,26 +77,20 @@ __device__ __forceinline__ void tex_features(const TexSvcPar &P, const double *t
 }
 
 // the decision function at the features f: the one vector loop of both kernels.  Squared distance from the differences in
-// feature order, exp2_neg_n<2>, one FMA into the slot's accumulator (svc_row_trips), the row closed by row_allsum, then the
-// intercept.  The same bits in the 16 lanes of the row.
+// feature order; trips, row sum and intercept are svc_row_decision's.
 template <int NFP>
 __device__ __forceinline__ double tex_decision(const double *psv, const double *pdu, int nsv, double g, double intercept,
                                                const double (&f)[NFP])
 {
-    double acc[2] = {0., 0.};
-    svc_row_trips<tex_stride(NFP)>(
-        psv, pdu, nsv, g,
-        [&](const double *v, int) {
-            double hh = 0.;
+    return svc_row_decision<tex_stride(NFP)>(psv, pdu, nsv, g, intercept, [&](const double *v, int) {
+        double hh = 0.;
 #pragma unroll
-            for (int j = 0; j < NFP; j++) {
-                const double d = f[j] - v[j];
-                hh = fma(d, d, hh);
-            }
-            return hh;
-        },
-        [&](int c, double du, double e) { acc[c] = fma(du, e, acc[c]); });
-    return YfSvcRow<1>::row_allsum(acc[0] + acc[1]) + intercept;
+        for (int j = 0; j < NFP; j++) {
+            const double d = f[j] - v[j];
+            hh = fma(d, d, hh);
+        }
+        return hh;
+    });
 }
 
 // calc_yf(sig, tex=) at n points.  The texture of point i: tex_id[i] when given, else row 0 (ntex = 1, shared) or row i
@@ -131,8 +125,11 @@ k_tex_yf(const TexSvcPar P, const double *__restrict__ gsv, const double *__rest
 // yield_scale(su, tex=) on ntex x nray rays, texture-major: ray q = t nray + r runs along the unit stress r at the texture t.
 // Only x moves along a ray: u_j = s_j / scale_j and c_j = mean_j / scale_j are set up once (s the deviator for a dev_only set),
 // the texture features as in k_tex_yf, and every evaluation forms f_j = fma(x, u_j, -c_j) once -- not per vector -- before the
-// vector loop of tex_decision.  The search, its caps and its status values are those of k_yield_scale (plfx_kernels.hpp), the
-// five-state loop, row-uniform; the rows of a wave diverge freely.
+// vector loop of tex_decision.  The search, its caps and its status values 0 / 1 / 2 are ray_root's (plfx_rayroot.hpp), but
+// written out in the kernel as k_hessian_row writes out its trips: called through ray_root the NFP = 12 instantiation is
+// allocated 120 instead of 134 VGPRs, arranges an evaluation differently and measured 27.6 % slower on 432 rays, 2.4 % on
+// 504 000.  A change to the search is made in both places; tests/test_gpu_texture.py holds this copy to
+// the fixture's status and roots.  Status 3 is decided here: su = 0, a non-finite stress, texture or x0, x0 <= 0.
 template <int NFP>
 __global__ void __launch_bounds__(TEX_BLOCK)
 k_tex_yield_scale(const TexSvcPar P, const double *__restrict__ gsv, const double *__restrict__ gdu, int nray,
@@ -165,7 +162,7 @@ k_tex_yield_scale(const TexSvcPar P, const double *__restrict__ gsv, const doubl
         double root = __builtin_nan("");
         if (!fin || zero || !isfinite(x0) || !(x0 > 0.)) st = 3;
         if (st == 0) {
-            int phase = 0, cnt = 0;   // 0 first point, 1 marching down, 2 marching up, 3 bracket found, 4 bisection
+            int phase = 0, cnt = 0;   // the search of ray_root, written out: see the comment above the kernel
             double x = x0, lo = 0., hi = 0., flo = 0., fhi = 0.;
             for (;;) {
                 // ---- f(x): the decision function at x su (the only evaluation site)

@@ -1120,24 +1120,13 @@ class Material(object):
         if tex is not None:
             raise NotImplementedError('yield_scale: tex needs a texture material (from_data on data sets with tx_data)')
         e = self._epl_rows(epl, len(s), 'yield_scale')
-        if x0 is not None:
-            x0 = np.asarray(x0, dtype=float)
-            if x0.ndim == 0:
-                x0 = np.full(len(s), float(x0))
-            if x0.shape != (len(s),):
-                raise ValueError('yield_scale: x0 must be a scalar or hold one start value per stress; got shape %s'
-                                 % (x0.shape,))
+        x0 = self._ray_x0(x0, (len(s),), None,
+                          'yield_scale: x0 must be a scalar or hold one start value per stress; got shape %s')
         ml = self.ML_yf
         # (_princ_rows: principal-stress materials see general states through the host's LAPACK call; plfx_yield_scale does the
         # same for callers of the C-ABI, csrc/plfx.hip, and finds nothing left to reduce in these rows)
         x, st = self._load(ana=not ml).yield_scale(0, self._princ_rows(s), e, x0)
-        bad = int(np.sum(st != 0))
-        if bad:
-            warnings.warn('yield_scale: no point of the yield locus found along %d of %d direction(s); NaN returned there'
-                          % (bad, len(s)))
-        if single:
-            return (float(x[0]), int(st[0])) if return_status else float(x[0])
-        return (x, st) if return_status else x
+        return self._ray_result('yield_scale', 'direction', x, st, single, return_status)
 
     def yield_stress(self, su, epl=None, tex=None):
         """Stresses on the yield locus along the unit stresses ``su``: ``su * yield_scale(su, epl)[:, None]`` (NaN rows where
@@ -1146,17 +1135,33 @@ class Material(object):
         x = self.yield_scale(s, epl=epl, tex=tex)
         return s * x if s.ndim == 1 else s * x[:, None]
 
-    def _tex_x0(self, s, x0, shape, name):
-        """start values of the ray search of a texture material: given (scalar or of `shape`), else sy / seq_J2(su)"""
+    def _ray_x0(self, x0, shape, s, message=None):
+        """Start values of a ray search: a scalar, or an array of `shape` (else ValueError(message % its shape)).  None: for
+        the rays s of a texture material sy / seq_J2(s); with s None it stays None and the device forms
+        get_sflow(epl) / seq_J2(su)."""
         if x0 is None:
+            if s is None:
+                return None
             with np.errstate(divide='ignore'):
                 return np.broadcast_to(self.sy / sig_eq_j2(s), shape)
         x0 = np.asarray(x0, dtype=float)
         if x0.ndim == 0:
             return np.full(shape, float(x0))
         if x0.shape != shape:
-            raise ValueError('%s: x0 must be a scalar or of shape %s; got %s' % (name, shape, x0.shape))
+            raise ValueError(message % (x0.shape,))
         return x0
+
+    @staticmethod
+    def _ray_result(name, noun, x, st, single=False, return_status=False):
+        """The tail of a ray search: one warning that counts the rays without a root (status != 0, NaN in x), then x -- a
+        float for a single ray -- with the status beside it on request"""
+        bad = int(np.sum(st != 0))
+        if bad:
+            warnings.warn('%s: no point of the yield locus found along %d of %d %s(s); NaN returned there'
+                          % (name, bad, st.size, noun))
+        if single:
+            x, st = float(x[0]), int(st[0])
+        return (x, st) if return_status else x
 
     def _yield_scale_tex(self, s, single, tex, x0, return_status):
         """yield_scale of a texture material through plfx_tex_svc_yield_scale: one launch for a shared texture, one per
@@ -1167,7 +1172,7 @@ class Material(object):
             self._svc_refuse('yield_scale')
         n = len(s)
         t = self._tex_rows(tex, n, 'yield_scale')
-        x0 = self._tex_x0(s, x0, (n,), 'yield_scale')
+        x0 = self._ray_x0(x0, (n,), s, 'yield_scale: x0 must be a scalar or of shape %s; got %%s' % ((n,),))
         ctx = self._load_tex()
         if len(t) == 1 or n == 1:
             x, st = ctx.tex_svc_yield_scale(s, t[:1], np.ascontiguousarray(x0[None, :]))
@@ -1180,13 +1185,7 @@ class Material(object):
                 sel = np.nonzero(inv == k)[0]
                 xx, ss = ctx.tex_svc_yield_scale(s[sel], ut[k:k + 1], np.ascontiguousarray(x0[None, sel]))
                 x[sel], st[sel] = xx[0], ss[0]
-        bad = int(np.sum(st != 0))
-        if bad:
-            warnings.warn('yield_scale: no point of the yield locus found along %d of %d direction(s); NaN returned there'
-                          % (bad, n))
-        if single:
-            return (float(x[0]), int(st[0])) if return_status else float(x[0])
-        return (x, st) if return_status else x
+        return self._ray_result('yield_scale', 'direction', x, st, single, return_status)
 
     def texture_loci(self, tex=None, Na=72, return_status=False):
         """The yield loci that the reference's ``examples/Texture/train_texture.py`` computes before it draws them, one per
@@ -1210,16 +1209,13 @@ class Material(object):
         theta = np.linspace(-np.pi, np.pi, Na)
         snorm = np.zeros((Na, 6))
         snorm[:, 0:3] = sig_cyl2princ(np.array([np.ones(Na), theta]).T)
-        x0 = np.ascontiguousarray(self._tex_x0(snorm, None, (len(t), Na), 'texture_loci'))
+        x0 = np.ascontiguousarray(self._ray_x0(None, (len(t), Na), snorm))
         x, st = self._load_tex().tex_svc_yield_scale(snorm, np.ascontiguousarray(t), x0)
         seq = np.full(x.shape, np.nan)
         ok = st == 0
         if np.any(ok):
             seq[ok] = sig_eq_j2((snorm[None, :, :] * x[:, :, None])[ok])
-        bad = int(np.sum(~ok))
-        if bad:
-            warnings.warn('texture_loci: no point of the yield locus found along %d of %d ray(s); NaN returned there'
-                          % (bad, x.size))
+        self._ray_result('texture_loci', 'ray', seq, st)   # (the warning)
         return (theta, seq, st) if return_status else (theta, seq)
 
     def polar_yield_locus(self, Na=72, cmat=None, scaling=None, sJ2=False):

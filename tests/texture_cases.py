@@ -20,6 +20,8 @@ import os
 
 import numpy as np
 
+from ray_cases import march_replay as _march_replay, ulp
+
 LD = np.longdouble
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 FIXTURE = os.path.join(GOLD, 'texture_svc.npz')
@@ -187,10 +189,6 @@ def restate(p, su, tex, x, LD=LD):
     return f, df, A
 
 
-def ulp(x):
-    return np.spacing(np.abs(np.asarray(x, dtype=float)))
-
-
 def value_bar(calib, yf):
     """bar (1), the bar of DESIGN.md §21: 4 max(calib, 1e-12 max|yf|)"""
     return 4. * max(float(calib), 1e-12 * float(np.max(np.abs(yf))))
@@ -265,28 +263,10 @@ def crossing_intercept(p, tex0):
 
 
 def march_replay(p, su, tex, x0):
-    """status per ray (0 bracket found, 1 none) of the march of yield_scale replayed with the restatement, and the
-    smallest |f_L| / A met on the march (how clear of rounding the decisions were)"""
-    n = len(su)
-    x0 = np.asarray(x0, dtype=float)
-    x = np.array(x0)
-    f, _, A = restate(p, su, tex, x)
-    down = np.asarray(f >= 0)
-    st = np.full(n, -1)
-    clear = np.asarray(np.abs(f), dtype=float)
-    for _ in range(260):
-        act = np.flatnonzero(st < 0)
-        if not len(act):
-            break
-        out = np.where(down[act], x[act] < 0.01 * x0[act], x[act] > 5. * x0[act])
-        st[act[out]] = 1
-        act = act[~out]
-        if not len(act):
-            break
-        x[act] *= np.where(down[act], 0.98, 1.02)
-        f, _, A = restate(p, su[act], tex, x[act])
+    """status per ray (0 bracket found, 1 none) of the march of yield_scale replayed with the restatement
+    (ray_cases.march_replay), and the smallest |f_L| met on the march (how clear of rounding the decisions were)"""
+    clear = np.full(len(su), np.inf)
+
+    def seen(act, f, A):
         clear[act] = np.minimum(clear[act], np.asarray(np.abs(f), dtype=float))
-        found = np.where(down[act], f < 0, f >= 0)
-        st[act[np.asarray(found)]] = 0
-    st[st < 0] = 1
-    return st, clear
+    return _march_replay(lambda act, x: restate(p, su[act], tex, x)[::2], x0, seen), clear

@@ -13,6 +13,8 @@ import os
 
 import numpy as np
 
+from ray_cases import march_replay as _march_replay, ulp
+
 LD = np.longdouble
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 EPS53 = LD(2.) ** -53
@@ -128,10 +130,6 @@ def restate(p, su, epl, x, LD=LD):
     return f, df, A
 
 
-def ulp(x):
-    return np.spacing(np.abs(np.asarray(x, dtype=float)))
-
-
 def residual_bar(U, df, A, x):
     """bar (1): evaluation noise at termination plus the resolution of x"""
     return LD(U) * A * EPS53 + np.abs(df) * 2 * ulp(x)
@@ -171,28 +169,11 @@ def crossing_intercept(p, su, ep, x0s):
 
 
 def march_replay(p, su, ep, x0):
-    """status per ray (0 bracket found, 1 none) of the march of yield_scale, replayed with the restatement: from x0 down by
-    0.98 while f_L >= 0 (to 0.01 x0), else up by 1.02 while f_L < 0 (to 5 x0); `clear` is False where some |f_L| of the march
-    is within 1e-9 A of zero, i.e. where FP64 noise could decide otherwise"""
-    n = len(su)
-    x = np.array(x0, dtype=float)
-    f, _, A = restate(p, su, ep, x)
-    down = np.asarray(f >= 0)
-    st = np.full(n, -1)
-    clear = np.abs(f) > 1e-9 * A
-    for _ in range(260):
-        act = np.flatnonzero(st < 0)
-        if not len(act):
-            break
-        out = np.where(down[act], x[act] < 0.01 * x0[act], x[act] > 5. * x0[act])
-        st[act[out]] = 1
-        act = act[~out]
-        if not len(act):
-            break
-        x[act] *= np.where(down[act], 0.98, 1.02)
-        f, _, A = restate(p, su[act], ep[act], x[act])
+    """status per ray (0 bracket found, 1 none) of the march of yield_scale, replayed with the restatement
+    (ray_cases.march_replay); `clear` is False where some |f_L| of the march is within 1e-9 A of zero, i.e. where FP64 noise
+    could decide otherwise"""
+    clear = np.ones(len(su), dtype=bool)
+
+    def seen(act, f, A):
         clear[act] &= np.asarray(np.abs(f) > 1e-9 * A)
-        found = np.where(down[act], f < 0, f >= 0)
-        st[act[np.asarray(found)]] = 0
-    st[st < 0] = 1
-    return st, clear
+    return _march_replay(lambda act, x: restate(p, su[act], ep[act], x)[::2], x0, seen), clear

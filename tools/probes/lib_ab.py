@@ -9,7 +9,8 @@ last column / row: area-scaled diagonal, k_mg_coarsen_M), non-proportional lamin
 6-feature SVC material on 32 x 32 (the row kernels and their 50-sub-step corrector), config 5's J2 + SVC laminate on 128 x 64,
 a solve on 64 x 64 with three indefinite element tangents that GMRES completes, and 32 x 32 with PLFX_MG_MAXIT=2, where
 the single-GPU Jacobi-PCG fall-back completes the solves.  --points adds the batched point functions of the C-ABI (function
-points below): every output array of a call digested, inputs from a fixed-seed generator, n = 67 and 1025 points."""
+points below), the two of the context's texture set included: every output array of a call digested, inputs from a fixed-seed
+generator, n = 67 and 1025 points."""
 import hashlib
 import os
 import subprocess
@@ -21,7 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 
 def points(out):
     """hessian and yield_scale (tables as trained, cut to the remainders of the 16-lane trip loop, padded past the LDS),
-    committee_yf (as trained and with cut members) and, once each, seq / fgrad / fgrad_seq / fgrad_wh / yf / full_yf / response / the analytic yield_scale on principal stresses:
+    committee_yf (as trained and with cut members), tex_svc_yf and tex_svc_yield_scale of the context's texture set (every
+    padded width, the same cuts and padding) and, once each, seq / fgrad / fgrad_seq / fgrad_wh / yf / full_yf / response / the
+    analytic yield_scale on principal stresses:
     name|digest of all outputs|n (yield_scale: n, rays with a root)"""
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import numpy as np
@@ -130,6 +133,56 @@ def points(out):
         finally:
             del os.environ['PLFX_RESPONSE_ROW']
     with_context([hill6, hill, wh, princ3], fn)
+
+    # the texture set of the context (tests/golden/texture_svc.npz): both descriptors as trained (NFP 12 and 16), cut to two
+    # texture columns (NFP 8) and widened to ten, cut to the remainders of the trip loop, padded past the LDS, dev_only once
+    import texture_cases as TC
+    tz = TC.load()
+    SY = 40.   # about where the fits change sign along a ray
+
+    def tex_case(tag, p, tex):
+        def fn(ctx, n):
+            q = inputs(n, SY, 1.)
+            emit('tex_svc_yf %s, shared texture' % tag, n, [ctx.tex_svc_yf(q['sig'], tex[:1])])
+            emit('tex_svc_yf %s, one texture per point' % tag, n, [ctx.tex_svc_yf(q['sig'], tex[np.arange(n) % len(tex)])])
+            emit('tex_svc_yf %s, tex_id' % tag, n, [ctx.tex_svc_yf(q['sig'], tex[:3], np.arange(n, dtype=np.int32) % 3)])
+            for nt in (1, 3):
+                x0 = np.ascontiguousarray(np.tile(q['x0'], (nt, 1)) * (1. + 0.1 * np.arange(nt))[:, None])
+                emit_ys('tex_svc_yield_scale %s, ntex %d, x0' % (tag, nt), n, ctx.tex_svc_yield_scale(q['su'], tex[:nt], x0))
+
+        def fn_unit(ctx, n):
+            q = inputs(n, 1., 1.)
+            for nt in (1, 3):
+                emit_ys('tex_svc_yield_scale %s, ntex %d' % (tag, nt), n, ctx.tex_svc_yield_scale(q['su'], tex[:nt]))
+        ctx = _lib.Context(0)
+        try:
+            # without x0 the search starts at a J2 stress of one stress unit: these rays run on the set with its stress columns
+            # in units of SY (a second call replaces the set)
+            unit = np.concatenate((np.full(6, SY), np.ones(p['tdim'])))
+            ctx.tex_svc_set(p['sv'], p['dual'], p['intercept'], p['gamma'], p['mean'] / unit, p['scale'] / unit, dev_only=p['dev_only'])
+            for n in (67, 1025):
+                fn_unit(ctx, n)
+            ctx.tex_svc_set(p['sv'], p['dual'], p['intercept'], p['gamma'], p['mean'], p['scale'], dev_only=p['dev_only'])
+            info = ctx.tex_svc_info()
+            assert info['nsv'] == len(p['sv']) and info['tdim'] == p['tdim']
+            nfp = 8 if p['tdim'] <= 2 else 12 if p['tdim'] <= 6 else 16
+            assert info['staged'] == ('padded' not in tag) and (info['staged'] or len(p['sv']) * (nfp + 3) > 20480)
+            for n in (67, 1025):
+                fn(ctx, n)
+        finally:
+            ctx.close()
+
+    for desc in TC.DESCRIPTORS:
+        full, tex = TC.tables(tz, desc), TC.textures(tz, desc)
+        tex_case(desc, full, tex)
+        for k in (1, 16, 17, 32, 33):
+            p = TC.cut(full, nsv=k)
+            tex_case('%s nsv %d' % (desc, k), TC.cut(p, intercept=TC.crossing_intercept(p, tex[0])), tex)
+    tex_case('GSH_7 dev_only', TC.tables(tz, 'GSH_7', dev=True), TC.textures(tz, 'GSH_7'))
+    p, tex = TC.tables(tz, 'GSH_3'), TC.textures(tz, 'GSH_3')
+    tex_case('GSH_3 cut to tdim 2', TC.cut(p, tdim=2), tex[:, :2])
+    tex_case('GSH_7 widened to tdim 10', *TC.widen(TC.tables(tz, 'GSH_7'), TC.textures(tz, 'GSH_7'), 10))
+    tex_case('GSH_3 padded to 1500', TC.cut(p, pad=1500 - len(p['sv'])), tex)   # 1500 (12 + 3) doubles > 20480: device memory
 
 
 def child(more, pts=False):
