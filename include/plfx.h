@@ -166,6 +166,26 @@ int plfx_hessian_batch(plfx_ctx *ctx, int mat, int n, const double *sig, const d
  * where x follows from it -- analytic kinds, or no x0 given --, a non-finite input, x0 <= 0).  x is NaN unless status is 0. */
 int plfx_yield_scale(plfx_ctx *ctx, int mat, int n, const double *su, const double *epl, const double *x0, double *x,
                      int32_t *status);
+/* Material.flow_curve: n flow curves along the unit stresses su[n*6] (of unit J2 stress), the loop of
+ * plot_sig_eps in the reference's examples/train_hardening.py:83-133 with whole chains on the device, ONE launch per call
+ * whatever n and max_steps.  Per curve, with epl = epl0 (NULL: zeros): x_0 is the point of the yield locus along su at epl;
+ * then, while eps_eq(epl) + depl <= epl_max and k < max_steps: peeq = eps_eq(epl) + depl,
+ * a = calc_fgrad(su (x_k + peeq predictor), epl), epl += a depl / eps_eq(a), x_{k+1} the point of the locus at the new epl.
+ * The point of the locus: PLFX_SVC6 / PLFX_SVC_WH the root of plfx_yield_scale started at the previous root (x_0: at sy), with
+ * its bits; PLFX_HILL6 sflow(epl) / seq(su).  epl_max = inf runs exactly max_steps steps.
+ * Outputs, curve-major, NaN past a curve's last recorded point: x[n*(max_steps+1)], epl[n*(max_steps+1)*6],
+ * yf[n*(max_steps+1)] the yield function at the recorded point (the decision function at the root; seq - sflow for
+ * PLFX_HILL6), hk (NULL or [n*max_steps]) the raw hardening value of every gradient evaluation as plfx_fgrad_batch_wh
+ * returns it (NaN for kinds without work-hardening features; the material's khard is neither read for it nor changed),
+ * nsteps[n] completed steps, status[n]: 0 complete; 1 / 2 the status of the root search at the step where the curve ended;
+ * 3 degenerate direction (su = 0, seq(su) <= 0 for PLFX_HILL6, a non-finite input); 4 eps_eq(a) zero or not finite.
+ * n = 0 is PLFX_OK with nothing launched.  PLFX_ERR_ARG for depl <= 0 or not finite, max_steps < 0, a predictor that is not
+ * finite, an epl_max that is NaN, an elastic material and every kind not named above. */
+int plfx_flow_curve(plfx_ctx *ctx, int mat, int n, const double *su, const double *epl0, int max_steps, double depl,
+                    double epl_max, double predictor, double *x, double *epl, double *yf, double *hk, int32_t *nsteps,
+                    int32_t *status);
+/* launches of the flow-curve kernels by this context */
+int plfx_flow_info(plfx_ctx *ctx, int64_t *launches);
 
 /* A committee of SVC yield functions on n shared unit stresses su[n*6] (query by committee): member k is
  * material mats[k] of the context, 1 <= nmem <= 16, duplicates allowed, each a 6-feature SVC on Voigt stresses (PLFX_SVC6,
@@ -562,7 +582,7 @@ int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
- *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_committee_yf, plfx_tex_svc_yf, plfx_tex_svc_yield_scale, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_flow_curve, plfx_committee_yf, plfx_tex_svc_yf, plfx_tex_svc_yield_scale, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

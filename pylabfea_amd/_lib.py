@@ -64,6 +64,7 @@ SYMBOLS = [
     'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info', 'plfx_yield_scale',
     'plfx_committee_yf', 'plfx_committee_info',
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
+    'plfx_flow_curve', 'plfx_flow_info',
 ]
 
 _lib = None
@@ -311,6 +312,30 @@ class Context(object):
         st = np.zeros(len(su), dtype=np.int32)
         self._chk(self.lib.plfx_yield_scale(self.h, int(mat), len(su), _dp(su), _dp(epl), _dp(x0), _dp(x), _dp(st)))
         return x, st
+
+    def flow_curve(self, mat, su, epl0=None, max_steps=300, depl=1.e-3, epl_max=0.02, predictor=0.):
+        """Flow curves along N unit stresses su (N,6), whole chains in one launch (plfx_flow_curve): dict of x (N,K+1),
+        epl (N,K+1,6), yf (N,K+1), hk (N,K), nsteps (N,), status (N,) with K = max_steps; NaN past a curve's last recorded
+        point.  epl0 (N,6) or None (zeros).  Status 0 complete, 1 / 2 the root search's status where the curve ended,
+        3 degenerate direction, 4 eps_eq of the gradient zero or not finite."""
+        su = _f64(su).reshape(-1, 6)
+        epl0 = None if epl0 is None else _f64(epl0).reshape(-1, 6)
+        if epl0 is not None and len(epl0) != len(su):
+            raise ValueError('flow_curve: one initial plastic strain per unit stress expected')
+        n, K = len(su), int(max_steps)
+        K0 = max(K, 0)
+        x, yf = np.full((n, K0 + 1), np.nan), np.full((n, K0 + 1), np.nan)
+        epl, hk = np.full((n, K0 + 1, 6), np.nan), np.full((n, K0), np.nan)
+        ns, st = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        self._chk(self.lib.plfx_flow_curve(self.h, int(mat), n, _dp(su), _dp(epl0), K, C.c_double(depl), C.c_double(epl_max),
+                                           C.c_double(predictor), _dp(x), _dp(epl), _dp(yf), _dp(hk), _dp(ns), _dp(st)))
+        return dict(x=x, epl=epl, yf=yf, hk=hk, nsteps=ns, status=st)
+
+    def flow_info(self):
+        """dict(launches): launches of the flow-curve kernels by this context"""
+        nl = C.c_int64()
+        self._chk(self.lib.plfx_flow_info(self.h, C.byref(nl)))
+        return dict(launches=int(nl.value))
 
     def committee_yf(self, mats, scale, su, want_yf=True, want_mean=False, want_var=False, want_best=False):
         """A committee of 6-feature SVC materials on N shared unit stresses su (N,6) in one launch (plfx_committee_yf):

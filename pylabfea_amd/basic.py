@@ -165,6 +165,16 @@ def sig_spherical_to_cartesian(angles, seq=1.0):
     return x[0] if single else x
 
 
+# the reference's legacy names (basic.py:579-603), which its examples still call: the same objects under a second name.
+# svoigt is not offered: it names sig_cyl2voigt, which this package does not have.
+seq_J2 = sig_eq_j2
+sprinc = sig_princ
+sp_cart = sig_cyl2princ
+s_cyl = sig_princ2cyl
+sdev = sig_dev
+polar_ang = sig_polar_ang
+
+
 class Stress(object):
     """A Voigt stress with its tensor, principal values (axis-tracking order), hydrostatic and deviatoric parts
     (basic.py:366-484); ``seq(mat)`` is the material's equivalent stress (evaluated on the GPU through

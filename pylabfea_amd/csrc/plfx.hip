@@ -12,6 +12,7 @@
 #include "plfx_kernels.hpp"
 #include "plfx_mg.hpp"
 #include "plfx_tex.hpp"
+#include "plfx_flow.hpp"
 
 #include <dlfcn.h>
 #include <algorithm>
@@ -154,6 +155,7 @@ struct plfx_ctx {
     double *tex_sv = nullptr, *tex_dual = nullptr;   // [nsv * tex_stride(tex_nfp)] padded vectors, [nsv] coefficients
     int tex_nfp = 0;                  // padded feature slots of the set: 8, 12 or 16
     int64_t tex_yf_launches = 0, tex_ray_launches = 0;
+    int64_t flow_launches = 0;        // k_flow_curve / k_flow_curve_analytic launches of this context (plfx_flow_info)
     int svc_lds_need = 0;
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
@@ -2082,6 +2084,8 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<2>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<15>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_committee_yf, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_flow_curve<6>, bytes));
+        HIPCHK(c, set_dyn_lds((const void *)k_flow_curve<15>, bytes));
     }
     c->M_dirty = true;
     c->memo.valid = false;
@@ -2429,6 +2433,71 @@ int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double
     HIPCHK(c, hipMemcpyAsync(x, dx, N * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+// Material.flow_curve: n flow curves of up to max_steps steps along the unit stresses su, the whole chains
+// in ONE launch.  SVC kinds: k_flow_curve, 16 lanes per curve; Hill / J2 / Drucker on Voigt stresses: k_flow_curve_analytic.
+int plfx_flow_curve(plfx_ctx *c, int mat, int n, const double *su, const double *epl0, int max_steps, double depl,
+                    double epl_max, double predictor, double *x, double *epl, double *yf, double *hk, int32_t *nsteps,
+                    int32_t *status)
+{
+    if (int rc = point_check(c, mat, n >= 0 && su && x && epl && yf && nsteps && status)) return rc;
+    if (max_steps < 0 || !(depl > 0.) || !std::isfinite(depl) || !std::isfinite(predictor) || epl_max != epl_max)
+        return fail(c, PLFX_ERR_ARG, "flow_curve: max_steps >= 0, a finite depl > 0, a finite predictor and an epl_max that is a number expected");
+    const int kind = c->hmat[mat].kind;
+    if (kind == PLFX_ELASTIC) return fail(c, PLFX_ERR_ARG, "flow_curve: material %d has no yield strength", mat);
+    if (kind != PLFX_HILL6 && kind != PLFX_SVC6 && kind != PLFX_SVC_WH)
+        return fail(c, PLFX_ERR_ARG, "flow_curve: offered for Hill / J2 / Drucker on Voigt stresses and for the 6- and 15-feature SVC; material %d is of kind %d", mat, kind);
+    if (n == 0) return PLFX_OK;
+    const size_t N = n, K1 = (size_t)max_steps + 1, K = (size_t)max_steps;
+    CallBuffers B;
+    double *dsu = nullptr, *de0 = nullptr, *dx = nullptr, *de = nullptr, *dyf = nullptr, *dhk = nullptr;
+    int32_t *dns = nullptr, *dst = nullptr;
+    if (int rc = B.put(c, &dsu, su, 6 * N)) return rc;
+    if (epl0)
+        if (int rc = B.put(c, &de0, epl0, 6 * N)) return rc;
+    if (int rc = B.get(c, &dx, N * K1)) return rc;
+    if (int rc = B.get(c, &de, 6 * N * K1)) return rc;
+    if (int rc = B.get(c, &dyf, N * K1)) return rc;
+    if (hk && K > 0)
+        if (int rc = B.get(c, &dhk, N * K)) return rc;
+    if (int rc = B.get(c, &dns, N)) return rc;
+    if (int rc = B.get(c, &dst, N)) return rc;
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    if (kind == PLFX_HILL6) {
+        hipLaunchKernelGGL(k_flow_curve_analytic, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->dmat, mat, n, dsu, de0,
+                           max_steps, depl, epl_max, predictor, dx, de, dyf, dhk, dns, dst);
+    } else {
+        const int block = row16_block(c, n, YS_BLOCK);
+        const dim3 grid = row16_grid(c, n, block, 4);
+#define FC_LAUNCH(NF)                                                                                                     \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_curve<NF>), grid, dim3(block), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat, \
+                       c->svc_lds_need, mat, n, dsu, de0, max_steps, depl, epl_max, predictor, dx, de, dyf, dhk, dns, dst)
+        if (kind == PLFX_SVC6)
+            FC_LAUNCH(6);
+        else
+            FC_LAUNCH(15);
+#undef FC_LAUNCH
+    }
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->flow_launches++;
+    HIPCHK(c, hipMemcpyAsync(x, dx, N * K1 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(epl, de, N * K1 * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(yf, dyf, N * K1 * 8, hipMemcpyDeviceToHost, c->stream));
+    if (dhk) HIPCHK(c, hipMemcpyAsync(hk, dhk, N * K * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nsteps, dns, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+int plfx_flow_info(plfx_ctx *c, int64_t *launches)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (launches) *launches = c->flow_launches;
     return PLFX_OK;
 }
 

@@ -1135,6 +1135,122 @@ class Material(object):
         x = self.yield_scale(s, epl=epl, tex=tex)
         return s * x if s.ndim == 1 else s * x[:, None]
 
+    # ------------------------------------------------------------------ flow curves as arrays
+    def flow_curve(self, su, epl_max=0.02, depl=1.e-3, epl0=None, predictor=0., max_steps=300, return_status=False):
+        """Flow curves along fixed stress directions ``su`` -- (6,) or (N,6) -- as arrays: what ``plot_sig_eps`` of the
+        reference's ``examples/train_hardening.py`` (lines 83-133) computes before it draws, N curves in one launch with the
+        whole chains on the device.  Every direction is normalised to unit J2 stress.  Per curve, with ``epl = epl0``
+        (None: zeros; (6,) or (N,6)): ``x_0`` is the point of the yield locus along ``su`` at ``epl``; then, while
+        ``eps_eq(epl) + depl <= epl_max`` and fewer than ``max_steps`` steps are done: ``peeq = eps_eq(epl) + depl``,
+        ``a = calc_fgrad(su * (x_k + peeq * predictor), epl)``, ``epl += a * depl / eps_eq(a)``, and ``x_{k+1}`` is the point
+        of the locus at the new ``epl``.  ``predictor`` is the hardening coefficient that the example adds to the stress
+        before it takes the gradient (its script-global ``khard``); 0 takes the gradient on the locus.
+        ``epl_max = np.inf`` runs exactly ``max_steps`` steps.
+
+        The point of the locus is the root of ``yield_scale`` for an ML yield function -- started at ``sy`` for ``x_0``, then
+        at the previous root, so ``x_{k+1}`` has the bits of ``yield_scale(su, epl_{k+1}, x0=x_k)``; where the yield function
+        changes sign once near the locus this is the root that the example's ``fsolve(..., mat.sy, xtol=1e-5)`` converges
+        to, within that tolerance -- and ``get_sflow(epl) / calc_seq(su)`` for Hill / J2 / Drucker materials.
+
+        Returns a dict (a single direction drops the leading N): ``sig`` (N,K+1,6) = ``su * x``, ``epl`` (N,K+1,6),
+        ``seq`` (N,K+1) = ``sig_eq_j2(sig)``, ``peeq`` (N,K+1) = ``eps_eq(epl)``, ``yf`` (N,K+1) the yield function at every
+        recorded point (the example reports its largest magnitude per curve), ``hk`` (N,K) the raw hardening value of every
+        gradient evaluation as ``calc_fgrad`` forms it before the clip at 0 (NaN for materials without work-hardening
+        features), ``nsteps`` (N,).  ``K = max(nsteps)``; entries past a curve's ``nsteps`` are NaN.  Unlike ``calc_fgrad``
+        this function leaves ``khard`` alone (the reference overwrites it at every gradient evaluation).
+        ``return_status`` adds ``status`` (N,): 0 complete; 1 / 2 the root search's status (``yield_scale``) at the step where
+        the curve ended; 3 a degenerate direction or input; 4 ``eps_eq(a)`` zero or not finite.  One warning counts the
+        curves that ended early.
+
+        Offered for Hill / J2 / Drucker materials and ML yield functions with ``sdim = 6``; ``NotImplementedError`` for
+        ``sdim = 3``, Tresca, Barlat, an SVR gradient (``ML_grad``) and texture materials."""
+        if self.ML_yf:
+            self._tex_refuse('flow_curve')
+        self._no_svr_gradient('flow_curve')
+        if self.sy is None:
+            raise ValueError('flow_curve: the material has no yield strength')
+        if self.sdim != 6:
+            raise NotImplementedError('flow_curve: not offered for sdim = 3 materials; the example integrates Voigt stresses')
+        ml = bool(self.ML_yf)
+        if not ml and (self.tresca or self.barlat):
+            raise NotImplementedError('flow_curve: not offered for %s materials (Hill / J2 / Drucker and ML yield functions only)'
+                                      % ('Tresca' if self.tresca else 'Barlat'))
+        s = np.array(su, dtype=float)
+        single = s.shape == (6,)
+        if single:
+            s = s[None, :]
+        if s.ndim != 2 or s.shape[1] != 6:
+            raise ValueError('Parameter "sig0" must be given as unit Voigt stress tensor.')
+        n = len(s)
+        seq = sig_eq_j2(s) if n else np.zeros(0)
+        if np.any(np.isclose(seq, 0.0)) or not np.all(np.isfinite(seq)):
+            raise ValueError('Parameter "sig0" has zero equivalent stress.')
+        s = np.ascontiguousarray(s / seq[:, None])
+        if epl0 is not None:
+            e0 = np.asarray(epl0, dtype=float)
+            if e0.shape == (6,):
+                e0 = np.tile(e0, (n, 1))
+            if e0.shape != (n, 6):
+                raise ValueError('flow_curve: epl0 must be None, (6,) or (N,6) with one row per direction; got shape %s'
+                                 % (np.shape(epl0),))
+            epl0 = np.ascontiguousarray(e0)
+        max_steps = int(max_steps)
+        if max_steps < 0 or not (np.isfinite(depl) and depl > 0.) or not np.isfinite(predictor) or np.isnan(epl_max):
+            raise ValueError('flow_curve: max_steps >= 0, a finite depl > 0, a finite predictor and an epl_max that is a '
+                             'number expected')
+        r = self._load(ana=not ml).flow_curve(0, s, epl0, max_steps=max_steps, depl=float(depl), epl_max=float(epl_max),
+                                              predictor=float(predictor))
+        ns, st = r['nsteps'], r['status']
+        K = int(np.max(ns)) if n else 0
+        bad = int(np.sum(st != 0))
+        if bad:
+            warnings.warn('flow_curve: %d of %d curve(s) ended early (no point of the yield locus found, or a flow direction '
+                          'without length); NaN returned from there on' % (bad, n))
+        x, epl = r['x'][:, :K + 1], r['epl'][:, :K + 1]
+        sig = s[:, None, :] * x[:, :, None]
+        out = dict(sig=sig, epl=epl, seq=sig_eq_j2(sig.reshape(-1, 6)).reshape(n, K + 1),
+                   peeq=eps_eq(epl.reshape(-1, 6)).reshape(n, K + 1), yf=r['yf'][:, :K + 1], hk=r['hk'][:, :K], nsteps=ns)
+        if return_status:
+            out['status'] = st
+        if single:
+            out = {k: v[0] for k, v in out.items()}
+        return out
+
+    def data_curve(self, ilc, epl_crit=0.002, return_status=False):
+        """What ``plot_lc`` of the reference's ``examples/train_hardening.py`` (lines 135-169; the "Reconstruct Stress-Strain
+        Curve" block of ``Train_CPFEM/train_cpfem.py``) computes before it draws: the ML yield stress along training load
+        case ``ilc`` at every plastic strain of its data.  The rows ``lc_indices[ilc] : lc_indices[ilc + 1]`` of
+        ``msparam[0]`` with ``eps_eq(plastic_strain) >= epl_crit`` are kept; ``sig0`` is the last kept stress over its J2
+        stress; the yield stresses are ONE ``yield_scale`` call along ``sig0`` with the kept plastic strains as ``epl`` rows
+        and ``x0 = sy`` (the example runs one ``fsolve`` from ``sy`` per row).
+        Returns a dict: ``peeq`` (Np,), ``seq_data`` (Np,) = ``sig_eq_j2`` of the kept stresses, ``seq_ml`` (Np,) =
+        ``sig_eq_j2(sig_ml)``, ``sig_ml`` (Np,6) = ``sig0 * x``, ``sig0`` (6,), ``index`` the kept rows within ``msparam[0]``;
+        ``return_status`` adds ``status`` (Np,) of ``yield_scale``."""
+        if isinstance(ilc, bool) or not isinstance(ilc, (int, np.integer)):
+            raise ValueError('Parameter "ilc" must be an integer number specifying the load case.')
+        ms = getattr(self, 'msparam', None)
+        if ms is None:
+            raise AttributeError('data_curve: the material holds no data sets (msparam); from_data installs them')
+        ms = ms[0]
+        if 'lc_indices' not in ms:
+            raise AttributeError('data_curve: the data set holds no load-case indices (lc_indices)')
+        lci = np.asarray(ms['lc_indices'])
+        istart, istop = int(lci[ilc]), int(lci[ilc + 1])
+        sig_dat = np.asarray(ms['flow_stress'], dtype=float)[istart:istop, :]
+        epl_dat = np.asarray(ms['plastic_strain'], dtype=float)[istart:istop, :]
+        keep = np.nonzero(eps_eq(epl_dat) >= epl_crit)[0] if len(epl_dat) else np.zeros(0, dtype=int)
+        if len(keep) == 0:
+            raise ValueError('data_curve: load case %d holds no plastic strain of at least %g' % (ilc, epl_crit))
+        sig_f, epl_f = sig_dat[keep], np.ascontiguousarray(epl_dat[keep])
+        sig0 = sig_f[-1] / sig_eq_j2(sig_f[-1])
+        x, st = self.yield_scale(np.tile(sig0, (len(keep), 1)), epl=epl_f, x0=float(self.sy), return_status=True)
+        sig_ml = sig0[None, :] * x[:, None]
+        out = dict(peeq=eps_eq(epl_f), seq_data=sig_eq_j2(sig_f), seq_ml=sig_eq_j2(sig_ml), sig_ml=sig_ml, sig0=sig0,
+                   index=istart + keep)
+        if return_status:
+            out['status'] = st
+        return out
+
     def _ray_x0(self, x0, shape, s, message=None):
         """Start values of a ray search: a scalar, or an array of `shape` (else ValueError(message % its shape)).  None: for
         the rays s of a texture material sy / seq_J2(s); with s None it stays None and the device forms

@@ -146,6 +146,28 @@ def training_score(yf_ref, yf_ml, plot=False):
     return mae, precision, Accuracy, Recall, F1Score, MCC
 
 
+TEST_SIG_FACTORS = ((1.5, 1.2, 1.1, 1.01), (0.99, 0.9, 0.8, 0.5))   # outside / inside the yield locus (training.py:282-289)
+
+
+def create_test_sig(file, number_sig_per_strain=4):
+    """Test stresses for a trained yield function from a JSON database of stress-strain data (training.py:244-302):
+    ``(ts_sig, epl_tot, yf_ref)``.  The database is read as the reference reads it, ``Data(file, epl_crit=2e-3,
+    epl_start=1e-3, epl_max=0.03, depl=0.0)``; every flow stress is scaled by 1.5, 1.2, 1.1, 1.01 (plastic) and by 0.99,
+    0.9, 0.8, 0.5 (elastic).  ``ts_sig``: all plastic stresses, data row by data row, then all elastic ones; ``epl_tot``:
+    each row's plastic strain ``number_sig_per_strain`` times, the whole list twice; ``yf_ref``: +1 for the first half of
+    ``ts_sig``, -1 for the rest.  As in the reference the rows of ``ts_sig`` and ``epl_tot`` pair up only for the default
+    ``number_sig_per_strain = 4``."""
+    from .data import Data
+    md = Data(file, epl_crit=2.e-3, epl_start=1.e-3, epl_max=0.03, depl=0.0).mat_data
+    fs = np.asarray(md['flow_stress'], dtype=float)
+    ep = np.asarray(md['plastic_strain'], dtype=float)
+    ts_sig = np.concatenate([(fs[:, None, :] * np.array(f)[None, :, None]).reshape(-1, fs.shape[1]) for f in TEST_SIG_FACTORS])
+    epl_tot = np.tile(np.repeat(ep, int(number_sig_per_strain), axis=0), (2, 1))
+    half = len(ts_sig) // 2
+    yf_ref = np.concatenate((np.ones(half), -np.ones(len(ts_sig) - half)))
+    return ts_sig, epl_tot, yf_ref
+
+
 def stratified_folds(y, n_splits=5):
     """Test-fold index arrays of stratified k-fold cross-validation without shuffling, in the assignment of
     scikit-learn's ``StratifiedKFold(n_splits)`` (what ``GridSearchCV(cv=5)`` uses for a classifier): the samples,
