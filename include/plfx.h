@@ -321,6 +321,15 @@ int plfx_sweep_launch_info(plfx_ctx *ctx, int64_t *heavy_skipped, int64_t *heavy
  * solves whose du was composed behind the first convergence test, under the host's wait for it (du_early).  Results are
  * the same bit for bit either way. */
 int plfx_bc_info(plfx_ctx *ctx, int64_t *rhs_rows_only, int64_t *dinv_kept, int64_t *dinv_refreshed, int64_t *du_early);
+/* Stores that nothing reads (one GPU, no strip; PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: all
+ * four stay 0).  Sweeps of plfx_load_step that were certain to be repeated if they changed a tangent, and in which the
+ * elements whose tangent changed therefore left res_sig, res_depl and fyn to the next sweep (armed_sweeps; the tangents they
+ * rewrote: tangents_rewritten_in_armed_sweeps, 104 B not stored for each of those the streaming kernel rewrote); solves that
+ * started with the sums of the first tolerance test alone, without r, z and r.z (test_only_starts), and those among them
+ * whose test failed, so that the full start followed (test_only_retries: one operator pass each).  Results are the same bit
+ * for bit either way.  plfx_sweep called from outside plfx_load_step always stores every element. */
+int plfx_dead_store_info(plfx_ctx *ctx, int64_t *armed_sweeps, int64_t *tangents_rewritten_in_armed_sweeps,
+                         int64_t *test_only_starts, int64_t *test_only_retries);
 /* Which kernels run the 6-feature SVC materials (Material.response with an ML yield function, material.py:398-405 evaluates
  * any trained svm_yf): bit k of *row_materials = material k runs with 16 lanes per element / point (one launch per material
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read

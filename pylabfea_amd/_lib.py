@@ -65,6 +65,7 @@ SYMBOLS = [
     'plfx_committee_yf', 'plfx_committee_info',
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
     'plfx_flow_curve', 'plfx_flow_info',
+    'plfx_dead_store_info',
 ]
 
 _lib = None
@@ -675,6 +676,14 @@ class Context(object):
         again on its own, solves whose du was composed under the wait for the first test) since the context was created"""
         a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self.lib.plfx_bc_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
+        return a.value, b.value, r.value, d.value
+
+    def dead_store_info(self):
+        """(sweeps of load steps whose changed elements left res_sig / res_depl / fyn to the next sweep, tangents rewritten in
+        them, solves started with the sums of the first test alone, those among them that needed the full start after all)
+        since the context was created"""
+        a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_dead_store_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
         return a.value, b.value, r.value, d.value
 
     def svc_info(self):

@@ -269,6 +269,14 @@ struct plfx_ctx {
     // plfx_load_step, single GPU: the set-up pass of the next stiffness iteration and the K du of the end of the load step are
     // enqueued behind k_sweep_flags with device-side predicates, before the host has read the flags
     bool spec_arm = false, spec_setup = false, spec_kdu = false, spec_was_clean = false;
+    // Stores nobody reads (PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: off).  dead_arm: plfx_load_step says of
+    // the sweep it is about to launch that another one follows whenever a tangent changes -- the elements whose tangent changes
+    // may leave res_sig, res_depl and fyn unwritten.  res_partial: the last sweep did leave some unwritten (it ran armed and
+    // reported a changed tangent); cleared by the next sweep, and until then the three fields are not to be read.  Seen from
+    // outside only after plfx_load_step returned an error between two sweeps.
+    // test_starts: a solve whose first test is expected to pass starts with k_cg_start_test (solve_start).
+    bool dead_stores = true, test_starts = true, dead_arm = false, res_partial = false;
+    long long n_dead_sweeps = 0, n_dead_tangents = 0, n_test_starts = 0, n_test_retries = 0;   // plfx_dead_store_info
     // plfx_load_step tells the solver which of its two solves this is (site 0 predictor of the load step, 1 stiffness iteration;
     // -1 any other caller); first_test_hint[site]: the last solve of that kind was answered by the test of the plain warm start
     // -- the next one waits for that test before it enqueues the six launches of the interpolated start behind it
@@ -1765,6 +1773,12 @@ int plfx_create(int device, plfx_ctx **out)
     if (const char *e4 = getenv("PLFX_MG_GRAPH")) c->want_mg_graph = atoi(e4) ? 1 : 0;
     if (const char *e8 = getenv("PLFX_REUSE")) c->reuse = atoi(e8) != 0;
     if (const char *e9 = getenv("PLFX_BC_ROWS")) c->bc_rows_on = atoi(e9) != 0;
+    if (const char *e10 = getenv("PLFX_DEAD_STORES")) {   // 0: off, 1: on; 2 / 3: the sweeps / the starts alone (to measure them apart)
+        const int v = atoi(e10);
+        c->dead_stores = v == 1 || v == 2;
+        c->test_starts = v == 1 || v == 3;
+    }
+    if (!c->reuse) c->dead_stores = c->test_starts = false;
     if (const char *e9 = getenv("PLFX_PREDICT")) c->predict = atoi(e9) != 0;
     {
         const char *e5 = getenv("PLFX_MAILBOX");
@@ -3544,6 +3558,17 @@ int plfx_bc_info(plfx_ctx *c, int64_t *rhs_rows_only, int64_t *dinv_kept, int64_
     return PLFX_OK;
 }
 
+int plfx_dead_store_info(plfx_ctx *c, int64_t *armed_sweeps, int64_t *tangents_rewritten_in_armed_sweeps, int64_t *test_only_starts,
+                         int64_t *test_only_retries)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (armed_sweeps) *armed_sweeps = c->n_dead_sweeps;
+    if (tangents_rewritten_in_armed_sweeps) *tangents_rewritten_in_armed_sweeps = c->n_dead_tangents;
+    if (test_only_starts) *test_only_starts = c->n_test_starts;
+    if (test_only_retries) *test_only_retries = c->n_test_retries;
+    return PLFX_OK;
+}
+
 int plfx_sweep_launch_info(plfx_ctx *c, int64_t *heavy_skipped, int64_t *heavy_recovered)
 {
     if (!c) return PLFX_ERR_ARG;
@@ -3861,8 +3886,8 @@ int plfx_state_reset(plfx_ctx *c)
     c->assembled = false, c->M_dirty = true;
     c->x_is_du = false;
     c->rhs_rows_ok = c->dinv_ok = false;   // (a new history starts with one full k_bc_finish)
-    c->res_is_sig = c->res_fresh = c->eps_stale = false;
-    c->last_heavy = -1;   // the next sweep launches its corrector kernels whatever the one before found
+    c->res_is_sig = c->res_fresh = c->eps_stale = c->res_partial = false;
+    c->last_heavy = -1;  // the next sweep launches its corrector kernels whatever the one before found
     return PLFX_OK;
 }
 
@@ -3904,10 +3929,22 @@ static void finish_done(plfx_ctx *c, bool swap)
     c->eps_stale = true;
 }
 
+// readers of res_sig / res_depl / fyn: not between a sweep that left them partial (plfx_ctx::res_partial) and its successor
+static int res_complete(plfx_ctx *c, const char *who)
+{
+    if (!c->res_partial) return 0;
+    return fail(c, PLFX_ERR_STATE, "%s: the last sweep left res_sig / res_depl / fyn partial (a load step ended in an error "
+                                   "between two sweeps): sweep again first", who);
+}
+
 static int state_ptr(plfx_ctx *c, int which, double **p, size_t *comps, size_t *n, bool *soa)
 {
     *soa = true;
     *n = c->nel;
+    if (which == 3 || which == 4 || which == 9) {
+        const int rcp = res_complete(c, "state");
+        if (rcp) return rcp;
+    }
     if (which == 1 || which == 6) {   // eps is read, or eps / u is about to be overwritten: the stored field first
         const int rce = ensure_eps(c);
         if (rce) return rce;
@@ -4498,8 +4535,11 @@ int plfx_load_step(plfx_ctx *c, plfx_step *st, double *u_at, double *f_at, doubl
             // (the loop goes on after this sweep only if nit + 1 <= 15: then -- and only then -- what follows the flags is decided
             // by the flags alone and can be enqueued behind them with device-side predicates)
             c->spec_arm = (nit + 1 <= 15) && c->reuse && !wh_sequential(c);
-            if ((rc = plfx_sweep(c, nit, &change, &conv))) return rc;  // model.py:1340-1361
-            c->spec_arm = false;
+            // (... and a sweep that changes a tangent is then followed by one that rewrites every plastic element's response)
+            c->dead_arm = (nit + 1 <= 15) && !wh_sequential(c);
+            rc = plfx_sweep(c, nit, &change, &conv);  // model.py:1340-1361
+            c->spec_arm = c->dead_arm = false;
+            if (rc) return rc;
             st->nsweeps++;
             if (!conv) st->nconv++;
             nit++;
@@ -4545,6 +4585,7 @@ int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
 {
     if (!c || !c->fin_dev) return c ? fail(c, PLFX_ERR_STATE, "set_finish_set first") : PLFX_ERR_STATE;
     if (!c->assembled) return fail(c, PLFX_ERR_STATE, "assemble first");
+    if (res_complete(c, "finish_step")) return PLFX_ERR_STATE;
     // plfx_update_state with calc_global's element sums fused into the state-update kernel (one pass over the state)
     const size_t nd = c->ndof;
     int rc = 0;
@@ -4943,7 +4984,11 @@ struct SolveRun {
     bool pred_d_ready, pred_moved;   // (d = x - pred_x is in pred_d; the start x + alpha d was accepted as the solution)
     bool pred_finished;              // (... and k_pred_finish has composed du and advanced the history already)
     bool du_early;                   // the gated k_compose_du behind the first test has composed du (that test passed)
+    bool test_only;                  // started by k_cg_start_test: r, z and r.z are not there until k_cg_start follows
 };
+
+// PLFX_WAIT_FIRST=0: a solve never waits for its first test before it enqueues the interpolated start (always speculate, as before DESIGN 24)
+bool wait_first_on() { static const bool on = !(getenv("PLFX_WAIT_FIRST") && atoi(getenv("PLFX_WAIT_FIRST")) == 0); return on; }
 
 bool solve_debug_on() { static const bool on = getenv("PLFX_SOLVE_DEBUG") && atoi(getenv("PLFX_SOLVE_DEBUG")) != 0; return on; }
 
@@ -5047,6 +5092,17 @@ int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
                            (const CgScalars *)nullptr);
         hipLaunchKernelGGL(k_cg_start_pred, dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, (const double2 *)c->x, (const double2 *)c->pred_d,
                            (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], s.P_rr[1], s.P_bb);
+    } else if (c->test_starts && s.mg && wait_first_on() && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on &&
+               !comm_active(c) && matfree(c)) {
+        // solve_first_test will wait for the first test before it enqueues anything that reads r or z, and expects it to pass:
+        // the sums of that test alone.  If it fails, k_cg_start follows there.
+#define TEST_START(G)                                                                                                          \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cg_start_test<G>), dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, 1, (const double2 *)c->x, \
+                       (const double2 *)c->rhs, (const double2 *)c->dinv, s.P_rr[1], s.P_bb, s.olo, s.ohi)
+        if (c->op.colr) TEST_START(2); else TEST_START(1);   // (the matrix-free instantiations, as LAUNCH_OP1 picks them)
+#undef TEST_START
+        s.test_only = true;
+        c->n_test_starts++;
     } else   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
         LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, warm ? 1 : 0, (const double2 *)c->x, (const double2 *)c->rhs,
                    (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, s.olo, s.ohi);
@@ -5067,7 +5123,7 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
     int rc;
     bool first_passed = false, pred_first_passed = false;
     unsigned long long seq = cg_setup_check_post(c, s.P_bb, s.P_rr[1], gn, rtol);   // (scalars set up and first test: one launch)
-    static const bool wait_first = !(getenv("PLFX_WAIT_FIRST") && atoi(getenv("PLFX_WAIT_FIRST")) == 0);   // (0: always speculate, as before)
+    const bool wait_first = wait_first_on();
     if (wait_first && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on) {
         // the predictor solve of a load step repeats the system of the solve before it up to the last bits of its boundary
         // values: x passes the first test.  Learn that before enqueuing what would return at once (six launches, 28 us)
@@ -5084,6 +5140,15 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
         if (early && s.done == 1) {
             s.du_early = true;
             c->n_du_early++;
+        }
+        if (s.test_only && !first_passed) {
+            // the hint was wrong: r, z and r.z after all -- one operator pass more than without the test-only start.  The sums of
+            // r.r and b.b are rewritten with the bits the test has seen.
+            LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
+                       (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, olo, ohi);
+            HIPCHK(c, hipGetLastError());
+            s.test_only = false;
+            c->n_test_retries++;
         }
     }
     if (first_passed) {
@@ -5426,6 +5491,12 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     // every plastic element's res_sig is written below: the buffer is a field of its own again, whatever it held
     c->res_is_sig = false;
     c->res_fresh = true;
+    // Armed by plfx_load_step alone (plfx_sweep from anywhere else stores everything): if this sweep changes a tangent, the loop
+    // there launches another one before anything reads res_sig, res_depl or fyn.  One GPU, no strip, no communicator.
+    // (k_sweep_light<1> and <2> honour it: only a model with one of their materials is armed)
+    const int dead = (c->dead_arm && c->dead_stores && !comm_active(c) && !c->strip.on && !wh_seq && (c->has_analytic || c->has_princ)) ? 1 : 0;
+    c->dead_arm = false;
+    c->res_partial = dead != 0;   // (until the final flags are known below; an error return on the way leaves it standing)
     EvPair *ev;
     tim_begin(c, 0, &ev);
 #define SWEEP_ARGS(lds) c->dmat, c->nmat, c->dcls, c->ncls, lds, c->nel, c->e0, c->dconn, c->dcls_id,          \
@@ -5441,22 +5512,22 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh)) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), first, 0u);
+                           SWEEP_ARGS(0), first, 0u, dead);
         first = 0;
     }
     if (c->has_princ) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<2>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), first, 0u);
+                           SWEEP_ARGS(0), first, 0u, dead);
         first = 0;
     }
     if (c->has_barlat) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<5>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), first, 0u);
+                           SWEEP_ARGS(0), first, 0u, 0);
         first = 0;
     }
     if (svc_thread) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, fast);
+                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, fast, 0);
         first = 0;
         c->n_svc_thread_launches++;
     }
@@ -5470,7 +5541,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     }
     if (c->has_svc3) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, 0u);
+                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, 0u, 0);
         first = 0;
     }
     // work-hardening SVC materials: one wave per element (PLFX_WH_WAVE=0: one thread per element, rounds 2-3)
@@ -5485,7 +5556,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         first = 0;
     } else if (c->has_svcwh) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<7>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, 0u, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
+                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, 0u, 0, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
                            wh_seq ? c->kh_touch : (int32_t *)nullptr);
         first = 0;
     }
@@ -5598,6 +5669,12 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     if (h[0]) c->M_dirty = true;  // generators are rewritten exactly where a tangent changed (finish_element)
     c->n_sweeps++;
     c->n_tangents_rewritten += h[3];
+    // the final flags (after a corrector recovery, if there was one): a changed tangent in an armed sweep = fields left partial
+    c->res_partial = dead && h[0];
+    if (dead) {
+        c->n_dead_sweeps++;
+        c->n_dead_tangents += h[3];
+    }
     c->last_heavy = h[2];
     return PLFX_OK;
 }
@@ -5841,6 +5918,7 @@ int plfx_scf_all(plfx_ctx *c, const double *sld, int64_t *count, double *minv, d
 int plfx_update_state(plfx_ctx *c)
 {
     if (!c || !c->assembled) return c ? fail(c, PLFX_ERR_STATE, "assemble first") : PLFX_ERR_STATE;
+    if (res_complete(c, "update_state")) return PLFX_ERR_STATE;
     const size_t nd = c->ndof;
     int rc = 0;
     const bool kdu_done = c->spec_kdu && c->spec_h0 == 0 && c->spec_h1 == 0 && !c->strip.on;   // (ran behind the last sweep's flags)
@@ -5883,6 +5961,7 @@ int plfx_global_sums(plfx_ctx *c, double *out18)
 {
     if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
     if (!out18) return fail(c, PLFX_ERR_ARG, "null output");
+    if (res_complete(c, "global_sums")) return PLFX_ERR_STATE;
     const int g = grid_for(c->nel, SUMPART);  // same grid as the fused sums of plfx_finish_step: identical numbers
     const int rce = ensure_eps(c);
     if (rce) return rce;

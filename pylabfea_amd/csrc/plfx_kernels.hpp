@@ -896,21 +896,29 @@ __device__ __forceinline__ int tan_load_fac(const TanStore &ts, int nel, int e, 
 // factors in Ct[0..6]; the corrector: TAN_FULL).  The stored tangent comes as its form tag `oform` and, for TAN_FAC, its
 // factors ofac[0..6], so that a streaming caller can have them in flight long before (k_sweep_light); the 21 entries of a
 // TAN_FULL element (cold path) are loaded here.  omax: the element's max_steps so far.
+template <bool MAY_SKIP = false>
 __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &m, int e, int nel,
                                                const double *s, const double *ep, const double *depl,
                                                int form, const double *Ct, double fy, int ns, const TanStore &ts,
                                                int oform, const double *ofac, int omax,
                                                double *Mel, int mel_stride, double *res_sig,
                                                double *res_depl, double *fyn, int32_t *max_steps, int nit,
-                                               int &changed, int &nconv, double kh = -1.)
+                                               int &changed, int &nconv, double kh = -1., int dead_ok = 0)
 {
+    // dead_ok (k_sweep_light inside plfx_load_step): a sweep that changes any tangent is certainly followed by another
+    // one, which rewrites res_sig, res_depl and fyn of every plastic element before anything reads them -- an element whose
+    // tangent changes here leaves the three stores out.  Which elements those are is known only behind the tangent test, so the
+    // stores wait for it; without dead_ok (every other caller: MAY_SKIP false) they stand where they always stood.
+    const bool late = MAY_SKIP && dead_ok;   // (MAY_SKIP false: the function is the one it was, to the letter)
+    if (!late) {
 #pragma unroll
-    for (int k = 0; k < 6; k++) {
-        res_sig[(size_t)k * nel + e] = s[k];
-        res_depl[(size_t)k * nel + e] = depl[k];
+        for (int k = 0; k < 6; k++) {
+            res_sig[(size_t)k * nel + e] = s[k];
+            res_depl[(size_t)k * nel + e] = depl[k];
+        }
     }
     const double f = fy / (kh >= 0. ? m.sy + eps_eq(ep) * kh : sflow_of(m, ep));  // model.py:1345 (kh: the modulus a work-hardening SVC left behind)
-    fyn[e] = f;
+    if (!late) fyn[e] = f;
     if (!(f <= YF_TOL * 1.0001)) nconv = 1;  // model.py:1361
     // Frobenius norm of the tangent change over the full 6x6 (model.py:1346)
     double Dold[21], Dnew[21];
@@ -930,6 +938,14 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
             hh += (i == j ? 1. : 2.) * d * d;
         }
     hh = sqrt(hh);
+    if (late && !(hh > 1.e-3)) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            res_sig[(size_t)k * nel + e] = s[k];
+            res_depl[(size_t)k * nel + e] = depl[k];
+        }
+        fyn[e] = f;
+    }
     if (hh > 1.e-3) {  // model.py:1348-1355
         if (nit >= 15) {
 #pragma unroll
@@ -1128,6 +1144,7 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
               const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts,
               double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
               int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, unsigned skip_mask,
+              int dead_ok /* elements whose tangent changes leave res_sig, res_depl, fyn unwritten (sweep_epilogue) */,
               double *kh_el = nullptr /* KIND 7: hardening modulus of every material point, carried from sweep to sweep */,
               double *kh_out = nullptr, int32_t *kh_touch = nullptr /* sequential-carry mode: kh_el is read only; the exit
               modulus and "a gradient evaluation overwrote it" go here */)
@@ -1146,6 +1163,8 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
     // The next tile's streams are kept in registers only by the analytic Hill sweep (KIND 1: HBM-bound, 256 VGPRs at two
     // waves per SIMD); the other kinds, compute-bound or already spilling, load the current tile's at the top of the pass.
     constexpr bool PREFETCH = (KIND == 1);
+    // dead_ok is honoured by the streaming kinds only (KIND 1, 2: HBM-bound); the others are compute-bound or their elements few
+    constexpr bool DEAD_STORES = (KIND == 1 || KIND == 2);
     int t = xcd_tile(blockIdx.x, nb);
     SweepIn nx;
     if (PREFETCH) sweep_in_load(nx, (long long)t * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
@@ -1179,8 +1198,8 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
                 if (st == 2)
                     heavy = true;  // (the corrector kernel repeats the prelude from the same entry modulus)
                 else {
-                    sweep_epilogue(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, in.ms, Mel, mel_stride, res_sig,
-                                   res_depl, fyn, max_steps, nit, changed, nconv, KIND == 7 ? yf.kh() : -1.);
+                    sweep_epilogue<DEAD_STORES>(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, in.ms, Mel, mel_stride, res_sig,
+                                   res_depl, fyn, max_steps, nit, changed, nconv, KIND == 7 ? yf.kh() : -1., dead_ok);
                     if (KIND == 7 && kh_el) {
                         (kh_out ? kh_out : kh_el)[e] = yf.kh();
                         if (kh_touch) kh_touch[e] = yf.touched();
@@ -2520,12 +2539,13 @@ k_cg_update(int nnode, const double2 *__restrict__ p, const double2 *__restrict_
 
 // Start of a PCG solve in one pass: q = K x0 (warm start), r = mask (b - q), z = dinv r and the partial sums of r.z,
 // r.r, b.b -- k_spmv<0> + k_cg_init without the round trip of q through memory.
-template <int GRID>
-__global__ void __launch_bounds__(BLOCK)
-k_cg_start(KOp op, int nnode, int warm, const double2 *__restrict__ x, const double2 *__restrict__ b,
-           const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ z,
-           double *__restrict__ part_rz_out, double *__restrict__ part_rr_out, double *__restrict__ part_bb_out,
-           int own_lo, int own_hi /* nodes whose sums this rank takes (strip: owned columns; else all) */)
+// TEST_ONLY (k_cg_start_test): the partial sums of r.r and b.b alone -- no r, no z, no r.z.
+template <int GRID, bool TEST_ONLY>
+__device__ __forceinline__ void
+cg_start_body(const KOp &op, int nnode, int warm, const double2 *__restrict__ x, const double2 *__restrict__ b,
+              const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ z,
+              double *__restrict__ part_rz_out, double *__restrict__ part_rr_out, double *__restrict__ part_bb_out,
+              int own_lo, int own_hi)
 {
     __shared__ double sh[BLOCK / 64];
     double a_rz = 0., a_rr = 0., a_bb = 0.;
@@ -2539,25 +2559,49 @@ k_cg_start(KOp op, int nnode, int warm, const double2 *__restrict__ x, const dou
         double2 ri, zi;
         ri.x = (di.x != 0.) ? bi.x - qi.x : 0.;
         ri.y = (di.y != 0.) ? bi.y - qi.y : 0.;
-        zi.x = di.x * ri.x;
-        zi.y = di.y * ri.y;
-        r[i] = ri;
-        z[i] = zi;
+        if (!TEST_ONLY) {
+            zi.x = di.x * ri.x;
+            zi.y = di.y * ri.y;
+            r[i] = ri;
+            z[i] = zi;
+        }
         if (i >= own_lo && i < own_hi) {
-            a_rz = fma(ri.x, zi.x, fma(ri.y, zi.y, a_rz));
+            if (!TEST_ONLY) a_rz = fma(ri.x, zi.x, fma(ri.y, zi.y, a_rz));
             a_rr = fma(ri.x, ri.x, fma(ri.y, ri.y, a_rr));
             const double bx = (di.x != 0.) ? bi.x : 0., by = (di.y != 0.) ? bi.y : 0.;
             a_bb = fma(bx, bx, fma(by, by, a_bb));
         }
     }
-    const double t1 = block_sum(a_rz, sh);
+    const double t1 = TEST_ONLY ? 0. : block_sum(a_rz, sh);
     const double t2 = block_sum(a_rr, sh);
     const double t3 = block_sum(a_bb, sh);
     if (threadIdx.x == 0) {
-        part_rz_out[blockIdx.x] = t1;
+        if (!TEST_ONLY) part_rz_out[blockIdx.x] = t1;
         part_rr_out[blockIdx.x] = t2;
         part_bb_out[blockIdx.x] = t3;
     }
+}
+
+template <int GRID>
+__global__ void __launch_bounds__(BLOCK)
+k_cg_start(KOp op, int nnode, int warm, const double2 *__restrict__ x, const double2 *__restrict__ b,
+           const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ z,
+           double *__restrict__ part_rz_out, double *__restrict__ part_rr_out, double *__restrict__ part_bb_out,
+           int own_lo, int own_hi /* nodes whose sums this rank takes (strip: owned columns; else all) */)
+{
+    cg_start_body<GRID, false>(op, nnode, warm, x, b, dinv, r, z, part_rz_out, part_rr_out, part_bb_out, own_lo, own_hi);
+}
+
+// The start of a solve whose first tolerance test is expected to pass (solve_start): the same grid, the same walk
+// over the tiles and the same sums of r.r and b.b as k_cg_start, bit for bit -- and nothing else.  If the test fails after all,
+// k_cg_start follows and rewrites the same sums with r, z and r.z beside them.
+template <int GRID>
+__global__ void __launch_bounds__(BLOCK)
+k_cg_start_test(KOp op, int nnode, int warm, const double2 *__restrict__ x, const double2 *__restrict__ b,
+                const double2 *__restrict__ dinv, double *__restrict__ part_rr_out, double *__restrict__ part_bb_out,
+                int own_lo, int own_hi)
+{
+    cg_start_body<GRID, true>(op, nnode, warm, x, b, dinv, nullptr, nullptr, nullptr, part_rr_out, part_bb_out, own_lo, own_hi);
 }
 
 // k_cg_start of a warm-started multigrid-PCG solve that will try the interpolated start x + alpha d (plfx_solve):
