@@ -232,6 +232,35 @@ int plfx_tex_svc_yield_scale(plfx_ctx *ctx, int nray, const double *su, int ntex
 /* the set (nsv = 0: none), launches of k_tex_yf / k_tex_yield_scale since it was set, and whether its tables are staged in LDS
  * (0: read from device memory) */
 int plfx_tex_svc_info(plfx_ctx *ctx, int *nsv, int *tdim, int64_t *yf_launches, int64_t *ray_launches, int *staged);
+/* Flow rule and stress update of the texture SVC (the reference has none that run).  sig, tex, tex_id, ntex
+ * and their conventions are those of plfx_tex_svc_yf: n = 0 is PLFX_OK with nothing launched, PLFX_ERR_STATE before
+ * plfx_tex_svc_set, PLFX_ERR_ARG for ntex not in {1, n} without tex_id and for a tex_id outside 0..ntex-1.
+ * grad[n*6] = d calc_yf(sig_i, tex=) / d sig: with f the standardised features, v_k the vectors and K_k the kernel values,
+ * g_j = -2 gamma sum_k dual_k K_k (f_j - v_kj) and a_j = g_j / scale[j] for j < 6; for a dev_only set (a_0 + a_1 + a_2) / 3
+ * is then taken off a_0..a_2 (the chain rule through the deviator).  With equal scales and zero means on the six stress columns
+ * this is the gradient of a PLFX_SVC6 material (plfx_fgrad_batch) up to rounding -- for a dev_only set as far as the vectors
+ * are deviators, since that gradient is not projected.  A point's six values do not depend on n, its place, or how its
+ * texture was addressed; a non-finite stress or texture component makes them NaN and nothing else. */
+int plfx_tex_svc_fgrad(plfx_ctx *ctx, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *grad);
+/* ML_full_yf(sig_i, tex=) (material.py:414-516 as plfx_full_yf_batch runs it for a PLFX_SVC6 material, without loading
+ * direction and with epl = 0): the decision function is the texture one at the point's texture; seq and the flow stress sy
+ * come from material 0 of the context, which must be a PLFX_HILL6 record (PLFX_ERR_STATE without materials,
+ * PLFX_ERR_UNSUPPORTED for another kind).  f[n], status[n]: 0 root found, 1 no bracket, 2 search not converged (1 and 2: the
+ * conservative estimate seq - 0.85 sy).  A non-finite stress or texture component: NaN and status 1. */
+int plfx_tex_svc_full_yf(plfx_ctx *ctx, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *f,
+                         int32_t *status);
+/* Material.response (material.py:207-346) on n points with the texture SVC as yield function: the update of
+ * plfx_response_batch with calc_yf, ML_full_yf and calc_fgrad replaced by the texture forms above at the point's texture.
+ * `mat`: a PLFX_HILL6 record among the context's materials, which gives the elastic matrix, sy, khard (flow stress
+ * sy + khard peeq, hardening modulus khard) and the Hill form of seq; any other kind is PLFX_ERR_UNSUPPORTED.  maxit: the
+ * sub-steps of a sub-divided increment (PLFX_ERR_ARG below 1).  Outputs as plfx_response_batch: fy[n], sig_out[n*6],
+ * depl[n*6], ct[n*36], nsteps[n].  A point with a non-finite sig, epl, deps or texture component: all outputs NaN and
+ * nsteps = -1, nothing else changes. */
+int plfx_tex_svc_response(plfx_ctx *ctx, int mat, int n, const double *sig, const double *epl, const double *deps, int ntex,
+                          const double *tex, const int32_t *tex_id, int maxit, double *fy, double *sig_out, double *depl,
+                          double *ct, int32_t *nsteps);
+/* launches of k_tex_fgrad / k_tex_full_yf / k_tex_response since the set was installed (each pointer may be NULL) */
+int plfx_tex_svc_flow_info(plfx_ctx *ctx, int64_t *fgrad_launches, int64_t *full_yf_launches, int64_t *response_launches);
 
 /* Index products of Model.mesh for the reference's structured NX x NY grid, computed on the host (no context, no GPU):
  * conn[NX*NY*4] = [n1, n1+1, n1+NnodeY, n1+NnodeY+1] with n1 = (ih / NY) * NnodeY + ih % NY for element ih = j*NY + k
@@ -591,7 +620,7 @@ int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:
  * which: 0 streaming phase of the material sweep (k_sweep_light / k_sweep_svc_row<0>); also the kernels of the batched point
- *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_flow_curve, plfx_committee_yf, plfx_tex_svc_yf, plfx_tex_svc_yield_scale, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
+ *          functions (plfx_response_batch, plfx_seq / fgrad / yf / full_yf_batch, plfx_hessian_batch, plfx_yield_scale, plfx_flow_curve, plfx_committee_yf, plfx_tex_svc_yf, plfx_tex_svc_yield_scale, plfx_tex_svc_fgrad / full_yf / response, plfx_svr_predict_multi), 1 spmv(+dot), 2 cg vector
  *        update, 3 assemble, 4 multigrid V-cycle (whole cycle), 5 fine-level multigrid smoother launches,
  *        6 sub-stepping phase of the material sweep (k_sweep_heavy / k_sweep_svc_row<1>),
  *        7 collectives on the library's stream (RCCL all-reduces, halo and generator exchanges; every call is timed, the time

@@ -64,6 +64,7 @@ SYMBOLS = [
     'plfx_sweep_launch_info', 'plfx_element_fields', 'plfx_bc_info', 'plfx_yield_scale',
     'plfx_committee_yf', 'plfx_committee_info',
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
+    'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info',
     'plfx_dead_store_info',
 ]
@@ -426,6 +427,56 @@ class Context(object):
         self._chk(self.lib.plfx_tex_svc_info(self.h, C.byref(nsv), C.byref(td), C.byref(ny), C.byref(nr), C.byref(st)))
         return dict(nsv=int(nsv.value), tdim=int(td.value), yf_launches=int(ny.value), ray_launches=int(nr.value),
                     staged=bool(st.value))
+
+    def tex_svc_flow_info(self):
+        """dict(fgrad_launches, full_yf_launches, response_launches): launches of the flow-rule kernels of the texture SVC
+        since the set was installed (plfx_tex_svc_flow_info)"""
+        ng, nf, nq = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_tex_svc_flow_info(self.h, C.byref(ng), C.byref(nf), C.byref(nq)))
+        return dict(fgrad_launches=int(ng.value), full_yf_launches=int(nf.value), response_launches=int(nq.value))
+
+    @staticmethod
+    def _tex_args(name, sig, tex, tex_id):
+        sig = _f64(sig).reshape(-1, 6)
+        tex = _f64(tex)
+        if tex.ndim != 2:
+            raise ValueError('%s: tex (T, tdim) expected' % name)
+        tid = None if tex_id is None else _i32(tex_id).reshape(-1)
+        if tid is not None and len(tid) != len(sig):
+            raise ValueError('%s: one texture index per stress expected' % name)
+        return sig, tex, tid
+
+    def tex_svc_fgrad(self, sig, tex, tex_id=None):
+        """calc_fgrad(sig, tex=) of the texture SVC at N stresses (N,6) in one launch (plfx_tex_svc_fgrad): (N,6); tex and
+        tex_id as in tex_svc_yf"""
+        sig, tex, tid = self._tex_args('tex_svc_fgrad', sig, tex, tex_id)
+        out = np.empty_like(sig)
+        self._chk(self.lib.plfx_tex_svc_fgrad(self.h, len(sig), _dp(sig), len(tex), _dp(tex), _dp(tid), _dp(out)))
+        return out
+
+    def tex_svc_full_yf(self, sig, tex, tex_id=None):
+        """(f (N,), status (N,) int32): ML_full_yf(sig, tex=) of the texture SVC beside material 0 of the context, an
+        analytic Hill / J2 record (plfx_tex_svc_full_yf)"""
+        sig, tex, tid = self._tex_args('tex_svc_full_yf', sig, tex, tex_id)
+        out = np.empty(len(sig))
+        st = np.zeros(len(sig), dtype=np.int32)
+        self._chk(self.lib.plfx_tex_svc_full_yf(self.h, len(sig), _dp(sig), len(tex), _dp(tex), _dp(tid), _dp(out), _dp(st)))
+        return out, st
+
+    def tex_svc_response(self, sig, epl, deps, tex, tex_id=None, mat=0, maxit=50):
+        """(fy, sig, depl, ct (N,36), nsteps): Material.response with the texture SVC as yield function beside the analytic
+        Hill / J2 record `mat` of the context (plfx_tex_svc_response)"""
+        sig, tex, tid = self._tex_args('tex_svc_response', sig, tex, tex_id)
+        n = len(sig)
+        epl = _f64(epl).reshape(-1, 6)
+        deps = _f64(deps).reshape(-1, 6)
+        if len(epl) != n or len(deps) != n:
+            raise ValueError('tex_svc_response: sig, epl and deps of one length expected')
+        fy, so, dp, ct = np.empty(n), np.empty((n, 6)), np.empty((n, 6)), np.empty((n, 36))
+        ns = np.empty(n, dtype=np.int32)
+        self._chk(self.lib.plfx_tex_svc_response(self.h, int(mat), n, _dp(sig), _dp(epl), _dp(deps), len(tex), _dp(tex),
+                                                 _dp(tid), int(maxit), _dp(fy), _dp(so), _dp(dp), _dp(ct), _dp(ns)))
+        return fy, so, dp, ct, ns
 
     def yf(self, mat, sig, epl=None):
         sig = _f64(sig).reshape(-1, 6)

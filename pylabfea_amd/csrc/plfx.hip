@@ -12,6 +12,7 @@
 #include "plfx_kernels.hpp"
 #include "plfx_mg.hpp"
 #include "plfx_tex.hpp"
+#include "plfx_texflow.hpp"
 #include "plfx_flow.hpp"
 
 #include <dlfcn.h>
@@ -155,6 +156,7 @@ struct plfx_ctx {
     double *tex_sv = nullptr, *tex_dual = nullptr;   // [nsv * tex_stride(tex_nfp)] padded vectors, [nsv] coefficients
     int tex_nfp = 0;                  // padded feature slots of the set: 8, 12 or 16
     int64_t tex_yf_launches = 0, tex_ray_launches = 0;
+    int64_t tex_fgrad_launches = 0, tex_full_launches = 0, tex_resp_launches = 0;   // the flow-rule calls
     int64_t flow_launches = 0;        // k_flow_curve / k_flow_curve_analytic launches of this context (plfx_flow_info)
     int svc_lds_need = 0;
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
@@ -2610,6 +2612,7 @@ int plfx_tex_svc_set(plfx_ctx *c, int nsv, int tdim, const double *sv, const dou
         c->tex = TexSvcPar();
         c->tex_nfp = 0;
         c->tex_yf_launches = c->tex_ray_launches = 0;
+        c->tex_fgrad_launches = c->tex_full_launches = c->tex_resp_launches = 0;
         return PLFX_OK;
     }
     if (tdim < 1 || tdim > TEX_TMAX)
@@ -2653,12 +2656,16 @@ int plfx_tex_svc_set(plfx_ctx *c, int nsv, int tdim, const double *sv, const dou
             tex_for_nfp(width, [&](auto w) {
                 if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_yf<decltype(w)::value>, bytes);
                 if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_yield_scale<decltype(w)::value>, bytes);
+                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_fgrad<decltype(w)::value>, bytes);
+                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_full_yf<decltype(w)::value>, bytes);
+                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_response<decltype(w)::value>, bytes);
             });
         HIPCHK(c, e);
     }
     c->tex = P;
     c->tex_nfp = nfp;
     c->tex_yf_launches = c->tex_ray_launches = 0;
+    c->tex_fgrad_launches = c->tex_full_launches = c->tex_resp_launches = 0;
     return PLFX_OK;
 }
 
@@ -2767,6 +2774,157 @@ int plfx_tex_svc_info(plfx_ctx *c, int *nsv, int *tdim, int64_t *yf_launches, in
     if (yf_launches) *yf_launches = c->tex_yf_launches;
     if (ray_launches) *ray_launches = c->tex_ray_launches;
     if (staged) *staged = c->tex.staged;
+    return PLFX_OK;
+}
+
+// ---- flow rule and stress update of the texture SVC (kernels in plfx_texflow.hpp)
+// what the three calls ask of their common arguments; 1: n = 0, nothing to do
+static int tex_flow_check(plfx_ctx *c, const char *who, int n, const double *sig, int ntex, const double *tex,
+                          const int32_t *tex_id, bool outs_ok)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (c->tex.nsv == 0) return fail(c, PLFX_ERR_STATE, "%s: plfx_tex_svc_set first", who);
+    if (n < 0 || n > INT32_MAX / 36 || (n > 0 && (!sig || !tex || !outs_ok || ntex < 1)))
+        return fail(c, PLFX_ERR_ARG, "%s: bad argument", who);
+    if (n == 0) return 1;
+    if (!tex_id && ntex != 1 && ntex != n)
+        return fail(c, PLFX_ERR_ARG, "%s: %d textures for %d points; without tex_id one shared texture or one per point is "
+                    "expected", who, ntex, n);
+    if (tex_id)
+        for (int i = 0; i < n; i++)
+            if (tex_id[i] < 0 || tex_id[i] >= ntex)
+                return fail(c, PLFX_ERR_ARG, "%s: tex_id[%d] = %d, the call holds %d textures", who, i, tex_id[i], ntex);
+    return PLFX_OK;
+}
+
+// the material record the thread-per-point kernels take seq, sy, khard and the elastic matrix from
+static int tex_flow_material(plfx_ctx *c, const char *who, int mat)
+{
+    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "%s: set_materials first", who);
+    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "%s: material %d of %d", who, mat, c->nmat);
+    if (c->hmat[mat].kind != PLFX_HILL6)
+        return fail(c, PLFX_ERR_UNSUPPORTED, "%s: material %d is of kind %d; the record beside a texture set is an analytic "
+                    "PLFX_HILL6 one", who, mat, (int)c->hmat[mat].kind);
+    return PLFX_OK;
+}
+
+// calc_fgrad(sig, tex=) of the set at n points, one launch of k_tex_fgrad
+int plfx_tex_svc_fgrad(plfx_ctx *c, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *grad)
+{
+    if (int rc = tex_flow_check(c, "plfx_tex_svc_fgrad", n, sig, ntex, tex, tex_id, grad != nullptr)) return rc > 0 ? PLFX_OK : rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = n, td = c->tex.tdim;
+    CallBuffers B;
+    double *dsig = nullptr, *dtex = nullptr, *dg = nullptr;
+    int32_t *did = nullptr;
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
+    if (tex_id)
+        if (int rc = B.put(c, &did, tex_id, N)) return rc;
+    if (int rc = B.get(c, &dg, 6 * N)) return rc;
+    const int block = row16_block(c, n, TEX_BLOCK);
+    const dim3 grid = row16_grid(c, n, block, 8);
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    tex_for_nfp(c->tex_nfp, [&](auto w) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_fgrad<decltype(w)::value>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,
+                           (const double *)c->tex_sv, (const double *)c->tex_dual, n, (const double *)dsig, ntex,
+                           (const double *)dtex, (const int32_t *)did, dg);
+    });
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->tex_fgrad_launches++;
+    HIPCHK(c, hipMemcpyAsync(grad, dg, 6 * N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+// ML_full_yf(sig, tex=) of the set at n points beside material 0 of the context, one launch of k_tex_full_yf
+int plfx_tex_svc_full_yf(plfx_ctx *c, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *f,
+                         int32_t *status)
+{
+    if (int rc = tex_flow_check(c, "plfx_tex_svc_full_yf", n, sig, ntex, tex, tex_id, f && status)) return rc > 0 ? PLFX_OK : rc;
+    if (int rc = tex_flow_material(c, "plfx_tex_svc_full_yf", 0)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = n, td = c->tex.tdim;
+    CallBuffers B;
+    double *dsig = nullptr, *dtex = nullptr, *df = nullptr;
+    int32_t *did = nullptr, *dst = nullptr;
+    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
+    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
+    if (tex_id)
+        if (int rc = B.put(c, &did, tex_id, N)) return rc;
+    if (int rc = B.get(c, &df, N)) return rc;
+    if (int rc = B.get(c, &dst, N)) return rc;
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    tex_for_nfp(c->tex_nfp, [&](auto w) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_full_yf<decltype(w)::value>), dim3(grid_for(N)), dim3(BLOCK), tex_lds_bytes(c),
+                           c->stream, (const MatDev *)c->dmat, c->nmat, 0, c->tex, (const double *)c->tex_sv,
+                           (const double *)c->tex_dual, n, (const double *)dsig, ntex, (const double *)dtex,
+                           (const int32_t *)did, df, dst);
+    });
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->tex_full_launches++;
+    HIPCHK(c, hipMemcpyAsync(f, df, N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+// Material.response(..., tex=) of the set at n points beside material `mat`, one launch of k_tex_response
+int plfx_tex_svc_response(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, const double *deps, int ntex,
+                          const double *tex, const int32_t *tex_id, int maxit, double *fy, double *sig_out, double *depl,
+                          double *ct, int32_t *nsteps)
+{
+    if (int rc = tex_flow_check(c, "plfx_tex_svc_response", n, sig, ntex, tex, tex_id,
+                                epl && deps && fy && sig_out && depl && ct && nsteps))
+        return rc > 0 ? PLFX_OK : rc;
+    if (maxit < 1) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_response: maxit = %d", maxit);
+    if (int rc = tex_flow_material(c, "plfx_tex_svc_response", mat)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N = n, td = c->tex.tdim;
+    CallBuffers B;
+    double *d_in = nullptr, *d_out = nullptr, *dtex = nullptr;
+    int32_t *did = nullptr, *d_ns = nullptr;
+    if (int rc = B.get(c, &d_in, N * 18)) return rc;
+    if (int rc = B.get(c, &d_out, N * (1 + 6 + 6 + 36))) return rc;
+    if (int rc = B.get(c, &d_ns, N)) return rc;
+    HIPCHK(c, hipMemcpyAsync(d_in, sig, N * 48, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in + 6 * N, epl, N * 48, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in + 12 * N, deps, N * 48, hipMemcpyHostToDevice, c->stream));
+    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
+    if (tex_id)
+        if (int rc = B.put(c, &did, tex_id, N)) return rc;
+    double *d_fy = d_out, *d_so = d_out + N, *d_dp = d_out + 7 * N, *d_ct = d_out + 13 * N;
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    tex_for_nfp(c->tex_nfp, [&](auto w) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_response<decltype(w)::value>), dim3(grid_for(N)), dim3(BLOCK), tex_lds_bytes(c),
+                           c->stream, (const MatDev *)c->dmat, c->nmat, mat, c->tex, (const double *)c->tex_sv,
+                           (const double *)c->tex_dual, n, (const double *)d_in, (const double *)(d_in + 6 * N),
+                           (const double *)(d_in + 12 * N), ntex, (const double *)dtex, (const int32_t *)did, d_fy, d_so, d_dp,
+                           d_ct, d_ns, maxit);
+    });
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->tex_resp_launches++;
+    HIPCHK(c, hipMemcpyAsync(fy, d_fy, N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sig_out, d_so, N * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(depl, d_dp, N * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ct, d_ct, N * 288, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(nsteps, d_ns, N * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    return PLFX_OK;
+}
+
+int plfx_tex_svc_flow_info(plfx_ctx *c, int64_t *fgrad_launches, int64_t *full_yf_launches, int64_t *response_launches)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (fgrad_launches) *fgrad_launches = c->tex_fgrad_launches;
+    if (full_yf_launches) *full_yf_launches = c->tex_full_launches;
+    if (response_launches) *response_launches = c->tex_resp_launches;
     return PLFX_OK;
 }
 

@@ -784,16 +784,31 @@ struct BrentState {
 
 // Yield-function policy: RBF-SVC (ML_yf) on NF = 6 stress features (sdim 6) or NF = 2 (sdim 3), one thread per point
 // (entry points, calc_scf, the thread sweeps).  calc_seq of an ML material is J2 (hill = ones), on Voigt or on principal stresses.
-template <int NF>
-struct YfSvcT {
+// SRC: where the decision function and its gradient come from.  void: the tables of the material record (every SVC material);
+// else an object with decision(s) and fgrad(s, a) that the policy holds a reference to (the texture SVC of plfx_texflow.hpp,
+// whose tables belong to the context) -- the search of ML_full_yf and everything else below then run on that function.
+template <class SRC>
+struct YfSvcSource {
+    const SRC &src;
+};
+template <>
+struct YfSvcSource<void> {
+};
+template <int NF, class SRC = void>
+struct YfSvcT : YfSvcSource<SRC> {
     const MatDev &m;
     const double *sv;
     const double *dual;
     __device__ YfSvcT(const MatDev &mm, const double *s, const double *d) : m(mm), sv(s), dual(d) {}
+    template <class S>
+    __device__ YfSvcT(const MatDev &mm, const S &source) : YfSvcSource<SRC>{source}, m(mm), sv(nullptr), dual(nullptr) {}
     __device__ __forceinline__ double seq(const double *s) const { return NF == 6 ? hill_seq(m, s) : princ_seq(m, s); }
     __device__ __forceinline__ double decision(const double *s) const
     {
-        return NF == 6 ? svc_decision(m, sv, dual, s) : svc3_decision(m, sv, dual, s);
+        if constexpr (!__is_same(SRC, void))
+            return this->src.decision(s);
+        else
+            return NF == 6 ? svc_decision(m, sv, dual, s) : svc3_decision(m, sv, dual, s);
     }
     __device__ __forceinline__ double plain(const double *s, const double *epl) const
     {
@@ -902,7 +917,9 @@ struct YfSvcT {
     }
     __device__ __forceinline__ void fgrad(const double *s, double *a) const
     {
-        if (NF == 6)
+        if constexpr (!__is_same(SRC, void))
+            this->src.fgrad(s, a);
+        else if (NF == 6)
             svc_fgrad(m, sv, dual, s, a);
         else
             svc3_fgrad(m, sv, dual, s, a);

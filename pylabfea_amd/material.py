@@ -10,7 +10,9 @@ Same names, argument meaning and error behaviour; arguments are never mutated.
 Out of scope here: plotting.  What the yield-locus plots compute comes back as arrays (``yield_scale``,
 ``polar_yield_locus``, ``polar_field``, ``yield_slices``; ``texture_loci`` for a texture material, §28).
 Texture materials (``from_data`` on data sets with ``tx_data``) are trained and evaluated as yield functions --
-``train_SVC``, ``calc_yf``, ``find_yloc``, ``yield_scale``, ``texture_loci`` -- and, like in the reference, nothing past that.
+``train_SVC``, ``calc_yf``, ``find_yloc``, ``yield_scale``, ``texture_loci`` -- and, like in the reference, nothing past that
+unless the caller passes ``tex=``: ``calc_fgrad``, ``ML_full_yf``, ``response``, ``response_batch``, ``epl_dot`` and ``C_tan``
+then run at that texture (an extension).
 A trained SVC enters through
 :meth:`Material.train_SVC` (trained on the GPU), :meth:`Material.set_svc` or :meth:`Material.from_sklearn`.
 sdim=3 flow rules use the reference's axis-tracking principal stresses (exact for plane states);
@@ -407,10 +409,14 @@ class Material(object):
     # ------------------------------------------------------------------ texture materials
     # what the reference does where this engine refuses a texture material
     _TEX_REFUSALS = {
-        'calc_fgrad': 'the reference raises AttributeError there (self.self.scale_seq, material.py:811)',
-        'ML_full_yf': "the reference raises ValueError there: its calls of calc_yf pass no texture (material.py:475-491)",
-        'response': 'the reference raises ValueError in its first calc_yf call, which passes no texture (material.py:252)',
-        'response_batch': 'the reference has no response for a texture material: its calc_yf calls pass no texture (material.py:252)',
+        'calc_fgrad': 'the reference raises AttributeError there (self.self.scale_seq, material.py:811); calc_fgrad(sig, tex=) '
+                      'runs the gradient of this engine (DESIGN.md §32)',
+        'ML_full_yf': "the reference raises ValueError there: its calls of calc_yf pass no texture (material.py:475-491); "
+                      "ML_full_yf(sig, tex=) runs the search at a texture (DESIGN.md §32)",
+        'response': 'the reference raises ValueError in its first calc_yf call, which passes no texture (material.py:252); '
+                    'response(..., tex=) runs the update at a texture (DESIGN.md §32)',
+        'response_batch': 'the reference has no response for a texture material: its calc_yf calls pass no texture '
+                          '(material.py:252); response_batch(..., tex=) runs the update at a texture (DESIGN.md §32)',
         'calc_hessian': 'the reference rescales the Hessian of the scaler-standardised features by 1 / scale_seq**2, and '
                         'scale_seq is not a feature scale of a texture material (material.py:952-960)',
         'calc_properties': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343)',
@@ -464,6 +470,47 @@ class Material(object):
                             self.std_scaler.scale_, dev_only=self.dev_only)
             ctx._tex_key = key
         return ctx
+
+    def _tex_flow_ok(self, what):
+        """``tex=`` of the flow-rule methods needs a texture material, as calc_yf's does"""
+        if not getattr(self, 'txdat', False):
+            raise NotImplementedError('%s: tex needs a texture material (from_data on data sets with tx_data)' % what)
+        if not self._is_tex():
+            self._svc_refuse(what)
+
+    def _load_tex_flow(self, CV=None):
+        """The texture set and, beside it as material 0 of the shared point context, the analytic Hill / J2 record of this
+        material with the call's CV: elastic matrix, sy, khard and the form of seq for ML_full_yf(tex=) and response(tex=).
+        ``_tex_key`` and ``_content_key`` decide when either is re-sent."""
+        self._load_tex()
+        return self._load(CV, ana=True)
+
+    def _fgrad_tex(self, s0, epl, tex):
+        """calc_fgrad(sig, tex=): the stress derivative of calc_yf(sig, tex) on the device (plfx_tex_svc_fgrad).  With f the
+        standardised features, v_i the vectors and K_i = exp(-gamma |f - v_i|^2):
+        g_j = -2 gamma sum_i dual_i K_i (f_j - v_ij), a_j = g_j / scale_j for the six stress columns, and for a dev_only set
+        (a_0 + a_1 + a_2) / 3 is taken off a_0 .. a_2, the chain rule through the deviator.  With equal scales and zero means
+        on the six stress columns this is the gradient of the 6-feature SVC material up to rounding (for a dev_only set: as
+        far as the vectors are deviators, since the 6-feature gradient, like the reference's, is not projected).  khard is
+        set to 0 and msg['gradient'] as in the 6-feature branch."""
+        self._tex_flow_ok('calc_fgrad')
+        if epl is not None and np.shape(epl) != s0.shape:
+            raise ValueError('Parameter sig and epl must have the same shape.')
+        if s0.shape != (6,) and not (s0.ndim == 2 and s0.shape[1] == 6):
+            raise ValueError('Unknown format of stress in calc_fgrad')
+        s, single = self._voigt(s0, 'calc_fgrad')
+        t = self._tex_rows(tex, len(s), 'calc_fgrad')
+        a = self._load_tex().tex_svc_fgrad(s, t)
+        self.khard = 0.
+        self.msg['gradient'] = 'gradient to ML_yf'
+        return a[0] if single else a
+
+    def _tex_no_hardening(self, what, epl):
+        """texture together with work hardening is not built: the device call of ML_full_yf(tex=) takes no plastic strain,
+        so the flow stress is sy -- which is sy + khard peeq whenever khard or the plastic strain is zero"""
+        if epl is not None and self.khard and np.any(np.asarray(epl, dtype=float) != 0.):
+            raise NotImplementedError('%s: a plastic strain together with khard = %g on a texture material; texture and work '
+                                      'hardening are not combined' % (what, self.khard))
 
     def set_tex_svc(self, support_vectors, dual_coef, intercept, gamma, mean, scale, dev_only=False, C=None):
         """Install a trained texture SVC on a material that ``from_data`` made a texture material: standardised support
@@ -736,9 +783,13 @@ class Material(object):
             raise ValueError("SVM is trained on texture data but no texture data was provided to this function.")
         return self.calc_yf(float(x) * np.asarray(su, dtype=float), epl=epl, tex=tex)
 
-    def ML_full_yf(self, sig, epl=None, ld=None, verb=True, **kw):
+    def ML_full_yf(self, sig, epl=None, ld=None, verb=True, tex=None, **kw):
         """Distance of a stress to the ML yield locus along its ray / the loading direction
-        (material.py:414-516).  Accepts a single stress like the reference, or (N,6)."""
+        (material.py:414-516).  Accepts a single stress like the reference, or (N,6).  EXTENSION: a texture material takes
+        ``tex``, (tdim,) or (N, tdim): the same search on calc_yf(x su, tex) with seq the J2 / Hill form of the material and
+        the flow stress sy + khard peeq; ``ld`` is not offered together with ``tex``."""
+        if tex is not None:
+            return self._full_yf_tex(sig, epl, ld, verb, tex)
         self._tex_refuse('ML_full_yf')
         if not self.ML_yf:
             raise AttributeError('ML_full_yf: material has no trained ML yield function')
@@ -758,8 +809,28 @@ class Material(object):
                           'conservative estimate seq-0.85*sflow returned' % int(np.sum(st != 0)))
         return f[0] if single else f
 
-    def calc_fgrad(self, sig, epl=None, seq=None, ana=False, **kw):
-        """Gradient of the yield function w.r.t. stress (material.py:704-858)."""
+    def _full_yf_tex(self, sig, epl, ld, verb, tex):
+        self._tex_flow_ok('ML_full_yf')
+        if ld is not None:
+            raise NotImplementedError('ML_full_yf: a loading direction ld together with tex is not offered')
+        s = np.asarray(sig, dtype=float)
+        if s.shape != (6,) and not (s.ndim == 2 and s.shape[1] == 6):
+            raise ValueError('Only individual stress tensors supported in material.ML_full_yf. '
+                             'Shape of argument is {}'.format(s.shape))
+        s, single = self._voigt(s, 'ML_full_yf')
+        t = self._tex_rows(tex, len(s), 'ML_full_yf')
+        self._tex_no_hardening('ML_full_yf', epl)
+        f, st = self._load_tex_flow().tex_svc_full_yf(s, t)
+        if verb and np.any(st != 0):
+            warnings.warn('ML_full_yf: Could not bracket / locate the yield locus for %d stress(es); '
+                          'conservative estimate seq-0.85*sflow returned' % int(np.sum(st != 0)))
+        return f[0] if single else f
+
+    def calc_fgrad(self, sig, epl=None, seq=None, ana=False, tex=None, **kw):
+        """Gradient of the yield function w.r.t. stress (material.py:704-858).  EXTENSION: a texture material takes ``tex``,
+        (tdim,) or (N, tdim), and returns the stress derivative of ``calc_yf(sig, tex=)`` (see ``_fgrad_tex``)."""
+        if tex is not None and not ana:
+            return self._fgrad_tex(np.asarray(sig, dtype=float), epl, tex)
         if self.ML_yf and not ana:
             self._tex_refuse('calc_fgrad')
         s0 = np.asarray(sig, dtype=float)
@@ -920,9 +991,11 @@ class Material(object):
                         raise ValueError('Parameter sig and epl must have the same shape.')
         return self._load().hessian(0, np.ascontiguousarray(s), e) / self.scale_seq
 
-    def response(self, sig, epl, deps, CV, maxit=50):
+    def response(self, sig, epl, deps, CV, maxit=50, tex=None):
         """Elastic-predictor / plastic-corrector update of one material point (material.py:207-346).
-        Returns ``fy1, sig, depl, grad_stiff``; ``msg['nsteps']`` is set as in the reference."""
+        Returns ``fy1, sig, depl, grad_stiff``; ``msg['nsteps']`` is set as in the reference.  EXTENSION: a texture
+        material takes ``tex`` (tdim,): the same update with calc_yf, ML_full_yf and calc_fgrad at that texture
+        (DESIGN.md §32)."""
         sig = np.asarray(sig, dtype=float)
         sh = sig.shape
         if sh != (6,) and sh != (3,):
@@ -930,6 +1003,16 @@ class Material(object):
                              'Shape of argument is {}'.format(sh))
         if sh == (3,):
             raise NotImplementedError('response: pass the Voigt stress (6,); (3,) principal input is not supported')
+        if tex is not None:
+            self._tex_flow_ok('response')
+            maxit = int(maxit)
+            if maxit < 1:
+                raise ValueError('response: maxit must be >= 1')
+            t = self._tex_rows(tex, 1, 'response')
+            fy, so, dp, ct, ns = self._load_tex_flow(CV).tex_svc_response(
+                sig[None, :], np.asarray(epl, dtype=float)[None, :], np.asarray(deps, dtype=float)[None, :], t, maxit=maxit)
+            self.msg['nsteps'] = int(ns[0])
+            return fy[0], so[0], dp[0], ct[0].reshape(6, 6)
         self._tex_refuse('response')
         self._no_svr_gradient('response')
         self._no_flow_rule()
@@ -952,10 +1035,22 @@ class Material(object):
         self.msg['nsteps'] = int(ns[0])
         return fy[0], so[0], dp[0], ct[0].reshape(6, 6)
 
-    def response_batch(self, sig, epl, deps, CV, khard_in=None, return_khard=False):
+    def response_batch(self, sig, epl, deps, CV, khard_in=None, return_khard=False, tex=None):
         """``response`` on (N,6) arrays in one launch (extension; same numbers point by point).  ``khard_in`` /
         ``return_khard``: for a material that follows the SVR flow rule (``enable_svr_flow``), the hardening modulus of
-        every point on entry (default: ``khard``) and, appended to the result, on exit; ``khard`` itself is left alone."""
+        every point on entry (default: ``khard``) and, appended to the result, on exit; ``khard`` itself is left alone.
+        A texture material takes ``tex``, (tdim,) shared by the points or (N, tdim); a point with a non-finite input comes
+        back as NaN with nsteps = -1."""
+        if tex is not None:
+            self._tex_flow_ok('response_batch')
+            if khard_in is not None or return_khard:
+                raise ValueError('response_batch: khard_in / return_khard are not offered together with tex')
+            s = np.asarray(sig, dtype=float)
+            if s.ndim != 2 or s.shape[1] != 6 or np.shape(epl) != s.shape or np.shape(deps) != s.shape:
+                raise ValueError('response_batch: sig, epl and deps of shape (N, 6) expected with tex')
+            t = self._tex_rows(tex, len(s), 'response_batch')
+            fy, so, dp, ct, ns = self._load_tex_flow(CV).tex_svc_response(s, epl, deps, t)
+            return fy, so, dp, ct.reshape(-1, 6, 6), ns
         self._tex_refuse('response_batch')
         self._no_svr_gradient('response_batch')
         if khard_in is not None or return_khard:
@@ -967,22 +1062,25 @@ class Material(object):
         fy, so, dp, ct, ns = self._load(CV).response(sig, epl, deps)
         return fy, so, dp, ct.reshape(-1, 6, 6), ns
 
-    def epl_dot(self, sig, epl, Cel, deps, **kw):
-        """Plastic strain increment relaxing the stress to the yield locus (material.py:1009-1055)."""
+    def epl_dot(self, sig, epl, Cel, deps, tex=None, **kw):
+        """Plastic strain increment relaxing the stress to the yield locus (material.py:1009-1055); ``tex`` (tdim,) for a
+        texture material."""
         sig = np.asarray(sig, dtype=float)
         Cel = np.asarray(Cel, dtype=float)
         deps = np.asarray(deps, dtype=float)
-        yfun = self.calc_yf(sig + Cel @ deps, epl=epl)
+        yfun = self.calc_yf(sig + Cel @ deps, epl=epl, tex=tex)
         if yfun <= yf_tolerance:
             return np.zeros(6)
-        a = self._flow_normal(sig, epl)
+        a = self._flow_normal(sig, epl, tex)
         hh = a @ Cel @ a + self.khard
         return (a @ Cel @ deps / hh) * a
 
-    def _flow_normal(self, sig, epl=None):
+    def _flow_normal(self, sig, epl=None, tex=None):
         """Normal of the flow rule as epl_dot / C_tan take it: calc_fgrad of the Voigt stress for sdim = 6; for sdim = 3 the
         gradient w.r.t. the PRINCIPAL stresses in the normal Voigt rows, shear rows zero (material.py:1044-1047, 1079-1081) --
         not calc_fgrad's form for a (6,) stress of such a material (see there)."""
+        if tex is not None:
+            return self.calc_fgrad(sig, tex=tex)
         if self.sdim == 3 and not (self.tresca or self.barlat):
             s, _ = self._voigt(sig, 'calc_fgrad')
             if not self.ML_yf:
@@ -990,13 +1088,13 @@ class Material(object):
             return self._load(ana=not self.ML_yf).fgrad(0, self._princ_rows(s))[0]
         return self.calc_fgrad(sig) if epl is None else self.calc_fgrad(sig, epl=np.asarray(epl, dtype=float))
 
-    def C_tan(self, sig, Cel, epl=None):
-        """Continuum tangent stiffness (material.py:1057-1086)."""
+    def C_tan(self, sig, Cel, epl=None, tex=None):
+        """Continuum tangent stiffness (material.py:1057-1086); ``tex`` (tdim,) for a texture material."""
         Cel = np.asarray(Cel, dtype=float)
         # the reference evaluates calc_fgrad(sig, epl=epl) with zeros when epl is None (material.py:1076-1082): for a
         # work-hardening SVC the plastic strain is part of the feature vector and the call sets self.khard used below
         epl = np.zeros(self.sdim) if epl is None else np.asarray(epl, dtype=float)
-        a = self._flow_normal(np.asarray(sig, dtype=float), epl)
+        a = self._flow_normal(np.asarray(sig, dtype=float), epl, tex)
         ca = Cel @ a
         return Cel - np.outer(ca, ca) / (a @ ca + self.khard)
 

@@ -8,7 +8,13 @@ stream (timing family 0, plfx_timing_get): one warm-up call, then the median of 
 beside it.  Every step runs in a child process of its own under its own time limit, and nothing more is started after one
 that fails.  One JSON line per step.
 
-    python tools/texture_bench.py [--reps 11] [--limit 240]
+--flow times the flow rule and the stress update instead: calc_fgrad(tex=) (k_tex_fgrad) at 1 point and
+at 100 000 points with a shared texture and with one texture per row -- beside calc_yf(tex=) at the same 100 000 points, whose
+pass over the vectors the gradient repeats with six more FMAs per vector -- and response_batch(tex=) (k_tex_response) at 1
+and at 10 000 plastic points: stresses on the yield locus of texture 2 with an oblique strain increment of 1.5e-3, which the
+update sub-divides.
+
+    python tools/texture_bench.py [--flow] [--reps 11] [--limit 240]
 """
 import argparse
 import json
@@ -25,6 +31,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 STEPS = ('loci:6', 'loci:100', 'loci:7000', 'yf:1', 'yf:100000')
+FLOW_STEPS = ('fgrad:1', 'fgrad:100000', 'resp:1', 'resp:10000')
 DESC = 'GSH_3'
 
 
@@ -83,6 +90,33 @@ def step(name, reps):
                    wall_ratio=p_wall / k_wall, kernel_ratio=p_ms / k_ms,
                    same_bits=bool(np.array_equal(FE.sig_eq_j2((snorm[None] * x[:, :, None]).reshape(-1, 6)).reshape(x.shape)[st == 0],
                                                  seq[st == 0]) and np.all(np.isnan(x[st != 0]))))
+    elif kind == 'fgrad':
+        u = rng.normal(size=(n, 6))
+        sig = u / np.linalg.norm(u, axis=1)[:, None] * 100.
+        tid = rng.integers(0, 6, size=n)
+        a1, s_ms, s_wall, s_l = timed(lambda: m.calc_fgrad(sig, tex=tex6[2]))
+        a2, r_ms, r_wall, r_l = timed(lambda: m.calc_fgrad(sig, tex=tex6[tid]))
+        y1, y_ms, y_wall, y_l = timed(lambda: m.calc_yf(sig, tex=tex6[2]))
+        assert s_l == 1 and r_l == 1 and y_l == 1 and np.all(np.isfinite(a1)) and np.all(np.isfinite(a2))
+        res.update(points=n, shared_texture_kernel_ms=s_ms, shared_texture_wall_ms=s_wall, texture_per_row_kernel_ms=r_ms,
+                   texture_per_row_wall_ms=r_wall, calc_yf_shared_texture_kernel_ms=y_ms, calc_yf_shared_texture_wall_ms=y_wall,
+                   kernel_ratio_to_calc_yf=s_ms / y_ms)
+    elif kind == 'resp':
+        cand = np.array(z['probe_sig'])
+        import yield_locus_cases as YC
+        su = cand / YC.j2(cand)[:, None]
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            x = m.yield_scale(su, tex=tex6[2])
+        on = (x[:, None] * su)[np.isfinite(x)]
+        sig = np.ascontiguousarray(on[np.arange(n) % len(on)])
+        v = rng.normal(size=(n, 6))
+        deps = 1.5e-3 * v / np.linalg.norm(v, axis=1)[:, None]
+        epl = np.zeros((n, 6))
+        CV = np.array(m.CV)
+        out, k_ms, k_wall, k_l = timed(lambda: m.response_batch(sig, epl, deps, CV, tex=tex6[2]))
+        assert k_l == 1 and np.all(np.isfinite(out[1]))
+        res.update(points=n, sub_divided=int(np.sum(out[4] == 49)), kernel_ms=k_ms, wall_ms=k_wall)
     else:
         u = rng.normal(size=(n, 6))
         sig = u / np.linalg.norm(u, axis=1)[:, None] * 100.
@@ -102,13 +136,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--reps', type=int, default=11)
     ap.add_argument('--limit', type=int, default=240, help='time limit of one step in seconds')
+    ap.add_argument('--flow', action='store_true', help='time calc_fgrad(tex=) and response_batch(tex=) instead')
     ap.add_argument('--step', default='', help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
         return step(a.step, a.reps)
     if a.reps < 10:
         ap.error('--reps must be at least 10 (median of >= 10 launches)')
-    for name in STEPS:   # a fresh child per step, each under its own limit; stop at the first that fails
+    for name in (FLOW_STEPS if a.flow else STEPS):   # a fresh child per step, each under its own limit; stop at the first that fails
         rc = subprocess.call(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__),
                               '--step', name, '--reps', str(a.reps)])
         if rc != 0:
