@@ -359,6 +359,23 @@ int plfx_bc_info(plfx_ctx *ctx, int64_t *rhs_rows_only, int64_t *dinv_kept, int6
  * for bit either way.  plfx_sweep called from outside plfx_load_step always stores every element. */
 int plfx_dead_store_info(plfx_ctx *ctx, int64_t *armed_sweeps, int64_t *tangents_rewritten_in_armed_sweeps,
                          int64_t *test_only_starts, int64_t *test_only_retries);
+/* Plane columns (one GPU, no strip, no communicator; PLFX_PLANE_COLS=0 or PLFX_REUSE=0 at plfx_create:
+ * off).  Every model here is a plane model: the yz / zx shears (Voigt columns 3 and 4) of sig, epl, res_sig, res_depl are zero,
+ * and elastic and analytic Hill / J2 materials whose CV does not couple those shears to the rest keep them zero.  While that
+ * holds (*mode_on = 1) the Hill sweep and the state update neither load nor store these columns (plane_sweeps, plane_updates:
+ * launches of the plane kernels since plfx_create).  The mode is switched on by plfx_state_reset / plfx_set_mesh alone and goes
+ * off, until the next reset, for the reason in *switched_off_by (PLFX_PLANE_*).  Results are the same bit for bit either way,
+ * but for the sign of zeros in columns 3 and 4 of res_depl. */
+enum {
+    PLFX_PLANE_ON = 0,          /* not switched off */
+    PLFX_PLANE_NEVER_ON = 1,    /* no state reset yet */
+    PLFX_PLANE_SWITCH = 2,      /* PLFX_PLANE_COLS=0 or PLFX_REUSE=0 */
+    PLFX_PLANE_SHARDED = 3,     /* the context owns a part of the mesh / strip / communicator */
+    PLFX_PLANE_MATERIALS = 4,   /* a material is not elastic / Hill6, couples the shears, or has a non-finite parameter */
+    PLFX_PLANE_STATE_SET = 5,   /* plfx_state_set delivered a non-zero in column 3 or 4 of sig, epl, res_sig or res_depl */
+    PLFX_PLANE_TANGENT_SET = 6  /* plfx_state_set of the tangents */
+};
+int plfx_plane_info(plfx_ctx *ctx, int *mode_on, int64_t *plane_sweeps, int64_t *plane_updates, int *switched_off_by);
 /* Which kernels run the 6-feature SVC materials (Material.response with an ML yield function, material.py:398-405 evaluates
  * any trained svm_yf): bit k of *row_materials = material k runs with 16 lanes per element / point (one launch per material
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read

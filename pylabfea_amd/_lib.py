@@ -66,7 +66,7 @@ SYMBOLS = [
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info',
-    'plfx_dead_store_info',
+    'plfx_dead_store_info', 'plfx_plane_info',
 ]
 
 _lib = None
@@ -736,6 +736,15 @@ class Context(object):
         a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self.lib.plfx_dead_store_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
         return a.value, b.value, r.value, d.value
+
+    PLANE_OFF_REASONS = ('on', 'no state reset yet', 'switch', 'sharded', 'materials', 'state_set', 'tangent set')
+
+    def plane_info(self):
+        """(plane-column mode on, launches of the plane Hill sweep, launches of the plane state update since the context was
+        created, why the mode is off: an index into PLANE_OFF_REASONS, 0 while it is on)"""
+        on, a, b, why = C.c_int(), C.c_int64(), C.c_int64(), C.c_int()
+        self._chk(self.lib.plfx_plane_info(self.h, C.byref(on), C.byref(a), C.byref(b), C.byref(why)))
+        return bool(on.value), a.value, b.value, why.value
 
     def svc_info(self):
         """(bit mask of the 6-feature SVC materials on the 16-lanes-per-element kernels, mask of those run one thread per

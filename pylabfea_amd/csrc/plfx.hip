@@ -279,6 +279,14 @@ struct plfx_ctx {
     // test_starts: a solve whose first test is expected to pass starts with k_cg_start_test (solve_start).
     bool dead_stores = true, test_starts = true, dead_arm = false, res_partial = false;
     long long n_dead_sweeps = 0, n_dead_tangents = 0, n_test_starts = 0, n_test_retries = 0;   // plfx_dead_store_info
+    // Plane columns (PLFX_PLANE_COLS=0 or PLFX_REUSE=0 at plfx_create: off).  plane_cols: columns 3 and 4 of sig, epl,
+    // res_sig, res_depl are zero-valued in memory in both buffers of the exchange, rows 4 and 5 of elfac are zero, and every
+    // material is elastic or analytic Hill / J2 with the yz / zx shears uncoupled (plane_mats_ok) -- the Hill sweep and the state
+    // update neither load nor store them.  Switched on by plfx_state_reset alone (which zero-fills all of these), switched off by
+    // whatever could put a non-zero there (plane_off), and then off until the next reset.
+    bool plane_switch = true, plane_mats_ok = false, plane_cols = false;
+    int plane_off_by = PLFX_PLANE_NEVER_ON;
+    long long n_plane_sweeps = 0, n_plane_updates = 0;   // plfx_plane_info
     // plfx_load_step tells the solver which of its two solves this is (site 0 predictor of the load step, 1 stiffness iteration;
     // -1 any other caller); first_test_hint[site]: the last solve of that kind was answered by the test of the plain warm start
     // -- the next one waits for that test before it enqueues the six launches of the interpolated start behind it
@@ -1781,6 +1789,8 @@ int plfx_create(int device, plfx_ctx **out)
         c->test_starts = v == 1 || v == 3;
     }
     if (!c->reuse) c->dead_stores = c->test_starts = false;
+    if (const char *e11 = getenv("PLFX_PLANE_COLS")) c->plane_switch = atoi(e11) != 0;
+    if (!c->reuse) c->plane_switch = false;
     if (const char *e9 = getenv("PLFX_PREDICT")) c->predict = atoi(e9) != 0;
     {
         const char *e5 = getenv("PLFX_MAILBOX");
@@ -1919,6 +1929,35 @@ int plfx_sync(plfx_ctx *c)
 static int ensure_eps(plfx_ctx *c);
 static int split_res_sig(plfx_ctx *c);
 
+// Plane columns.  The closure argument asks of every material of the table, used or not: elastic or analytic Hill /
+// J2 (the kinds whose gradient takes components 3 and 4 from components 3 and 4 alone), CV and SV exactly 0.0 between
+// {xx, yy, zz, xy} and {yz, zx}, and everything that multiplies a zero of those columns finite (0 * inf is not 0).
+static bool plane_materials_ok(const std::vector<MatDev> &mats)
+{
+    for (const MatDev &m : mats) {
+        if (m.kind != PLFX_ELASTIC && m.kind != PLFX_HILL6) return false;
+        for (int i : {0, 1, 2, 5})
+            for (int j : {3, 4})
+                if (m.CV[sym_idx(i, j)] != 0. || m.SV[sym_idx(i, j)] != 0.) return false;
+        for (const double *T : {m.CV, m.SV})
+            if (!std::isfinite(T[sym_idx(3, 3)]) || !std::isfinite(T[sym_idx(4, 4)]) || !std::isfinite(T[sym_idx(3, 4)])) return false;
+        if (!std::isfinite(m.hill[3]) || !std::isfinite(m.hill[4]) || !std::isfinite(m.sy) || !std::isfinite(m.khard) ||
+            !std::isfinite(m.d0))
+            return false;
+    }
+    return !mats.empty();
+}
+
+// the mode goes off and stays off until the next plfx_state_reset (the first reason is the one reported)
+static void plane_off(plfx_ctx *c, int why)
+{
+    if (c->plane_cols) c->plane_off_by = why;
+    c->plane_cols = false;
+}
+
+// (a strip or a communicator can be set up after the reset: asked at every launch)
+static bool plane_active(const plfx_ctx *c) { return c->plane_cols && !c->strip.on && !comm_active(c) && !c->sharded; }
+
 int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
 {
     if (!c || !c->stream) return PLFX_ERR_STATE;
@@ -1938,6 +1977,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     c->has_svc = c->has_svc3 = c->has_analytic = c->has_elastic = c->has_princ = false;
     c->has_barlat = false;
     c->has_svcwh = false;
+    c->plane_mats_ok = false;
     c->n_noflow = 0;
     c->svc_lds_need = 0;
     c->svc_row_all = c->svc_row_lds = c->svc6_mask = c->svcwh_mask = 0;
@@ -2067,6 +2107,8 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         }
     }
     c->nmat = nmat;
+    c->plane_mats_ok = plane_materials_ok(c->hmat);
+    if (!c->plane_mats_ok) plane_off(c, PLFX_PLANE_MATERIALS);
     int rc = dalloc(c, &c->dmat, (size_t)nmat);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->dmat, c->hmat.data(), sizeof(MatDev) * nmat, hipMemcpyHostToDevice, c->stream));
@@ -3727,6 +3769,17 @@ int plfx_dead_store_info(plfx_ctx *c, int64_t *armed_sweeps, int64_t *tangents_r
     return PLFX_OK;
 }
 
+int plfx_plane_info(plfx_ctx *c, int *mode_on, int64_t *plane_sweeps, int64_t *plane_updates, int *switched_off_by)
+{
+    if (!c) return PLFX_ERR_ARG;
+    const bool on = plane_active(c);
+    if (mode_on) *mode_on = on ? 1 : 0;
+    if (plane_sweeps) *plane_sweeps = c->n_plane_sweeps;
+    if (plane_updates) *plane_updates = c->n_plane_updates;
+    if (switched_off_by) *switched_off_by = on ? PLFX_PLANE_ON : c->plane_cols ? PLFX_PLANE_SHARDED : c->plane_off_by;
+    return PLFX_OK;
+}
+
 int plfx_sweep_launch_info(plfx_ctx *c, int64_t *heavy_skipped, int64_t *heavy_recovered)
 {
     if (!c) return PLFX_ERR_ARG;
@@ -4041,6 +4094,12 @@ int plfx_state_reset(plfx_ctx *c)
         hipLaunchKernelGGL(k_init_M_all, dim3((c->nel_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
                            c->dmat, c->dcls, c->nel_total, c->dcls_all, c->Mel);
     HIPCHK(c, hipGetLastError());
+    // plane columns: the four state arrays are zero from the memsets above; rows 4 and 5 of the factors, which tan_alloc and
+    // k_init_tangent leave as they are, are zeroed here -- the invariant holds from this point on
+    c->plane_off_by = !c->plane_switch ? PLFX_PLANE_SWITCH : (c->sharded || c->strip.on || comm_active(c)) ? PLFX_PLANE_SHARDED :
+                      !c->plane_mats_ok ? PLFX_PLANE_MATERIALS : PLFX_PLANE_ON;
+    c->plane_cols = c->plane_off_by == PLFX_PLANE_ON;
+    if (c->plane_cols) HIPCHK(c, hipMemsetAsync(c->elfac + 4 * ne, 0, 16 * ne, c->stream));
     c->assembled = false, c->M_dirty = true;
     c->x_is_du = false;
     c->rhs_rows_ok = c->dinv_ok = false;   // (a new history starts with one full k_bc_finish)
@@ -4198,6 +4257,15 @@ int plfx_state_set(plfx_ctx *c, int which, const double *in)
             for (int i = 0; i < 6; i++)
                 for (int j = i; j < 6; j++) t[(size_t)sym_idx(i, j) * n + e] = in[36 * e + 6 * i + j];
     }
+    if (c->plane_cols && (which == 0 || which == 2 || which == 3 || which == 4)) {   // a non-zero in column 3 or 4 ends the plane mode
+        const double *c34 = t.data() + 3 * n;
+        for (size_t i = 0; i < 2 * n; i++)
+            if (c34[i] != 0.) {
+                plane_off(c, PLFX_PLANE_STATE_SET);
+                break;
+            }
+    }
+    if (which == 5) plane_off(c, PLFX_PLANE_TANGENT_SET);   // (conservative: a tangent from outside may couple the shears)
     HIPCHK(c, hipMemcpyAsync(p, t.data(), 8 * comps * n, hipMemcpyHostToDevice, c->stream));
     if (which == 5) {  // every element's tangent is now held in full form
         c->M_dirty = true;
@@ -4761,10 +4829,16 @@ int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
     const int g = grid_for(c->nel, SUMPART);
     bool swap;
     if ((rc = finish_mode(c, &swap))) return rc;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
-                       c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
-                       tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, c->part_g,
-                       c->strip.on ? c->strip.eown_lo : 0, c->strip.on ? c->strip.eown_hi : 0x7fffffff);
+    if (plane_active(c)) {   // 
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state_plane<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
+                           c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
+                           tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, c->part_g);
+        c->n_plane_updates++;
+    } else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
+                           c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
+                           tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, c->part_g,
+                           c->strip.on ? c->strip.eown_lo : 0, c->strip.on ? c->strip.eown_hi : 0x7fffffff);
     finish_done(c, swap);
     const int n = c->fin_n;
     const int tot = 2 * n + 18;
@@ -5669,8 +5743,12 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                   c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,       \
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh)) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), first, 0u, dead);
+        if (plane_active(c)) {   // (the same timing family)
+            hipLaunchKernelGGL(k_sweep_light_plane, dim3(c->grid_el), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead);
+            c->n_plane_sweeps++;
+        } else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
+                               SWEEP_ARGS(0), first, 0u, dead);
         first = 0;
     }
     if (c->has_princ) {
@@ -6092,10 +6170,17 @@ int plfx_update_state(plfx_ctx *c)
     }
     bool swap;
     if ((rc = finish_mode(c, &swap))) return rc;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
-                       c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                       (const double2 *)c->u, c->sig, c->epl, tan_store(c), c->res_sig,
-                       c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, (double *)nullptr);
+    if (plane_active(c)) {   // 
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state_plane<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
+                           c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
+                           (const double2 *)c->u, c->sig, c->epl, tan_store(c), c->res_sig,
+                           c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, (double *)nullptr);
+        c->n_plane_updates++;
+    } else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
+                           c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
+                           (const double2 *)c->u, c->sig, c->epl, tan_store(c), c->res_sig,
+                           c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, (double *)nullptr);
     HIPCHK(c, hipGetLastError());
     finish_done(c, swap);
     return PLFX_OK;

@@ -890,13 +890,20 @@ __device__ __forceinline__ int tan_load_fac(const TanStore &ts, int nel, int e, 
     return form;
 }
 
+// Plane columns: what a plane model with elastic / analytic Hill materials can fill, and so what the PLANE forms
+// below load and store
+constexpr __device__ __host__ bool plane_col(int k) { return k != 3 && k != 4; }   // Voigt components a plane model can fill
+constexpr __device__ __host__ bool plane_fac(int k) { return k != 4 && k != 5; }   // rows of TanStore::fac: f0, ca[0..5]
+
 // Tail of the per-element sweep (model.py:1343-1357): store the response, yield-function ratio,
 // tangent test ||elstiff - Ct||_F > 1e-3 and tangent / stiffness-generator refresh.
 // The new tangent Ct comes in form `form` (response_light<true>: TAN_CV for st 0 with Ct unused, TAN_FAC for st 1 with the
 // factors in Ct[0..6]; the corrector: TAN_FULL).  The stored tangent comes as its form tag `oform` and, for TAN_FAC, its
 // factors ofac[0..6], so that a streaming caller can have them in flight long before (k_sweep_light); the 21 entries of a
 // TAN_FULL element (cold path) are loaded here.  omax: the element's max_steps so far.
-template <bool MAY_SKIP = false>
+// PLANE (k_sweep_light_plane): columns 3 and 4 of res_sig / res_depl and rows 4 and 5 of the factors are zero-valued
+// in memory and stay so -- their stores are left out.  A template parameter for the reason MAY_SKIP is one.
+template <bool MAY_SKIP = false, bool PLANE = false>
 __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &m, int e, int nel,
                                                const double *s, const double *ep, const double *depl,
                                                int form, const double *Ct, double fy, int ns, const TanStore &ts,
@@ -913,6 +920,7 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
     if (!late) {
 #pragma unroll
         for (int k = 0; k < 6; k++) {
+            if (PLANE && !plane_col(k)) continue;
             res_sig[(size_t)k * nel + e] = s[k];
             res_depl[(size_t)k * nel + e] = depl[k];
         }
@@ -941,6 +949,7 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
     if (late && !(hh > 1.e-3)) {
 #pragma unroll
         for (int k = 0; k < 6; k++) {
+            if (PLANE && !plane_col(k)) continue;
             res_sig[(size_t)k * nel + e] = s[k];
             res_depl[(size_t)k * nel + e] = depl[k];
         }
@@ -958,7 +967,8 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
             for (int k = 0; k < 21; k++) ts.full[(size_t)k * nel + e] = Dnew[k];
         } else if (form == TAN_FAC) {
 #pragma unroll
-            for (int k = 0; k < 7; k++) ts.fac[(size_t)k * nel + e] = Ct[k];
+            for (int k = 0; k < 7; k++)
+                if (!PLANE || plane_fac(k)) ts.fac[(size_t)k * nel + e] = Ct[k];
         }
         double M[6];
         tangent_to_M(Dnew, c.kappa, M);
@@ -978,6 +988,8 @@ struct SweepIn {
 };
 
 // e < nel is the predicate of every load: no address beyond the arrays is formed for the tile past the end
+// PLANE: s[3], s[4], ep[3], ep[4], fac[4], fac[5] are not loaded and stay 0. (what memory holds there)
+template <bool PLANE = false>
 __device__ __forceinline__ void sweep_in_load(SweepIn &in, long long e, int nel, int e_off, const int32_t *__restrict__ cls,
                                               const int32_t *__restrict__ conn, const double *__restrict__ sig,
                                               const double *__restrict__ epl, const TanStore &ts,
@@ -991,13 +1003,15 @@ __device__ __forceinline__ void sweep_in_load(SweepIn &in, long long e, int nel,
         for (int k = 0; k < 4; k++) in.n[k] = conn[ge * 4 + k];
 #pragma unroll
         for (int k = 0; k < 6; k++) {
+            if (PLANE && !plane_col(k)) continue;
             in.s[k] = sig[(size_t)k * nel + e];
             in.ep[k] = epl[(size_t)k * nel + e];
         }
         in.form = ts.tag[e];
         in.ms = max_steps[e];
 #pragma unroll
-        for (int k = 0; k < 7; k++) in.fac[k] = ts.fac[(size_t)k * nel + e];
+        for (int k = 0; k < 7; k++)
+            if (!PLANE || plane_fac(k)) in.fac[k] = ts.fac[(size_t)k * nel + e];
     }
 }
 
@@ -1208,6 +1222,69 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
             }
         }
         // compact the elements that need the 50-sub-step corrector: one atomic per wave
+        const unsigned long long mask = __ballot(heavy);
+        if (mask) {
+            const int lane = threadIdx.x & 63;
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&flags[2], __popcll(mask));
+            base = __shfl(base, 0, 64);
+            if (heavy) list[base + __popcll(mask & ((1ull << lane) - 1ull))] = e;
+        }
+    }
+    post_block_flags(changed, nconv, bflags);
+}
+
+// k_sweep_light<1> of a plane model whose materials are all elastic or analytic Hill / J2 (plane_cols in plfx.hip):
+// the yz / zx shears -- columns 3 and 4 of sig, epl, res_sig, res_depl, rows 4 and 5 of the tangent factors -- are zero in
+// memory and the return mapping keeps them zero, so they are neither loaded nor stored; the arithmetic is the one above, on
+// zeros held in registers.  A kernel of its own and not a parameter of k_sweep_light: a shared body behind two entry points
+// changed the registers and the scratch of k_sweep_light<1>, <2>, <5>, <6> and <7>, which must stay what they are.  What
+// differs from the text above: the PLANE forms of sweep_in_load and sweep_epilogue, and KIND = 1 written out (no SVC tables,
+// no hardening modulus per material point).
+__global__ void __launch_bounds__(BLOCK, PLFX_SWEEP_WAVES < 2 ? 2 : PLFX_SWEEP_WAVES)
+k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
+                    int lds_doubles, int nel, int e_off, const int32_t *__restrict__ conn,
+                    const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
+                    const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts,
+                    double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
+                    int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, unsigned skip_mask, int dead_ok)
+{
+    __shared__ SweepTables tb;
+    stage_tables(tb, gmat, nmat, gcls, ncls);
+    __syncthreads();
+    int changed = 0, nconv = 0;
+    const int nb = gridDim.x;
+    int t = xcd_tile(blockIdx.x, nb);
+    SweepIn nx;
+    sweep_in_load<true>(nx, (long long)t * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+    for (; t * BLOCK < nel; t += nb) {
+        const int e = t * BLOCK + threadIdx.x;
+        bool heavy = false;
+        const SweepIn in = nx;   // (in flight since the previous pass; the next tile's streams go out now, as in k_sweep_light<1>)
+        sweep_in_load<true>(nx, (long long)(t + nb) * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+        asm volatile("" ::: "memory");
+        if (e < nel) {
+            const ClassDev &c = tb.scls[in.cl];
+            const MatDev &m = tb.smat[c.mat];
+            if (m.kind == 0) {
+                if (first_kind) fyn[e] = 0.;
+            } else if (m.kind == 1 && !((skip_mask >> c.mat) & 1u)) {
+                double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
+                class_strain(c, du2, in.n[0], in.n[1], in.n[2], in.n[3], deps);
+#pragma unroll
+                for (int k = 0; k < 6; k++) {
+                    s[k] = in.s[k];
+                    ep[k] = in.ep[k];
+                }
+                const YfOf<1>::type yf = make_policy<1>(m, nullptr, nullptr, m.khard);
+                const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
+                if (st == 2)
+                    heavy = true;  // (k_sweep_heavy<1> stores all six columns, zero-valued in columns 3 and 4)
+                else
+                    sweep_epilogue<true, true>(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, in.ms, Mel, mel_stride, res_sig,
+                                               res_depl, fyn, max_steps, nit, changed, nconv, -1., dead_ok);
+            }
+        }
         const unsigned long long mask = __ballot(heavy);
         if (mask) {
             const int lane = threadIdx.x & 63;
@@ -3021,13 +3098,14 @@ k_axpy_uf(size_t ndof, const double *__restrict__ du, const double *__restrict__
 // eps = class_strain(u) is formed for the sums only and not stored: k_eps_from_u writes the field when somebody asks for it
 // (ensure_eps, plfx.hip).  swap != 0 (every material plastic, a sweep wrote res_sig for every element since the last
 // exchange): the new sig IS res_sig, so it is only read for the sums and the host exchanges the two pointers behind the launch.
-template <int SUMS>
-__global__ void __launch_bounds__(BLOCK)
-k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off, const int32_t *__restrict__ conn,
-               const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
-               TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
-               int nonlin, int swap, double *__restrict__ part /* SUMS: [18][gridDim.x] volume-weighted sums of the new sig, eps, epl */,
-               int sum_lo = 0, int sum_hi = 0x7fffffff /* elements that enter the sums (strip: owned columns) */)
+// PLANE (k_update_state_plane): columns 3 and 4 of epl, res_depl, res_sig and (elastic branch) sig are zero in memory
+// and stay so -- neither loaded nor stored; the sums are formed by the same chain with the zeros in place.
+template <int SUMS, bool PLANE>
+__device__ __forceinline__ void
+update_state_body(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off, const int32_t *__restrict__ conn,
+                  const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
+                  TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
+                  int nonlin, int swap, double *__restrict__ part, int sum_lo, int sum_hi)
 {
     __shared__ SweepTables tb;
     stage_tables(tb, gmat, nmat, gcls, ncls);
@@ -3040,12 +3118,14 @@ k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
         const size_t ge = (size_t)e + e_off;
         const int cl = cls[e];
         const int n0 = conn[ge * 4], n1 = conn[ge * 4 + 1], n2 = conn[ge * 4 + 2], n3 = conn[ge * 4 + 3];
-        double po[6], rd[6] = {}, rs[6] = {};
+        double po[6] = {}, rd[6] = {}, rs[6] = {};
 #pragma unroll
-        for (int k = 0; k < 6; k++) po[k] = epl[(size_t)k * nel + e];
+        for (int k = 0; k < 6; k++)
+            if (!PLANE || plane_col(k)) po[k] = epl[(size_t)k * nel + e];
         if (nonlin) {
 #pragma unroll
             for (int k = 0; k < 6; k++) {
+                if (PLANE && !plane_col(k)) continue;
                 rd[k] = res_depl[(size_t)k * nel + e];
                 rs[k] = res_sig[(size_t)k * nel + e];
             }
@@ -3062,12 +3142,14 @@ k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
                 sn[k] = rs[k];
             }
 #pragma unroll
-            for (int k = 0; k < 6; k++) epl[(size_t)k * nel + e] = pn[k];
+            for (int k = 0; k < 6; k++)
+                if (!PLANE || plane_col(k)) epl[(size_t)k * nel + e] = pn[k];
         } else {  // el.sig += elstiff @ deps ; depl = 0 for elastic materials (model.py:1387-1388)
-            double de[6], D[21], ds[6], so[6];
+            double de[6], D[21], ds[6], so[6] = {};
             class_strain(c, du2, n0, n1, n2, n3, de);
 #pragma unroll
-            for (int k = 0; k < 6; k++) so[k] = sig[(size_t)k * nel + e];
+            for (int k = 0; k < 6; k++)
+                if (!PLANE || plane_col(k)) so[k] = sig[(size_t)k * nel + e];
             tan_load(ts, nel, e, m.CV, D);
             symv(D, de, ds);
 #pragma unroll
@@ -3078,7 +3160,8 @@ k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
         }
         if (!swap) {
 #pragma unroll
-            for (int k = 0; k < 6; k++) sig[(size_t)k * nel + e] = sn[k];
+            for (int k = 0; k < 6; k++)
+                if (!PLANE || plane_col(k)) sig[(size_t)k * nel + e] = sn[k];
         }
         if (SUMS && e >= sum_lo && e < sum_hi) {
             const double v = c.vel;
@@ -3091,6 +3174,29 @@ k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
         }
     }
     if (SUMS) block_sums_to_partials(acc, part);
+}
+
+template <int SUMS>
+__global__ void __launch_bounds__(BLOCK)
+k_update_state(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off, const int32_t *__restrict__ conn,
+               const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
+               TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
+               int nonlin, int swap, double *__restrict__ part /* SUMS: [18][gridDim.x] volume-weighted sums of the new sig, eps, epl */,
+               int sum_lo = 0, int sum_hi = 0x7fffffff /* elements that enter the sums (strip: owned columns) */)
+{
+    update_state_body<SUMS, false>(gmat, nmat, gcls, ncls, nel, e_off, conn, cls, du2, u2, sig, epl, ts, res_sig, res_depl, nonlin, swap, part,
+                                   sum_lo, sum_hi);
+}
+
+template <int SUMS>
+__global__ void __launch_bounds__(BLOCK)
+k_update_state_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off, const int32_t *__restrict__ conn,
+                     const int32_t *__restrict__ cls, const double2 *__restrict__ du2, const double2 *__restrict__ u2, double *__restrict__ sig, double *__restrict__ epl,
+                     TanStore ts, const double *__restrict__ res_sig, const double *__restrict__ res_depl,
+                     int nonlin, int swap, double *__restrict__ part)
+{
+    update_state_body<SUMS, true>(gmat, nmat, gcls, ncls, nel, e_off, conn, cls, du2, u2, sig, epl, ts, res_sig, res_depl, nonlin, swap, part,
+                                  0, 0x7fffffff);
 }
 
 // eps = class_strain(u) of every element: the stored field behind Element.eps and plfx_global_sums, written on demand (the

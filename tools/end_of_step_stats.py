@@ -34,7 +34,7 @@ def main(argv):
 
     def per_step(names):
         return [sum(e - a for a, e, k in s if k in names) / 1e3 for s in steps]
-    for label, names in (('k_update_state<1>', ('k_update_state<1>',)), ('k_gather2 + k_reduce_rows', ('k_gather2', 'k_reduce_rows')),
+    for label, names in (('k_update_state<1> / _plane<1>', ('k_update_state<1>', 'k_update_state_plane<1>')), ('k_gather2 + k_reduce_rows', ('k_gather2', 'k_reduce_rows')),
                          ('k_finish_out', ('k_finish_out',)), ('k_sweep_heavy<1>', ('k_sweep_heavy<1>',)), ('k_sweep_flags', ('k_sweep_flags',))):
         v = per_step(names)
         cnt = [sum(1 for _, _, k in s if k in names) for s in steps]
@@ -44,7 +44,7 @@ def main(argv):
         per = []
         for path, cname in ((argv[3], 'FETCH_SIZE'), (argv[4], 'WRITE_SIZE')):
             r = [(int(x['Start_Timestamp']), float(x['Counter_Value']) * 1024 / 1e6) for x in csv.DictReader(open(path))
-                 if x['Counter_Name'] == cname and short(x['Kernel_Name']) == 'k_update_state<1>']
+                 if x['Counter_Name'] == cname and short(x['Kernel_Name']) in ('k_update_state<1>', 'k_update_state_plane<1>')]
             r.sort()
             per.append([v for _, v in r][-n:])
         f, w = median(per[0]), median(per[1])

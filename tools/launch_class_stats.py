@@ -16,6 +16,10 @@ def short(name):
     return m.group(1).replace(' ', '') if m else name[:40]
 
 
+# the analytic Hill sweep under either of its names (k_sweep_light_plane: the plane-column form)
+SWEEP = ('k_sweep_light<1>', 'k_sweep_light_plane')
+
+
 def median(v):
     v = sorted(v)
     return v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
@@ -33,8 +37,8 @@ def main(argv):
     print('%d load steps; kernels per step median %g; span median %.1f us; busy median %.1f us'
           % (len(steps), median([len(s) for s in steps]), median([(s[-1][1] - s[0][0]) / 1e3 for s in steps]),
              median([sum(e - a for a, e, _ in s) / 1e3 for s in steps])))
-    sw = [[(e - a) / 1e3 for a, e, k in s if k == 'k_sweep_light<1>'] for s in steps]
-    print('k_sweep_light<1> launches per step: median %g' % median([len(x) for x in sw]))
+    sw = [[(e - a) / 1e3 for a, e, k in s if k in SWEEP] for s in steps]
+    print('k_sweep_light<1> / k_sweep_light_plane launches per step: median %g' % median([len(x) for x in sw]))
     for pos in range(int(max(len(x) for x in sw))):
         v = [x[pos] for x in sw if len(x) > pos]
         print('  sweep %d of the step: n=%d median %.2f us (min %.2f max %.2f)' % (pos + 1, len(v), median(v), min(v), max(v)))
@@ -47,7 +51,7 @@ def main(argv):
     if len(argv) > 4:
         # position of every sweep launch in its step, from the trace; the PMC passes run the same launches in the same order
         idx = {}
-        order = [i for i, r in enumerate(rows) if r[2] == 'k_sweep_light<1>']
+        order = [i for i, r in enumerate(rows) if r[2] in SWEEP]
         ends = [i for i, r in enumerate(rows) if r[2].startswith('k_update_state')]
         pos_of = []
         e = 0
@@ -59,21 +63,21 @@ def main(argv):
             pos_of.append(cnt)
             cnt += 1
         for path, cname in ((argv[3], 'FETCH_SIZE'), (argv[4], 'WRITE_SIZE')):
-            for kern in ('k_sweep_light<1>', 'k_cg_start<1>', 'k_cg_start_test<1>'):
+            for kern in (SWEEP, ('k_cg_start<1>',), ('k_cg_start_test<1>',)):
                 r = sorted((int(x['Start_Timestamp']), float(x['Counter_Value']) * 1024 / 1e6) for x in csv.DictReader(open(path))
-                           if x['Counter_Name'] == cname and short(x['Kernel_Name']) == kern)
+                           if x['Counter_Name'] == cname and short(x['Kernel_Name']) in kern)
                 v = [b for _, b in r]
                 if not v:
                     continue
-                if kern == 'k_sweep_light<1>' and len(v) == len(pos_of):
+                if kern is SWEEP and len(v) == len(pos_of):
                     tail = 2 * n
                     for pos in sorted(set(pos_of[-tail:])):
                         w = [v[i] for i in range(len(v) - tail, len(v)) if pos_of[i] == pos]
                         print('%s %s, sweep %d of the step (last %d launches): n=%d median %.2f MB (min %.2f max %.2f)'
-                              % (cname, kern, pos + 1, tail, len(w), median(w), min(w), max(w)))
+                              % (cname, ' / '.join(kern), pos + 1, tail, len(w), median(w), min(w), max(w)))
                 else:
                     w = v[-n:]
-                    print('%s %s (last %d dispatches of %d): median %.2f MB (min %.2f max %.2f)' % (cname, kern, len(w), len(v), median(w), min(w), max(w)))
+                    print('%s %s (last %d dispatches of %d): median %.2f MB (min %.2f max %.2f)' % (cname, kern[0], len(w), len(v), median(w), min(w), max(w)))
 
 
 if __name__ == '__main__':
