@@ -41,9 +41,14 @@ enum {
                          plfx_material.barlat_normal is set (native normal, extension) */
     PLFX_SVC3 = 6,    /* sdim=3 ML material: RBF-SVC on 2 features (seq_J2/scale - 1, polar angle/pi) of the
                          principal stresses, gradient through the Jacobian (material.py:779-807, 2331-2333) */
-    PLFX_SVC_WH = 7   /* RBF-SVC with work-hardening features (material.py:2342-2346): 15 features = 6 stress features, the
+    PLFX_SVC_WH = 7,  /* RBF-SVC with work-hardening features (material.py:2342-2346): 15 features = 6 stress features, the
                          plastic strain / scale_wh (6), accumulated strain, max. stress / scale_seq, flag (the last three are
                          zero on the path); the hardening modulus is read off the gradient (material.py:808-814) */
+    PLFX_SVC6_COLS = 8 /* RBF-SVC on 6 features with ONE SCALE PER STRESS COLUMN, x_j = s_j / scale_j (plfx_set_svc_cols), and
+                         the gradient of a dev_only set projected onto the deviator: a texture SVC bound to one texture
+                         (DESIGN section 34).  Fields of a PLFX_SVC6 record.  Runs on the 16-lane row kernels only: sweeps,
+                         calc_scf, plfx_response_batch, plfx_full_yf_batch; every other point function is
+                         PLFX_ERR_UNSUPPORTED for it */
 };
 
 /* error codes */
@@ -381,7 +386,7 @@ int plfx_plane_info(plfx_ctx *ctx, int *mode_on, int64_t *plane_sweeps, int64_t 
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read
  * from device memory otherwise -- no limit on the number of 6-feature SVC materials or of their support vectors;
  * bit k of *thread_materials = material k runs one thread per element / point (only when the row kernels are switched off
- * by PLFX_SVC_WAVE).  Launch counters of the sweep kernels of either form since plfx_create. */
+ * by PLFX_SVC_WAVE).  A PLFX_SVC6_COLS material is always among the row materials and never among the thread ones.  Launch counters of the sweep kernels of either form since plfx_create. */
 int plfx_svc_info(plfx_ctx *ctx, int *row_materials, int *thread_materials, int64_t *row_launches, int64_t *thread_launches);
 /* B matrices of element e at its 4 Gauss points, [4*6*8] (Element.calc_Bmat, model.py:439) */
 int plfx_get_bmat(plfx_ctx *ctx, int e, double *B);
@@ -630,6 +635,10 @@ int plfx_svr_predict_multi(plfx_ctx *ctx, int n, int d, const double *X, double 
 int plfx_set_svr_flow(plfx_ctx *ctx, int mat, int l, const double *X, const double *coef, const double *intercept,
                       double gamma, const double *feat_mean, const double *feat_scale, const double *out_mean,
                       const double *out_scale);
+/* The six column scales of material `mat`, a PLFX_SVC6_COLS record (any other kind: PLFX_ERR_UNSUPPORTED; without materials:
+ * PLFX_ERR_STATE): its features are x_j = s_j / scale[j].  plfx_set_materials sets every one to the record's scale_seq; the
+ * scales given here hold until the next plfx_set_materials.  A scale that is not finite or <= 0 is PLFX_ERR_ARG. */
+int plfx_set_svc_cols(plfx_ctx *ctx, int mat, const double scale[6]);
 /* rows of the rule attached to material `mat` (0: none) and the response launches that took the SVR kernel for it since
  * it was attached (either pointer may be NULL) */
 int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PLFX_LIB', os.path.join(_HERE, 'libplfx.so'))  # PLFX_LIB: kernel-variant experiments
 
 # yield-function kinds (include/plfx.h)
-ELASTIC, HILL6, PRINC3, SVC6, TRESCA, BARLAT, SVC3, SVC_WH = 0, 1, 2, 3, 4, 5, 6, 7
+ELASTIC, HILL6, PRINC3, SVC6, TRESCA, BARLAT, SVC3, SVC_WH, SVC6_COLS = 0, 1, 2, 3, 4, 5, 6, 7, 8
 
 # state ids of plfx_state_get/_set
 ST_SIG, ST_EPS, ST_EPL, ST_RES_SIG, ST_RES_DEPL, ST_ELSTIFF, ST_U, ST_F, ST_DU, ST_FYN, ST_MAXSTEPS, ST_KHARD = range(12)
@@ -67,6 +67,7 @@ SYMBOLS = [
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info',
     'plfx_dead_store_info', 'plfx_plane_info',
+    'plfx_set_svc_cols',
 ]
 
 _lib = None
@@ -159,8 +160,9 @@ def eig3_host(sig):
 
 def pack_material(kind, CV, E=0., nu=0., sy=0., khard=0., hill=None, drucker=0., svc=None, barlat=None,
                   barlat_exp=0., barlat_normal=False):
-    """Build a plfx_material record.  svc = dict(sv, dual, gamma, intercept, scale_seq, dev_only).
-    Returns (struct, keepalive) - keepalive holds the arrays the struct points to."""
+    """Build a plfx_material record.  svc = dict(sv, dual, gamma, intercept, scale_seq, dev_only); a SVC6_COLS record adds
+    scale_cols, its six column scales.  Returns (struct, keepalive) - keepalive holds the arrays the struct points to (and,
+    as its third entry, the column scales that Context.set_materials sends after the record)."""
     m = CMaterial()
     m.kind = int(kind)
     m.sdim = 3 if kind in (PRINC3, SVC3) else 6
@@ -192,6 +194,11 @@ def pack_material(kind, CV, E=0., nu=0., sy=0., khard=0., hill=None, drucker=0.,
         m.scale_wh = float(svc.get('scale_wh', 1.) or 1.)
         m.sv = sv.ctypes.data
         m.dual = dual.ctypes.data
+        if kind == SVC6_COLS:
+            cols = _f64(svc['scale_cols']).reshape(-1)
+            if cols.shape != (6,):
+                raise ValueError('pack_material: a SVC6_COLS record needs six column scales (scale_cols)')
+            keep.append(cols)
     return m, keep
 
 
@@ -254,6 +261,16 @@ class Context(object):
             self._keep.append(keep)
         self._chk(self.lib.plfx_set_materials(self.h, len(records), arr))
         self.nmat = len(records)
+        for i, (m, keep) in enumerate(records):   # the column scales of SVC6_COLS records (pack_material)
+            if m.kind == SVC6_COLS:
+                self.set_svc_cols(i, keep[2])
+
+    def set_svc_cols(self, mat, scale):
+        """the six column scales of the SVC6_COLS material ``mat`` (plfx_set_svc_cols); they hold until the next set_materials"""
+        sc = _f64(scale).reshape(-1)
+        if sc.shape != (6,):
+            raise ValueError('set_svc_cols: six scales expected')
+        self._chk(self.lib.plfx_set_svc_cols(self.h, int(mat), _dp(sc)))
 
     # -- batched point evaluation (host AoS arrays)
     def seq(self, mat, sig):

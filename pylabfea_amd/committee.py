@@ -44,6 +44,8 @@ class Committee(object):
         for k, m in enumerate(members):
             if isinstance(m, Material) and getattr(m, 'txdat', False):
                 m._tex_refuse('Committee')
+            if isinstance(m, Material):
+                m._bound_refuse('Committee')
             if not isinstance(m, Material) or not m.ML_yf or m.svc is None:
                 raise ValueError('Committee: member %d has no trained SVC yield function' % k)
             if m.sdim != 6:

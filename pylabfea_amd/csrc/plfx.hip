@@ -162,6 +162,7 @@ struct plfx_ctx {
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
     unsigned svc6_mask = 0;      // bit k: material k is a 6-feature SVC
+    unsigned svc_cols_mask = 0;  // bit k: material k is a PLFX_SVC6_COLS record (always among svc_row_all, never in svc6_mask)
     unsigned svcwh_mask = 0;     // bit k: material k is an SVC with work-hardening features
     int svc_wave_lds = 0;        // dynamic LDS bytes of the row kernels with their tables in LDS (k_*_row<..., true>)
     int n_svc6 = 0;              // number of 6-feature SVC materials
@@ -1909,17 +1910,28 @@ int plfx_sync(plfx_ctx *c)
     return PLFX_OK;
 }
 
-// launch a row kernel for material k: tables in LDS when they fit, else read from device memory (no dynamic LDS)
+// launch a row kernel for material k: tables in LDS when they fit, else read from device memory (no dynamic LDS); a
+// PLFX_SVC6_COLS material takes the per-column instantiation
 #define LAUNCH_ROW1(c, k, kern, grid, ...)                                                                                 \
     do {                                                                                                                 \
-        if (((c)->svc_row_lds >> (k)) & 1u)                                                                              \
+        const bool cols_ = ((c)->svc_cols_mask >> (k)) & 1u;                                                             \
+        if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<true, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);  \
+        else if (cols_)                                                                                                  \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<false, true>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);        \
+        else if (((c)->svc_row_lds >> (k)) & 1u)                                                                         \
             hipLaunchKernelGGL(kern<true>, grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);        \
         else                                                                                                             \
             hipLaunchKernelGGL(kern<false>, grid, dim3(512), 0, (c)->stream, __VA_ARGS__);                               \
     } while (0)
 #define LAUNCH_ROW2(c, k, kern, H, grid, ...)                                                                              \
     do {                                                                                                                 \
-        if (((c)->svc_row_lds >> (k)) & 1u)                                                                              \
+        const bool cols_ = ((c)->svc_cols_mask >> (k)) & 1u;                                                             \
+        if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);   \
+        else if (cols_)                                                                                                  \
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false, true>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);     \
+        else if (((c)->svc_row_lds >> (k)) & 1u)                                                                         \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);   \
         else                                                                                                             \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);           \
@@ -1980,7 +1992,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     c->plane_mats_ok = false;
     c->n_noflow = 0;
     c->svc_lds_need = 0;
-    c->svc_row_all = c->svc_row_lds = c->svc6_mask = c->svcwh_mask = 0;
+    c->svc_row_all = c->svc_row_lds = c->svc6_mask = c->svcwh_mask = c->svc_cols_mask = 0;
     c->svc_wave_lds = 0;
     c->n_svc6 = 0;
     c->nonlin = false;
@@ -1990,7 +2002,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         const plfx_material &s = mats[k];
         MatDev &m = c->hmat[k];
         memset(&m, 0, sizeof(m));
-        if (s.kind < PLFX_ELASTIC || s.kind > PLFX_SVC_WH)
+        if (s.kind < PLFX_ELASTIC || s.kind > PLFX_SVC6_COLS)
             return fail(c, PLFX_ERR_ARG, "material %d: unknown kind %d", k, s.kind);
         for (int i = 0; i < 6; i++)
             for (int j = i + 1; j < 6; j++)
@@ -2028,8 +2040,9 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         if (s.kind == PLFX_ELASTIC) c->has_elastic = true;
         if (s.kind == PLFX_BARLAT && s.barlat_normal) c->has_barlat = true;
         if (s.kind == PLFX_TRESCA || (s.kind == PLFX_BARLAT && !s.barlat_normal)) c->n_noflow++;
-        if (s.kind == PLFX_SVC6 || s.kind == PLFX_SVC3 || s.kind == PLFX_SVC_WH) {
-            const int nf = (s.kind == PLFX_SVC6) ? 6 : (s.kind == PLFX_SVC3) ? 2 : 15;
+        const bool cols = (s.kind == PLFX_SVC6_COLS);
+        if (s.kind == PLFX_SVC6 || s.kind == PLFX_SVC3 || s.kind == PLFX_SVC_WH || cols) {
+            const int nf = (s.kind == PLFX_SVC6 || cols) ? 6 : (s.kind == PLFX_SVC3) ? 2 : 15;
             if (s.kind == PLFX_SVC_WH && !(s.scale_wh > 0.)) return fail(c, PLFX_ERR_ARG, "material %d: scale_wh must be positive", k);
             if (s.nsv < 1 || s.nfeat != nf || !s.sv || !s.dual)
                 return fail(c, PLFX_ERR_ARG, "material %d: SVC needs nsv>=1, nfeat==%d, sv and dual", k, nf);
@@ -2055,12 +2068,23 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
                 m.svc_vvmax = std::max(m.svc_vvmax, vv);
                 m.svc_sabs += std::fabs(s.dual[i]);
             }
-            if (s.nsv * (nf + 1) <= c->lds_doubles) c->svc_lds_need = std::max(c->svc_lds_need, s.nsv * (nf + 1));
-            if (s.kind == PLFX_SVC6) c->has_svc = true; else if (s.kind == PLFX_SVC3) c->has_svc3 = true; else c->has_svcwh = true, c->svcwh_mask |= 1u << k;
-            if (s.kind == PLFX_SVC6) {
-                c->n_svc6++;
-                c->svc6_mask |= 1u << k;
-                if (c->want_svc_wave) {
+            if (cols) {
+                // the row kernels alone run this kind (none of the thread-per-point tables or flags): every column scale is
+                // scale_seq until plfx_set_svc_cols says otherwise
+                if (!(s.scale_seq > 0.) || !std::isfinite(s.scale_seq))
+                    return fail(c, PLFX_ERR_ARG, "material %d: scale_seq must be finite and positive", k);
+                for (int j = 0; j < 6; j++) m.col_inv[j] = 1. / s.scale_seq;
+                c->svc_cols_mask |= 1u << k;
+            } else {
+                if (s.nsv * (nf + 1) <= c->lds_doubles) c->svc_lds_need = std::max(c->svc_lds_need, s.nsv * (nf + 1));
+                if (s.kind == PLFX_SVC6) c->has_svc = true; else if (s.kind == PLFX_SVC3) c->has_svc3 = true; else c->has_svcwh = true, c->svcwh_mask |= 1u << k;
+            }
+            if (s.kind == PLFX_SVC6 || cols) {
+                if (!cols) {
+                    c->n_svc6++;
+                    c->svc6_mask |= 1u << k;
+                }
+                if (c->want_svc_wave || cols) {
                     // the tables of the row kernels in device memory, in the layout of their LDS copy (stage_svc_row): read from
                     // there by the kernels when the material has more support vectors than the LDS of a CU holds
                     const int rp = (s.nsv + 63) & ~63;
@@ -2098,7 +2122,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
                     }
                     // kept from the removed wave kernels (tables padded to 256, first fitting material): shrinking it changes the launch
                     const int npad = (s.nsv + 255) & ~255;
-                    if (9 * npad + SVC_WAVE_EXTRA <= c->lds_doubles && npad <= 2048 && !wave_pad) {
+                    if (9 * npad + SVC_WAVE_EXTRA <= c->lds_doubles && npad <= 2048 && !wave_pad && !cols) {
                         wave_pad = true;
                         c->svc_wave_lds = std::max(c->svc_wave_lds, (9 * npad + SVC_WAVE_EXTRA) * 8);
                     }
@@ -2119,6 +2143,13 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true>, c->svc_wave_lds));
         HIPCHK(c, set_dyn_lds((const void *)k_response_row<true>, c->svc_wave_lds));
         HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true>, c->svc_wave_lds));
+        if (c->svc_cols_mask & c->svc_row_lds) {
+            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<0, true, true>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<1, true, true>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true, true>, c->svc_wave_lds));
+        }
     }
     if (c->has_svc || c->has_svc3 || c->has_svcwh) {  // opt in to > 64 KiB dynamic LDS for the SVC kernels
         const int bytes = (int)dyn_lds_bytes(c);
@@ -2150,6 +2181,35 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     return PLFX_OK;
 }
 
+// the six column scales of a PLFX_SVC6_COLS material: the record keeps their reciprocals (MatDev::col_inv)
+int plfx_set_svc_cols(plfx_ctx *c, int mat, const double scale[6])
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
+    if (mat < 0 || mat >= c->nmat || !scale) return fail(c, PLFX_ERR_ARG, "plfx_set_svc_cols: bad argument");
+    if (c->hmat[mat].kind != PLFX_SVC6_COLS)
+        return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_set_svc_cols: material %d is of kind %d; column scales belong to a "
+                    "PLFX_SVC6_COLS material only", mat, c->hmat[mat].kind);
+    for (int j = 0; j < 6; j++)
+        if (!std::isfinite(scale[j]) || !(scale[j] > 0.))
+            return fail(c, PLFX_ERR_ARG, "plfx_set_svc_cols: scale %d must be finite and positive", j);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, stream_sync(c));   // no launch may still read the record that changes
+    for (int j = 0; j < 6; j++) c->hmat[mat].col_inv[j] = 1. / scale[j];
+    HIPCHK(c, hipMemcpyAsync(c->dmat + mat, &c->hmat[mat], sizeof(MatDev), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, stream_sync(c));
+    c->memo.valid = false;
+    return PLFX_OK;
+}
+
+// a PLFX_SVC6_COLS material runs on the row kernels alone: what every other point function answers for it
+static int cols_refuse(plfx_ctx *c, int mat, const char *what)
+{
+    if (c && c->dmat && mat >= 0 && mat < c->nmat && c->hmat[mat].kind == PLFX_SVC6_COLS)
+        return fail(c, PLFX_ERR_UNSUPPORTED, "%s: material %d is a PLFX_SVC6_COLS record, which runs on the row kernels only "
+                    "(sweeps, calc_scf, response, ML_full_yf)", what, mat);
+    return PLFX_OK;
+}
 
 // ------------------------------------------------------------------------------ batched point evaluation
 // the opening check of a point function of one material; args_ok: what the function asks of its other arguments
@@ -2196,6 +2256,8 @@ static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, 
                       const double *ld, double *out, int32_t *status)
 {
     if (int rc = point_check(c, mat, n >= 0 && sig && out)) return rc;
+    const bool cols = (c->hmat[mat].kind == PLFX_SVC6_COLS);
+    if (cols && what != 3) return cols_refuse(c, mat, what == 0 ? "calc_seq" : what == 1 ? "calc_fgrad" : "calc_yf");
     if (n == 0) return PLFX_OK;
     const size_t N = n, wout = (what == 1) ? 6 : 1;
     CallBuffers B;
@@ -2212,7 +2274,7 @@ static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, 
     static const bool wave_full = !(getenv("PLFX_FULL_YF_WAVE") && atoi(getenv("PLFX_FULL_YF_WAVE")) == 0);
     EvPair *ev;
     tim_begin(c, 0, &ev);   // family 0 like plfx_response_batch: the kernel alone, without the copies
-    if (what == 3 && wave_full && ((c->svc_row_all >> mat) & 1u))  // ML_full_yf of a row-kernel SVC material
+    if (what == 3 && (wave_full || cols) && ((c->svc_row_all >> mat) & 1u))  // ML_full_yf of a row-kernel SVC material
         LAUNCH_ROW1(c, mat, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
                    c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
     else
@@ -2311,7 +2373,7 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
     if (c->has_barlat)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<5>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, RB_ARGS(0), RB_TAIL);
     const bool resp_row = !(getenv("PLFX_RESPONSE_ROW") && atoi(getenv("PLFX_RESPONSE_ROW")) == 0);   // read per call: tests compare the two forms
-    const unsigned rmask = resp_row ? c->svc_row_all : 0u;
+    const unsigned rmask = resp_row ? c->svc_row_all : c->svc_cols_mask;   // (PLFX_SVC6_COLS has no other form)
     if (c->has_svc && (c->svc6_mask & ~rmask))
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<3>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
                            c->stream, RB_ARGS(c->svc_lds_need), (const double *)nullptr, (double *)nullptr, rmask, c->resp_maxit);
@@ -2394,6 +2456,7 @@ int plfx_fgrad_batch_wh(plfx_ctx *c, int mat, int n, const double *sig, const do
 int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *hess)
 {
     if (int rc = point_check(c, mat, n >= 0 && sig && hess)) return rc;
+    if (int rc = cols_refuse(c, mat, "calc_hessian")) return rc;
     const int kind = c->hmat[mat].kind;
     if (kind != PLFX_SVC6 && kind != PLFX_SVC_WH)
         return fail(c, PLFX_ERR_UNSUPPORTED, kind == PLFX_SVC3 ? "calc_hessian: not implemented for 3D stress (material.py:950)"
@@ -2428,6 +2491,7 @@ int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double
                      int32_t *status)
 {
     if (int rc = point_check(c, mat, n >= 0 && su && x && status)) return rc;
+    if (int rc = cols_refuse(c, mat, "yield_scale")) return rc;
     const int kind = c->hmat[mat].kind;
     if (kind == PLFX_ELASTIC) return fail(c, PLFX_ERR_ARG, "yield_scale: material %d has no yield strength", mat);
     if (n == 0) return PLFX_OK;
@@ -2501,6 +2565,7 @@ int plfx_flow_curve(plfx_ctx *c, int mat, int n, const double *su, const double 
                     int32_t *status)
 {
     if (int rc = point_check(c, mat, n >= 0 && su && x && epl && yf && nsteps && status)) return rc;
+    if (int rc = cols_refuse(c, mat, "flow_curve")) return rc;
     if (max_steps < 0 || !(depl > 0.) || !std::isfinite(depl) || !std::isfinite(predictor) || epl_max != epl_max)
         return fail(c, PLFX_ERR_ARG, "flow_curve: max_steps >= 0, a finite depl > 0, a finite predictor and an epl_max that is a number expected");
     const int kind = c->hmat[mat].kind;
@@ -2567,7 +2632,7 @@ int plfx_committee_yf(plfx_ctx *c, int nmem, const int32_t *mats, const double *
 {
     static const char *const kind_names[] = {"elastic", "Hill / J2 on Voigt stresses", "Hill / J2 on principal stresses",
                                              "6-feature SVC", "Tresca", "Barlat", "2-feature SVC on principal stresses",
-                                             "SVC with work-hardening features"};
+                                             "SVC with work-hardening features", "6-feature SVC with column scales"};
     if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
     if (nmem < 1 || nmem > MAXMAT) return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: nmem = %d, must be in 1..%d", nmem, MAXMAT);
     if (!mats || !scale || n < 0 || n > INT32_MAX - CY_BLOCK || (n > 0 && !su)) return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: bad argument");
@@ -5742,7 +5807,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
 #define ROW_ARGS c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,  \
                   c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,       \
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
-    if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh)) {
+    if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh && !c->svc_cols_mask)) {
         if (plane_active(c)) {   // (the same timing family)
             hipLaunchKernelGGL(k_sweep_light_plane, dim3(c->grid_el), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead);
             c->n_plane_sweeps++;
@@ -5767,7 +5832,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         first = 0;
         c->n_svc_thread_launches++;
     }
-    if (c->has_svc && fast) {
+    if (fast) {
         for (int k = 0; k < c->nmat; k++)   // one launch per material: its tables fill the LDS
             if ((fast >> k) & 1u) {
                 LAUNCH_ROW2(c, k, k_sweep_svc_row, 0, dim3(grid_r), ROW_ARGS, first, k);
@@ -5816,7 +5881,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         if (svc_thread)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
                                c->stream, SWEEP_ARGS(c->svc_lds_need), fast);
-        if (c->has_svc && fast)
+        if (fast)
             for (int k = 0; k < c->nmat; k++)
                 if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
         if (c->has_svc3)

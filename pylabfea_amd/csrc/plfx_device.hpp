@@ -162,7 +162,11 @@ struct MatDev {
     int32_t rowpad, _pad_row;    // support vectors padded to a multiple of 64
     const double *sv;    // device pointer [nsv*nfeat]
     const double *dual;  // device pointer [nsv]
-    double barlat[18], barlat_exp;  // Yld2004-18p coefficients
+    union {
+        double barlat[18];   // Yld2004-18p coefficients
+        double col_inv[6];   // PLFX_SVC6_COLS: 1 / scale of stress column j (plfx_set_svc_cols); no SVC kind reads barlat
+    };
+    double barlat_exp;
     int32_t kind, sdim, nsv, dev_only, nfeat, barlat_normal;  // barlat_normal: the native Barlat normal is enabled (extension)
 };
 
@@ -1111,7 +1115,10 @@ struct YfSvcWhT {
 //  * the root (:501-503): brentq(xtol = 1e-5) on [x0, x1] is replayed iterate for iterate (BrentState) with p as the function
 //    (the support-vector sums where p does not cover an iterate), so the value response() branches on is the reference's
 //    last iterate to ~1e-11, not a better root.
-template <int NC, bool INLDS = true>
+// COLS (PLFX_SVC6_COLS): one scale per stress column, x_j = s_j / scale_j, and the gradient of a dev_only set
+// projected onto the deviator.  Only features() and the closing of fgrad_impl differ; along a ray x = t D with
+// D_j = su_j / scale_j every term is still a Gaussian in t, so the sampled ray, the march and the brentq replay are shared.
+template <int NC, bool INLDS = true, bool COLS = false>
 struct YfSvcRow {
     static constexpr int GS = 16, NS = RAYPOLY_N;
     static constexpr bool FUSED = true;   // fgrad_plain(): gradient at one point and decision function at another in one pass
@@ -1141,6 +1148,12 @@ struct YfSvcRow {
     // held to 1e-6 sy like every SVC path (brentq's xtol), not to the bit
     __device__ __forceinline__ void features(const double *s, double *x) const
     {
+        if (COLS) {
+            const double p = m.dev_only ? (s[0] + s[1] + s[2]) / 3. : 0.;
+#pragma unroll
+            for (int i = 0; i < 6; i++) x[i] = (i < 3 ? s[i] - p : s[i]) * m.col_inv[i];
+            return;
+        }
         const double inv = 1. / m.scale_seq;
         const double p = m.dev_only ? (s[0] + s[1] + s[2]) / 3. : 0.;
         x[0] = (s[0] - p) * inv;
@@ -1252,9 +1265,21 @@ struct YfSvcRow {
                 for (int i = 0; i < 6; i++) acc[i] = fma(w, v[c][i], acc[i]);
             }
         }
-        const double sc = -2. * m.gamma / m.scale_seq;
+        if (COLS) {   // a_j = -2 gamma sum_j / scale_j, then the chain rule through the deviator (tex_grad_close)
+            const double c2 = -2. * m.gamma;
 #pragma unroll
-        for (int i = 0; i < 6; i++) a[i] = row_allsum(acc[i]) * sc;
+            for (int i = 0; i < 6; i++) a[i] = row_allsum(acc[i]) * (c2 * m.col_inv[i]);
+            if (m.dev_only) {
+                const double p = (a[0] + a[1] + a[2]) / 3.;
+                a[0] -= p;
+                a[1] -= p;
+                a[2] -= p;
+            }
+        } else {
+            const double sc = -2. * m.gamma / m.scale_seq;
+#pragma unroll
+            for (int i = 0; i < 6; i++) a[i] = row_allsum(acc[i]) * sc;
+        }
         if (!WITH2) return 0.;
         double t = f2[0];
 #pragma unroll

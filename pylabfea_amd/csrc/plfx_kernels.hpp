@@ -1388,7 +1388,9 @@ constexpr int SVC_WAVE_EXTRA = RAYPOLY_N * RAYPOLY_N + 128;   // doubles behind 
 // Row-per-element variants (round 5; YfSvcRow) for one 6-feature SVC material: 16 lanes = one DPP row per element, four
 // elements per wave, the ray search in its sampled form.  The two sweep phases of k_sweep_svc_row share the 50-sub-step list
 // and the flags with the thread-per-element kernels (flags[2]); lane 0 of a row stores.
-template <bool INLDS>
+// COLS: the instantiations for a PLFX_SVC6_COLS material (one scale per stress column, YfSvcRow<.., true>); the tables, their
+// staging and every launch argument are those of the 6-feature material.
+template <bool INLDS, bool COLS = false>
 __global__ void __launch_bounds__(512)
 k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const double *__restrict__ sig_in,
               const double *__restrict__ epl_in, const double *__restrict__ ld, double *__restrict__ out, int32_t *__restrict__ status)
@@ -1412,7 +1414,7 @@ k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const d
             s[c] = sig_in[6 * (size_t)i + c];
             e[c] = epl_in ? epl_in[6 * (size_t)i + c] : 0.;
         }
-        const YfSvcRow<4, INLDS> yf(m, npad);
+        const YfSvcRow<4, INLDS, COLS> yf(m, npad);
         int st = 0;
         const double f = yf.full_ld(s, e, ld ? ldv : nullptr, &st);
         if (l16 == 0) {
@@ -1424,7 +1426,7 @@ k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const d
 
 // Material.response on n points of the row-kernel SVC material `mat` (host-layout arrays as in k_response_batch; points of
 // other materials are left to k_response_batch<3>): the same code path as the sweeps of a model, callable point by point
-template <bool INLDS>
+template <bool INLDS, bool COLS = false>
 __global__ void __launch_bounds__(512)
 k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const int32_t *__restrict__ mat_id,
                const double *__restrict__ sig_in, const double *__restrict__ epl_in, const double *__restrict__ deps_in,
@@ -1447,7 +1449,7 @@ k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const 
             epl[c] = epl_in[6 * (size_t)i + c];
             deps[c] = deps_in[6 * (size_t)i + c];
         }
-        const YfSvcRow<4, INLDS> yf(m, npad);
+        const YfSvcRow<4, INLDS, COLS> yf(m, npad);
         const int ns = response_point(m, yf, sig, epl, deps, f, depl, Ct, maxit);
         if (l16 == 0) {
             fy[i] = f;
@@ -1465,7 +1467,7 @@ k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const 
     }
 }
 
-template <int HEAVY, bool INLDS>
+template <int HEAVY, bool INLDS, bool COLS = false>
 __global__ void __launch_bounds__(512)
 k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
                 int nel, int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls,
@@ -1502,7 +1504,7 @@ k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
             s[k] = sig[(size_t)k * nel + e];
             ep[k] = epl[(size_t)k * nel + e];
         }
-        const YfSvcRow<NC, INLDS> yf(m, npad);
+        const YfSvcRow<NC, INLDS, COLS> yf(m, npad);
         const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
         if (HEAVY) {
             response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
@@ -3518,7 +3520,7 @@ k_scf_elements(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
 // calc_scf for the elements of the 6-feature SVC material `mat`, 16 lanes per element (YfSvcRow; ML_full_yf along the
 // loading direction is a ray search, model.py:1049-1052) -- the thread-per-element form above took 4.5 ms per call on
 // 16 384 elements, a quarter of a 50-sub-step corrector launch
-template <bool INLDS>
+template <bool INLDS, bool COLS = false>
 __global__ void __launch_bounds__(512)
 k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int mat, int nel,
           int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
@@ -3553,7 +3555,7 @@ k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict_
                 s[k] = sig[(size_t)k * nel + e];
                 ep[k] = epl[(size_t)k * nel + e];
             }
-            const YfSvcRow<4, INLDS> yf(m, npad);
+            const YfSvcRow<4, INLDS, COLS> yf(m, npad);
             double yf0 = yf.plain(s, ep);
             if (yf0 < SPLIT_THRESHOLD) {  // branch test on the decision function (model.py:1046-1048)
                 yf0 = yf.full_ld(s, ep, ld, nullptr);  // model.py:1049-1052

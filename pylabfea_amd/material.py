@@ -12,7 +12,8 @@ Out of scope here: plotting.  What the yield-locus plots compute
 Texture materials (``from_data`` on data sets with ``tx_data``) are trained and evaluated as yield functions --
 ``train_SVC``, ``calc_yf``, ``find_yloc``, ``yield_scale``, ``texture_loci`` -- and, like in the reference, nothing past that
 unless the caller passes ``tex=``: ``calc_fgrad``, ``ML_full_yf``, ``response``, ``response_batch``, ``epl_dot`` and ``C_tan``
-then run at that texture (an extension).
+then run at that texture (an extension).  ``at_texture(tex)`` binds a trained texture material to one texture:
+the bound material is what ``Model.assign`` takes, one texture per section.
 A trained SVC enters through
 :meth:`Material.train_SVC` (trained on the GPU), :meth:`Material.set_svc` or :meth:`Material.from_sklearn`.
 sdim=3 flow rules use the reference's axis-tracking principal stresses (exact for plane states);
@@ -111,6 +112,7 @@ class Material(object):
         self.propJ2 = {k: {'ys': None, 'seq': None, 'eeq': None, 'peeq': None} for k in lcs}
         self.sigeps = {k: {'sig': None, 'eps': None, 'epl': None} for k in lcs}
         self._version = 0
+        self._bound = None      # at_texture: dict(parent, tex, scale) of a material bound to one texture
 
     # ------------------------------------------------------------------ definition
     def elasticity(self, C11=None, C12=None, C44=None, CV=None, E=None, nu=None):
@@ -269,6 +271,7 @@ class Material(object):
         then the support vectors row by row -- and ``file-svm_meta.json``."""
         import datetime, getpass, json, platform
         self._tex_refuse('export_MLparam')
+        self._bound_refuse('export_MLparam')
         if not self.ML_yf:
             raise AttributeError('export_MLparam: No ML flow rule defined.')
         if descr is not None and param is not None and len(descr) != len(param):
@@ -376,6 +379,11 @@ class Material(object):
         """plfx_material record of this material with the element matrix CV."""
         if self.sy is None:
             return _lib.pack_material(_lib.ELASTIC, CV, E=self.E, nu=self.nu)
+        if self.ML_yf and not ana and getattr(self, '_bound', None) is not None:
+            svc = dict(sv=self.svc['sv'], dual=self.svc['dual'], intercept=self.svc['intercept'], gamma=self.gam_yf,
+                       scale_seq=self.scale_seq, dev_only=self.dev_only, scale_cols=self._bound['scale'])
+            return _lib.pack_material(_lib.SVC6_COLS, CV, E=self.E, nu=self.nu, sy=self.sy, khard=self.khard,
+                                      hill=self.hill, drucker=self.drucker, svc=svc)
         if self.ML_yf and not ana:
             self._tex_refuse('Model.assign')
             svc = dict(sv=self.svc['sv'], dual=self.svc['dual'], intercept=self.svc['intercept'],
@@ -419,14 +427,16 @@ class Material(object):
                           '(material.py:252); response_batch(..., tex=) runs the update at a texture (DESIGN.md §32)',
         'calc_hessian': 'the reference rescales the Hessian of the scaler-standardised features by 1 / scale_seq**2, and '
                         'scale_seq is not a feature scale of a texture material (material.py:952-960)',
-        'calc_properties': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343)',
+        'calc_properties': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343); '
+                           'at_texture(tex) binds the material to one texture, and the bound material runs (DESIGN.md §34)',
         'setup_fgrad_SVM': 'the reference needs work-hardening data, which a texture material cannot carry here',
         'export_MLparam': "the reference's file has no slots for the scaler's mean and scale (material.py:2130-2271)",
         'polar_yield_locus': 'the reference\'s polar_plot_yl calls find_yloc without a texture and raises ValueError '
                              '(material.py:3292); texture_loci traces the loci',
         'yield_slices': "the reference's plot_yield_locus calls calc_yf without a texture and raises ValueError (material.py:3017)",
         'Committee': 'the reference example forms committees of texture-free yield functions only',
-        'Model.assign': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343)',
+        'Model.assign': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343); '
+                        'at_texture(tex) binds the material to one texture, and a model takes the bound material (DESIGN.md §34)',
     }
 
     def _is_tex(self):
@@ -504,6 +514,85 @@ class Material(object):
         self.khard = 0.
         self.msg['gradient'] = 'gradient to ML_yf'
         return a[0] if single else a
+
+    # ------------------------------------------------------------------ a texture material bound to one texture
+    def fold_texture(self, tex):
+        """The texture SVC at the fixed texture ``tex`` (tdim,) as a 6-feature SVC with one scale per stress column, host
+        NumPy.  With f_j = (s_j - mean_j) / scale_j the stress features, ft the standardised features of ``tex``, v_k the
+        vectors and K_k = exp(-gamma |f - v_k|^2): c_k = sum_t (ft_t - v_{k,6+t})^2 is a constant per vector,
+        so  calc_yf(sig, tex=tex) = sum_k d'_k exp(-gamma |x - v'_k|^2) + intercept  with  d'_k = dual_k exp(-gamma c_k),
+        v'_kj = v_kj + mean_j / scale_j  and  x_j = s_j / scale_j  (s: the deviator for a dev_only set).
+        Returns ``dict(sv=v' (nsv,6), dual=d' (nsv,), intercept, gamma, scale (6,), dev_only)``: what ``at_texture`` sends to
+        the device."""
+        if not getattr(self, 'txdat', False):
+            raise NotImplementedError('fold_texture: tex needs a texture material (from_data on data sets with tx_data)')
+        if not self._is_tex():
+            self._svc_refuse('fold_texture')
+        if not self.ML_yf or self.svc is None or getattr(self, 'std_scaler', None) is None:
+            raise AttributeError('texture material has no trained ML yield function; train_SVC trains it')
+        t = np.asarray(tex, dtype=float)
+        if t.shape != (self.tdim,) or not np.all(np.isfinite(t)):
+            raise ValueError('fold_texture: tex must be a finite (%d,) array; got shape %s' % (self.tdim, np.shape(tex)))
+        mean = np.asarray(self.std_scaler.mean_, dtype=float)
+        scale = np.asarray(self.std_scaler.scale_, dtype=float)
+        sv = np.asarray(self.svc['sv'], dtype=float)
+        ft = (t - mean[6:]) / scale[6:]
+        c = np.sum((ft[None, :] - sv[:, 6:]) ** 2, axis=1)
+        return dict(sv=np.ascontiguousarray(sv[:, :6] + (mean[:6] / scale[:6])[None, :]),
+                    dual=np.asarray(self.svc['dual'], dtype=float) * np.exp(-self.gam_yf * c),
+                    intercept=float(self.svc['intercept']), gamma=float(self.gam_yf), scale=scale[:6].copy(),
+                    dev_only=bool(self.dev_only))
+
+    def at_texture(self, tex, name=None):
+        """A new Material: this trained texture material bound to the texture ``tex`` (tdim,), which an FE model can hold --
+        ``Model.assign``, ``solve``, ``field``, ``calc_properties`` -- and ``response`` / ``response_batch`` / ``ML_full_yf``
+        run on the 16-lane row kernels.  It carries this material's elastic constants, sy, khard, Hill form
+        and sdim = 6, the folded tables of ``fold_texture``, the texture and a reference to this material, which is left as it
+        is.  ``calc_yf``, ``calc_fgrad``, ``yield_scale`` and ``yield_stress`` of the bound material are this material's
+        ``tex=`` calls at the bound texture.  It hardens as ``response(..., tex=)`` does: sflow = sy + khard peeq."""
+        f = self.fold_texture(tex)
+        b = Material(name=name if name is not None else '%s@texture' % self.name, num=self.num)
+        for k in ('E', 'nu', 'C11', 'C12', 'C44', 'sy', 'sy0', 'khard', 'drucker', 'hill_3p', 'hill_6p'):
+            setattr(b, k, getattr(self, k))
+        b.CV = np.array(self.CV, dtype=float)
+        b.hill = np.array(self.hill, dtype=float)
+        b.sdim = 6
+        b.svc = dict(sv=f['sv'], dual=f['dual'], intercept=f['intercept'])
+        b.gam_yf, b.C_yf, b.dev_only = f['gamma'], self.C_yf, f['dev_only']
+        b.scale_seq = float(f['scale'][0])   # the record's nominal scale; the device divides column j by scale[j]
+        b.ML_yf = True
+        b.Ndof = 6
+        b._bound = dict(parent=self, tex=np.array(tex, dtype=float), scale=f['scale'])
+        return b
+
+    # what to do instead where a bound material refuses
+    _BOUND_REFUSALS = {
+        'calc_hessian': 'no Hessian of the texture SVC is built',
+        'flow_curve': "the parent's yield_scale(su, tex=) gives the points of the locus; response_batch follows a path",
+        'polar_yield_locus': "the parent's texture_loci(tex) traces the locus",
+        'yield_slices': "the parent's yield_scale(su, tex=) along the slice's directions gives the locus",
+        'setup_fgrad_SVM': 'texture and work-hardening data are not combined',
+        'train_SVC': 'train the parent and bind it again with at_texture',
+        'export_MLparam': "the reference's file has no slots for one scale per stress column",
+        'Committee': 'committees evaluate 6-feature SVC yield functions with one scale',
+        'create_scaled_input': "fold_texture of the parent states the features, x_j = s_j / scale_j",
+        'Model.distribute': 'a bound material runs on one GPU',
+    }
+
+    def _bound_refuse(self, what):
+        """the one gate of a material bound to a texture (at_texture): the row kernels run it and nothing else does"""
+        if getattr(self, '_bound', None) is not None:
+            raise NotImplementedError('%s: not offered for a material bound to a texture (at_texture); %s'
+                                      % (what, self._BOUND_REFUSALS.get(what, 'use the parent material')))
+
+    def _bound_call(self, fn, *a, **kw):
+        """a ``tex=`` call of the parent at the bound texture; the parent's khard, which its calc_fgrad(tex=) resets, is put back"""
+        par = self._bound['parent']
+        kh = par.khard
+        try:
+            return getattr(par, fn)(*a, tex=self._bound['tex'], **kw)
+        finally:
+            par.khard = kh
 
     def _tex_no_hardening(self, what, epl):
         """texture together with work hardening is not built: the device call of ML_full_yf(tex=) takes no plastic strain,
@@ -692,6 +781,7 @@ class Material(object):
         work-hardening features — the ones this engine evaluates): principal-stress cylinder coordinates for sdim=3,
         (deviatoric) Voigt stress / scale_seq for sdim=6.  Host-side helper for scripts; the kernels build the same
         features in registers."""
+        self._bound_refuse('create_scaled_input')
         if self._is_tex():   # material.py:2347-2361 (no PCA): unscaled features through the fitted scaler
             if tex is None:
                 raise ValueError('create_scaled_input: a texture material needs tex')
@@ -731,6 +821,12 @@ class Material(object):
         """Yield function: analytic ``calc_seq - sflow`` or the SVC decision function (material.py:348-412).  A texture
         material takes ``tex``, one descriptor (tdim,) or one per stress (N, tdim), and raises the reference's ValueError
         without it."""
+        if getattr(self, '_bound', None) is not None and not ana:   # (no plastic strain enters the texture features)
+            if tex is not None:
+                raise ValueError('calc_yf: the material is bound to a texture (at_texture) and takes no tex')
+            f = self._bound_call('calc_yf', sig, pred=pred)
+            self.msg['yield_fct'] = self._bound['parent'].msg['yield_fct']
+            return f
         s, single = self._voigt(sig, 'calc_yf')
         if self.ML_yf and not ana and getattr(self, 'txdat', False):
             if tex is None:
@@ -829,6 +925,12 @@ class Material(object):
     def calc_fgrad(self, sig, epl=None, seq=None, ana=False, tex=None, **kw):
         """Gradient of the yield function w.r.t. stress (material.py:704-858).  EXTENSION: a texture material takes ``tex``,
         (tdim,) or (N, tdim), and returns the stress derivative of ``calc_yf(sig, tex=)`` (see ``_fgrad_tex``)."""
+        if getattr(self, '_bound', None) is not None and not ana:   # (khard is a parameter of a bound material: left alone)
+            if tex is not None:
+                raise ValueError('calc_fgrad: the material is bound to a texture (at_texture) and takes no tex')
+            a = self._bound_call('calc_fgrad', sig, epl=epl)
+            self.msg['gradient'] = 'gradient to ML_yf'
+            return a
         if tex is not None and not ana:
             return self._fgrad_tex(np.asarray(sig, dtype=float), epl, tex)
         if self.ML_yf and not ana:
@@ -886,6 +988,7 @@ class Material(object):
         epsilon 0.01 and tol 1e-4, fitted in one batched call on the GPU (libsvm's epsilon-SVR without shrinking).  Sets
         svm_grad0 .. svm_grad5, svm_khard, sc_feat, sc_grad, sc_khard and ML_grad = True."""
         self._tex_refuse('setup_fgrad_SVM')
+        self._bound_refuse('setup_fgrad_SVM')
         if not getattr(self, 'whdat', False):
             raise ValueError('No strain hardening data available.')
         if not self._msparam_ok():
@@ -954,6 +1057,7 @@ class Material(object):
         Hessian in the reference (``ValueError``), nor have sdim = 3 ML materials (``NotImplementedError``).
         Unlike ``calc_fgrad`` this touches neither ``khard`` nor ``msg``."""
         self._tex_refuse('calc_hessian')
+        self._bound_refuse('calc_hessian')
         if tex is not None:
             raise NotImplementedError('calc_hessian: texture features are outside this engine; ' + self._TEX_REFUSALS['calc_hessian'])
         if getattr(self, 'ML_grad', False) and not ana:
@@ -1053,6 +1157,8 @@ class Material(object):
             return fy, so, dp, ct.reshape(-1, 6, 6), ns
         self._tex_refuse('response_batch')
         self._no_svr_gradient('response_batch')
+        if getattr(self, '_bound', None) is not None:
+            return self._response_batch_bound(sig, epl, deps, CV, khard_in, return_khard)
         if khard_in is not None or return_khard:
             if not self._svr_flow_on():
                 raise ValueError('response_batch: khard_in / return_khard are for a material that follows the SVR flow rule '
@@ -1061,6 +1167,23 @@ class Material(object):
             return (fy, so, dp, ct.reshape(-1, 6, 6), ns) + ((kout,) if return_khard else ())
         fy, so, dp, ct, ns = self._load(CV).response(sig, epl, deps)
         return fy, so, dp, ct.reshape(-1, 6, 6), ns
+
+    def _response_batch_bound(self, sig, epl, deps, CV, khard_in, return_khard):
+        """response_batch of a material bound to a texture: rows with a non-finite sig, epl or deps are masked here and never
+        sent; they come back NaN with nsteps = -1, the rule of response_batch(tex=)"""
+        if khard_in is not None or return_khard:
+            raise ValueError('response_batch: khard_in / return_khard are not offered for a material bound to a texture')
+        s, e, d = (np.asarray(a, dtype=float) for a in (sig, epl, deps))
+        if s.ndim != 2 or s.shape[1] != 6 or e.shape != s.shape or d.shape != s.shape:
+            raise ValueError('response_batch: sig, epl and deps of shape (N, 6) expected')
+        n = len(s)
+        ok = np.all(np.isfinite(s) & np.isfinite(e) & np.isfinite(d), axis=1)
+        fy, so, dp = np.full(n, np.nan), np.full((n, 6), np.nan), np.full((n, 6), np.nan)
+        ct, ns = np.full((n, 6, 6), np.nan), np.full(n, -1, dtype=np.int32)
+        if np.any(ok):
+            r = self._load(CV).response(np.ascontiguousarray(s[ok]), np.ascontiguousarray(e[ok]), np.ascontiguousarray(d[ok]))
+            fy[ok], so[ok], dp[ok], ct[ok], ns[ok] = r[0], r[1], r[2], r[3].reshape(-1, 6, 6), r[4]
+        return fy, so, dp, ct, ns
 
     def epl_dot(self, sig, epl, Cel, deps, tex=None, **kw):
         """Plastic strain increment relaxing the stress to the yield locus (material.py:1009-1055); ``tex`` (tdim,) for a
@@ -1212,6 +1335,10 @@ class Material(object):
         ``x0`` is ``sy / seq_J2(su)`` (no plastic strain enters its features)."""
         if self.sy is None:
             raise ValueError('yield_scale: the material has no yield strength')
+        if getattr(self, '_bound', None) is not None:   # (the parent's search at the bound texture; no plastic strain enters it)
+            if tex is not None:
+                raise ValueError('yield_scale: the material is bound to a texture (at_texture) and takes no tex')
+            return self._bound_call('yield_scale', su, x0=x0, return_status=return_status)
         s, single = self._voigt(su, 'yield_scale')
         if self.ML_yf and getattr(self, 'txdat', False):
             return self._yield_scale_tex(s, single, tex, x0, return_status)
@@ -1264,6 +1391,7 @@ class Material(object):
         ``sdim = 3``, Tresca, Barlat, an SVR gradient (``ML_grad``) and texture materials."""
         if self.ML_yf:
             self._tex_refuse('flow_curve')
+            self._bound_refuse('flow_curve')
         self._no_svr_gradient('flow_curve')
         if self.sy is None:
             raise ValueError('flow_curve: the material has no yield strength')
@@ -1439,6 +1567,7 @@ class Material(object):
         per material of ``cmat`` along the same directions.  Like the reference (:3308), the curves of ``cmat`` are put through
         THIS material's ``calc_seq`` (``sig_eq_j2`` with ``sJ2``), not their own.  ``scaling`` divides the stresses."""
         self._tex_refuse('polar_yield_locus')
+        self._bound_refuse('polar_yield_locus')
         if self.sy is None:
             raise ValueError('polar_yield_locus: the material has no yield strength')
         sf = 1. if scaling is None else 1. / scaling
@@ -1531,6 +1660,7 @@ class Material(object):
 
         The caller's ``axis1`` / ``axis2`` lists are not modified (the reference rewrites code 3 in place)."""
         self._tex_refuse('yield_slices')
+        self._bound_refuse('yield_slices')
         if self.sy is None:
             raise ValueError('yield_slices: the material has no yield strength')
         if len(axis1) != len(axis2):
@@ -1819,6 +1949,7 @@ class Material(object):
         """Train the SVC yield function (material.py:1442-1640, the branch without microstructure data): elasticity and
         plasticity from ``mat_ref`` (or sy = mean J2 stress of ``sdata``), training data from ``create_sig_data``, the fit
         by the batched SMO solver on the GPU (libsvm's C-SVC).  Returns (train score, test score)."""
+        self._bound_refuse('train_SVC')
         self._svc_refuse('train_SVC')
         if scaler is not None or pca is not None:
             raise NotImplementedError('train_SVC: scaler / pca (a given scaler, the PCA of address-vector descriptors) are '

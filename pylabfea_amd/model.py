@@ -245,6 +245,8 @@ class Model(object):
         for mat in mats:
             if getattr(mat, 'txdat', False):   # no response exists for a texture material, here or in the reference
                 mat._tex_refuse('Model.assign')
+            if getattr(self, '_shard', None) is not None and hasattr(mat, '_bound_refuse'):
+                mat._bound_refuse('Model.distribute')
         self.mat = mats
         self.nonlin = False
         for mat in mats:
@@ -503,6 +505,9 @@ class Model(object):
             raise ValueError("distribute: mode must be None, 'strip' or 'replicated'")
         if int(nranks) > 1 and uid is None and host_allreduce is None:
             raise ValueError('distribute: pass the RCCL unique id (uid) or a host_allreduce callback')
+        for mat in (getattr(self, 'mat', None) or []):   # a material bound to a texture (Material.at_texture) runs on one GPU
+            if hasattr(mat, '_bound_refuse'):
+                mat._bound_refuse('Model.distribute')
         self._shard = (int(rank), int(nranks), uid)
         self._host_allreduce = host_allreduce
         self._dist_mode = mode

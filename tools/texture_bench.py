@@ -14,7 +14,14 @@ pass over the vectors the gradient repeats with six more FMAs per vector -- and 
 and at 10 000 plastic points: stresses on the yield locus of texture 2 with an oblique strain increment of 1.5e-3, which the
 update sub-divides.
 
-    python tools/texture_bench.py [--flow] [--reps 11] [--limit 240]
+--bound times a material bound to one texture instead (Material.at_texture): bound.response_batch on
+the 16-lane row kernels at 1 and at 10 000 of the plastic points of --flow, beside parent.response_batch(tex=) on the same
+points in the same process; then one Model.solve on 256 x 256 elements, three sections bound at three training textures,
+plane strain, a top displacement of 1.2 x the largest uniaxial yield strain in min_step = 10 increments (the schedule of
+benchmark configuration 4), and for context the 6-feature 'hill' material of that configuration on the same mesh: wall time,
+sweeps, and the corrector's kernel time per element update.
+
+    python tools/texture_bench.py [--flow | --bound] [--reps 11] [--limit 240]
 """
 import argparse
 import json
@@ -32,6 +39,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 STEPS = ('loci:6', 'loci:100', 'loci:7000', 'yf:1', 'yf:100000')
 FLOW_STEPS = ('fgrad:1', 'fgrad:100000', 'resp:1', 'resp:10000')
+BOUND_STEPS = ('bound:1', 'bound:10000', 'model:256', 'model6:256')
 DESC = 'GSH_3'
 
 
@@ -42,6 +50,8 @@ def step(name, reps):
     from pylabfea_amd.material import _ctx
     kind, n = name.split(':')
     n = int(n)
+    if kind in ('model', 'model6'):
+        return model_step(kind, n)
     z = TC.load()
     with tempfile.TemporaryDirectory() as tmp:
         m, _ = TC.facade(FE, z, tmp, DESC)
@@ -101,7 +111,7 @@ def step(name, reps):
         res.update(points=n, shared_texture_kernel_ms=s_ms, shared_texture_wall_ms=s_wall, texture_per_row_kernel_ms=r_ms,
                    texture_per_row_wall_ms=r_wall, calc_yf_shared_texture_kernel_ms=y_ms, calc_yf_shared_texture_wall_ms=y_wall,
                    kernel_ratio_to_calc_yf=s_ms / y_ms)
-    elif kind == 'resp':
+    elif kind in ('resp', 'bound'):
         cand = np.array(z['probe_sig'])
         import yield_locus_cases as YC
         su = cand / YC.j2(cand)[:, None]
@@ -117,6 +127,13 @@ def step(name, reps):
         out, k_ms, k_wall, k_l = timed(lambda: m.response_batch(sig, epl, deps, CV, tex=tex6[2]))
         assert k_l == 1 and np.all(np.isfinite(out[1]))
         res.update(points=n, sub_divided=int(np.sum(out[4] == 49)), kernel_ms=k_ms, wall_ms=k_wall)
+        if kind == 'bound':   # the same points on the row kernels, in the same process
+            b = m.at_texture(tex6[2])
+            got, b_ms, b_wall, b_l = timed(lambda: b.response_batch(sig, epl, deps, CV))
+            assert b_l == 1 and np.all(np.isfinite(got[1]))
+            res.update(bound_kernel_ms=b_ms, bound_wall_ms=b_wall, kernel_ratio=k_ms / b_ms, wall_ratio=k_wall / b_wall,
+                       bound_sub_divided=int(np.sum(got[4] == 49)), nsteps_equal=int(np.sum(got[4] == out[4])),
+                       max_stress_difference_over_sy=float(np.max(np.abs(got[1] - out[1]))) / float(m.sy))
     else:
         u = rng.normal(size=(n, 6))
         sig = u / np.linalg.norm(u, axis=1)[:, None] * 100.
@@ -132,18 +149,80 @@ def step(name, reps):
     return 0
 
 
+def model_step(kind, n):
+    """one Model.solve on n x n elements: three sections bound at three training textures (model), or the 6-feature 'hill'
+    material of benchmark configuration 4 in all three (model6)"""
+    import texture_cases as TC
+    import pylabfea_amd as FE
+    from pylabfea_amd import _lib
+    if kind == 'model':
+        z = TC.load()
+        with tempfile.TemporaryDirectory() as tmp:
+            m, _ = TC.facade(FE, z, tmp, DESC)
+        TC.install(m, TC.tables(z, DESC))
+        tex = TC.textures(z, DESC)[:3]
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            ys = [float(m.yield_scale(np.array([0., 1., 0., 0., 0., 0.]), tex=t)) for t in tex]
+        mats = [m.at_texture(t) for t in tex]
+        eps, nsv = 1.2 * max(ys) / m.E, len(m.svc['dual'])
+    else:
+        g = np.load(os.path.join(ROOT, 'tests', 'golden', 'svc_hill.npz'))
+        m6 = FE.Material(name='ML-Hill-p1')
+        m6.elasticity(CV=g['par_CV'])
+        m6.plasticity(sy=float(g['par_sy']), sdim=6)
+        m6.set_svc(g['par_sv'], g['par_dual'], float(g['par_intercept']), float(g['par_gamma']), float(g['par_scale_seq']))
+        mats, eps, nsv = [m6, m6, m6], 0.001, len(g['par_dual'])
+    fe = FE.Model(dim=2, planestress=False)
+    fe.geom([1, 1, 1], LY=3.)
+    fe.assign(mats)
+    fe.bcleft(0.)
+    fe.bcbot(0.)
+    fe.bcright(0., 'force')
+    fe.bctop(eps * fe.leny, 'disp')
+    fe.mesh(NX=n, NY=n)
+    eng = fe._ensure_engine()
+    dev, cus, _ = eng.device_info()
+    eng.timing_reset()
+    eng.timing_select((_lib.T_SWEEP, _lib.T_SWEEP_HEAVY))
+    eng.timing_enable(True)
+    t0 = time.perf_counter()
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        fe.solve(min_step=10)
+    eng.sync()
+    wall = time.perf_counter() - t0
+    eng.timing_enable(False)
+    ms_l, n_l = eng.timing_get(_lib.T_SWEEP)
+    ms_h, n_h = eng.timing_get(_lib.T_SWEEP_HEAVY)
+    row, thread, nrow, nthread = eng.svc_info()
+    steps = np.asarray(fe._state('max_steps'))
+    res = dict(device=dev, cus=cus, step='%s:%d' % (kind, n), nsv=int(nsv), elements=int(fe.Nel), eps=float(eps), wall_s=wall,
+               load_steps=int(fe.nsteps), sweeps=int(fe.n_sweeps), streaming_kernel_ms=ms_l, corrector_kernel_ms=ms_h,
+               streaming_launches=int(n_l), corrector_launches=int(n_h), row_materials=int(row), thread_launches=int(nthread),
+               plastic_elements=int(np.sum(np.any(fe._state('epl') != 0., axis=1))), sub_divided_elements=int(np.sum(steps > 0)),
+               us_per_element_update_wall=1e6 * wall / (fe.Nel * fe.n_sweeps),
+               us_per_element_update_kernels=1e3 * (ms_l + ms_h) / (fe.Nel * fe.n_sweeps),
+               sgl_yy=float(fe.sgl[-1][1]))
+    print(json.dumps(res))
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--reps', type=int, default=11)
     ap.add_argument('--limit', type=int, default=240, help='time limit of one step in seconds')
     ap.add_argument('--flow', action='store_true', help='time calc_fgrad(tex=) and response_batch(tex=) instead')
+    ap.add_argument('--bound', action='store_true', help='time a material bound to one texture (at_texture) instead')
     ap.add_argument('--step', default='', help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
         return step(a.step, a.reps)
     if a.reps < 10:
         ap.error('--reps must be at least 10 (median of >= 10 launches)')
-    for name in (FLOW_STEPS if a.flow else STEPS):   # a fresh child per step, each under its own limit; stop at the first that fails
+    if a.flow and a.bound:
+        ap.error('--flow and --bound are two runs')
+    for name in (BOUND_STEPS if a.bound else FLOW_STEPS if a.flow else STEPS):   # a fresh child per step, each under its own limit; stop at the first that fails
         rc = subprocess.call(['timeout', '-k', '10', str(a.limit), sys.executable, os.path.abspath(__file__),
                               '--step', name, '--reps', str(a.reps)])
         if rc != 0:
