@@ -381,6 +381,29 @@ enum {
     PLFX_PLANE_TANGENT_SET = 6  /* plfx_state_set of the tangents */
 };
 int plfx_plane_info(plfx_ctx *ctx, int *mode_on, int64_t *plane_sweeps, int64_t *plane_updates, int *switched_off_by);
+/* Which form of the multigrid V-cycle the next cycle of this context runs (read-only, tests assert the
+ * path they were written for).  *levels = levels of the hierarchy (0: none).  The first min(*levels, max_levels) entries of
+ * the per-level arrays (any of them may be null): dims[2l], dims[2l+1] = nx, ny elements; ratios[2l], ratios[2l+1] = rx, ry,
+ * the size of the last element column / row relative to the others; matfree[l] = 1 where the level's operator is applied from
+ * the stiffness generators (its smoothing diagonal comes from the generators too: area-scaled on a level with rx or ry != 1),
+ * 0 where it is an assembled block-ELL matrix with the true diagonal.  *tail_level = first level of the single-workgroup tail
+ * (-1: no tail kernel; the coarsest level is then solved by a launch of its own), *tail_kernel = PLFX_MG_TAIL_*,
+ * *coarse_solver = PLFX_MG_COARSE_* with *cheby_steps and *cheby_kappa (0 unless Chebyshev), *march = 1 where the fine-level
+ * kernels of the cycle run in marching form. */
+enum {
+    PLFX_MG_TAIL_NONE = 0,       /* every level is launched kernel by kernel */
+    PLFX_MG_TAIL_GENERIC = 1,    /* k_mg_tail: vectors in global memory, any number of sweeps, any coarsest solver */
+    PLFX_MG_TAIL_LDS = 2,        /* k_mg_tail_lds: assembled levels, vectors and neighbour tables in LDS */
+    PLFX_MG_TAIL_MF = 3,         /* k_mg_tail_mf<false>: matrix-free, every tail level halves exactly */
+    PLFX_MG_TAIL_MF_RAGGED = 4   /* k_mg_tail_mf<true>: matrix-free, a tail level has a last column / row of another size */
+};
+enum {
+    PLFX_MG_COARSE_DENSE = 0,    /* dense inverse (unpivoted Gauss-Jordan, once per set of boundary conditions) */
+    PLFX_MG_COARSE_CHEBY = 1,    /* fixed number of Jacobi-preconditioned Chebyshev steps */
+    PLFX_MG_COARSE_PCG = 2       /* Jacobi-PCG inside one workgroup, vectors in LDS, to 1e-10 */
+};
+int plfx_mg_info(plfx_ctx *ctx, int max_levels, int *levels, int *dims, double *ratios, int *matfree, int *tail_level,
+                 int *tail_kernel, int *coarse_solver, int *cheby_steps, double *cheby_kappa, int *march);
 /* Which kernels run the 6-feature SVC materials (Material.response with an ML yield function, material.py:398-405 evaluates
  * any trained svm_yf): bit k of *row_materials = material k runs with 16 lanes per element / point (one launch per material
  * and sweep phase), its support-vector tables staged in LDS when they fit the 160 KB of a CU (up to ~2200 vectors) and read

@@ -67,7 +67,7 @@ SYMBOLS = [
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info',
     'plfx_dead_store_info', 'plfx_plane_info',
-    'plfx_set_svc_cols',
+    'plfx_set_svc_cols', 'plfx_mg_info',
 ]
 
 _lib = None
@@ -762,6 +762,25 @@ class Context(object):
         on, a, b, why = C.c_int(), C.c_int64(), C.c_int64(), C.c_int()
         self._chk(self.lib.plfx_plane_info(self.h, C.byref(on), C.byref(a), C.byref(b), C.byref(why)))
         return bool(on.value), a.value, b.value, why.value
+
+    MG_TAIL_KERNELS = ('none', 'tail', 'tail_lds', 'tail_mf', 'tail_mf_ragged')
+    MG_COARSE_SOLVERS = ('dense', 'cheby', 'pcg')
+
+    def mg_info(self):
+        """dict: the form of the V-cycle the next cycle runs (plfx_mg_info) -- 'levels': [(nx, ny, rx, ry, matrix-free), ...],
+        'tail_level' (-1: no tail kernel), 'tail_kernel' (one of MG_TAIL_KERNELS), 'coarse_solver' (one of MG_COARSE_SOLVERS),
+        'cheby_steps', 'cheby_kappa', 'march' (marching fine-level kernels)"""
+        cap = 64
+        nl, tl, tk, cs, st, ma = (C.c_int() for _ in range(6))
+        kap = C.c_double()
+        dims, rat, mf = np.zeros((cap, 2), dtype=np.int32), np.zeros((cap, 2)), np.zeros(cap, dtype=np.int32)
+        self._chk(self.lib.plfx_mg_info(self.h, cap, C.byref(nl), _dp(dims), _dp(rat), _dp(mf), C.byref(tl), C.byref(tk),
+                                        C.byref(cs), C.byref(st), C.byref(kap), C.byref(ma)))
+        n = min(nl.value, cap)
+        return {'levels': [(int(dims[l, 0]), int(dims[l, 1]), float(rat[l, 0]), float(rat[l, 1]), bool(mf[l])) for l in range(n)],
+                'tail_level': tl.value, 'tail_kernel': self.MG_TAIL_KERNELS[tk.value],
+                'coarse_solver': self.MG_COARSE_SOLVERS[cs.value], 'cheby_steps': st.value, 'cheby_kappa': kap.value,
+                'march': bool(ma.value)}
 
     def svc_info(self):
         """(bit mask of the 6-feature SVC materials on the 16-lanes-per-element kernels, mask of those run one thread per

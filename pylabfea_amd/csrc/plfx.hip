@@ -1292,6 +1292,13 @@ int assemble_fine_val(plfx_ctx *c)
 // the level halves exactly and all its cells have one size (every level of a mesh whose sizes are multiples of 2^levels)
 static bool level_plain(const plfx_ctx::MgLevel &L) { return !(L.nx & 1) && !(L.ny & 1) && L.rx == 1. && L.ry == 1.; }
 
+// level l >= 1 is applied from its generators (launched matrix-free, or inside the matrix-free tail): only its diagonal is
+// formed, by k_grid_setup; every other level >= 1 is assembled, diagonal included, by k_assemble
+static bool level_from_generators(const plfx_ctx *c, int l)
+{
+    return matfree(c) && (c->mg[l].matfree || (tail_mf(c) && l < (int)c->mg.size() - 1));
+}
+
 // coarse operators: restrict M level by level and re-assemble (called after the fine assembly)
 int mg_assemble(plfx_ctx *c)
 {
@@ -1308,7 +1315,7 @@ int mg_assemble(plfx_ctx *c)
             hipLaunchKernelGGL(k_mg_coarsen_M, dim3(grid_for(L.nel)), dim3(BLOCK), 0, c->stream, L.nx, L.ny, F.ny,
                                F.nel, (l == 1 && mf) ? c->mg[0].op.M : F.Mel, L.Mel, mf ? 1 : 0, mf ? 1 : 0, F.rx, F.ry);  // matrix-free mode: pair
                                // layout on every level >= 1 and in the snapshot of level 0 (the live array of level 0 is SoA)
-        const bool setup_mf = mf && (L.matfree || (tail_mf(c) && l < nl - 1));  // coarsest: assembled for the dense inverse
+        const bool setup_mf = level_from_generators(c, l);  // coarsest: assembled for the dense inverse
         if (setup_mf)  // only the diagonal (Jacobi smoother) is needed
             LAUNCH_SETUP(1, L.op, (double2 *)L.diag,
                                (double *)nullptr, (l + 1 < nl && level_plain(L)) ? c->mg[l + 1].Mel : (double *)nullptr,
@@ -1446,6 +1453,22 @@ int mg_up_level(plfx_ctx *c, int l, double *rz_part, bool *wrote)
     return 0;
 }
 
+// which single-workgroup kernel runs the levels >= lt of a cycle (PLFX_MG_TAIL_*; NONE: the coarsest level alone, by a launch
+// of its own).  mg_coarse_part launches by it and plfx_mg_info reports it.
+int mg_tail_kernel(const plfx_ctx *c)
+{
+    const int nl = (int)c->mg.size();
+    const int lt = (c->mg_tail > 0) ? c->mg_tail : nl - 1;
+    if (!(lt < nl - 1)) return PLFX_MG_TAIL_NONE;
+    if (tail_mf(c)) {
+        bool ragged = false;   // some level of the tail is not "all cells alike, halving exactly" (hierarchy of an odd-sized mesh)
+        for (int l = lt; l < nl - 1; l++) ragged = ragged || !level_plain(c->mg[l]);
+        return ragged ? PLFX_MG_TAIL_MF_RAGGED : PLFX_MG_TAIL_MF;
+    }
+    if (c->mg_tail_T > 0 && c->mg_nu == 2) return PLFX_MG_TAIL_LDS;
+    return PLFX_MG_TAIL_GENERIC;
+}
+
 // levels 1 .. coarsest: every kernel here is launch-latency bound (<= 513^2 nodes)
 int mg_coarse_part(plfx_ctx *c)
 {
@@ -1484,21 +1507,18 @@ int mg_coarse_part(plfx_ctx *c)
     } else {
         auto &L = c->mg[nl - 1];
         const size_t lds = (size_t)L.nnode * 4 * sizeof(double2);
-        if (lt < nl - 1 && tail_mf(c)) {
-            bool ragged = false;   // some level of the tail is not "all cells alike, halving exactly" (hierarchy of an odd-sized mesh)
-            for (int l = lt; l < nl - 1; l++) ragged = ragged || !level_plain(c->mg[l]);
-            if (ragged)
-                hipLaunchKernelGGL(k_mg_tail_mf<true>, dim3(1), dim3(MG_TAIL_BLOCK), c->mg_tail_lds,
-                                   c->stream, c->mg_dev, lt, nl, c->mg_tail_T, c->mg_tail_E, c->dtab, om, c->sc);
-            else
-                hipLaunchKernelGGL(k_mg_tail_mf<false>, dim3(1), dim3(MG_TAIL_BLOCK), c->mg_tail_lds,
-                                   c->stream, c->mg_dev, lt, nl, c->mg_tail_T, c->mg_tail_E, c->dtab, om, c->sc);
-        }
-        else if (lt < nl - 1 && c->mg_tail_T > 0 && c->mg_nu == 2)
+        const int tail = mg_tail_kernel(c);
+        if (tail == PLFX_MG_TAIL_MF_RAGGED)
+            hipLaunchKernelGGL(k_mg_tail_mf<true>, dim3(1), dim3(MG_TAIL_BLOCK), c->mg_tail_lds,
+                               c->stream, c->mg_dev, lt, nl, c->mg_tail_T, c->mg_tail_E, c->dtab, om, c->sc);
+        else if (tail == PLFX_MG_TAIL_MF)
+            hipLaunchKernelGGL(k_mg_tail_mf<false>, dim3(1), dim3(MG_TAIL_BLOCK), c->mg_tail_lds,
+                               c->stream, c->mg_dev, lt, nl, c->mg_tail_T, c->mg_tail_E, c->dtab, om, c->sc);
+        else if (tail == PLFX_MG_TAIL_LDS)
             hipLaunchKernelGGL(k_mg_tail_lds, dim3(1), dim3(MG_TAIL_BLOCK),
                                (size_t)c->mg_tail_T * (4 * sizeof(double2) + 9 * sizeof(int)), c->stream, c->mg_dev,
                                lt, nl, c->mg_tail_T, om, c->sc);
-        else if (lt < nl - 1)
+        else if (tail == PLFX_MG_TAIL_GENERIC)
             hipLaunchKernelGGL(k_mg_tail, dim3(1), dim3(MG_TAIL_BLOCK), lds, c->stream, c->mg_dev, lt, nl, om,
                                c->mg_nu, c->sc);
         else if (L.ainv)
@@ -3842,6 +3862,31 @@ int plfx_plane_info(plfx_ctx *c, int *mode_on, int64_t *plane_sweeps, int64_t *p
     if (plane_sweeps) *plane_sweeps = c->n_plane_sweeps;
     if (plane_updates) *plane_updates = c->n_plane_updates;
     if (switched_off_by) *switched_off_by = on ? PLFX_PLANE_ON : c->plane_cols ? PLFX_PLANE_SHARDED : c->plane_off_by;
+    return PLFX_OK;
+}
+
+int plfx_mg_info(plfx_ctx *c, int max_levels, int *levels, int *dims, double *ratios, int *matfree_level, int *tail_level,
+                 int *tail_kernel, int *coarse_solver, int *cheby_steps, double *cheby_kappa, int *march)
+{
+    if (!c) return PLFX_ERR_ARG;
+    const int nl = mg_active(c) ? (int)c->mg.size() : 0;
+    if (levels) *levels = nl;
+    for (int l = 0; l < nl && l < max_levels; l++) {
+        const auto &L = c->mg[l];
+        if (dims) dims[2 * l] = L.nx, dims[2 * l + 1] = L.ny;
+        if (ratios) ratios[2 * l] = L.rx, ratios[2 * l + 1] = L.ry;
+        if (matfree_level) matfree_level[l] = (l == 0 ? matfree(c) : level_from_generators(c, l)) ? 1 : 0;
+    }
+    const int tail = (nl && !c->strip.on) ? mg_tail_kernel(c) : PLFX_MG_TAIL_NONE;
+    if (tail_kernel) *tail_kernel = tail;
+    if (tail_level) *tail_level = tail != PLFX_MG_TAIL_NONE ? c->mg_tail : -1;
+    // (what mg_coarse_part does with the coarsest level: the LDS-resident tails require the dense inverse)
+    const bool dense = nl && c->mg.back().ainv;
+    const bool cheby = nl && !dense && tail == PLFX_MG_TAIL_NONE && c->mg_cheby > 0;
+    if (coarse_solver) *coarse_solver = dense ? PLFX_MG_COARSE_DENSE : cheby ? PLFX_MG_COARSE_CHEBY : PLFX_MG_COARSE_PCG;
+    if (cheby_steps) *cheby_steps = cheby ? c->mg_cheby : 0;
+    if (cheby_kappa) *cheby_kappa = cheby ? c->mg_cheby_kappa : 0.;
+    if (march) *march = (nl && c->mg[0].matfree && march_mg(c)) ? 1 : 0;
     return PLFX_OK;
 }
 
