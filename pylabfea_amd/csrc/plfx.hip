@@ -1990,6 +1990,16 @@ static void plane_off(plfx_ctx *c, int why)
 // (a strip or a communicator can be set up after the reset: asked at every launch)
 static bool plane_active(const plfx_ctx *c) { return c->plane_cols && !c->strip.on && !comm_active(c) && !c->sharded; }
 
+// Grid of k_sweep_light_plane: the element grid (PLFX_SWEEP_BLOCKS included), but no more blocks than the device holds
+// at once -- 4 SIMDs per CU at the waves per SIMD the kernel is compiled for.  A count that is off costs speed only.
+static int plane_sweep_grid(const plfx_ctx *c)
+{
+    const int resident = c->prop.multiProcessorCount * (PLANE_SWEEP_WAVES * 4 * 64 / BLOCK);
+    int g = std::min(c->grid_el, std::max(resident, 1));
+    if (g >= 16) g &= ~7;   // (xcd_tile, as grid_xcd)
+    return g;
+}
+
 int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
 {
     if (!c || !c->stream) return PLFX_ERR_STATE;
@@ -5854,7 +5864,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh && !c->svc_cols_mask)) {
         if (plane_active(c)) {   // (the same timing family)
-            hipLaunchKernelGGL(k_sweep_light_plane, dim3(c->grid_el), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead);
+            hipLaunchKernelGGL(k_sweep_light_plane, dim3(plane_sweep_grid(c)), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead);
             c->n_plane_sweeps++;
         } else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,

@@ -812,6 +812,31 @@ __device__ __forceinline__ void class_strain(const ClassDev &c, const double2 *u
     e[5] = gxy;
 }
 
+// A use of x that costs no instruction: the compiler's wait for the load that produces x is placed here and nowhere later
+// (k_sweep_light_plane)
+template <class T>
+__device__ __forceinline__ void landed(const T &x)
+{
+    asm volatile("" ::"v"(x));
+}
+
+// class_strain on nodal values that are already in registers (k_sweep_light_plane gathers them a tile ahead):
+// the same expressions in the same order, so the same bits
+__device__ __forceinline__ void class_strain_of(const ClassDev &c, const double2 &u0, const double2 &u1,
+                                                const double2 &u2_, const double2 &u3, double *e)
+{
+    const double ex = c.bxs[0] * u0.x + c.bxs[1] * u1.x + c.bxs[2] * u2_.x + c.bxs[3] * u3.x;
+    const double ey = c.bys[0] * u0.y + c.bys[1] * u1.y + c.bys[2] * u2_.y + c.bys[3] * u3.y;
+    const double gxy = c.bys[0] * u0.x + c.bxs[0] * u0.y + c.bys[1] * u1.x + c.bxs[1] * u1.y +
+                       c.bys[2] * u2_.x + c.bxs[2] * u2_.y + c.bys[3] * u3.x + c.bxs[3] * u3.y;
+    e[0] = ex;
+    e[1] = ey;
+    e[2] = c.kappa * (ex + ey);
+    e[3] = 0.;
+    e[4] = 0.;
+    e[5] = gxy;
+}
+
 // compact element stiffness generator M = [X Y S]^T D [X Y S], X = e0 + kappa e2, Y = e1 + kappa e2,
 // S = e5: the six numbers from which every 2x2 block of B^T D B follows (see k_assemble).
 __device__ __forceinline__ void tangent_to_M(const double *D, double kappa, double *M)
@@ -903,7 +928,10 @@ constexpr __device__ __host__ bool plane_fac(int k) { return k != 4 && k != 5; }
 // TAN_FULL element (cold path) are loaded here.  omax: the element's max_steps so far.
 // PLANE (k_sweep_light_plane): columns 3 and 4 of res_sig / res_depl and rows 4 and 5 of the factors are zero-valued
 // in memory and stay so -- their stores are left out.  A template parameter for the reason MAY_SKIP is one.
-template <bool MAY_SKIP = false, bool PLANE = false>
+// AHEAD (k_sweep_light_plane): the caller has the next tile's loads in flight.  The 21 loads of a TAN_FULL old tangent
+// are waited for inside their own (cold) branch; left to the compiler, the wait stands behind the join, where on the common
+// path it waits for nothing but the caller's prefetch.
+template <bool MAY_SKIP = false, bool PLANE = false, bool AHEAD = false>
 __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &m, int e, int nel,
                                                const double *s, const double *ep, const double *depl,
                                                int form, const double *Ct, double fy, int ns, const TanStore &ts,
@@ -933,6 +961,10 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
     if (oform == TAN_FULL) {
 #pragma unroll
         for (int k = 0; k < 21; k++) Dold[k] = ts.full[(size_t)k * nel + e];
+        if (AHEAD) {
+#pragma unroll
+            for (int k = 0; k < 21; k++) landed(Dold[k]);
+        }
     } else {
         tan_expand(oform, m.CV, ofac, Dold);
     }
@@ -989,18 +1021,22 @@ struct SweepIn {
 
 // e < nel is the predicate of every load: no address beyond the arrays is formed for the tile past the end
 // PLANE: s[3], s[4], ep[3], ep[4], fac[4], fac[5] are not loaded and stay 0. (what memory holds there)
-template <bool PLANE = false>
+// AHEAD (k_sweep_light_plane): the streams alone, of an element index the caller has clamped into the arrays -- no
+// predicate; the connectivity goes its own way there, two tiles ahead, and max_steps is not read (in.n and in.ms stay 0)
+template <bool PLANE = false, bool AHEAD = false>
 __device__ __forceinline__ void sweep_in_load(SweepIn &in, long long e, int nel, int e_off, const int32_t *__restrict__ cls,
                                               const int32_t *__restrict__ conn, const double *__restrict__ sig,
                                               const double *__restrict__ epl, const TanStore &ts,
                                               const int32_t *max_steps)
 {
     in = SweepIn{};
-    if (e < nel) {
+    if (AHEAD || e < nel) {
         const size_t ge = (size_t)e + e_off;
         in.cl = cls[e];
+        if (!AHEAD) {
 #pragma unroll
-        for (int k = 0; k < 4; k++) in.n[k] = conn[ge * 4 + k];
+            for (int k = 0; k < 4; k++) in.n[k] = conn[ge * 4 + k];
+        }
 #pragma unroll
         for (int k = 0; k < 6; k++) {
             if (PLANE && !plane_col(k)) continue;
@@ -1008,7 +1044,7 @@ __device__ __forceinline__ void sweep_in_load(SweepIn &in, long long e, int nel,
             in.ep[k] = epl[(size_t)k * nel + e];
         }
         in.form = ts.tag[e];
-        in.ms = max_steps[e];
+        if (!AHEAD) in.ms = max_steps[e];
 #pragma unroll
         for (int k = 0; k < 7; k++)
             if (!PLANE || plane_fac(k)) in.fac[k] = ts.fac[(size_t)k * nel + e];
@@ -1239,9 +1275,14 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
 // memory and the return mapping keeps them zero, so they are neither loaded nor stored; the arithmetic is the one above, on
 // zeros held in registers.  A kernel of its own and not a parameter of k_sweep_light: a shared body behind two entry points
 // changed the registers and the scratch of k_sweep_light<1>, <2>, <5>, <6> and <7>, which must stay what they are.  What
-// differs from the text above: the PLANE forms of sweep_in_load and sweep_epilogue, and KIND = 1 written out (no SVC tables,
-// no hardening modulus per material point).
-__global__ void __launch_bounds__(BLOCK, PLFX_SWEEP_WAVES < 2 ? 2 : PLFX_SWEEP_WAVES)
+// differs from the text above: the PLANE forms of sweep_in_load and sweep_epilogue, KIND = 1 written out (no SVC tables,
+// no hardening modulus per material point), and the tile loop, which is pipelined a whole tile ahead with the gather of du
+// included and does not read max_steps (252 VGPRs, no scratch, two waves per SIMD).
+// The grid (plane_sweep_grid in plfx.hip) is at most the blocks the device holds at once at PLANE_SWEEP_WAVES waves per SIMD:
+// every block is resident from the start and takes more passes, over which the pipeline's two dependent round trips in front
+// of the loop are spread.
+constexpr int PLANE_SWEEP_WAVES = PLFX_SWEEP_WAVES < 2 ? 2 : PLFX_SWEEP_WAVES;   // waves per SIMD the kernel is compiled for
+__global__ void __launch_bounds__(BLOCK, PLANE_SWEEP_WAVES)
 k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
                     int lds_doubles, int nel, int e_off, const int32_t *__restrict__ conn,
                     const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
@@ -1255,13 +1296,44 @@ k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *_
     int changed = 0, nconv = 0;
     const int nb = gridDim.x;
     int t = xcd_tile(blockIdx.x, nb);
+    // Pipelined a whole tile ahead, gather included.  A pass consumes nothing that it requests itself: the streams
+    // (nx) and the four nodal du values (nu) of its tile were requested a pass earlier, through a connectivity (cn) requested
+    // two passes earlier.  For a tile past the end the last element stands in (el): every address lies inside its array and
+    // every gathered node index is a real one; what comes back is dropped (e < nel below).
+    const int4 *__restrict__ conn4 = reinterpret_cast<const int4 *>(conn);   // (4 ints per element, 16-byte aligned)
+    const auto el = [&](long long tile) { return (int)min(tile * BLOCK + threadIdx.x, (long long)nel - 1); };
     SweepIn nx;
-    sweep_in_load<true>(nx, (long long)t * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+    double2 nu[4];
+    int4 cn;
+    {
+        const int4 c0 = conn4[(size_t)el(t) + e_off];
+        cn = conn4[(size_t)el((long long)t + nb) + e_off];
+        sweep_in_load<true, true>(nx, el(t), nel, e_off, cls, conn, sig, epl, ts, max_steps);
+        nu[0] = du2[c0.x], nu[1] = du2[c0.y], nu[2] = du2[c0.z], nu[3] = du2[c0.w];
+        // The first pass needs all of this at its top anyway.  Asked for here, in front of the loop, it leaves the compiler's
+        // wait counts inside the loop free of the prologue: with loads pending on entry it put waits for them -- which are
+        // waits for the pass's own loads as well, the counter being one queue -- in the middle of the pass.
+        landed(cn.x), landed(cn.y), landed(cn.z), landed(cn.w), landed(nx.cl), landed(nx.form);
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            if (k < 6 && plane_col(k)) landed(nx.s[k]), landed(nx.ep[k]);
+            if (plane_fac(k)) landed(nx.fac[k]);
+            if (k < 4) landed(nu[k].x), landed(nu[k].y);
+        }
+    }
     for (; t * BLOCK < nel; t += nb) {
         const int e = t * BLOCK + threadIdx.x;
         bool heavy = false;
-        const SweepIn in = nx;   // (in flight since the previous pass; the next tile's streams go out now, as in k_sweep_light<1>)
-        sweep_in_load<true>(nx, (long long)(t + nb) * BLOCK + threadIdx.x, nel, e_off, cls, conn, sig, epl, ts, max_steps);
+        const SweepIn in = nx;
+        const double2 u0 = nu[0], u1 = nu[1], u2_ = nu[2], u3 = nu[3];
+        // The order of issue is part of the design: the gather of tile t + nb first (its addresses, cn, are a pass old), then
+        // the connectivity of tile t + 2 nb, then the streams of tile t + nb.  A gather behind the stream loads would make
+        // the compiler wait for all of them in front of the gather's address registers.
+        nu[0] = du2[cn.x], nu[1] = du2[cn.y], nu[2] = du2[cn.z], nu[3] = du2[cn.w];
+        asm volatile("" ::: "memory");
+        cn = conn4[(size_t)el((long long)t + 2 * nb) + e_off];
+        asm volatile("" ::: "memory");
+        sweep_in_load<true, true>(nx, el((long long)t + nb), nel, e_off, cls, conn, sig, epl, ts, max_steps);
         asm volatile("" ::: "memory");
         if (e < nel) {
             const ClassDev &c = tb.scls[in.cl];
@@ -1270,7 +1342,7 @@ k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *_
                 if (first_kind) fyn[e] = 0.;
             } else if (m.kind == 1 && !((skip_mask >> c.mat) & 1u)) {
                 double deps[6], s[6], ep[6], depl[6], Ct[21], dr[6], fy, st_scal;
-                class_strain(c, du2, in.n[0], in.n[1], in.n[2], in.n[3], deps);
+                class_strain_of(c, u0, u1, u2_, u3, deps);
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
                     s[k] = in.s[k];
@@ -1281,8 +1353,10 @@ k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *_
                 if (st == 2)
                     heavy = true;  // (k_sweep_heavy<1> stores all six columns, zero-valued in columns 3 and 4)
                 else
-                    sweep_epilogue<true, true>(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, in.ms, Mel, mel_stride, res_sig,
-                                               res_depl, fyn, max_steps, nit, changed, nconv, -1., dead_ok);
+                    // (omax = 0 and not max_steps[e]: with ns = 0 the store `if (ns > omax)` never happens -- max_steps is zero-filled
+                    // by plfx_state_reset, a running maximum, and not settable from outside -- so the value is not loaded)
+                    sweep_epilogue<true, true, true>(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, 0, Mel, mel_stride,
+                                                     res_sig, res_depl, fyn, max_steps, nit, changed, nconv, -1., dead_ok);
             }
         }
         const unsigned long long mask = __ballot(heavy);
