@@ -665,6 +665,30 @@ int plfx_set_svc_cols(plfx_ctx *ctx, int mat, const double scale[6]);
 /* rows of the rule attached to material `mat` (0: none) and the response launches that took the SVR kernel for it since
  * it was attached (either pointer may be NULL) */
 int plfx_svr_flow_info(plfx_ctx *ctx, int mat, int *rows, int64_t *launches);
+/* A texture field on material `mat`, a PLFX_SVC6_COLS record: coef[ntex * nsv], row-major, holds one row of
+ * dual coefficients per texture (Material.fold_textures); an element or point with texture row t runs with row t in place of
+ * the record's dual and with sum |coef[t][.]| (fabs in index order, as plfx_set_materials sums the record's) in the error bound
+ * of the sampled ray.  Vectors, column scales, gamma and intercept are the record's.  The rows are copied to device memory
+ * owned by the context, padded with zeros to the width of the row tables.  ntex = 0 detaches: the material is the plain
+ * record again.  plfx_set_materials detaches every field; plfx_destroy frees them.  Another kind: PLFX_ERR_UNSUPPORTED; without
+ * materials: PLFX_ERR_STATE; a coefficient that is not finite, ntex < 0 or ntex * (padded width) > INT32_MAX: PLFX_ERR_ARG. */
+int plfx_set_svc_textures(plfx_ctx *ctx, int mat, int ntex, const double *coef);
+/* The texture row of every element, tex_id[nel] in element order (after the mesh; every rank-owned element of a single-GPU
+ * mesh).  NULL, or a new mesh, clears it: every element has row 0.  Entries of elements whose material carries no field are
+ * ignored; the others are checked on the host against the attached rows when a sweep or calc_scf is set up, and an entry
+ * outside 0..ntex-1 is PLFX_ERR_ARG there, before anything is launched.  A strip, a shard or a communicator with a field
+ * material in the model is PLFX_ERR_UNSUPPORTED. */
+int plfx_set_element_textures(plfx_ctx *ctx, const int32_t *tex_id);
+/* plfx_full_yf_batch / plfx_response_batch with the texture row of every point, tex_id[n] (NULL: row 0).  Points of materials
+ * without a field ignore their entry; the others are checked on the host (PLFX_ERR_ARG, nothing launched). */
+int plfx_full_yf_batch_tid(plfx_ctx *ctx, int mat, int n, const double *sig, const double *epl,
+                           const double *ld, double *yf, int32_t *status, const int32_t *tex_id);
+int plfx_response_batch_tid(plfx_ctx *ctx, int n, const int32_t *mat_id, const double *sig,
+                            const double *epl, const double *deps, double *fy, double *sig_out,
+                            double *depl, double *ct /* [n*36] */, int32_t *nsteps, const int32_t *tex_id);
+/* rows attached to material `mat` (0: none), whether they are staged in LDS (0: the kernels read them from device memory),
+ * and the launches that took a texture-field instantiation for it since the rows were attached (any pointer may be NULL) */
+int plfx_svc_textures_info(plfx_ctx *ctx, int mat, int *rows, int *staged, int64_t *launches);
 
 /* ---------------------------------------------------------------- instrumentation */
 /* accumulated HIP-event time (ms) and launch count of a named kernel family since the last reset:

@@ -68,6 +68,8 @@ SYMBOLS = [
     'plfx_flow_curve', 'plfx_flow_info',
     'plfx_dead_store_info', 'plfx_plane_info',
     'plfx_set_svc_cols', 'plfx_mg_info',
+    'plfx_set_svc_textures', 'plfx_set_element_textures', 'plfx_response_batch_tid', 'plfx_full_yf_batch_tid',
+    'plfx_svc_textures_info',
 ]
 
 _lib = None
@@ -161,8 +163,9 @@ def eig3_host(sig):
 def pack_material(kind, CV, E=0., nu=0., sy=0., khard=0., hill=None, drucker=0., svc=None, barlat=None,
                   barlat_exp=0., barlat_normal=False):
     """Build a plfx_material record.  svc = dict(sv, dual, gamma, intercept, scale_seq, dev_only); a SVC6_COLS record adds
-    scale_cols, its six column scales.  Returns (struct, keepalive) - keepalive holds the arrays the struct points to (and,
-    as its third entry, the column scales that Context.set_materials sends after the record)."""
+    scale_cols, its six column scales, and for a texture field coef, the (T, nsv) coefficient rows.  Returns
+    (struct, keepalive) - keepalive holds the arrays the struct points to (and, as its third entry, the column scales and,
+    as its fourth, the coefficient rows that Context.set_materials sends after the record)."""
     m = CMaterial()
     m.kind = int(kind)
     m.sdim = 3 if kind in (PRINC3, SVC3) else 6
@@ -199,6 +202,11 @@ def pack_material(kind, CV, E=0., nu=0., sy=0., khard=0., hill=None, drucker=0.,
             if cols.shape != (6,):
                 raise ValueError('pack_material: a SVC6_COLS record needs six column scales (scale_cols)')
             keep.append(cols)
+            if svc.get('coef') is not None:
+                coef = _f64(svc['coef'])
+                if coef.ndim != 2 or coef.shape[1] != m.nsv or len(coef) < 1:
+                    raise ValueError('pack_material: the coefficient rows of a texture field must be (T, nsv) with T >= 1')
+                keep.append(coef)
     return m, keep
 
 
@@ -264,6 +272,8 @@ class Context(object):
         for i, (m, keep) in enumerate(records):   # the column scales of SVC6_COLS records (pack_material)
             if m.kind == SVC6_COLS:
                 self.set_svc_cols(i, keep[2])
+                if len(keep) > 3:   # ... and the coefficient rows of a texture field
+                    self.set_svc_textures(i, keep[3])
 
     def set_svc_cols(self, mat, scale):
         """the six column scales of the SVC6_COLS material ``mat`` (plfx_set_svc_cols); they hold until the next set_materials"""
@@ -271,6 +281,33 @@ class Context(object):
         if sc.shape != (6,):
             raise ValueError('set_svc_cols: six scales expected')
         self._chk(self.lib.plfx_set_svc_cols(self.h, int(mat), _dp(sc)))
+
+    def set_svc_textures(self, mat, coef):
+        """the coefficient rows (T, nsv) of a texture field on the SVC6_COLS material ``mat`` (plfx_set_svc_textures); None
+        detaches; they hold until the next set_materials"""
+        if coef is None:
+            self._chk(self.lib.plfx_set_svc_textures(self.h, int(mat), 0, None))
+            return
+        co = _f64(coef)
+        if co.ndim != 2:
+            raise ValueError('set_svc_textures: coefficient rows (T, nsv) expected')
+        self._chk(self.lib.plfx_set_svc_textures(self.h, int(mat), len(co), _dp(co)))
+
+    def set_element_textures(self, tex_id):
+        """the texture row of every owned element, (nel,) int (plfx_set_element_textures); None: every element has row 0"""
+        if tex_id is None:
+            self._chk(self.lib.plfx_set_element_textures(self.h, None))
+            return
+        ids = _i32(tex_id).reshape(-1)
+        if len(ids) != self.nel_owned:
+            raise ValueError('set_element_textures: one row index per element expected (%d); got %d' % (self.nel_owned, len(ids)))
+        self._chk(self.lib.plfx_set_element_textures(self.h, _dp(ids)))
+
+    def svc_textures_info(self, mat):
+        """dict(rows, staged, launches) of the texture field on material ``mat`` (plfx_svc_textures_info)"""
+        rows, staged, nl = C.c_int(), C.c_int(), C.c_int64()
+        self._chk(self.lib.plfx_svc_textures_info(self.h, int(mat), C.byref(rows), C.byref(staged), C.byref(nl)))
+        return dict(rows=int(rows.value), staged=bool(staged.value), launches=int(nl.value))
 
     # -- batched point evaluation (host AoS arrays)
     def seq(self, mat, sig):
@@ -502,12 +539,20 @@ class Context(object):
         self._chk(self.lib.plfx_yf_batch(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(out)))
         return out
 
-    def full_yf(self, mat, sig, epl=None, ld=None):
+    def full_yf(self, mat, sig, epl=None, ld=None, tex_id=None):
+        """tex_id: (N,) texture row per point of a material with a texture field (plfx_full_yf_batch_tid)"""
         sig = _f64(sig).reshape(-1, 6)
         epl = np.zeros_like(sig) if epl is None else _f64(epl).reshape(-1, 6)
         ldp = None if ld is None else _f64(ld).reshape(6)
         out = np.empty(len(sig))
         st = np.zeros(len(sig), dtype=np.int32)
+        if tex_id is not None:
+            tid = _i32(tex_id).reshape(-1)
+            if len(tid) != len(sig):
+                raise ValueError('full_yf: one texture row per stress expected')
+            self._chk(self.lib.plfx_full_yf_batch_tid(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(ldp),
+                                                      _dp(out), _dp(st), _dp(tid)))
+            return out, st
         self._chk(self.lib.plfx_full_yf_batch(self.h, int(mat), len(sig), _dp(sig), _dp(epl), _dp(ldp),
                                               _dp(out), _dp(st)))
         return out, st
@@ -663,13 +708,14 @@ class Context(object):
     def set_response_maxit(self, maxit=50):
         self._chk(self.lib.plfx_set_response_maxit(self.h, int(maxit)))
 
-    def response(self, sig, epl, deps, mat_id=None, khard_in=None, return_khard=False, maxit=50):
+    def response(self, sig, epl, deps, mat_id=None, khard_in=None, return_khard=False, maxit=50, tex_id=None):
         """khard_in / return_khard: entry / exit value of Material.khard per point (work-hardening SVC materials);
-        maxit: Material.response's argument (sub-steps of a sub-divided increment)"""
+        maxit: Material.response's argument (sub-steps of a sub-divided increment); tex_id: (N,) texture row per point of
+        the materials with a texture field (plfx_response_batch_tid)"""
         if maxit != 50:
             self.set_response_maxit(maxit)
             try:
-                return self.response(sig, epl, deps, mat_id, khard_in, return_khard)
+                return self.response(sig, epl, deps, mat_id, khard_in, return_khard, tex_id=tex_id)
             finally:
                 self.set_response_maxit(50)
         sig = _f64(sig).reshape(-1, 6)
@@ -689,6 +735,13 @@ class Context(object):
                                                       _dp(fy), _dp(so), _dp(dp), _dp(ct), _dp(ns), _dp(kout)))
             if return_khard:
                 return fy, so, dp, ct, ns, kout
+            return fy, so, dp, ct, ns
+        if tex_id is not None:
+            tid = _i32(tex_id).reshape(-1)
+            if len(tid) != n:
+                raise ValueError('response: one texture row per point expected')
+            self._chk(self.lib.plfx_response_batch_tid(self.h, n, _dp(mid), _dp(sig), _dp(epl), _dp(deps),
+                                                       _dp(fy), _dp(so), _dp(dp), _dp(ct), _dp(ns), _dp(tid)))
             return fy, so, dp, ct, ns
         self._chk(self.lib.plfx_response_batch(self.h, n, _dp(mid), _dp(sig), _dp(epl), _dp(deps),
                                                _dp(fy), _dp(so), _dp(dp), _dp(ct), _dp(ns)))

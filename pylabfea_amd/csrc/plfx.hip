@@ -158,6 +158,16 @@ struct plfx_ctx {
     int64_t tex_yf_launches = 0, tex_ray_launches = 0;
     int64_t tex_fgrad_launches = 0, tex_full_launches = 0, tex_resp_launches = 0;   // the flow-rule calls
     int64_t flow_launches = 0;        // k_flow_curve / k_flow_curve_analytic launches of this context (plfx_flow_info)
+    // texture fields (plfx_set_svc_textures): coefficient rows of material k, a PLFX_SVC6_COLS record; coef and sabs are
+    // owned device memory, ids is filled in per launch.  tex_ids / htex_ids: the row of every owned element (null / empty: row 0),
+    // checked against the attached rows by tex_field_check before a sweep or calc_scf (tex_ids_ok: since the last change of either)
+    TexFieldDev tex_field[MAXMAT] = {};
+    int tex_field_rows[MAXMAT] = {0};
+    int64_t tex_field_launches[MAXMAT] = {0};
+    unsigned tex_field_mask = 0;      // bit k: material k has rows attached (its launches take the TEXF instantiations)
+    int32_t *tex_ids = nullptr;
+    std::vector<int32_t> htex_ids;
+    bool tex_ids_ok = false;
     int svc_lds_need = 0;
     unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
     unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
@@ -978,6 +988,21 @@ void free_mesh(plfx_ctx *c)
     dfree(c->bc_rows);
     c->bc_nrows = 0;
     c->rhs_rows_ok = c->dinv_ok = false;
+    dfree(c->tex_ids);
+    c->htex_ids.clear();
+    c->tex_ids_ok = false;
+}
+
+void free_tex_field(plfx_ctx *c, int k)
+{
+    TexFieldDev &f = c->tex_field[k];
+    if (f.coef) hipFree((void *)f.coef);
+    if (f.sabs) hipFree((void *)f.sabs);
+    f = TexFieldDev();
+    c->tex_field_mask &= ~(1u << k);
+    c->tex_field_rows[k] = 0;
+    c->tex_field_launches[k] = 0;
+    c->tex_ids_ok = false;
 }
 
 void free_svr_flow(plfx_ctx *c, int k)
@@ -993,6 +1018,7 @@ void free_svr_flow(plfx_ctx *c, int k)
 void free_materials(plfx_ctx *c)
 {
     for (int k = 0; k < MAXMAT; k++) free_svr_flow(c, k);   // a rule belongs to the material it was attached to
+    for (int k = 0; k < MAXMAT; k++) free_tex_field(c, k);  // ... and so does a texture field
     for (double *p : c->dsv) hipFree(p);
     c->dsv.clear();
     dfree(c->dmat);
@@ -1931,11 +1957,20 @@ int plfx_sync(plfx_ctx *c)
 }
 
 // launch a row kernel for material k: tables in LDS when they fit, else read from device memory (no dynamic LDS); a
-// PLFX_SVC6_COLS material takes the per-column instantiation
-#define LAUNCH_ROW1(c, k, kern, grid, ...)                                                                                 \
+// PLFX_SVC6_COLS material takes the per-column instantiation, and with a texture field attached the TEXF one, which
+// takes the field with the rows `ids` of the elements / points as its last argument
+#define LAUNCH_ROW1(c, k, ids_, kern, grid, ...)                                                                            \
     do {                                                                                                                 \
         const bool cols_ = ((c)->svc_cols_mask >> (k)) & 1u;                                                             \
-        if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
+        if (((c)->tex_field_mask >> (k)) & 1u) {                                                                         \
+            TexFieldDev tf_ = (c)->tex_field[k];                                                                         \
+            tf_.ids = (ids_);                                                                                            \
+            if (((c)->svc_row_lds >> (k)) & 1u)                                                                          \
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<true, true, true, TexFieldDev>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__, tf_);  \
+            else                                                                                                         \
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<false, true, true, TexFieldDev>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__, tf_);  \
+            (c)->tex_field_launches[k]++;                                                                                \
+        } else if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<true, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);  \
         else if (cols_)                                                                                                  \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<false, true>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);        \
@@ -1944,10 +1979,18 @@ int plfx_sync(plfx_ctx *c)
         else                                                                                                             \
             hipLaunchKernelGGL(kern<false>, grid, dim3(512), 0, (c)->stream, __VA_ARGS__);                               \
     } while (0)
-#define LAUNCH_ROW2(c, k, kern, H, grid, ...)                                                                              \
+#define LAUNCH_ROW2(c, k, ids_, kern, H, grid, ...)                                                                         \
     do {                                                                                                                 \
         const bool cols_ = ((c)->svc_cols_mask >> (k)) & 1u;                                                             \
-        if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
+        if (((c)->tex_field_mask >> (k)) & 1u) {                                                                         \
+            TexFieldDev tf_ = (c)->tex_field[k];                                                                         \
+            tf_.ids = (ids_);                                                                                            \
+            if (((c)->svc_row_lds >> (k)) & 1u)                                                                          \
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true, true, true, TexFieldDev>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__, tf_);  \
+            else                                                                                                         \
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false, true, true, TexFieldDev>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__, tf_);  \
+            (c)->tex_field_launches[k]++;                                                                                \
+        } else if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);   \
         else if (cols_)                                                                                                  \
             hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false, true>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);     \
@@ -2179,6 +2222,12 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
             HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true>, c->svc_wave_lds));
             HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true>, c->svc_wave_lds));
             HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true, true>, c->svc_wave_lds));
+            // (a texture field can be attached to any of them)
+            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<0, true, true, true, TexFieldDev>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<1, true, true, true, TexFieldDev>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
         }
     }
     if (c->has_svc || c->has_svc3 || c->has_svcwh) {  // opt in to > 64 KiB dynamic LDS for the SVC kernels
@@ -2241,6 +2290,105 @@ static int cols_refuse(plfx_ctx *c, int mat, const char *what)
     return PLFX_OK;
 }
 
+// A texture field on a PLFX_SVC6_COLS material: one row of dual coefficients per texture, padded like the row tables
+int plfx_set_svc_textures(plfx_ctx *c, int mat, int ntex, const double *coef)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
+    if (mat < 0 || mat >= c->nmat || ntex < 0 || (ntex > 0 && !coef)) return fail(c, PLFX_ERR_ARG, "plfx_set_svc_textures: bad argument");
+    if (c->hmat[mat].kind != PLFX_SVC6_COLS)
+        return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_set_svc_textures: material %d is of kind %d; a texture field belongs to a "
+                    "PLFX_SVC6_COLS material only", mat, c->hmat[mat].kind);
+    const int nsv = c->hmat[mat].nsv, rp = c->hmat[mat].rowpad;
+    if ((long long)ntex * rp > (long long)INT32_MAX)
+        return fail(c, PLFX_ERR_ARG, "plfx_set_svc_textures: %d rows of %d coefficients are more than INT32_MAX", ntex, rp);
+    for (size_t i = 0; i < (size_t)ntex * nsv; i++)
+        if (!std::isfinite(coef[i]))
+            return fail(c, PLFX_ERR_ARG, "plfx_set_svc_textures: coefficient %zu of row %zu is not finite", i % nsv, i / nsv);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, stream_sync(c));   // no launch may still read the rows that go away
+    free_tex_field(c, mat);
+    if (ntex == 0) return PLFX_OK;
+    std::vector<double> T((size_t)ntex * rp, 0.), S((size_t)ntex, 0.);
+    for (int t = 0; t < ntex; t++)
+        for (int i = 0; i < nsv; i++) {
+            T[(size_t)t * rp + i] = coef[(size_t)t * nsv + i];
+            S[t] += std::fabs(coef[(size_t)t * nsv + i]);
+        }
+    double *dT = nullptr, *dS = nullptr;
+    HIPCHK(c, hipMalloc((void **)&dT, T.size() * 8));
+    c->tex_field[mat].coef = dT;   // (owned from here on: freed by free_tex_field whatever follows)
+    HIPCHK(c, hipMalloc((void **)&dS, S.size() * 8));
+    c->tex_field[mat].sabs = dS;
+    HIPCHK(c, hipMemcpy(dT, T.data(), T.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dS, S.data(), S.size() * 8, hipMemcpyHostToDevice));
+    c->tex_field[mat].stride = rp;
+    c->tex_field_rows[mat] = ntex;
+    c->tex_field_mask |= 1u << mat;
+    return PLFX_OK;
+}
+
+int plfx_set_element_textures(plfx_ctx *c, const int32_t *tex_id)
+{
+    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, stream_sync(c));
+    c->tex_ids_ok = false;
+    if (!tex_id) {
+        dfree(c->tex_ids);
+        c->htex_ids.clear();
+        return PLFX_OK;
+    }
+    if (!c->tex_ids)
+        if (int rc = dalloc(c, &c->tex_ids, (size_t)c->nel)) return rc;
+    c->htex_ids.assign(tex_id, tex_id + c->nel);
+    HIPCHK(c, hipMemcpy(c->tex_ids, tex_id, (size_t)c->nel * 4, hipMemcpyHostToDevice));
+    return PLFX_OK;
+}
+
+int plfx_svc_textures_info(plfx_ctx *c, int mat, int *rows, int *staged, int64_t *launches)
+{
+    if (!c || mat < 0 || mat >= MAXMAT) return c ? fail(c, PLFX_ERR_ARG, "material %d out of range", mat) : PLFX_ERR_ARG;
+    if (rows) *rows = c->tex_field_rows[mat];
+    if (staged) *staged = 0;   // the rows are read from device memory
+    if (launches) *launches = c->tex_field_launches[mat];
+    return PLFX_OK;
+}
+
+// Before a sweep or calc_scf of a model with a texture field: every element of a field material has a row that exists.  Nothing
+// is launched on an index out of range.
+static int tex_field_check(plfx_ctx *c)
+{
+    if (!c->tex_field_mask) return PLFX_OK;
+    if (c->strip.on || c->sharded || comm_active(c))
+        return fail(c, PLFX_ERR_UNSUPPORTED, "a texture field runs on one GPU without strips or shards");
+    if (c->tex_ids_ok || !c->tex_ids) return PLFX_OK;   // (no array: row 0, and an attached field has at least one row)
+    for (int e = 0; e < c->nel; e++) {
+        const int k = c->hcls[c->hcls_id[(size_t)c->e0 + e]].mat;
+        if (!((c->tex_field_mask >> k) & 1u)) continue;
+        const int32_t t = c->htex_ids[e];
+        if (t < 0 || t >= c->tex_field_rows[k])
+            return fail(c, PLFX_ERR_ARG, "texture row %d of element %d is outside the %d rows of material %d", (int)t, e,
+                        c->tex_field_rows[k], k);
+    }
+    c->tex_ids_ok = true;
+    return PLFX_OK;
+}
+
+// the rows of the points of a _tid call: checked on the host for the materials that carry a field
+static int tex_point_check(plfx_ctx *c, int n, int mat, const int32_t *mat_id, const int32_t *tex_id)
+{
+    if (!tex_id || !c->tex_field_mask) return PLFX_OK;
+    for (int i = 0; i < n; i++) {
+        const int k = mat >= 0 ? mat : (mat_id ? mat_id[i] : 0);
+        if (k < 0 || k >= c->nmat || !((c->tex_field_mask >> k) & 1u)) continue;
+        if (tex_id[i] < 0 || tex_id[i] >= c->tex_field_rows[k])
+            return fail(c, PLFX_ERR_ARG, "tex_id[%d] = %d is outside the %d rows of material %d", i, (int)tex_id[i],
+                        c->tex_field_rows[k], k);
+    }
+    return PLFX_OK;
+}
+
 // ------------------------------------------------------------------------------ batched point evaluation
 // the opening check of a point function of one material; args_ok: what the function asks of its other arguments
 static int point_check(plfx_ctx *c, int mat, bool args_ok)
@@ -2283,9 +2431,10 @@ static void tex_for_nfp(int nfp, F &&f)
 }
 
 static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, const double *epl,
-                      const double *ld, double *out, int32_t *status)
+                      const double *ld, double *out, int32_t *status, const int32_t *tex_id = nullptr)
 {
     if (int rc = point_check(c, mat, n >= 0 && sig && out)) return rc;
+    if (int rc = tex_point_check(c, n, mat, nullptr, tex_id)) return rc;
     const bool cols = (c->hmat[mat].kind == PLFX_SVC6_COLS);
     if (cols && what != 3) return cols_refuse(c, mat, what == 0 ? "calc_seq" : what == 1 ? "calc_fgrad" : "calc_yf");
     if (n == 0) return PLFX_OK;
@@ -2301,11 +2450,14 @@ static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, 
         if (int rc = B.put(c, &dld, ld, 6)) return rc;
     if (status)
         if (int rc = B.get(c, &dst, N)) return rc;
+    int32_t *d_tid = nullptr;
+    if (tex_id && ((c->tex_field_mask >> mat) & 1u))
+        if (int rc = B.put(c, &d_tid, tex_id, N)) return rc;
     static const bool wave_full = !(getenv("PLFX_FULL_YF_WAVE") && atoi(getenv("PLFX_FULL_YF_WAVE")) == 0);
     EvPair *ev;
     tim_begin(c, 0, &ev);   // family 0 like plfx_response_batch: the kernel alone, without the copies
     if (what == 3 && (wave_full || cols) && ((c->svc_row_all >> mat) & 1u))  // ML_full_yf of a row-kernel SVC material
-        LAUNCH_ROW1(c, mat, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
+        LAUNCH_ROW1(c, mat, (const int32_t *)d_tid, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
                    c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
     else
         hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
@@ -2357,10 +2509,16 @@ int plfx_full_yf_batch(plfx_ctx *c, int mat, int n, const double *sig, const dou
 {
     return point_eval(c, 3, mat, n, sig, epl, ld, yf, status);
 }
+int plfx_full_yf_batch_tid(plfx_ctx *c, int mat, int n, const double *sig, const double *epl,
+                           const double *ld, double *yf, int32_t *status, const int32_t *tex_id)
+{
+    return point_eval(c, 3, mat, n, sig, epl, ld, yf, status, tex_id);
+}
 
 static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig,
                                const double *epl, const double *deps, double *fy, double *sig_out,
-                               double *depl, double *ct, int32_t *nsteps, const double *kh_in, double *kh_out)
+                               double *depl, double *ct, int32_t *nsteps, const double *kh_in, double *kh_out,
+                               const int32_t *tex_id = nullptr)
 {
     if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
     if (n < 0 || !sig || !epl || !deps || !fy || !sig_out || !depl || !ct || !nsteps)
@@ -2370,10 +2528,13 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
     if (mat_id)
         for (int i = 0; i < n; i++)
             if (mat_id[i] < 0 || mat_id[i] >= c->nmat) return fail(c, PLFX_ERR_ARG, "mat_id[%d] out of range", i);
+    if (int rc = tex_point_check(c, n, -1, mat_id, tex_id)) return rc;
     CallBuffers B;
     double *d_in = nullptr, *d_out = nullptr;
-    int32_t *d_mid = nullptr, *d_ns = nullptr;
+    int32_t *d_mid = nullptr, *d_ns = nullptr, *d_tid = nullptr;
     const size_t N = n;
+    if (tex_id && c->tex_field_mask)
+        if (int rc = B.put(c, &d_tid, tex_id, N)) return rc;
     if (int rc = B.get(c, &d_in, N * 18)) return rc;
     if (int rc = B.get(c, &d_out, N * (1 + 6 + 6 + 36))) return rc;
     if (int rc = B.get(c, &d_ns, N)) return rc;
@@ -2409,7 +2570,7 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
                            c->stream, RB_ARGS(c->svc_lds_need), (const double *)nullptr, (double *)nullptr, rmask, c->resp_maxit);
     for (int k = 0; k < c->nmat; k++)   // 6-feature SVC materials with tables in LDS: 16 lanes per point (the code path of the sweeps)
         if ((rmask >> k) & 1u)
-            LAUNCH_ROW1(c, k, k_response_row, dim3(std::max(1, std::min((n + 31) / 32, 1024))),
+            LAUNCH_ROW1(c, k, (const int32_t *)d_tid, k_response_row, dim3(std::max(1, std::min((n + 31) / 32, 1024))),
                        c->dmat, c->nmat, k, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so, d_dp, d_ct, d_ns, c->resp_maxit);
     if (c->has_svc3)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<6>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
@@ -2448,6 +2609,13 @@ int plfx_response_batch(plfx_ctx *c, int n, const int32_t *mat_id, const double 
                         double *depl, double *ct, int32_t *nsteps)
 {
     return response_batch_impl(c, n, mat_id, sig, epl, deps, fy, sig_out, depl, ct, nsteps, nullptr, nullptr);
+}
+
+int plfx_response_batch_tid(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig,
+                            const double *epl, const double *deps, double *fy, double *sig_out,
+                            double *depl, double *ct, int32_t *nsteps, const int32_t *tex_id)
+{
+    return response_batch_impl(c, n, mat_id, sig, epl, deps, fy, sig_out, depl, ct, nsteps, nullptr, nullptr, tex_id);
 }
 
 int plfx_response_batch_kh(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig, const double *epl,
@@ -5839,6 +6007,7 @@ int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double
 // ------------------------------------------------------------------------------ non-linear driver pieces
 static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq)
 {
+    if (int rct = tex_field_check(c)) return rct;
     // (flags / bflags are left zeroed by the k_sweep_flags of the previous sweep)
     // every plastic element's res_sig is written below: the buffer is a field of its own again, whatever it held
     c->res_is_sig = false;
@@ -5890,7 +6059,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     if (fast) {
         for (int k = 0; k < c->nmat; k++)   // one launch per material: its tables fill the LDS
             if ((fast >> k) & 1u) {
-                LAUNCH_ROW2(c, k, k_sweep_svc_row, 0, dim3(grid_r), ROW_ARGS, first, k);
+                LAUNCH_ROW2(c, k, (const int32_t *)c->tex_ids, k_sweep_svc_row, 0, dim3(grid_r), ROW_ARGS, first, k);
                 first = 0;
                 c->n_svc_row_launches++;
             }
@@ -5938,7 +6107,7 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                                c->stream, SWEEP_ARGS(c->svc_lds_need), fast);
         if (fast)
             for (int k = 0; k < c->nmat; k++)
-                if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
+                if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, (const int32_t *)c->tex_ids, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
         if (c->has_svc3)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
                                c->stream, SWEEP_ARGS(c->svc_lds_need), 0u);
@@ -6195,7 +6364,7 @@ static void launch_scf_elements(plfx_ctx *c)
                        c->small + 32, c->scf_hh, c->scf_mult, scf_moduli(c), fast);
     for (int k = 0; k < c->nmat; k++)
         if ((fast >> k) & 1u)
-            LAUNCH_ROW1(c, k, k_scf_row, dim3(std::max(1, std::min((c->nel + 31) / 32, 1024))),
+            LAUNCH_ROW1(c, k, (const int32_t *)c->tex_ids, k_scf_row, dim3(std::max(1, std::min((c->nel + 31) / 32, 1024))),
                        c->dmat, c->nmat, c->dcls, k, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
                        c->sig, c->epl, tan_store(c), c->small + 32, c->scf_hh, c->scf_mult);
 }
@@ -6207,6 +6376,7 @@ int plfx_scf_stats(plfx_ctx *c, const double *sld, double *sum, double *sumsq_c,
     const int g = grid_for(c->nel, 256);
     if (pass == 0) {
         if (!sld) return fail(c, PLFX_ERR_ARG, "sld required");
+        if (int rct = tex_field_check(c)) return rct;
         HIPCHK(c, hipMemcpyAsync(c->small + 32, sld, 48, hipMemcpyHostToDevice, c->stream));
         launch_scf_elements(c);
         HIPCHK(c, hipGetLastError());
@@ -6237,6 +6407,7 @@ int plfx_scf_all(plfx_ctx *c, const double *sld, int64_t *count, double *minv, d
 {
     if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
     if (!sld) return fail(c, PLFX_ERR_ARG, "sld required");
+    if (int rct = tex_field_check(c)) return rct;
     const int g = grid_for(c->nel, 256);
     HIPCHK(c, hipMemcpyAsync(c->small + 32, sld, 48, hipMemcpyHostToDevice, c->stream));
     launch_scf_elements(c);

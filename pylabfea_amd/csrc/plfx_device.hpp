@@ -1118,14 +1118,40 @@ struct YfSvcWhT {
 // COLS (PLFX_SVC6_COLS): one scale per stress column, x_j = s_j / scale_j, and the gradient of a dev_only set
 // projected onto the deviator.  Only features() and the closing of fgrad_impl differ; along a ray x = t D with
 // D_j = su_j / scale_j every term is still a Gaussian in t, so the sampled ray, the march and the brentq replay are shared.
-template <int NC, bool INLDS = true, bool COLS = false>
-struct YfSvcRow {
+// TEXF (texture field): the dual coefficients and their sum of moduli are those of the point's texture row,
+// read from device memory (crow: rowpad doubles, zero behind nsv; the 16 lanes of a row read 128 consecutive bytes).  The
+// coefficient is read in load7 and in the loop of ray_sample, the sum in ray_sample's bound and margin; nothing else differs.
+struct TexFieldDev {
+    const double *coef;    // [ntex][stride] coefficient rows
+    const double *sabs;    // [ntex] sum |coef| of a row, in index order
+    const int32_t *ids;    // row of every element / point, or null: row 0
+    int stride;            // = MatDev::rowpad of the material
+};
+template <bool TEXF>
+struct SvcTexRow {};
+template <>
+struct SvcTexRow<true> {
+    const double *crow;
+    double csabs;
+};
+template <int NC, bool INLDS = true, bool COLS = false, bool TEXF = false>
+struct YfSvcRow : SvcTexRow<TEXF> {
     static constexpr int GS = 16, NS = RAYPOLY_N;
     static constexpr bool FUSED = true;   // fgrad_plain(): gradient at one point and decision function at another in one pass
     static_assert(NS == GS, "lane i of a row holds Chebyshev coefficient i");
     const MatDev &m;
     int npad;
-    __device__ YfSvcRow(const MatDev &mm, int np) : m(mm), npad(np) {}
+    __device__ YfSvcRow(const MatDev &mm, int np) : m(mm), npad(np) { static_assert(!TEXF, "a texture field needs its row"); }
+    __device__ YfSvcRow(const MatDev &mm, int np, const TexFieldDev &tf, int t) : m(mm), npad(np)
+    {
+        this->crow = tf.coef + (size_t)t * tf.stride;
+        this->csabs = tf.sabs[t];
+    }
+    __device__ __forceinline__ double sabs() const
+    {
+        if constexpr (TEXF) return this->csabs;
+        else return m.svc_sabs;
+    }
     // the tables: dynamic LDS (staged by stage_svc_row), or the material's copy in device memory (INLDS = false: more support
     // vectors than the LDS holds; the 16 lanes of a row read 128 consecutive bytes, the four rows of a wave the same ones)
     __device__ __forceinline__ const double *tabs() const { return INLDS ? dyn_lds : m.rowtab; }
@@ -1170,6 +1196,10 @@ struct YfSvcRow {
         for (int i = 0; i < 7; i++)
 #pragma unroll
             for (int c = 0; c < NC; c++) v[c][i] = T[i * npad + k + GS * c];
+        if constexpr (TEXF) {   // the coefficient of the point's texture row in place of slot 6 of the tables
+#pragma unroll
+            for (int c = 0; c < NC; c++) v[c][6] = this->crow[k + GS * c];
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int c = 0; c < NC; c++)
@@ -1348,7 +1378,7 @@ struct YfSvcRow {
         static_assert(NS == 16, "KN and the 16th power below are written for 16 samples");
         double b = q * dl;
         b *= b; b *= b; b *= b; b *= b;
-        double bound = m.svc_sabs * KN * b;
+        double bound = sabs() * KN * b;
         if (!(bound <= RAY_BOUND)) {
             if (!(bound < 1.e300)) return;
             const double sh = sqrt(sqrt(sqrt(sqrt(RAY_BOUND / bound))));   // (RAY_BOUND / bound)^(1/16)
@@ -1372,6 +1402,10 @@ struct YfSvcRow {
             for (int i = 0; i < 8; i++)
 #pragma unroll
                 for (int c = 0; c < NC; c++) v[c][i] = T[i * npad + k + GS * c];
+            if constexpr (TEXF) {
+#pragma unroll
+                for (int c = 0; c < NC; c++) v[c][6] = this->crow[k + GS * c];
+            }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int c = 0; c < NC; c++)
@@ -1419,7 +1453,7 @@ struct YfSvcRow {
         P.hi = hi;
         P.ua = 2. / (hi - lo);
         P.ub = -(hi + lo) / (hi - lo);
-        P.margin = bound + 4.e-12 * m.svc_sabs;
+        P.margin = bound + 4.e-12 * sabs();
         P.ok = true;
     }
     // f(x su): the polynomial where it decides (phase < 3: and is farther from zero than its error bound), the support-vector

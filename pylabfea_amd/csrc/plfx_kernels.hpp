@@ -1458,17 +1458,34 @@ __device__ __forceinline__ int stage_svc_row(const MatDev *smat, int mat)
 }
 constexpr int SVC_WAVE_EXTRA = RAYPOLY_N * RAYPOLY_N + 128;   // doubles behind the 9 npad of the support-vector tables
 
+// The policy of a row kernel for element / point i.  A kernel of a texture field (TEXF) carries one more
+// argument, the field; the other instantiations carry none (an empty pack: their argument lists are what they were).
+template <int NC, bool INLDS, bool COLS>
+__device__ __forceinline__ YfSvcRow<NC, INLDS, COLS> row_policy(const MatDev &m, int npad, int)
+{
+    return YfSvcRow<NC, INLDS, COLS>(m, npad);
+}
+template <int NC, bool INLDS, bool COLS>
+__device__ __forceinline__ YfSvcRow<NC, INLDS, COLS, true> row_policy(const MatDev &m, int npad, int i, const TexFieldDev &tf)
+{
+    return YfSvcRow<NC, INLDS, COLS, true>(m, npad, tf, tf.ids ? tf.ids[i] : 0);
+}
+
 
 // Row-per-element variants (round 5; YfSvcRow) for one 6-feature SVC material: 16 lanes = one DPP row per element, four
 // elements per wave, the ray search in its sampled form.  The two sweep phases of k_sweep_svc_row share the 50-sub-step list
 // and the flags with the thread-per-element kernels (flags[2]); lane 0 of a row stores.
 // COLS: the instantiations for a PLFX_SVC6_COLS material (one scale per stress column, YfSvcRow<.., true>); the tables, their
 // staging and every launch argument are those of the 6-feature material.
-template <bool INLDS, bool COLS = false>
+// TEXF: the instantiations for such a material with a texture field attached (plfx_set_svc_textures): one
+// more launch argument, the field (TF = TexFieldDev), whose row ids[e] / ids[i] gives the element's / point's coefficients.
+template <bool INLDS, bool COLS = false, bool TEXF = false, class... TF>
 __global__ void __launch_bounds__(512)
 k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const double *__restrict__ sig_in,
-              const double *__restrict__ epl_in, const double *__restrict__ ld, double *__restrict__ out, int32_t *__restrict__ status)
+              const double *__restrict__ epl_in, const double *__restrict__ ld, double *__restrict__ out, int32_t *__restrict__ status,
+              TF... tf)
 {
+    static_assert(sizeof...(TF) == (TEXF ? 1 : 0), "a texture-field instantiation takes the field, the others nothing");
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
@@ -1488,7 +1505,7 @@ k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const d
             s[c] = sig_in[6 * (size_t)i + c];
             e[c] = epl_in ? epl_in[6 * (size_t)i + c] : 0.;
         }
-        const YfSvcRow<4, INLDS, COLS> yf(m, npad);
+        const auto yf = row_policy<4, INLDS, COLS>(m, npad, i, tf...);
         int st = 0;
         const double f = yf.full_ld(s, e, ld ? ldv : nullptr, &st);
         if (l16 == 0) {
@@ -1500,13 +1517,14 @@ k_full_yf_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const d
 
 // Material.response on n points of the row-kernel SVC material `mat` (host-layout arrays as in k_response_batch; points of
 // other materials are left to k_response_batch<3>): the same code path as the sweeps of a model, callable point by point
-template <bool INLDS, bool COLS = false>
+template <bool INLDS, bool COLS = false, bool TEXF = false, class... TF>
 __global__ void __launch_bounds__(512)
 k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const int32_t *__restrict__ mat_id,
                const double *__restrict__ sig_in, const double *__restrict__ epl_in, const double *__restrict__ deps_in,
                double *__restrict__ fy, double *__restrict__ sig_out, double *__restrict__ depl_out, double *__restrict__ ct_out,
-               int32_t *__restrict__ nsteps, int maxit = MAXIT)
+               int32_t *__restrict__ nsteps, int maxit, TF... tf)
 {
+    static_assert(sizeof...(TF) == (TEXF ? 1 : 0), "a texture-field instantiation takes the field, the others nothing");
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
@@ -1523,7 +1541,7 @@ k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const 
             epl[c] = epl_in[6 * (size_t)i + c];
             deps[c] = deps_in[6 * (size_t)i + c];
         }
-        const YfSvcRow<4, INLDS, COLS> yf(m, npad);
+        const auto yf = row_policy<4, INLDS, COLS>(m, npad, i, tf...);
         const int ns = response_point(m, yf, sig, epl, deps, f, depl, Ct, maxit);
         if (l16 == 0) {
             fy[i] = f;
@@ -1541,14 +1559,15 @@ k_response_row(const MatDev *__restrict__ gmat, int nmat, int mat, int n, const 
     }
 }
 
-template <int HEAVY, bool INLDS, bool COLS = false>
+template <int HEAVY, bool INLDS, bool COLS = false, bool TEXF = false, class... TF>
 __global__ void __launch_bounds__(512)
 k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
                 int nel, int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls,
                 const double2 *__restrict__ du2, const double *__restrict__ sig, const double *__restrict__ epl,
                 TanStore ts, double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
-                int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, int wave_mat)
+                int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, int wave_mat, TF... tf)
 {
+    static_assert(sizeof...(TF) == (TEXF ? 1 : 0), "a texture-field instantiation takes the field, the others nothing");
     const int count = HEAVY ? flags[2] : nel;
     if (count == 0) return;
     __shared__ SweepTables tb;
@@ -1578,7 +1597,7 @@ k_sweep_svc_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
             s[k] = sig[(size_t)k * nel + e];
             ep[k] = epl[(size_t)k * nel + e];
         }
-        const YfSvcRow<NC, INLDS, COLS> yf(m, npad);
+        const auto yf = row_policy<NC, INLDS, COLS>(m, npad, e, tf...);
         const int st = response_light<true>(m, yf, s, ep, deps, fy, depl, Ct, dr, st_scal);
         if (HEAVY) {
             response_heavy(m, yf, s, ep, dr, st_scal, fy, depl, Ct);
@@ -3594,13 +3613,14 @@ k_scf_elements(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
 // calc_scf for the elements of the 6-feature SVC material `mat`, 16 lanes per element (YfSvcRow; ML_full_yf along the
 // loading direction is a ray search, model.py:1049-1052) -- the thread-per-element form above took 4.5 ms per call on
 // 16 384 elements, a quarter of a 50-sub-step corrector launch
-template <bool INLDS, bool COLS = false>
+template <bool INLDS, bool COLS = false, bool TEXF = false, class... TF>
 __global__ void __launch_bounds__(512)
 k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int mat, int nel,
           int e_off, const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
           const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts, const double *__restrict__ sld,
-          double *__restrict__ hh_out, int32_t *__restrict__ mult_out)
+          double *__restrict__ hh_out, int32_t *__restrict__ mult_out, TF... tf)
 {
+    static_assert(sizeof...(TF) == (TEXF ? 1 : 0), "a texture-field instantiation takes the field, the others nothing");
     __shared__ MatDev smat[MAXMAT];
     stage_materials(smat, gmat, nmat);
     __syncthreads();
@@ -3629,7 +3649,7 @@ k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict_
                 s[k] = sig[(size_t)k * nel + e];
                 ep[k] = epl[(size_t)k * nel + e];
             }
-            const YfSvcRow<4, INLDS, COLS> yf(m, npad);
+            const auto yf = row_policy<4, INLDS, COLS>(m, npad, e, tf...);
             double yf0 = yf.plain(s, ep);
             if (yf0 < SPLIT_THRESHOLD) {  // branch test on the decision function (model.py:1046-1048)
                 yf0 = yf.full_ld(s, ep, ld, nullptr);  // model.py:1049-1052

@@ -13,7 +13,8 @@ Texture materials (``from_data`` on data sets with ``tx_data``) are trained and 
 ``train_SVC``, ``calc_yf``, ``find_yloc``, ``yield_scale``, ``texture_loci`` -- and, like in the reference, nothing past that
 unless the caller passes ``tex=``: ``calc_fgrad``, ``ML_full_yf``, ``response``, ``response_batch``, ``epl_dot`` and ``C_tan``
 then run at that texture (an extension).  ``at_texture(tex)`` binds a trained texture material to one texture:
-the bound material is what ``Model.assign`` takes, one texture per section.
+the bound material is what ``Model.assign`` takes, one texture per section; ``at_textures(tex)`` binds it to a
+field of textures, one per element (``Model.set_texture_ids``) or per point (``tex_id=``), as one material.
 A trained SVC enters through
 :meth:`Material.train_SVC` (trained on the GPU), :meth:`Material.set_svc` or :meth:`Material.from_sklearn`.
 sdim=3 flow rules use the reference's axis-tracking principal stresses (exact for plane states);
@@ -381,7 +382,8 @@ class Material(object):
             return _lib.pack_material(_lib.ELASTIC, CV, E=self.E, nu=self.nu)
         if self.ML_yf and not ana and getattr(self, '_bound', None) is not None:
             svc = dict(sv=self.svc['sv'], dual=self.svc['dual'], intercept=self.svc['intercept'], gamma=self.gam_yf,
-                       scale_seq=self.scale_seq, dev_only=self.dev_only, scale_cols=self._bound['scale'])
+                       scale_seq=self.scale_seq, dev_only=self.dev_only, scale_cols=self._bound['scale'],
+                       coef=self._bound.get('coef'))
             return _lib.pack_material(_lib.SVC6_COLS, CV, E=self.E, nu=self.nu, sy=self.sy, khard=self.khard,
                                       hill=self.hill, drucker=self.drucker, svc=svc)
         if self.ML_yf and not ana:
@@ -565,6 +567,55 @@ class Material(object):
         b._bound = dict(parent=self, tex=np.array(tex, dtype=float), scale=f['scale'])
         return b
 
+    # ------------------------------------------------------------------ a texture field: one texture per element
+    def fold_textures(self, tex):
+        """``fold_texture`` for T textures, ``tex`` (T, tdim) with T >= 1: the dict of ``fold_texture`` with ``dual`` of shape
+        (T, nsv).  Only the dual coefficients depend on the texture; vectors, scales, gamma and intercept are shared.  Row t
+        is ``fold_texture(tex[t])['dual']`` bit for bit: the rows are folded one by one, in the summation order of the
+        single fold."""
+        if not getattr(self, 'txdat', False):
+            raise NotImplementedError('fold_textures: tex needs a texture material (from_data on data sets with tx_data)')
+        if not self._is_tex():
+            self._svc_refuse('fold_textures')
+        if not self.ML_yf or self.svc is None or getattr(self, 'std_scaler', None) is None:
+            raise AttributeError('texture material has no trained ML yield function; train_SVC trains it')
+        t = np.asarray(tex, dtype=float)
+        if t.ndim != 2 or t.shape[1] != self.tdim or len(t) < 1 or not np.all(np.isfinite(t)):
+            raise ValueError('fold_textures: tex must be a finite (T, %d) array with T >= 1; got shape %s'
+                             % (self.tdim, np.shape(tex)))
+        f = self.fold_texture(t[0])
+        f['dual'] = np.ascontiguousarray(np.stack([f['dual']] + [self.fold_texture(r)['dual'] for r in t[1:]]))
+        return f
+
+    def at_textures(self, tex, name=None):
+        """A new Material: this trained texture material with a FIELD of textures ``tex`` (T, tdim), one row per element of a
+        model (``Model.set_texture_ids``) or per point (``tex_id=`` of ``response``, ``response_batch``, ``ML_full_yf``).  An
+        element with row t behaves as ``at_texture(tex[t])`` does, in every output.  It is a bound material
+        whose ``svc['dual']`` is row 0; ``_bound`` holds the textures and the coefficient rows ``coef`` (T, nsv) besides.
+        One engine material and one launch per sweep phase, whatever T is."""
+        f = self.fold_textures(tex)
+        b = self.at_texture(np.asarray(tex, dtype=float)[0], name=name if name is not None else '%s@textures' % self.name)
+        b._bound['tex'] = np.array(tex, dtype=float)
+        b._bound['coef'] = f['dual']
+        return b
+
+    def _tex_ids(self, tex_id, n, what):
+        """``tex_id`` of a point function: None for a material without a texture field (which takes none), else the rows of
+        the n points as an (n,) int32 array (an int is shared by the points; default row 0)"""
+        b = getattr(self, '_bound', None)
+        if b is None or 'coef' not in b:
+            if tex_id is not None:
+                raise NotImplementedError('%s: tex_id needs a material with a texture field (at_textures)' % what)
+            return None
+        T = len(b['coef'])
+        ids = np.asarray(0 if tex_id is None else tex_id)
+        if ids.dtype.kind not in 'iu' or ids.ndim > 1 or (ids.ndim == 1 and len(ids) != n):
+            raise ValueError('%s: tex_id must be an int or an (N,) int array with one row index per point; got dtype %s, '
+                             'shape %s' % (what, ids.dtype, ids.shape))
+        if ids.size and (ids.min() < 0 or ids.max() >= T):
+            raise ValueError('%s: tex_id outside 0..%d' % (what, T - 1))
+        return np.ascontiguousarray(np.broadcast_to(ids, (n,)), dtype=np.int32)
+
     # what to do instead where a bound material refuses
     _BOUND_REFUSALS = {
         'calc_hessian': 'no Hessian of the texture SVC is built',
@@ -578,19 +629,38 @@ class Material(object):
         'create_scaled_input': "fold_texture of the parent states the features, x_j = s_j / scale_j",
         'Model.distribute': 'a bound material runs on one GPU',
     }
+    # ... and where a texture field refuses what a material bound to one texture offers
+    _FIELD_REFUSALS = {
+        'calc_properties': 'bind one texture with at_texture',
+    }
+
 
     def _bound_refuse(self, what):
         """the one gate of a material bound to a texture (at_texture): the row kernels run it and nothing else does"""
-        if getattr(self, '_bound', None) is not None:
-            raise NotImplementedError('%s: not offered for a material bound to a texture (at_texture); %s'
-                                      % (what, self._BOUND_REFUSALS.get(what, 'use the parent material')))
+        b = getattr(self, '_bound', None)
+        if b is None:
+            return
+        if what in self._FIELD_REFUSALS:   # offered for one texture, refused for a field of them (at_textures)
+            if 'coef' in b:
+                raise NotImplementedError('%s: not offered for a texture field (at_textures); %s' % (what, self._FIELD_REFUSALS[what]))
+            return
+        raise NotImplementedError('%s: not offered for a material bound to a texture (at_texture); %s'
+                                  % (what, self._BOUND_REFUSALS.get(what, 'use the parent material')))
 
-    def _bound_call(self, fn, *a, **kw):
-        """a ``tex=`` call of the parent at the bound texture; the parent's khard, which its calc_fgrad(tex=) resets, is put back"""
+    def _bound_call(self, fn, *a, tex_id=None, **kw):
+        """a ``tex=`` call of the parent at the bound texture (a texture field: at the rows ``tex_id``, an int or one per
+        point); the parent's khard, which its calc_fgrad(tex=) resets, is put back"""
         par = self._bound['parent']
+        tex = self._bound['tex']
+        if 'coef' in self._bound:
+            n = len(a[0]) if np.ndim(a[0]) == 2 else 1
+            ids = self._tex_ids(tex_id, n, fn)
+            tex = tex[ids[0]] if np.ndim(0 if tex_id is None else tex_id) == 0 else tex[ids]
+        elif tex_id is not None:
+            self._tex_ids(tex_id, 1, fn)
         kh = par.khard
         try:
-            return getattr(par, fn)(*a, tex=self._bound['tex'], **kw)
+            return getattr(par, fn)(*a, tex=tex, **kw)
         finally:
             par.khard = kh
 
@@ -817,16 +887,17 @@ class Material(object):
         peeq = epl if type(epl) in (float, np.float64) else eps_eq(epl)
         return self.sy + peeq * self.khard
 
-    def calc_yf(self, sig, epl=None, ana=False, pred=False, tex=None, **kw):
+    def calc_yf(self, sig, epl=None, ana=False, pred=False, tex=None, tex_id=None, **kw):
         """Yield function: analytic ``calc_seq - sflow`` or the SVC decision function (material.py:348-412).  A texture
         material takes ``tex``, one descriptor (tdim,) or one per stress (N, tdim), and raises the reference's ValueError
         without it."""
         if getattr(self, '_bound', None) is not None and not ana:   # (no plastic strain enters the texture features)
             if tex is not None:
                 raise ValueError('calc_yf: the material is bound to a texture (at_texture) and takes no tex')
-            f = self._bound_call('calc_yf', sig, pred=pred)
+            f = self._bound_call('calc_yf', np.asarray(sig, dtype=float), pred=pred, tex_id=tex_id)
             self.msg['yield_fct'] = self._bound['parent'].msg['yield_fct']
             return f
+        self._tex_ids(tex_id, 1, 'calc_yf')
         s, single = self._voigt(sig, 'calc_yf')
         if self.ML_yf and not ana and getattr(self, 'txdat', False):
             if tex is None:
@@ -879,13 +950,17 @@ class Material(object):
             raise ValueError("SVM is trained on texture data but no texture data was provided to this function.")
         return self.calc_yf(float(x) * np.asarray(su, dtype=float), epl=epl, tex=tex)
 
-    def ML_full_yf(self, sig, epl=None, ld=None, verb=True, tex=None, **kw):
+    def ML_full_yf(self, sig, epl=None, ld=None, verb=True, tex=None, tex_id=None, **kw):
         """Distance of a stress to the ML yield locus along its ray / the loading direction
         (material.py:414-516).  Accepts a single stress like the reference, or (N,6).  EXTENSION: a texture material takes
         ``tex``, (tdim,) or (N, tdim): the same search on calc_yf(x su, tex) with seq the J2 / Hill form of the material and
-        the flow stress sy + khard peeq; ``ld`` is not offered together with ``tex``."""
+        the flow stress sy + khard peeq; ``ld`` is not offered together with ``tex``.  A texture field
+        (``at_textures``) takes ``tex_id``, an int or (N,) ints, the row of its texture table per stress."""
         if tex is not None:
+            self._tex_ids(tex_id, 1, 'ML_full_yf')
             return self._full_yf_tex(sig, epl, ld, verb, tex)
+        if getattr(self, '_bound', None) is None:
+            self._tex_ids(tex_id, 1, 'ML_full_yf')   # (refused: no texture field)
         self._tex_refuse('ML_full_yf')
         if not self.ML_yf:
             raise AttributeError('ML_full_yf: material has no trained ML yield function')
@@ -899,7 +974,8 @@ class Material(object):
             e = np.asarray(epl, dtype=float)
             if e.ndim == 1:
                 e = np.tile(e, (len(s), 1))
-        f, st = self._load().full_yf(0, self._princ_rows(s), e, ld)
+        tid = self._tex_ids(tex_id, len(s), 'ML_full_yf')
+        f, st = self._load().full_yf(0, self._princ_rows(s), e, ld, tex_id=tid)
         if verb and np.any(st != 0):
             warnings.warn('ML_full_yf: Could not bracket / locate the yield locus for %d stress(es); '
                           'conservative estimate seq-0.85*sflow returned' % int(np.sum(st != 0)))
@@ -922,15 +998,16 @@ class Material(object):
                           'conservative estimate seq-0.85*sflow returned' % int(np.sum(st != 0)))
         return f[0] if single else f
 
-    def calc_fgrad(self, sig, epl=None, seq=None, ana=False, tex=None, **kw):
+    def calc_fgrad(self, sig, epl=None, seq=None, ana=False, tex=None, tex_id=None, **kw):
         """Gradient of the yield function w.r.t. stress (material.py:704-858).  EXTENSION: a texture material takes ``tex``,
         (tdim,) or (N, tdim), and returns the stress derivative of ``calc_yf(sig, tex=)`` (see ``_fgrad_tex``)."""
         if getattr(self, '_bound', None) is not None and not ana:   # (khard is a parameter of a bound material: left alone)
             if tex is not None:
                 raise ValueError('calc_fgrad: the material is bound to a texture (at_texture) and takes no tex')
-            a = self._bound_call('calc_fgrad', sig, epl=epl)
+            a = self._bound_call('calc_fgrad', np.asarray(sig, dtype=float), epl=epl, tex_id=tex_id)
             self.msg['gradient'] = 'gradient to ML_yf'
             return a
+        self._tex_ids(tex_id, 1, 'calc_fgrad')
         if tex is not None and not ana:
             return self._fgrad_tex(np.asarray(sig, dtype=float), epl, tex)
         if self.ML_yf and not ana:
@@ -1095,11 +1172,11 @@ class Material(object):
                         raise ValueError('Parameter sig and epl must have the same shape.')
         return self._load().hessian(0, np.ascontiguousarray(s), e) / self.scale_seq
 
-    def response(self, sig, epl, deps, CV, maxit=50, tex=None):
+    def response(self, sig, epl, deps, CV, maxit=50, tex=None, tex_id=0):
         """Elastic-predictor / plastic-corrector update of one material point (material.py:207-346).
         Returns ``fy1, sig, depl, grad_stiff``; ``msg['nsteps']`` is set as in the reference.  EXTENSION: a texture
         material takes ``tex`` (tdim,): the same update with calc_yf, ML_full_yf and calc_fgrad at that texture
-        (DESIGN.md §32)."""
+        (DESIGN.md §32).  A texture field (``at_textures``) takes ``tex_id``, the row of its texture table."""
         sig = np.asarray(sig, dtype=float)
         sh = sig.shape
         if sh != (6,) and sh != (3,):
@@ -1107,6 +1184,15 @@ class Material(object):
                              'Shape of argument is {}'.format(sh))
         if sh == (3,):
             raise NotImplementedError('response: pass the Voigt stress (6,); (3,) principal input is not supported')
+        b = getattr(self, '_bound', None)
+        if b is None or 'coef' not in b or tex is not None:   # (only a texture field takes a row; 0, the default, is no row)
+            if np.ndim(tex_id) != 0 or tex_id != 0:
+                self._tex_ids(tex_id, 1, 'response')
+            tid = None
+        else:
+            if np.ndim(tex_id) != 0:
+                raise ValueError('response: tex_id must be one int')
+            tid = self._tex_ids(tex_id, 1, 'response')
         if tex is not None:
             self._tex_flow_ok('response')
             maxit = int(maxit)
@@ -1135,16 +1221,19 @@ class Material(object):
                 self.msg['gradient'] = 'SVR gradient'
         else:
             fy, so, dp, ct, ns = self._load(CV).response(sig[None, :], np.asarray(epl, dtype=float)[None, :],
-                                                         np.asarray(deps, dtype=float)[None, :], maxit=maxit)
+                                                         np.asarray(deps, dtype=float)[None, :], maxit=maxit, tex_id=tid)
         self.msg['nsteps'] = int(ns[0])
         return fy[0], so[0], dp[0], ct[0].reshape(6, 6)
 
-    def response_batch(self, sig, epl, deps, CV, khard_in=None, return_khard=False, tex=None):
+    def response_batch(self, sig, epl, deps, CV, khard_in=None, return_khard=False, tex=None, tex_id=None):
         """``response`` on (N,6) arrays in one launch (extension; same numbers point by point).  ``khard_in`` /
         ``return_khard``: for a material that follows the SVR flow rule (``enable_svr_flow``), the hardening modulus of
         every point on entry (default: ``khard``) and, appended to the result, on exit; ``khard`` itself is left alone.
         A texture material takes ``tex``, (tdim,) shared by the points or (N, tdim); a point with a non-finite input comes
-        back as NaN with nsteps = -1."""
+        back as NaN with nsteps = -1.  A texture field (``at_textures``) takes ``tex_id``, an int or (N,) ints: the row of
+        its texture table per point (default 0); any other material raises NotImplementedError for it."""
+        if getattr(self, '_bound', None) is None or tex is not None:
+            self._tex_ids(tex_id, 1, 'response_batch')   # (refused: no texture field)
         if tex is not None:
             self._tex_flow_ok('response_batch')
             if khard_in is not None or return_khard:
@@ -1158,7 +1247,7 @@ class Material(object):
         self._tex_refuse('response_batch')
         self._no_svr_gradient('response_batch')
         if getattr(self, '_bound', None) is not None:
-            return self._response_batch_bound(sig, epl, deps, CV, khard_in, return_khard)
+            return self._response_batch_bound(sig, epl, deps, CV, khard_in, return_khard, tex_id)
         if khard_in is not None or return_khard:
             if not self._svr_flow_on():
                 raise ValueError('response_batch: khard_in / return_khard are for a material that follows the SVR flow rule '
@@ -1168,7 +1257,7 @@ class Material(object):
         fy, so, dp, ct, ns = self._load(CV).response(sig, epl, deps)
         return fy, so, dp, ct.reshape(-1, 6, 6), ns
 
-    def _response_batch_bound(self, sig, epl, deps, CV, khard_in, return_khard):
+    def _response_batch_bound(self, sig, epl, deps, CV, khard_in, return_khard, tex_id=None):
         """response_batch of a material bound to a texture: rows with a non-finite sig, epl or deps are masked here and never
         sent; they come back NaN with nsteps = -1, the rule of response_batch(tex=)"""
         if khard_in is not None or return_khard:
@@ -1177,11 +1266,13 @@ class Material(object):
         if s.ndim != 2 or s.shape[1] != 6 or e.shape != s.shape or d.shape != s.shape:
             raise ValueError('response_batch: sig, epl and deps of shape (N, 6) expected')
         n = len(s)
+        tid = self._tex_ids(tex_id, n, 'response_batch')
         ok = np.all(np.isfinite(s) & np.isfinite(e) & np.isfinite(d), axis=1)
         fy, so, dp = np.full(n, np.nan), np.full((n, 6), np.nan), np.full((n, 6), np.nan)
         ct, ns = np.full((n, 6, 6), np.nan), np.full(n, -1, dtype=np.int32)
         if np.any(ok):
-            r = self._load(CV).response(np.ascontiguousarray(s[ok]), np.ascontiguousarray(e[ok]), np.ascontiguousarray(d[ok]))
+            r = self._load(CV).response(np.ascontiguousarray(s[ok]), np.ascontiguousarray(e[ok]), np.ascontiguousarray(d[ok]),
+                                        tex_id=None if tid is None else np.ascontiguousarray(tid[ok]))
             fy[ok], so[ok], dp[ok], ct[ok], ns[ok] = r[0], r[1], r[2], r[3].reshape(-1, 6, 6), r[4]
         return fy, so, dp, ct, ns
 
@@ -1315,7 +1406,7 @@ class Material(object):
                              % (name, e.shape))
         return e
 
-    def yield_scale(self, su, epl=None, x0=None, return_status=False, tex=None):
+    def yield_scale(self, su, epl=None, x0=None, return_status=False, tex=None, tex_id=None):
         """Factor ``x`` with ``calc_yf(x * su, epl) = 0`` along unit stresses ``su`` -- (sdim,), (N,3) or (N,6) -- i.e. where
         the yield locus lies along these directions: the root search behind the reference's ``polar_plot_yl``
         (material.py:3290-3293, one ``fsolve`` over all N unknowns there), done on the device ray by ray in one launch.
@@ -1338,7 +1429,8 @@ class Material(object):
         if getattr(self, '_bound', None) is not None:   # (the parent's search at the bound texture; no plastic strain enters it)
             if tex is not None:
                 raise ValueError('yield_scale: the material is bound to a texture (at_texture) and takes no tex')
-            return self._bound_call('yield_scale', su, x0=x0, return_status=return_status)
+            return self._bound_call('yield_scale', np.asarray(su, dtype=float), x0=x0, return_status=return_status, tex_id=tex_id)
+        self._tex_ids(tex_id, 1, 'yield_scale')
         s, single = self._voigt(su, 'yield_scale')
         if self.ML_yf and getattr(self, 'txdat', False):
             return self._yield_scale_tex(s, single, tex, x0, return_status)
@@ -1353,11 +1445,11 @@ class Material(object):
         x, st = self._load(ana=not ml).yield_scale(0, self._princ_rows(s), e, x0)
         return self._ray_result('yield_scale', 'direction', x, st, single, return_status)
 
-    def yield_stress(self, su, epl=None, tex=None):
+    def yield_stress(self, su, epl=None, tex=None, tex_id=None):
         """Stresses on the yield locus along the unit stresses ``su``: ``su * yield_scale(su, epl)[:, None]`` (NaN rows where
         no point of the locus was found); ``tex`` for a texture material."""
         s = np.asarray(su, dtype=float)
-        x = self.yield_scale(s, epl=epl, tex=tex)
+        x = self.yield_scale(s, epl=epl, tex=tex, tex_id=tex_id)
         return s * x if s.ndim == 1 else s * x[:, None]
 
     # ------------------------------------------------------------------ flow curves as arrays (DESIGN.md §30)
@@ -2118,6 +2210,7 @@ class Material(object):
         (material.py:3062-3166); the harness of the reference's plasticity tests."""
         from .model import Model
         self._tex_refuse('calc_properties')
+        self._bound_refuse('calc_properties')
         self._no_svr_gradient('calc_properties')
 
         def calc_strength(vbc1, nbc1, vbc2, nbc2, sel):

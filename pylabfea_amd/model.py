@@ -397,7 +397,60 @@ class Model(object):
         self._bnd_offs = None
         self._bc_struct = None
         self._bc_registered = None
+        self._tex_ids = None          # set_texture_ids holds until the next mesh()
         self._drop_engine()
+
+    # -- texture rows of the elements of a texture field (Material.at_textures)
+    _tex_ids = None
+    _tex_ids_sent = False         # what the engine holds: False nothing sent yet, else the array (or None) sent last
+
+    def set_texture_ids(self, ids):
+        """The texture row of every element for the materials with a texture field (``Material.at_textures``): an int array
+        in the shape and orientation of ``mesh(elmts=)``, (NX, NY) with element ``j*NY + k``, or flat (Nel,) in element
+        order.  Given after ``mesh()``; holds until the next ``mesh()``.  Entries of elements of other materials are
+        ignored; an entry of a field-material element outside ``0..T-1`` of its material raises ValueError when the engine
+        is set up.  Without a call every element has row 0.  Between two ``solve()`` calls only the index array is
+        re-sent."""
+        if getattr(self, '_grid', None) is None:
+            raise RuntimeError('set_texture_ids: call mesh() first')
+        a = np.asarray(ids)
+        if a.dtype.kind not in 'iu':
+            raise TypeError('set_texture_ids: an int array is expected; got dtype %s' % a.dtype)
+        if a.shape != (self._NX, self._NY) and a.shape != (self.Nel,):
+            raise ValueError('set_texture_ids: ids must be (%d, %d) like mesh(elmts=) or (%d,) in element order; got shape %s'
+                             % (self._NX, self._NY, self.Nel, a.shape))
+        self._tex_ids = np.ascontiguousarray(a.reshape(-1), dtype=np.int32)
+        if self._tex_ids_sent is None:
+            self._tex_ids_sent = False
+
+    @property
+    def texture_ids(self):
+        """the texture row of every element, (Nel,) in element order, read-only; None before mesh()"""
+        if getattr(self, '_grid', None) is None:
+            return None
+        a = np.zeros(self.Nel, dtype=np.int32) if self._tex_ids is None else self._tex_ids.copy()
+        a.flags.writeable = False
+        return a
+
+    def _send_texture_ids(self, eng):
+        """check the rows of the field-material elements against their materials and send the index array, when it changed"""
+        if self._tex_ids_sent is self._tex_ids or (self._tex_ids_sent is False and self._tex_ids is None):
+            return
+        if self._tex_ids is not None:
+            mid = None
+            for j, m in enumerate(self.mat):
+                b = getattr(m, '_bound', None)
+                if b is None or 'coef' not in b:
+                    continue
+                mid = np.asarray(self._mat_id) if mid is None else mid
+                t = self._tex_ids[mid == j]
+                if t.size and (t.min() < 0 or t.max() >= len(b['coef'])):
+                    raise ValueError('set_texture_ids: a texture row of an element of material %d is outside 0..%d'
+                                     % (j, len(b['coef']) - 1))
+            eng.set_element_textures(self._tex_ids[self._e0:self._e1])
+        else:
+            eng.set_element_textures(None)
+        self._tex_ids_sent = self._tex_ids
 
     # -- mesh-sized products of Model.mesh, materialised on first access
     _grid = None
@@ -608,6 +661,7 @@ class Model(object):
         # honoured like in the reference, and a new Material at a recycled address is never mistaken for the old one
         vers = tuple(m._content_key(self._element_CV(m), parameters_only=True) for m in self.mat)
         if self._engine is not None and self._mat_versions == vers:
+            self._send_texture_ids(self._engine)
             return self._engine
         if self._engine is not None and self.u is not None:
             raise RuntimeError('materials were modified after the model was solved; call mesh() again')
@@ -687,6 +741,12 @@ class Model(object):
                           'than 1.5 apart, or a grid too irregular to coarsen): the solve falls back to Jacobi-PCG on the assembled '
                           'operator'.format(self.Nel))
         self._dev_coll = eng.comm_info()[2]  # RCCL communicator: scalars are all-reduced inside the library
+        self._tex_ids_sent = False
+        try:
+            self._send_texture_ids(eng)
+        except Exception:
+            eng.close()
+            raise
         self._engine = eng
         self._mat_versions = vers
         plastic = any(m.sy is not None for m in self.mat)
