@@ -351,10 +351,22 @@ int plfx_sweep_launch_info(plfx_ctx *ctx, int64_t *heavy_skipped, int64_t *heavy
 /* Between the boundary values and the first operator pass (one GPU, no strip; PLFX_BC_ROWS=0 or
  * PLFX_REUSE=0 at plfx_create: all four stay 0).  apply_bc calls that rewrote rhs on the rows next to prescribed nodes only
  * (same Dirichlet set, no force vector) instead of passing over all DOFs (rhs_rows_only); those among them that kept the
- * Jacobi scaling because the diagonal had not been rewritten (dinv_kept) / formed it again on its own (dinv_refreshed);
+ * Jacobi scaling because the diagonal had not been rewritten (dinv_kept) / had it to form again on its own (dinv_refreshed:
+ * at once, or in front of its first reader of values, plfx_short_info);
  * solves whose du was composed behind the first convergence test, under the host's wait for it (du_early).  Results are
  * the same bit for bit either way. */
 int plfx_bc_info(plfx_ctx *ctx, int64_t *rhs_rows_only, int64_t *dinv_kept, int64_t *dinv_refreshed, int64_t *du_early);
+/* Passes an accepted interpolated start never needs (one GPU, no strip, no communicator; PLFX_SHORT_SOLVE
+ * at plfx_create is a bit mask -- 1: the fine level's dinv waits for its first reader of values, like the coarse set-up; 2:
+ * k_pred_finish leaves the d of the next interpolated start behind, k_pred_diff is left out -- default 3, other bits ignored,
+ * 0 or PLFX_REUSE=0: the launches as they were, all counters stay 0).  apply_bc calls that left dinv unformed although the
+ * diagonal had been rewritten (dinv_deferred; they count in plfx_bc_info's dinv_refreshed too); k_dinv launches that made up
+ * for one in front of a reader of values (dinv_formed_late; the rest were superseded unread); solves that left k_pred_diff out
+ * (d_kept).  spec_merged: always 0 (one launch behind a sweep's flags instead of two was built and not kept).
+ * Results are the same bit for bit either way -- for every solve that follows an apply_bc of the present diagonal, which is
+ * every solve of plfx_load_step; plfx_solve called after plfx_assemble or a tangent-changing sweep WITHOUT an apply_bc in
+ * between is preconditioned with the dinv of the new diagonal where it used to get the old one's. */
+int plfx_short_info(plfx_ctx *ctx, int64_t *dinv_deferred, int64_t *dinv_formed_late, int64_t *d_kept, int64_t *spec_merged);
 /* Stores that nothing reads (one GPU, no strip; PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: all
  * four stay 0).  Sweeps of plfx_load_step that were certain to be repeated if they changed a tangent, and in which the
  * elements whose tangent changed therefore left res_sig, res_depl and fyn to the next sweep (armed_sweeps; the tangents they

@@ -267,6 +267,16 @@ struct plfx_ctx {
     bool bc_rows_on = true;
     bool rhs_rows_ok = false, dinv_ok = false;
     long long n_rhs_rows = 0, n_dinv_kept = 0, n_dinv_refreshed = 0, n_du_early = 0;   // plfx_bc_info
+    // Passes an accepted interpolated start never needs (PLFX_SHORT_SOLVE at plfx_create, a bit mask: 1 = A, 2 = B;
+    // default 3, other bits ignored, PLFX_REUSE=0: 0; never with a strip or inside a communicator).
+    // A. dinv_late: the diagonal was rewritten and c->dinv NOT formed again -- its zero pattern is the present Dirichlet mask
+    //    (same set, and 1/|diag| is non-zero for every finite diag), its values are those of an older diagonal.  Whoever reads
+    //    VALUES calls ensure_dinv first; the kernels of an interpolated start only test dinv != 0.
+    // B. pred_d_kept: pred_d holds (free ? x - pred_x : 0) of the present x, pred_x and Dirichlet set, written by k_pred_finish;
+    //    cleared at every other writer of x, pred_x or pred_d.  While it stands, k_pred_diff is left out.
+    int short_solve = 3;
+    bool dinv_late = false, pred_d_kept = false;
+    long long n_dinv_deferred = 0, n_dinv_late = 0, n_d_kept = 0;   // plfx_short_info
     int last_heavy = -1;  // elements that needed the sub-divided corrector in the last sweep (-1: no sweep yet)
     long long n_heavy_skipped = 0, n_heavy_recovered = 0;   // sweeps that left the corrector launches out / had to add them after all
     bool x_is_du = false;  // c->x still holds the last solution on the free DOFs (0 on the prescribed ones) = the warm start
@@ -938,7 +948,7 @@ void free_mesh(plfx_ctx *c)
     dfree(c->q);
     dfree(c->pred_x);
     dfree(c->pred_d);
-    c->pred_valid = false;
+    c->pred_valid = c->pred_d_kept = false;
     for (auto &b : c->gm_blk) dfree(b);
     c->gm_blk.clear();
     c->gm_m = 0;
@@ -987,7 +997,7 @@ void free_mesh(plfx_ctx *c)
     dfree(c->kw);
     dfree(c->bc_rows);
     c->bc_nrows = 0;
-    c->rhs_rows_ok = c->dinv_ok = false;
+    c->rhs_rows_ok = c->dinv_ok = c->dinv_late = false;
     dfree(c->tex_ids);
     c->htex_ids.clear();
     c->tex_ids_ok = false;
@@ -1302,9 +1312,26 @@ KOp make_op(const plfx_ctx *c, int nnode, int nslot, const int32_t *col, const d
     return o;
 }
 
+// The fine-level dinv that apply_bc_impl left unformed (plfx_ctx::dinv_late), in front of whoever reads its VALUES:
+// k_dinv as apply_bc_impl would have launched it.  INVARIANT: between an apply_bc_impl and the solve it prepares nothing writes
+// c->diag, so the launch here sees the (diag, is_presc) that one saw.  The writers of diag: assemble_fine_val calls this first;
+// plfx_assemble's set-up pass and the speculative one behind a sweep's flags do NOT -- they clear dinv_ok, the next
+// apply_bc_impl decides again, and a late dinv that was never read is simply superseded.  A solve that follows either of them
+// WITHOUT an apply_bc in between therefore gets the dinv of the new diagonal where the parent had the old one's.
+int ensure_dinv(plfx_ctx *c)
+{
+    if (!c->dinv_late) return 0;
+    hipLaunchKernelGGL(k_dinv, dim3(grid_for(c->ndof)), dim3(BLOCK), 0, c->stream, (size_t)c->ndof, c->diag, c->is_presc, c->dinv);
+    HIPCHK(c, hipGetLastError());
+    c->dinv_late = false;
+    c->n_dinv_late++;
+    return 0;
+}
+
 // fine block-ELL values on demand (matrix-free runs only need them for plfx_get_csr)
 int assemble_fine_val(plfx_ctx *c)
 {
+    if (int rc = ensure_dinv(c)) return rc;   // (k_assemble rewrites c->diag: a late dinv belongs to the diagonal as it is now)
     hipLaunchKernelGGL(k_assemble, dim3(grid_for(c->nnode), c->nslot), dim3(BLOCK), 0, c->stream,
                        c->dcls, c->ncls, c->nnode, c->nslot, c->nq, c->nel_total, c->dcontrib, c->dcls_all,
                        (matfree(c) && c->assembled) ? c->Mop : c->Mel, c->dcol, c->dval, c->diag,
@@ -1610,10 +1637,12 @@ int mg_update_dinv(plfx_ctx *c, bool same_set);
 bool mg_lazy(const plfx_ctx *c) { return c->predict && matfree(c) && !c->strip.on && !comm_active(c); }
 int mg_ensure(plfx_ctx *c)
 {
+    int rc = ensure_dinv(c);   // (a V-cycle follows: the smoothers and k_mg_coarse_dinv read the fine level's values)
+    if (rc) return rc;
     if (!c->mg_pending) return 0;
     c->mg_pending = false;
     c->n_mg_setup++;
-    int rc = mg_assemble(c);
+    rc = mg_assemble(c);
     if (rc) return rc;
     return mg_update_dinv(c, c->mg_pending_same);
 }
@@ -1838,6 +1867,8 @@ int plfx_create(int device, plfx_ctx **out)
     if (!c->reuse) c->dead_stores = c->test_starts = false;
     if (const char *e11 = getenv("PLFX_PLANE_COLS")) c->plane_switch = atoi(e11) != 0;
     if (!c->reuse) c->plane_switch = false;
+    if (const char *e12 = getenv("PLFX_SHORT_SOLVE")) c->short_solve = atoi(e12) & 3;
+    if (!c->reuse) c->short_solve = 0;
     if (const char *e9 = getenv("PLFX_PREDICT")) c->predict = atoi(e9) != 0;
     {
         const char *e5 = getenv("PLFX_MAILBOX");
@@ -3942,6 +3973,7 @@ int plfx_set_strip(plfx_ctx *c, int own_col0, int own_col1, int global_col0, int
     c->bc_set = false;
     c->bc_valid = false;
     c->rhs_rows_ok = c->dinv_ok = false;
+    c->dinv_late = c->pred_d_kept = false;   // (a strip never defers: the full k_bc_finish of its first apply_bc writes dinv)
     c->x_is_du = false;
     c->memo.valid = false;
     return PLFX_OK;
@@ -4018,6 +4050,16 @@ int plfx_bc_info(plfx_ctx *c, int64_t *rhs_rows_only, int64_t *dinv_kept, int64_
     if (dinv_kept) *dinv_kept = c->n_dinv_kept;
     if (dinv_refreshed) *dinv_refreshed = c->n_dinv_refreshed;
     if (du_early) *du_early = c->n_du_early;
+    return PLFX_OK;
+}
+
+int plfx_short_info(plfx_ctx *c, int64_t *dinv_deferred, int64_t *dinv_formed_late, int64_t *d_kept, int64_t *spec_merged)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (dinv_deferred) *dinv_deferred = c->n_dinv_deferred;
+    if (dinv_formed_late) *dinv_formed_late = c->n_dinv_late;
+    if (d_kept) *d_kept = c->n_d_kept;
+    if (spec_merged) *spec_merged = 0;   // (no merged launch behind a sweep's flags in this library: DESIGN 38 C)
     return PLFX_OK;
 }
 
@@ -4283,7 +4325,7 @@ int plfx_precond_apply(plfx_ctx *c, const double *r, double *z)
         return c ? fail(c, PLFX_ERR_STATE, "needs the multigrid hierarchy of a single-GPU solve, assembled") : PLFX_ERR_STATE;
     HIPCHK(c, hipMemsetAsync(&c->sc->done, 0, sizeof(int), c->stream));  // the fine-level kernels are no-ops while it is set
     HIPCHK(c, hipMemcpyAsync(c->r, r, (size_t)8 * c->ndof, hipMemcpyHostToDevice, c->stream));
-    const int rc = mg_vcycle(c);
+    const int rc = mg_vcycle(c);   // (mg_ensure in it forms a late fine-level dinv first)
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(z, c->z, (size_t)8 * c->ndof, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, stream_sync(c));
@@ -4391,6 +4433,8 @@ int plfx_state_reset(plfx_ctx *c)
     c->assembled = false, c->M_dirty = true;
     c->x_is_du = false;
     c->rhs_rows_ok = c->dinv_ok = false;   // (a new history starts with one full k_bc_finish)
+    // (... which writes dinv for every DOF and clears dinv_late there: until then a late dinv stays owed, bc_set still stands)
+    c->pred_d_kept = false;   // (the first solve rebuilds x from du)
     c->res_is_sig = c->res_fresh = c->eps_stale = c->res_partial = false;
     c->last_heavy = -1;  // the next sweep launches its corrector kernels whatever the one before found
     return PLFX_OK;
@@ -4532,6 +4576,7 @@ int plfx_state_set(plfx_ctx *c, int which, const double *in)
     if (rc) return rc;
     if (!soa) {
         c->x_is_du = false;  // u / f / du written from outside
+        c->pred_d_kept = false;   // (the next solve rebuilds x from du: pred_d belongs to the x that was there)
         HIPCHK(c, hipMemcpyAsync(p, in, 8 * n, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, stream_sync(c));
         return PLFX_OK;
@@ -4692,6 +4737,7 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
                           (n == 0 || memcmp(c->bc_idx.data(), idx, (size_t)4 * n) == 0);
     if (!same_set) {
         c->x_is_du = false;  // another Dirichlet mask: x0 has to be rebuilt from du
+        c->pred_d_kept = false;   // (and pred_d was masked with the old one)
         HIPCHK(c, hipMemsetAsync(c->is_presc, 0, 8 * nd, c->stream));
         HIPCHK(c, hipMemsetAsync(c->dup, 0, 8 * nd, c->stream));
         HIPCHK(c, hipMemsetAsync(c->wv, 0, 8 * nd, c->stream));
@@ -4794,15 +4840,25 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
     if (rows_only) {
         c->n_rhs_rows++;
         if (c->dinv_ok)
-            c->n_dinv_kept++;
-        else {
+            c->n_dinv_kept++;   // (dinv_late stands as it is: still the mask of this set, still unformed)
+        else if ((c->short_solve & 1) && mg_lazy(c) && mg_active(c) && c->mg_pending) {
+            // The coarse levels wait for the first V-cycle, and so does the fine level's dinv: until then its readers
+            // only test dinv != 0, and the old dinv answers that test as the new one would -- same_set holds on this branch, and
+            // free ? 1/|diag| : 0 is non-zero on every free DOF whatever the diagonal.  PRECONDITION: diag is finite (1/inf = 0
+            // would take a DOF out of the pattern; k_dinv maps 0, denormals and NaN to non-zero values).
+            c->dinv_late = true;
+            c->n_dinv_refreshed++;   // (rows_only = kept + refreshed as before; n_dinv_deferred says how many of these were left open)
+            c->n_dinv_deferred++;
+        } else {
             hipLaunchKernelGGL(k_dinv, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->diag, c->is_presc, c->dinv);
             c->n_dinv_refreshed++;
+            c->dinv_late = false;
         }
     } else {
         hipLaunchKernelGGL(k_bc_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd,
                            fext ? c->fext : nullptr, c->kw, c->diag, c->is_presc, c->rhs, c->dinv);
         c->rhs_rows_ok = !fext;
+        c->dinv_late = false;   // (written for every DOF)
     }
     c->dinv_ok = true;
     HIPCHK(c, hipGetLastError());
@@ -5311,6 +5367,8 @@ int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
     std::vector<double> H((size_t)(M + 1) * M), cs(M), sn(M), g(M + 1), hcol(M + 2);
     std::vector<double> Hraw((size_t)(M + 1) * M);
     static const bool gm_dbg = getenv("PLFX_GMRES_DEBUG") != nullptr;
+    if ((rc = ensure_dinv(c))) return rc;   // (k_cg_start's z = dinv r, the Jacobi form of apply_B)
+    c->pred_d_kept = false;
     while (true) {
         // r0 = P (b - K x) -> c->r; beta = |r0|
         LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
@@ -5505,6 +5563,7 @@ struct SolveRun {
     bool pred_finished;              // (... and k_pred_finish has composed du and advanced the history already)
     bool du_early;                   // the gated k_compose_du behind the first test has composed du (that test passed)
     bool test_only;                  // started by k_cg_start_test: r, z and r.z are not there until k_cg_start follows
+    bool d_kept;                     // pred_d already holds this solve's d (plfx_ctx::pred_d_kept and x as the last solve left it): no k_pred_diff
 };
 
 // PLFX_WAIT_FIRST=0: a solve never waits for its first test before it enqueues the interpolated start (always speculate, as before DESIGN 24)
@@ -5567,8 +5626,10 @@ int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
     const int nn = s.nn, gn = s.gn;
     // x0: the previous solution restricted to the free DOFs is still in c->x when neither du nor the Dirichlet set changed
     const bool x_kept = warm && c->x_is_du;
-    if (!x_kept)
+    if (!x_kept) {
         hipLaunchKernelGGL(k_x0, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->is_presc, warm, 1., c->x);
+        c->pred_d_kept = false;   // (x rewritten)
+    }
     c->x_is_du = false;
     int rc = 0;
     // Initial guess from the last TWO solutions (round 5; acceptance rule of round 6).  A warm start uses
@@ -5596,9 +5657,12 @@ int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
         else {
             HIPCHK(c, hipMemcpyAsync(c->pred_x, c->x, 8 * nd, hipMemcpyDeviceToDevice, c->stream));
             c->pred_valid = true;
+            c->pred_d_kept = false;   // (pred_x rewritten)
         }
     } else
-        c->pred_valid = false;   // a cold start or another solver: the history starts again
+        c->pred_valid = c->pred_d_kept = false;   // a cold start or another solver: the history starts again
+    // d of the interpolated start is in pred_d already (k_pred_finish of the solve that last moved x wrote it)
+    s.d_kept = s.pred_active && c->pred_d_kept && x_kept && (c->short_solve & 2) && !c->strip.on && !comm_active(c);
     // A solve that may be answered by x + alpha d needs K d as well as K x: where the plain start is not expected to pass its
     // test, both come from ONE pass over the generators (k_cg_start_pred) instead of k_cg_start and k_spmv<0>.  A site
     // whose last solve was answered by the plain start (the predictor solve of a load step) keeps k_cg_start: it would pay for a
@@ -5608,8 +5672,11 @@ int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
     if (s.pred_fused) {
         // d = x - (solution before) first (k_pred_diff without the flag: the test of this solve has not run yet), then
         // r = P(b - K x) and K d -> p[0]; partials of r.r and b.b -> slot 1 (z and r.z: written by the V-cycle if there is one)
-        hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d,
-                           (const CgScalars *)nullptr);
+        if (s.d_kept)
+            c->n_d_kept++;
+        else
+            hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d,
+                               (const CgScalars *)nullptr);
         hipLaunchKernelGGL(k_cg_start_pred, dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, (const double2 *)c->x, (const double2 *)c->pred_d,
                            (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], s.P_rr[1], s.P_bb);
     } else if (c->test_starts && s.mg && wait_first_on() && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on &&
@@ -5623,14 +5690,19 @@ int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
 #undef TEST_START
         s.test_only = true;
         c->n_test_starts++;
-    } else   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
+    } else {   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
+        if ((rc = ensure_dinv(c))) return rc;   // (z = dinv r)
         LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, warm ? 1 : 0, (const double2 *)c->x, (const double2 *)c->rhs,
                    (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, s.olo, s.ohi);
+    }
     if (c->strip.on) {  // sums of the whole grid; r valid on every local column (the V-cycle reads the halo)
         if ((rc = part_allreduce(c, s.P_rz[1], (size_t)3 * MAXPART))) return rc;
         if ((rc = halo_refresh(c, c->r))) return rc;
     }
-    if (!s.mg) hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, s.P_bb, gn, rtol, c->sc);
+    if (!s.mg) {   // Jacobi-PCG reads dinv's values in every update (the plain start above has formed a late one already)
+        if ((rc = ensure_dinv(c))) return rc;
+        hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, s.P_bb, gn, rtol, c->sc);
+    }
     return 0;
 }
 
@@ -5664,6 +5736,7 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
         if (s.test_only && !first_passed) {
             // the hint was wrong: r, z and r.z after all -- one operator pass more than without the test-only start.  The sums of
             // r.r and b.b are rewritten with the bits the test has seen.
+            if ((rc = ensure_dinv(c))) return rc;
             LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
                        (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, olo, ohi);
             HIPCHK(c, hipGetLastError());
@@ -5679,7 +5752,10 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
         // test (round 6: three round trips -> one).  d = x - (solution before), K d, the two sums, alpha on the device
         // (k_pred_alpha), | P (r - alpha K d) |^2 into the free slot P_rr[0] without touching x, r, z, the test on it.
         if (!s.pred_fused) {   // (the fused start has left d in pred_d and K d in p[0])
-            hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
+            if (s.d_kept)
+                c->n_d_kept++;
+            else
+                hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
             LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)c->pred_d, nullptr, nullptr, (double2 *)c->p[0],
                        nullptr, nullptr, nullptr, 0, nullptr, c->sc, 0, 0, 0);
         }
@@ -5695,10 +5771,13 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
         seq = cg_check_post(c, s.P_rr[0], gn, -2);   // (iters = -2 marks "converged by the interpolated start")
         if (!c->strip.on)   // x, du and the history in one pass -- behind the test, before the host has seen it (no-op unless accepted)
             hipLaunchKernelGGL(k_pred_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x,
-                               (const double *)c->pred_d, c->pred_x, (const double *)c->dup, (const double *)c->is_presc, c->du);
+                               c->pred_d, c->pred_x, (const double *)c->dup, (const double *)c->is_presc, c->du,
+                               ((c->short_solve & 2) && !comm_active(c)) ? 1 : 0);
         if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
         s.done = s.hs.done;
         if (s.done == 1 && s.hs.iters == -2) {   // it is the solution: commit x (r, z are not read again: the loop is skipped)
+            // (k_pred_finish has moved x and pred_x -- and, told to, left the d of the next start in pred_d; k_pred_commit moves x alone)
+            c->pred_d_kept = !c->strip.on && (c->short_solve & 2) && !comm_active(c);
             if (!c->strip.on)
                 s.pred_finished = true;
             else
@@ -5727,6 +5806,7 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
             if ((rc = mg_vcycle_head(c))) return rc;
         }
     } else {
+        if ((rc = ensure_dinv(c))) return rc;     // (never late here -- a late dinv has a pending set-up beside it -- but cheap to say)
         if ((rc = mg_vcycle_head(c))) return rc;  // speculative: its kernels return at once if the flag says converged
         if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
         s.done = s.hs.done;
@@ -5745,6 +5825,7 @@ int pcg_iterate(plfx_ctx *c, SolveRun &s, int maxit)
     int rc;
     const int chunk = mg ? 1 : 50;  // multigrid: the flag is polled inside the iteration, before the V-cycle
     int &it = s.it;
+    if (it < maxit && !s.done) c->pred_d_kept = false;   // (the update kernels move x)
     while (it < maxit && !s.done) {
         const int stop = std::min(maxit, it + chunk);
         for (; it < stop; it++) {
@@ -5885,6 +5966,7 @@ int finish_by_gmres(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, 
     int itm = 0, rc;
     double rl = 0.;
     c->n_indefinite++;
+    c->pred_d_kept = false;   // (GMRES moves x)
     const int rcm = gmres_solve(c, rtol, maxit_all, &itm, &rl);
     if (rcm < 0) return rcm;
     c->n_gmres++;
@@ -5893,7 +5975,7 @@ int finish_by_gmres(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, 
     c->x_is_du = true;
     if (iters) *iters = s.it + itm;
     if (relres) *relres = rl;
-    c->pred_valid = false;   // (not a plain PCG solve: the history of the initial guess starts again)
+    c->pred_valid = c->pred_d_kept = false;   // (not a plain PCG solve: the history of the initial guess starts again)
     remember(c, rtol, rl, rcm == 0);
     return rcm == 0 ? PLFX_OK : 1;
 }
@@ -5904,6 +5986,8 @@ int finish_by_gmres(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, 
 int fall_back_to_jacobi(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, int *iters, double *relres)
 {
     int rc;
+    c->pred_d_kept = false;
+    if ((rc = ensure_dinv(c))) return rc;   // (Jacobi-PCG: z = dinv r throughout)
     if ((rc = compose_du(c))) return rc;
     const int saved = c->precond;   // (changed and restored off a strip only)
     if (c->strip.on) c->strip_jacobi = true;
@@ -5938,8 +6022,10 @@ int solve_finish(plfx_ctx *c, SolveRun &s, double rtol, int *iters, double *relr
     const int its_done = (done && hs.iters >= 0) ? hs.iters : it;
     // history of the initial guess: the solution this solve started from becomes "the one before" -- only if this solve moved
     // away from it (the reference repeats solves of one system: such a solve ends where it started and must not erase d)
-    if (s.pred_d_ready && !s.pred_finished && (s.pred_moved || its_done > 0))
+    if (s.pred_d_ready && !s.pred_finished && (s.pred_moved || its_done > 0)) {
         hipLaunchKernelGGL(k_pred_advance, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->pred_x, c->pred_d);
+        c->pred_d_kept = false;   // (pred_x moved)
+    }
     if (iters) *iters = its_done;
     if (c->tim.on && done) {  // launches after convergence are no-ops: keep them out of the averages
         c->tim.noop[1] += it - hs.iters;

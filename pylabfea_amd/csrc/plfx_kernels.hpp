@@ -3159,9 +3159,14 @@ k_pred_commit(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict_
 
 // the accepted start in one pass (single GPU): x += alpha d, du = x on the free DOFs / the prescribed increment elsewhere
 // (k_compose_du), and the history of the initial guess advances (xprev += d: the solution this solve started from)
+// keep_d != 0: d of the NEXT interpolated start as well, d = free ? x - xprev : 0 of the two values just stored --
+// k_pred_diff's expression on the doubles it would load, so that solve leaves k_pred_diff out while nothing else has written x,
+// xprev or d.  The mask here is is_presc == 0 where k_pred_diff tests dinv != 0: the same set, dinv = free ? 1/|diag| : 0 being
+// non-zero on every free DOF of a finite diagonal.  A plain subtraction: nothing for the compiler to contract.
 __global__ void __launch_bounds__(BLOCK)
-k_pred_finish(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict__ x, const double *__restrict__ d,
-              double *__restrict__ xprev, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du)
+k_pred_finish(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict__ x, double *__restrict__ d,
+              double *__restrict__ xprev, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du,
+              int keep_d)
 {
     // enqueued BEFORE the host has seen the test (its round trip overlaps this pass): does nothing unless the interpolated
     // start was accepted (k_cg_check marks that with iters = -2)
@@ -3170,9 +3175,12 @@ k_pred_finish(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict_
     for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK) {
         const double di = d[i];
         const double xi = fma(alpha, di, x[i]);
+        const double mi = is_presc[i];
         x[i] = xi;
-        du[i] = (is_presc[i] != 0.) ? dup[i] : xi;
-        xprev[i] += di;
+        du[i] = (mi != 0.) ? dup[i] : xi;
+        const double xp = xprev[i] + di;
+        xprev[i] = xp;
+        if (keep_d) d[i] = (mi == 0.) ? xi - xp : 0.;
     }
 }
 
