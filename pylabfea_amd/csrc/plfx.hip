@@ -1,60 +1,20 @@
-// plfx.hip — host side of libplfx.so: context, HBM residency, C-ABI (include/plfx.h).
-//
-// HBM layout (FP64 / int32, everything resident for the life of the mesh):
-//   per owned element e (SoA, component-major [c*nel + e]): sig[6] epl[6] eps[6] res_sig[6]
-//     res_depl[6] tangent (TanStore: form tag, factors[7], elstiff[21, symmetric]) M[6] (compact stiffness generator)
-//     fyn max_steps cls
-//   connectivity conn[nel_total*4] (global element ids), per node: block-ELL matrix
-//     val[nslot][2x2][nnode], col[nslot][nnode], contrib[nslot][nq][nnode] (assembly gather lists)
-//   per DOF (interleaved x,y per node = double2): u f du rhs dinv diag is_presc + PCG vectors
-//     x r z q p0 p1
-#include "../../include/plfx.h"
-#include "plfx_kernels.hpp"
+// plfx.hip -- host side of libplfx.so: context, HBM residency, C-ABI (include/plfx.h) -- all but the sweeps, the load step and the
+// state access, which are plfx_step.hip.  What the two units share is plfx_host.hpp; unit map and the rule that every kernel has
+// one owning unit: DESIGN.md section 39.  This unit owns the kernels of all the groups below but PLFX_UNIT_STEP.
+#define PLFX_UNIT_CONTEXT
+#define PLFX_UNIT_MATERIALS
+#define PLFX_UNIT_MESH
+#define PLFX_UNIT_OPERATOR
+#define PLFX_UNIT_SOLVE
+#include "plfx_host.hpp"
 #include "plfx_mg.hpp"
-#include "plfx_tex.hpp"
 #include "plfx_texflow.hpp"
 #include "plfx_flow.hpp"
 
-#include <dlfcn.h>
-#include <algorithm>
-#include <chrono>
-#include <thread>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <mutex>
-#include <string>
-#include <type_traits>
-#include <vector>
-
-using namespace plfx;
-
-#define PLFX_VERSION "0.1.0-r1"
-
-namespace {
-
-struct EvPair {
-    hipEvent_t a, b;
-    int which;
-    bool pending;
-};
-
-struct Timing {
-    bool on = false;
-    unsigned mask = 0xFFu;  // families that are timed (plfx_timing_select)
-    int every = 1;          // ... every n-th launch of a family (plfx_timing_sample)
-    long long seen[8] = {0};
-    std::vector<EvPair> ring;
-    size_t head = 0;
-    double ms[8] = {0};
-    int64_t n[8] = {0};
-    int64_t noop[8] = {0};  // launches that returned immediately (PCG already converged)
-};
+namespace plfx {
+namespace host {
 
 // minimal RCCL surface (dlopen'ed so the library loads on hosts without RCCL in the path)
-typedef struct ncclComm *ncclComm_t;
 typedef struct { char internal[128]; } ncclUniqueId;
 typedef int (*fn_ncclGetUniqueId)(ncclUniqueId *);
 typedef int (*fn_ncclCommInitRank)(ncclComm_t *, int, ncclUniqueId, int);
@@ -99,11 +59,6 @@ bool load_rccl()
     g_rccl.GroupEnd = (fn_ncclGroup)dlsym(g_rccl.h, "ncclGroupEnd");
     return g_rccl.GetUniqueId && g_rccl.CommInitRank && g_rccl.AllReduce && g_rccl.CommDestroy;
 }
-constexpr int NCCL_FLOAT64 = 8;  // ncclDouble
-constexpr int NCCL_INT32 = 2;    // ncclInt32
-constexpr int NCCL_SUM = 0;
-constexpr int NCCL_MIN = 3;
-
 // Opt-in to > 64 KiB of dynamic LDS is a per-function attribute shared by every context of the process (several models, the
 // point-evaluation context, the coarse context of a strip): only ever raise it, so that a context created later with
 // smaller tables cannot shrink the limit under a context that still launches with the larger ones.
@@ -122,335 +77,11 @@ hipError_t set_dyn_lds(const void *fn, int bytes)
     return e;
 }
 
-template <class T>
-struct DBuf {  // device buffer
-    T *p = nullptr;
-    size_t n = 0;
-};
+}  // namespace host
+}  // namespace plfx
 
-}  // namespace
-
-struct plfx_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    hipDeviceProp_t prop;
-    int lds_doubles = 0;  // dynamic LDS budget (doubles) for SVC staging
-
-    // materials
-    int nmat = 0;
-    std::vector<MatDev> hmat;
-    MatDev *dmat = nullptr;
-    std::vector<double *> dsv;  // owned device copies of sv/dual
-    bool has_svc = false, has_svc3 = false, has_analytic = false, has_elastic = false, has_princ = false;
-    bool has_barlat = false;     // Barlat material with the native normal (plfx_material.barlat_normal)
-    bool has_svcwh = false;      // SVC with work-hardening features (PLFX_SVC_WH)
-    SvrFlowDev svr_flow[MAXMAT] = {}; // SVR flow rule of material k (plfx_set_svr_flow); l == 0: none; X and coef are owned device memory
-    unsigned svr_mask = 0;       // bit k: material k has a rule attached (its points run on k_response_svr)
-    int64_t svr_launches[MAXMAT] = {0};   // response launches of k_response_svr per material since the rule was attached
-    int n_noflow = 0;            // materials without a flow rule (Tresca, Barlat without the native normal)
-    int64_t committee_launches = 0;   // k_committee_yf launches of this context (plfx_committee_info)
-    int32_t committee_staged = 0;     // bit k: member k of the last plfx_committee_yf call had its tables staged in LDS
-    // texture SVC (plfx_tex_svc_set): a table set of its own, owned by the context; plfx_set_materials leaves it alone
-    TexSvcPar tex = {};               // tex.nsv == 0: no set
-    double *tex_sv = nullptr, *tex_dual = nullptr;   // [nsv * tex_stride(tex_nfp)] padded vectors, [nsv] coefficients
-    int tex_nfp = 0;                  // padded feature slots of the set: 8, 12 or 16
-    int64_t tex_yf_launches = 0, tex_ray_launches = 0;
-    int64_t tex_fgrad_launches = 0, tex_full_launches = 0, tex_resp_launches = 0;   // the flow-rule calls
-    int64_t flow_launches = 0;        // k_flow_curve / k_flow_curve_analytic launches of this context (plfx_flow_info)
-    // texture fields (plfx_set_svc_textures): coefficient rows of material k, a PLFX_SVC6_COLS record; coef and sabs are
-    // owned device memory, ids is filled in per launch.  tex_ids / htex_ids: the row of every owned element (null / empty: row 0),
-    // checked against the attached rows by tex_field_check before a sweep or calc_scf (tex_ids_ok: since the last change of either)
-    TexFieldDev tex_field[MAXMAT] = {};
-    int tex_field_rows[MAXMAT] = {0};
-    int64_t tex_field_launches[MAXMAT] = {0};
-    unsigned tex_field_mask = 0;      // bit k: material k has rows attached (its launches take the TEXF instantiations)
-    int32_t *tex_ids = nullptr;
-    std::vector<int32_t> htex_ids;
-    bool tex_ids_ok = false;
-    int svc_lds_need = 0;
-    unsigned svc_row_all = 0;    // bit k: material k is a 6-feature SVC run by the row kernels (one launch per material)
-    unsigned svc_row_lds = 0;    // ... of these, the ones whose tables fit the LDS of a CU (the others are read from device memory)
-    unsigned svc6_mask = 0;      // bit k: material k is a 6-feature SVC
-    unsigned svc_cols_mask = 0;  // bit k: material k is a PLFX_SVC6_COLS record (always among svc_row_all, never in svc6_mask)
-    unsigned svcwh_mask = 0;     // bit k: material k is an SVC with work-hardening features
-    int svc_wave_lds = 0;        // dynamic LDS bytes of the row kernels with their tables in LDS (k_*_row<..., true>)
-    int n_svc6 = 0;              // number of 6-feature SVC materials
-    int want_svc_wave = 1;       // PLFX_SVC_WAVE
-
-    // mesh
-    int nel_total = 0, nnode = 0, ndof = 0, e0 = 0, nel = 0;  // nel = owned
-    int planestress = 0;
-    double thick = 1.;
-    int ncls = 0;
-    std::vector<ClassDev> hcls;
-    std::vector<int32_t> hcls_id;  // per total element
-    std::vector<int32_t> hconn;
-    std::vector<double> hlxy;
-    ClassDev *dcls = nullptr;
-    int32_t *dconn = nullptr, *dcls_id = nullptr;  // dcls_id: owned elements only
-    int32_t *dcls_all = nullptr;                   // class ids of ALL elements (assembly of the replicated matrix)
-    bool sharded = false;                          // owns a strict subset of the elements
-    int own_n0 = 0, own_n1 = 0;                    // disjoint node ownership for the sharded SpMV rows
-    int nslot = 0, nq = 0;
-    int32_t *dcol = nullptr, *dcontrib = nullptr;
-    std::vector<int32_t> hcol;   // host copy of the neighbour slots (empty when the pattern is the closed-form structured one)
-    int pat_nx = 0, pat_ny = 0;  // > 0: structured nx x ny grid, pattern in closed form (structured_slot), hcol not kept
-    double *dval = nullptr;
-    int n_begin = 0, n_end = 0;  // node range touched by owned elements
-    bool nonlin = false;
-
-    // element state (owned)
-    double *sig = nullptr, *epl = nullptr, *eps = nullptr, *res_sig = nullptr, *res_depl = nullptr;
-    // End of a load step.  res_is_sig: the last finish exchanged sig and res_sig instead of copying one into the
-    // other -- c->sig holds both fields, the res_sig buffer is scratch until the next sweep writes it.  res_fresh: a sweep wrote
-    // res_sig since the last exchange.  eps_stale: the stored eps is behind u; the wanted field is class_strain(u) (ensure_eps).
-    bool res_is_sig = false, res_fresh = false, eps_stale = false;
-    // plfx_element_fields: the rows of the last call (grown when a call asks for more rows than any before it, else reused) and
-    // the per-block minimum / maximum partials with their host mirror
-    double *fld_buf = nullptr, *fld_part = nullptr;
-    size_t fld_cap = 0;
-    std::vector<double> fld_host;
-    double *Mel = nullptr, *fyn = nullptr, *scf_hh = nullptr;
-    // element tangents (TanStore, plfx_kernels.hpp): one allocation tan_buf = [21][nel] full entries (elstiff), [7][nel] factors
-    // (elfac), [nel] form tags (eltag)
-    double *tan_buf = nullptr, *elstiff = nullptr, *elfac = nullptr;
-    uint8_t *eltag = nullptr;
-    double *kh_el = nullptr;   // hardening modulus per material point (work-hardening SVC: mutable, carried from sweep to sweep)
-    // work-hardening SVC, sequential carry (the reference's semantics, plfx_kernels.hpp: k_wh_entry): kh_el holds the ENTRY
-    // modulus of every element, kh_out / kh_touch what its response() left, wh_carry the value each material object holds now
-    int hint_nx = 0, hint_ny = 0;   // the mesh came from plfx_set_mesh_structured (numbering known, no verification scans)
-    bool hint_uniform = false;
-    double *colr = nullptr;         // [gx] relative column widths of a non-proportional laminate (else null), KOp::colr
-    double colr_ratio = 1.;
-    int wh_mode = 1;           // 1 = sequential carry (default on one GPU), 0 = one modulus per material point
-    double wh_carry[16] = {0};
-    double *kh_out = nullptr, *kh_new = nullptr, *wh_snap_el = nullptr, *wh_snap_M = nullptr;
-    int32_t *wh_snap_ms = nullptr;   // max_steps at the start of a sequential-carry sweep
-    int32_t *kh_touch = nullptr, *wh_bmax = nullptr, *wh_cnt = nullptr;
-    bool kh_out_valid = false;
-    int64_t n_wh_passes = 0, n_wh_sweeps = 0, n_wh_unresolved = 0;
-    int32_t *max_steps = nullptr, *scf_mult = nullptr, *heavy_list = nullptr;
-    // dof vectors
-    double *u = nullptr, *f = nullptr, *du = nullptr, *rhs = nullptr, *dinv = nullptr, *diag = nullptr,
-           *is_presc = nullptr, *dup = nullptr, *wv = nullptr, *fext = nullptr;
-    double *x = nullptr, *r = nullptr, *z = nullptr, *q = nullptr, *p[2] = {nullptr, nullptr};
-    // scalars / partials
-    double *part = nullptr;  // [8][MAXPART]
-    double *part_g = nullptr;
-    CgScalars *sc = nullptr;
-    int *flags = nullptr;
-    int *bflags = nullptr;  // per-block result slots of the sweep kernels (post_block_flags)
-    double *small = nullptr;  // [64] scratch outputs
-    int32_t *idx_tmp = nullptr;
-    double *val_tmp = nullptr;
-    size_t tmp_cap = 0;
-    bool assembled = false, bc_set = false;
-    std::vector<int32_t> bc_idx;  // prescribed DOFs of the last apply_bc (the device mask is reused when unchanged)
-    bool bc_valid = false;
-    double *stage = nullptr;      // pinned host staging buffer, two halves used alternately
-    size_t stage_cap = 0;
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};  // H2D copy out of half h has completed
-    bool stage_busy[2] = {false, false};
-    int stage_flip = 0;
-    int32_t *bc_idx_dev = nullptr;  // device copy of bc_idx (idx_tmp is shared with plfx_gather)
-    size_t bc_idx_cap = 0;
-    int32_t *bc_rows = nullptr;     // nodes whose matrix rows touch a prescribed node (rows of K w that can be non-zero)
-    int bc_nrows = 0;
-    double *kw = nullptr;           // K w, zero outside bc_rows
-    // Between "the boundary values are known" and the first operator pass (PLFX_BC_ROWS=0 or PLFX_REUSE=0: off;
-    // never with a strip or inside a communicator).  rhs_rows_ok: the last full k_bc_finish ran with this Dirichlet set and
-    // this row list and without a force vector, and nothing has made rhs dense since -- rhs is +0.0 off bc_rows and
-    // k_spmv_rows rewrites it on them.  dinv_ok: c->dinv was formed from the present (diag, is_presc); cleared at every launch
-    // that writes c->diag.  A plain flag, not op_epoch: the set-up pass enqueued behind a sweep's flags writes diag before
-    // plfx_assemble counts it, and assemble_fine_val on behalf of plfx_get_csr never counts.
-    bool bc_rows_on = true;
-    bool rhs_rows_ok = false, dinv_ok = false;
-    long long n_rhs_rows = 0, n_dinv_kept = 0, n_dinv_refreshed = 0, n_du_early = 0;   // plfx_bc_info
-    // Passes an accepted interpolated start never needs (PLFX_SHORT_SOLVE at plfx_create, a bit mask: 1 = A, 2 = B;
-    // default 3, other bits ignored, PLFX_REUSE=0: 0; never with a strip or inside a communicator).
-    // A. dinv_late: the diagonal was rewritten and c->dinv NOT formed again -- its zero pattern is the present Dirichlet mask
-    //    (same set, and 1/|diag| is non-zero for every finite diag), its values are those of an older diagonal.  Whoever reads
-    //    VALUES calls ensure_dinv first; the kernels of an interpolated start only test dinv != 0.
-    // B. pred_d_kept: pred_d holds (free ? x - pred_x : 0) of the present x, pred_x and Dirichlet set, written by k_pred_finish;
-    //    cleared at every other writer of x, pred_x or pred_d.  While it stands, k_pred_diff is left out.
-    int short_solve = 3;
-    bool dinv_late = false, pred_d_kept = false;
-    long long n_dinv_deferred = 0, n_dinv_late = 0, n_d_kept = 0;   // plfx_short_info
-    int last_heavy = -1;  // elements that needed the sub-divided corrector in the last sweep (-1: no sweep yet)
-    long long n_heavy_skipped = 0, n_heavy_recovered = 0;   // sweeps that left the corrector launches out / had to add them after all
-    bool x_is_du = false;  // c->x still holds the last solution on the free DOFs (0 on the prescribed ones) = the warm start
-    // initial guess from the last two solutions (plfx_solve): the solution before the one in c->x, scratch for the difference,
-    // whether pred_x is that vector (same mesh, same Dirichlet set, c->x untouched since), counters
-    double *pred_x = nullptr, *pred_d = nullptr;
-    bool pred_valid = false;
-    bool predict = true;            // PLFX_PREDICT=0 (read at plfx_create) switches the two-solution initial guess off
-    // the coarse levels are set up when a V-cycle is about to run, not when the tangents change (most tangent-update solves of
-    // a steady workload start below the tolerance, see plfx_solve): an assembly is pending; every BC application since kept the set
-    bool mg_pending = false, mg_pending_same = true;
-    long long n_mg_setup = 0, n_mg_setup_skipped = 0;
-    // plfx_load_step, single GPU: the set-up pass of the next stiffness iteration and the K du of the end of the load step are
-    // enqueued behind k_sweep_flags with device-side predicates, before the host has read the flags
-    bool spec_arm = false, spec_setup = false, spec_kdu = false, spec_was_clean = false;
-    // Stores nobody reads (PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: off).  dead_arm: plfx_load_step says of
-    // the sweep it is about to launch that another one follows whenever a tangent changes -- the elements whose tangent changes
-    // may leave res_sig, res_depl and fyn unwritten.  res_partial: the last sweep did leave some unwritten (it ran armed and
-    // reported a changed tangent); cleared by the next sweep, and until then the three fields are not to be read.  Seen from
-    // outside only after plfx_load_step returned an error between two sweeps.
-    // test_starts: a solve whose first test is expected to pass starts with k_cg_start_test (solve_start).
-    bool dead_stores = true, test_starts = true, dead_arm = false, res_partial = false;
-    long long n_dead_sweeps = 0, n_dead_tangents = 0, n_test_starts = 0, n_test_retries = 0;   // plfx_dead_store_info
-    // Plane columns (PLFX_PLANE_COLS=0 or PLFX_REUSE=0 at plfx_create: off).  plane_cols: columns 3 and 4 of sig, epl,
-    // res_sig, res_depl are zero-valued in memory in both buffers of the exchange, rows 4 and 5 of elfac are zero, and every
-    // material is elastic or analytic Hill / J2 with the yz / zx shears uncoupled (plane_mats_ok) -- the Hill sweep and the state
-    // update neither load nor store them.  Switched on by plfx_state_reset alone (which zero-fills all of these), switched off by
-    // whatever could put a non-zero there (plane_off), and then off until the next reset.
-    bool plane_switch = true, plane_mats_ok = false, plane_cols = false;
-    int plane_off_by = PLFX_PLANE_NEVER_ON;
-    long long n_plane_sweeps = 0, n_plane_updates = 0;   // plfx_plane_info
-    // plfx_load_step tells the solver which of its two solves this is (site 0 predictor of the load step, 1 stiffness iteration;
-    // -1 any other caller); first_test_hint[site]: the last solve of that kind was answered by the test of the plain warm start
-    // -- the next one waits for that test before it enqueues the six launches of the interpolated start behind it
-    bool first_test_hint[2] = {false, false};
-    int spec_h0 = 0, spec_h1 = 0;
-    CgScalars *spec_sc = nullptr;
-    long long n_spec_setup = 0, n_spec_kdu = 0;
-    int resp_maxit = MAXIT;          // plfx_set_response_maxit: sub-steps of Material.response's sub-divided increment (point entry only)
-    long long n_pred = 0, n_pred_skipped = 0, n_pred_rejected = 0;   // accepted as the solution / alpha < 0.01 / failed the tolerance test
-    // Unchanged inputs are not recomputed (PLFX_REUSE=0 switches this off): the generators are re-snapshotted only when a
-    // sweep reported a changed tangent (or they were written from outside) since the last plfx_assemble; a registered BC
-    // plan with the same segment values on the same operator is not re-applied; and a solve of the system that the previous
-    // converged solve already solved returns that solution (the reference repeats the last solve of a load step as the
-    // predictor and as the first stiffness iteration of the next one whenever the increments are equal).
-    bool reuse = true;
-    bool M_dirty = true;             // generators (or anything plfx_assemble depends on) changed since the last assembly
-    unsigned long long op_epoch = 0; // counts executed assemblies
-    bool bc_memo = false, bc_memo_fext = false;
-    unsigned long long bc_epoch = 0;
-    BcSegVals bc_last{};
-    struct { bool valid = false; double rtol = 0., relres = 0.; } memo;
-    int n_reuse_assemble = 0, n_reuse_bc = 0, n_reuse_solve = 0;
-    long long n_sweeps = 0, n_tangents_rewritten = 0;  // plfx_sweep_info
-    long long n_svc_row_launches = 0, n_svc_thread_launches = 0;  // plfx_svc_info
-    // registered boundary-condition plan (plfx_set_bc_plan): calc_BC's index structure, fixed for a load history
-    struct BcPlan {
-        int nseg = 0;
-        std::vector<int32_t> seg_of;    // segment of every entry (reference order)
-        std::vector<int32_t> presc;     // ascending unique prescribed DOFs
-        std::vector<int32_t> first_pos; // entry that writes du for presc[k] (first occurrence)
-        std::vector<int32_t> inv;       // entry -> position in presc
-        std::vector<double> first, w;   // scratch
-        bool valid = false;
-        int32_t *seg4 = nullptr;        // device: up to 4 segments per prescribed DOF in entry order (-1 = unused); null when
-                                        // a DOF has more entries or there are more than BcSegVals::N segments
-        // plfx_set_bc_sources: where each segment's value comes from, and the force-controlled segments
-        std::vector<int32_t> src, k, fsrc, fk, flen, fidx;
-        std::vector<double> fshare, fext;
-        bool sources = false;
-    } plan;
-    // registered DOF set of plfx_finish_step (boundary nodes of calc_global)
-    int32_t *fin_idx = nullptr;
-    int fin_n = 0;
-    double *fin_dev = nullptr;      // [2 n + 18] gathered u, f and the 18 element sums
-    double *fin_host = nullptr;     // pinned mirror
-    // deferred end-of-step results (plfx_step.defer_slot): two pinned slots, posted by the device, collected by
-    // plfx_finish_fetch while the next load step is already running
-    CgMbox *fin_box[2] = {nullptr, nullptr};
-    double *fin_pin[2] = {nullptr, nullptr};
-    unsigned long long fin_seq[2] = {0, 0};
-    bool fin_pending[2] = {false, false};
-    int fin_pin_n = 0;
-    int fin_defer = -1;             // slot the next plfx_finish_step posts into instead of waiting
-    int mg_fallbacks = 0; // solves that fell back from multigrid- to Jacobi-PCG
-    int n_indefinite = 0; // solves with an indefinite tangent stiffness (PCG met negative curvature, GMRES completed them)
-    std::vector<double *> gm_blk;                // GMRES: Krylov basis in blocks of GMRES_BLK vectors, allocated as a cycle grows into them
-    double *gm_part = nullptr;                   //        partial sums, on first use
-    double *gm_part2 = nullptr, *gm_red = nullptr, *gm_coef = nullptr;   // delayed re-orthogonalisation: partials of all columns, their sums, coefficients
-    long long n_gmres_its = 0;
-    int n_gmres = 0, gm_m = 0;
-    bool strip_jacobi = false;  // strip-local engine during such a fall-back: the V-cycle is replaced by z = D^-1 r
-    int grid_nodes = 0, grid_el = 0;
-
-    // geometric multigrid preconditioner (structured grids, plfx_set_grid)
-    struct MgLevel {
-        int nx = 0, ny = 0, nnode = 0, nel = 0, nslot = 0, nq = 0, grid = 1;
-        int32_t *col = nullptr, *contrib = nullptr, *cls0 = nullptr;
-        double *val = nullptr, *diag = nullptr, *dinv = nullptr, *Mel = nullptr;
-        double *x = nullptr, *b = nullptr, *t = nullptr, *res = nullptr;
-        double *ainv = nullptr;  // dense inverse (coarsest level, small grids)
-        KOp op{};                // operator descriptor (block-ELL arrays + grid/generator form)
-        double rx = 1., ry = 1.; // relative size of the level's last element column / row (levels of an odd-sized mesh, KOp::rx)
-        ClassDev *cls4 = nullptr; // geometry tables of its four cell shapes (interior, last column, last row, corner), when assembled
-        bool matfree = false;    // applied from the generators (no assembled matrix on this level)
-        bool owned = false;  // level 0 aliases the fine-grid arrays of the context
-    };
-    std::vector<MgLevel> mg;
-    ClassDev *mg_cls = nullptr;  // geometry tables shared by all levels
-    MgLevDev *mg_dev = nullptr;  // level descriptors for the single-workgroup tail kernel
-    int mg_tail = -1;            // first level handled by the tail kernel (-1: none)
-    int mg_tail_T = 0;           // nodes of all tail levels; > 0: the LDS-resident tail kernel is usable
-    int mg_cheby = 0;            // > 0: Chebyshev steps that solve the coarsest level (no dense inverse: odd coarse sizes)
-    double mg_cheby_kappa = 1.;  // assumed condition number of D^-1 K on the coarsest level
-    int mg_tail_E = 0;           // elements of the tail levels without the coarsest; > 0: the matrix-free tail is usable
-    size_t mg_tail_lds = 0;      // dynamic LDS of k_mg_tail_mf
-    bool mg_inv_valid = false;   // the dense coarse inverse matches the current coarse matrix and Dirichlet mask
-    bool mg_dinv_current = false; // the matrix-free levels' dinv was written by the last mg_assemble with the current mask
-    CgMbox *mbox = nullptr;                // pinned host mailbox of the PCG convergence flag (PLFX_MAILBOX)
-    unsigned long long mbox_seq = 0;
-    double *mb_buf = nullptr;              // pinned result buffer of fetch_results
-    int mb_cap = 0;
-    hipGraph_t mg_graph = nullptr;         // captured launches of the V-cycle's coarse levels
-    hipGraphExec_t mg_graph_exec = nullptr;
-    int want_mg_graph = 1;                 // PLFX_MG_GRAPH
-    int gx = 0, gy = 0;          // structured grid (elements) if known
-    int precond = 1;             // 0 = Jacobi, 1 = multigrid when available
-    double mg_omega = 0.65;  // damped Jacobi; lambda_max(D^-1 K) ~ 2.3 for Q4 elasticity (0.9 diverges)
-    int mg_nu = 2;
-    // matrix-free operator on structured grids with one element shape (plfx_set_grid)
-    bool grid_ok = false;        // the structured, uniform grid form is available
-    int want_matfree = 1;        // plfx_set_operator / PLFX_MATFREE
-    double *dtab = nullptr;      // geometry table of grid_apply
-    double *Mop = nullptr;       // generators as of the last plfx_assemble (the matrix-free K is a snapshot like setupK's)
-    KOp op{};                    // fine-level operator
-    bool val_valid = false;      // the fine block-ELL values match the current generators
-
-    // multi-GPU
-    ncclComm_t comm = nullptr;
-    plfx_allreduce_fn host_ar = nullptr;  // host-staged collective transport (plfx_comm_init_callback: tests, hosts without RCCL)
-    void *host_ar_user = nullptr;
-    std::vector<char> host_ar_buf;
-    int rank = 0, nranks = 1;
-    const char *last_coll = nullptr;   // the collective enqueued last on this context's stream, and how many there have been:
-    long long n_coll = 0;              // named in the error a wait for device results ends with after coll_timeout_s
-    double coll_timeout_s = 300.;      // PLFX_COLL_TIMEOUT (seconds; 0 = wait for ever): a peer that never arrives must not hang the job
-
-    // Strip-local engine (plfx_set_strip): this context holds ONE x-strip of a larger structured grid as
-    // a standalone local grid -- the owned element columns [oc0, oc1) plus W halo columns on every interior side.  Three
-    // things stitch the strips together: the halo refresh of a node vector (contiguous node columns, one send/recv pair per
-    // neighbour), owned-only reductions followed by all-reduces of the per-block partial sums, and a replicated coarse
-    // problem (`child`: levels >= Ld of the GLOBAL grid, fed by one all-reduce of the owned level-Ld residual per V-cycle).
-    struct Strip {
-        bool on = false;
-        int oc0 = 0, oc1 = 0;            // owned element columns of the local grid
-        int W = 0;                       // halo width in element columns
-        int Ld = 0;                      // first level of the replicated coarse problem
-        int gcol0 = 0, gnx = 0;          // global element column of local column 0, global element columns
-        bool has_left = false, has_right = false;
-        int own_lo = 0, own_hi = 0;      // owned node range [lo, hi): disjoint over the ranks (reductions)
-        int eown_lo = 0, eown_hi = 0;    // owned element range
-        plfx_ctx *child = nullptr;
-        std::vector<double> hbuf;        // host staging of the callback transport
-        long long n_halo = 0, n_coarse = 0, n_part = 0, n_gen = 0;
-        // launches of the local levels 1 .. Ld-1 before / after the coarse hand-over, captured once and replayed
-        hipGraph_t g_down = nullptr, g_up = nullptr;
-        hipGraphExec_t x_down = nullptr, x_up = nullptr;
-    } strip;
-    bool is_child = false;               // coarse context of a strip: shares stream, sc and dtab with its parent
-
-    Timing tim;
-};
-
-namespace {
+namespace plfx {
+namespace host {
 
 int fail(plfx_ctx *c, int code, const char *fmt, ...)
 {
@@ -462,61 +93,6 @@ int fail(plfx_ctx *c, int code, const char *fmt, ...)
     if (c) c->err = buf;
     return code;
 }
-
-#define HIPCHK(c, call)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(c, PLFX_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                  \
-    } while (0)
-
-template <class T>
-int dalloc(plfx_ctx *c, T **p, size_t n)
-{
-    if (*p) {
-        hipFree(*p);
-        *p = nullptr;
-    }
-    if (n == 0) n = 1;
-    HIPCHK(c, hipMalloc((void **)p, n * sizeof(T)));
-    HIPCHK(c, hipMemsetAsync(*p, 0, n * sizeof(T), c->stream));
-    return 0;
-}
-
-template <class T>
-void dfree(T *&p)
-{
-    if (p) hipFree(p);
-    p = nullptr;
-}
-
-// device buffers of one call, released on every exit path
-struct CallBuffers {
-    std::vector<void *> p;
-    template <class T>
-    int get(plfx_ctx *c, T **q, size_t n)
-    {
-        HIPCHK(c, hipMalloc((void **)q, std::max<size_t>(n, 1) * sizeof(T)));
-        p.push_back(*q);
-        return 0;
-    }
-    // get + upload of n elements on c->stream (host stays valid until the stream is synchronised)
-    template <class T>
-    int put(plfx_ctx *c, T **q, const T *host, size_t n)
-    {
-        if (int rc = get(c, q, n)) return rc;
-        HIPCHK(c, hipMemcpyAsync(*q, host, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-        return 0;
-    }
-    ~CallBuffers()
-    {
-        for (void *q : p) hipFree(q);
-    }
-};
-
-// doubles of the tangent store of n elements: 21 entries + 7 factors + one tag byte per element
-inline size_t tan_words(size_t n) { return 28 * n + (n + 7) / 8; }
 
 int tan_alloc(plfx_ctx *c, size_t n)
 {
@@ -535,16 +111,7 @@ void tan_free(plfx_ctx *c)
     c->eltag = nullptr;
 }
 
-inline TanStore tan_store(const plfx_ctx *c) { return TanStore{c->eltag, c->elfac, c->elstiff}; }
-
-// blocks of the kernels that reduce the 18 element sums of calc_global (part_g): k_update_state<1> at 1024^2, same-box
-// rocprofv3 averages (tools/probes/r04_sumpart_ab.sh): 1024 blocks with 18 sequential block sums 86-88 us; the 18 sums behind
-// ONE barrier (block_sums_to_partials, bit-identical) 81-83; and then 2048 blocks 74, 4096 blocks 78
-#ifndef PLFX_SUMPART
-#define PLFX_SUMPART 2048
-#endif
-constexpr int SUMPART = PLFX_SUMPART;
-int grid_for(size_t n, int cap = MAXPART)
+int grid_for(size_t n, int cap)
 {
     size_t g = (n + BLOCK - 1) / BLOCK;
     if (g < 1) g = 1;
@@ -655,7 +222,7 @@ hipError_t stream_sync(plfx_ctx *c)
 }
 
 // wait until a kernel has posted `seq` to the pinned mailbox (a failed launch or a hung queue must not spin forever)
-int mbox_wait(plfx_ctx *c, unsigned long long seq, CgMbox *box = nullptr)
+int mbox_wait(plfx_ctx *c, unsigned long long seq, CgMbox *box)
 {
     if (!box) box = c->mbox;
     // waits as long as the stream has work in flight (like hipStreamSynchronize would: a corrector sweep over millions
@@ -898,10 +465,6 @@ bool build_pattern(int nnode, const int32_t *conn, int el_begin, int el_end, std
     return true;
 }
 
-void mg_graph_drop(plfx_ctx *c);
-int strip_coarse(plfx_ctx *c);
-void strip_free(plfx_ctx *c);
-
 void free_mesh(plfx_ctx *c)
 {
     mg_graph_drop(c);
@@ -1049,10 +612,6 @@ int ensure_tmp(plfx_ctx *c, size_t n)
     return 0;
 }
 
-bool matfree(const plfx_ctx *c) { return c->grid_ok && c->want_matfree; }
-bool comm_active(const plfx_ctx *c);
-// work-hardening SVC in the reference's sequential-carry semantics: single rank only (the chain crosses every shard)
-bool wh_sequential(const plfx_ctx *c) { return c->has_svcwh && c->wh_mode == 1 && !comm_active(c) && !c->sharded && !c->strip.on; }
 // Marching form of the finest-grid operator kernels (grid_march): PLFX_MARCH=0 never, =1 always; default: the PCG operator
 // kernel always (faster at every size measured), the three V-cycle kernels when one operator pass (112 B per node) exceeds
 // 192 MiB -- three quarters of the 256 MiB Infinity Cache: a pass shares the cache with the other vectors of the cycle, and the
@@ -1075,45 +634,6 @@ bool tail_mf(const plfx_ctx *c)
     return matfree(c) && c->mg_tail_T > 0 && c->mg_tail_E > 0 && c->mg_nu == 2 && !c->mg.empty() && c->mg.back().ainv;
 }
 
-// kernels templated on the operator form: <.., 1> matrix-free grid, <.., 0> block-ELL
-// (the first kernel argument is the operator: one with per-column widths takes instantiation 2)
-template <class... T> static inline bool first_op_columns(const KOp &o, const T &...) { return o.colr != nullptr; }
-#define LAUNCH_OP1(KERN, mf, grid, ...)                                                                        \
-    do {                                                                                                       \
-        if ((mf) && first_op_columns(__VA_ARGS__))                                                             \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<2>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);        \
-        else if (mf)                                                                                           \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<1>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);        \
-        else                                                                                                   \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<0>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);        \
-    } while (0)
-// ... and on a multigrid level whose last element column / row has another size (KOp::rx, ry): instantiation 2
-#define LAUNCH_OP1R(KERN, mf, op, grid, ...)                                                                   \
-    do {                                                                                                       \
-        if ((mf) && ((op).rx != 1. || (op).ry != 1.))                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<2>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);        \
-        else                                                                                                   \
-            LAUNCH_OP1(KERN, mf, grid, __VA_ARGS__);                                                           \
-    } while (0)
-#define LAUNCH_OP2R(KERN, A, mf, op, grid, ...)                                                                \
-    do {                                                                                                       \
-        if ((mf) && ((op).rx != 1. || (op).ry != 1.))                                                          \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<A, 2>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);     \
-        else                                                                                                   \
-            LAUNCH_OP2(KERN, A, mf, grid, __VA_ARGS__);                                                        \
-    } while (0)
-#define LAUNCH_OP2(KERN, A, mf, grid, ...)                                                                     \
-    do {                                                                                                       \
-        if ((mf) && first_op_columns(__VA_ARGS__))                                                             \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<A, 2>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);     \
-        else if (mf)                                                                                           \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<A, 1>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);     \
-        else                                                                                                   \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(KERN<A, 0>), grid, dim3(BLOCK), 0, c->stream, __VA_ARGS__);     \
-    } while (0)
-
-size_t dyn_lds_bytes(const plfx_ctx *c) { return (c->has_svc || c->has_svc3 || c->has_svcwh) ? (size_t)c->svc_lds_need * 8 : 0; }
-
 int plain_spmv(plfx_ctx *c, const double *in, double *out)
 {
     LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(c->grid_nodes), c->op, 0, c->nnode, (const double2 *)in, nullptr, nullptr,
@@ -1121,8 +641,6 @@ int plain_spmv(plfx_ctx *c, const double *in, double *out)
     HIPCHK(c, hipGetLastError());
     return 0;  // the matrix is replicated on every rank: no collective here
 }
-
-bool comm_active(const plfx_ctx *c) { return c->comm != nullptr || c->host_ar != nullptr; }
 
 // in-place all-reduce of a device buffer on the library's stream: RCCL, or the host-staged callback transport
 int allreduce(plfx_ctx *c, void *dev, size_t count, int nccl_dtype, int nccl_op, const char *what)
@@ -1154,7 +672,6 @@ int allreduce(plfx_ctx *c, void *dev, size_t count, int nccl_dtype, int nccl_op,
 
 // Sharded runs: make the stiffness generators of the whole mesh consistent on every rank after a sweep
 // changed the owned ones (own part + exact zeros elsewhere, summed by one all-reduce).
-int strip_sync_M(plfx_ctx *c);
 int sync_M(plfx_ctx *c)
 {
     if (!comm_active(c) || !c->sharded) return 0;
@@ -1169,13 +686,11 @@ int sync_M(plfx_ctx *c)
 // ---------------------------------------------------------------------------------------------- strip-local engine
 // collectives of a strip run whenever there are peers -- and with a single rank when PLFX_STRIP_FORCE_COLL=1 (exercises the
 // RCCL calls of the path on a 1-rank communicator: tests)
-inline bool strip_coll(const plfx_ctx *c)
+bool strip_coll(const plfx_ctx *c)
 {
     static const bool force = getenv("PLFX_STRIP_FORCE_COLL") && atoi(getenv("PLFX_STRIP_FORCE_COLL")) != 0;
     return c->nranks > 1 || (force && (c->comm || c->host_ar));
 }
-inline int own_lo(const plfx_ctx *c) { return c->strip.on ? c->strip.own_lo : 0; }
-inline int own_hi(const plfx_ctx *c) { return c->strip.on ? c->strip.own_hi : c->nnode; }
 
 // all-reduce of per-block partial sums (owned-only on every rank): the consumer kernels keep summing the <= 1024 entries
 // redundantly in a fixed order, so every rank takes bitwise the same decisions
@@ -1293,9 +808,8 @@ int strip_sync_M(plfx_ctx *c)
 }
 
 
-bool mg_active(const plfx_ctx *c) { return c->precond == 1 && c->mg.size() >= 2; }
 KOp make_op(const plfx_ctx *c, int nnode, int nslot, const int32_t *col, const double *val, int nx, int ny, int nel,
-            const double *M, double rx = 1., double ry = 1.)
+            const double *M, double rx, double ry)
 {
     KOp o;
     o.rx = rx;
@@ -1341,9 +855,6 @@ int assemble_fine_val(plfx_ctx *c)
     c->val_valid = true;
     return 0;
 }
-
-// the level halves exactly and all its cells have one size (every level of a mesh whose sizes are multiples of 2^levels)
-static bool level_plain(const plfx_ctx::MgLevel &L) { return !(L.nx & 1) && !(L.ny & 1) && L.rx == 1. && L.ry == 1.; }
 
 // level l >= 1 is applied from its generators (launched matrix-free, or inside the matrix-free tail): only its diagonal is
 // formed, by k_grid_setup; every other level >= 1 is assembled, diagonal included, by k_assemble
@@ -1632,8 +1143,6 @@ void mg_graph_drop(plfx_ctx *c)
 // steady workload most tangent-update solves then start below the tolerance and never apply the preconditioner, and the ~70 us of
 // the coarse set-up (8 launch-bound level passes + the coarsest assembly and its dense inverse) were spent for nothing.  Whoever
 // is about to run a V-cycle calls mg_ensure first.  Single GPU (a strip sets its child context up in lock-step with the others).
-int mg_assemble(plfx_ctx *c);
-int mg_update_dinv(plfx_ctx *c, bool same_set);
 bool mg_lazy(const plfx_ctx *c) { return c->predict && matfree(c) && !c->strip.on && !comm_active(c); }
 int mg_ensure(plfx_ctx *c)
 {
@@ -1830,7 +1339,36 @@ void strip_free(plfx_ctx *c)
     c->strip = plfx_ctx::Strip();
 }
 
-}  // namespace
+// the mode goes off and stays off until the next plfx_state_reset (the first reason is the one reported)
+void plane_off(plfx_ctx *c, int why)
+{
+    if (c->plane_cols) c->plane_off_by = why;
+    c->plane_cols = false;
+}
+
+// ---- launches of this unit's kernels on behalf of the step unit (one owner per kernel)
+void launch_mbox_post(plfx_ctx *c, const double *src, int n, double *dst, CgMbox *mb, unsigned long long seq)
+{
+    hipLaunchKernelGGL(k_mbox_post, dim3(1), dim3(BLOCK), 0, c->stream, src, n, dst, mb, seq);
+}
+
+void launch_kdu_uf(plfx_ctx *c, CgScalars *spec)
+{
+    LAUNCH_OP2(k_spmv, 3, matfree(c), dim3(c->grid_nodes), c->op, 0, c->nnode, (const double2 *)c->du, nullptr, (double2 *)c->u,
+               (double2 *)c->f, nullptr, nullptr, nullptr, 0, nullptr, spec, 0, 0, 0);
+}
+
+void launch_spec_setup(plfx_ctx *c)
+{
+    KOp live = c->op;
+    live.M = c->Mel;
+    LAUNCH_SETUP(0, live, (double2 *)c->diag,
+                       c->Mop, (mg_active(c) && level_plain(c->mg[0])) ? c->mg[1].Mel : (double *)nullptr, (const double2 *)nullptr, 0, 0,
+                       (double2 *)nullptr, 0x7fffffff, (const int *)(c->flags + 8));
+}
+
+}  // namespace host
+}  // namespace plfx
 
 #include "plfx_svm.hpp"
 
@@ -1909,7 +1447,8 @@ void plfx_destroy(plfx_ctx *c)
 #ifdef PLFX_PROF_REGIONS
     {
         unsigned long long h[16];
-        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_prof), sizeof(h)) == hipSuccess && h[7]) {
+        // (g_prof is a device variable per unit: this unit's copy plus the step unit's, whose kernels hold most of the regions)
+        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_prof), sizeof(h)) == hipSuccess && prof_regions_add(h) && h[7]) {
             static const char *nm[8] = {"fgrad", "plain", "ray_sample pass", "ray_sample post", "march", "brentq", "full() in corrector", "corrector loop"};
             for (int i = 0; i < 8; i++) fprintf(stderr, "[prof] %-22s %14llu ticks  %5.1f %% of the corrector loop\n", nm[i], h[i], 100. * h[i] / h[7]);
             fprintf(stderr, "[prof] rows: ray searches %llu, direct evaluations %llu (no polynomial %llu, outside its interval %llu, inside the margin %llu), of the outside ones: below lo %llu, at brentq iterates %llu, at the start point %llu\n",
@@ -1987,54 +1526,7 @@ int plfx_sync(plfx_ctx *c)
     return PLFX_OK;
 }
 
-// launch a row kernel for material k: tables in LDS when they fit, else read from device memory (no dynamic LDS); a
-// PLFX_SVC6_COLS material takes the per-column instantiation, and with a texture field attached the TEXF one, which
-// takes the field with the rows `ids` of the elements / points as its last argument
-#define LAUNCH_ROW1(c, k, ids_, kern, grid, ...)                                                                            \
-    do {                                                                                                                 \
-        const bool cols_ = ((c)->svc_cols_mask >> (k)) & 1u;                                                             \
-        if (((c)->tex_field_mask >> (k)) & 1u) {                                                                         \
-            TexFieldDev tf_ = (c)->tex_field[k];                                                                         \
-            tf_.ids = (ids_);                                                                                            \
-            if (((c)->svc_row_lds >> (k)) & 1u)                                                                          \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<true, true, true, TexFieldDev>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__, tf_);  \
-            else                                                                                                         \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<false, true, true, TexFieldDev>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__, tf_);  \
-            (c)->tex_field_launches[k]++;                                                                                \
-        } else if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<true, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);  \
-        else if (cols_)                                                                                                  \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<false, true>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);        \
-        else if (((c)->svc_row_lds >> (k)) & 1u)                                                                         \
-            hipLaunchKernelGGL(kern<true>, grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);        \
-        else                                                                                                             \
-            hipLaunchKernelGGL(kern<false>, grid, dim3(512), 0, (c)->stream, __VA_ARGS__);                               \
-    } while (0)
-#define LAUNCH_ROW2(c, k, ids_, kern, H, grid, ...)                                                                         \
-    do {                                                                                                                 \
-        const bool cols_ = ((c)->svc_cols_mask >> (k)) & 1u;                                                             \
-        if (((c)->tex_field_mask >> (k)) & 1u) {                                                                         \
-            TexFieldDev tf_ = (c)->tex_field[k];                                                                         \
-            tf_.ids = (ids_);                                                                                            \
-            if (((c)->svc_row_lds >> (k)) & 1u)                                                                          \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true, true, true, TexFieldDev>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__, tf_);  \
-            else                                                                                                         \
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false, true, true, TexFieldDev>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__, tf_);  \
-            (c)->tex_field_launches[k]++;                                                                                \
-        } else if ((((c)->svc_row_lds >> (k)) & 1u) && cols_)                                                                   \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);   \
-        else if (cols_)                                                                                                  \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false, true>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);     \
-        else if (((c)->svc_row_lds >> (k)) & 1u)                                                                         \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, true>), grid, dim3(512), (size_t)(c)->svc_wave_lds, (c)->stream, __VA_ARGS__);   \
-        else                                                                                                             \
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(kern<H, false>), grid, dim3(512), 0, (c)->stream, __VA_ARGS__);           \
-    } while (0)
-
 // ------------------------------------------------------------------------------ materials
-static int ensure_eps(plfx_ctx *c);
-static int split_res_sig(plfx_ctx *c);
-
 // Plane columns.  The closure argument asks of every material of the table, used or not: elastic or analytic Hill /
 // J2 (the kinds whose gradient takes components 3 and 4 from components 3 and 4 alone), CV and SV exactly 0.0 between
 // {xx, yy, zz, xy} and {yz, zx}, and everything that multiplies a zero of those columns finite (0 * inf is not 0).
@@ -2054,26 +1546,6 @@ static bool plane_materials_ok(const std::vector<MatDev> &mats)
     return !mats.empty();
 }
 
-// the mode goes off and stays off until the next plfx_state_reset (the first reason is the one reported)
-static void plane_off(plfx_ctx *c, int why)
-{
-    if (c->plane_cols) c->plane_off_by = why;
-    c->plane_cols = false;
-}
-
-// (a strip or a communicator can be set up after the reset: asked at every launch)
-static bool plane_active(const plfx_ctx *c) { return c->plane_cols && !c->strip.on && !comm_active(c) && !c->sharded; }
-
-// Grid of k_sweep_light_plane: the element grid (PLFX_SWEEP_BLOCKS included), but no more blocks than the device holds
-// at once -- 4 SIMDs per CU at the waves per SIMD the kernel is compiled for.  A count that is off costs speed only.
-static int plane_sweep_grid(const plfx_ctx *c)
-{
-    const int resident = c->prop.multiProcessorCount * (PLANE_SWEEP_WAVES * 4 * 64 / BLOCK);
-    int g = std::min(c->grid_el, std::max(resident, 1));
-    if (g >= 16) g &= ~7;   // (xcd_tile, as grid_xcd)
-    return g;
-}
-
 int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
 {
     if (!c || !c->stream) return PLFX_ERR_STATE;
@@ -2084,8 +1556,7 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
         if ((rcs = ensure_eps(c)) || (rcs = split_res_sig(c))) return rcs;
         c->res_fresh = false;
         // the tangent store refers to the CV of the current materials: hold every stored tangent in full form first
-        hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->elstiff, 1);
+        launch_tangent_expand(c, c->elstiff, 1);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, stream_sync(c));
     }
@@ -2241,42 +1712,22 @@ int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->dmat, c->hmat.data(), sizeof(MatDev) * nmat, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, stream_sync(c));
+    if (int rcl = raise_step_lds(c)) return rcl;   // the sweep, scf and response row kernels, which the step unit launches
     if (c->svc_wave_lds > 0) {
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<0, true>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<1, true>, c->svc_wave_lds));
         HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_response_row<true>, c->svc_wave_lds));
-        HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true>, c->svc_wave_lds));
         if (c->svc_cols_mask & c->svc_row_lds) {
-            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<0, true, true>, c->svc_wave_lds));
-            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<1, true, true>, c->svc_wave_lds));
             HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true>, c->svc_wave_lds));
-            HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true>, c->svc_wave_lds));
-            HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true, true>, c->svc_wave_lds));
             // (a texture field can be attached to any of them)
-            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<0, true, true, true, TexFieldDev>, c->svc_wave_lds));
-            HIPCHK(c, set_dyn_lds((const void *)k_sweep_svc_row<1, true, true, true, TexFieldDev>, c->svc_wave_lds));
             HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
-            HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
-            HIPCHK(c, set_dyn_lds((const void *)k_scf_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
         }
     }
     if (c->has_svc || c->has_svc3 || c->has_svcwh) {  // opt in to > 64 KiB dynamic LDS for the SVC kernels
         const int bytes = (int)dyn_lds_bytes(c);
         HIPCHK(c, set_dyn_lds((const void *)k_response_batch<3>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_response_batch<6>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_light<6>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_heavy<6>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_point_eval, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_light<3>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_heavy<3>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_scf_elements, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_response_batch<7>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_response_svr, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_light<7>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_heavy<7>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_wh_wave<0>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_sweep_wh_wave<1>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<6>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<15>, bytes));
         HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<6>, bytes));
@@ -2386,26 +1837,6 @@ int plfx_svc_textures_info(plfx_ctx *c, int mat, int *rows, int *staged, int64_t
     return PLFX_OK;
 }
 
-// Before a sweep or calc_scf of a model with a texture field: every element of a field material has a row that exists.  Nothing
-// is launched on an index out of range.
-static int tex_field_check(plfx_ctx *c)
-{
-    if (!c->tex_field_mask) return PLFX_OK;
-    if (c->strip.on || c->sharded || comm_active(c))
-        return fail(c, PLFX_ERR_UNSUPPORTED, "a texture field runs on one GPU without strips or shards");
-    if (c->tex_ids_ok || !c->tex_ids) return PLFX_OK;   // (no array: row 0, and an attached field has at least one row)
-    for (int e = 0; e < c->nel; e++) {
-        const int k = c->hcls[c->hcls_id[(size_t)c->e0 + e]].mat;
-        if (!((c->tex_field_mask >> k) & 1u)) continue;
-        const int32_t t = c->htex_ids[e];
-        if (t < 0 || t >= c->tex_field_rows[k])
-            return fail(c, PLFX_ERR_ARG, "texture row %d of element %d is outside the %d rows of material %d", (int)t, e,
-                        c->tex_field_rows[k], k);
-    }
-    c->tex_ids_ok = true;
-    return PLFX_OK;
-}
-
 // the rows of the points of a _tid call: checked on the host for the materials that carry a field
 static int tex_point_check(plfx_ctx *c, int n, int mat, const int32_t *mat_id, const int32_t *tex_id)
 {
@@ -2427,23 +1858,6 @@ static int point_check(plfx_ctx *c, int mat, bool args_ok)
     if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
     if (mat < 0 || mat >= c->nmat || !args_ok) return fail(c, PLFX_ERR_ARG, "bad argument");
     return PLFX_OK;
-}
-
-// Block size of a kernel with 16 lanes per point whose blocks stage the tables once: the fewest points per block that still
-// leave no more than a few blocks per CU, so that a short batch spreads over the device.  No result depends on the choice.
-static int row16_block(const plfx_ctx *c, int n, int cap)
-{
-    int block = 64;
-    while (block < cap && (n + block / 16 - 1) / (block / 16) > 2 * c->prop.multiProcessorCount) block *= 2;
-    return block;
-}
-
-// Grid of such a kernel: a block per block / 16 points, but no more than `rounds` blocks per CU, since every block stages the
-// tables again
-static dim3 row16_grid(const plfx_ctx *c, int n, int block, int rounds)
-{
-    const int rpb = block / 16;
-    return dim3(std::max(1, std::min((n + rpb - 1) / rpb, rounds * c->prop.multiProcessorCount)));
 }
 
 // f(std::integral_constant<int, NFP>) for the padded width nfp of a texture set (plfx_tex.hpp): the one place that lists the
@@ -2601,8 +2015,7 @@ static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const 
                            c->stream, RB_ARGS(c->svc_lds_need), (const double *)nullptr, (double *)nullptr, rmask, c->resp_maxit);
     for (int k = 0; k < c->nmat; k++)   // 6-feature SVC materials with tables in LDS: 16 lanes per point (the code path of the sweeps)
         if ((rmask >> k) & 1u)
-            LAUNCH_ROW1(c, k, (const int32_t *)d_tid, k_response_row, dim3(std::max(1, std::min((n + 31) / 32, 1024))),
-                       c->dmat, c->nmat, k, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so, d_dp, d_ct, d_ns, c->resp_maxit);
+            launch_response_row(c, k, (const int32_t *)d_tid, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so, d_dp, d_ct, d_ns);
     if (c->has_svc3)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<6>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
                            c->stream, RB_ARGS(c->svc_lds_need), RB_TAIL);
@@ -4393,246 +3806,6 @@ int plfx_solve_fallbacks(plfx_ctx *c, int64_t *count)
     return PLFX_OK;
 }
 
-// ------------------------------------------------------------------------------ state
-int plfx_state_reset(plfx_ctx *c)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    const size_t ne = c->nel, nd = c->ndof;
-    HIPCHK(c, hipMemsetAsync(c->sig, 0, 48 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->epl, 0, 48 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->eps, 0, 48 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->res_sig, 0, 48 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->res_depl, 0, 48 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->fyn, 0, 8 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->max_steps, 0, 4 * ne, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->u, 0, 8 * nd, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->f, 0, 8 * nd, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->du, 0, 8 * nd, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->flags, 0, 32, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->bflags, 0, (size_t)8 * SWEEP_SLOTS, c->stream));
-    {   // hardening modulus of every material point = its material's khard (Material.khard before the first response call)
-        std::vector<double> kh(c->nel);
-        for (int e = 0; e < c->nel; e++) kh[e] = c->hmat[c->hcls[c->hcls_id[c->e0 + e]].mat].khard;
-        HIPCHK(c, hipMemcpyAsync(c->kh_el, kh.data(), (size_t)8 * c->nel, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, stream_sync(c));
-        for (int m = 0; m < c->nmat && m < 16; m++) c->wh_carry[m] = c->hmat[m].khard;
-        c->kh_out_valid = false;
-    }
-    hipLaunchKernelGGL(k_init_tangent, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                       c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->Mel + c->e0, c->nel_total);
-    if (c->sharded)
-        hipLaunchKernelGGL(k_init_M_all, dim3((c->nel_total + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                           c->dmat, c->dcls, c->nel_total, c->dcls_all, c->Mel);
-    HIPCHK(c, hipGetLastError());
-    // plane columns: the four state arrays are zero from the memsets above; rows 4 and 5 of the factors, which tan_alloc and
-    // k_init_tangent leave as they are, are zeroed here -- the invariant holds from this point on
-    c->plane_off_by = !c->plane_switch ? PLFX_PLANE_SWITCH : (c->sharded || c->strip.on || comm_active(c)) ? PLFX_PLANE_SHARDED :
-                      !c->plane_mats_ok ? PLFX_PLANE_MATERIALS : PLFX_PLANE_ON;
-    c->plane_cols = c->plane_off_by == PLFX_PLANE_ON;
-    if (c->plane_cols) HIPCHK(c, hipMemsetAsync(c->elfac + 4 * ne, 0, 16 * ne, c->stream));
-    c->assembled = false, c->M_dirty = true;
-    c->x_is_du = false;
-    c->rhs_rows_ok = c->dinv_ok = false;   // (a new history starts with one full k_bc_finish)
-    // (... which writes dinv for every DOF and clears dinv_late there: until then a late dinv stays owed, bc_set still stands)
-    c->pred_d_kept = false;   // (the first solve rebuilds x from du)
-    c->res_is_sig = c->res_fresh = c->eps_stale = c->res_partial = false;
-    c->last_heavy = -1;  // the next sweep launches its corrector kernels whatever the one before found
-    return PLFX_OK;
-}
-
-// the stored eps field, brought up to date: eps = class_strain(u) (k_update_state forms it for the sums and does not store it)
-static int ensure_eps(plfx_ctx *c)
-{
-    if (!c->eps_stale) return 0;
-    hipLaunchKernelGGL(k_eps_from_u, dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
-                       c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->u, c->eps);
-    HIPCHK(c, hipGetLastError());
-    c->eps_stale = false;
-    return 0;
-}
-
-// res_sig as a field of its own again (after an exchange c->sig holds both): copy, then the two buffers are independent
-static int split_res_sig(plfx_ctx *c)
-{
-    if (!c->res_is_sig) return 0;
-    HIPCHK(c, hipMemcpyAsync(c->res_sig, c->sig, (size_t)48 * c->nel, hipMemcpyDeviceToDevice, c->stream));
-    c->res_is_sig = false;
-    return 0;
-}
-
-// what the end of a load step does with sig: exchange it with res_sig (true) or run the kernel as ever (false)
-static int finish_mode(plfx_ctx *c, bool *swap)
-{
-    *swap = c->nonlin && !c->has_elastic && c->res_fresh;
-    if (*swap) return 0;
-    return split_res_sig(c);   // no sweep since the last exchange: res_sig == sig, as the kernel will read it
-}
-
-static void finish_done(plfx_ctx *c, bool swap)
-{
-    if (swap) {
-        std::swap(c->sig, c->res_sig);
-        c->res_is_sig = true;
-        c->res_fresh = false;
-    }
-    c->eps_stale = true;
-}
-
-// readers of res_sig / res_depl / fyn: not between a sweep that left them partial (plfx_ctx::res_partial) and its successor
-static int res_complete(plfx_ctx *c, const char *who)
-{
-    if (!c->res_partial) return 0;
-    return fail(c, PLFX_ERR_STATE, "%s: the last sweep left res_sig / res_depl / fyn partial (a load step ended in an error "
-                                   "between two sweeps): sweep again first", who);
-}
-
-static int state_ptr(plfx_ctx *c, int which, double **p, size_t *comps, size_t *n, bool *soa)
-{
-    *soa = true;
-    *n = c->nel;
-    if (which == 3 || which == 4 || which == 9) {
-        const int rcp = res_complete(c, "state");
-        if (rcp) return rcp;
-    }
-    if (which == 1 || which == 6) {   // eps is read, or eps / u is about to be overwritten: the stored field first
-        const int rce = ensure_eps(c);
-        if (rce) return rce;
-    }
-    switch (which) {
-    case 0: *p = c->sig; *comps = 6; break;
-    case 1: *p = c->eps; *comps = 6; break;
-    case 2: *p = c->epl; *comps = 6; break;
-    case 3: *p = c->res_is_sig ? c->sig : c->res_sig; *comps = 6; break;
-    case 4: *p = c->res_depl; *comps = 6; break;
-    case 5: *p = c->elstiff; *comps = 21; break;
-    case 6: *p = c->u; *comps = 1; *n = c->ndof; *soa = false; break;
-    case 7: *p = c->f; *comps = 1; *n = c->ndof; *soa = false; break;
-    case 8: *p = c->du; *comps = 1; *n = c->ndof; *soa = false; break;
-    case 9: *p = c->fyn; *comps = 1; *soa = false; break;
-    case 11: *p = (wh_sequential(c) && c->kh_out_valid) ? c->kh_out : c->kh_el; *comps = 1; *soa = false; break;  // exit moduli of the last sweep
-    default: return fail(c, PLFX_ERR_ARG, "unknown state id %d", which);
-    }
-    return 0;
-}
-
-int plfx_state_get(plfx_ctx *c, int which, double *out)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (!out) return fail(c, PLFX_ERR_ARG, "null output");
-    if (which == 10) {
-        std::vector<int32_t> t(c->nel);
-        HIPCHK(c, hipMemcpyAsync(t.data(), c->max_steps, (size_t)4 * c->nel, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_sync(c));
-        for (int e = 0; e < c->nel; e++) out[e] = t[e];
-        return PLFX_OK;
-    }
-    double *p;
-    size_t comps, n;
-    bool soa;
-    int rc = state_ptr(c, which, &p, &comps, &n, &soa);
-    if (rc) return rc;
-    if (!soa) {
-        HIPCHK(c, hipMemcpyAsync(out, p, 8 * n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_sync(c));
-        return PLFX_OK;
-    }
-    std::vector<double> t(comps * n);
-    if (which == 5) {  // the tangent store expanded to 21 entries per element
-        double *tmp = nullptr;
-        if ((rc = dalloc(c, &tmp, 21 * n))) return rc;
-        hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), tmp, 0);
-        hipError_t er = hipGetLastError();
-        if (er == hipSuccess) er = hipMemcpyAsync(t.data(), tmp, 8 * comps * n, hipMemcpyDeviceToHost, c->stream);
-        if (er == hipSuccess) er = stream_sync(c);
-        dfree(tmp);
-        HIPCHK(c, er);
-    } else {
-        HIPCHK(c, hipMemcpyAsync(t.data(), p, 8 * comps * n, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_sync(c));
-    }
-    if (comps == 6) {
-        for (size_t e = 0; e < n; e++)
-            for (int k = 0; k < 6; k++) out[6 * e + k] = t[(size_t)k * n + e];
-    } else {  // symmetric 21 -> full 36
-        for (size_t e = 0; e < n; e++)
-            for (int i = 0; i < 6; i++)
-                for (int j = 0; j < 6; j++) out[36 * e + 6 * i + j] = t[(size_t)sym_idx(i, j) * n + e];
-    }
-    return PLFX_OK;
-}
-
-int plfx_state_set(plfx_ctx *c, int which, const double *in)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (!in) return fail(c, PLFX_ERR_ARG, "null input");
-    if (which == 10) return fail(c, PLFX_ERR_ARG, "max_steps is read-only");
-    double *p;
-    size_t comps, n;
-    bool soa;
-    int rc = (which == 0 || which == 3) ? split_res_sig(c) : 0;   // sig / res_sig written from outside: two buffers first
-    if (rc) return rc;
-    rc = state_ptr(c, which, &p, &comps, &n, &soa);
-    if (rc) return rc;
-    if (!soa) {
-        c->x_is_du = false;  // u / f / du written from outside
-        c->pred_d_kept = false;   // (the next solve rebuilds x from du: pred_d belongs to the x that was there)
-        HIPCHK(c, hipMemcpyAsync(p, in, 8 * n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, stream_sync(c));
-        return PLFX_OK;
-    }
-    std::vector<double> t(comps * n);
-    if (comps == 6) {
-        for (size_t e = 0; e < n; e++)
-            for (int k = 0; k < 6; k++) t[(size_t)k * n + e] = in[6 * e + k];
-    } else {
-        for (size_t e = 0; e < n; e++)
-            for (int i = 0; i < 6; i++)
-                for (int j = i; j < 6; j++) t[(size_t)sym_idx(i, j) * n + e] = in[36 * e + 6 * i + j];
-    }
-    if (c->plane_cols && (which == 0 || which == 2 || which == 3 || which == 4)) {   // a non-zero in column 3 or 4 ends the plane mode
-        const double *c34 = t.data() + 3 * n;
-        for (size_t i = 0; i < 2 * n; i++)
-            if (c34[i] != 0.) {
-                plane_off(c, PLFX_PLANE_STATE_SET);
-                break;
-            }
-    }
-    if (which == 5) plane_off(c, PLFX_PLANE_TANGENT_SET);   // (conservative: a tangent from outside may couple the shears)
-    HIPCHK(c, hipMemcpyAsync(p, t.data(), 8 * comps * n, hipMemcpyHostToDevice, c->stream));
-    if (which == 5) {  // every element's tangent is now held in full form
-        c->M_dirty = true;
-        HIPCHK(c, hipMemsetAsync(c->eltag, TAN_FULL, n, c->stream));
-        hipLaunchKernelGGL(k_refresh_M, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                           c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->Mel + c->e0, c->nel_total);
-        HIPCHK(c, hipGetLastError());
-        int rcm = sync_M(c);
-        if (rcm) return rcm;
-    }
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-int plfx_gather(plfx_ctx *c, int which, int n, const int32_t *idx, double *out)
-{
-    if (!c || !c->u) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (n < 0 || !idx || !out) return fail(c, PLFX_ERR_ARG, "bad argument");
-    if (n == 0) return PLFX_OK;
-    const double *src = which == 6 ? c->u : which == 7 ? c->f : which == 8 ? c->du : nullptr;
-    if (!src) return fail(c, PLFX_ERR_ARG, "gather supports u(6), f(7), du(8)");
-    for (int k = 0; k < n; k++)
-        if (idx[k] < 0 || idx[k] >= c->ndof) return fail(c, PLFX_ERR_ARG, "idx[%d] out of range", k);
-    int rc = ensure_tmp(c, n);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->idx_tmp, idx, (size_t)4 * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gather, dim3((n + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, n, c->idx_tmp, src, c->val_tmp);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->val_tmp, (size_t)8 * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// ------------------------------------------------------------------------------ assembly
 int plfx_assemble(plfx_ctx *c)
 {
     if (!c || !c->dval) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
@@ -5002,252 +4175,10 @@ int plfx_set_bc_sources(plfx_ctx *c, int nseg, const int32_t *src, const int32_t
     return PLFX_OK;
 }
 
-namespace {
+}  // extern "C"
 
-int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *iters, double *relres);
-
-// calc_BC through the registered plan for the current increments; returns the first inconsistent entry or -1
-int step_apply_bc(plfx_ctx *c, const plfx_step *st, const double *dbcr, const double *dbct, const double *dbcn, int *bad)
-{
-    auto &P = c->plan;
-    const double *val[5] = {st->bcl0, st->bcb0, dbcr, dbct, dbcn};
-    std::vector<double> seg(P.nseg);
-    for (int i = 0; i < P.nseg; i++) seg[i] = val[P.src[i]][P.k[i]];
-    const double *fext = nullptr;
-    bool any = false;
-    size_t o = 0;
-    for (size_t f = 0; f < P.fsrc.size(); f++) {  // edge / node-set forces (model.py:1145-1151, 1173-1179, 1203-1205)
-        const double v = val[P.fsrc[f]][P.fk[f]];
-        if (v != 0.) {
-            if (!any) P.fext.assign(c->ndof, 0.);
-            any = true;
-            for (int q = 0; q < P.flen[f]; q++) P.fext[P.fidx[o + q]] += v * P.fshare[o + q];
-        }
-        o += P.flen[f];
-    }
-    if (any) fext = P.fext.data();
-    int b = -1;
-    int rc = plfx_apply_bc_plan(c, seg.data(), fext, &b);
-    if (bad && *bad < 0) *bad = b;
-    return rc;
-}
-
-// site: which of the two solves of a load step this is (0 predictor, 1 stiffness iteration; plfx_ctx::first_test_hint)
-int step_solve(plfx_ctx *c, plfx_step *st, int warm, int site)
-{
-    int it = 0;
-    double rr = 0.;
-    const int rc = solve_impl(c, st->rtol, st->maxit, warm, site, &it, &rr);
-    if (rc < 0) return rc;
-    if (st->nsolves < 40) {
-        st->its[st->nsolves] = it;
-        st->relres[st->nsolves] = rr;
-    }
-    st->nsolves++;
-    if (rc == 1) st->soft_fail++;
-    return 0;
-}
-
-}  // namespace
-
-int plfx_load_step(plfx_ctx *c, plfx_step *st, double *u_at, double *f_at, double *sums18)
-{
-    if (!c || !st) return PLFX_ERR_ARG;
-    if (!c->plan.valid || !c->plan.sources) return fail(c, PLFX_ERR_STATE, "set_bc_plan / set_bc_sources first");
-    if (!c->fin_dev) return fail(c, PLFX_ERR_STATE, "set_finish_set first");
-    st->nit = st->nconv = st->nsweeps = st->nsolves = st->soft_fail = 0;
-    st->inconsistent_entry = -1;
-    st->scale_bc = 1.;
-    int rc;
-    double dbcr[2] = {st->max_dbcr[0], st->max_dbcr[1]}, dbct[2] = {st->max_dbct[0], st->max_dbct[1]};
-    double *dbcn = st->max_dbcn;  // the reference's dbcn IS max_dbcn (alias, model.py:1285)
-    // elastic predictor with the stiffness of the previous step (model.py:1290-1291)
-    if ((rc = step_apply_bc(c, st, dbcr, dbct, dbcn, &st->inconsistent_entry))) return rc;
-    if ((rc = step_solve(c, st, st->warm, 0))) return rc;
-    if (st->nonlin) {
-        if (st->il < 10) {  // calc_scf (model.py:1036-1067, 1296)
-            int64_t cnt = 0;
-            double mn = 0., sm = 0., s2 = 0.;
-            if ((rc = plfx_scf_all(c, st->sld, &cnt, &mn, &sm, &s2))) return rc;
-            if (cnt > 0) {
-                const double mean = sm / (double)cnt, sd = std::sqrt(s2 / (double)cnt);
-                double scf = (sd < 0.1) ? mn : std::max(1.e-3, mean - sd);
-                if (scf < 1.e-3) scf = 1.e-3;
-                st->scale_bc = scf;
-            }
-        }
-        for (int k = 0; k < 2; k++) {
-            dbcr[k] = st->max_dbcr[k] * st->scale_bc;
-            dbct[k] = st->max_dbct[k] * st->scale_bc;
-        }
-        int nit = 0, change = 1, conv = 0;
-        while ((change || !conv) && nit <= 15) {  // model.py:1306
-            if (st->il < 6 && nit > 1) {          // reduce the load increment to reach convergence (:1308-1330)
-                const double hs = 0.5;
-                auto halve = [&](double mx, double tot, double cur0, double &d) {
-                    if (mx >= 0.)
-                        d = std::max(0.05 * mx, std::min(tot - cur0, d * hs));
-                    else
-                        d = std::min(0.05 * mx, std::max(tot - cur0, d * hs));
-                };
-                for (int k = 0; k < 2; k++) {
-                    halve(st->max_dbcr[k], st->bcr[k], st->bcr0[k], dbcr[k]);
-                    halve(st->max_dbct[k], st->bct[k], st->bct0[k], dbct[k]);
-                    if (st->has_nodeset) {  // d and mx are the same variable here
-                        const double mx = dbcn[k];
-                        halve(mx, st->bcn[k], st->bcn0[k], dbcn[k]);
-                    }
-                }
-            }
-            if ((rc = plfx_assemble(c))) return rc;  // updated tangent stiffness (model.py:1333)
-            if ((rc = step_apply_bc(c, st, dbcr, dbct, dbcn, &st->inconsistent_entry))) return rc;
-            if ((rc = step_solve(c, st, 1, 1))) return rc;
-            // (the loop goes on after this sweep only if nit + 1 <= 15: then -- and only then -- what follows the flags is decided
-            // by the flags alone and can be enqueued behind them with device-side predicates)
-            c->spec_arm = (nit + 1 <= 15) && c->reuse && !wh_sequential(c);
-            // (... and a sweep that changes a tangent is then followed by one that rewrites every plastic element's response)
-            c->dead_arm = (nit + 1 <= 15) && !wh_sequential(c);
-            rc = plfx_sweep(c, nit, &change, &conv);  // model.py:1340-1361
-            c->spec_arm = c->dead_arm = false;
-            if (rc) return rc;
-            st->nsweeps++;
-            if (!conv) st->nconv++;
-            nit++;
-        }
-        st->nit = nit;
-    }
-    for (int k = 0; k < 2; k++) {
-        st->dbcr[k] = dbcr[k];
-        st->dbct[k] = dbct[k];
-        st->dbcn[k] = dbcn[k];
-    }
-    if (st->defer_slot == 1 || st->defer_slot == 2) {
-        if (!c->mbox) return fail(c, PLFX_ERR_UNSUPPORTED, "deferred results need the pinned mailbox (PLFX_MAILBOX=0 is set)");
-        c->fin_defer = st->defer_slot - 1;
-    }
-    return plfx_finish_step(c, u_at, f_at, sums18);
-}
-
-int plfx_set_finish_set(plfx_ctx *c, int n, const int32_t *idx)
-{
-    if (!c || !c->u) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (n < 0 || (n > 0 && !idx)) return fail(c, PLFX_ERR_ARG, "bad argument");
-    for (int k = 0; k < n; k++)
-        if (idx[k] < 0 || idx[k] >= c->ndof) return fail(c, PLFX_ERR_ARG, "idx[%d] out of range", k);
-    HIPCHK(c, stream_sync(c));
-    dfree(c->fin_idx);
-    dfree(c->fin_dev);
-    c->fin_pin_n = 0;  // slots are re-allocated for the new set at the next deferred step
-    c->fin_pending[0] = c->fin_pending[1] = false;
-    if (c->fin_host) hipHostFree(c->fin_host);
-    c->fin_host = nullptr;
-    int rc;
-    if ((rc = dalloc(c, &c->fin_idx, (size_t)std::max(n, 1)))) return rc;
-    if ((rc = dalloc(c, &c->fin_dev, (size_t)2 * n + 18))) return rc;
-    HIPCHK(c, hipHostMalloc((void **)&c->fin_host, ((size_t)2 * n + 18) * 8));
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(c->fin_idx, idx, (size_t)4 * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, stream_sync(c));
-    c->fin_n = n;
-    return PLFX_OK;
-}
-
-int plfx_finish_step(plfx_ctx *c, double *u_at, double *f_at, double *sums18)
-{
-    if (!c || !c->fin_dev) return c ? fail(c, PLFX_ERR_STATE, "set_finish_set first") : PLFX_ERR_STATE;
-    if (!c->assembled) return fail(c, PLFX_ERR_STATE, "assemble first");
-    if (res_complete(c, "finish_step")) return PLFX_ERR_STATE;
-    // plfx_update_state with calc_global's element sums fused into the state-update kernel (one pass over the state)
-    const size_t nd = c->ndof;
-    int rc = 0;
-    const bool kdu_done = c->spec_kdu && c->spec_h0 == 0 && c->spec_h1 == 0 && !c->strip.on;   // (ran behind the last sweep's flags)
-    c->spec_setup = c->spec_kdu = false;
-    if (kdu_done)   // u += du, f += K du happened in that pass
-        c->n_spec_kdu++;
-    else if (!comm_active(c) && !c->strip.on)   // K du over all DOFs (reaction forces, model.py:1384) with the two updates in its epilogue
-        LAUNCH_OP2(k_spmv, 3, matfree(c), dim3(c->grid_nodes), c->op, 0, c->nnode, (const double2 *)c->du, nullptr, (double2 *)c->u,
-                   (double2 *)c->f, nullptr, nullptr, nullptr, 0, nullptr, (CgScalars *)nullptr, 0, 0, 0);
-    else {
-        if ((rc = plain_spmv(c, c->du, c->q))) return rc;
-        hipLaunchKernelGGL(k_axpy_uf, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->q, c->u, c->f);
-    }
-    const int g = grid_for(c->nel, SUMPART);
-    bool swap;
-    if ((rc = finish_mode(c, &swap))) return rc;
-    if (plane_active(c)) {   // 
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state_plane<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
-                           c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
-                           tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, c->part_g);
-        c->n_plane_updates++;
-    } else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<1>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls, c->ncls,
-                           c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, (const double2 *)c->u, c->sig, c->epl,
-                           tan_store(c), c->res_sig, c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, c->part_g,
-                           c->strip.on ? c->strip.eown_lo : 0, c->strip.on ? c->strip.eown_hi : 0x7fffffff);
-    finish_done(c, swap);
-    const int n = c->fin_n;
-    const int tot = 2 * n + 18;
-    const int sl = c->fin_defer;  // >= 0: post into that pinned slot and return without waiting (plfx_finish_fetch collects)
-    c->fin_defer = -1;
-    if (sl >= 0 && c->fin_pin_n < tot) {
-        HIPCHK(c, stream_sync(c));
-        for (int q = 0; q < 2; q++) {
-            if (c->fin_pin[q]) hipHostFree(c->fin_pin[q]);
-            c->fin_pin[q] = nullptr;
-            HIPCHK(c, hipHostMalloc((void **)&c->fin_pin[q], (size_t)8 * tot, hipHostMallocMapped | hipHostMallocCoherent));
-            if (!c->fin_box[q]) {
-                HIPCHK(c, hipHostMalloc((void **)&c->fin_box[q], sizeof(CgMbox), hipHostMallocMapped | hipHostMallocCoherent));
-                memset(c->fin_box[q], 0, sizeof(CgMbox));
-            }
-            c->fin_pending[q] = false;
-        }
-        c->fin_pin_n = tot;
-    }
-    // Deferred and no all-reduce pending: the gather / reduction kernels write the pinned slot themselves (32 + 32 + 18 blocks
-    // instead of one workgroup pushing 131 KB through PCIe: 25 -> 4 us on the stream at 1024^2) and the post only publishes the
-    // sequence number -- their stores are visible to the host before the post kernel starts (kernel boundary on one stream)
-    static const bool direct_ok = !(getenv("PLFX_FINISH_DIRECT") && atoi(getenv("PLFX_FINISH_DIRECT")) == 0);
-    const bool direct = sl >= 0 && direct_ok && !comm_active(c);
-    double *out = direct ? c->fin_pin[sl] : c->fin_dev;
-    // boundary values of u and f and the 18 row sums: independent, one launch (the first blocks gather, the last 18 reduce)
-    hipLaunchKernelGGL(k_finish_out, dim3((n + BLOCK - 1) / BLOCK + 18), dim3(BLOCK), 0, c->stream, n, c->fin_idx, (const double *)c->u,
-                       (const double *)c->f, out, out + n, (const double *)c->part_g, 18, g, out + 2 * (size_t)n);
-    HIPCHK(c, hipGetLastError());
-    if (comm_active(c) &&  // element sums of the whole mesh (calc_global, model.py:1473-1511)
-        (rc = allreduce(c, c->fin_dev + 2 * (size_t)n, 18, NCCL_FLOAT64, NCCL_SUM, "sums")))
-        return rc;
-    if (sl >= 0) {
-        // a slot that was never collected (caller left its loop early) is simply overwritten: the sequence number tells
-        // plfx_finish_fetch which post it is waiting for
-        const unsigned long long seq = ++c->fin_seq[sl];
-        hipLaunchKernelGGL(k_mbox_post, dim3(1), dim3(BLOCK), 0, c->stream, c->fin_dev, direct ? 0 : tot, c->fin_pin[sl],
-                           c->fin_box[sl], seq);
-        HIPCHK(c, hipGetLastError());
-        c->fin_pending[sl] = true;
-        return PLFX_OK;
-    }
-    if ((rc = fetch_results(c, c->fin_dev, 2 * n + 18, c->fin_host))) return rc;
-    if (u_at && n > 0) memcpy(u_at, c->fin_host, (size_t)8 * n);
-    if (f_at && n > 0) memcpy(f_at, c->fin_host + n, (size_t)8 * n);
-    if (sums18) memcpy(sums18, c->fin_host + 2 * (size_t)n, 18 * 8);
-    return PLFX_OK;
-}
-
-int plfx_finish_fetch(plfx_ctx *c, int slot, double *u_at, double *f_at, double *sums18)
-{
-    if (!c || !c->fin_dev) return c ? fail(c, PLFX_ERR_STATE, "set_finish_set first") : PLFX_ERR_STATE;
-    if (slot < 0 || slot > 1 || !c->fin_pending[slot]) return fail(c, PLFX_ERR_STATE, "no deferred results in slot %d", slot);
-    int rc = mbox_wait(c, c->fin_seq[slot], c->fin_box[slot]);
-    if (rc) return rc;
-    c->fin_pending[slot] = false;
-    const int n = c->fin_n;
-    const double *h = c->fin_pin[slot];
-    if (u_at && n > 0) memcpy(u_at, h, (size_t)8 * n);
-    if (f_at && n > 0) memcpy(f_at, h + n, (size_t)8 * n);
-    if (sums18) memcpy(sums18, h + 2 * (size_t)n, 18 * 8);
-    return PLFX_OK;
-}
-
-namespace {
+namespace plfx {
+namespace host {
 
 // launch k_cg_check and fetch the scalars: through the pinned mailbox (host spins on the sequence number) or, without
 // it, by a device->host copy + stream synchronisation
@@ -5942,8 +4873,7 @@ void solve_debug_dump(plfx_ctx *c, const SolveRun &s)
             {
                 double *tmp = nullptr;
                 if (!dalloc(c, &tmp, 21 * n)) {
-                    hipLaunchKernelGGL(k_tangent_expand, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
-                                       c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), tmp, 0);
+                    launch_tangent_expand(c, tmp, 0);
                     hipStreamSynchronize(c->stream);
                     for (int k = 0; k < 21; k++) hipMemcpy(&v[k], tmp + k * n + e, 8, hipMemcpyDeviceToHost);
                     dfree(tmp);
@@ -6082,485 +5012,15 @@ int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *ite
     return solve_finish(c, s, rtol, iters, relres);
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace plfx
+
+extern "C" {
 
 int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double *relres)
 {
     if (!c || !c->bc_set) return c ? fail(c, PLFX_ERR_STATE, "apply_bc first") : PLFX_ERR_STATE;
     return solve_impl(c, rtol, maxit, warm, -1, iters, relres);
-}
-
-// ------------------------------------------------------------------------------ non-linear driver pieces
-static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq)
-{
-    if (int rct = tex_field_check(c)) return rct;
-    // (flags / bflags are left zeroed by the k_sweep_flags of the previous sweep)
-    // every plastic element's res_sig is written below: the buffer is a field of its own again, whatever it held
-    c->res_is_sig = false;
-    c->res_fresh = true;
-    // Armed by plfx_load_step alone (plfx_sweep from anywhere else stores everything): if this sweep changes a tangent, the loop
-    // there launches another one before anything reads res_sig, res_depl or fyn.  One GPU, no strip, no communicator.
-    // (k_sweep_light<1> and <2> honour it: only a model with one of their materials is armed)
-    const int dead = (c->dead_arm && c->dead_stores && !comm_active(c) && !c->strip.on && !wh_seq && (c->has_analytic || c->has_princ)) ? 1 : 0;
-    c->dead_arm = false;
-    c->res_partial = dead != 0;   // (until the final flags are known below; an error return on the way leaves it standing)
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-#define SWEEP_ARGS(lds) c->dmat, c->nmat, c->dcls, c->ncls, lds, c->nel, c->e0, c->dconn, c->dcls_id,          \
-                        (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, \
-                        c->res_sig, c->res_depl, c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list
-    // phase 1 per material kind present (the first launched instantiation also clears fyn of elastic elements)
-    int first = 1;
-    const unsigned fast = c->svc_row_all;   // these materials run on the row kernels, the thread-per-element kernels skip them
-    const bool svc_thread = c->has_svc && (c->svc6_mask & ~fast);
-    const int grid_r = std::max(1, std::min((c->nel + 31) / 32, 1024));   // 16 lanes per element: 32 elements per block and round
-#define ROW_ARGS c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,  \
-                  c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,       \
-                  c->max_steps, nit, c->flags, c->bflags, c->heavy_list
-    if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh && !c->svc_cols_mask)) {
-        if (plane_active(c)) {   // (the same timing family)
-            hipLaunchKernelGGL(k_sweep_light_plane, dim3(plane_sweep_grid(c)), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead);
-            c->n_plane_sweeps++;
-        } else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                               SWEEP_ARGS(0), first, 0u, dead);
-        first = 0;
-    }
-    if (c->has_princ) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<2>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), first, 0u, dead);
-        first = 0;
-    }
-    if (c->has_barlat) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<5>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                           SWEEP_ARGS(0), first, 0u, 0);
-        first = 0;
-    }
-    if (svc_thread) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, fast, 0);
-        first = 0;
-        c->n_svc_thread_launches++;
-    }
-    if (fast) {
-        for (int k = 0; k < c->nmat; k++)   // one launch per material: its tables fill the LDS
-            if ((fast >> k) & 1u) {
-                LAUNCH_ROW2(c, k, (const int32_t *)c->tex_ids, k_sweep_svc_row, 0, dim3(grid_r), ROW_ARGS, first, k);
-                first = 0;
-                c->n_svc_row_launches++;
-            }
-    }
-    if (c->has_svc3) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, 0u, 0);
-        first = 0;
-    }
-    // work-hardening SVC materials: one wave per element (PLFX_WH_WAVE=0: one thread per element, rounds 2-3)
-    const bool wh_wave = !(getenv("PLFX_WH_WAVE") && atoi(getenv("PLFX_WH_WAVE")) == 0);   // read per sweep: tests compare the two forms
-    const int grid_wh = std::max(1, std::min((c->nel + 3) / 4, SWEEP_SLOTS));  // one bflags slot pair per block (the kernel grid-strides)
-    if (c->has_svcwh && wh_wave) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_wh_wave<0>), dim3(grid_wh), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
-                           c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn, c->dcls_id,
-                           (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
-                           c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list, first, c->kh_el,
-                           wh_seq ? c->kh_out : (double *)nullptr, wh_seq ? c->kh_touch : (int32_t *)nullptr);
-        first = 0;
-    } else if (c->has_svcwh) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<7>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, SWEEP_ARGS(c->svc_lds_need), first, 0u, 0, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
-                           wh_seq ? c->kh_touch : (int32_t *)nullptr);
-        first = 0;
-    }
-    tim_end(c, ev);  // family 0: the streaming phase (one launch per material kind present)
-    // phase 2 reads the list length from the device; an empty list costs one empty launch per kind.  Single GPU with the mailbox:
-    // after a sweep whose list was empty the launches are left out, k_sweep_flags reports a list that turned up after all, and
-    // the launches follow then (one more round trip, in the first sweep that grows a list: DESIGN 22)
-    const bool mb_flags = !comm_active(c) && c->mbox && c->mb_cap >= 2;
-    const bool skip_heavy = mb_flags && !c->strip.on && c->last_heavy == 0;
-    auto launch_phase2 = [&]() {
-        tim_begin(c, 6, &ev);  // family 6: the compacted 50-sub-step corrector
-        if (c->has_analytic)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                               SWEEP_ARGS(0), 0u);
-        if (c->has_princ)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<2>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                               SWEEP_ARGS(0), 0u);
-        if (c->has_barlat)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<5>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
-                               SWEEP_ARGS(0), 0u);
-        if (svc_thread)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<3>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                               c->stream, SWEEP_ARGS(c->svc_lds_need), fast);
-        if (fast)
-            for (int k = 0; k < c->nmat; k++)
-                if ((fast >> k) & 1u) LAUNCH_ROW2(c, k, (const int32_t *)c->tex_ids, k_sweep_svc_row, 1, dim3(grid_r), ROW_ARGS, 0, k);
-        if (c->has_svc3)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<6>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                               c->stream, SWEEP_ARGS(c->svc_lds_need), 0u);
-        if (c->has_svcwh && wh_wave)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_wh_wave<1>), dim3(grid_wh), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
-                               c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn, c->dcls_id,
-                               (const double2 *)c->du, c->sig, c->epl, tan_store(c), c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl,
-                               c->fyn, c->max_steps, nit, c->flags, c->bflags, c->heavy_list, 0, c->kh_el,
-                               wh_seq ? c->kh_out : (double *)nullptr, wh_seq ? c->kh_touch : (int32_t *)nullptr);
-        else if (c->has_svcwh)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_heavy<7>), dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c),
-                               c->stream, SWEEP_ARGS(c->svc_lds_need), 0u, c->kh_el, wh_seq ? c->kh_out : (double *)nullptr,
-                               wh_seq ? c->kh_touch : (int32_t *)nullptr);
-        tim_end(c, ev);
-    };
-#undef SWEEP_ARGS
-#undef ROW_ARGS
-    if (skip_heavy)
-        c->n_heavy_skipped++;
-    else
-        launch_phase2();
-    int h[4];
-    const bool spec = c->spec_arm && !comm_active(c) && c->mbox && c->mb_cap >= 2 && matfree(c) && !c->strip.on && c->assembled;
-    c->spec_arm = false;
-    if (mb_flags) {   // single GPU: the flags kernel posts its results itself
-        const unsigned long long seq = ++c->mbox_seq;
-        hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4,
-                           reinterpret_cast<int *>(c->mb_buf), c->mbox, seq, spec ? c->flags + 8 : (int *)nullptr,
-                           spec ? c->spec_sc : (CgScalars *)nullptr, skip_heavy ? 1 : 0);
-        if (spec) {
-            // what the host would enqueue after reading the flags, enqueued now (the round trip overlaps it): the set-up pass of
-            // plfx_assemble if a tangent changed, else -- if every element converged as well -- the K du of plfx_finish_step
-            KOp live = c->op;
-            live.M = c->Mel;
-            LAUNCH_SETUP(0, live, (double2 *)c->diag,
-                               c->Mop, (mg_active(c) && level_plain(c->mg[0])) ? c->mg[1].Mel : (double *)nullptr, (const double2 *)nullptr, 0, 0,
-                               (double2 *)nullptr, 0x7fffffff, (const int *)(c->flags + 8));
-            // (u += du and f += K du in the same pass, MODE 3: the predicate is exactly "plfx_finish_step comes next")
-            LAUNCH_OP2(k_spmv, 3, matfree(c), dim3(c->grid_nodes), c->op, 0, c->nnode, (const double2 *)c->du, nullptr, (double2 *)c->u,
-                       (double2 *)c->f, nullptr, nullptr, nullptr, 0, nullptr, c->spec_sc, 0, 0, 0);
-            c->spec_was_clean = !c->M_dirty;
-            c->spec_setup = c->spec_kdu = true;
-        }
-        HIPCHK(c, hipGetLastError());
-        const int rcw = mbox_wait(c, seq);
-        if (rcw) return rcw;
-        memcpy(h, c->mb_buf, sizeof(h));
-        if (skip_heavy && h[0] < 0) {
-            // elements need the corrector after all: the flags kernel left its inputs alone and told the two speculative kernels to
-            // do nothing; the corrector launches and an unarmed flags kernel follow, and their results are the sweep's
-            c->n_heavy_recovered++;
-            c->spec_setup = c->spec_kdu = false;
-            launch_phase2();
-            const unsigned long long seq2 = ++c->mbox_seq;
-            hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4,
-                               reinterpret_cast<int *>(c->mb_buf), c->mbox, seq2, (int *)nullptr, (CgScalars *)nullptr, 0);
-            HIPCHK(c, hipGetLastError());
-            const int rcw2 = mbox_wait(c, seq2);
-            if (rcw2) return rcw2;
-            memcpy(h, c->mb_buf, sizeof(h));
-        }
-        c->spec_h0 = h[0];
-        c->spec_h1 = h[1];
-        // the speculative set-up pass rewrote c->diag exactly if the flags kernel it sits behind reported a changed tangent
-        // (its predicate flags[8] is "h[0] == 0" of that kernel; after a recovery it was told to skip, and plfx_assemble launches)
-        if (spec && h[0]) c->dinv_ok = false;
-    } else {
-        hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4);
-        HIPCHK(c, hipGetLastError());
-        if (comm_active(c)) {  // changed / not-converged / list length of the whole mesh: no host-side collective needed
-            // strip: the counts of rewritten tangents / sub-stepped elements stay local (halo elements are replicas)
-            const int rca = allreduce(c, c->flags + 4, c->strip.on ? 2 : 4, NCCL_INT32, NCCL_SUM, "flags");
-            if (rca) return rca;
-        }
-        const int rcf = fetch_results(c, reinterpret_cast<const double *>(c->flags + 4), 2, reinterpret_cast<double *>(h));
-        if (rcf) return rcf;
-    }
-    if (h[0] || !c->reuse) {  // the replicated generators are exchanged only when some rank rewrote some of its own
-        int rcm = sync_M(c);
-        if (rcm) return rcm;
-    }
-    if (changed) *changed = h[0];
-    if (conv) *conv = h[1] ? 0 : 1;
-    if (h[0]) c->M_dirty = true;  // generators are rewritten exactly where a tangent changed (finish_element)
-    c->n_sweeps++;
-    c->n_tangents_rewritten += h[3];
-    // the final flags (after a corrector recovery, if there was one): a changed tangent in an armed sweep = fields left partial
-    c->res_partial = dead && h[0];
-    if (dead) {
-        c->n_dead_sweeps++;
-        c->n_dead_tangents += h[3];
-    }
-    c->last_heavy = h[2];
-    return PLFX_OK;
-}
-
-// Sweep of a model with a work-hardening SVC material in the reference's semantics: ONE hardening modulus per Material object,
-// handed from element to element in index order (material.py:808-814, model.py:1340-1359).  The entry modulus of an element is
-// the exit modulus of the last element before it whose call evaluated a gradient (else what the material held when the sweep
-// began) -- a chain the data-parallel sweep resolves as a fixed point: sweep with guessed entry values (those of the previous
-// sweep), derive the entry values that sweep implies (k_wh_entry), repeat while any element's entry value changed.  What a
-// sweep rewrites besides its outputs -- tangents and stiffness generators -- is restored from a snapshot before every
-// repetition, so the last pass IS the sequential loop's sweep, bit for bit in its inputs.  A handful of passes in practice
-// (an entry value only enters the yield check of its call, material.py:259-265 via get_sflow).
-static int sweep_wh_sequential(plfx_ctx *c, int nit, int *changed, int *conv)
-{
-    int rc;
-    const size_t ne = c->nel;
-    const int nblk = (int)((ne + BLOCK - 1) / BLOCK);
-    if (!c->kh_out) {
-        if ((rc = dalloc(c, &c->kh_out, ne)) || (rc = dalloc(c, &c->kh_new, ne)) || (rc = dalloc(c, &c->kh_touch, ne)) ||
-            (rc = dalloc(c, &c->wh_bmax, (size_t)nblk)) || (rc = dalloc(c, &c->wh_cnt, 4)) ||
-            (rc = dalloc(c, &c->wh_snap_el, tan_words(ne))) || (rc = dalloc(c, &c->wh_snap_M, (size_t)6 * c->nel_total)) ||
-            (rc = dalloc(c, &c->wh_snap_ms, ne)))
-            return rc;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->wh_snap_el, c->tan_buf, tan_words(ne) * 8, hipMemcpyDeviceToDevice, c->stream));  // tags and factors too
-    HIPCHK(c, hipMemcpyAsync(c->wh_snap_M, c->Mel, (size_t)6 * c->nel_total * 8, hipMemcpyDeviceToDevice, c->stream));
-    // max_steps is a running maximum (sweep_epilogue): passes that ran with entry moduli the chain does not confirm must not leave their counts
-    HIPCHK(c, hipMemcpyAsync(c->wh_snap_ms, c->max_steps, ne * 4, hipMemcpyDeviceToDevice, c->stream));
-    const int64_t sw0 = c->n_sweeps, tr0 = c->n_tangents_rewritten;
-    int64_t tr_before = tr0;
-    bool any_changed = false;
-    const bool dirty0 = c->M_dirty;
-    int32_t last[16];
-    // every pass confirms at least one more element of the chain (the first one whose entry value was wrong now runs with the
-    // right one, everything before it is final), so ne + 2 passes always reach the sequential loop's sweep; two or three do
-    // on every trace seen so far (the exit modulus of a call hardly depends on its entry modulus)
-    // ... but a pass is a whole sweep + three snapshot restores + host round trips: a chain that resolves one element per pass on
-    // a large mesh would cost O(ne) sweeps without a word.  Cap (PLFX_WH_MAXPASS, default 512; never more than ne + 2): beyond it
-    // the sweep is reported unresolved (plfx_wh_info) and says so on stderr -- its tangents are those of the last pass
-    static const int wh_cap = getenv("PLFX_WH_MAXPASS") ? std::max(2, atoi(getenv("PLFX_WH_MAXPASS"))) : 512;
-    const int max_pass = (int)std::min<size_t>(ne + 2, (size_t)wh_cap);
-    int pass = 0;
-    for (;; pass++) {
-        if (pass > 0) {
-            HIPCHK(c, hipMemcpyAsync(c->tan_buf, c->wh_snap_el, tan_words(ne) * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->Mel, c->wh_snap_M, (size_t)6 * c->nel_total * 8, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->max_steps, c->wh_snap_ms, ne * 4, hipMemcpyDeviceToDevice, c->stream));
-        }
-        int ch = 0, cv = 0;
-        tr_before = c->n_tangents_rewritten;
-        if ((rc = sweep_once(c, nit, &ch, &cv, true))) return rc;
-        any_changed = (ch != 0);   // of the accepted (last) pass: the earlier ones are undone by the snapshot
-        if (changed) *changed = ch;
-        if (conv) *conv = cv;
-        // entry values this pass implies
-        HIPCHK(c, hipMemcpyAsync(c->kh_new, c->kh_el, ne * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->wh_cnt, 0, 16, c->stream));
-        for (int m = 0; m < c->nmat && m < 16; m++) {
-            last[m] = -1;
-            if (c->hmat[m].kind != 7) continue;
-            hipLaunchKernelGGL(k_wh_blockmax, dim3(nblk), dim3(BLOCK), 0, c->stream, c->nel, m, c->dcls, c->dcls_id, c->kh_touch, c->wh_bmax);
-            hipLaunchKernelGGL(k_wh_scan, dim3(1), dim3(BLOCK), 0, c->stream, nblk, c->wh_bmax, c->wh_cnt + 1);
-            hipLaunchKernelGGL(k_wh_entry, dim3(nblk), dim3(BLOCK), 0, c->stream, c->nel, m, c->dcls, c->dcls_id, c->kh_touch, c->wh_bmax,
-                               (const double *)c->kh_out, c->wh_carry[m], (const double *)c->kh_el, c->kh_new, c->wh_cnt);
-            HIPCHK(c, hipGetLastError());
-            int32_t h2[2];
-            HIPCHK(c, hipMemcpyAsync(h2, c->wh_cnt, 8, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, stream_sync(c));
-            last[m] = h2[1];   // (h2[0] accumulates over the materials)
-        }
-        int32_t nch = 0;
-        HIPCHK(c, hipMemcpyAsync(&nch, c->wh_cnt, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_sync(c));
-        c->n_wh_passes++;
-        if (getenv("PLFX_WH_DEBUG")) {
-            std::vector<double> ko(ne), ki(ne);
-            std::vector<int32_t> tc(ne);
-            hipMemcpy(ko.data(), c->kh_out, ne * 8, hipMemcpyDeviceToHost);
-            hipMemcpy(ki.data(), c->kh_el, ne * 8, hipMemcpyDeviceToHost);
-            hipMemcpy(tc.data(), c->kh_touch, ne * 4, hipMemcpyDeviceToHost);
-            int nt = 0;
-            double kmax = 0., imax = 0.;
-            for (size_t e = 0; e < ne; e++) nt += tc[e], kmax = std::max(kmax, ko[e]), imax = std::max(imax, ki[e]);
-            fprintf(stderr, "[wh] sweep %lld pass %d: %d entries changed, %d touched, max entry %.6g, max exit %.6g, last touched %d, carry %.6g\n",
-                    (long long)c->n_wh_sweeps, pass, nch, nt, imax, kmax, last[0], c->wh_carry[0]);
-        }
-        if (nch == 0) break;
-        if (pass + 1 >= max_pass) {  // (ne + 2 passes always resolve the chain; the cap above may end it earlier)
-            if (c->n_wh_unresolved++ == 0)
-                fprintf(stderr, "[plfx] work-hardening carry chain not resolved after %d passes (%d entry moduli still changed): "
-                                "PLFX_WH_MAXPASS raises the cap (plfx_wh_info counts such sweeps)\n", pass + 1, (int)nch);
-            break;
-        }
-        std::swap(c->kh_el, c->kh_new);
-    }
-    // the material objects now hold what their last gradient evaluation of this sweep left
-    for (int m = 0; m < c->nmat && m < 16; m++)
-        if (c->hmat[m].kind == 7 && last[m] >= 0)
-            HIPCHK(c, hipMemcpy(&c->wh_carry[m], c->kh_out + last[m], 8, hipMemcpyDeviceToHost));
-    c->kh_out_valid = true;
-    c->n_wh_sweeps++;
-    c->n_sweeps = sw0 + 1;   // one sweep of the load-step loop, however many passes it took
-    c->n_tangents_rewritten = tr0 + (c->n_tangents_rewritten - tr_before);   // ... and the rewrites of its last pass
-    c->M_dirty = dirty0 || any_changed;   // (sweep_once set it in passes the snapshot has undone)
-    return PLFX_OK;
-}
-
-int plfx_sweep(plfx_ctx *c, int nit, int *changed, int *conv)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (c->n_noflow) return fail(c, PLFX_ERR_UNSUPPORTED, "a Tresca / Barlat material without flow rule is loaded (material.py:822-825)");
-    c->spec_setup = c->spec_kdu = false;
-    if (wh_sequential(c)) return sweep_wh_sequential(c, nit, changed, conv);
-    return sweep_once(c, nit, changed, conv, false);
-}
-
-// moduli calc_scf reads (model.py:1036-1067: calc_yf / ML_full_yf -> get_sflow with the value the material holds NOW): per
-// point, or -- sequential carry -- the material object's current value for every element of that material
-static const double *scf_moduli(plfx_ctx *c)
-{
-    if (!wh_sequential(c)) return c->kh_el;
-    if (!c->kh_new && dalloc(c, &c->kh_new, (size_t)c->nel)) return c->kh_el;
-    WhCarry w;
-    for (int m = 0; m < 16; m++) w.v[m] = c->wh_carry[m];
-    hipLaunchKernelGGL(k_wh_fill, dim3(grid_for(c->nel)), dim3(BLOCK), 0, c->stream, c->nel, c->dcls, c->dcls_id, w, c->kh_new);
-    return c->kh_new;
-}
-
-int plfx_set_wh_mode(plfx_ctx *c, int sequential)
-{
-    if (!c) return PLFX_ERR_STATE;
-    c->wh_mode = sequential ? 1 : 0;
-    c->kh_out_valid = false;
-    return PLFX_OK;
-}
-
-int plfx_wh_info(plfx_ctx *c, int *sequential_in_use, int64_t *sweeps, int64_t *passes, int64_t *unresolved)
-{
-    if (!c) return PLFX_ERR_STATE;
-    if (unresolved) *unresolved = c->n_wh_unresolved;
-    if (sequential_in_use) *sequential_in_use = wh_sequential(c) ? 1 : 0;
-    if (sweeps) *sweeps = c->n_wh_sweeps;
-    if (passes) *passes = c->n_wh_passes;
-    return PLFX_OK;
-}
-
-int plfx_wh_carry(plfx_ctx *c, int mat, const double *set, double *get)
-{
-    if (!c || mat < 0 || mat >= c->nmat || mat >= 16) return c ? fail(c, PLFX_ERR_ARG, "material %d out of range", mat) : PLFX_ERR_STATE;
-    if (set) c->wh_carry[mat] = *set;
-    if (get) *get = c->wh_carry[mat];
-    return PLFX_OK;
-}
-
-// calc_scf per element: hh and multiplicity of every owned element into scf_hh / scf_mult (sld at small + 32)
-static void launch_scf_elements(plfx_ctx *c)
-{
-    const unsigned fast = c->svc_row_all;
-    hipLaunchKernelGGL(k_scf_elements, dim3(c->grid_el), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
-                       c->dmat, c->nmat, c->dcls, c->ncls, c->svc_lds_need, c->nel, c->e0, c->dconn,
-                       c->dcls_id, (const double2 *)c->du, c->sig, c->epl, tan_store(c),
-                       c->small + 32, c->scf_hh, c->scf_mult, scf_moduli(c), fast);
-    for (int k = 0; k < c->nmat; k++)
-        if ((fast >> k) & 1u)
-            LAUNCH_ROW1(c, k, (const int32_t *)c->tex_ids, k_scf_row, dim3(std::max(1, std::min((c->nel + 31) / 32, 1024))),
-                       c->dmat, c->nmat, c->dcls, k, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                       c->sig, c->epl, tan_store(c), c->small + 32, c->scf_hh, c->scf_mult);
-}
-
-int plfx_scf_stats(plfx_ctx *c, const double *sld, double *sum, double *sumsq_c, double *minv,
-                   int64_t *count, double mean_in, int pass)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    const int g = grid_for(c->nel, 256);
-    if (pass == 0) {
-        if (!sld) return fail(c, PLFX_ERR_ARG, "sld required");
-        if (int rct = tex_field_check(c)) return rct;
-        HIPCHK(c, hipMemcpyAsync(c->small + 32, sld, 48, hipMemcpyHostToDevice, c->stream));
-        launch_scf_elements(c);
-        HIPCHK(c, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_scf_reduce, dim3(g), dim3(BLOCK), 0, c->stream, c->nel, c->scf_hh, c->scf_mult,
-                       mean_in, pass, c->part_g);
-    HIPCHK(c, hipGetLastError());
-    std::vector<double> h((size_t)3 * g);
-    HIPCHK(c, hipMemcpyAsync(h.data(), c->part_g, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    double s = 0., cnt = 0., mn = 1.e300;
-    for (int b = 0; b < g; b++) {
-        s += h[b];
-        cnt += h[g + b];
-        mn = std::min(mn, h[2 * (size_t)g + b]);
-    }
-    if (pass == 0) {
-        if (sum) *sum = s;
-        if (count) *count = (int64_t)(cnt + 0.5);
-        if (minv) *minv = mn;
-    } else if (sumsq_c) {
-        *sumsq_c = s;
-    }
-    return PLFX_OK;
-}
-
-int plfx_scf_all(plfx_ctx *c, const double *sld, int64_t *count, double *minv, double *sum, double *sumsq_c)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (!sld) return fail(c, PLFX_ERR_ARG, "sld required");
-    if (int rct = tex_field_check(c)) return rct;
-    const int g = grid_for(c->nel, 256);
-    HIPCHK(c, hipMemcpyAsync(c->small + 32, sld, 48, hipMemcpyHostToDevice, c->stream));
-    launch_scf_elements(c);
-    const int elo = c->strip.on ? c->strip.eown_lo : 0, ehi = c->strip.on ? c->strip.eown_hi : 0x7fffffff;
-    hipLaunchKernelGGL(k_scf_reduce, dim3(g), dim3(BLOCK), 0, c->stream, c->nel, c->scf_hh, c->scf_mult, 0., 0,
-                       c->part_g, (const double *)nullptr, elo, ehi);
-    hipLaunchKernelGGL(k_scf_finish, dim3(1), dim3(BLOCK), 0, c->stream, c->part_g, g, 0, c->small + 40);
-    if (comm_active(c)) {  // statistics of the whole mesh: sum, count (SUM) and minimum (MIN), then the global mean
-        int rca = allreduce(c, c->small + 40, 2, NCCL_FLOAT64, NCCL_SUM, "scf sums");
-        if (!rca) rca = allreduce(c, c->small + 42, 1, NCCL_FLOAT64, NCCL_MIN, "scf min");
-        if (rca) return rca;
-        hipLaunchKernelGGL(k_scf_mean, dim3(1), dim3(64), 0, c->stream, c->small + 40);
-    }
-    // second pass with the mean taken from device memory: no host round trip between the passes
-    hipLaunchKernelGGL(k_scf_reduce, dim3(g), dim3(BLOCK), 0, c->stream, c->nel, c->scf_hh, c->scf_mult, 0., 1,
-                       c->part_g, (const double *)(c->small + 43), elo, ehi);
-    hipLaunchKernelGGL(k_scf_finish, dim3(1), dim3(BLOCK), 0, c->stream, c->part_g, g, 1, c->small + 40);
-    if (comm_active(c)) {
-        const int rca = allreduce(c, c->small + 44, 1, NCCL_FLOAT64, NCCL_SUM, "scf squares");
-        if (rca) return rca;
-    }
-    HIPCHK(c, hipGetLastError());
-    double h[5];
-    {
-        const int rcf = fetch_results(c, c->small + 40, 5, h);
-        if (rcf) return rcf;
-    }
-    if (sum) *sum = h[0];
-    if (count) *count = (int64_t)(h[1] + 0.5);
-    if (minv) *minv = h[2];
-    if (sumsq_c) *sumsq_c = h[4];
-    return PLFX_OK;
-}
-
-int plfx_update_state(plfx_ctx *c)
-{
-    if (!c || !c->assembled) return c ? fail(c, PLFX_ERR_STATE, "assemble first") : PLFX_ERR_STATE;
-    if (res_complete(c, "update_state")) return PLFX_ERR_STATE;
-    const size_t nd = c->ndof;
-    int rc = 0;
-    const bool kdu_done = c->spec_kdu && c->spec_h0 == 0 && c->spec_h1 == 0 && !c->strip.on;   // (ran behind the last sweep's flags)
-    c->spec_setup = c->spec_kdu = false;
-    if (kdu_done)   // u += du, f += K du happened in that pass
-        c->n_spec_kdu++;
-    else if (!comm_active(c) && !c->strip.on)   // K du over all DOFs (reaction forces, model.py:1384) with the two updates in its epilogue
-        LAUNCH_OP2(k_spmv, 3, matfree(c), dim3(c->grid_nodes), c->op, 0, c->nnode, (const double2 *)c->du, nullptr, (double2 *)c->u,
-                   (double2 *)c->f, nullptr, nullptr, nullptr, 0, nullptr, (CgScalars *)nullptr, 0, 0, 0);
-    else {
-        if ((rc = plain_spmv(c, c->du, c->q))) return rc;
-        hipLaunchKernelGGL(k_axpy_uf, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->q, c->u, c->f);
-    }
-    bool swap;
-    if ((rc = finish_mode(c, &swap))) return rc;
-    if (plane_active(c)) {   // 
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state_plane<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
-                           c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                           (const double2 *)c->u, c->sig, c->epl, tan_store(c), c->res_sig,
-                           c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, (double *)nullptr);
-        c->n_plane_updates++;
-    } else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_update_state<0>), dim3(grid_for(c->nel, MAXPART)), dim3(BLOCK), 0, c->stream,
-                           c->dmat, c->nmat, c->dcls, c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du,
-                           (const double2 *)c->u, c->sig, c->epl, tan_store(c), c->res_sig,
-                           c->res_depl, c->nonlin ? 1 : 0, swap ? 1 : 0, (double *)nullptr);
-    HIPCHK(c, hipGetLastError());
-    finish_done(c, swap);
-    return PLFX_OK;
 }
 
 int plfx_matvec(plfx_ctx *c, const double *x, double *y)
@@ -6577,118 +5037,6 @@ int plfx_matvec(plfx_ctx *c, const double *x, double *y)
     return PLFX_OK;
 }
 
-int plfx_global_sums(plfx_ctx *c, double *out18)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (!out18) return fail(c, PLFX_ERR_ARG, "null output");
-    if (res_complete(c, "global_sums")) return PLFX_ERR_STATE;
-    const int g = grid_for(c->nel, SUMPART);  // same grid as the fused sums of plfx_finish_step: identical numbers
-    const int rce = ensure_eps(c);
-    if (rce) return rce;
-    hipLaunchKernelGGL(k_global_partials, dim3(g), dim3(BLOCK), 0, c->stream, c->dcls, c->nel, c->dcls_id,
-                       c->sig, c->eps, c->epl, c->part_g);
-    hipLaunchKernelGGL(k_reduce_rows, dim3(18), dim3(BLOCK), 0, c->stream, c->part_g, 18, g, c->small);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out18, c->small, 18 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// Element result fields (Model.field / fields / field_range): reads the state, changes none of it and none of its flags
-int plfx_element_fields(plfx_ctx *c, int nsel, const int32_t *sel, double *out, double *range)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    if (nsel < 0 || (nsel > 0 && !sel)) return fail(c, PLFX_ERR_ARG, "bad selector list");
-    for (int k = 0; k < nsel; k++)
-        if (sel[k] < 0 || sel[k] >= FLD_COUNT) return fail(c, PLFX_ERR_ARG, "unknown field selector %d (sel[%d])", sel[k], k);
-    if (nsel == 0 || (!out && !range)) return PLFX_OK;
-    const size_t ne = c->nel;
-    FieldPlan pl{};
-    int first[FLD_COUNT];   // first position of a selector in the list: the row the kernel writes
-    for (int id = 0; id < FLD_COUNT; id++) first[id] = -1;
-    for (int k = 0; k < nsel; k++)
-        if (first[sel[k]] < 0) first[sel[k]] = k;
-    bool disp = false, strain = false, all_kinds = false;
-    for (int id = 0; id < FLD_COUNT; id++) {
-        if (first[id] < 0) continue;
-        pl.want |= 1u << id;
-        pl.row[id] = first[id];
-        switch (id) {
-        case FLD_STRAIN1: pl.eps_cols |= 1u; strain = true; break;
-        case FLD_STRAIN2: pl.eps_cols |= 2u; strain = true; break;
-        case FLD_STRAIN12: pl.eps_cols |= 32u; strain = true; break;
-        case FLD_ETOT: pl.eps_cols |= 63u; strain = true; break;
-        case FLD_STRESS1: pl.sig_cols |= 1u; break;
-        case FLD_STRESS2: pl.sig_cols |= 2u; break;
-        case FLD_STRESS12: pl.sig_cols |= 32u; break;
-        case FLD_SEQ: case FLD_SEQJ2: pl.sig_cols |= 63u; break;
-        case FLD_PLASTIC1: pl.epl_cols |= 1u; break;
-        case FLD_PLASTIC2: pl.epl_cols |= 2u; break;
-        case FLD_PLASTIC12: pl.epl_cols |= 32u; break;
-        case FLD_PEEQ: pl.epl_cols |= 63u; break;
-        default: disp = true; break;   // ux, uy
-        }
-    }
-    pl.eps_from_u = (strain && c->eps_stale) ? 1 : 0;   // never a stale c->eps; eps_stale and the stored field stay as they are
-    if (pl.eps_from_u) pl.eps_cols = 0;
-    pl.need_u = (disp || pl.eps_from_u) ? 1 : 0;
-    pl.store = out ? 1 : 0;
-    if ((pl.want >> FLD_SEQ) & 1u)
-        for (int m = 0; m < c->nmat; m++) {
-            const int kd = c->hmat[m].kind;
-            if (kd == 2 || kd == 4 || kd == 5 || kd == 6) all_kinds = true;
-        }
-    int rc;
-    if (out && c->fld_cap < (size_t)nsel * ne) {
-        if ((rc = dalloc(c, &c->fld_buf, (size_t)nsel * ne))) return rc;
-        c->fld_cap = (size_t)nsel * ne;
-    }
-    if (range && !c->fld_part && (rc = dalloc(c, &c->fld_part, (size_t)2 * FLD_COUNT * MAXPART))) return rc;
-    const int g = grid_for(ne, MAXPART);
-    EvPair *ev;
-    tim_begin(c, 0, &ev);   // family 0, like the batched point kernels: the kernel alone, without the copies
-    // sig through c->sig at launch time: after an exchange it holds the current stress, the other buffer is scratch
-#define PLFX_FLD_LAUNCH(A, R)                                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_element_fields<A, R>), dim3(g), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls,  \
-                       c->ncls, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->u, c->sig, c->epl, c->eps, pl,        \
-                       c->fld_buf, c->fld_part)
-    if (all_kinds) {
-        if (range) PLFX_FLD_LAUNCH(1, 1); else PLFX_FLD_LAUNCH(1, 0);
-    } else {
-        if (range) PLFX_FLD_LAUNCH(0, 1); else PLFX_FLD_LAUNCH(0, 0);
-    }
-#undef PLFX_FLD_LAUNCH
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    if (out) {
-        for (int k = 0; k < nsel; k++)   // a selector named again: its row once more
-            if (first[sel[k]] != k)
-                HIPCHK(c, hipMemcpyAsync(c->fld_buf + (size_t)k * ne, c->fld_buf + (size_t)first[sel[k]] * ne, 8 * ne,
-                                         hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out, c->fld_buf, (size_t)nsel * ne * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (range) {
-        c->fld_host.resize((size_t)2 * FLD_COUNT * g);
-        HIPCHK(c, hipMemcpyAsync(c->fld_host.data(), c->fld_part, (size_t)2 * FLD_COUNT * g * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, stream_sync(c));
-    if (range)   // at most MAXPART partials per scalar: the last stage on the host
-        for (int k = 0; k < nsel; k++) {
-            const double *pmin = c->fld_host.data() + (size_t)(2 * sel[k]) * g, *pmax = pmin + g;
-            double lo = pmin[0], hi = pmax[0];
-            bool isnan_ = false;
-            for (int b = 0; b < g; b++) {
-                isnan_ = isnan_ || pmin[b] != pmin[b] || pmax[b] != pmax[b];
-                lo = std::min(lo, pmin[b]);
-                hi = std::max(hi, pmax[b]);
-            }
-            range[2 * k] = isnan_ ? std::nan("") : lo;
-            range[2 * k + 1] = isnan_ ? std::nan("") : hi;
-        }
-    return PLFX_OK;
-}
-
-// ------------------------------------------------------------------------------ multi-GPU
 int plfx_comm_info(plfx_ctx *c, int *rank, int *nranks, int *device_collectives)
 {
     if (!c) return PLFX_ERR_ARG;

@@ -11,6 +11,12 @@
 //   k_update_state    model.py:1383-1392
 // All reductions are two-stage with a fixed grid and are summed in index order, so results are
 // bitwise reproducible run to run.
+//
+// Owners: the library is several translation units and every kernel belongs to one.  A kernel template is
+// compiled where it is launched.  A kernel that is NO template is compiled wherever its definition is seen, so each stands
+// under #ifdef PLFX_UNIT_<OWNER>, the subsystem whose host code launches it; a unit defines the groups it owns before its first
+// include.  A new non-template kernel goes under the guard of the subsystem that launches it.  One left without a guard does
+// not pass unnoticed: its host stub is then defined in every object and the link of libplfx.so fails with a multiple definition.
 #pragma once
 #include "plfx_device.hpp"
 #include "plfx_rayroot.hpp"
@@ -343,6 +349,7 @@ k_response_batch(const MatDev *gmat, int nmat, int lds_doubles, int n, const int
 // reference's point function returns for a (6,) stress of a principal-stress material -- seq from sig_princ's order, the
 // deviator from the Voigt normals -- and differs from the principal-space normal that epl_dot / C_tan use (princ_fgrad)
 // as soon as the state has shear.
+#ifdef PLFX_UNIT_MATERIALS
 __global__ void __launch_bounds__(BLOCK)
 k_fgrad_seq(const MatDev *gmat, int mat, int n, const double *sig_in, const double *seq_in, double *out)
 {
@@ -449,6 +456,7 @@ k_point_eval(const MatDev *gmat, int nmat, int lds_doubles, int what, int mat, i
         }
     }
 }
+#endif
 
 // Material.calc_hessian (material.py:860-972) of the SVC material `mat` (NF = 6: PLFX_SVC6, NF = 15: PLFX_SVC_WH) on n points:
 // the 6 x 6 block of the Hessian of the decision function w.r.t. the stress features,
@@ -701,6 +709,7 @@ __device__ __forceinline__ void row_gather16(double y, double (&v)[16])   // v[L
     v[N] = YfSvcRow<1>::row_bcast<N>(y);
     if constexpr (N < 15) row_gather16<N + 1>(y, v);
 }
+#ifdef PLFX_UNIT_MATERIALS
 __global__ void __launch_bounds__(CY_BLOCK)
 k_committee_yf(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int nmem, const CommitteeArgs a, int n,
                const double *__restrict__ su_in, double *__restrict__ yf, double *__restrict__ mean_out,
@@ -793,6 +802,7 @@ k_committee_yf(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int n
         }
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // element strain from nodal values: (sum_gp B) u_e   (model.py:387-411)
@@ -1110,6 +1120,7 @@ __device__ void mbox_publish(CgMbox *mb, unsigned long long seq);   // (defined 
 // end of the load step only if the K-iteration loop ends here (spec->done = 0: nothing changed and every element converged)
 struct CgScalars;
 __device__ void spec_set(CgScalars *spec, int done);
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK) k_sweep_flags(int *__restrict__ bflags, int *__restrict__ flags, int *__restrict__ out,
                                                        int *__restrict__ pin = nullptr, CgMbox *mb = nullptr, unsigned long long seq = 0ull,
                                                        int *__restrict__ skip_setup = nullptr, CgScalars *spec = nullptr,
@@ -1176,6 +1187,7 @@ __global__ void __launch_bounds__(BLOCK) k_sweep_flags(int *__restrict__ bflags,
         flags[2] = 0;
     }
 }
+#endif
 
 // Material sweep over the owned elements (model.py:1340-1359), phase 1: elastic and one-step plastic
 // elements are finished here (streaming, HBM-bound); elements whose increment must be sub-divided are
@@ -1270,7 +1282,7 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
     post_block_flags(changed, nconv, bflags);
 }
 
-// k_sweep_light<1> of a plane model whose materials are all elastic or analytic Hill / J2 (plane_cols in plfx.hip):
+// k_sweep_light<1> of a plane model whose materials are all elastic or analytic Hill / J2 (plane_cols in plfx_host.hpp):
 // the yz / zx shears -- columns 3 and 4 of sig, epl, res_sig, res_depl, rows 4 and 5 of the tangent factors -- are zero in
 // memory and the return mapping keeps them zero, so they are neither loaded nor stored; the arithmetic is the one above, on
 // zeros held in registers.  A kernel of its own and not a parameter of k_sweep_light: a shared body behind two entry points
@@ -1278,10 +1290,11 @@ k_sweep_light(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restr
 // differs from the text above: the PLANE forms of sweep_in_load and sweep_epilogue, KIND = 1 written out (no SVC tables,
 // no hardening modulus per material point), and the tile loop, which is pipelined a whole tile ahead with the gather of du
 // included and does not read max_steps (252 VGPRs, no scratch, two waves per SIMD).
-// The grid (plane_sweep_grid in plfx.hip) is at most the blocks the device holds at once at PLANE_SWEEP_WAVES waves per SIMD:
+// The grid (plane_sweep_grid in plfx_step.hip) is at most the blocks the device holds at once at PLANE_SWEEP_WAVES waves per SIMD:
 // every block is resident from the start and takes more passes, over which the pipeline's two dependent round trips in front
 // of the loop are spread.
 constexpr int PLANE_SWEEP_WAVES = PLFX_SWEEP_WAVES < 2 ? 2 : PLFX_SWEEP_WAVES;   // waves per SIMD the kernel is compiled for
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK, PLANE_SWEEP_WAVES)
 k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls,
                     int lds_doubles, int nel, int e_off, const int32_t *__restrict__ conn,
@@ -1370,6 +1383,7 @@ k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *_
     }
     post_block_flags(changed, nconv, bflags);
 }
+#endif
 
 // Phase 2: the sub-divided plastic corrector for the compacted element list.  Every lane runs the
 // same 50 sub-steps (no divergence); FP64-VALU bound.
@@ -1675,6 +1689,7 @@ k_sweep_wh_wave(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__res
 }
 
 // elstiff = CV, M from CV for all owned elements (model.py:1219-1221): the tag alone stores the tangent
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_init_tangent(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_t *cls,
                TanStore ts, double *Mel, int mel_stride)
@@ -1703,9 +1718,11 @@ k_init_M_all(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_t *c
 #pragma unroll
     for (int k = 0; k < 6; k++) Mel[(size_t)k * nel + e] = M[k];
 }
+#endif
 
 // zero the stiffness generators of the elements this rank does not own (before the all-reduce that
 // makes M consistent on every rank: x + 0 + ... + 0 = x exactly)
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_zero_foreign_M(int nel_total, int e0, int e1, double *Mel)
 {
@@ -1715,8 +1732,10 @@ k_zero_foreign_M(int nel_total, int e0, int e1, double *Mel)
         if (e < e0 || e >= e1) Mel[i] = 0.;
     }
 }
+#endif
 
 // recompute M from elstiff (after plfx_state_set of the tangent)
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_refresh_M(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_t *cls, TanStore ts, double *Mel,
             int mel_stride)
@@ -1744,6 +1763,7 @@ k_tangent_expand(const MatDev *gmat, const ClassDev *gcls, int nel, const int32_
     for (int k = 0; k < 21; k++) out[(size_t)k * nel + e] = D[k];
     if (to_full) ts.tag[e] = TAN_FULL;
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Layouts of the six stiffness generators (XX XY XS YY YS SS) of nel elements:
@@ -1791,6 +1811,7 @@ __host__ __device__ inline void structured_slot(int nx, int ny, int i, int s, in
 
 // col[s * nnode + i], contrib[(s * 4 + q) * nnode + i] of a structured nx x ny grid, filled on the device (no host pattern,
 // no upload: 180 B per node)
+#ifdef PLFX_UNIT_MESH
 __global__ void __launch_bounds__(256)
 k_structured_pattern(int nx, int ny, int32_t *__restrict__ col, int32_t *__restrict__ contrib)
 {
@@ -1806,12 +1827,14 @@ k_structured_pattern(int nx, int ny, int32_t *__restrict__ col, int32_t *__restr
         }
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Assembly (model.py:954-977) as a gather: thread (node i, slot s) sums the <= nq element
 // contributions of block K[i, col(s)] in ascending element order.  contrib code = e*16 + a*4 + b
 // (e local owned-element index, a/b local node numbers), -1 = none.
 // val layout: [(s*4 + r*2 + c) * nnode + i]
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_assemble(const ClassDev *gcls, int ncls, int nnode, int nslot, int nq, int nel,
            const int32_t *contrib, const int32_t *cls, const double *Mel, const int32_t *col,
@@ -1853,6 +1876,7 @@ k_assemble(const ClassDev *gcls, int ncls, int nnode, int nslot, int nq, int nel
         }
     }
 }
+#endif
 
 // Row pair i of the block-ELL matrix times a vector given as a functor xf(j) -> double2.
 // Nine slots (every structured Q4 grid): branch-free and fully unrolled, so that the 9 column ids, the 36
@@ -2631,6 +2655,7 @@ k_spmv_march(KOp op, const double2 *__restrict__ p, const double2 *__restrict__ 
 
 // partial sums of p.q over all nodes (multi-GPU: after the all-reduce of q), and the p update for
 // nodes outside the rank's own SpMV range
+#ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_dot_pq(int nnode, const double2 *__restrict__ p, const double2 *__restrict__ q, double *__restrict__ part_pq, const CgScalars *__restrict__ sc)
 {
@@ -2708,6 +2733,7 @@ k_cg_update(int nnode, const double2 *__restrict__ p, const double2 *__restrict_
         part_rr_out[blockIdx.x] = t2;
     }
 }
+#endif
 
 // Start of a PCG solve in one pass: q = K x0 (warm start), r = mask (b - q), z = dinv r and the partial sums of r.z,
 // r.r, b.b -- k_spmv<0> + k_cg_init without the round trip of q through memory.
@@ -2781,6 +2807,7 @@ k_cg_start_test(KOp op, int nnode, int warm, const double2 *__restrict__ x, cons
 // the d that k_pred_diff has just written).  No z and no r.z: the V-cycle that follows a failed test starts from a zero guess
 // and writes every entry of z, and its last smoothing launch (or k_dot_rz) writes the r.z partials.  One GPU, no strip: the
 // sums run over all nodes.
+#ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 *__restrict__ d, const double2 *__restrict__ b,
                 const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ kd,
@@ -2863,11 +2890,14 @@ __global__ void k_cg_setup(const double *part_bb, int npart, double rtol, CgScal
         sc->aux = 0.;
     }
 }
+#endif
 
 // k_cg_setup + k_cg_check in one launch (start of a solve)
 struct CgMbox;
+#ifdef PLFX_UNIT_SOLVE
 __global__ void k_cg_setup_check(const double *part_bb, const double *part_rr, int npart, double rtol, CgScalars *sc, int it_done,
                                  CgMbox *mb, unsigned long long seq);
+#endif
 
 // Pinned, host-visible copy of the PCG scalars: a kernel posts them with a sequence number and the host spins on the
 // number instead of enqueueing a device->host copy and synchronising the stream (12 instead of 19 us per round trip on
@@ -2887,6 +2917,7 @@ __device__ void mbox_publish(CgMbox *mb, unsigned long long seq)
 
 // convergence test on the residual partials an update kernel just wrote (one block): lets the host stop
 // BEFORE it launches the next preconditioner application (a V-cycle is the most expensive part of an iteration)
+#ifdef PLFX_UNIT_SOLVE
 __global__ void k_cg_check(const double *part_rr, int npart, CgScalars *sc, int it_done, CgMbox *mb,
                            unsigned long long seq)
 {
@@ -2932,8 +2963,10 @@ __global__ void k_cg_setup_check(const double *part_bb, const double *part_rr, i
         }
     }
 }
+#endif
 
 // copy n doubles of results to pinned host memory and post the sequence number (one block)
+#ifdef PLFX_UNIT_CONTEXT
 __global__ void __launch_bounds__(BLOCK)
 k_mbox_post(const double *__restrict__ src, int n, double *__restrict__ dst, CgMbox *mb, unsigned long long seq)
 {
@@ -2942,8 +2975,10 @@ k_mbox_post(const double *__restrict__ src, int n, double *__restrict__ dst, CgM
     __syncthreads();
     if (threadIdx.x == 0) __atomic_store_n(&mb->seq, seq, __ATOMIC_RELEASE);
 }
+#endif
 
 // final rr for reporting when the iteration limit was hit
+#ifdef PLFX_UNIT_SOLVE
 __global__ void k_cg_final(const double *part_rr, int npart, CgScalars *sc)
 {
     __shared__ double sh[BLOCK / 64];
@@ -2962,8 +2997,10 @@ __global__ void __launch_bounds__(BLOCK) k_scatter(int n, const int32_t *idx, co
     const int k = blockIdx.x * BLOCK + threadIdx.x;
     if (k < n) y[idx[k]] = v[k];
 }
+#endif
 
 // y[idx[k]] = a[k], z[idx[k]] = b[k], (flag ? m[idx[k]] = 1)  : prescribed-DOF data of apply_bc in one launch
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_scatter_bc(int n, const int32_t *idx, const double *a, const double *b, double *y, double *z, double *m, int flag)
 {
@@ -2974,6 +3011,7 @@ k_scatter_bc(int n, const int32_t *idx, const double *a, const double *b, double
     z[i] = b[k];
     if (flag) m[i] = 1.;
 }
+#endif
 
 // the same for a registered BC plan: every prescribed DOF takes the value of its first entry's segment (y) and the sum
 // over the segments of all its entries in entry order (z; a DOF on two edges counts twice, model.py:1115-1122); the
@@ -2983,6 +3021,7 @@ struct BcSegVals {
     double v[N];
 };
 
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_scatter_bc_plan(int n, const int32_t *__restrict__ idx, const int32_t *__restrict__ seg4, BcSegVals sv,
                   double *__restrict__ y, double *__restrict__ z, double *__restrict__ m, int flag)
@@ -3005,12 +3044,15 @@ k_scatter_bc_plan(int n, const int32_t *__restrict__ idx, const int32_t *__restr
     z[i] = w;
     if (flag) m[i] = 1.;
 }
+#endif
 
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK) k_gather(int n, const int32_t *idx, const double *y, double *v)
 {
     const int k = blockIdx.x * BLOCK + threadIdx.x;
     if (k < n) v[k] = y[idx[k]];
 }
+#endif
 
 // q[i] = (K w)[i] for the listed nodes only: w is non-zero on prescribed DOFs, so K w vanishes except on the
 // rows of nodes that touch a prescribed node (O(boundary) work instead of a full matrix pass)
@@ -3033,6 +3075,7 @@ k_spmv_rows(int nlist, const int32_t *__restrict__ list, KOp op, const double2 *
 }
 
 // rhs = fext - K w (q holds K w);  dinv = free ? 1/|diag| : 0
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_bc_finish(size_t ndof, const double *__restrict__ fext, const double *__restrict__ kw, const double *__restrict__ diag,
             const double *__restrict__ is_presc, double *__restrict__ rhs, double *__restrict__ dinv)
@@ -3055,9 +3098,11 @@ k_dinv(size_t ndof, const double *__restrict__ diag, const double *__restrict__ 
         dinv[i] = free_dof ? (d > 1e-300 ? 1. / d : 1.) : 0.;
     }
 }
+#endif
 
 // du = x (free) + du_presc (prescribed).  gate != null: enqueued behind a convergence test the host has not seen yet --
 // a no-op unless that test passed (done == 1), in which case x is the solution
+#ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_compose_du(size_t ndof, const double *__restrict__ x, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du,
              const CgScalars *__restrict__ gate = nullptr)
@@ -3183,8 +3228,10 @@ k_pred_finish(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict_
         if (keep_d) d[i] = (mi == 0.) ? xi - xp : 0.;
     }
 }
+#endif
 
 // u += du ; f += q  (q = K du)     (model.py:1383-1384)
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_axpy_uf(size_t ndof, const double *__restrict__ du, const double *__restrict__ q, double *__restrict__ u, double *__restrict__ f)
 {
@@ -3193,13 +3240,14 @@ k_axpy_uf(size_t ndof, const double *__restrict__ du, const double *__restrict__
         f[i] += q[i];
     }
 }
+#endif
 
 // element state update at the end of a load step (model.py:1385-1392); u already updated
 // Latency structure as in k_sweep_light: tables in LDS, every stream whose address depends on the element index alone issued
 // at the top of the pass (res_sig / res_depl whenever the step was non-linear, whatever the element's material turns out to
 // be), the gathers of u and du behind conn, and the stores after the last load.
 // eps = class_strain(u) is formed for the sums only and not stored: k_eps_from_u writes the field when somebody asks for it
-// (ensure_eps, plfx.hip).  swap != 0 (every material plastic, a sweep wrote res_sig for every element since the last
+// (ensure_eps, plfx_step.hip).  swap != 0 (every material plastic, a sweep wrote res_sig for every element since the last
 // exchange): the new sig IS res_sig, so it is only read for the sums and the host exchanges the two pointers behind the launch.
 // PLANE (k_update_state_plane): columns 3 and 4 of epl, res_depl, res_sig and (elastic branch) sig are zero in memory
 // and stay so -- neither loaded nor stored; the sums are formed by the same chain with the zeros in place.
@@ -3304,6 +3352,7 @@ k_update_state_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *
 
 // eps = class_strain(u) of every element: the stored field behind Element.eps and plfx_global_sums, written on demand (the
 // same inline function on the same staged class tables as k_update_state: the same bits as the sums saw)
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_eps_from_u(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict__ gcls, int ncls, int nel, int e_off,
              const int32_t *__restrict__ conn, const int32_t *__restrict__ cls, const double2 *__restrict__ u2, double *__restrict__ eps)
@@ -3320,6 +3369,7 @@ k_eps_from_u(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restri
         for (int k = 0; k < 6; k++) eps[(size_t)k * nel + e] = et[k];
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Element result fields (plfx_element_fields): the values the closures of the reference's Model.plot compute per element
@@ -3479,6 +3529,7 @@ k_element_fields(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__re
 }
 
 // calc_global sums (model.py:1500-1507): partials of sum(x*Vel) for the 18 components
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_global_partials(const ClassDev *__restrict__ gcls, int nel, const int32_t *__restrict__ cls, const double *__restrict__ sig,
                   const double *__restrict__ eps, const double *__restrict__ epl, double *__restrict__ part /* [18][gridDim.x] */)
@@ -3617,6 +3668,7 @@ k_scf_elements(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__rest
         mult_out[e] = mult;
     }
 }
+#endif
 
 // calc_scf for the elements of the 6-feature SVC material `mat`, 16 lanes per element (YfSvcRow; ML_full_yf along the
 // loading direction is a ray search, model.py:1049-1052) -- the thread-per-element form above took 4.5 ms per call on
@@ -3676,6 +3728,7 @@ k_scf_row(const MatDev *__restrict__ gmat, int nmat, const ClassDev *__restrict_
 }
 
 // pass 0: sum(mult*hh), min(hh | mult>0), count ; pass 1: sum(mult*(hh-mean)^2)
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_scf_reduce(int nel, const double *hh, const int32_t *mult, double mean, int pass,
              double *part /* [3][gridDim.x] */, const double *mean_dev = nullptr, int e_lo = 0, int e_hi = 0x7fffffff)
@@ -3750,6 +3803,7 @@ __global__ void k_scf_mean(double *out)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) out[3] = out[1] > 0. ? out[0] / (double)(long long)(out[1] + 0.5) : 0.;
 }
+#endif
 
 
 // ---------------------------------------------------------------------------------------------
@@ -3760,10 +3814,11 @@ __global__ void k_scf_mean(double *out)
 // none, with the value the material object held when the sweep began.  Given the exit moduli and "touched" flags of a
 // data-parallel sweep, these three kernels compute that entry value for every element (an exclusive prefix maximum of the
 // touched element indices) and count the elements whose entry value differs from the one the sweep was run with; the host
-// repeats the sweep until the count is zero (fixed point = the sequential loop's result, plfx.hip: sweep_wh_sequential).
+// repeats the sweep until the count is zero (fixed point = the sequential loop's result, plfx_step.hip: sweep_wh_sequential).
 struct WhCarry {
     double v[16];
 };
+#ifdef PLFX_UNIT_STEP
 __global__ void __launch_bounds__(BLOCK)
 k_wh_fill(int nel, const ClassDev *__restrict__ gcls, const int32_t *__restrict__ cls, WhCarry w, double *__restrict__ kh)
 {
@@ -3824,6 +3879,7 @@ k_wh_entry(int nel, int mat, const ClassDev *__restrict__ gcls, const int32_t *_
     const unsigned long long m = __ballot(diff);
     if (m && (threadIdx.x & 63) == 0) atomicAdd(nchanged, __popcll(m));
 }
+#endif
 
 }  // namespace plfx
 

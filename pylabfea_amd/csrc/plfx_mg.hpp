@@ -113,6 +113,7 @@ k_mg_residual(KOp op,
 
 // The three fine-level kernels of the V-cycle in marching form (grid_march, plfx_kernels.hpp): bit-identical results, fewer
 // and fully coalesced loads; used on the finest grid when one operator pass exceeds the Infinity Cache (plfx.hip: use_march)
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_mg_smooth_march(KOp op, const double2 *__restrict__ dinv, const double2 *__restrict__ b, const double2 *__restrict__ xin,
                   double2 *__restrict__ xout, double omega, const CgScalars *sc, DotOut dot)
@@ -160,6 +161,7 @@ k_mg_residual_march(KOp op, const double2 *__restrict__ dinv, const double2 *__r
             res[i] = make_double2(di.x != 0. ? bi.x - qv.x : 0., di.y != 0. ? bi.y - qv.y : 0.);
         });
 }
+#endif
 
 // One step of the Jacobi-preconditioned Chebyshev iteration for K x = b (coarsest level too large for a dense inverse):
 //   d <- c1 d + c2 D^-1 (b - K x),  x <- x + d        (first != 0: x = 0, d = c2 D^-1 b)
@@ -265,6 +267,7 @@ __device__ __forceinline__ double2 mg_restrict_at(int J, int K, int nfx, int nfy
 
 // restriction b_c = P^T res_f (P: bilinear interpolation, mg_tr1d per direction); nyf/nyc = nodes per column; rxf, ryf =
 // relative size of the fine level's last cell
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_mg_restrict(int nxc_nodes, int nyc, int nxf_nodes, int nyf, const double2 *__restrict__ res_f,
               const double2 *__restrict__ dinv_c, double2 *__restrict__ b_c, double rxf = 1., double ryf = 1.,
@@ -410,6 +413,7 @@ k_jacobi_z(int nn, const double2 *__restrict__ dinv, const double2 *__restrict__
         z[i] = make_double2(d.x * ri.x, d.y * ri.y);
     }
 }
+#endif
 
 // ---------------------------------------------------------------------------------------------- operator application for GMRES
 // The tangents of the reference are not always positive semi-definite: the correction step of Material.response
@@ -465,6 +469,7 @@ struct Ptr8 {
 };
 
 // w += sum_k c_k V_k, k < n (<= 8): the solution update at the end of a cycle (coefficients by value)
+#ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_gmres_axpy(int nn, int n, double2 *__restrict__ w, Ptr8 V, Coef8 C)
 {
@@ -492,6 +497,7 @@ k_scale_copy(int nn, double s, const double2 *__restrict__ src, double2 *__restr
         if (dst2) dst2[i] = b;
     }
 }
+#endif
 
 // ---- Arnoldi with delayed re-orthogonalisation (round 6): the basis is read TWICE per iteration.  Classical
 // Gram-Schmidt twice would make two projection passes per new vector, each a dots pass + an update pass over the j basis
@@ -512,6 +518,7 @@ struct GmBlocks {
 // vectors (first version: 16 vectors per launch with 32 register accumulators per thread -- 3.3 TB/s and a re-read of a, b per
 // launch; profiles/r07d_config5_kernel_summary_first_dcgs2.txt).
 constexpr int GM_KC = 128;
+#ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_gmres_dots3(int own_lo, int own_hi, int k0, int kn, GmBlocks B, size_t nd, const double2 *__restrict__ a,
               const double2 *__restrict__ b, int extra, double *__restrict__ part)
@@ -621,6 +628,7 @@ k_gmres_update2(int nn, size_t nd, int j, GmBlocks B, const double *__restrict__
         uout[i] = b;
     }
 }
+#endif
 
 constexpr int MG_COARSE_MAX = 1089;  // 33 x 33 nodes
 constexpr int MG_TAIL_BLOCK = 1024;  // threads of the single-workgroup tail kernel
@@ -730,6 +738,7 @@ __device__ inline void coarse_solve_block(int nnode, int nslot, const int32_t *_
 
 // Dense inverse of the coarsest operator (n = 2*nnode <= MG_DENSE_MAX) by in-place Gauss-Jordan in
 // LDS; prescribed DOFs are replaced by identity rows/columns.  Runs once per apply_bc.
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_mg_coarse_invert(int nnode, int nslot, const int32_t *__restrict__ col, const double *__restrict__ val,
                    const double2 *__restrict__ dinv, double *__restrict__ ainv)
@@ -785,6 +794,7 @@ k_mg_coarse_invert(int nnode, int nslot, const int32_t *__restrict__ col, const 
     }
     for (int i = threadIdx.x; i < n * n; i += BLOCK) ainv[i] = A[i];
 }
+#endif
 
 // x = Ainv b on the coarsest grid (masked DOFs stay zero because b is zero there)
 __device__ inline void coarse_dense_block(int nnode, const double *__restrict__ ainv,
@@ -801,6 +811,7 @@ __device__ inline void coarse_dense_block(int nnode, const double *__restrict__ 
     __syncthreads();
 }
 
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_mg_coarse_solve(int nnode, int nslot, const int32_t *__restrict__ col, const double *__restrict__ val,
                   const double2 *__restrict__ dinv, const double2 *__restrict__ b, double2 *__restrict__ x,
@@ -818,6 +829,7 @@ k_mg_coarse_dense(int nnode, const double *__restrict__ ainv, const double2 *__r
     if (sc->done) return;
     coarse_dense_block(nnode, ainv, b, x);
 }
+#endif
 
 // ---- single-workgroup pieces of the V-cycle (levels with few nodes are launch-latency bound:
 //      one workgroup walks them all, separated by workgroup barriers instead of kernel boundaries)
@@ -913,6 +925,7 @@ __device__ inline void blk_prolong_add(const MgLevDev &F, const MgLevDev &Cc)
 }
 
 // V-cycle over the levels [l0, nl) in ONE workgroup: b of level l0 in, x of level l0 out.
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(MG_TAIL_BLOCK)
 k_mg_tail(const MgLevDev *__restrict__ lev, int l0, int nl, double omega, int nu, const CgScalars *sc)
 {
@@ -952,6 +965,7 @@ k_mg_tail(const MgLevDev *__restrict__ lev, int l0, int nl, double omega, int nu
         }
     }
 }
+#endif
 
 // ---- LDS-resident tail: the vectors (x, b, t, res) and the neighbour tables of ALL tail levels live in
 //      LDS (<= ~1500 nodes x 100 B), so a smoothing step is [coalesced matrix loads from L2] + [LDS gathers]
@@ -1004,6 +1018,7 @@ __device__ __forceinline__ double2 tail_apply(const MgLevDev &L, const TailView 
     return make_double2(qx, qy);
 }
 
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(MG_TAIL_BLOCK)
 k_mg_tail_lds(const MgLevDev *__restrict__ lev, int l0, int nl, int T, double omega, const CgScalars *sc)
 {
@@ -1124,6 +1139,7 @@ k_mg_tail_lds(const MgLevDev *__restrict__ lev, int l0, int nl, int T, double om
         for (int i = threadIdx.x; i < L.nnode; i += nt) L.x[i] = v.x[i];
     }
 }
+#endif
 
 // ---- matrix-free LDS-resident tail: like k_mg_tail_lds, but the operator is applied from the stiffness generators,
 //      which are staged into LDS together with the vectors (x, b, w: 48 B/node; M: 48 B/element; <= 1502 nodes and
@@ -1306,6 +1322,7 @@ k_mg_tail_mf(const MgLevDev *__restrict__ lev, int l0, int nl, int T, int E, con
 }
 
 // PCG update without the Jacobi z (the V-cycle computes z): x += alpha p; r -= alpha q; partial r.r
+#ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_cg_update_mg(int nnode, const double2 *__restrict__ p, const double2 *__restrict__ q,
                const double2 *__restrict__ dinv, double2 *__restrict__ x, double2 *__restrict__ r, const double *__restrict__ part_pq,
@@ -1359,10 +1376,12 @@ k_dot_rz(int own_lo, int own_hi, const double2 *__restrict__ r, const double2 *_
     const double t = block_sum(acc, sh);
     if (threadIdx.x == 0) part_rz_out[blockIdx.x] = t;
 }
+#endif
 
 // Strip-local engine: dst[c * dst_n + i] = (off <= i < off + cnt) ? src[c * src_n + i - off + soff] : 0 for c < ncomp -- the owned
 // window of a strip's level-Ld array placed into the zero-filled array of the replicated coarse grid; one all-reduce over
 // the ranks then completes it (x + 0 + ... + 0 = x exactly).  Node / element columns are contiguous, so a window is a range.
+#ifdef PLFX_UNIT_OPERATOR
 __global__ void __launch_bounds__(BLOCK)
 k_strip_pack(int ncomp, size_t dst_n, size_t src_n, size_t off, size_t cnt, size_t soff, const double *__restrict__ src,
              double *__restrict__ dst)
@@ -1373,5 +1392,6 @@ k_strip_pack(int ncomp, size_t dst_n, size_t src_n, size_t off, size_t cnt, size
         dst[t] = (i >= off && i < off + cnt) ? src[c * src_n + (i - off) + soff] : 0.;
     }
 }
+#endif
 
 }  // namespace plfx
