@@ -192,6 +192,37 @@ int plfx_flow_curve(plfx_ctx *ctx, int mat, int n, const double *su, const doubl
 /* launches of the flow-curve kernels by this context */
 int plfx_flow_info(plfx_ctx *ctx, int64_t *launches);
 
+/* Material.load_path: n points of material `mat` driven along load paths of K increments, each step
+ * starting from the state the last one left, every path in ONE launch with one copy in and one copy out.
+ * dload[K][n][6], or [K][6] with shared != 0 (one path for all points).  control: NULL (every component strain-controlled) or
+ * int32[n], bit c set = component c of dload is a stress increment, clear = a strain increment; constant along a path.
+ * sig0, epl0: [n][6] or NULL (zeros).  tex_id: [n] rows of a texture field or NULL (row 0), as plfx_response_batch_tid.
+ * With S the strain- and F the stress-controlled components, the stress target is t_k[F] = t_{k-1}[F] + dload[k][F],
+ * t_{-1} = sig0[F] (one rounded add per step).  One step, from (sig, epl) and the tangent Ct of the last accepted step (the
+ * material's CV before the first): deps[S] = dload[k][S]; deps[F] solves Ct_FF deps_F = (t_k - sig)_F - Ct_FS deps_S; the
+ * trial is Material.response(sig, epl, deps, CV, maxit), accepted when F is empty or max |sig'[F] - t_k[F]| <= stol; else
+ * deps[F] -= Ct'_FF^-1 (sig'[F] - t_k[F]) and the trial is repeated from the same state, at most `newton` corrections.  On
+ * acceptance sig = sig', epl = epl + depl (one rounded add), Ct = Ct'.  An elastic material's trial is sig + CV deps.
+ * The masked tangent is factored as L D L^T without pivoting.  No trial is evaluated on a deps that is not finite or has
+ * max |deps| > eps_cap: the path ends instead.
+ * Out, step-major: sig, epl, deps [K][n][6] (state after step k, increment taken; on S the bits of dload), fy[K][n],
+ * nsteps[K][n] (Material.response's value and sub-step count of the accepted trial), newton_out[K][n] corrections taken,
+ * ksteps[n] steps completed, status[n]: 0 complete, 1 stol not reached within `newton` corrections, 2 a pivot of the masked
+ * tangent zero or not finite, 3 deps not finite or beyond eps_cap.  Steps from ksteps[i] on hold NaN (-1 in the int arrays);
+ * the completed steps are exactly those of the same path cut to ksteps[i] steps.  ct: NULL or [n][36], the tangent after the
+ * last completed step.  With F empty the results have the bits of K plfx_response_batch calls with epl += depl in between.
+ * Kinds: PLFX_ELASTIC, PLFX_HILL6, PLFX_PRINC3, PLFX_BARLAT with barlat_normal, and PLFX_SVC6 / PLFX_SVC6_COLS on the row
+ * kernels (texture fields included); every other kind is PLFX_ERR_UNSUPPORTED.  PLFX_ERR_ARG, with nothing launched: mat out
+ * of range, n or K < 0, maxit < 1, newton < 0, stol or eps_cap not finite or <= 0, a dload, sig0 or epl0 that is not finite,
+ * a strain-controlled |dload| > eps_cap, a control outside 0..63, a tex_id outside the attached rows, K n 19 > INT32_MAX.
+ * n = 0 or K = 0 is PLFX_OK with nothing launched (K = 0: ksteps = status = 0 and ct = CV). */
+int plfx_load_path(plfx_ctx *ctx, int mat, int n, int K, const double *dload, int shared, const int32_t *control,
+                   const double *sig0, const double *epl0, const int32_t *tex_id, int maxit, int newton, double stol,
+                   double eps_cap, double *sig, double *epl, double *deps, double *fy, int32_t *nsteps, int32_t *newton_out,
+                   int32_t *ksteps, int32_t *status, double *ct);
+/* launches of the load-path kernels by this context */
+int plfx_load_path_info(plfx_ctx *ctx, int64_t *launches);
+
 /* A committee of SVC yield functions on n shared unit stresses su[n*6] (query by committee): member k is
  * material mats[k] of the context, 1 <= nmem <= 16, duplicates allowed, each a 6-feature SVC on Voigt stresses (PLFX_SVC6,
  * dev_only or not), with its own stress scale scale[k] (finite, > 0).  One launch of k_committee_yf, whatever nmem is:

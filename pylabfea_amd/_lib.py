@@ -65,7 +65,7 @@ SYMBOLS = [
     'plfx_committee_yf', 'plfx_committee_info',
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
-    'plfx_flow_curve', 'plfx_flow_info',
+    'plfx_flow_curve', 'plfx_flow_info', 'plfx_load_path', 'plfx_load_path_info',
     'plfx_dead_store_info', 'plfx_plane_info', 'plfx_short_info',
     'plfx_set_svc_cols', 'plfx_mg_info',
     'plfx_set_svc_textures', 'plfx_set_element_textures', 'plfx_response_batch_tid', 'plfx_full_yf_batch_tid',
@@ -391,6 +391,51 @@ class Context(object):
         """dict(launches): launches of the flow-curve kernels by this context"""
         nl = C.c_int64()
         self._chk(self.lib.plfx_flow_info(self.h, C.byref(nl)))
+        return dict(launches=int(nl.value))
+
+    def load_path(self, mat, dload, control=None, sig0=None, epl0=None, tex_id=None, maxit=50, newton=30, stol=1., eps_cap=0.05,
+                  return_tangent=False):
+        """Load paths of N points of material ``mat`` in one launch (plfx_load_path): dload (K,N,6), or (K,6) shared by the
+        points, whose number then comes from sig0 / epl0 / control / tex_id (else 1); control None or (N,) int32 with bit c set
+        where component c is stress-controlled; sig0, epl0 (N,6) or None (zeros); tex_id (N,) or None.  Dict, step-major: sig,
+        epl, deps (K,N,6), fy (K,N), nsteps, newton (K,N) int32, ksteps, status (N,) int32 and, with return_tangent, ct
+        (N,6,6).  Status 0 complete, 1 stol not reached, 2 pivot zero or not finite, 3 deps not finite or beyond eps_cap."""
+        dload = _f64(dload)
+        shared = dload.ndim == 2
+        if dload.ndim not in (2, 3) or dload.shape[-1] != 6:
+            raise ValueError('load_path: dload of shape (K, N, 6) or (K, 6) expected')
+        control = None if control is None else _i32(control).reshape(-1)
+        sig0 = None if sig0 is None else _f64(sig0).reshape(-1, 6)
+        epl0 = None if epl0 is None else _f64(epl0).reshape(-1, 6)
+        tex_id = None if tex_id is None else _i32(tex_id).reshape(-1)
+        given = [len(a) for a in (control, sig0, epl0, tex_id) if a is not None]
+        n = dload.shape[1] if not shared else (given[0] if given else 1)
+        if any(g != n for g in given):
+            raise ValueError('load_path: one row of control, sig0, epl0 and tex_id per point expected')
+        K = len(dload)
+        # one block in the order of the library's device buffer: the results then arrive in one copy, without staging
+        KN, nct = K * n, 36 * n if return_tangent else 0
+        # (not filled: a call that launches writes every entry, NaN and -1 past a path's end included, and one that does not
+        # has K = 0 or n = 0, or raises)
+        buf = np.empty(19 * KN + nct + KN + n)
+        ints = buf[19 * KN + nct:].view(np.int32)
+        out = dict(sig=buf[:6 * KN].reshape(K, n, 6), epl=buf[6 * KN:12 * KN].reshape(K, n, 6),
+                   deps=buf[12 * KN:18 * KN].reshape(K, n, 6), fy=buf[18 * KN:19 * KN].reshape(K, n),
+                   nsteps=ints[:KN].reshape(K, n), newton=ints[KN:2 * KN].reshape(K, n), ksteps=ints[2 * KN:2 * KN + n],
+                   status=ints[2 * KN + n:])
+        ct = buf[19 * KN:19 * KN + nct].reshape(n, 6, 6) if return_tangent else None
+        self._chk(self.lib.plfx_load_path(self.h, int(mat), n, K, _dp(dload), int(shared), _dp(control), _dp(sig0), _dp(epl0),
+                                          _dp(tex_id), int(maxit), int(newton), C.c_double(stol), C.c_double(eps_cap),
+                                          _dp(out['sig']), _dp(out['epl']), _dp(out['deps']), _dp(out['fy']), _dp(out['nsteps']),
+                                          _dp(out['newton']), _dp(out['ksteps']), _dp(out['status']), _dp(ct)))
+        if return_tangent:
+            out['ct'] = ct
+        return out
+
+    def load_path_info(self):
+        """dict(launches): launches of the load-path kernels by this context"""
+        nl = C.c_int64()
+        self._chk(self.lib.plfx_load_path_info(self.h, C.byref(nl)))
         return dict(launches=int(nl.value))
 
     def committee_yf(self, mats, scale, su, want_yf=True, want_mean=False, want_var=False, want_best=False):

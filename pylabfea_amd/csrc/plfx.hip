@@ -2266,6 +2266,145 @@ int plfx_flow_info(plfx_ctx *c, int64_t *launches)
     return PLFX_OK;
 }
 
+// Material.load_path: n material points of material `mat` along load paths of K increments, every path in
+// ONE launch: k_path_batch for the kinds of k_response_batch<1 | 2 | 5>, k_path_row (launch_path_row, plfx_step.hip) for the
+// 6-feature SVC materials of the row kernels.  One copy in, one copy out.  Everything is checked before anything is launched.
+int plfx_load_path(plfx_ctx *c, int mat, int n, int K, const double *dload, int shared, const int32_t *control,
+                   const double *sig0, const double *epl0, const int32_t *tex_id, int maxit, int newton, double stol,
+                   double eps_cap, double *sig, double *epl, double *deps, double *fy, int32_t *nsteps, int32_t *newton_out,
+                   int32_t *ksteps, int32_t *status, double *ct)
+{
+    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
+    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "load_path: material %d, the context holds %d", mat, c->nmat);
+    const MatDev &hm = c->hmat[mat];
+    const bool row = (hm.kind == PLFX_SVC6 || hm.kind == PLFX_SVC6_COLS) && ((c->svc_row_all >> mat) & 1u);
+    int kind = 0;   // instantiation of k_path_batch
+    if (hm.kind == PLFX_ELASTIC || hm.kind == PLFX_HILL6)
+        kind = 1;
+    else if (hm.kind == PLFX_PRINC3)
+        kind = 2;
+    else if (hm.kind == PLFX_BARLAT && hm.barlat_normal)
+        kind = 5;
+    else if (!row)
+        return fail(c, PLFX_ERR_UNSUPPORTED, "load_path: offered for elastic, Hill / J2 / Drucker materials, Barlat with the native "
+                    "normal and the 6-feature SVC of the row kernels; material %d is of kind %d", mat, hm.kind);
+    if (n < 0 || K < 0) return fail(c, PLFX_ERR_ARG, "load_path: n >= 0 and K >= 0 expected");
+    if (maxit < 1 || newton < 0 || !(stol > 0.) || !std::isfinite(stol) || !(eps_cap > 0.) || !std::isfinite(eps_cap))
+        return fail(c, PLFX_ERR_ARG, "load_path: maxit >= 1, newton >= 0 and finite stol > 0, eps_cap > 0 expected");
+    if (n == 0) return PLFX_OK;
+    if (!ksteps || !status || (K > 0 && (!dload || !sig || !epl || !deps || !fy || !nsteps || !newton_out)))
+        return fail(c, PLFX_ERR_ARG, "load_path: null argument");
+    const size_t N = n, KK = K, nd = shared ? 1 : N;
+    if (KK * N * 19 > (size_t)INT32_MAX) return fail(c, PLFX_ERR_ARG, "load_path: K n 19 = %zu exceeds INT32_MAX", KK * N * 19);
+    unsigned any_strain = control ? 0u : 63u;   // components that are strain-controlled at some point (a shared dload)
+    if (control)
+        for (size_t i = 0; i < N; i++) {
+            if (control[i] < 0 || control[i] >= 64) return fail(c, PLFX_ERR_ARG, "load_path: control[%zu] = %d, six bits expected", i, (int)control[i]);
+            any_strain |= ~(unsigned)control[i] & 63u;
+        }
+    for (size_t j = 0; j < KK * nd * 6; j++) {
+        if (!std::isfinite(dload[j])) return fail(c, PLFX_ERR_ARG, "load_path: dload is not finite at entry %zu", j);
+        const unsigned strain = shared ? any_strain : (control ? ~(unsigned)control[(j / 6) % N] & 63u : 63u);
+        if (((strain >> (j % 6)) & 1u) && std::fabs(dload[j]) > eps_cap)
+            return fail(c, PLFX_ERR_ARG, "load_path: the strain increment %g at entry %zu of dload is beyond eps_cap = %g", dload[j], j, eps_cap);
+    }
+    for (const double *p : {sig0, epl0})
+        if (p)
+            for (size_t j = 0; j < 6 * N; j++)
+                if (!std::isfinite(p[j])) return fail(c, PLFX_ERR_ARG, "load_path: %s is not finite at entry %zu", p == sig0 ? "sig0" : "epl0", j);
+    if (int rc = tex_point_check(c, n, mat, nullptr, tex_id)) return rc;
+    if (K == 0) {   // nothing to follow: no step completed, the tangent is the elastic one
+        for (size_t i = 0; i < N; i++) {
+            ksteps[i] = status[i] = 0;
+            if (ct)
+                for (int r = 0; r < 6; r++)
+                    for (int q = 0; q < 6; q++) ct[36 * i + r * 6 + q] = hm.CV[sym_idx(r, q)];
+        }
+        return PLFX_OK;
+    }
+    const bool field = tex_id && ((c->tex_field_mask >> mat) & 1u);
+    // one buffer in: dload | sig0 | epl0 | control, tex_id (int32)
+    const size_t o_s0 = KK * nd * 6, o_e0 = o_s0 + (sig0 ? 6 * N : 0), o_int = o_e0 + (epl0 ? 6 * N : 0);
+    const size_t n_int = (control ? N : 0) + (field ? N : 0), in_words = o_int + (n_int + 1) / 2;
+    const std::unique_ptr<double[]> hin(new double[std::max<size_t>(in_words, 1)]);   // (not zeroed: every word sent is written)
+    memcpy(hin.get(), dload, o_s0 * 8);
+    if (sig0) memcpy(hin.get() + o_s0, sig0, N * 48);
+    if (epl0) memcpy(hin.get() + o_e0, epl0, N * 48);
+    int32_t *hint = (int32_t *)(hin.get() + o_int);
+    if (n_int & 1) hint[n_int] = 0;
+    if (control) memcpy(hint, control, N * 4);
+    if (field) memcpy(hint + (control ? N : 0), tex_id, N * 4);
+    // one buffer out: sig | epl | deps | fy | ct | nsteps, newton, ksteps, status (int32)
+    const size_t KN = KK * N, o_ct = 19 * KN, o_oi = o_ct + (ct ? 36 * N : 0), out_words = o_oi + KN + N;
+    CallBuffers B;
+    double *d_in = nullptr, *d_out = nullptr;
+    if (int rc = B.put(c, &d_in, (const double *)hin.get(), in_words)) return rc;
+    if (int rc = B.get(c, &d_out, out_words)) return rc;
+    const int32_t *d_int = (const int32_t *)(d_in + o_int);
+    int32_t *d_oi = (int32_t *)(d_out + o_oi);
+    PathArgs a;
+    a.n = n;
+    a.K = K;
+    a.dload = d_in;
+    a.dl_stride = shared ? 0 : 6;
+    a.control = control ? d_int : nullptr;
+    a.sig0 = sig0 ? d_in + o_s0 : nullptr;
+    a.epl0 = epl0 ? d_in + o_e0 : nullptr;
+    a.maxit = maxit;
+    a.newton = newton;
+    a.stol = stol;
+    a.eps_cap = eps_cap;
+    a.sig = d_out;
+    a.epl = d_out + 6 * KN;
+    a.deps = d_out + 12 * KN;
+    a.fy = d_out + 18 * KN;
+    a.ct = ct ? d_out + o_ct : nullptr;
+    a.nsteps = d_oi;
+    a.newton_out = d_oi + KN;
+    a.ksteps = d_oi + 2 * KN;
+    a.status = d_oi + 2 * KN + N;
+    EvPair *ev;
+    tim_begin(c, 0, &ev);
+    if (row)
+        launch_path_row(c, mat, field ? d_int + (control ? N : 0) : nullptr, a);
+    else if (kind == 1)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_batch<1>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, mat, a);
+    else if (kind == 2)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_batch<2>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, mat, a);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_batch<5>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, mat, a);
+    tim_end(c, ev);
+    HIPCHK(c, hipGetLastError());
+    c->path_launches++;
+    // one copy out: straight into the caller's arrays where they lie in one block in the order of the device buffer (the Python
+    // binding's do), else through a staging block
+    const bool packed = epl == sig + 6 * KN && deps == sig + 12 * KN && fy == sig + 18 * KN && (!ct || ct == sig + o_ct) &&
+                        (const void *)nsteps == (const void *)(sig + o_oi) && newton_out == nsteps + KN &&
+                        ksteps == nsteps + 2 * KN && status == ksteps + N;
+    std::unique_ptr<double[]> hout(packed ? nullptr : new double[out_words]);
+    HIPCHK(c, hipMemcpyAsync(packed ? sig : hout.get(), d_out, out_words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
+    if (packed) return PLFX_OK;
+    memcpy(sig, hout.get(), KN * 48);
+    memcpy(epl, hout.get() + 6 * KN, KN * 48);
+    memcpy(deps, hout.get() + 12 * KN, KN * 48);
+    memcpy(fy, hout.get() + 18 * KN, KN * 8);
+    if (ct) memcpy(ct, hout.get() + o_ct, N * 288);
+    const int32_t *hoi = (const int32_t *)(hout.get() + o_oi);
+    memcpy(nsteps, hoi, KN * 4);
+    memcpy(newton_out, hoi + KN, KN * 4);
+    memcpy(ksteps, hoi + 2 * KN, N * 4);
+    memcpy(status, hoi + 2 * KN + N, N * 4);
+    return PLFX_OK;
+}
+
+int plfx_load_path_info(plfx_ctx *c, int64_t *launches)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (launches) *launches = c->path_launches;
+    return PLFX_OK;
+}
+
 // A committee of SVC yield functions on n shared unit stresses: all members in ONE launch of k_committee_yf, mean and
 // variance over the members per point, and the point of largest variance (the blocks' partials are closed here, in block
 // order: a strictly larger variance replaces, so equal variances resolve to the smaller index).

@@ -15,6 +15,7 @@
 #include "../../include/plfx.h"
 #include "plfx_kernels.hpp"
 #include "plfx_tex.hpp"   // TexSvcPar (its kernels are templates: nothing is compiled where nothing launches them)
+#include "plfx_path.hpp"  // PathArgs and the load-path kernels (templates as well)
 
 #include <dlfcn.h>
 #include <algorithm>
@@ -25,6 +26,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -102,6 +104,7 @@ struct plfx_ctx {
     int64_t tex_yf_launches = 0, tex_ray_launches = 0;
     int64_t tex_fgrad_launches = 0, tex_full_launches = 0, tex_resp_launches = 0;   // the flow-rule calls
     int64_t flow_launches = 0;        // k_flow_curve / k_flow_curve_analytic launches of this context (plfx_flow_info)
+    int64_t path_launches = 0;        // k_path_batch / k_path_row launches of this context (plfx_load_path_info)
     // texture fields (plfx_set_svc_textures): coefficient rows of material k, a PLFX_SVC6_COLS record; coef and sabs are
     // owned device memory, ids is filled in per launch.  tex_ids / htex_ids: the row of every owned element (null / empty: row 0),
     // checked against the attached rows by tex_field_check before a sweep or calc_scf (tex_ids_ok: since the last change of either)
@@ -619,6 +622,7 @@ int split_res_sig(plfx_ctx *c);
 int raise_step_lds(plfx_ctx *c);
 void launch_response_row(plfx_ctx *c, int k, const int32_t *tex_id, int n, const int32_t *mat_id, const double *sig, const double *epl,
                          const double *deps, double *fy, double *sig_out, double *depl, double *ct, int32_t *nsteps);   // k_response_row
+void launch_path_row(plfx_ctx *c, int k, const int32_t *tex_id, const PathArgs &a);   // k_path_row
 void launch_tangent_expand(plfx_ctx *c, double *out, int to_full);
 #ifdef PLFX_PROF_REGIONS
 bool prof_regions_add(unsigned long long h[16]);   // h += the step unit's g_prof (probe builds; plfx_destroy prints the sums)

@@ -101,8 +101,20 @@ int raise_step_lds(plfx_ctx *c)
             HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true>, c->svc_wave_lds));
             HIPCHK(c, set_dyn_lds((const void *)k_response_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
         }
+        HIPCHK(c, set_dyn_lds((const void *)k_path_row<true>, c->svc_wave_lds));
+        if (c->svc_cols_mask & c->svc_row_lds) {
+            HIPCHK(c, set_dyn_lds((const void *)k_path_row<true, true>, c->svc_wave_lds));
+            HIPCHK(c, set_dyn_lds((const void *)k_path_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
+        }
     }
     return 0;
+}
+
+// The load paths of row-kernel material k (plfx_load_path, plfx.hip): here for the reason given at launch_response_row, and
+// behind every other row kernel of this file, so that theirs are named first.  Grid as k_response_row.
+void launch_path_row(plfx_ctx *c, int k, const int32_t *tex_id, const PathArgs &a)
+{
+    LAUNCH_ROW1(c, k, tex_id, k_path_row, dim3(std::max(1, std::min((a.n + 31) / 32, 1024))), c->dmat, c->nmat, k, a);
 }
 
 }  // namespace host

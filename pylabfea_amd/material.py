@@ -437,6 +437,9 @@ class Material(object):
                              '(material.py:3292); texture_loci traces the loci',
         'yield_slices': "the reference's plot_yield_locus calls calc_yf without a texture and raises ValueError (material.py:3017)",
         'Committee': 'the reference example forms committees of texture-free yield functions only',
+        'load_path': 'the reference has no response for a texture material (material.py:252); at_texture(tex) binds the '
+                     'material to one texture and at_textures(tex) to a field of them, and the bound material follows a '
+                     'path (DESIGN.md §40)',
         'Model.assign': 'the reference fails in Model.solve, whose response calls pass no texture (model.py:1343); '
                         'at_texture(tex) binds the material to one texture, and a model takes the bound material (DESIGN.md §34)',
     }
@@ -1533,6 +1536,122 @@ class Material(object):
         if single:
             out = {k: v[0] for k, v in out.items()}
         return out
+
+    # ------------------------------------------------------------------ load paths of a material point
+    @staticmethod
+    def _path_control(control):
+        """``control`` of load_path -- None, (6,) or (N,6) of bools -- as (None | (1,) | (N,) int32 bit masks, N or None)"""
+        if control is None:
+            return None, None
+        m = np.asarray(control)
+        if m.dtype.kind != 'b' or m.shape[-1:] != (6,) or m.ndim not in (1, 2):
+            raise ValueError('load_path: control must be None, (6,) or (N, 6) of bools (True: the component of dload is a '
+                             'stress increment); got dtype %s, shape %s' % (m.dtype, m.shape))
+        bits = (m.reshape(-1, 6).astype(np.int32) << np.arange(6, dtype=np.int32)).sum(axis=1).astype(np.int32)
+        return bits, (len(bits) if m.ndim == 2 else None)
+
+    def load_path(self, dload, control=None, sig0=None, epl0=None, CV=None, maxit=50, newton=30, stol=None, eps_cap=0.05,
+                  tex_id=None, return_tangent=False):
+        """EXTENSION: material points driven along load paths, every path in one launch -- what the reference's
+        ``examples/UMAT/calc_properties.py`` hands to a one-element block of an FE code: uniaxial and biaxial curves,
+        r-values, plane-strain compression, cyclic paths.  ``dload`` is (K,N,6): K increments of N points, or (K,6), one path
+        shared by the points, whose number then comes from ``sig0`` / ``epl0`` / ``tex_id`` / a 2-d ``control`` (else 1).
+        ``control``: None (every component a strain increment), (6,) or (N,6) of bools; True makes that component of
+        ``dload`` a stress increment.  The mask is constant along a path.  With S the strain- and F the stress-controlled
+        components, the stress target is ``t_k[F] = t_{k-1}[F] + dload[k][F]`` with ``t_{-1} = sig0[F]`` -- ``np.cumsum``
+        started at ``sig0`` has its bits.  One step, from ``(sig, epl)`` and the tangent ``Ct`` of the last accepted step
+        (``CV`` before the first): ``deps[S] = dload[k][S]``; ``deps[F]`` solves ``Ct_FF deps_F = (t_k - sig)[F] - Ct_FS
+        deps_S``; the trial is ``response(sig, epl, deps, CV, maxit)``, accepted when F is empty or ``max|sig'[F] - t_k[F]|
+        <= stol`` (default ``1e-9 sy``); else ``deps[F] -= Ct'_FF^-1 (sig'[F] - t_k[F])`` and the trial is repeated from the
+        same state, at most ``newton`` times.  Then ``sig = sig'``, ``epl += depl``, ``Ct = Ct'``.  No trial is evaluated on
+        an increment that is not finite or has a component beyond ``eps_cap``: the path ends there.  An elastic material
+        answers a trial with ``sig + CV deps``.
+
+        Returns a dict, step-major: ``sig``, ``epl`` (K,N,6) the state after each step -- with strain control alone the bits
+        of K ``response_batch`` calls with ``epl += depl`` in between --, ``deps`` (K,N,6) the increment taken, ``fy`` (K,N)
+        and ``nsteps`` (K,N) of the accepted trial, ``newton`` (K,N) corrections taken, ``ksteps`` (N,) steps completed,
+        ``status`` (N,): 0 complete, 1 ``stol`` not reached within ``newton`` corrections, 2 a pivot of the masked tangent
+        zero or not finite, 3 ``deps`` not finite or beyond ``eps_cap``; with ``return_tangent`` also ``ct`` (N,6,6), the
+        tangent after the last completed step.  Steps from ``ksteps`` on hold NaN (-1 in the int arrays).  A path that ends
+        early is a result, not an error: its completed steps are those of the same path cut to ``ksteps`` steps.
+        Neither ``khard`` nor ``msg`` is touched.
+
+        Limit: full stress control across the yield point of a weakly hardening material ends with status 1 (the elastic
+        tangent overshoots, the plastic one is nearly singular); drive at least one component by strain there.
+
+        Offered for elastic, Hill / J2 / Drucker (``sdim`` 6 and 3), Barlat with ``enable_barlat_normal`` and 6-feature ML
+        yield functions, materials bound to a texture and texture fields (``tex_id``: int or (N,)) included.
+        ``NotImplementedError`` for ``sdim = 3`` ML yield functions, work-hardening ML yield functions, ``ML_grad``, a
+        parent texture material, Tresca and Barlat without a flow rule."""
+        if getattr(self, '_bound', None) is None:
+            self._tex_refuse('load_path')
+        self._no_svr_gradient('load_path')
+        if self.ML_yf and self.sdim != 6:
+            raise NotImplementedError('load_path: not offered for sdim = 3 ML yield functions; only the 6-feature SVC runs on '
+                                      'the row kernels that follow a path')
+        if self.ML_yf and getattr(self, 'whdat', False):
+            raise NotImplementedError('load_path: not offered for work-hardening ML yield functions, whose khard is carried '
+                                      'from one gradient evaluation to the next; flow_curve follows their hardening')
+        if not self.ML_yf and self.sy is not None and (self.tresca or (self.barlat and not getattr(self, 'barlat_normal', False))):
+            raise NotImplementedError('load_path: %s has no flow rule (calc_fgrad raises in the reference, material.py:822-825)%s'
+                                      % ('Tresca' if self.tresca else 'Barlat',
+                                         '' if self.tresca else '; enable_barlat_normal() gives Barlat one'))
+        d = np.asarray(dload, dtype=float)
+        if d.ndim not in (2, 3) or d.shape[-1] != 6:
+            raise ValueError('load_path: dload must be (K, N, 6), or (K, 6) shared by the points; got shape %s' % (d.shape,))
+        bits, nc = self._path_control(control)
+        sizes = {}
+        if d.ndim == 3:
+            sizes['dload'] = d.shape[1]
+        if nc is not None:
+            sizes['control'] = nc
+        rows = {}
+        for name, a in (('sig0', sig0), ('epl0', epl0)):
+            if a is None:
+                continue
+            a = np.asarray(a, dtype=float)
+            if a.shape[-1:] != (6,) or a.ndim not in (1, 2):
+                raise ValueError('load_path: %s must be None, (6,) or (N, 6); got shape %s' % (name, a.shape))
+            if a.ndim == 2:
+                sizes[name] = len(a)
+            rows[name] = a
+        if tex_id is not None and np.ndim(tex_id) == 1:
+            sizes['tex_id'] = len(tex_id)
+        if len(set(sizes.values())) > 1:
+            raise ValueError('load_path: the number of points differs between the arguments: %s'
+                             % ', '.join('%s %d' % kv for kv in sizes.items()))
+        n = next(iter(sizes.values())) if sizes else 1
+        tid = self._tex_ids(tex_id, n, 'load_path')
+        s0, e0 = (None if name not in rows else np.ascontiguousarray(np.broadcast_to(rows[name], (n, 6)))
+                  for name in ('sig0', 'epl0'))
+        if bits is not None:
+            bits = np.ascontiguousarray(np.broadcast_to(bits, (n,)))
+        mixed = bits is not None and bool(np.any(bits))
+        maxit, newton = int(maxit), int(newton)
+        if maxit < 1:
+            raise ValueError('load_path: maxit must be >= 1')
+        if newton < 0:
+            raise ValueError('load_path: newton must be >= 0')
+        if stol is None:
+            if self.sy is None and mixed:
+                raise ValueError('load_path: stol must be given for a material without yield strength (the default is 1e-9 sy)')
+            stol = 1.e-9 * self.sy if self.sy is not None else 1.
+        stol, eps_cap = float(stol), float(eps_cap)
+        if not (np.isfinite(stol) and stol > 0.):
+            raise ValueError('load_path: stol must be finite and positive')
+        if not (np.isfinite(eps_cap) and eps_cap > 0.):
+            raise ValueError('load_path: eps_cap must be finite and positive')
+        for name, a in (('dload', d), ('sig0', s0), ('epl0', e0)):
+            if a is not None and not np.all(np.isfinite(a)):
+                raise ValueError('load_path: %s must be finite' % name)
+        if d.size:
+            strain = np.ones((n, 6), dtype=bool) if bits is None else ((bits[:, None] >> np.arange(6)) & 1) == 0
+            dd = np.abs(d) if d.ndim == 3 else np.abs(d)[:, None, :]
+            if np.any((dd > eps_cap) & strain[None]):
+                raise ValueError('load_path: a strain increment of dload is beyond eps_cap = %g' % eps_cap)
+        return self._load(CV).load_path(0, np.ascontiguousarray(d), control=bits if mixed else None, sig0=s0, epl0=e0, tex_id=tid,
+                                        maxit=maxit, newton=newton, stol=stol, eps_cap=eps_cap,
+                                        return_tangent=bool(return_tangent))
 
     def data_curve(self, ilc, epl_crit=0.002, return_status=False):
         """What ``plot_lc`` of the reference's ``examples/train_hardening.py`` (lines 135-169; the "Reconstruct Stress-Strain
