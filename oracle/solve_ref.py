@@ -224,8 +224,10 @@ class RefSolver(object):
         peeq = np.sqrt(2. * (np.sum(e[:, 0:3] ** 2, axis=1) + 0.5 * np.sum(e[:, 3:6] ** 2, axis=1)) / 3.)
         return sy + peeq * kh
 
-    # model.py:1036-1067
-    def calc_scf(self, du, sld):
+    # model.py:1036-1058
+    def scf_list(self, du, sld):
+        """the list calc_scf collects: one ratio per plastic element whose trial stress increment counts (sref > 0.1), and the
+        ratios of the elements deep inside the yield locus (yf0 < -0.15) a second time (model.py:1054 and :1058)"""
         deps = self.strain(du)
         dsig = np.einsum('eij,ej->ei', self.elstiff.reshape(-1, 6, 6), deps)
         sc = []
@@ -254,6 +256,11 @@ class RefSolver(object):
                           np.minimum(1., np.sqrt(1.5) * self.sflow(self.epl[sel], sel) / sref))
             sc.extend(hh.tolist())
             sc.extend(hh[low].tolist())  # appended twice (model.py:1054 and :1058)
+        return sc
+
+    # model.py:1036-1067
+    def calc_scf(self, du, sld):
+        sc = self.scf_list(du, sld)
         if len(sc) == 0:
             sc = [1.]
         hh = np.std(sc)

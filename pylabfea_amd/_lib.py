@@ -941,6 +941,11 @@ class Context(object):
         self.wh_unresolved = u.value
         return bool(a.value), b.value, c_.value
 
+    def wh_unresolved_sweeps(self):
+        """sweeps whose carry chain was still changing when the pass cap (PLFX_WH_MAXPASS) ended them"""
+        self.wh_info()
+        return self.wh_unresolved
+
     def wh_carry(self, mat, value=None):
         """the hardening modulus material `mat` holds now (sequential carry); value != None sets it first"""
         g = C.c_double()
