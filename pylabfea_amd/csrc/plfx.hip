@@ -1,15 +1,13 @@
-// plfx.hip -- host side of libplfx.so: context, HBM residency, C-ABI (include/plfx.h) -- all but the sweeps, the load step and the
-// state access, which are plfx_step.hip.  What the two units share is plfx_host.hpp; unit map and the rule that every kernel has
-// one owning unit: DESIGN.md section 39.  This unit owns the kernels of all the groups below but PLFX_UNIT_STEP.
+// plfx.hip -- host side of libplfx.so: context, HBM residency, collectives, mesh and pattern, operator, multigrid, strip engine,
+// boundary conditions, instrumentation.  The sweeps, the load step and the state access are plfx_step.hip, the material tables
+// and the material-point functions plfx_material.hip, the linear solve plfx_solve.hip.  What the four units share is
+// plfx_host.hpp; unit map and the rule that every kernel has one owning unit: DESIGN.md sections 39 and 42.  This unit owns the
+// kernels of the three groups below.
 #define PLFX_UNIT_CONTEXT
-#define PLFX_UNIT_MATERIALS
 #define PLFX_UNIT_MESH
 #define PLFX_UNIT_OPERATOR
-#define PLFX_UNIT_SOLVE
 #include "plfx_host.hpp"
 #include "plfx_mg.hpp"
-#include "plfx_texflow.hpp"
-#include "plfx_flow.hpp"
 
 namespace plfx {
 namespace host {
@@ -77,11 +75,6 @@ hipError_t set_dyn_lds(const void *fn, int bytes)
     return e;
 }
 
-}  // namespace host
-}  // namespace plfx
-
-namespace plfx {
-namespace host {
 
 int fail(plfx_ctx *c, int code, const char *fmt, ...)
 {
@@ -273,42 +266,6 @@ int fetch_results(plfx_ctx *c, const double *src_dev, int n, double *dst_host)
     if (rc) return rc;
     memcpy(dst_host, c->mb_buf, (size_t)8 * n);
     return 0;
-}
-
-// 6x6 symmetric (row-major 36) -> 21
-void pack_sym(const double *A, double *S)
-{
-    for (int i = 0; i < 6; i++)
-        for (int j = i; j < 6; j++) S[sym_idx(i, j)] = A[i * 6 + j];
-}
-
-// inverse of the leading n x n block (n = 2 or 3) by Gauss-Jordan with partial pivoting
-bool inv_small(const double *A, int lda, int n, double *Ai)
-{
-    double w[3][6];
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) {
-            w[i][j] = A[i * lda + j];
-            w[i][n + j] = (i == j) ? 1. : 0.;
-        }
-    for (int col = 0; col < n; col++) {
-        int piv = col;
-        for (int r = col + 1; r < n; r++)
-            if (std::fabs(w[r][col]) > std::fabs(w[piv][col])) piv = r;
-        if (w[piv][col] == 0.) return false;
-        if (piv != col)
-            for (int j = 0; j < 2 * n; j++) std::swap(w[col][j], w[piv][j]);
-        const double d = w[col][col];
-        for (int j = 0; j < 2 * n; j++) w[col][j] /= d;
-        for (int r = 0; r < n; r++)
-            if (r != col) {
-                const double fct = w[r][col];
-                for (int j = 0; j < 2 * n; j++) w[r][j] -= fct * w[col][j];
-            }
-    }
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) Ai[i * n + j] = w[i][n + j];
-    return true;
 }
 
 // Gauss point i of the Q4 element (model.py:339-346)
@@ -566,39 +523,6 @@ void free_mesh(plfx_ctx *c)
     c->tex_ids_ok = false;
 }
 
-void free_tex_field(plfx_ctx *c, int k)
-{
-    TexFieldDev &f = c->tex_field[k];
-    if (f.coef) hipFree((void *)f.coef);
-    if (f.sabs) hipFree((void *)f.sabs);
-    f = TexFieldDev();
-    c->tex_field_mask &= ~(1u << k);
-    c->tex_field_rows[k] = 0;
-    c->tex_field_launches[k] = 0;
-    c->tex_ids_ok = false;
-}
-
-void free_svr_flow(plfx_ctx *c, int k)
-{
-    SvrFlowDev &f = c->svr_flow[k];
-    if (f.X) hipFree((void *)f.X);
-    if (f.coef) hipFree((void *)f.coef);
-    f = SvrFlowDev();
-    c->svr_mask &= ~(1u << k);
-    c->svr_launches[k] = 0;
-}
-
-void free_materials(plfx_ctx *c)
-{
-    for (int k = 0; k < MAXMAT; k++) free_svr_flow(c, k);   // a rule belongs to the material it was attached to
-    for (int k = 0; k < MAXMAT; k++) free_tex_field(c, k);  // ... and so does a texture field
-    for (double *p : c->dsv) hipFree(p);
-    c->dsv.clear();
-    dfree(c->dmat);
-    c->hmat.clear();
-    c->nmat = 0;
-}
-
 int ensure_tmp(plfx_ctx *c, size_t n)
 {
     if (n <= c->tmp_cap) return 0;
@@ -634,10 +558,15 @@ bool tail_mf(const plfx_ctx *c)
     return matfree(c) && c->mg_tail_T > 0 && c->mg_tail_E > 0 && c->mg_nu == 2 && !c->mg.empty() && c->mg.back().ainv;
 }
 
-int plain_spmv(plfx_ctx *c, const double *in, double *out)
+void launch_spmv_plain(plfx_ctx *c, const double *in, double *out, CgScalars *sc)
 {
     LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(c->grid_nodes), c->op, 0, c->nnode, (const double2 *)in, nullptr, nullptr,
-               (double2 *)out, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0);
+               (double2 *)out, nullptr, nullptr, nullptr, 0, nullptr, sc, 0, 0, 0);
+}
+
+int plain_spmv(plfx_ctx *c, const double *in, double *out)
+{
+    launch_spmv_plain(c, in, out, nullptr);
     HIPCHK(c, hipGetLastError());
     return 0;  // the matrix is replicated on every rank: no collective here
 }
@@ -1172,8 +1101,7 @@ int mg_vcycle_head(plfx_ctx *c)
 int mg_vcycle_rest(plfx_ctx *c, double *rz_part, bool *wrote)
 {
     if (c->strip_jacobi) {  // Jacobi fall-back of a strip: same PCG loop, same exchanges, z = D^-1 r on the local grid
-        hipLaunchKernelGGL(k_jacobi_z, dim3(grid_for(c->nnode)), dim3(BLOCK), 0, c->stream, c->nnode, (const double2 *)c->dinv,
-                           (const double2 *)c->r, (double2 *)c->z, c->sc);
+        launch_jacobi_z(c);
         HIPCHK(c, hipGetLastError());
         return 0;
     }
@@ -1346,7 +1274,13 @@ void plane_off(plfx_ctx *c, int why)
     c->plane_cols = false;
 }
 
-// ---- launches of this unit's kernels on behalf of the step unit (one owner per kernel)
+// ---- launches of this unit's kernels on behalf of the step and solve units (one owner per kernel)
+void launch_jacobi_z(plfx_ctx *c)
+{
+    hipLaunchKernelGGL(k_jacobi_z, dim3(grid_for(c->nnode)), dim3(BLOCK), 0, c->stream, c->nnode, (const double2 *)c->dinv,
+                       (const double2 *)c->r, (double2 *)c->z, c->sc);
+}
+
 void launch_mbox_post(plfx_ctx *c, const double *src, int n, double *dst, CgMbox *mb, unsigned long long seq)
 {
     hipLaunchKernelGGL(k_mbox_post, dim3(1), dim3(BLOCK), 0, c->stream, src, n, dst, mb, seq);
@@ -1369,8 +1303,6 @@ void launch_spec_setup(plfx_ctx *c)
 
 }  // namespace host
 }  // namespace plfx
-
-#include "plfx_svm.hpp"
 
 extern "C" {
 
@@ -1446,9 +1378,9 @@ void plfx_destroy(plfx_ctx *c)
     if (c->stream) stream_sync(c);
 #ifdef PLFX_PROF_REGIONS
     {
-        unsigned long long h[16];
-        // (g_prof is a device variable per unit: this unit's copy plus the step unit's, whose kernels hold most of the regions)
-        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_prof), sizeof(h)) == hipSuccess && prof_regions_add(h) && h[7]) {
+        unsigned long long h[16] = {0};
+        // (g_prof is a device variable per unit: the copies of the two units whose kernels hold regions)
+        if (prof_regions_add_step(h) && prof_regions_add_material(h) && h[7]) {
             static const char *nm[8] = {"fgrad", "plain", "ray_sample pass", "ray_sample post", "march", "brentq", "full() in corrector", "corrector loop"};
             for (int i = 0; i < 8; i++) fprintf(stderr, "[prof] %-22s %14llu ticks  %5.1f %% of the corrector loop\n", nm[i], h[i], 100. * h[i] / h[7]);
             fprintf(stderr, "[prof] rows: ray searches %llu, direct evaluations %llu (no polynomial %llu, outside its interval %llu, inside the margin %llu), of the outside ones: below lo %llu, at brentq iterates %llu, at the start point %llu\n",
@@ -1523,1296 +1455,6 @@ int plfx_sync(plfx_ctx *c)
 {
     if (!c || !c->stream) return PLFX_ERR_STATE;
     HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// ------------------------------------------------------------------------------ materials
-// Plane columns.  The closure argument asks of every material of the table, used or not: elastic or analytic Hill /
-// J2 (the kinds whose gradient takes components 3 and 4 from components 3 and 4 alone), CV and SV exactly 0.0 between
-// {xx, yy, zz, xy} and {yz, zx}, and everything that multiplies a zero of those columns finite (0 * inf is not 0).
-static bool plane_materials_ok(const std::vector<MatDev> &mats)
-{
-    for (const MatDev &m : mats) {
-        if (m.kind != PLFX_ELASTIC && m.kind != PLFX_HILL6) return false;
-        for (int i : {0, 1, 2, 5})
-            for (int j : {3, 4})
-                if (m.CV[sym_idx(i, j)] != 0. || m.SV[sym_idx(i, j)] != 0.) return false;
-        for (const double *T : {m.CV, m.SV})
-            if (!std::isfinite(T[sym_idx(3, 3)]) || !std::isfinite(T[sym_idx(4, 4)]) || !std::isfinite(T[sym_idx(3, 4)])) return false;
-        if (!std::isfinite(m.hill[3]) || !std::isfinite(m.hill[4]) || !std::isfinite(m.sy) || !std::isfinite(m.khard) ||
-            !std::isfinite(m.d0))
-            return false;
-    }
-    return !mats.empty();
-}
-
-int plfx_set_materials(plfx_ctx *c, int nmat, const plfx_material *mats)
-{
-    if (!c || !c->stream) return PLFX_ERR_STATE;
-    if (nmat < 1 || nmat > MAXMAT || !mats) return fail(c, PLFX_ERR_ARG, "nmat must be in 1..%d", MAXMAT);
-    if (c->tan_buf && c->dmat && c->nel > 0) {
-        // eps and res_sig as stored fields before the tables they were deferred under go away
-        int rcs;
-        if ((rcs = ensure_eps(c)) || (rcs = split_res_sig(c))) return rcs;
-        c->res_fresh = false;
-        // the tangent store refers to the CV of the current materials: hold every stored tangent in full form first
-        launch_tangent_expand(c, c->elstiff, 1);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, stream_sync(c));
-    }
-    free_materials(c);
-    c->has_svc = c->has_svc3 = c->has_analytic = c->has_elastic = c->has_princ = false;
-    c->has_barlat = false;
-    c->has_svcwh = false;
-    c->plane_mats_ok = false;
-    c->n_noflow = 0;
-    c->svc_lds_need = 0;
-    c->svc_row_all = c->svc_row_lds = c->svc6_mask = c->svcwh_mask = c->svc_cols_mask = 0;
-    c->svc_wave_lds = 0;
-    c->n_svc6 = 0;
-    c->nonlin = false;
-    c->hmat.resize(nmat);
-    bool wave_pad = false;
-    for (int k = 0; k < nmat; k++) {
-        const plfx_material &s = mats[k];
-        MatDev &m = c->hmat[k];
-        memset(&m, 0, sizeof(m));
-        if (s.kind < PLFX_ELASTIC || s.kind > PLFX_SVC6_COLS)
-            return fail(c, PLFX_ERR_ARG, "material %d: unknown kind %d", k, s.kind);
-        for (int i = 0; i < 6; i++)
-            for (int j = i + 1; j < 6; j++)
-                if (std::fabs(s.CV[i * 6 + j] - s.CV[j * 6 + i]) >
-                    1e-9 * (std::fabs(s.CV[i * 6 + j]) + std::fabs(s.CV[j * 6 + i]) + 1e-300))
-                    return fail(c, PLFX_ERR_ARG, "material %d: CV must be symmetric", k);
-        pack_sym(s.CV, m.CV);
-        // compliance of the scale-back step (material.py:315-320)
-        double SV[36] = {0.};
-        const int nb = (s.CV[2 * 6 + 2] > 1.) ? 3 : 2;
-        double hh[9];
-        if (!inv_small(s.CV, 6, nb, hh)) return fail(c, PLFX_ERR_ARG, "material %d: singular CV block", k);
-        for (int i = 0; i < nb; i++)
-            for (int j = 0; j < nb; j++) SV[i * 6 + j] = hh[i * nb + j];
-        for (int i = 3; i < 6; i++)
-            if (s.CV[i * 6 + i] > 1.) SV[i * 6 + i] = 1. / s.CV[i * 6 + i];
-        // symmetrise round-off of the Gauss-Jordan inverse
-        for (int i = 0; i < 6; i++)
-            for (int j = i + 1; j < 6; j++) SV[i * 6 + j] = SV[j * 6 + i] = 0.5 * (SV[i * 6 + j] + SV[j * 6 + i]);
-        pack_sym(SV, m.SV);
-        for (int i = 0; i < 6; i++) m.hill[i] = (s.kind == PLFX_ELASTIC) ? 1. : s.hill[i];
-        m.sy = s.sy;
-        m.khard = s.khard;
-        m.d0 = (s.kind == PLFX_ELASTIC) ? 0. : s.drucker;
-        m.E = s.E;
-        m.nu = s.nu;
-        m.kind = s.kind;
-        m.sdim = (s.kind == PLFX_PRINC3 || s.kind == PLFX_SVC3) ? 3 : 6;
-        for (int i = 0; i < 18; i++) m.barlat[i] = s.barlat[i];
-        m.barlat_exp = s.barlat_exp;
-        m.barlat_normal = (s.kind == PLFX_BARLAT && s.barlat_normal) ? 1 : 0;
-        if (s.kind != PLFX_ELASTIC) c->nonlin = true;
-        if (s.kind == PLFX_HILL6) c->has_analytic = true;
-        if (s.kind == PLFX_PRINC3) c->has_princ = true;
-        if (s.kind == PLFX_ELASTIC) c->has_elastic = true;
-        if (s.kind == PLFX_BARLAT && s.barlat_normal) c->has_barlat = true;
-        if (s.kind == PLFX_TRESCA || (s.kind == PLFX_BARLAT && !s.barlat_normal)) c->n_noflow++;
-        const bool cols = (s.kind == PLFX_SVC6_COLS);
-        if (s.kind == PLFX_SVC6 || s.kind == PLFX_SVC3 || s.kind == PLFX_SVC_WH || cols) {
-            const int nf = (s.kind == PLFX_SVC6 || cols) ? 6 : (s.kind == PLFX_SVC3) ? 2 : 15;
-            if (s.kind == PLFX_SVC_WH && !(s.scale_wh > 0.)) return fail(c, PLFX_ERR_ARG, "material %d: scale_wh must be positive", k);
-            if (s.nsv < 1 || s.nfeat != nf || !s.sv || !s.dual)
-                return fail(c, PLFX_ERR_ARG, "material %d: SVC needs nsv>=1, nfeat==%d, sv and dual", k, nf);
-            double *dsv = nullptr, *ddu = nullptr;
-            HIPCHK(c, hipMalloc((void **)&dsv, (size_t)s.nsv * nf * 8));
-            c->dsv.push_back(dsv);
-            HIPCHK(c, hipMalloc((void **)&ddu, (size_t)s.nsv * 8));
-            c->dsv.push_back(ddu);
-            HIPCHK(c, hipMemcpy(dsv, s.sv, (size_t)s.nsv * nf * 8, hipMemcpyHostToDevice));
-            HIPCHK(c, hipMemcpy(ddu, s.dual, (size_t)s.nsv * 8, hipMemcpyHostToDevice));
-            m.sv = dsv;
-            m.dual = ddu;
-            m.nsv = s.nsv;
-            m.nfeat = nf;
-            m.dev_only = s.dev_only;
-            m.gamma = s.gamma;
-            m.intercept = s.intercept;
-            m.scale_seq = s.scale_seq;
-            m.scale_wh = (s.kind == PLFX_SVC_WH) ? s.scale_wh : 1.;
-            for (int i = 0; i < s.nsv; i++) {
-                double vv = 0.;
-                for (int f = 0; f < nf; f++) vv += s.sv[(size_t)i * nf + f] * s.sv[(size_t)i * nf + f];
-                m.svc_vvmax = std::max(m.svc_vvmax, vv);
-                m.svc_sabs += std::fabs(s.dual[i]);
-            }
-            if (cols) {
-                // the row kernels alone run this kind (none of the thread-per-point tables or flags): every column scale is
-                // scale_seq until plfx_set_svc_cols says otherwise
-                if (!(s.scale_seq > 0.) || !std::isfinite(s.scale_seq))
-                    return fail(c, PLFX_ERR_ARG, "material %d: scale_seq must be finite and positive", k);
-                for (int j = 0; j < 6; j++) m.col_inv[j] = 1. / s.scale_seq;
-                c->svc_cols_mask |= 1u << k;
-            } else {
-                if (s.nsv * (nf + 1) <= c->lds_doubles) c->svc_lds_need = std::max(c->svc_lds_need, s.nsv * (nf + 1));
-                if (s.kind == PLFX_SVC6) c->has_svc = true; else if (s.kind == PLFX_SVC3) c->has_svc3 = true; else c->has_svcwh = true, c->svcwh_mask |= 1u << k;
-            }
-            if (s.kind == PLFX_SVC6 || cols) {
-                if (!cols) {
-                    c->n_svc6++;
-                    c->svc6_mask |= 1u << k;
-                }
-                if (c->want_svc_wave || cols) {
-                    // the tables of the row kernels in device memory, in the layout of their LDS copy (stage_svc_row): read from
-                    // there by the kernels when the material has more support vectors than the LDS of a CU holds
-                    const int rp = (s.nsv + 63) & ~63;
-                    std::vector<double> T((size_t)9 * rp + SVC_WAVE_EXTRA, 0.);
-                    for (int i = 0; i < s.nsv; i++) {
-                        double vv = 0.;
-                        for (int f = 0; f < 6; f++) {
-                            T[(size_t)f * rp + i] = s.sv[(size_t)i * 6 + f];
-                            vv = std::fma(s.sv[(size_t)i * 6 + f], s.sv[(size_t)i * 6 + f], vv);
-                        }
-                        T[(size_t)6 * rp + i] = s.dual[i];
-                        T[(size_t)7 * rp + i] = vv;
-                    }
-                    double *ext = T.data() + (size_t)9 * rp;
-                    memcpy(ext, RAYPOLY_MT_HOST, sizeof(double) * RAYPOLY_N * RAYPOLY_N);
-                    double a = 1., b = 1.;
-                    for (int i = 0; i < 64; i++) {
-                        ext[RAYPOLY_N * RAYPOLY_N + i] = a;
-                        ext[RAYPOLY_N * RAYPOLY_N + 64 + i] = b;
-                        a *= 0.98;
-                        b *= 1.02;
-                    }
-                    double *dT = nullptr;
-                    HIPCHK(c, hipMalloc((void **)&dT, T.size() * 8));
-                    c->dsv.push_back(dT);
-                    HIPCHK(c, hipMemcpy(dT, T.data(), T.size() * 8, hipMemcpyHostToDevice));
-                    m.rowtab = dT;
-                    m.rowpad = rp;
-                    c->svc_row_all |= 1u << k;
-                    // v[6], dual, |v|^2, one unused slot + the tables of the sampled-ray form, the vectors padded to 64 (up to
-                    // 2176 vectors fit the 160 KB of a CU)
-                    if (9 * rp + SVC_WAVE_EXTRA <= c->lds_doubles) {
-                        c->svc_row_lds |= 1u << k;
-                        c->svc_wave_lds = std::max(c->svc_wave_lds, (9 * rp + SVC_WAVE_EXTRA) * 8);
-                    }
-                    // kept from the removed wave kernels (tables padded to 256, first fitting material): shrinking it changes the launch
-                    const int npad = (s.nsv + 255) & ~255;
-                    if (9 * npad + SVC_WAVE_EXTRA <= c->lds_doubles && npad <= 2048 && !wave_pad && !cols) {
-                        wave_pad = true;
-                        c->svc_wave_lds = std::max(c->svc_wave_lds, (9 * npad + SVC_WAVE_EXTRA) * 8);
-                    }
-                }
-            }
-        }
-    }
-    c->nmat = nmat;
-    c->plane_mats_ok = plane_materials_ok(c->hmat);
-    if (!c->plane_mats_ok) plane_off(c, PLFX_PLANE_MATERIALS);
-    int rc = dalloc(c, &c->dmat, (size_t)nmat);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->dmat, c->hmat.data(), sizeof(MatDev) * nmat, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, stream_sync(c));
-    if (int rcl = raise_step_lds(c)) return rcl;   // the sweep, scf and response row kernels, which the step unit launches
-    if (c->svc_wave_lds > 0) {
-        HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true>, c->svc_wave_lds));
-        if (c->svc_cols_mask & c->svc_row_lds) {
-            HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true>, c->svc_wave_lds));
-            // (a texture field can be attached to any of them)
-            HIPCHK(c, set_dyn_lds((const void *)k_full_yf_row<true, true, true, TexFieldDev>, c->svc_wave_lds));
-        }
-    }
-    if (c->has_svc || c->has_svc3 || c->has_svcwh) {  // opt in to > 64 KiB dynamic LDS for the SVC kernels
-        const int bytes = (int)dyn_lds_bytes(c);
-        HIPCHK(c, set_dyn_lds((const void *)k_response_batch<3>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_response_batch<6>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_point_eval, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_response_batch<7>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_response_svr, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<6>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_hessian_row<15>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<6>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<2>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_yield_scale<15>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_committee_yf, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_flow_curve<6>, bytes));
-        HIPCHK(c, set_dyn_lds((const void *)k_flow_curve<15>, bytes));
-    }
-    c->M_dirty = true;
-    c->memo.valid = false;
-    return PLFX_OK;
-}
-
-// the six column scales of a PLFX_SVC6_COLS material: the record keeps their reciprocals (MatDev::col_inv)
-int plfx_set_svc_cols(plfx_ctx *c, int mat, const double scale[6])
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
-    if (mat < 0 || mat >= c->nmat || !scale) return fail(c, PLFX_ERR_ARG, "plfx_set_svc_cols: bad argument");
-    if (c->hmat[mat].kind != PLFX_SVC6_COLS)
-        return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_set_svc_cols: material %d is of kind %d; column scales belong to a "
-                    "PLFX_SVC6_COLS material only", mat, c->hmat[mat].kind);
-    for (int j = 0; j < 6; j++)
-        if (!std::isfinite(scale[j]) || !(scale[j] > 0.))
-            return fail(c, PLFX_ERR_ARG, "plfx_set_svc_cols: scale %d must be finite and positive", j);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, stream_sync(c));   // no launch may still read the record that changes
-    for (int j = 0; j < 6; j++) c->hmat[mat].col_inv[j] = 1. / scale[j];
-    HIPCHK(c, hipMemcpyAsync(c->dmat + mat, &c->hmat[mat], sizeof(MatDev), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, stream_sync(c));
-    c->memo.valid = false;
-    return PLFX_OK;
-}
-
-// a PLFX_SVC6_COLS material runs on the row kernels alone: what every other point function answers for it
-static int cols_refuse(plfx_ctx *c, int mat, const char *what)
-{
-    if (c && c->dmat && mat >= 0 && mat < c->nmat && c->hmat[mat].kind == PLFX_SVC6_COLS)
-        return fail(c, PLFX_ERR_UNSUPPORTED, "%s: material %d is a PLFX_SVC6_COLS record, which runs on the row kernels only "
-                    "(sweeps, calc_scf, response, ML_full_yf)", what, mat);
-    return PLFX_OK;
-}
-
-// A texture field on a PLFX_SVC6_COLS material: one row of dual coefficients per texture, padded like the row tables
-int plfx_set_svc_textures(plfx_ctx *c, int mat, int ntex, const double *coef)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
-    if (mat < 0 || mat >= c->nmat || ntex < 0 || (ntex > 0 && !coef)) return fail(c, PLFX_ERR_ARG, "plfx_set_svc_textures: bad argument");
-    if (c->hmat[mat].kind != PLFX_SVC6_COLS)
-        return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_set_svc_textures: material %d is of kind %d; a texture field belongs to a "
-                    "PLFX_SVC6_COLS material only", mat, c->hmat[mat].kind);
-    const int nsv = c->hmat[mat].nsv, rp = c->hmat[mat].rowpad;
-    if ((long long)ntex * rp > (long long)INT32_MAX)
-        return fail(c, PLFX_ERR_ARG, "plfx_set_svc_textures: %d rows of %d coefficients are more than INT32_MAX", ntex, rp);
-    for (size_t i = 0; i < (size_t)ntex * nsv; i++)
-        if (!std::isfinite(coef[i]))
-            return fail(c, PLFX_ERR_ARG, "plfx_set_svc_textures: coefficient %zu of row %zu is not finite", i % nsv, i / nsv);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, stream_sync(c));   // no launch may still read the rows that go away
-    free_tex_field(c, mat);
-    if (ntex == 0) return PLFX_OK;
-    std::vector<double> T((size_t)ntex * rp, 0.), S((size_t)ntex, 0.);
-    for (int t = 0; t < ntex; t++)
-        for (int i = 0; i < nsv; i++) {
-            T[(size_t)t * rp + i] = coef[(size_t)t * nsv + i];
-            S[t] += std::fabs(coef[(size_t)t * nsv + i]);
-        }
-    double *dT = nullptr, *dS = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dT, T.size() * 8));
-    c->tex_field[mat].coef = dT;   // (owned from here on: freed by free_tex_field whatever follows)
-    HIPCHK(c, hipMalloc((void **)&dS, S.size() * 8));
-    c->tex_field[mat].sabs = dS;
-    HIPCHK(c, hipMemcpy(dT, T.data(), T.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dS, S.data(), S.size() * 8, hipMemcpyHostToDevice));
-    c->tex_field[mat].stride = rp;
-    c->tex_field_rows[mat] = ntex;
-    c->tex_field_mask |= 1u << mat;
-    return PLFX_OK;
-}
-
-int plfx_set_element_textures(plfx_ctx *c, const int32_t *tex_id)
-{
-    if (!c || !c->sig) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, stream_sync(c));
-    c->tex_ids_ok = false;
-    if (!tex_id) {
-        dfree(c->tex_ids);
-        c->htex_ids.clear();
-        return PLFX_OK;
-    }
-    if (!c->tex_ids)
-        if (int rc = dalloc(c, &c->tex_ids, (size_t)c->nel)) return rc;
-    c->htex_ids.assign(tex_id, tex_id + c->nel);
-    HIPCHK(c, hipMemcpy(c->tex_ids, tex_id, (size_t)c->nel * 4, hipMemcpyHostToDevice));
-    return PLFX_OK;
-}
-
-int plfx_svc_textures_info(plfx_ctx *c, int mat, int *rows, int *staged, int64_t *launches)
-{
-    if (!c || mat < 0 || mat >= MAXMAT) return c ? fail(c, PLFX_ERR_ARG, "material %d out of range", mat) : PLFX_ERR_ARG;
-    if (rows) *rows = c->tex_field_rows[mat];
-    if (staged) *staged = 0;   // the rows are read from device memory
-    if (launches) *launches = c->tex_field_launches[mat];
-    return PLFX_OK;
-}
-
-// the rows of the points of a _tid call: checked on the host for the materials that carry a field
-static int tex_point_check(plfx_ctx *c, int n, int mat, const int32_t *mat_id, const int32_t *tex_id)
-{
-    if (!tex_id || !c->tex_field_mask) return PLFX_OK;
-    for (int i = 0; i < n; i++) {
-        const int k = mat >= 0 ? mat : (mat_id ? mat_id[i] : 0);
-        if (k < 0 || k >= c->nmat || !((c->tex_field_mask >> k) & 1u)) continue;
-        if (tex_id[i] < 0 || tex_id[i] >= c->tex_field_rows[k])
-            return fail(c, PLFX_ERR_ARG, "tex_id[%d] = %d is outside the %d rows of material %d", i, (int)tex_id[i],
-                        c->tex_field_rows[k], k);
-    }
-    return PLFX_OK;
-}
-
-// ------------------------------------------------------------------------------ batched point evaluation
-// the opening check of a point function of one material; args_ok: what the function asks of its other arguments
-static int point_check(plfx_ctx *c, int mat, bool args_ok)
-{
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat || !args_ok) return fail(c, PLFX_ERR_ARG, "bad argument");
-    return PLFX_OK;
-}
-
-// f(std::integral_constant<int, NFP>) for the padded width nfp of a texture set (plfx_tex.hpp): the one place that lists the
-// instantiations of its kernels
-extern "C++" {
-template <class F>
-static void tex_for_nfp(int nfp, F &&f)
-{
-    if (nfp == 8)
-        f(std::integral_constant<int, 8>());
-    else if (nfp == 12)
-        f(std::integral_constant<int, 12>());
-    else
-        f(std::integral_constant<int, 16>());
-}
-}
-
-static int point_eval(plfx_ctx *c, int what, int mat, int n, const double *sig, const double *epl,
-                      const double *ld, double *out, int32_t *status, const int32_t *tex_id = nullptr)
-{
-    if (int rc = point_check(c, mat, n >= 0 && sig && out)) return rc;
-    if (int rc = tex_point_check(c, n, mat, nullptr, tex_id)) return rc;
-    const bool cols = (c->hmat[mat].kind == PLFX_SVC6_COLS);
-    if (cols && what != 3) return cols_refuse(c, mat, what == 0 ? "calc_seq" : what == 1 ? "calc_fgrad" : "calc_yf");
-    if (n == 0) return PLFX_OK;
-    const size_t N = n, wout = (what == 1) ? 6 : 1;
-    CallBuffers B;
-    double *dsig = nullptr, *depl = nullptr, *dout = nullptr, *dld = nullptr;
-    int32_t *dst = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.get(c, &dout, N * wout)) return rc;
-    if (epl)
-        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
-    if (ld)
-        if (int rc = B.put(c, &dld, ld, 6)) return rc;
-    if (status)
-        if (int rc = B.get(c, &dst, N)) return rc;
-    int32_t *d_tid = nullptr;
-    if (tex_id && ((c->tex_field_mask >> mat) & 1u))
-        if (int rc = B.put(c, &d_tid, tex_id, N)) return rc;
-    static const bool wave_full = !(getenv("PLFX_FULL_YF_WAVE") && atoi(getenv("PLFX_FULL_YF_WAVE")) == 0);
-    EvPair *ev;
-    tim_begin(c, 0, &ev);   // family 0 like plfx_response_batch: the kernel alone, without the copies
-    if (what == 3 && (wave_full || cols) && ((c->svc_row_all >> mat) & 1u))  // ML_full_yf of a row-kernel SVC material
-        LAUNCH_ROW1(c, mat, (const int32_t *)d_tid, k_full_yf_row, dim3(std::max(1, std::min((n + 31) / 32, 2048))),
-                   c->dmat, c->nmat, mat, n, dsig, depl, dld, dout, dst);
-    else
-        hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream,
-                           c->dmat, c->nmat, c->svc_lds_need, what, mat, n, dsig, depl, dld, dout, dst);
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, dout, N * wout * 8, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-int plfx_seq_batch(plfx_ctx *c, int mat, int n, const double *sig, double *seq)
-{
-    return point_eval(c, 0, mat, n, sig, nullptr, nullptr, seq, nullptr);
-}
-int plfx_fgrad_batch(plfx_ctx *c, int mat, int n, const double *sig, double *a)
-{
-    if (c && mat >= 0 && mat < c->nmat &&
-        (c->hmat[mat].kind == PLFX_TRESCA || (c->hmat[mat].kind == PLFX_BARLAT && !c->hmat[mat].barlat_normal)))
-        return fail(c, PLFX_ERR_UNSUPPORTED, "calc_fgrad: no analytical gradient for this Tresca / Barlat material (material.py:822-825)");
-    return point_eval(c, 1, mat, n, sig, nullptr, nullptr, a, nullptr);
-}
-int plfx_fgrad_seq_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *seq, double *a)
-{
-    if (int rc = point_check(c, mat, n >= 0 && sig && seq && a)) return rc;
-    const int kind = c->hmat[mat].kind;
-    if (kind != PLFX_HILL6 && kind != PLFX_PRINC3)
-        return fail(c, PLFX_ERR_UNSUPPORTED, "calc_fgrad(seq=...): analytic Hill materials only (material.py:822-847)");
-    if (n == 0) return PLFX_OK;
-    const size_t N = n;
-    CallBuffers B;
-    double *dsig = nullptr, *dseq = nullptr, *dout = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.put(c, &dseq, seq, N)) return rc;
-    if (int rc = B.get(c, &dout, 6 * N)) return rc;
-    hipLaunchKernelGGL(k_fgrad_seq, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->dmat, mat, n, dsig, dseq, dout);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(a, dout, N * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-int plfx_yf_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *yf)
-{
-    return point_eval(c, 2, mat, n, sig, epl, nullptr, yf, nullptr);
-}
-int plfx_full_yf_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl,
-                       const double *ld, double *yf, int32_t *status)
-{
-    return point_eval(c, 3, mat, n, sig, epl, ld, yf, status);
-}
-int plfx_full_yf_batch_tid(plfx_ctx *c, int mat, int n, const double *sig, const double *epl,
-                           const double *ld, double *yf, int32_t *status, const int32_t *tex_id)
-{
-    return point_eval(c, 3, mat, n, sig, epl, ld, yf, status, tex_id);
-}
-
-static int response_batch_impl(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig,
-                               const double *epl, const double *deps, double *fy, double *sig_out,
-                               double *depl, double *ct, int32_t *nsteps, const double *kh_in, double *kh_out,
-                               const int32_t *tex_id = nullptr)
-{
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (n < 0 || !sig || !epl || !deps || !fy || !sig_out || !depl || !ct || !nsteps)
-        return fail(c, PLFX_ERR_ARG, "null argument");
-    if (c->n_noflow) return fail(c, PLFX_ERR_UNSUPPORTED, "a Tresca / Barlat material without flow rule is loaded (material.py:822-825)");
-    if (n == 0) return PLFX_OK;
-    if (mat_id)
-        for (int i = 0; i < n; i++)
-            if (mat_id[i] < 0 || mat_id[i] >= c->nmat) return fail(c, PLFX_ERR_ARG, "mat_id[%d] out of range", i);
-    if (int rc = tex_point_check(c, n, -1, mat_id, tex_id)) return rc;
-    CallBuffers B;
-    double *d_in = nullptr, *d_out = nullptr;
-    int32_t *d_mid = nullptr, *d_ns = nullptr, *d_tid = nullptr;
-    const size_t N = n;
-    if (tex_id && c->tex_field_mask)
-        if (int rc = B.put(c, &d_tid, tex_id, N)) return rc;
-    if (int rc = B.get(c, &d_in, N * 18)) return rc;
-    if (int rc = B.get(c, &d_out, N * (1 + 6 + 6 + 36))) return rc;
-    if (int rc = B.get(c, &d_ns, N)) return rc;
-    HIPCHK(c, hipMemcpyAsync(d_in, sig, N * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in + 6 * N, epl, N * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in + 12 * N, deps, N * 48, hipMemcpyHostToDevice, c->stream));
-    if (mat_id)
-        if (int rc = B.put(c, &d_mid, mat_id, N)) return rc;
-    double *d_fy = d_out, *d_so = d_out + N, *d_dp = d_out + 7 * N, *d_ct = d_out + 13 * N;
-    double *d_kh = nullptr;   // [2N]: entry / exit hardening modulus of the work-hardening SVC points
-    if (c->has_svcwh) {
-        if (int rc = B.get(c, &d_kh, 2 * N)) return rc;
-        std::vector<double> k0(N);
-        for (size_t i = 0; i < N; i++) k0[i] = kh_in ? kh_in[i] : c->hmat[mat_id ? mat_id[i] : 0].khard;
-        HIPCHK(c, hipMemcpyAsync(d_kh, k0.data(), N * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_kh + N, d_kh, N * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, stream_sync(c));
-    }
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-#define RB_ARGS(lds) c->dmat, c->nmat, lds, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so, d_dp, d_ct, d_ns
-#define RB_TAIL (const double *)nullptr, (double *)nullptr, 0u, c->resp_maxit
-    if (c->has_analytic || c->has_elastic)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<1>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, RB_ARGS(0), RB_TAIL);
-    if (c->has_princ)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<2>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, RB_ARGS(0), RB_TAIL);
-    if (c->has_barlat)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<5>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, RB_ARGS(0), RB_TAIL);
-    const bool resp_row = !(getenv("PLFX_RESPONSE_ROW") && atoi(getenv("PLFX_RESPONSE_ROW")) == 0);   // read per call: tests compare the two forms
-    const unsigned rmask = resp_row ? c->svc_row_all : c->svc_cols_mask;   // (PLFX_SVC6_COLS has no other form)
-    if (c->has_svc && (c->svc6_mask & ~rmask))
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<3>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, RB_ARGS(c->svc_lds_need), (const double *)nullptr, (double *)nullptr, rmask, c->resp_maxit);
-    for (int k = 0; k < c->nmat; k++)   // 6-feature SVC materials with tables in LDS: 16 lanes per point (the code path of the sweeps)
-        if ((rmask >> k) & 1u)
-            launch_response_row(c, k, (const int32_t *)d_tid, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so, d_dp, d_ct, d_ns);
-    if (c->has_svc3)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<6>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, RB_ARGS(c->svc_lds_need), RB_TAIL);
-    if (c->has_svcwh && (c->svcwh_mask & ~c->svr_mask))
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_response_batch<7>), dim3(grid_for(N)), dim3(BLOCK), dyn_lds_bytes(c),
-                           c->stream, RB_ARGS(c->svc_lds_need), (const double *)d_kh, d_kh + N, c->svr_mask, c->resp_maxit);
-    for (int k = 0; k < c->nmat; k++)   // work-hardening SVC materials with an SVR flow rule attached: one launch per material
-        if ((c->svr_mask >> k) & 1u) {
-            hipLaunchKernelGGL(k_response_svr, dim3(grid_for(N)), dim3(SVR_FLOW_BLOCK), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat,
-                               c->svc_lds_need, k, c->svr_flow[k], c->svr_flow[k].X, c->svr_flow[k].coef, n, d_mid, d_in, d_in + 6 * N, d_in + 12 * N, d_fy, d_so,
-                               d_dp, d_ct, d_ns, (const double *)d_kh, d_kh + N, c->resp_maxit);
-            c->svr_launches[k]++;
-        }
-#undef RB_ARGS
-#undef RB_TAIL
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(fy, d_fy, N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sig_out, d_so, N * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(depl, d_dp, N * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ct, d_ct, N * 288, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nsteps, d_ns, N * 4, hipMemcpyDeviceToHost, c->stream));
-    if (kh_out) {
-        if (d_kh)
-            HIPCHK(c, hipMemcpyAsync(kh_out, d_kh + N, N * 8, hipMemcpyDeviceToHost, c->stream));
-        else
-            for (size_t i = 0; i < N; i++) kh_out[i] = kh_in ? kh_in[i] : c->hmat[mat_id ? mat_id[i] : 0].khard;
-    }
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-int plfx_response_batch(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig,
-                        const double *epl, const double *deps, double *fy, double *sig_out,
-                        double *depl, double *ct, int32_t *nsteps)
-{
-    return response_batch_impl(c, n, mat_id, sig, epl, deps, fy, sig_out, depl, ct, nsteps, nullptr, nullptr);
-}
-
-int plfx_response_batch_tid(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig,
-                            const double *epl, const double *deps, double *fy, double *sig_out,
-                            double *depl, double *ct, int32_t *nsteps, const int32_t *tex_id)
-{
-    return response_batch_impl(c, n, mat_id, sig, epl, deps, fy, sig_out, depl, ct, nsteps, nullptr, nullptr, tex_id);
-}
-
-int plfx_response_batch_kh(plfx_ctx *c, int n, const int32_t *mat_id, const double *sig, const double *epl,
-                           const double *deps, const double *khard_in, double *fy, double *sig_out, double *depl,
-                           double *ct, int32_t *nsteps, double *khard_out)
-{
-    return response_batch_impl(c, n, mat_id, sig, epl, deps, fy, sig_out, depl, ct, nsteps, khard_in, khard_out);
-}
-
-int plfx_fgrad_batch_wh(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *fgrad, double *khard_raw)
-{
-    if (int rc = point_check(c, mat, n >= 0 && sig && fgrad)) return rc;
-    if (c->hmat[mat].kind != PLFX_SVC_WH) return fail(c, PLFX_ERR_ARG, "material %d has no work-hardening features", mat);
-    if (n == 0) return PLFX_OK;
-    const size_t N = n;
-    CallBuffers B;
-    double *dsig = nullptr, *depl = nullptr, *dout = nullptr, *dkh = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.get(c, &dout, 6 * N)) return rc;
-    if (int rc = B.get(c, &dkh, N)) return rc;
-    if (epl)
-        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    hipLaunchKernelGGL(k_point_eval, dim3(grid_for(n)), dim3(BLOCK), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat,
-                       c->svc_lds_need, 1, mat, n, dsig, depl, (const double *)nullptr, dout, (int32_t *)nullptr, dkh);
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(fgrad, dout, N * 48, hipMemcpyDeviceToHost, c->stream));
-    if (khard_raw) HIPCHK(c, hipMemcpyAsync(khard_raw, dkh, N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// Material.calc_hessian of an SVC material: sibling of point_eval with 36 numbers per point and the row kernel
-int plfx_hessian_batch(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, double *hess)
-{
-    if (int rc = point_check(c, mat, n >= 0 && sig && hess)) return rc;
-    if (int rc = cols_refuse(c, mat, "calc_hessian")) return rc;
-    const int kind = c->hmat[mat].kind;
-    if (kind != PLFX_SVC6 && kind != PLFX_SVC_WH)
-        return fail(c, PLFX_ERR_UNSUPPORTED, kind == PLFX_SVC3 ? "calc_hessian: not implemented for 3D stress (material.py:950)"
-                    : "calc_hessian: no analytical hessian for this Hill / Tresca / Barlat material (material.py:965-970)");
-    if (n == 0) return PLFX_OK;
-    const size_t N = n;
-    CallBuffers B;
-    double *dsig = nullptr, *depl = nullptr, *dout = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.get(c, &dout, 36 * N)) return rc;
-    if (epl && kind == PLFX_SVC_WH)
-        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
-    const dim3 grid = row16_grid(c, n, HESS_BLOCK, 4);   // 64 points per block
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    if (kind == PLFX_SVC6)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hessian_row<6>), grid, dim3(HESS_BLOCK), dyn_lds_bytes(c), c->stream,
-                           c->dmat, c->nmat, c->svc_lds_need, mat, n, dsig, depl, dout);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hessian_row<15>), grid, dim3(HESS_BLOCK), dyn_lds_bytes(c), c->stream,
-                           c->dmat, c->nmat, c->svc_lds_need, mat, n, dsig, depl, dout);
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(hess, dout, N * 288, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// Material.yield_scale: the factor x with calc_yf(x su) = 0 along n unit stresses.  SVC kinds: the search of k_yield_scale,
-// one launch; analytic kinds: the closed form sflow / seq(su).
-int plfx_yield_scale(plfx_ctx *c, int mat, int n, const double *su, const double *epl, const double *x0, double *x,
-                     int32_t *status)
-{
-    if (int rc = point_check(c, mat, n >= 0 && su && x && status)) return rc;
-    if (int rc = cols_refuse(c, mat, "yield_scale")) return rc;
-    const int kind = c->hmat[mat].kind;
-    if (kind == PLFX_ELASTIC) return fail(c, PLFX_ERR_ARG, "yield_scale: material %d has no yield strength", mat);
-    if (n == 0) return PLFX_OK;
-    const size_t N = n;
-    CallBuffers B;
-    double *dsu = nullptr, *depl = nullptr, *dx0 = nullptr, *dx = nullptr;
-    int32_t *dst = nullptr;
-    if (int rc = B.get(c, &dsu, 6 * N)) return rc;
-    if (int rc = B.get(c, &dx, N)) return rc;
-    if (int rc = B.get(c, &dst, N)) return rc;
-    // principal-stress kinds (2-feature SVC, Hill-3 / J2 on principal stresses): rays with out-of-plane shear are reduced to
-    // their principal stresses here, by the LAPACK replay that the device runs for such states (plfx_sig_princ_host); the order
-    // of the principal stresses does not change along a ray.  The kernels then need the closed form of plane states only.
-    // (Material.yield_scale has done the same through _princ_rows, material.py, and nothing is left to reduce for its rays;
-    // this pass serves callers of the C-ABI.)
-    std::vector<double> red;
-    if (kind == PLFX_SVC3 || kind == PLFX_PRINC3)
-        for (int i = 0; i < n; i++) {
-            const double *s = su + 6 * (size_t)i;
-            bool fin = true;
-            for (int k = 0; k < 6; k++) fin = fin && std::isfinite(s[k]);
-            if (!fin || (s[3] == 0. && s[4] == 0.)) continue;
-            if (red.empty()) red.assign(su, su + 6 * (size_t)n);
-            double *r = red.data() + 6 * (size_t)i;
-            lapack3::sig_princ_lapack3(s, r);
-            r[3] = r[4] = r[5] = 0.;
-        }
-    HIPCHK(c, hipMemcpyAsync(dsu, red.empty() ? su : red.data(), N * 48, hipMemcpyHostToDevice, c->stream));
-    if (epl)
-        if (int rc = B.put(c, &depl, epl, 6 * N)) return rc;
-    if (x0)
-        if (int rc = B.put(c, &dx0, x0, N)) return rc;
-    const int block = row16_block(c, n, YS_BLOCK);
-    const dim3 grid = row16_grid(c, n, block, 4);
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-#define YS_LAUNCH(NF)                                                                                                      \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_yield_scale<NF>), grid, dim3(block), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat, \
-                       c->svc_lds_need, mat, n, dsu, depl, dx0, dx, dst)
-    if (kind == PLFX_SVC6)
-        YS_LAUNCH(6);
-    else if (kind == PLFX_SVC3)
-        YS_LAUNCH(2);
-    else if (kind == PLFX_SVC_WH)
-        YS_LAUNCH(15);
-#undef YS_LAUNCH
-#define YS_LAUNCH(KD)                                                                                                       \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_yield_scale_analytic<KD>), dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->dmat, mat, n, \
-                       dsu, depl, dx0, dx, dst)
-    else if (kind == PLFX_PRINC3)
-        YS_LAUNCH(2);
-    else if (kind == PLFX_TRESCA)
-        YS_LAUNCH(4);
-    else if (kind == PLFX_BARLAT)
-        YS_LAUNCH(5);
-    else
-        YS_LAUNCH(1);
-#undef YS_LAUNCH
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(x, dx, N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// Material.flow_curve: n flow curves of up to max_steps steps along the unit stresses su, the whole chains
-// in ONE launch.  SVC kinds: k_flow_curve, 16 lanes per curve; Hill / J2 / Drucker on Voigt stresses: k_flow_curve_analytic.
-int plfx_flow_curve(plfx_ctx *c, int mat, int n, const double *su, const double *epl0, int max_steps, double depl,
-                    double epl_max, double predictor, double *x, double *epl, double *yf, double *hk, int32_t *nsteps,
-                    int32_t *status)
-{
-    if (int rc = point_check(c, mat, n >= 0 && su && x && epl && yf && nsteps && status)) return rc;
-    if (int rc = cols_refuse(c, mat, "flow_curve")) return rc;
-    if (max_steps < 0 || !(depl > 0.) || !std::isfinite(depl) || !std::isfinite(predictor) || epl_max != epl_max)
-        return fail(c, PLFX_ERR_ARG, "flow_curve: max_steps >= 0, a finite depl > 0, a finite predictor and an epl_max that is a number expected");
-    const int kind = c->hmat[mat].kind;
-    if (kind == PLFX_ELASTIC) return fail(c, PLFX_ERR_ARG, "flow_curve: material %d has no yield strength", mat);
-    if (kind != PLFX_HILL6 && kind != PLFX_SVC6 && kind != PLFX_SVC_WH)
-        return fail(c, PLFX_ERR_ARG, "flow_curve: offered for Hill / J2 / Drucker on Voigt stresses and for the 6- and 15-feature SVC; material %d is of kind %d", mat, kind);
-    if (n == 0) return PLFX_OK;
-    const size_t N = n, K1 = (size_t)max_steps + 1, K = (size_t)max_steps;
-    CallBuffers B;
-    double *dsu = nullptr, *de0 = nullptr, *dx = nullptr, *de = nullptr, *dyf = nullptr, *dhk = nullptr;
-    int32_t *dns = nullptr, *dst = nullptr;
-    if (int rc = B.put(c, &dsu, su, 6 * N)) return rc;
-    if (epl0)
-        if (int rc = B.put(c, &de0, epl0, 6 * N)) return rc;
-    if (int rc = B.get(c, &dx, N * K1)) return rc;
-    if (int rc = B.get(c, &de, 6 * N * K1)) return rc;
-    if (int rc = B.get(c, &dyf, N * K1)) return rc;
-    if (hk && K > 0)
-        if (int rc = B.get(c, &dhk, N * K)) return rc;
-    if (int rc = B.get(c, &dns, N)) return rc;
-    if (int rc = B.get(c, &dst, N)) return rc;
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    if (kind == PLFX_HILL6) {
-        hipLaunchKernelGGL(k_flow_curve_analytic, dim3(grid_for(n)), dim3(BLOCK), 0, c->stream, c->dmat, mat, n, dsu, de0,
-                           max_steps, depl, epl_max, predictor, dx, de, dyf, dhk, dns, dst);
-    } else {
-        const int block = row16_block(c, n, YS_BLOCK);
-        const dim3 grid = row16_grid(c, n, block, 4);
-#define FC_LAUNCH(NF)                                                                                                     \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_flow_curve<NF>), grid, dim3(block), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat, \
-                       c->svc_lds_need, mat, n, dsu, de0, max_steps, depl, epl_max, predictor, dx, de, dyf, dhk, dns, dst)
-        if (kind == PLFX_SVC6)
-            FC_LAUNCH(6);
-        else
-            FC_LAUNCH(15);
-#undef FC_LAUNCH
-    }
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->flow_launches++;
-    HIPCHK(c, hipMemcpyAsync(x, dx, N * K1 * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(epl, de, N * K1 * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(yf, dyf, N * K1 * 8, hipMemcpyDeviceToHost, c->stream));
-    if (dhk) HIPCHK(c, hipMemcpyAsync(hk, dhk, N * K * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nsteps, dns, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-int plfx_flow_info(plfx_ctx *c, int64_t *launches)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (launches) *launches = c->flow_launches;
-    return PLFX_OK;
-}
-
-// Material.load_path: n material points of material `mat` along load paths of K increments, every path in
-// ONE launch: k_path_batch for the kinds of k_response_batch<1 | 2 | 5>, k_path_row (launch_path_row, plfx_step.hip) for the
-// 6-feature SVC materials of the row kernels.  One copy in, one copy out.  Everything is checked before anything is launched.
-int plfx_load_path(plfx_ctx *c, int mat, int n, int K, const double *dload, int shared, const int32_t *control,
-                   const double *sig0, const double *epl0, const int32_t *tex_id, int maxit, int newton, double stol,
-                   double eps_cap, double *sig, double *epl, double *deps, double *fy, int32_t *nsteps, int32_t *newton_out,
-                   int32_t *ksteps, int32_t *status, double *ct)
-{
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "load_path: material %d, the context holds %d", mat, c->nmat);
-    const MatDev &hm = c->hmat[mat];
-    const bool row = (hm.kind == PLFX_SVC6 || hm.kind == PLFX_SVC6_COLS) && ((c->svc_row_all >> mat) & 1u);
-    int kind = 0;   // instantiation of k_path_batch
-    if (hm.kind == PLFX_ELASTIC || hm.kind == PLFX_HILL6)
-        kind = 1;
-    else if (hm.kind == PLFX_PRINC3)
-        kind = 2;
-    else if (hm.kind == PLFX_BARLAT && hm.barlat_normal)
-        kind = 5;
-    else if (!row)
-        return fail(c, PLFX_ERR_UNSUPPORTED, "load_path: offered for elastic, Hill / J2 / Drucker materials, Barlat with the native "
-                    "normal and the 6-feature SVC of the row kernels; material %d is of kind %d", mat, hm.kind);
-    if (n < 0 || K < 0) return fail(c, PLFX_ERR_ARG, "load_path: n >= 0 and K >= 0 expected");
-    if (maxit < 1 || newton < 0 || !(stol > 0.) || !std::isfinite(stol) || !(eps_cap > 0.) || !std::isfinite(eps_cap))
-        return fail(c, PLFX_ERR_ARG, "load_path: maxit >= 1, newton >= 0 and finite stol > 0, eps_cap > 0 expected");
-    if (n == 0) return PLFX_OK;
-    if (!ksteps || !status || (K > 0 && (!dload || !sig || !epl || !deps || !fy || !nsteps || !newton_out)))
-        return fail(c, PLFX_ERR_ARG, "load_path: null argument");
-    const size_t N = n, KK = K, nd = shared ? 1 : N;
-    if (KK * N * 19 > (size_t)INT32_MAX) return fail(c, PLFX_ERR_ARG, "load_path: K n 19 = %zu exceeds INT32_MAX", KK * N * 19);
-    unsigned any_strain = control ? 0u : 63u;   // components that are strain-controlled at some point (a shared dload)
-    if (control)
-        for (size_t i = 0; i < N; i++) {
-            if (control[i] < 0 || control[i] >= 64) return fail(c, PLFX_ERR_ARG, "load_path: control[%zu] = %d, six bits expected", i, (int)control[i]);
-            any_strain |= ~(unsigned)control[i] & 63u;
-        }
-    for (size_t j = 0; j < KK * nd * 6; j++) {
-        if (!std::isfinite(dload[j])) return fail(c, PLFX_ERR_ARG, "load_path: dload is not finite at entry %zu", j);
-        const unsigned strain = shared ? any_strain : (control ? ~(unsigned)control[(j / 6) % N] & 63u : 63u);
-        if (((strain >> (j % 6)) & 1u) && std::fabs(dload[j]) > eps_cap)
-            return fail(c, PLFX_ERR_ARG, "load_path: the strain increment %g at entry %zu of dload is beyond eps_cap = %g", dload[j], j, eps_cap);
-    }
-    for (const double *p : {sig0, epl0})
-        if (p)
-            for (size_t j = 0; j < 6 * N; j++)
-                if (!std::isfinite(p[j])) return fail(c, PLFX_ERR_ARG, "load_path: %s is not finite at entry %zu", p == sig0 ? "sig0" : "epl0", j);
-    if (int rc = tex_point_check(c, n, mat, nullptr, tex_id)) return rc;
-    if (K == 0) {   // nothing to follow: no step completed, the tangent is the elastic one
-        for (size_t i = 0; i < N; i++) {
-            ksteps[i] = status[i] = 0;
-            if (ct)
-                for (int r = 0; r < 6; r++)
-                    for (int q = 0; q < 6; q++) ct[36 * i + r * 6 + q] = hm.CV[sym_idx(r, q)];
-        }
-        return PLFX_OK;
-    }
-    const bool field = tex_id && ((c->tex_field_mask >> mat) & 1u);
-    // one buffer in: dload | sig0 | epl0 | control, tex_id (int32)
-    const size_t o_s0 = KK * nd * 6, o_e0 = o_s0 + (sig0 ? 6 * N : 0), o_int = o_e0 + (epl0 ? 6 * N : 0);
-    const size_t n_int = (control ? N : 0) + (field ? N : 0), in_words = o_int + (n_int + 1) / 2;
-    const std::unique_ptr<double[]> hin(new double[std::max<size_t>(in_words, 1)]);   // (not zeroed: every word sent is written)
-    memcpy(hin.get(), dload, o_s0 * 8);
-    if (sig0) memcpy(hin.get() + o_s0, sig0, N * 48);
-    if (epl0) memcpy(hin.get() + o_e0, epl0, N * 48);
-    int32_t *hint = (int32_t *)(hin.get() + o_int);
-    if (n_int & 1) hint[n_int] = 0;
-    if (control) memcpy(hint, control, N * 4);
-    if (field) memcpy(hint + (control ? N : 0), tex_id, N * 4);
-    // one buffer out: sig | epl | deps | fy | ct | nsteps, newton, ksteps, status (int32)
-    const size_t KN = KK * N, o_ct = 19 * KN, o_oi = o_ct + (ct ? 36 * N : 0), out_words = o_oi + KN + N;
-    CallBuffers B;
-    double *d_in = nullptr, *d_out = nullptr;
-    if (int rc = B.put(c, &d_in, (const double *)hin.get(), in_words)) return rc;
-    if (int rc = B.get(c, &d_out, out_words)) return rc;
-    const int32_t *d_int = (const int32_t *)(d_in + o_int);
-    int32_t *d_oi = (int32_t *)(d_out + o_oi);
-    PathArgs a;
-    a.n = n;
-    a.K = K;
-    a.dload = d_in;
-    a.dl_stride = shared ? 0 : 6;
-    a.control = control ? d_int : nullptr;
-    a.sig0 = sig0 ? d_in + o_s0 : nullptr;
-    a.epl0 = epl0 ? d_in + o_e0 : nullptr;
-    a.maxit = maxit;
-    a.newton = newton;
-    a.stol = stol;
-    a.eps_cap = eps_cap;
-    a.sig = d_out;
-    a.epl = d_out + 6 * KN;
-    a.deps = d_out + 12 * KN;
-    a.fy = d_out + 18 * KN;
-    a.ct = ct ? d_out + o_ct : nullptr;
-    a.nsteps = d_oi;
-    a.newton_out = d_oi + KN;
-    a.ksteps = d_oi + 2 * KN;
-    a.status = d_oi + 2 * KN + N;
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    if (row)
-        launch_path_row(c, mat, field ? d_int + (control ? N : 0) : nullptr, a);
-    else if (kind == 1)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_batch<1>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, mat, a);
-    else if (kind == 2)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_batch<2>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, mat, a);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_path_batch<5>), dim3(grid_for(N)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, mat, a);
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->path_launches++;
-    // one copy out: straight into the caller's arrays where they lie in one block in the order of the device buffer (the Python
-    // binding's do), else through a staging block
-    const bool packed = epl == sig + 6 * KN && deps == sig + 12 * KN && fy == sig + 18 * KN && (!ct || ct == sig + o_ct) &&
-                        (const void *)nsteps == (const void *)(sig + o_oi) && newton_out == nsteps + KN &&
-                        ksteps == nsteps + 2 * KN && status == ksteps + N;
-    std::unique_ptr<double[]> hout(packed ? nullptr : new double[out_words]);
-    HIPCHK(c, hipMemcpyAsync(packed ? sig : hout.get(), d_out, out_words * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    if (packed) return PLFX_OK;
-    memcpy(sig, hout.get(), KN * 48);
-    memcpy(epl, hout.get() + 6 * KN, KN * 48);
-    memcpy(deps, hout.get() + 12 * KN, KN * 48);
-    memcpy(fy, hout.get() + 18 * KN, KN * 8);
-    if (ct) memcpy(ct, hout.get() + o_ct, N * 288);
-    const int32_t *hoi = (const int32_t *)(hout.get() + o_oi);
-    memcpy(nsteps, hoi, KN * 4);
-    memcpy(newton_out, hoi + KN, KN * 4);
-    memcpy(ksteps, hoi + 2 * KN, N * 4);
-    memcpy(status, hoi + 2 * KN + N, N * 4);
-    return PLFX_OK;
-}
-
-int plfx_load_path_info(plfx_ctx *c, int64_t *launches)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (launches) *launches = c->path_launches;
-    return PLFX_OK;
-}
-
-// A committee of SVC yield functions on n shared unit stresses: all members in ONE launch of k_committee_yf, mean and
-// variance over the members per point, and the point of largest variance (the blocks' partials are closed here, in block
-// order: a strictly larger variance replaces, so equal variances resolve to the smaller index).
-int plfx_committee_yf(plfx_ctx *c, int nmem, const int32_t *mats, const double *scale, int n, const double *su, double *yf,
-                      double *mean, double *var, int32_t *best, double *best_var)
-{
-    static const char *const kind_names[] = {"elastic", "Hill / J2 on Voigt stresses", "Hill / J2 on principal stresses",
-                                             "6-feature SVC", "Tresca", "Barlat", "2-feature SVC on principal stresses",
-                                             "SVC with work-hardening features", "6-feature SVC with column scales"};
-    if (!c || !c->dmat) return c ? fail(c, PLFX_ERR_STATE, "set_materials first") : PLFX_ERR_STATE;
-    if (nmem < 1 || nmem > MAXMAT) return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: nmem = %d, must be in 1..%d", nmem, MAXMAT);
-    if (!mats || !scale || n < 0 || n > INT32_MAX - CY_BLOCK || (n > 0 && !su)) return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: bad argument");
-    CommitteeArgs a = {};
-    int32_t staged = 0;
-    for (int k = 0; k < nmem; k++) {
-        if (mats[k] < 0 || mats[k] >= c->nmat)
-            return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: member %d is material %d, the context holds %d", k, mats[k], c->nmat);
-        const MatDev &m = c->hmat[mats[k]];
-        if (m.kind != PLFX_SVC6)
-            return fail(c, PLFX_ERR_UNSUPPORTED, "plfx_committee_yf: member %d (material %d) is of kind %d (%s); only 6-feature SVC "
-                        "materials on Voigt stresses form a committee", k, mats[k], m.kind, kind_names[m.kind]);
-        if (!std::isfinite(scale[k]) || !(scale[k] > 0.))
-            return fail(c, PLFX_ERR_ARG, "plfx_committee_yf: scale of member %d must be finite and positive", k);
-        a.mat[k] = mats[k];
-        a.scale[k] = scale[k];
-        if (m.nsv * (m.nfeat + 1) <= c->svc_lds_need) staged |= 1 << k;   // the test of stage_svc
-    }
-    if (n == 0) return PLFX_OK;
-    const int block = row16_block(c, n, CY_BLOCK), rpb = block / 16, nblk = (n + rpb - 1) / rpb;
-    const bool query = best || best_var;
-    CallBuffers B;   // [su | yf | mean | var | partial variances], partial indices
-    double *dbuf = nullptr;
-    int32_t *dpi = nullptr;
-    const size_t nn = (size_t)n, o_yf = 6 * nn, o_mean = o_yf + (yf ? (size_t)nmem * nn : 0), o_var = o_mean + (mean ? nn : 0),
-                 o_pv = o_var + (var ? nn : 0);
-    if (int rc = B.get(c, &dbuf, o_pv + (query ? (size_t)nblk : 0))) return rc;
-    if (query)
-        if (int rc = B.get(c, &dpi, (size_t)nblk)) return rc;
-    HIPCHK(c, hipMemcpyAsync(dbuf, su, nn * 48, hipMemcpyHostToDevice, c->stream));
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    hipLaunchKernelGGL(k_committee_yf, dim3(nblk), dim3(block), dyn_lds_bytes(c), c->stream, c->dmat, c->nmat, c->svc_lds_need, nmem,
-                       a, n, (const double *)dbuf, yf ? dbuf + o_yf : nullptr, mean ? dbuf + o_mean : nullptr,
-                       var ? dbuf + o_var : nullptr, query ? dbuf + o_pv : nullptr, dpi);
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->committee_launches++;
-    c->committee_staged = staged;
-    if (yf) HIPCHK(c, hipMemcpyAsync(yf, dbuf + o_yf, (size_t)nmem * nn * 8, hipMemcpyDeviceToHost, c->stream));
-    if (mean) HIPCHK(c, hipMemcpyAsync(mean, dbuf + o_mean, nn * 8, hipMemcpyDeviceToHost, c->stream));
-    if (var) HIPCHK(c, hipMemcpyAsync(var, dbuf + o_var, nn * 8, hipMemcpyDeviceToHost, c->stream));
-    std::vector<double> pv;
-    std::vector<int32_t> pi;
-    if (query) {
-        pv.resize(nblk);
-        pi.resize(nblk);
-        HIPCHK(c, hipMemcpyAsync(pv.data(), dbuf + o_pv, (size_t)nblk * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(pi.data(), dpi, (size_t)nblk * 4, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, stream_sync(c));
-    if (query) {
-        double bv = std::nan("");
-        int32_t bi = -1;
-        for (int b = 0; b < nblk; b++)
-            if (pi[b] >= 0 && (bi < 0 || pv[b] > bv)) bv = pv[b], bi = pi[b];
-        if (best) *best = bi;
-        if (best_var) *best_var = bv;
-    }
-    return PLFX_OK;
-}
-
-int plfx_committee_info(plfx_ctx *c, int64_t *launches, int32_t *staged_members)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (launches) *launches = c->committee_launches;
-    if (staged_members) *staged_members = c->committee_staged;
-    return PLFX_OK;
-}
-
-// ------------------------------------------------------------------------------ texture SVC
-// The set: vectors padded to NFP = 8 / 12 / 16 slots at a row stride of NFP + 2 doubles (plfx_tex.hpp), coefficients, the
-// scaler's mean and scale per column.  nsv = 0 releases the set; a second call replaces it.
-int plfx_tex_svc_set(plfx_ctx *c, int nsv, int tdim, const double *sv, const double *dual, double intercept, double gamma,
-                     const double *mean, const double *scale, int dev_only)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (nsv < 0) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: nsv = %d", nsv);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (nsv == 0) {
-        HIPCHK(c, stream_sync(c));
-        dfree(c->tex_sv);
-        dfree(c->tex_dual);
-        c->tex = TexSvcPar();
-        c->tex_nfp = 0;
-        c->tex_yf_launches = c->tex_ray_launches = 0;
-        c->tex_fgrad_launches = c->tex_full_launches = c->tex_resp_launches = 0;
-        return PLFX_OK;
-    }
-    if (tdim < 1 || tdim > TEX_TMAX)
-        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: tdim = %d texture coefficients, 1 <= tdim <= %d supported", tdim, TEX_TMAX);
-    if (!sv || !dual || !mean || !scale) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: null argument");
-    if (!(gamma > 0.) || !std::isfinite(gamma)) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: gamma must be > 0 (got %g)", gamma);
-    if (!std::isfinite(intercept)) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: the intercept is not finite");
-    const int d = 6 + tdim, nfp = d <= 8 ? 8 : d <= 12 ? 12 : 16, st = tex_stride(nfp);
-    if ((int64_t)nsv * (st + 1) > INT32_MAX) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: nsv = %d is too large", nsv);
-    TexSvcPar P = {};
-    for (int j = 0; j < TEX_DMAX; j++) P.mean[j] = 0., P.scale[j] = 1.;
-    for (int j = 0; j < d; j++) {
-        if (!(scale[j] > 0.) || !std::isfinite(scale[j]))
-            return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: scale of column %d must be finite and > 0 (got %g)", j, scale[j]);
-        if (!std::isfinite(mean[j])) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: mean of column %d is not finite", j);
-        P.mean[j] = mean[j], P.scale[j] = scale[j];
-    }
-    std::vector<double> tab((size_t)nsv * st, 0.);
-    for (int k = 0; k < nsv; k++) {
-        if (!std::isfinite(dual[k])) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: coefficient %d is not finite", k);
-        for (int j = 0; j < d; j++) {
-            const double v = sv[(size_t)k * d + j];
-            if (!std::isfinite(v)) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_set: vector %d holds a non-finite value", k);
-            tab[(size_t)k * st + j] = v;
-        }
-    }
-    P.gamma = gamma, P.intercept = intercept, P.nsv = nsv, P.tdim = tdim, P.dev_only = dev_only ? 1 : 0;
-    P.staged = (int64_t)nsv * (st + 1) <= c->lds_doubles ? 1 : 0;
-    HIPCHK(c, stream_sync(c));   // no launch of the previous set is in flight when its tables go
-    c->tex = TexSvcPar();
-    c->tex_nfp = 0;
-    if (int rc = dalloc(c, &c->tex_sv, tab.size())) return rc;
-    if (int rc = dalloc(c, &c->tex_dual, (size_t)nsv)) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->tex_sv, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->tex_dual, dual, (size_t)nsv * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, stream_sync(c));
-    if (P.staged) {
-        const int bytes = nsv * (st + 1) * 8;
-        hipError_t e = hipSuccess;
-        for (int width : {8, 12, 16})   // every width, as the attribute is only ever raised (set_dyn_lds)
-            tex_for_nfp(width, [&](auto w) {
-                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_yf<decltype(w)::value>, bytes);
-                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_yield_scale<decltype(w)::value>, bytes);
-                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_fgrad<decltype(w)::value>, bytes);
-                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_full_yf<decltype(w)::value>, bytes);
-                if (e == hipSuccess) e = set_dyn_lds((const void *)k_tex_response<decltype(w)::value>, bytes);
-            });
-        HIPCHK(c, e);
-    }
-    c->tex = P;
-    c->tex_nfp = nfp;
-    c->tex_yf_launches = c->tex_ray_launches = 0;
-    c->tex_fgrad_launches = c->tex_full_launches = c->tex_resp_launches = 0;
-    return PLFX_OK;
-}
-
-static size_t tex_lds_bytes(const plfx_ctx *c)
-{
-    return c->tex.staged ? (size_t)c->tex.nsv * (tex_stride(c->tex_nfp) + 1) * 8 : 0;
-}
-
-// calc_yf(sig, tex=) of the set at n points, one launch of k_tex_yf
-int plfx_tex_svc_yf(plfx_ctx *c, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *yf)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (c->tex.nsv == 0) return fail(c, PLFX_ERR_STATE, "plfx_tex_svc_yf: plfx_tex_svc_set first");
-    if (n < 0 || n > INT32_MAX / 2 || (n > 0 && (!sig || !tex || !yf || ntex < 1)))
-        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yf: bad argument");
-    if (n == 0) return PLFX_OK;
-    if (!tex_id && ntex != 1 && ntex != n)
-        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yf: %d textures for %d points; without tex_id one shared texture or one per "
-                    "point is expected", ntex, n);
-    if (tex_id)
-        for (int i = 0; i < n; i++)
-            if (tex_id[i] < 0 || tex_id[i] >= ntex)
-                return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yf: tex_id[%d] = %d, the call holds %d textures", i, tex_id[i], ntex);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = n, td = c->tex.tdim;
-    CallBuffers B;
-    double *dsig = nullptr, *dtex = nullptr, *dyf = nullptr;
-    int32_t *did = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
-    if (tex_id)
-        if (int rc = B.put(c, &did, tex_id, N)) return rc;
-    if (int rc = B.get(c, &dyf, N)) return rc;
-    const int block = row16_block(c, n, TEX_BLOCK);
-    const dim3 grid = row16_grid(c, n, block, 8);
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    tex_for_nfp(c->tex_nfp, [&](auto w) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yf<decltype(w)::value>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,
-                           (const double *)c->tex_sv, (const double *)c->tex_dual, n, (const double *)dsig, ntex,
-                           (const double *)dtex, (const int32_t *)did, dyf);
-    });
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->tex_yf_launches++;
-    HIPCHK(c, hipMemcpyAsync(yf, dyf, N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// yield_scale(su, tex=) of the set: ntex x nray rays, texture-major, one launch of k_tex_yield_scale.  x0 NULL: the search of
-// ray (t, r) starts at 1 / seq_J2(su_r), the factor that brings the ray to a J2 stress of one stress unit
-int plfx_tex_svc_yield_scale(plfx_ctx *c, int nray, const double *su, int ntex, const double *tex, const double *x0, double *x,
-                             int32_t *status)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (c->tex.nsv == 0) return fail(c, PLFX_ERR_STATE, "plfx_tex_svc_yield_scale: plfx_tex_svc_set first");
-    if (nray < 0 || ntex < 0 || (int64_t)nray * ntex > INT32_MAX / 2)
-        return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yield_scale: bad argument");
-    if (nray == 0 || ntex == 0) return PLFX_OK;
-    if (!su || !tex || !x || !status) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_yield_scale: null argument");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int nq = nray * ntex;
-    const size_t Q = nq, td = c->tex.tdim;
-    std::vector<double> start;
-    if (!x0) {
-        start.resize(Q);
-        for (int r = 0; r < nray; r++) {
-            const double *s = su + 6 * (size_t)r;
-            const double d01 = s[0] - s[1], d12 = s[1] - s[2], d20 = s[2] - s[0];
-            const double sj2 = std::sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20) + 3. * (s[3] * s[3] + s[4] * s[4] + s[5] * s[5]));
-            for (int t = 0; t < ntex; t++) start[(size_t)t * nray + r] = 1. / sj2;   // (sj2 = 0: inf, status 3)
-        }
-    }
-    CallBuffers B;
-    double *dsu = nullptr, *dtex = nullptr, *dx0 = nullptr, *dx = nullptr;
-    int32_t *dst = nullptr;
-    if (int rc = B.put(c, &dsu, su, 6 * (size_t)nray)) return rc;
-    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
-    if (int rc = B.put(c, &dx0, x0 ? x0 : start.data(), Q)) return rc;
-    if (int rc = B.get(c, &dx, Q)) return rc;
-    if (int rc = B.get(c, &dst, Q)) return rc;
-    const int block = row16_block(c, nq, TEX_BLOCK);
-    const dim3 grid = row16_grid(c, nq, block, 4);
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    tex_for_nfp(c->tex_nfp, [&](auto w) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_yield_scale<decltype(w)::value>), grid, dim3(block), tex_lds_bytes(c), c->stream,
-                           c->tex, (const double *)c->tex_sv, (const double *)c->tex_dual, nray, (const double *)dsu, ntex,
-                           (const double *)dtex, (const double *)dx0, dx, dst);
-    });
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->tex_ray_launches++;
-    HIPCHK(c, hipMemcpyAsync(x, dx, Q * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, dst, Q * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-int plfx_tex_svc_info(plfx_ctx *c, int *nsv, int *tdim, int64_t *yf_launches, int64_t *ray_launches, int *staged)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (nsv) *nsv = c->tex.nsv;
-    if (tdim) *tdim = c->tex.tdim;
-    if (yf_launches) *yf_launches = c->tex_yf_launches;
-    if (ray_launches) *ray_launches = c->tex_ray_launches;
-    if (staged) *staged = c->tex.staged;
-    return PLFX_OK;
-}
-
-// ---- flow rule and stress update of the texture SVC (kernels in plfx_texflow.hpp)
-// what the three calls ask of their common arguments; 1: n = 0, nothing to do
-static int tex_flow_check(plfx_ctx *c, const char *who, int n, const double *sig, int ntex, const double *tex,
-                          const int32_t *tex_id, bool outs_ok)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (c->tex.nsv == 0) return fail(c, PLFX_ERR_STATE, "%s: plfx_tex_svc_set first", who);
-    if (n < 0 || n > INT32_MAX / 36 || (n > 0 && (!sig || !tex || !outs_ok || ntex < 1)))
-        return fail(c, PLFX_ERR_ARG, "%s: bad argument", who);
-    if (n == 0) return 1;
-    if (!tex_id && ntex != 1 && ntex != n)
-        return fail(c, PLFX_ERR_ARG, "%s: %d textures for %d points; without tex_id one shared texture or one per point is "
-                    "expected", who, ntex, n);
-    if (tex_id)
-        for (int i = 0; i < n; i++)
-            if (tex_id[i] < 0 || tex_id[i] >= ntex)
-                return fail(c, PLFX_ERR_ARG, "%s: tex_id[%d] = %d, the call holds %d textures", who, i, tex_id[i], ntex);
-    return PLFX_OK;
-}
-
-// the material record the thread-per-point kernels take seq, sy, khard and the elastic matrix from
-static int tex_flow_material(plfx_ctx *c, const char *who, int mat)
-{
-    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "%s: set_materials first", who);
-    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "%s: material %d of %d", who, mat, c->nmat);
-    if (c->hmat[mat].kind != PLFX_HILL6)
-        return fail(c, PLFX_ERR_UNSUPPORTED, "%s: material %d is of kind %d; the record beside a texture set is an analytic "
-                    "PLFX_HILL6 one", who, mat, (int)c->hmat[mat].kind);
-    return PLFX_OK;
-}
-
-// calc_fgrad(sig, tex=) of the set at n points, one launch of k_tex_fgrad
-int plfx_tex_svc_fgrad(plfx_ctx *c, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *grad)
-{
-    if (int rc = tex_flow_check(c, "plfx_tex_svc_fgrad", n, sig, ntex, tex, tex_id, grad != nullptr)) return rc > 0 ? PLFX_OK : rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = n, td = c->tex.tdim;
-    CallBuffers B;
-    double *dsig = nullptr, *dtex = nullptr, *dg = nullptr;
-    int32_t *did = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
-    if (tex_id)
-        if (int rc = B.put(c, &did, tex_id, N)) return rc;
-    if (int rc = B.get(c, &dg, 6 * N)) return rc;
-    const int block = row16_block(c, n, TEX_BLOCK);
-    const dim3 grid = row16_grid(c, n, block, 8);
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    tex_for_nfp(c->tex_nfp, [&](auto w) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_fgrad<decltype(w)::value>), grid, dim3(block), tex_lds_bytes(c), c->stream, c->tex,
-                           (const double *)c->tex_sv, (const double *)c->tex_dual, n, (const double *)dsig, ntex,
-                           (const double *)dtex, (const int32_t *)did, dg);
-    });
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->tex_fgrad_launches++;
-    HIPCHK(c, hipMemcpyAsync(grad, dg, 6 * N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// ML_full_yf(sig, tex=) of the set at n points beside material 0 of the context, one launch of k_tex_full_yf
-int plfx_tex_svc_full_yf(plfx_ctx *c, int n, const double *sig, int ntex, const double *tex, const int32_t *tex_id, double *f,
-                         int32_t *status)
-{
-    if (int rc = tex_flow_check(c, "plfx_tex_svc_full_yf", n, sig, ntex, tex, tex_id, f && status)) return rc > 0 ? PLFX_OK : rc;
-    if (int rc = tex_flow_material(c, "plfx_tex_svc_full_yf", 0)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = n, td = c->tex.tdim;
-    CallBuffers B;
-    double *dsig = nullptr, *dtex = nullptr, *df = nullptr;
-    int32_t *did = nullptr, *dst = nullptr;
-    if (int rc = B.put(c, &dsig, sig, 6 * N)) return rc;
-    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
-    if (tex_id)
-        if (int rc = B.put(c, &did, tex_id, N)) return rc;
-    if (int rc = B.get(c, &df, N)) return rc;
-    if (int rc = B.get(c, &dst, N)) return rc;
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    tex_for_nfp(c->tex_nfp, [&](auto w) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_full_yf<decltype(w)::value>), dim3(grid_for(N)), dim3(BLOCK), tex_lds_bytes(c),
-                           c->stream, (const MatDev *)c->dmat, c->nmat, 0, c->tex, (const double *)c->tex_sv,
-                           (const double *)c->tex_dual, n, (const double *)dsig, ntex, (const double *)dtex,
-                           (const int32_t *)did, df, dst);
-    });
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->tex_full_launches++;
-    HIPCHK(c, hipMemcpyAsync(f, df, N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, dst, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-// Material.response(..., tex=) of the set at n points beside material `mat`, one launch of k_tex_response
-int plfx_tex_svc_response(plfx_ctx *c, int mat, int n, const double *sig, const double *epl, const double *deps, int ntex,
-                          const double *tex, const int32_t *tex_id, int maxit, double *fy, double *sig_out, double *depl,
-                          double *ct, int32_t *nsteps)
-{
-    if (int rc = tex_flow_check(c, "plfx_tex_svc_response", n, sig, ntex, tex, tex_id,
-                                epl && deps && fy && sig_out && depl && ct && nsteps))
-        return rc > 0 ? PLFX_OK : rc;
-    if (maxit < 1) return fail(c, PLFX_ERR_ARG, "plfx_tex_svc_response: maxit = %d", maxit);
-    if (int rc = tex_flow_material(c, "plfx_tex_svc_response", mat)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N = n, td = c->tex.tdim;
-    CallBuffers B;
-    double *d_in = nullptr, *d_out = nullptr, *dtex = nullptr;
-    int32_t *did = nullptr, *d_ns = nullptr;
-    if (int rc = B.get(c, &d_in, N * 18)) return rc;
-    if (int rc = B.get(c, &d_out, N * (1 + 6 + 6 + 36))) return rc;
-    if (int rc = B.get(c, &d_ns, N)) return rc;
-    HIPCHK(c, hipMemcpyAsync(d_in, sig, N * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in + 6 * N, epl, N * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in + 12 * N, deps, N * 48, hipMemcpyHostToDevice, c->stream));
-    if (int rc = B.put(c, &dtex, tex, (size_t)ntex * td)) return rc;
-    if (tex_id)
-        if (int rc = B.put(c, &did, tex_id, N)) return rc;
-    double *d_fy = d_out, *d_so = d_out + N, *d_dp = d_out + 7 * N, *d_ct = d_out + 13 * N;
-    EvPair *ev;
-    tim_begin(c, 0, &ev);
-    tex_for_nfp(c->tex_nfp, [&](auto w) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_tex_response<decltype(w)::value>), dim3(grid_for(N)), dim3(BLOCK), tex_lds_bytes(c),
-                           c->stream, (const MatDev *)c->dmat, c->nmat, mat, c->tex, (const double *)c->tex_sv,
-                           (const double *)c->tex_dual, n, (const double *)d_in, (const double *)(d_in + 6 * N),
-                           (const double *)(d_in + 12 * N), ntex, (const double *)dtex, (const int32_t *)did, d_fy, d_so, d_dp,
-                           d_ct, d_ns, maxit);
-    });
-    tim_end(c, ev);
-    HIPCHK(c, hipGetLastError());
-    c->tex_resp_launches++;
-    HIPCHK(c, hipMemcpyAsync(fy, d_fy, N * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sig_out, d_so, N * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(depl, d_dp, N * 48, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ct, d_ct, N * 288, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(nsteps, d_ns, N * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, stream_sync(c));
-    return PLFX_OK;
-}
-
-int plfx_tex_svc_flow_info(plfx_ctx *c, int64_t *fgrad_launches, int64_t *full_yf_launches, int64_t *response_launches)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (fgrad_launches) *fgrad_launches = c->tex_fgrad_launches;
-    if (full_yf_launches) *full_yf_launches = c->tex_full_launches;
-    if (response_launches) *response_launches = c->tex_resp_launches;
     return PLFX_OK;
 }
 
@@ -3689,91 +2331,6 @@ int plfx_reuse_info(plfx_ctx *c, int *assemblies, int *bc_applications, int *sol
     return PLFX_OK;
 }
 
-int plfx_predict_info(plfx_ctx *c, int64_t *applied, int64_t *skipped, int64_t *rejected)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (applied) *applied = c->n_pred;
-    if (skipped) *skipped = c->n_pred_skipped;
-    if (rejected) *rejected = c->n_pred_rejected;
-    return PLFX_OK;
-}
-
-int plfx_svc_fit_batch(plfx_ctx *c, int n, int d, const double *X, const double *y, int nprob, const int32_t *off,
-                       const int32_t *idx, const double *C, const double *gamma, double tol, int64_t max_iter,
-                       double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status)
-{
-    return svc_fit_batch_impl(c, n, d, X, y, nprob, off, idx, C, gamma, tol, max_iter, alpha, rho, obj, iters, status);
-}
-
-int plfx_svc_fit_wide(plfx_ctx *c, int n, int d, const double *X, const double *y, double C, double gamma, double tol,
-                      int64_t max_iter, int nwg, double *alpha, double *rho, double *obj, int32_t *iters, int32_t *status)
-{
-    return svc_fit_wide_impl(c, n, d, X, y, C, gamma, tol, max_iter, nwg, alpha, rho, obj, iters, status);
-}
-
-int plfx_svc_decision_batch(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *sv_off,
-                            const int32_t *sv_idx, const double *coef, const double *intercept, const double *gamma,
-                            const int32_t *q_off, const int32_t *q_idx, double *dec)
-{
-    return svc_decision_batch_impl(c, n, d, X, nprob, sv_off, sv_idx, coef, intercept, gamma, q_off, q_idx, dec);
-}
-
-int plfx_svr_fit_batch(plfx_ctx *c, int n, int d, const double *X, int nprob, const int32_t *off, const int32_t *idx,
-                       const double *t, const double *C, const double *gamma, const double *epsilon, double tol,
-                       int64_t max_iter, double *coef, double *rho, double *obj, int32_t *iters, int32_t *status)
-{
-    return svr_fit_batch_impl(c, n, d, X, nprob, off, idx, t, C, gamma, epsilon, tol, max_iter, coef, rho, obj, iters, status);
-}
-
-int plfx_set_svr_flow(plfx_ctx *c, int mat, int l, const double *X, const double *coef, const double *intercept, double gamma,
-                      const double *feat_mean, const double *feat_scale, const double *out_mean, const double *out_scale)
-{
-    return set_svr_flow_impl(c, mat, l, X, coef, intercept, gamma, feat_mean, feat_scale, out_mean, out_scale);
-}
-
-int plfx_svr_flow_info(plfx_ctx *c, int mat, int *rows, int64_t *launches)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (!c->dmat) return fail(c, PLFX_ERR_STATE, "set_materials first");
-    if (mat < 0 || mat >= c->nmat) return fail(c, PLFX_ERR_ARG, "plfx_svr_flow_info: material %d out of range", mat);
-    if (rows) *rows = c->svr_flow[mat].l;
-    if (launches) *launches = c->svr_launches[mat];
-    return PLFX_OK;
-}
-
-int plfx_svr_predict_multi(plfx_ctx *c, int n, int d, const double *X, double gamma, int m, const double *coef,
-                           const double *intercept, int nq, const double *Q, double *out)
-{
-    return svr_predict_multi_impl(c, n, d, X, gamma, m, coef, intercept, nq, Q, out);
-}
-
-int plfx_set_response_maxit(plfx_ctx *c, int maxit)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (maxit < 1) return fail(c, PLFX_ERR_ARG, "maxit must be >= 1");
-    c->resp_maxit = maxit;
-    return PLFX_OK;
-}
-
-// host side of plfx_lapack3.hpp (no context, no GPU): what the device routine of the PRINC3 / SVC3 kernels computes
-int plfx_eig3_host(int n, const double *sig, double *w, double *V)
-{
-    if (n < 0 || !sig || !w) return PLFX_ERR_ARG;
-    double Vt[9];
-    for (int i = 0; i < n; i++)
-        if (lapack3::dgeev3(sig + 6 * (size_t)i, w + 3 * (size_t)i, V ? V + 9 * (size_t)i : Vt) != 0) return 1;
-    return PLFX_OK;
-}
-
-int plfx_sig_princ_host(int n, const double *sig, double *sp)
-{
-    if (n < 0 || !sig || !sp) return PLFX_ERR_ARG;
-    int rc = PLFX_OK;
-    for (int i = 0; i < n; i++)
-        if (lapack3::sig_princ_lapack3(sig + 6 * (size_t)i, sp + 3 * (size_t)i) != 0) rc = 1;
-    return rc;
-}
-
 int plfx_gen_structured(int NX, int NY, int32_t *conn, int32_t *noleft, int32_t *noright, int32_t *nobot, int32_t *notop)
 {
     if (NX < 1 || NY < 1 || (int64_t)(NX + 1) * (NY + 1) > INT32_MAX) return PLFX_ERR_ARG;
@@ -3856,18 +2413,6 @@ int plfx_precond_info(plfx_ctx *c, int *kind, int *levels)
     return PLFX_OK;
 }
 
-int plfx_indefinite_info(plfx_ctx *c, int64_t *solves, int64_t *by_minres_surrogate, int64_t *by_gmres, int64_t *surrogates_built,
-                         int64_t *elements_shifted)
-{
-    if (!c) return PLFX_ERR_ARG;
-    if (solves) *solves = c->n_indefinite;
-    if (by_minres_surrogate) *by_minres_surrogate = 0;
-    if (by_gmres) *by_gmres = c->n_gmres;
-    if (surrogates_built) *surrogates_built = 0;
-    if (elements_shifted) *elements_shifted = 0;
-    return PLFX_OK;
-}
-
 // measurement hook: `reps` applications of the preconditioner (z = M^-1 r on whatever r holds) back to back, timed with one
 // pair of HIP events; *us_coarse = the same with the fine level's launches left out (levels >= 1 only: the restriction to
 // level 1, the launch-latency-bound levels, the single-workgroup tail, the prolongation to level 0).
@@ -3936,13 +2481,6 @@ int plfx_precond_bench(plfx_ctx *c, int reps, double *us_per_cycle, double *us_c
     hipEventDestroy(e1);
     c->x_is_du = c->x_is_du && true;  // (c->x untouched: z and the level vectors are scratch outside a solve)
     return rc;
-}
-
-int plfx_solve_fallbacks(plfx_ctx *c, int64_t *count)
-{
-    if (!c || !count) return PLFX_ERR_ARG;
-    *count = (int64_t)c->mg_fallbacks + c->n_indefinite;
-    return PLFX_OK;
 }
 
 int plfx_assemble(plfx_ctx *c)
@@ -4033,7 +2571,7 @@ int plfx_get_csr(plfx_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *colidx, do
     return PLFX_OK;
 }
 
-// ------------------------------------------------------------------------------ BC + solve
+// ------------------------------------------------------------------------------ BC (the solve: plfx_solve.hip)
 namespace {
 // calc_BC on the device.  Values of the prescribed DOFs come either from host arrays (du_presc, w: one staged copy) or,
 // for a registered plan, from the per-segment values passed as kernel arguments (seg4 != null: no copy at all).
@@ -4312,854 +2850,6 @@ int plfx_set_bc_sources(plfx_ctx *c, int nseg, const int32_t *src, const int32_t
     P.fshare.assign(fshare, fshare + tot);
     P.sources = true;
     return PLFX_OK;
-}
-
-}  // extern "C"
-
-namespace plfx {
-namespace host {
-
-// launch k_cg_check and fetch the scalars: through the pinned mailbox (host spins on the sequence number) or, without
-// it, by a device->host copy + stream synchronisation
-// post: launch k_cg_check (with the mailbox: it also publishes the scalars); wait: fetch them.  Work enqueued between the
-// two overlaps the round trip.
-unsigned long long cg_check_post(plfx_ctx *c, const double *part_rr, int gn, int it_done)
-{
-    if (!c->mbox) {
-        hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(BLOCK), 0, c->stream, part_rr, gn, c->sc, it_done,
-                           (CgMbox *)nullptr, 0ull);
-        return 0;
-    }
-    const unsigned long long seq = ++c->mbox_seq;
-    hipLaunchKernelGGL(k_cg_check, dim3(1), dim3(BLOCK), 0, c->stream, part_rr, gn, c->sc, it_done, c->mbox, seq);
-    return seq;
-}
-
-// the set-up of the scalars (k_cg_setup) and the first test in one launch
-unsigned long long cg_setup_check_post(plfx_ctx *c, const double *part_bb, const double *part_rr, int gn, double rtol)
-{
-    const unsigned long long seq = c->mbox ? ++c->mbox_seq : 0ull;
-    hipLaunchKernelGGL(k_cg_setup_check, dim3(1), dim3(BLOCK), 0, c->stream, part_bb, part_rr, gn, rtol, c->sc, 0, c->mbox, seq);
-    return seq;
-}
-
-int cg_check_wait(plfx_ctx *c, unsigned long long seq, CgScalars *hs)
-{
-    if (!c->mbox) {  // note: waits for everything enqueued so far
-        HIPCHK(c, hipMemcpyAsync(hs, c->sc, sizeof(*hs), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_sync(c));
-        return 0;
-    }
-    HIPCHK(c, hipGetLastError());
-    {
-        const int rcw = mbox_wait(c, seq);
-        if (rcw) return rcw;
-    }
-    *hs = c->mbox->sc;
-    return 0;
-}
-
-// sum of per-block partials on the host (strip: all-reduced first): n slots of MAXPART doubles starting at `part`
-int host_sums(plfx_ctx *c, double *part, int nslots, int gn, double *out)
-{
-    int rc;
-    if ((rc = part_allreduce(c, part, (size_t)(nslots - 1) * MAXPART + gn))) return rc;
-    std::vector<double> h((size_t)(nslots - 1) * MAXPART + gn);
-    if ((rc = fetch_results(c, part, (int)h.size(), h.data()))) return rc;
-    for (int s = 0; s < nslots; s++) {
-        double t = 0.;
-        for (int i = 0; i < gn; i++) t += h[(size_t)s * MAXPART + i];
-        out[s] = t;
-    }
-    return 0;
-}
-
-// Right-preconditioned restarted GMRES on P K P x = P b from the iterate in c->x (see plfx_mg.hpp): x = x0 + B t with t in the
-// Krylov space of K B.  Returns 0 = |P(b - K x)| <= rtol |b|, 1 = iteration limit, < 0 = error.
-constexpr int GMRES_BLK = 32;  // basis vectors per allocation
-constexpr int GMRES_M = 1200;      // restart length (round 6): restarts stall on indefinite K -- a solve that needs 500 iterations took three cycles of
-                                   // 400 (1176 iterations) or none at all (residual stuck at 1e-6 after the first restart, profiles/r07e_*); with
-                                   // the basis read twice instead of four times per iteration a cycle three times as long costs what it cost,
-                                   // and the blocks are allocated as a cycle grows into them.  Reduced until the basis fits into a third of the
-                                   // free HBM (2048^2: 81 GB); PLFX_GMRES_M overrides
-int gmres_solve(plfx_ctx *c, double rtol, int maxit, int *iters, double *relres)
-{
-    const size_t nd = c->ndof;
-    const int nn = c->nnode, gn = c->grid_nodes;
-    const int olo = own_lo(c), ohi = own_hi(c);
-    int rc;
-    // LOCK-STEP: the first-use block below holds a collective.  Every rank of a communicator reaches it in the same
-    // solve, because what sends a solve here -- PCG's breakdown / stall flags -- is decided from partial sums that were
-    // all-reduced element-wise (strip) or computed redundantly on identical data (replicated solve): bitwise the same on every
-    // rank; gm_m is reset together with the mesh on all of them.
-    if (c->gm_m == 0) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(c, hipMemGetInfo(&fr, &tot));
-        c->gm_m = getenv("PLFX_GMRES_M") ? std::max(25, atoi(getenv("PLFX_GMRES_M"))) : GMRES_M;
-        c->gm_m = std::min(c->gm_m, 40 * GMRES_BLK - 1);
-        while (c->gm_m > 25 && (size_t)(c->gm_m + 1) * nd * 8 > fr / 3) c->gm_m = (c->gm_m * 2) / 3;
-        if (comm_active(c)) {  // every rank must run the same cycle length (paired collectives of a strip; identical iterates of a replicated solve)
-            double mv = c->gm_m;
-            HIPCHK(c, hipMemcpyAsync(c->small, &mv, 8, hipMemcpyHostToDevice, c->stream));
-            if ((rc = allreduce(c, c->small, 1, NCCL_FLOAT64, NCCL_MIN, "GMRES basis length"))) return rc;
-            if ((rc = fetch_results(c, c->small, 1, &mv))) return rc;
-            c->gm_m = (int)mv;
-        }
-    }
-    const int M = c->gm_m;
-    if (!c->gm_part && (rc = dalloc(c, &c->gm_part, (size_t)8 * MAXPART))) return rc;
-    // The basis grows with the cycle (round 4): most of these solves end after 40-100 iterations, a few need the whole cycle --
-    // the 401 vectors of a full cycle are 27 GB at 2048^2, the first block 2.2 GB.  Every rank of a communicator walks the same
-    // j, so the blocks appear in lock-step; the cycle LENGTH was agreed above from the memory that is free.
-    auto need = [&](int j) -> int {
-        while ((int)c->gm_blk.size() * GMRES_BLK <= j) {
-            double *b = nullptr;
-            const int e = dalloc(c, &b, (size_t)GMRES_BLK * nd);
-            if (e) return e;
-            c->gm_blk.push_back(b);
-        }
-        return 0;
-    };
-    auto Vj = [&](int j) { return c->gm_blk[j / GMRES_BLK] + (size_t)(j % GMRES_BLK) * nd; };
-    if ((rc = need(0))) return rc;
-    double *P_rz = c->part + 3 * MAXPART, *P_rr = c->part + 4 * MAXPART, *P_bb = c->part + 5 * MAXPART;
-    const bool use_mg = mg_active(c);
-    auto apply_B = [&]() -> int {  // c->z = B c->r
-        int e;
-        if (c->strip.on && (e = halo_refresh(c, c->r))) return e;
-        if (use_mg) return mg_vcycle(c);
-        hipLaunchKernelGGL(k_jacobi_z, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, (const double2 *)c->dinv,
-                           (const double2 *)c->r, (double2 *)c->z, c->sc);
-        return 0;
-    };
-    int itn = 0, cycles = 0, poor = 0;
-    double rl = 0., rr_prev = -1.;
-    std::vector<double> H((size_t)(M + 1) * M), cs(M), sn(M), g(M + 1), hcol(M + 2);
-    std::vector<double> Hraw((size_t)(M + 1) * M);
-    static const bool gm_dbg = getenv("PLFX_GMRES_DEBUG") != nullptr;
-    if ((rc = ensure_dinv(c))) return rc;   // (k_cg_start's z = dinv r, the Jacobi form of apply_B)
-    c->pred_d_kept = false;
-    while (true) {
-        // r0 = P (b - K x) -> c->r; beta = |r0|
-        LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
-                   (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, P_rz, P_rr, P_bb, olo, ohi);
-        HIPCHK(c, hipGetLastError());
-        double o[3];
-        if ((rc = host_sums(c, P_rz, 3, gn, o))) return rc;
-        const double rr = o[1], bb = o[2];
-        hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, P_bb, gn, rtol, c->sc);  // clears the sticky done flag
-        const double tol = rtol * std::sqrt(bb);
-        rl = bb > 0. ? std::sqrt(rr / bb) : 0.;
-        if (getenv("PLFX_SOLVE_DEBUG")) fprintf(stderr, "[gmres] cycle %d starts at iteration %d: true relative residual %.3e\n", cycles, itn, rl);
-        if (rr_prev >= 0. && rr > 0.25 * rr_prev) poor++;  // a whole cycle bought less than a factor of two
-        else poor = 0;
-        rr_prev = rr;
-        if (std::sqrt(rr) <= tol || itn >= maxit || poor >= 2 || cycles >= 20) {
-            if (iters) *iters = itn;
-            if (relres) *relres = rl;
-            return std::sqrt(rr) <= tol ? 0 : 1;
-        }
-        cycles++;
-        const double beta = std::sqrt(rr);
-        hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1. / beta, (const double2 *)c->r,
-                           (double2 *)Vj(0), (double2 *)nullptr);
-        std::fill(g.begin(), g.end(), 0.);
-        g[0] = beta;
-        int k = 0;  // columns built in this cycle
-        // ---- Arnoldi with delayed re-orthogonalisation (plfx_mg.hpp: k_gmres_dots3 / k_gmres_update2).
-        // State at the top of iteration j >= 1: q_0 .. q_{j-1} final in V_0 .. V_{j-1}; u = V_j the once-projected candidate
-        // for q_j (u = w_{j-1} - Q_j h1, h1 = the first-pass coefficients kept in h1p); column j-1 of the Hessenberg matrix
-        // still open.  One operator application z = A u, one dots pass (s = Q_j^T u, t = Q_j^T z, u.u, u.z), then on the host
-        //   alpha^2 = u.u - s.s                      (q_j = (u - Q_j s) / alpha: the delayed second pass of vector j)
-        //   column j-1 of H:  h1 + s  over  alpha    -> Givens, residual estimate, convergence test (one iteration late)
-        //   w_j = A q_j = (z - A Q_j s) / alpha,  A Q_j s = Q_j (H s) + q_j rho,  rho = alpha s_{j-1}     (Arnoldi relation)
-        //   first pass of w_j:  c = Q_j^T w_j = (t - H s) / alpha,   d = q_j^T w_j = ((u.z - s.t) / alpha - rho) / alpha
-        //   next candidate      w_j - Q_j c - q_j d = (z - Q_j t) / alpha - e (u - Q_j s),   e = (rho / alpha + d) / alpha
-        // and one update pass over Q_j that writes q_j into V_j and the next candidate into V_{j+1}.
-        std::vector<double> h1p, sv(M + 2), tv(M + 2), cf(2 * (size_t)M + 4), red(2 * (size_t)M + 4);
-        const int ncolmax = 2 * M + 4;
-        if (!c->gm_part2 && (rc = dalloc(c, &c->gm_part2, (size_t)ncolmax * MAXPART))) return rc;
-        if (!c->gm_red && (rc = dalloc(c, &c->gm_red, (size_t)ncolmax))) return rc;
-        if (!c->gm_coef && (rc = dalloc(c, &c->gm_coef, (size_t)ncolmax))) return rc;
-        GmBlocks GB;
-        auto fill_blocks = [&]() { for (int q = 0; q < 40; q++) GB.blk[q] = q < (int)c->gm_blk.size() ? c->gm_blk[q] : c->gm_blk[0]; };
-        // sums over the basis: columns 2k (V_k . a), 2k+1 (V_k . b), then a.a, a.b -- one reduction kernel, one host round trip
-        auto dots = [&](int j, const double *a, const double *bvec) -> int {
-            fill_blocks();
-            const int gd = std::min(gn, std::max(1, (ohi - olo + 2 * BLOCK - 1) / (2 * BLOCK)));   // tiles of 512 nodes
-            for (int b0 = 0; b0 < j; b0 += GM_KC)
-                hipLaunchKernelGGL(k_gmres_dots3, dim3(gd), dim3(BLOCK), 0, c->stream, olo, ohi, b0, std::min(GM_KC, j - b0), GB, nd,
-                                   (const double2 *)a, (const double2 *)bvec, b0 == 0 ? 2 * j : -1, c->gm_part2);
-            const int ncol = 2 * j + 2;
-            hipLaunchKernelGGL(k_gmres_reduce, dim3((ncol + BLOCK / 64 - 1) / (BLOCK / 64)), dim3(BLOCK), 0, c->stream, ncol, gd,
-                               (const double *)c->gm_part2, c->gm_red);
-            HIPCHK(c, hipGetLastError());
-            int e;
-            if (comm_active(c) && c->strip.on && (e = allreduce(c, c->gm_red, (size_t)ncol, NCCL_FLOAT64, NCCL_SUM, "GMRES sums"))) return e;
-            return fetch_results(c, c->gm_red, ncol, red.data());
-        };
-        // c->q = K B v (through c->r, c->z).  Defined behind the cycle's k_cg_start, as the launches it replaces were: the kernel
-        // templates appear in the code object in the order of their first use, and that order is kept
-        auto apply_A = [&](const double *v) -> int {
-            hipLaunchKernelGGL(k_scale_copy, dim3(grid_for(nn)), dim3(BLOCK), 0, c->stream, nn, 1., (const double2 *)v, (double2 *)c->r, (double2 *)nullptr);
-            if (const int e = apply_B()) return e;
-            LAUNCH_OP1(k_minres_apply, matfree(c), dim3(gn), c->op, nn, 1., (const double2 *)c->z, (const double2 *)c->dinv,
-                       (const double2 *)c->z, (double2 *)c->p[0], (double2 *)c->q, c->gm_part, c->gm_part + MAXPART, olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            return 0;
-        };
-        // first step: w_0 = A q_0; h1 = q_0 . w_0; candidate u_1 = w_0 - q_0 h1 -> V_1
-        itn++;
-        if ((rc = apply_A(Vj(0)))) return rc;
-        if ((rc = need(1))) return rc;
-        if ((rc = dots(1, c->q, nullptr))) return rc;
-        h1p.assign(1, red[0]);
-        cf[0] = red[0];
-        HIPCHK(c, hipMemcpyAsync(c->gm_coef + ncolmax / 2, cf.data(), 8, hipMemcpyHostToDevice, c->stream));
-        fill_blocks();
-        hipLaunchKernelGGL(k_gmres_update2, dim3(gn), dim3(BLOCK), 0, c->stream, nn, nd, 1, GB, (const double *)c->gm_coef,
-                           (const double *)(c->gm_coef + ncolmax / 2), 1., 0., (const double2 *)c->q, (const double2 *)nullptr,
-                           (double2 *)nullptr, (double2 *)Vj(1));
-        HIPCHK(c, hipGetLastError());
-        for (int j = 1; j <= M; j++) {
-            const bool more = j < M && itn < maxit;   // another basis vector may still be built after this one
-            // z = A u -> c->q   (the operator application of iteration j + 1, on the candidate: one ahead of the finished basis)
-            itn++;
-            if ((rc = apply_A(Vj(j)))) return rc;
-            if ((rc = dots(j, Vj(j), c->q))) return rc;
-            double ss = 0., st = 0.;
-            for (int q = 0; q < j; q++) {
-                sv[q] = red[2 * q];
-                tv[q] = red[2 * q + 1];
-                ss += sv[q] * sv[q];
-                st += sv[q] * tv[q];
-            }
-            const double uu = red[2 * j], uz = red[2 * j + 1];
-            const double a2 = uu - ss;
-            const double alpha = (a2 > 0. && std::isfinite(a2)) ? std::sqrt(a2) : 0.;
-            if (gm_dbg) {
-                double smax = 0.;
-                for (int q = 0; q < j; q++) smax = std::max(smax, std::fabs(sv[q]));
-                fprintf(stderr, "[gmres-d] j %d u.u %.6e s.s %.3e max|s| %.3e alpha %.6e |g| %.3e\n", j, uu, ss, smax, alpha, std::fabs(g[j - 1]));
-            }
-            // column j-1 of the Hessenberg matrix is complete: first-pass coefficients + the delayed second pass, alpha below
-            std::fill(hcol.begin(), hcol.end(), 0.);
-            for (int q = 0; q < j; q++) hcol[q] = h1p[q] + sv[q];
-            hcol[j] = alpha;
-            for (int q = 0; q <= j; q++) Hraw[(size_t)q * M + (j - 1)] = hcol[q];
-            for (int q = 0; q < j - 1; q++) {
-                const double t = cs[q] * hcol[q] + sn[q] * hcol[q + 1];
-                hcol[q + 1] = -sn[q] * hcol[q] + cs[q] * hcol[q + 1];
-                hcol[q] = t;
-            }
-            const double den = std::hypot(hcol[j - 1], hcol[j]);
-            cs[j - 1] = den > 0. ? hcol[j - 1] / den : 1.;
-            sn[j - 1] = den > 0. ? hcol[j] / den : 0.;
-            hcol[j - 1] = den;
-            hcol[j] = 0.;
-            g[j] = -sn[j - 1] * g[j - 1];
-            g[j - 1] = cs[j - 1] * g[j - 1];
-            for (int q = 0; q < j; q++) H[(size_t)q * M + (j - 1)] = hcol[q];
-            k = j;
-            if (std::fabs(g[j]) <= tol || !(alpha > 0.) || !more) break;
-            // first pass of the next vector, from the sums at hand
-            const double ia = 1. / alpha;
-            const double rho = alpha * sv[j - 1];
-            const double d = ((uz - st) * ia - rho) * ia;
-            const double e = (rho * ia + d) * ia;
-            h1p.assign(j + 1, 0.);
-            for (int q = 0; q < j; q++) {
-                double r = 0.;   // (H s)_q over the finished columns (upper Hessenberg: column p reaches row p + 1)
-                for (int p2 = (q > 0 ? q - 1 : 0); p2 < j; p2++) r += Hraw[(size_t)q * M + p2] * sv[p2];
-                h1p[q] = (tv[q] - r) * ia;
-                cf[q] = sv[q];
-                cf[ncolmax / 2 + q] = tv[q] * ia - e * sv[q];
-            }
-            h1p[j] = d;
-            if ((rc = need(j + 1))) return rc;
-            fill_blocks();
-            HIPCHK(c, hipMemcpyAsync(c->gm_coef, cf.data(), (size_t)8 * j, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->gm_coef + ncolmax / 2, cf.data() + ncolmax / 2, (size_t)8 * j, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_gmres_update2, dim3(gn), dim3(BLOCK), 0, c->stream, nn, nd, j, GB, (const double *)c->gm_coef,
-                               (const double *)(c->gm_coef + ncolmax / 2), ia, e, (const double2 *)Vj(j), (const double2 *)c->q,
-                               (double2 *)Vj(j), (double2 *)Vj(j + 1));
-            HIPCHK(c, hipGetLastError());
-        }
-        c->n_gmres_its += k;
-        // y = H^-1 g (upper triangular); t = V y -> c->r; x += B t
-        std::vector<double> y(k, 0.);
-        for (int q = k - 1; q >= 0; q--) {
-            double t = g[q];
-            for (int p2 = q + 1; p2 < k; p2++) t -= H[(size_t)q * M + p2] * y[p2];
-            y[q] = H[(size_t)q * M + q] != 0. ? t / H[(size_t)q * M + q] : 0.;
-        }
-        HIPCHK(c, hipMemsetAsync(c->r, 0, 8 * nd, c->stream));
-        for (int b0 = 0; b0 < k; b0 += 8) {
-            const int n8 = std::min(8, k - b0);
-            Ptr8 V8;
-            Coef8 C8;
-            for (int q = 0; q < 8; q++) {
-                V8.p[q] = (const double2 *)Vj(b0 + std::min(q, n8 - 1));
-                C8.c[q] = q < n8 ? y[b0 + q] : 0.;
-            }
-            hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, n8, (double2 *)c->r, V8, C8);
-        }
-        if ((rc = apply_B())) return rc;
-        {
-            Ptr8 V8;
-            Coef8 C8;
-            for (int q = 0; q < 8; q++) {
-                V8.p[q] = (const double2 *)c->z;
-                C8.c[q] = q == 0 ? 1. : 0.;
-            }
-            hipLaunchKernelGGL(k_gmres_axpy, dim3(gn), dim3(BLOCK), 0, c->stream, nn, 1, (double2 *)c->x, V8, C8);
-        }
-        HIPCHK(c, hipGetLastError());
-        // next cycle starts from the true residual of x (and ends the solve if it is small enough)
-    }
-}
-
-// What one solve carries from phase to phase (solve_impl and the functions it calls): a plain aggregate on the stack.
-struct SolveRun {
-    // partial-sum slots; r.z[1], r.r[1], b.b (written together by k_cg_start) are contiguous: one all-reduce in a strip
-    double *P_pq, *P_rz[2], *P_rr[2], *P_bb;
-    int olo, ohi, gn, nn;
-    size_t nd;
-    bool multi, mg;   // sharded SpMV (one all-reduce of q per CG step); multigrid-PCG (a strip's Jacobi fall-back included)
-    CgScalars hs;
-    int done, it;
-    bool pred_active, pred_fused;    // a history exists: this solve may be answered by x + alpha d; K d came with the start kernel's pass
-    bool pred_d_ready, pred_moved;   // (d = x - pred_x is in pred_d; the start x + alpha d was accepted as the solution)
-    bool pred_finished;              // (... and k_pred_finish has composed du and advanced the history already)
-    bool du_early;                   // the gated k_compose_du behind the first test has composed du (that test passed)
-    bool test_only;                  // started by k_cg_start_test: r, z and r.z are not there until k_cg_start follows
-    bool d_kept;                     // pred_d already holds this solve's d (plfx_ctx::pred_d_kept and x as the last solve left it): no k_pred_diff
-};
-
-// PLFX_WAIT_FIRST=0: a solve never waits for its first test before it enqueues the interpolated start (always speculate, as before DESIGN 24)
-bool wait_first_on() { static const bool on = !(getenv("PLFX_WAIT_FIRST") && atoi(getenv("PLFX_WAIT_FIRST")) == 0); return on; }
-
-bool solve_debug_on() { static const bool on = getenv("PLFX_SOLVE_DEBUG") && atoi(getenv("PLFX_SOLVE_DEBUG")) != 0; return on; }
-
-// z = (the rest of the V-cycle)(r) and the partials of r.z in `slot`: written by the last post-smoothing launch of the cycle
-// where that can be done, by k_dot_rz otherwise; all-reduced in a strip.  `vcycle_ev` (may be null) closes the timing of the cycle.
-int precondition_rz(plfx_ctx *c, double *slot, EvPair *vcycle_ev = nullptr)
-{
-    bool fused = false;
-    const int rc = mg_vcycle_rest(c, slot, &fused);
-    tim_end(c, vcycle_ev);
-    if (rc) return rc;
-    if (!fused)
-        hipLaunchKernelGGL(k_dot_rz, dim3(c->grid_nodes), dim3(BLOCK), 0, c->stream, own_lo(c), own_hi(c), (const double2 *)c->r,
-                           (const double2 *)c->z, slot);
-    return part_allreduce(c, slot, c->grid_nodes);
-}
-
-// p = z + beta p_old and q = K p of iteration `it`, partials of p.q
-void launch_direction(plfx_ctx *c, const SolveRun &s, int it)
-{
-    const int cur = it & 1, prev = cur ^ 1;  // (cur: the partial slot written by this iteration's update kernel)
-    const double2 *pold = (const double2 *)c->p[prev];
-    double2 *pnew = (double2 *)c->p[cur];
-    if (!s.multi && march_pcg(c)) {  // marching form of the matrix-free operator (bit-identical q, p)
-        if (it == 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_march<2>), dim3(s.gn), dim3(BLOCK), 0, c->stream, c->op, pold, (const double2 *)c->z,
-                               pnew, (double2 *)c->q, s.P_rz[prev], s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_march<1>), dim3(s.gn), dim3(BLOCK), 0, c->stream, c->op, pold, (const double2 *)c->z,
-                               pnew, (double2 *)c->q, s.P_rz[prev], s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
-    } else if (it == 0 && !s.multi)  // first iteration: p = z, p_old untouched
-        LAUNCH_OP2(k_spmv, 2, matfree(c), dim3(s.gn), c->op, 0, s.nn, pold, (const double2 *)c->z, pnew, (double2 *)c->q, s.P_rz[prev],
-                   s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
-    else
-        LAUNCH_OP2(k_spmv, 1, matfree(c), dim3(s.gn), c->op, s.multi ? c->own_n0 : 0, s.multi ? c->own_n1 : s.nn, pold, (const double2 *)c->z,
-                   pnew, (double2 *)c->q, s.P_rz[prev], s.P_rz[cur], s.P_rr[prev], s.gn, s.P_pq, c->sc, it, s.olo, s.ohi);
-}
-
-// du = x on the free DOFs, the prescribed values elsewhere (strip: x is valid on owned + 2 columns: complete the halo first)
-int compose_du(plfx_ctx *c)
-{
-    int rc;
-    if (c->strip.on && (rc = halo_refresh(c, c->x))) return rc;
-    hipLaunchKernelGGL(k_compose_du, dim3(grid_for(c->ndof)), dim3(BLOCK), 0, c->stream, c->ndof, c->x, c->dup, c->is_presc, c->du);
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-// the system just solved, for the shortcut at the top of solve_impl
-void remember(plfx_ctx *c, double rtol, double relres, bool valid) { c->memo = {valid, rtol, relres}; }
-
-// x0, the history of the initial guess, r0 (and z0 or K d), the scalars of a Jacobi-PCG solve
-int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
-{
-    const size_t nd = s.nd;
-    const int nn = s.nn, gn = s.gn;
-    // x0: the previous solution restricted to the free DOFs is still in c->x when neither du nor the Dirichlet set changed
-    const bool x_kept = warm && c->x_is_du;
-    if (!x_kept) {
-        hipLaunchKernelGGL(k_x0, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->du, c->is_presc, warm, 1., c->x);
-        c->pred_d_kept = false;   // (x rewritten)
-    }
-    c->x_is_du = false;
-    int rc = 0;
-    // Initial guess from the last TWO solutions (round 5; acceptance rule of round 6).  A warm start uses
-    // the previous solution x as it is.  The systems of consecutive solves differ by a tangent update and / or a scaled load
-    // increment, and so do their solutions, by nearly the same vector as last time: with d = x - (the last solution that differed
-    // from it; zero on DOFs that are prescribed now) and the alpha in [0, 1] that minimises | P (b - K (x + alpha d)) | -- one
-    // operator pass, two sums, after the plain start has failed the tolerance test -- x + alpha d is taken ONLY IF IT SATISFIES THE
-    // TOLERANCE AS IT IS (k_pred_try: one more pass over r and K d that writes nothing).  Otherwise x, r and z are what the plain
-    // warm start left and the solve iterates from x: every iterating solve is bit-identical to PLFX_PREDICT=0.  Why: the error a
-    // residual tolerance leaves sits in the soft modes of the plastic tangents, and it is the iterations of a long solve after a
-    // moved start that let those components drift (round 5 guarded that with an iteration-count threshold tuned on the test set;
-    // this rule follows from the mechanism and has no constant).  x itself is never rescaled (beta != 1 rescales its converged soft
-    // components, 4e-6 in the fields of the sensitive traces).  Tried on multigrid-PCG solves of meshes where a V-cycle costs more
-    // than the extra passes and the host round trips (>= 16384 nodes; the reference traces of the parity tests, <= 32 x 32
-    // elements, run the plain warm start).  Strips: x and the solution before it are valid on the halo columns, the sums are
-    // taken over the owned columns and all-reduced (host_sums / part_allreduce).  PLFX_PREDICT=0 at plfx_create switches it off.
-    // (every rank of a communicator takes the same decisions: the global node count and -- through the all-reduced sums -- alpha
-    // and the test are the same everywhere; a replicated solve computes everything redundantly)
-    const long long nn_global = c->strip.on ? (long long)(c->strip.gnx + 1) * (c->gy + 1) : (long long)c->nnode;
-    if (c->predict && warm && !s.multi && mg_active(c) && nn_global >= 16384) {
-        if (!c->pred_x && (rc = dalloc(c, &c->pred_x, nd))) return rc;
-        if (!c->pred_d && (rc = dalloc(c, &c->pred_d, nd))) return rc;
-        if (c->pred_valid)
-            s.pred_active = true;
-        else {
-            HIPCHK(c, hipMemcpyAsync(c->pred_x, c->x, 8 * nd, hipMemcpyDeviceToDevice, c->stream));
-            c->pred_valid = true;
-            c->pred_d_kept = false;   // (pred_x rewritten)
-        }
-    } else
-        c->pred_valid = c->pred_d_kept = false;   // a cold start or another solver: the history starts again
-    // d of the interpolated start is in pred_d already (k_pred_finish of the solve that last moved x wrote it)
-    s.d_kept = s.pred_active && c->pred_d_kept && x_kept && (c->short_solve & 2) && !c->strip.on && !comm_active(c);
-    // A solve that may be answered by x + alpha d needs K d as well as K x: where the plain start is not expected to pass its
-    // test, both come from ONE pass over the generators (k_cg_start_pred) instead of k_cg_start and k_spmv<0>.  A site
-    // whose last solve was answered by the plain start (the predictor solve of a load step) keeps k_cg_start: it would pay for a
-    // K d that nobody reads.  Matrix-free operator with cells all alike, one GPU, no strip.  If the plain start passes after
-    // all, pred_d and p[0] hold a d and a K d that nothing reads: pred_d_ready stays false, the next solve forms its own.
-    s.pred_fused = s.pred_active && matfree(c) && !c->op.colr && !c->strip.on && !comm_active(c) && site >= 0 && !c->first_test_hint[site];
-    if (s.pred_fused) {
-        // d = x - (solution before) first (k_pred_diff without the flag: the test of this solve has not run yet), then
-        // r = P(b - K x) and K d -> p[0]; partials of r.r and b.b -> slot 1 (z and r.z: written by the V-cycle if there is one)
-        if (s.d_kept)
-            c->n_d_kept++;
-        else
-            hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d,
-                               (const CgScalars *)nullptr);
-        hipLaunchKernelGGL(k_cg_start_pred, dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, (const double2 *)c->x, (const double2 *)c->pred_d,
-                           (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], s.P_rr[1], s.P_bb);
-    } else if (c->test_starts && s.mg && wait_first_on() && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on &&
-               !comm_active(c) && matfree(c)) {
-        // solve_first_test will wait for the first test before it enqueues anything that reads r or z, and expects it to pass:
-        // the sums of that test alone.  If it fails, k_cg_start follows there.
-#define TEST_START(G)                                                                                                          \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cg_start_test<G>), dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, 1, (const double2 *)c->x, \
-                       (const double2 *)c->rhs, (const double2 *)c->dinv, s.P_rr[1], s.P_bb, s.olo, s.ohi)
-        if (c->op.colr) TEST_START(2); else TEST_START(1);   // (the matrix-free instantiations, as LAUNCH_OP1 picks them)
-#undef TEST_START
-        s.test_only = true;
-        c->n_test_starts++;
-    } else {   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
-        if ((rc = ensure_dinv(c))) return rc;   // (z = dinv r)
-        LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, warm ? 1 : 0, (const double2 *)c->x, (const double2 *)c->rhs,
-                   (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, s.olo, s.ohi);
-    }
-    if (c->strip.on) {  // sums of the whole grid; r valid on every local column (the V-cycle reads the halo)
-        if ((rc = part_allreduce(c, s.P_rz[1], (size_t)3 * MAXPART))) return rc;
-        if ((rc = halo_refresh(c, c->r))) return rc;
-    }
-    if (!s.mg) {   // Jacobi-PCG reads dinv's values in every update (the plain start above has formed a late one already)
-        if ((rc = ensure_dinv(c))) return rc;
-        hipLaunchKernelGGL(k_cg_setup, dim3(1), dim3(BLOCK), 0, c->stream, s.P_bb, gn, rtol, c->sc);
-    }
-    return 0;
-}
-
-// multigrid-PCG: z0 = V-cycle(r0) replaces the Jacobi z of k_cg_init -- unless x0 already satisfies the tolerance.  Leaves
-// s.done / s.hs as the host saw them and, while not done, the head of the V-cycle enqueued.
-int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
-{
-    const size_t nd = s.nd;
-    const int nn = s.nn, gn = s.gn, olo = s.olo, ohi = s.ohi;
-    int rc;
-    bool first_passed = false, pred_first_passed = false;
-    unsigned long long seq = cg_setup_check_post(c, s.P_bb, s.P_rr[1], gn, rtol);   // (scalars set up and first test: one launch)
-    const bool wait_first = wait_first_on();
-    if (wait_first && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on) {
-        // the predictor solve of a load step repeats the system of the solve before it up to the last bits of its boundary
-        // values: x passes the first test.  Learn that before enqueuing what would return at once (six launches, 28 us)
-        // du of a passed test is composed under the round trip: gated on the flag the test just wrote, a no-op otherwise
-        const bool early = c->bc_rows_on && c->reuse && !comm_active(c);
-        if (early) {
-            hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du,
-                               (const CgScalars *)c->sc);
-            HIPCHK(c, hipGetLastError());
-        }
-        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
-        s.done = s.hs.done;
-        first_passed = s.done != 0;
-        if (early && s.done == 1) {
-            s.du_early = true;
-            c->n_du_early++;
-        }
-        if (s.test_only && !first_passed) {
-            // the hint was wrong: r, z and r.z after all -- one operator pass more than without the test-only start.  The sums of
-            // r.r and b.b are rewritten with the bits the test has seen.
-            if ((rc = ensure_dinv(c))) return rc;
-            LAUNCH_OP1(k_cg_start, matfree(c), dim3(gn), c->op, nn, 1, (const double2 *)c->x, (const double2 *)c->rhs,
-                       (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->z, s.P_rz[1], s.P_rr[1], s.P_bb, olo, ohi);
-            HIPCHK(c, hipGetLastError());
-            s.test_only = false;
-            c->n_test_retries++;
-        }
-    }
-    if (first_passed) {
-        pred_first_passed = true;   // (nothing to do: done, hs as the chain below would have left them)
-    } else if (s.pred_active) {
-        // Everything the interpolated start needs is enqueued behind the first test and returns at once if that test passed
-        // (the reference repeats solves of one system: x satisfies the tolerance as it is); the host waits ONCE, for the second
-        // test (round 6: three round trips -> one).  d = x - (solution before), K d, the two sums, alpha on the device
-        // (k_pred_alpha), | P (r - alpha K d) |^2 into the free slot P_rr[0] without touching x, r, z, the test on it.
-        if (!s.pred_fused) {   // (the fused start has left d in pred_d and K d in p[0])
-            if (s.d_kept)
-                c->n_d_kept++;
-            else
-                hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d, c->sc);
-            LAUNCH_OP2(k_spmv, 0, matfree(c), dim3(gn), c->op, 0, nn, (const double2 *)c->pred_d, nullptr, nullptr, (double2 *)c->p[0],
-                       nullptr, nullptr, nullptr, 0, nullptr, c->sc, 0, 0, 0);
-        }
-        const int gp = MAXPART;   // (one size on every rank: the all-reduce of the partial sums pairs up)
-        hipLaunchKernelGGL(k_pred_dots, dim3(gp), dim3(BLOCK), 0, c->stream, (size_t)2 * olo, (size_t)2 * ohi, c->dinv, c->r, c->p[0],
-                           c->part, c->sc);
-        HIPCHK(c, hipGetLastError());
-        if (c->strip.on && (rc = part_allreduce(c, c->part, (size_t)2 * MAXPART))) return rc;
-        hipLaunchKernelGGL(k_pred_try, dim3(gn), dim3(BLOCK), 0, c->stream, nn, c->sc, (const double *)c->part, gp, (const double2 *)c->r,
-                           (const double2 *)c->p[0], (const double2 *)c->dinv, s.P_rr[0], olo, ohi);
-        HIPCHK(c, hipGetLastError());
-        if (c->strip.on && (rc = part_allreduce(c, s.P_rr[0], gn))) return rc;
-        seq = cg_check_post(c, s.P_rr[0], gn, -2);   // (iters = -2 marks "converged by the interpolated start")
-        if (!c->strip.on)   // x, du and the history in one pass -- behind the test, before the host has seen it (no-op unless accepted)
-            hipLaunchKernelGGL(k_pred_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x,
-                               c->pred_d, c->pred_x, (const double *)c->dup, (const double *)c->is_presc, c->du,
-                               ((c->short_solve & 2) && !comm_active(c)) ? 1 : 0);
-        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
-        s.done = s.hs.done;
-        if (s.done == 1 && s.hs.iters == -2) {   // it is the solution: commit x (r, z are not read again: the loop is skipped)
-            // (k_pred_finish has moved x and pred_x -- and, told to, left the d of the next start in pred_d; k_pred_commit moves x alone)
-            c->pred_d_kept = !c->strip.on && (c->short_solve & 2) && !comm_active(c);
-            if (!c->strip.on)
-                s.pred_finished = true;
-            else
-                hipLaunchKernelGGL(k_pred_commit, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x, c->pred_d);
-            HIPCHK(c, hipGetLastError());
-            s.hs.iters = 0;
-            c->n_pred++;
-            s.pred_d_ready = true;
-            s.pred_moved = true;
-        } else if (!s.done) {
-            s.pred_d_ready = true;
-            if (s.hs.aux > 0.) c->n_pred_rejected++;
-            else c->n_pred_skipped++;
-        }
-        if (!s.done) {
-            if ((rc = mg_ensure(c))) return rc;
-            if ((rc = mg_vcycle_head(c))) return rc;
-        }
-        pred_first_passed = s.done == 1 && !s.pred_moved;
-    } else if (c->mg_pending) {
-        // the coarse levels are stale (mg_ensure): learn first whether a V-cycle is needed at all
-        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
-        s.done = s.hs.done;
-        if (!s.done) {
-            if ((rc = mg_ensure(c))) return rc;
-            if ((rc = mg_vcycle_head(c))) return rc;
-        }
-    } else {
-        if ((rc = ensure_dinv(c))) return rc;     // (never late here -- a late dinv has a pending set-up beside it -- but cheap to say)
-        if ((rc = mg_vcycle_head(c))) return rc;  // speculative: its kernels return at once if the flag says converged
-        if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
-        s.done = s.hs.done;
-    }
-    if (site >= 0 && s.pred_active) c->first_test_hint[site] = pred_first_passed;
-    return 0;
-}
-
-// the PCG loop: at most `maxit` iterations from s.it = 0, until the flag says done
-int pcg_iterate(plfx_ctx *c, SolveRun &s, int maxit)
-{
-    const int nn = s.nn, gn = s.gn, olo = s.olo, ohi = s.ohi;
-    const bool mg = s.mg, multi = s.multi;
-    double *const P_pq = s.P_pq, *const *P_rz = s.P_rz, *const *P_rr = s.P_rr;
-    CgScalars &hs = s.hs;
-    int rc;
-    const int chunk = mg ? 1 : 50;  // multigrid: the flag is polled inside the iteration, before the V-cycle
-    int &it = s.it;
-    if (it < maxit && !s.done) c->pred_d_kept = false;   // (the update kernels move x)
-    while (it < maxit && !s.done) {
-        const int stop = std::min(maxit, it + chunk);
-        for (; it < stop; it++) {
-            const int cur = it & 1;  // partial slot written by this iteration's update kernel
-            const int prev = cur ^ 1;
-            double *pold = c->p[prev], *pnew = c->p[cur];
-            EvPair *ev;
-            tim_begin(c, 1, &ev);
-            launch_direction(c, s, it);
-            tim_end(c, ev);
-            if ((rc = part_allreduce(c, P_pq, gn))) return rc;
-            if (multi) {
-                hipLaunchKernelGGL(k_p_update_outside, dim3(gn), dim3(BLOCK), 0, c->stream, nn, c->own_n0,
-                                   c->own_n1, (const double2 *)pold, (const double2 *)c->z, (double2 *)pnew,
-                                   (double2 *)c->q, P_rz[prev], P_rz[cur], P_rr[prev], gn, c->sc);
-                if ((rc = allreduce(c, c->q, s.nd, NCCL_FLOAT64, NCCL_SUM, "q"))) return rc;
-                hipLaunchKernelGGL(k_dot_pq, dim3(gn), dim3(BLOCK), 0, c->stream, nn, (const double2 *)pnew,
-                                   (const double2 *)c->q, P_pq, c->sc);
-            }
-            if (mg) {
-                tim_begin(c, 2, &ev);
-                hipLaunchKernelGGL(k_cg_update_mg, dim3(gn), dim3(BLOCK), 0, c->stream, nn, (const double2 *)pnew,
-                                   (const double2 *)c->q, (const double2 *)c->dinv, (double2 *)c->x,
-                                   (double2 *)c->r, P_pq, gn, P_rz[prev], gn, P_rr[cur], c->sc, olo, ohi);
-                tim_end(c, ev);
-                if (c->strip.on) {
-                    if ((rc = part_allreduce(c, P_rr[cur], gn))) return rc;
-                    if ((rc = halo_refresh(c, c->r))) return rc;  // the one vector exchange of a PCG iteration
-                }
-                // stop here if this update converged: the V-cycle below would only prepare the next iteration
-                const unsigned long long seq = cg_check_post(c, P_rr[cur], gn, it + 1);
-                EvPair *evv;
-                tim_begin(c, 4, &evv);
-                if ((rc = mg_vcycle_head(c))) return rc;  // overlaps the round trip of the flag
-                if ((rc = cg_check_wait(c, seq, &hs))) return rc;
-                if (hs.done) {
-                    tim_end(c, evv);
-                    if (c->tim.on) c->tim.noop[4]++;  // a head that returned at once is not a V-cycle
-                    it++;
-                    break;
-                }
-                if ((rc = precondition_rz(c, P_rz[cur], evv))) return rc;
-            } else {
-                tim_begin(c, 2, &ev);
-                hipLaunchKernelGGL(k_cg_update, dim3(gn), dim3(BLOCK), 0, c->stream, nn, (const double2 *)pnew,
-                                   (const double2 *)c->q, (const double2 *)c->dinv, (double2 *)c->x,
-                                   (double2 *)c->r, (double2 *)c->z, P_pq, gn, P_rz[prev], P_rr[prev], gn,
-                                   P_rz[cur], P_rr[cur], c->sc);
-                tim_end(c, ev);
-            }
-        }
-        HIPCHK(c, hipGetLastError());
-        if (!mg) {
-            HIPCHK(c, hipMemcpyAsync(&hs, c->sc, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, stream_sync(c));
-        }
-        s.done = hs.done;
-    }
-    return 0;
-}
-
-// PLFX_SOLVE_DEBUG: what made multigrid-PCG give up: sums of the last iteration, NaN census
-void solve_debug_dump(plfx_ctx *c, const SolveRun &s)
-{
-    const size_t nd = s.nd;
-    const int gn = s.gn, it = s.it;
-    const CgScalars &hs = s.hs;
-    stream_sync(c);
-    std::vector<double> hp((size_t)6 * MAXPART), hv(nd);
-    hipMemcpy(hp.data(), c->part, hp.size() * 8, hipMemcpyDeviceToHost);
-    auto psum = [&](int slot) { double t = 0.; for (int i = 0; i < gn; i++) t += hp[(size_t)slot * MAXPART + i]; return t; };
-    auto census = [&](const double *dev, const char *name) {
-        hipMemcpy(hv.data(), dev, nd * 8, hipMemcpyDeviceToHost);
-        size_t nan = 0, neg = 0; double mx = 0., mn = 1e300;
-        for (size_t i = 0; i < nd; i++) { const double v = hv[i]; if (!(v == v)) nan++; else { if (v < 0.) neg++; mx = std::max(mx, std::fabs(v)); if (v != 0.) mn = std::min(mn, std::fabs(v)); } }
-        fprintf(stderr, "    %-5s nan %zu  negative %zu  max|.| %.3e  min nonzero|.| %.3e\n", name, nan, neg, mx, mn);
-    };
-    fprintf(stderr, "[plfx_solve] multigrid-PCG gave up after %d iterations: done %d rr_final %.3e thresh2 %.3e | p.q %.6e  r.z %.6e / %.6e  r.r %.6e / %.6e  b.b %.6e\n",
-            it, hs.done, hs.rr_final, hs.thresh2, psum(0), psum(1), psum(3), psum(2), psum(4), psum(5));
-    census(c->dinv, "dinv"); census(c->r, "r"); census(c->z, "z"); census(c->x, "x"); census(c->q, "q");
-    {
-        std::vector<double> hm((size_t)6 * c->nel_total);
-        hipMemcpy(hm.data(), matfree(c) ? c->Mop : c->Mel, hm.size() * 8, hipMemcpyDeviceToHost);
-        size_t nan = 0; double mx = 0.;
-        for (double v : hm) { if (!(v == v)) nan++; else mx = std::max(mx, std::fabs(v)); }
-        fprintf(stderr, "    generators nan %zu  max|.| %.3e\n", nan, mx);
-        // per element: smallest eigenvalue of the 3 x 3 generator matrix [XX XY XS; XY YY YS; XS YS SS] (PSD for a PSD tangent)
-        const size_t ne = c->nel_total;
-        size_t nneg = 0, worst = 0; double wv = 0.;
-        for (size_t e = 0; e < ne; e++) {
-            const bool pr = matfree(c);  // layout of the array read above
-            const double a = hm[gen_index(pr, 0, ne, e)], b = hm[gen_index(pr, 1, ne, e)], cc = hm[gen_index(pr, 2, ne, e)],
-                         d = hm[gen_index(pr, 3, ne, e)], f = hm[gen_index(pr, 4, ne, e)], g = hm[gen_index(pr, 5, ne, e)];
-            // Sylvester: leading minors
-            const double m1 = a, m2 = a * d - b * b, m3 = a * (d * g - f * f) - b * (b * g - f * cc) + cc * (b * f - d * cc);
-            const double sc1 = std::fabs(a) + std::fabs(d) + std::fabs(g);
-            const double bad = std::min(m1 / sc1, std::min(m2 / (sc1 * sc1), m3 / (sc1 * sc1 * sc1)));
-            if (bad < -1e-9) { nneg++; if (bad < wv) { wv = bad; worst = e; } }
-        }
-        fprintf(stderr, "    elements with an indefinite generator matrix: %zu of %zu (worst scaled minor %.3e at element %zu)\n", nneg, ne, wv, worst);
-        if (nneg && worst >= (size_t)c->e0 && worst < (size_t)c->e0 + c->nel) {
-            const size_t e = worst - c->e0, n = c->nel;
-            double v[21]; int ms = 0; double fy = 0.;
-            fprintf(stderr, "      class %d material %d kind %d  M =", (int)c->hcls_id[worst], c->hcls[c->hcls_id[worst]].mat, (int)c->hmat[c->hcls[c->hcls_id[worst]].mat].kind);
-            for (int k = 0; k < 6; k++) fprintf(stderr, " %.6e", hm[gen_index(matfree(c), k, ne, worst)]);
-            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->sig + k * n + e, 8, hipMemcpyDeviceToHost);
-            fprintf(stderr, "\n      sig = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_sig + k * n + e, 8, hipMemcpyDeviceToHost);
-            fprintf(stderr, "\n      res_sig = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->epl + k * n + e, 8, hipMemcpyDeviceToHost);
-            fprintf(stderr, "\n      epl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-            for (int k = 0; k < 6; k++) hipMemcpy(&v[k], c->res_depl + k * n + e, 8, hipMemcpyDeviceToHost);
-            fprintf(stderr, "\n      res_depl = %.6e %.6e %.6e %.6e %.6e %.6e", v[0], v[1], v[2], v[3], v[4], v[5]);
-            {
-                double *tmp = nullptr;
-                if (!dalloc(c, &tmp, 21 * n)) {
-                    launch_tangent_expand(c, tmp, 0);
-                    hipStreamSynchronize(c->stream);
-                    for (int k = 0; k < 21; k++) hipMemcpy(&v[k], tmp + k * n + e, 8, hipMemcpyDeviceToHost);
-                    dfree(tmp);
-                }
-            }
-            fprintf(stderr, "\n      elstiff(21) =");
-            for (int k = 0; k < 21; k++) fprintf(stderr, " %.5e", v[k]);
-            hipMemcpy(&ms, c->max_steps + e, 4, hipMemcpyDeviceToHost);
-            hipMemcpy(&fy, c->fyn + e, 8, hipMemcpyDeviceToHost);
-            fprintf(stderr, "\n      max_steps %d  fyn %.6e\n", ms, fy);
-        }
-    }
-}
-
-// negative curvature met (p.K p <= 0) or a NaN residual: the tangent stiffness is not positive definite (lstsq
-// correction of Material.response, material.py:324-338) -- the reference's LU solves such systems, and so does
-// right-preconditioned GMRES with the V-cycle of the operator as it is (need not be SPD), from PCG's last iterate
-int finish_by_gmres(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, int *iters, double *relres)
-{
-    int itm = 0, rc;
-    double rl = 0.;
-    c->n_indefinite++;
-    c->pred_d_kept = false;   // (GMRES moves x)
-    const int rcm = gmres_solve(c, rtol, maxit_all, &itm, &rl);
-    if (rcm < 0) return rcm;
-    c->n_gmres++;
-    if (solve_debug_on()) fprintf(stderr, "[plfx_solve] GMRES(%d): rc %d, %d iterations, relative residual %.3e\n", c->gm_m, rcm, itm, rl);
-    if ((rc = compose_du(c))) return rc;
-    c->x_is_du = true;
-    if (iters) *iters = s.it + itm;
-    if (relres) *relres = rl;
-    c->pred_valid = c->pred_d_kept = false;   // (not a plain PCG solve: the history of the initial guess starts again)
-    remember(c, rtol, rl, rcm == 0);
-    return rcm == 0 ? PLFX_OK : 1;
-}
-
-// breakdown (indefinite tangent, preconditioner not SPD) or stagnation of multigrid-PCG: Jacobi-PCG, warm-started from the
-// last iterate.  Strip: every rank sees the same all-reduced sums and comes here together; Jacobi-PCG runs through the same
-// loop (owned-only sums, halo refresh of r per iteration) with z = D^-1 r in place of the V-cycle (strip_jacobi).
-int fall_back_to_jacobi(plfx_ctx *c, const SolveRun &s, double rtol, int maxit_all, int *iters, double *relres)
-{
-    int rc;
-    c->pred_d_kept = false;
-    if ((rc = ensure_dinv(c))) return rc;   // (Jacobi-PCG: z = dinv r throughout)
-    if ((rc = compose_du(c))) return rc;
-    const int saved = c->precond;   // (changed and restored off a strip only)
-    if (c->strip.on) c->strip_jacobi = true;
-    else c->precond = 0;
-    c->mg_fallbacks++;
-    int it2 = 0;
-    const int rc2 = solve_impl(c, rtol, maxit_all, 1, -1, &it2, relres);
-    if (c->strip.on) c->strip_jacobi = false;
-    else c->precond = saved;
-    // (the strip branch never printed this line: kept so, every rank would print it)
-    if (!c->strip.on && solve_debug_on()) fprintf(stderr, "[plfx_solve] Jacobi fall-back: rc %d, %d iterations, relative residual %.3e\n", rc2, it2, relres ? *relres : -1.);
-    if (iters) *iters = s.it + it2;
-    return rc2;
-}
-
-// the last residual if no test has seen it, du, the history of the initial guess, the memo
-int solve_finish(plfx_ctx *c, SolveRun &s, double rtol, int *iters, double *relres)
-{
-    const size_t nd = s.nd;
-    CgScalars &hs = s.hs;
-    int rc, done = s.done;
-    const int it = s.it;
-    if (done == 2) done = 0;  // Jacobi-PCG breakdown: report as not converged
-    if (!done) {
-        // the convergence test of iteration `it` has not run yet: evaluate the last residual
-        hipLaunchKernelGGL(k_cg_final, dim3(1), dim3(BLOCK), 0, c->stream, s.P_rr[(it - 1) & 1], s.gn, c->sc);
-        HIPCHK(c, hipMemcpyAsync(&hs, c->sc, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, stream_sync(c));
-    }
-    if (!s.pred_finished && !s.du_early && (rc = compose_du(c))) return rc;
-    c->x_is_du = true;  // x = du on the free DOFs, 0 on the prescribed ones: the next warm start
-    const int its_done = (done && hs.iters >= 0) ? hs.iters : it;
-    // history of the initial guess: the solution this solve started from becomes "the one before" -- only if this solve moved
-    // away from it (the reference repeats solves of one system: such a solve ends where it started and must not erase d)
-    if (s.pred_d_ready && !s.pred_finished && (s.pred_moved || its_done > 0)) {
-        hipLaunchKernelGGL(k_pred_advance, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->pred_x, c->pred_d);
-        c->pred_d_kept = false;   // (pred_x moved)
-    }
-    if (iters) *iters = its_done;
-    if (c->tim.on && done) {  // launches after convergence are no-ops: keep them out of the averages
-        c->tim.noop[1] += it - hs.iters;
-        c->tim.noop[2] += it - hs.iters;
-    }
-    const double bb = hs.thresh2 / (rtol * rtol);
-    const double rl = (bb > 0. && hs.rr_final >= 0.) ? std::sqrt(hs.rr_final / bb) : 0.;
-    if (relres) *relres = rl;
-    remember(c, rtol, rl, done == 1);
-    return done ? PLFX_OK : 1;  // 1 = iteration limit reached (soft failure, like co_nconv)
-}
-
-// The solve behind plfx_solve and plfx_load_step.  The caller guarantees c != null and c->bc_set (plfx_solve checks them;
-// step_solve runs behind a successful step_apply_bc).  site: see plfx_ctx::first_test_hint, -1 = no site.
-int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *iters, double *relres)
-{
-    c->spec_setup = c->spec_kdu = false;   // (a solve overwrites c->q: nothing enqueued behind a sweep's flags is valid beyond it)
-    if (maxit < 1) maxit = 1;
-    if (c->reuse && warm && c->x_is_du && c->memo.valid && c->memo.rtol == rtol) {
-        // the system of the previous converged solve (no assembly, no other boundary values since): du is its solution
-        c->n_reuse_solve++;
-        if (iters) *iters = 0;
-        if (relres) *relres = c->memo.relres;
-        return PLFX_OK;
-    }
-    SolveRun s{c->part, {c->part + MAXPART, c->part + 3 * MAXPART}, {c->part + 2 * MAXPART, c->part + 4 * MAXPART}, c->part + 5 * MAXPART,
-               own_lo(c), own_hi(c), c->grid_nodes, c->nnode, (size_t)c->ndof};   // (the rest: false / zero)
-    if (c->strip.on && !mg_active(c)) return fail(c, PLFX_ERR_STATE, "a strip solves with the multigrid preconditioner only");
-    // Sharded run with the assembled operator: every rank applies its own rows, one all-reduce of the global vector per
-    // CG step.  With the matrix-free operator every rank holds all generators and a full K p costs ~50 us at 1024^2 --
-    // several times less than all-reducing 16.8 MB over xGMI -- so the product is computed redundantly and the solve has
-    // no collective at all (PLFX_SHARD_SPMV=1 restores the sharded rows + all-reduce).
-    static const bool force_shard_spmv = getenv("PLFX_SHARD_SPMV") && atoi(getenv("PLFX_SHARD_SPMV")) != 0;
-    s.multi = comm_active(c) && (!matfree(c) || force_shard_spmv);
-    s.mg = mg_active(c);
-    int rc;
-    if ((rc = solve_start(c, s, rtol, warm, site))) return rc;
-    if (s.mg && (rc = solve_first_test(c, s, rtol, site))) return rc;
-    if (s.mg && !s.done && (rc = precondition_rz(c, s.P_rz[1]))) return rc;
-    // beta of the first iteration is 0 (k_spmv<1> takes p = z for it == 0 without touching p_old); only the sharded
-    // k_p_update_outside path still derives it from the partials: rz_old = +inf, p_old = 0
-    if (s.multi) {
-        hipLaunchKernelGGL(k_fill, dim3(1), dim3(BLOCK), 0, c->stream, s.P_rz[0], (size_t)s.gn, (double)INFINITY);
-        HIPCHK(c, hipMemsetAsync(c->p[1], 0, 8 * s.nd, c->stream));
-    }
-    HIPCHK(c, hipGetLastError());
-    // multigrid-PCG converges in tens of iterations or not at all (PLFX_MG_MAXIT: the cap, for tests of the fall-back)
-    const int mg_cap = getenv("PLFX_MG_MAXIT") ? std::max(1, atoi(getenv("PLFX_MG_MAXIT"))) : 300;
-    const int maxit_pcg = (s.mg && !c->strip_jacobi) ? std::min(maxit, mg_cap) : maxit;
-    if ((rc = pcg_iterate(c, s, maxit_pcg))) return rc;
-    if (solve_debug_on() && s.mg && s.done != 1) solve_debug_dump(c, s);
-    if (s.done != 1 && s.hs.done == 2) return finish_by_gmres(c, s, rtol, maxit, iters, relres);
-    if (s.mg && s.done != 1 && !c->strip_jacobi) return fall_back_to_jacobi(c, s, rtol, maxit, iters, relres);
-    return solve_finish(c, s, rtol, iters, relres);
-}
-
-}  // namespace host
-}  // namespace plfx
-
-extern "C" {
-
-int plfx_solve(plfx_ctx *c, double rtol, int maxit, int warm, int *iters, double *relres)
-{
-    if (!c || !c->bc_set) return c ? fail(c, PLFX_ERR_STATE, "apply_bc first") : PLFX_ERR_STATE;
-    return solve_impl(c, rtol, maxit, warm, -1, iters, relres);
 }
 
 int plfx_matvec(plfx_ctx *c, const double *x, double *y)

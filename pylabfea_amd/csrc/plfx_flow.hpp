@@ -3,7 +3,7 @@
 //   x_0 = the point of the yield locus along su at epl; record (x_0, epl, yf_0); then, while eps_eq(epl) + depl <= epl_max
 //   and k < max_steps:  peeq = eps_eq(epl) + depl;  a = calc_fgrad(su (x_k + peeq predictor), epl);
 //   epl += a depl / eps_eq(a);  x_{k+1} = the point of the locus at the new epl; record it.
-// Included from plfx.hip after plfx_kernels.hpp.
+// Included from plfx_material.hip after plfx_kernels.hpp.
 //
 // k_flow_curve<NF>: the SVC kinds, NF = 6 / 15.  Block, table staging and lane contract are k_yield_scale's (DESIGN section
 // 27): 16 lanes per curve, four curves per wave, svc_row_tables / svc_row_trips, rows closed by row_allsum.  The step loop

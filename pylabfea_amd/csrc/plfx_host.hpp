@@ -1,7 +1,7 @@
 // plfx_host.hpp -- what the translation units of libplfx.so share on the host side: the context, the error / allocation /
-// timing helpers and the launch macros.  Included by plfx.hip and plfx_step.hip and by nothing outside csrc/.  Every helper
-// declared here is defined in exactly one unit (named at its declaration); the unit map and the rule that every kernel has one
-// owning unit are in DESIGN.md section 39.  The C-ABI is include/plfx.h.
+// timing helpers and the launch macros.  Included by the four units (plfx.hip, plfx_step.hip, plfx_material.hip, plfx_solve.hip)
+// and by nothing outside csrc/.  Every helper declared here is defined in exactly one unit (named at its declaration); the unit
+// map and the rule that every kernel has one owning unit are in DESIGN.md sections 39 and 42.  The C-ABI is include/plfx.h.
 //
 // HBM layout (FP64 / int32, everything resident for the life of the mesh):
 //   per owned element e (SoA, component-major [c*nel + e]): sig[6] epl[6] eps[6] res_sig[6]
@@ -610,8 +610,15 @@ void mg_graph_drop(plfx_ctx *c);
 int strip_coarse(plfx_ctx *c);
 void strip_free(plfx_ctx *c);
 int plain_spmv(plfx_ctx *c, const double *in, double *out);
-int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *iters, double *relres);
-// ... and its kernels that the step unit needs launched
+bool march_pcg(const plfx_ctx *c);
+int ensure_dinv(plfx_ctx *c);
+int mg_ensure(plfx_ctx *c);
+int mg_vcycle_head(plfx_ctx *c);
+int mg_vcycle_rest(plfx_ctx *c, double *rz_part, bool *wrote);
+int mg_vcycle(plfx_ctx *c);
+// ... and its kernels that the step and solve units need launched
+void launch_spmv_plain(plfx_ctx *c, const double *in, double *out, CgScalars *sc);   // k_spmv MODE 0: out = K in (sc: device-side predicate or null)
+void launch_jacobi_z(plfx_ctx *c);                      // k_jacobi_z: z = D^-1 r
 void launch_mbox_post(plfx_ctx *c, const double *src, int n, double *dst, CgMbox *mb, unsigned long long seq);   // k_mbox_post
 void launch_kdu_uf(plfx_ctx *c, CgScalars *spec);       // k_spmv MODE 3: u += du, f += K du (spec: device-side predicate or null)
 void launch_spec_setup(plfx_ctx *c);                    // the set-up pass a sweep enqueues behind its flags (k_grid_setup)
@@ -623,10 +630,19 @@ int raise_step_lds(plfx_ctx *c);
 void launch_response_row(plfx_ctx *c, int k, const int32_t *tex_id, int n, const int32_t *mat_id, const double *sig, const double *epl,
                          const double *deps, double *fy, double *sig_out, double *depl, double *ct, int32_t *nsteps);   // k_response_row
 void launch_path_row(plfx_ctx *c, int k, const int32_t *tex_id, const PathArgs &a);   // k_path_row
-void launch_tangent_expand(plfx_ctx *c, double *out, int to_full);
+void launch_tangent_expand(plfx_ctx *c, double *out, int to_full);   // k_tangent_expand over the owned elements
 #ifdef PLFX_PROF_REGIONS
-bool prof_regions_add(unsigned long long h[16]);   // h += the step unit's g_prof (probe builds; plfx_destroy prints the sums)
-#endif   // k_tangent_expand over the owned elements
+bool prof_regions_add_step(unsigned long long h[16]);   // h += the step unit's g_prof (probe builds; plfx_destroy prints the sums)
+#endif
+
+// plfx_material.hip
+void free_materials(plfx_ctx *c);
+#ifdef PLFX_PROF_REGIONS
+bool prof_regions_add_material(unsigned long long h[16]);   // ... += the material unit's
+#endif
+
+// plfx_solve.hip
+int solve_impl(plfx_ctx *c, double rtol, int maxit, int warm, int site, int *iters, double *relres);
 
 }  // namespace host
 }  // namespace plfx

@@ -2990,13 +2990,6 @@ __global__ void __launch_bounds__(BLOCK) k_fill(double *a, size_t n, double v)
 {
     for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < n; i += (size_t)gridDim.x * BLOCK) a[i] = v;
 }
-
-// y[idx[k]] = v[k]
-__global__ void __launch_bounds__(BLOCK) k_scatter(int n, const int32_t *idx, const double *v, double *y)
-{
-    const int k = blockIdx.x * BLOCK + threadIdx.x;
-    if (k < n) y[idx[k]] = v[k];
-}
 #endif
 
 // y[idx[k]] = a[k], z[idx[k]] = b[k], (flag ? m[idx[k]] = 1)  : prescribed-DOF data of apply_bc in one launch

@@ -504,7 +504,7 @@ k_scale_copy(int nn, double s, const double2 *__restrict__ src, double2 *__restr
 // vectors; here the second pass of vector j is delayed by one iteration and shares its two sweeps over the basis with the
 // first pass of vector j + 1 (Swirydowicz, Langou, Ananthan, Yang, Thomas 2020; Bielich et al. 2022: "DCGS-2"):
 // with u = the once-projected candidate for q_j and z = A u, ONE dots pass yields s = Q^T u, t = Q^T z, u.u, u.z, and ONE update
-// pass writes q_j = (u - Q s) / alpha and the next candidate (z - Q t) / alpha - e alpha q_j (plfx.hip: gmres_solve has the
+// pass writes q_j = (u - Q s) / alpha and the next candidate (z - Q t) / alpha - e alpha q_j (plfx_solve.hip: gmres_solve has the
 // algebra).  Up to 128 basis vectors per dots launch, all of them in one update launch.
 struct GmBlocks {
     const double *blk[40];   // 40 allocations of GMRES_BLK = 32 vectors hold the 1201 vectors of the longest cycle

@@ -1,6 +1,6 @@
 // plfx_step.hip -- libplfx.so: sweeps, load step, state update, state access, global sums, element fields.
-// Everything else of the host side is plfx.hip.  Unit map and the one-owner rule for kernels: DESIGN.md section 39; what the
-// two units share: plfx_host.hpp.
+// The material-point functions are plfx_material.hip, the linear solve plfx_solve.hip, everything else of the host side
+// plfx.hip.  Unit map and the one-owner rule for kernels: DESIGN.md sections 39 and 42; what the units share: plfx_host.hpp.
 #define PLFX_UNIT_STEP
 #include "plfx_host.hpp"
 
@@ -31,7 +31,7 @@ int split_res_sig(plfx_ctx *c)
 }
 
 #ifdef PLFX_PROF_REGIONS
-bool prof_regions_add(unsigned long long h[16])
+bool prof_regions_add_step(unsigned long long h[16])
 {
     unsigned long long mine[16];
     if (hipMemcpyFromSymbol(mine, HIP_SYMBOL(g_prof), sizeof(mine)) != hipSuccess) return false;

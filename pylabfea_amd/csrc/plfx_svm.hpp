@@ -1,5 +1,5 @@
 // plfx_svm.hpp — training of binary RBF C-SVC yield functions (Material.train_SVC, material.py:1596-1640): a batched SMO
-// solver and a batched decision function.  Included from plfx.hip after its error helpers (fail, HIPCHK).
+// solver and a batched decision function.  Included from plfx_material.hip after the error helpers (fail, HIPCHK).
 //
 // The problem is libsvm's C-SVC dual, min 1/2 a'Qa - e'a, 0 <= a <= C, y'a = 0, Q_ij = y_i y_j exp(-g |x_i - x_j|^2), solved
 // by libsvm's NON-shrinking solver step for step (Fan, Chen & Lin, JMLR 6, 2005; Chang & Lin, ACM TIST 2, 2011): a = 0,

@@ -2,7 +2,7 @@
 // [six stresses | tdim texture coefficients], every column standardised with its own mean and scale (the reference's
 // StandardScaler on a txdat material, material.py:2347-2361), evaluated at points (k_tex_yf) and searched along rays
 // (k_tex_yield_scale: the loci of examples/Texture/train_texture.py, every texture x every ray in one launch).
-// Included from plfx_host.hpp (for TexSvcPar) after plfx_kernels.hpp; its kernels are launched by plfx.hip alone.  The set belongs to the context, not to a material record.
+// Included from plfx_host.hpp (for TexSvcPar) after plfx_kernels.hpp; its kernels are launched by plfx_material.hip alone.  The set belongs to the context, not to a material record.
 //
 // Tables: nsv vectors of NFP feature slots, NFP = 8 / 12 / 16 the padded 6 + tdim, stored with a row stride of NFP + 2 doubles
 // both in device memory and in LDS: the stride in dwords is then 4 (mod 8) x odd, so the 16 lanes of a row, which read 16

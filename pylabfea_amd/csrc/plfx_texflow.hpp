@@ -1,6 +1,6 @@
 // plfx_texflow.hpp -- flow rule and stress update of the texture-dependent SVC yield function: the
 // gradient of calc_yf(sig, tex=) w.r.t. the stress (k_tex_fgrad), ML_full_yf(sig, tex=) (k_tex_full_yf) and
-// Material.response(..., tex=) (k_tex_response).  Included from plfx.hip after plfx_tex.hpp, whose tables, staging and
+// Material.response(..., tex=) (k_tex_response).  Included from plfx_material.hip after plfx_tex.hpp, whose tables, staging and
 // features these kernels share.  The reference has none of this (its calc_fgrad and ML_full_yf fail for a texture material);
 // the semantics are the project's own and are stated where they are implemented.
 //

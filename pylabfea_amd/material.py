@@ -1444,7 +1444,7 @@ class Material(object):
                           'yield_scale: x0 must be a scalar or hold one start value per stress; got shape %s')
         ml = self.ML_yf
         # (_princ_rows: principal-stress materials see general states through the host's LAPACK call; plfx_yield_scale does the
-        # same for callers of the C-ABI, csrc/plfx.hip, and finds nothing left to reduce in these rows)
+        # same for callers of the C-ABI, csrc/plfx_material.hip, and finds nothing left to reduce in these rows)
         x, st = self._load(ana=not ml).yield_scale(0, self._princ_rows(s), e, x0)
         return self._ray_result('yield_scale', 'direction', x, st, single, return_status)
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""numpy model of GMRES with delayed re-orthogonalisation as gmres_solve (plfx.hip) implements it, beside classical Gram-Schmidt twice:
+"""numpy model of GMRES with delayed re-orthogonalisation as gmres_solve (plfx_solve.hip) implements it, beside classical Gram-Schmidt twice:
 same residual history, orthogonality of the basis to 1e-14.   python tools/probes/dcgs2_model.py"""
 import numpy as np
 rng=np.random.default_rng(0)
