@@ -398,6 +398,15 @@ int plfx_bc_info(plfx_ctx *ctx, int64_t *rhs_rows_only, int64_t *dinv_kept, int6
  * every solve of plfx_load_step; plfx_solve called after plfx_assemble or a tangent-changing sweep WITHOUT an apply_bc in
  * between is preconditioned with the dinv of the new diagonal where it used to get the old one's. */
 int plfx_short_info(plfx_ctx *ctx, int64_t *dinv_deferred, int64_t *dinv_formed_late, int64_t *d_kept, int64_t *spec_merged);
+/* Rewritten generators straight into the operator's snapshot (one GPU, plane Hill sweep, matrix-free grid
+ * of one column width, no strip, no communicator; PLFX_DIRECT_SNAP at plfx_create is a bit mask -- 1: a sweep of plfx_load_step
+ * that is certain to be followed by plfx_assemble if it changes a tangent stores each rewritten generator into the snapshot as
+ * well, and the set-up pass behind its flags is left out; 2 (needs 1): into the snapshot alone, the live array follows in
+ * front of its next reader -- default 3, 0 or PLFX_REUSE=0: the launches as they were, all counters stay 0).  Such sweeps
+ * (direct_sweeps); plfx_assemble calls that found the snapshot taken and launched nothing (direct_acknowledged); set-up passes
+ * launched after all in front of a reader of the fine diagonal or of the level-1 generators (setup_formed_late; the rest were
+ * superseded unread); copies of the snapshot back into the live array (live_restored).  Results are the same bit for bit. */
+int plfx_snap_info(plfx_ctx *ctx, int64_t *direct_sweeps, int64_t *direct_acknowledged, int64_t *setup_formed_late, int64_t *live_restored);
 /* Stores that nothing reads (one GPU, no strip; PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: all
  * four stay 0).  Sweeps of plfx_load_step that were certain to be repeated if they changed a tangent, and in which the
  * elements whose tangent changed therefore left res_sig, res_depl and fyn to the next sweep (armed_sweeps; the tangents they

@@ -66,7 +66,7 @@ SYMBOLS = [
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info', 'plfx_load_path', 'plfx_load_path_info',
-    'plfx_dead_store_info', 'plfx_plane_info', 'plfx_short_info',
+    'plfx_dead_store_info', 'plfx_plane_info', 'plfx_short_info', 'plfx_snap_info',
     'plfx_set_svc_cols', 'plfx_mg_info',
     'plfx_set_svc_textures', 'plfx_set_element_textures', 'plfx_response_batch_tid', 'plfx_full_yf_batch_tid',
     'plfx_svc_textures_info',
@@ -850,6 +850,14 @@ class Context(object):
         launch behind the sweep's flags was not kept) since the context was created; PLFX_SHORT_SOLVE=0: all zero"""
         a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self.lib.plfx_short_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
+        return a.value, b.value, r.value, d.value
+
+    def snap_info(self):
+        """(sweeps that stored their rewritten generators into the operator's snapshot themselves, assemblies that found it taken
+        and launched nothing, set-up passes launched after all in front of a reader of the fine diagonal or the level-1
+        generators, copies of the snapshot back into the live array) since the context was created; PLFX_DIRECT_SNAP=0: all zero"""
+        a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_snap_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
         return a.value, b.value, r.value, d.value
 
     def dead_store_info(self):

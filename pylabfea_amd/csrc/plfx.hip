@@ -518,6 +518,7 @@ void free_mesh(plfx_ctx *c)
     dfree(c->bc_rows);
     c->bc_nrows = 0;
     c->rhs_rows_ok = c->dinv_ok = c->dinv_late = false;
+    c->direct_done = c->setup_owed = c->live_owed = false;
     dfree(c->tex_ids);
     c->htex_ids.clear();
     c->tex_ids_ok = false;
@@ -604,6 +605,7 @@ int allreduce(plfx_ctx *c, void *dev, size_t count, int nccl_dtype, int nccl_op,
 int sync_M(plfx_ctx *c)
 {
     if (!comm_active(c) || !c->sharded) return 0;
+    if (int rc = before_M_write(c)) return rc;   // (never owed inside a communicator: said for the rule's sake)
     if (c->strip.on) return strip_sync_M(c);  // strip-local engine: only the halo columns, from the neighbour that owns them
     hipLaunchKernelGGL(k_zero_foreign_M, dim3(grid_for((size_t)6 * c->nel_total)), dim3(BLOCK), 0, c->stream,
                        c->nel_total, c->e0, c->e0 + c->nel, c->Mel);
@@ -764,6 +766,7 @@ KOp make_op(const plfx_ctx *c, int nnode, int nslot, const int32_t *col, const d
 int ensure_dinv(plfx_ctx *c)
 {
     if (!c->dinv_late) return 0;
+    if (int rc = ensure_setup(c)) return rc;   // (c->diag may be owed as well)
     hipLaunchKernelGGL(k_dinv, dim3(grid_for(c->ndof)), dim3(BLOCK), 0, c->stream, (size_t)c->ndof, c->diag, c->is_presc, c->dinv);
     HIPCHK(c, hipGetLastError());
     c->dinv_late = false;
@@ -775,6 +778,8 @@ int ensure_dinv(plfx_ctx *c)
 int assemble_fine_val(plfx_ctx *c)
 {
     if (int rc = ensure_dinv(c)) return rc;   // (k_assemble rewrites c->diag: a late dinv belongs to the diagonal as it is now)
+    if (int rc = ensure_setup(c)) return rc;  // (... and an owed set-up pass must not overwrite k_assemble's diagonal later)
+    if (int rc = ensure_live_M(c)) return rc;
     hipLaunchKernelGGL(k_assemble, dim3(grid_for(c->nnode), c->nslot), dim3(BLOCK), 0, c->stream,
                        c->dcls, c->ncls, c->nnode, c->nslot, c->nq, c->nel_total, c->dcontrib, c->dcls_all,
                        (matfree(c) && c->assembled) ? c->Mop : c->Mel, c->dcol, c->dval, c->diag,
@@ -797,6 +802,7 @@ int mg_assemble(plfx_ctx *c)
 {
     const bool mf = matfree(c);
     const int nl = (int)c->mg.size();
+    if (int rc = ensure_setup(c)) return rc;   // (the generators of level 1 come from the fine level's pass)
     // the matrix-free levels get their Jacobi scaling with the known Dirichlet mask (taken straight from the finest grid: the
     // node lines of every level, the last one included, coincide with node lines of the finest grid)
     c->mg_dinv_current = mf && c->bc_valid;
@@ -1301,6 +1307,53 @@ void launch_spec_setup(plfx_ctx *c)
                        (double2 *)nullptr, 0x7fffffff, (const int *)(c->flags + 8));
 }
 
+// a direct sweep left its new generators in the snapshot alone; the live array gets them back in front of whoever
+// reads it or writes part of it
+int ensure_live_M(plfx_ctx *c)
+{
+    if (!c->live_owed) return 0;
+    hipLaunchKernelGGL(k_restore_M, dim3(grid_for((size_t)c->nel_total, 1 << 16)), dim3(BLOCK), 0, c->stream, (size_t)c->nel_total,
+                       (const double2 *)c->Mop, c->Mel);
+    HIPCHK(c, hipGetLastError());
+    c->live_owed = false;
+    c->n_live_restored++;
+    return 0;
+}
+
+// the set-up pass that a direct sweep left out, in front of whoever reads c->diag or the generators of level 1 --
+// and of whoever writes part of the live array, which this pass reads (before_M_write).  The pass plfx_assemble launches, on
+// generators that are what they were when it was owed: it rewrites the snapshot with equal values.
+int ensure_setup(plfx_ctx *c)
+{
+    if (!c->setup_owed) return 0;
+    if (int rc = ensure_live_M(c)) return rc;
+    KOp live = c->op;
+    live.M = c->Mel;
+    LAUNCH_SETUP(0, live, (double2 *)c->diag,
+                       c->Mop, (mg_active(c) && level_plain(c->mg[0])) ? c->mg[1].Mel : (double *)nullptr, (const double2 *)nullptr, 0, 0,
+                       (double2 *)nullptr);
+    HIPCHK(c, hipGetLastError());
+    c->setup_owed = false;
+    c->n_setup_late++;
+    return 0;
+}
+
+int before_M_write(plfx_ctx *c)
+{
+    c->direct_done = false;   // (a sweep's changed tangents are not the last word on the generators: plfx_assemble launches its pass)
+    if (int rc = ensure_setup(c)) return rc;
+    return ensure_live_M(c);
+}
+
+// A call that re-shapes what plfx_assemble builds: the live generators whole, nothing owed, and the next assembly a full one
+static int snap_settle(plfx_ctx *c)
+{
+    if (int rc = ensure_live_M(c)) return rc;
+    c->direct_done = c->setup_owed = false;
+    c->M_dirty = true;
+    return 0;
+}
+
 }  // namespace host
 }  // namespace plfx
 
@@ -1339,6 +1392,8 @@ int plfx_create(int device, plfx_ctx **out)
     if (!c->reuse) c->plane_switch = false;
     if (const char *e12 = getenv("PLFX_SHORT_SOLVE")) c->short_solve = atoi(e12) & 3;
     if (!c->reuse) c->short_solve = 0;
+    if (const char *e13 = getenv("PLFX_DIRECT_SNAP")) c->direct_snap = atoi(e13) & 3;
+    if (!(c->direct_snap & 1) || !c->reuse) c->direct_snap = 0;   // (B needs A)
     if (const char *e9 = getenv("PLFX_PREDICT")) c->predict = atoi(e9) != 0;
     {
         const char *e5 = getenv("PLFX_MAILBOX");
@@ -1705,6 +1760,10 @@ int plfx_get_kel(plfx_ctx *c, int e, double *Kel)
 {
     if (!c || !c->Mel) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
     if (e < c->e0 || e >= c->e0 + c->nel || !Kel) return fail(c, PLFX_ERR_ARG, "element not owned");
+    if (c->live_owed) {
+        if (int rc = ensure_live_M(c)) return rc;
+        HIPCHK(c, stream_sync(c));   // (the copies below run on the null stream)
+    }
     double M[6];
     for (int k = 0; k < 6; k++)
         HIPCHK(c, hipMemcpy(&M[k], c->Mel + (size_t)k * c->nel_total + e, 8, hipMemcpyDeviceToHost));
@@ -1952,6 +2011,7 @@ int plfx_set_grid(plfx_ctx *c, int nx, int ny)
         return fail(c, PLFX_ERR_ARG, "grid %dx%d does not match the mesh", nx, ny);
     if (c->strip.on)  // the hierarchy, halo analysis and coarse child context of a strip belong to the grid they were set up for
         return fail(c, PLFX_ERR_STATE, "plfx_set_grid after plfx_set_strip: call plfx_set_mesh again");
+    if (int rcs = snap_settle(c)) return rcs;
     const int nrow = ny + 1;
     const bool known = c->hint_nx == nx && c->hint_ny == ny;   // written by plfx_set_mesh_structured: nothing to verify
     for (int e = 0; e < c->nel_total && !known; e++) {  // model.py:935-948
@@ -2049,6 +2109,7 @@ int plfx_set_strip(plfx_ctx *c, int own_col0, int own_col1, int global_col0, int
     if (!c->grid_ok || !c->want_matfree || c->mg.size() < 2)
         return fail(c, PLFX_ERR_UNSUPPORTED, "a strip needs the uniform structured grid (matrix-free operator + multigrid)");
     if (c->colr) return fail(c, PLFX_ERR_UNSUPPORTED, "a strip needs element columns of one width");
+    if (int rcs = snap_settle(c)) return rcs;
     const int nx = c->gx, ny = c->gy, Ld = coarse_level;
     // material state and sweeps: either the whole local mesh (halo elements swept redundantly) or exactly the owned columns
     // (el_begin / el_end of plfx_set_mesh; the generators of the halo columns then come from the neighbours: strip_sync_M)
@@ -2208,6 +2269,7 @@ int plfx_set_operator(plfx_ctx *c, int kind)
     if (kind != 0 && kind != 1) return fail(c, PLFX_ERR_ARG, "operator kind must be 0 (assembled) or 1 (matrix-free)");
     if (c->strip.on && kind != 1) return fail(c, PLFX_ERR_UNSUPPORTED, "a strip (plfx_set_strip) runs the matrix-free operator only");
     if (kind != c->want_matfree) {
+        if (int rcs = snap_settle(c)) return rcs;
         mg_graph_drop(c);
         c->want_matfree = kind;
         c->assembled = false, c->M_dirty = true;  // diagonal / matrix values of the other form have to be rebuilt
@@ -2254,6 +2316,16 @@ int plfx_short_info(plfx_ctx *c, int64_t *dinv_deferred, int64_t *dinv_formed_la
     if (dinv_formed_late) *dinv_formed_late = c->n_dinv_late;
     if (d_kept) *d_kept = c->n_d_kept;
     if (spec_merged) *spec_merged = 0;   // (no merged launch behind a sweep's flags in this library: DESIGN 38 C)
+    return PLFX_OK;
+}
+
+int plfx_snap_info(plfx_ctx *c, int64_t *direct_sweeps, int64_t *direct_acknowledged, int64_t *setup_formed_late, int64_t *live_restored)
+{
+    if (!c) return PLFX_ERR_STATE;
+    if (direct_sweeps) *direct_sweeps = c->n_direct_sweeps;
+    if (direct_acknowledged) *direct_acknowledged = c->n_direct_ack;
+    if (setup_formed_late) *setup_formed_late = c->n_setup_late;
+    if (live_restored) *live_restored = c->n_live_restored;
     return PLFX_OK;
 }
 
@@ -2397,6 +2469,7 @@ int plfx_set_precond(plfx_ctx *c, int kind, double omega, int nu)
                         "smoother chosen before plfx_set_strip");
         return PLFX_OK;
     }
+    if (int rcs = snap_settle(c)) return rcs;
     c->precond = kind;
     if (omega > 0.) c->mg_omega = omega;
     if (nu > 0) c->mg_nu = nu;
@@ -2487,8 +2560,10 @@ int plfx_assemble(plfx_ctx *c)
 {
     if (!c || !c->dval) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
     // (the set-up pass may have run already, behind the flags of the sweep that changed the tangents: sweep_once)
-    const bool setup_done = c->spec_setup && c->spec_was_clean && c->spec_h0 != 0 && matfree(c);
-    c->spec_setup = c->spec_kdu = false;
+    // (... or have been left out, where that sweep wrote its generators into the snapshot itself: DESIGN 43)
+    const bool direct = c->direct_done && matfree(c) && c->M_dirty;
+    const bool setup_done = (c->spec_setup && c->spec_was_clean && c->spec_h0 != 0 && matfree(c)) || direct;
+    c->spec_setup = c->spec_kdu = c->direct_done = false;
     if (c->reuse && c->assembled && !c->M_dirty) {  // no tangent changed since the last assembly: K is what it was
         c->n_reuse_assemble++;
         return PLFX_OK;
@@ -2498,12 +2573,18 @@ int plfx_assemble(plfx_ctx *c)
     if (matfree(c)) {  // operators are applied from the generators: only the diagonal is formed
         KOp live = c->op;
         live.M = c->Mel;  // diagonal + snapshot of the generators (+ generators of multigrid level 1) in one pass
-        if (setup_done)
+        if (direct) {   // diag and the generators of level 1 are owed to their first reader (ensure_setup)
+            c->n_direct_ack++;
+            c->setup_owed = true;
+        } else if (setup_done)
             c->n_spec_setup++;
-        else
+        else {
+            if (int rc = ensure_live_M(c)) return rc;
             LAUNCH_SETUP(0, live, (double2 *)c->diag,
                                c->Mop, (mg_active(c) && level_plain(c->mg[0])) ? c->mg[1].Mel : (double *)nullptr, (const double2 *)nullptr, 0, 0,
                                (double2 *)nullptr);
+            c->setup_owed = false;   // (superseded)
+        }
         c->dinv_ok = false;   // (c->diag rewritten, here or by the pass behind the sweep's flags)
         c->val_valid = false;
     } else {
@@ -2700,11 +2781,13 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
             c->n_dinv_refreshed++;   // (rows_only = kept + refreshed as before; n_dinv_deferred says how many of these were left open)
             c->n_dinv_deferred++;
         } else {
+            if ((rc = ensure_setup(c))) return rc;
             hipLaunchKernelGGL(k_dinv, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->diag, c->is_presc, c->dinv);
             c->n_dinv_refreshed++;
             c->dinv_late = false;
         }
     } else {
+        if ((rc = ensure_setup(c))) return rc;
         hipLaunchKernelGGL(k_bc_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd,
                            fext ? c->fext : nullptr, c->kw, c->diag, c->is_presc, c->rhs, c->dinv);
         c->rhs_rows_ok = !fext;

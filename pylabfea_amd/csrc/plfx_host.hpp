@@ -239,6 +239,18 @@ struct plfx_ctx {
     // plfx_load_step, single GPU: the set-up pass of the next stiffness iteration and the K du of the end of the load step are
     // enqueued behind k_sweep_flags with device-side predicates, before the host has read the flags
     bool spec_arm = false, spec_setup = false, spec_kdu = false, spec_was_clean = false;
+    // Rewritten generators straight into the operator's snapshot (PLFX_DIRECT_SNAP at plfx_create, a bit mask: 1 = A,
+    // 2 = B, which needs A; default 3, PLFX_REUSE=0: 0).  INVARIANT while M_dirty is clear: Mop[e] == Mel[e] for every element (in
+    // the other layout), except that with live_owed Mel is older than Mop.
+    // A. an armed plane sweep that finds the invariant intact stores a rewritten generator to Mop as well (sweep_once: direct)
+    //    and no set-up pass follows it.  direct_done: that sweep reported a changed tangent and the next plfx_assemble has
+    //    nothing to launch.  setup_owed: diag and mg[1].Mel are older than Mop -- ensure_setup, in front of their readers and
+    //    of every other writer of Mel, launches the pass the sweep left out.
+    // B. the direct sweep does not write Mel.  live_owed: Mel is older than Mop -- ensure_live_M copies it back in front of every
+    //    reader or partial writer of Mel.
+    int direct_snap = 3;
+    bool direct_done = false, setup_owed = false, live_owed = false;
+    long long n_direct_sweeps = 0, n_direct_ack = 0, n_setup_late = 0, n_live_restored = 0;   // plfx_snap_info
     // Stores nobody reads (PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: off).  dead_arm: plfx_load_step says of
     // the sweep it is about to launch that another one follows whenever a tangent changes -- the elements whose tangent changes
     // may leave res_sig, res_depl and fyn unwritten.  res_partial: the last sweep did leave some unwritten (it ran armed and
@@ -622,6 +634,9 @@ void launch_jacobi_z(plfx_ctx *c);                      // k_jacobi_z: z = D^-1 
 void launch_mbox_post(plfx_ctx *c, const double *src, int n, double *dst, CgMbox *mb, unsigned long long seq);   // k_mbox_post
 void launch_kdu_uf(plfx_ctx *c, CgScalars *spec);       // k_spmv MODE 3: u += du, f += K du (spec: device-side predicate or null)
 void launch_spec_setup(plfx_ctx *c);                    // the set-up pass a sweep enqueues behind its flags (k_grid_setup)
+int ensure_live_M(plfx_ctx *c);                         // k_restore_M if the live generators are owed
+int ensure_setup(plfx_ctx *c);                          // the set-up pass a direct sweep left out, if it is owed
+int before_M_write(plfx_ctx *c);                        // both, in front of whatever writes part of the live generators
 
 // plfx_step.hip
 int ensure_eps(plfx_ctx *c);

@@ -948,7 +948,8 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
                                                int oform, const double *ofac, int omax,
                                                double *Mel, int mel_stride, double *res_sig,
                                                double *res_depl, double *fyn, int32_t *max_steps, int nit,
-                                               int &changed, int &nconv, double kh = -1., int dead_ok = 0)
+                                               int &changed, int &nconv, double kh = -1., int dead_ok = 0,
+                                               double *snap = nullptr, size_t snap_nel = 0, size_t snap_e = 0)
 {
     // dead_ok (k_sweep_light inside plfx_load_step): a sweep that changes any tangent is certainly followed by another
     // one, which rewrites res_sig, res_depl and fyn of every plastic element before anything reads them -- an element whose
@@ -1014,8 +1015,18 @@ __device__ __forceinline__ void sweep_epilogue(const ClassDev &c, const MatDev &
         }
         double M[6];
         tangent_to_M(Dnew, c.kappa, M);
+        if (!AHEAD || Mel) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) Mel[(size_t)k * mel_stride + e] = M[k];
+            for (int k = 0; k < 6; k++) Mel[(size_t)k * mel_stride + e] = M[k];
+        }
+        // AHEAD with snap: the generators go where the operator reads them, element snap_e of snap_nel in pair
+        // layout (gen_index) -- the snapshot, taken where it can differ.  Mel null: the live array is owed (ensure_live_M)
+        if (AHEAD && snap) {
+            double2 *S2 = reinterpret_cast<double2 *>(snap);
+            S2[snap_e] = make_double2(M[0], M[1]);
+            S2[snap_nel + snap_e] = make_double2(M[2], M[3]);
+            S2[2 * snap_nel + snap_e] = make_double2(M[4], M[5]);
+        }
         changed += 1;  // counts the elements whose tangent (and generator) this thread rewrote
     }
     if (ns > omax) max_steps[e] = ns;  // stat_nlin['max_steps'] (model.py:1356)
@@ -1301,7 +1312,8 @@ k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *_
                     const int32_t *__restrict__ cls, const double2 *__restrict__ du2,
                     const double *__restrict__ sig, const double *__restrict__ epl, TanStore ts,
                     double *Mel, int mel_stride, double *res_sig, double *res_depl, double *fyn,
-                    int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, unsigned skip_mask, int dead_ok)
+                    int32_t *max_steps, int nit, int *flags, int *bflags, int32_t *list, int first_kind, unsigned skip_mask, int dead_ok,
+                    double *snap /* the operator's snapshot (all mel_stride elements, pair layout), or null; then Mel may be null: DESIGN 43 */)
 {
     __shared__ SweepTables tb;
     stage_tables(tb, gmat, nmat, gcls, ncls);
@@ -1369,7 +1381,8 @@ k_sweep_light_plane(const MatDev *__restrict__ gmat, int nmat, const ClassDev *_
                     // (omax = 0 and not max_steps[e]: with ns = 0 the store `if (ns > omax)` never happens -- max_steps is zero-filled
                     // by plfx_state_reset, a running maximum, and not settable from outside -- so the value is not loaded)
                     sweep_epilogue<true, true, true>(c, m, e, nel, s, ep, depl, st, Ct, fy, 0, ts, in.form, in.fac, 0, Mel, mel_stride,
-                                                     res_sig, res_depl, fyn, max_steps, nit, changed, nconv, -1., dead_ok);
+                                                     res_sig, res_depl, fyn, max_steps, nit, changed, nconv, -1., dead_ok,
+                                                     snap, (size_t)mel_stride, (size_t)e + e_off);
             }
         }
         const unsigned long long mask = __ballot(heavy);
@@ -1776,6 +1789,22 @@ __host__ __device__ __forceinline__ size_t gen_index(bool pair, int c, size_t ne
 {
     return pair ? ((size_t)(c >> 1) * nel + e) * 2 + (c & 1) : (size_t)c * nel + e;
 }
+
+#ifdef PLFX_UNIT_OPERATOR
+// The live SoA array from the snapshot (pair layout), all nel elements: a copy, no arithmetic (ensure_live_M)
+__global__ void __launch_bounds__(BLOCK)
+k_restore_M(size_t nel, const double2 *__restrict__ snap, double *__restrict__ Mel)
+{
+    for (size_t e = (size_t)blockIdx.x * BLOCK + threadIdx.x; e < nel; e += (size_t)gridDim.x * BLOCK) {
+#pragma unroll
+        for (int p = 0; p < 3; p++) {
+            const double2 v = snap[(size_t)p * nel + e];
+            Mel[(size_t)(2 * p) * nel + e] = v.x;
+            Mel[(size_t)(2 * p + 1) * nel + e] = v.y;
+        }
+    }
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Block-ELL pattern of the reference's STRUCTURED grid in closed form (what build_pattern() derives from the connectivity

@@ -190,6 +190,7 @@ int plfx_state_reset(plfx_ctx *c)
     c->plane_cols = c->plane_off_by == PLFX_PLANE_ON;
     if (c->plane_cols) HIPCHK(c, hipMemsetAsync(c->elfac + 4 * ne, 0, 16 * ne, c->stream));
     c->assembled = false, c->M_dirty = true;
+    c->direct_done = c->setup_owed = c->live_owed = false;   // (every generator was rewritten above; the next assembly is a full one)
     c->x_is_du = false;
     c->rhs_rows_ok = c->dinv_ok = false;   // (a new history starts with one full k_bc_finish)
     // (... which writes dinv for every DOF and clears dinv_late there: until then a late dinv stays owed, bc_set still stands)
@@ -340,6 +341,7 @@ int plfx_state_set(plfx_ctx *c, int which, const double *in)
     HIPCHK(c, hipMemcpyAsync(p, t.data(), 8 * comps * n, hipMemcpyHostToDevice, c->stream));
     if (which == 5) {  // every element's tangent is now held in full form
         c->M_dirty = true;
+        if (int rcw = before_M_write(c)) return rcw;
         HIPCHK(c, hipMemsetAsync(c->eltag, TAN_FULL, n, c->stream));
         hipLaunchKernelGGL(k_refresh_M, dim3((c->nel + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream,
                            c->dmat, c->dcls, c->nel, c->dcls_id, tan_store(c), c->Mel + c->e0, c->nel_total);
@@ -628,6 +630,20 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     const int dead = (c->dead_arm && c->dead_stores && !comm_active(c) && !c->strip.on && !wh_seq && (c->has_analytic || c->has_princ)) ? 1 : 0;
     c->dead_arm = false;
     c->res_partial = dead != 0;   // (until the final flags are known below; an error return on the way leaves it standing)
+    // what follows the flags can be enqueued behind them (plfx_load_step arms it; see below)
+    const bool mb_flags = !comm_active(c) && c->mbox && c->mb_cap >= 2;
+    const bool skip_heavy = mb_flags && !c->strip.on && c->last_heavy == 0;
+    const bool spec = c->spec_arm && !comm_active(c) && c->mbox && c->mb_cap >= 2 && matfree(c) && !c->strip.on && c->assembled;
+    c->spec_arm = false;
+    // Direct sweep: an assembly follows this sweep whenever it changes a tangent, the snapshot equals the live array,
+    // and the plane kernel alone writes generators (no corrector enqueued) -- it stores them into the snapshot itself and the
+    // set-up pass behind the flags is left out.  Bit 2: into the snapshot alone.
+    const bool plane_only = plane_active(c) && c->has_analytic && !c->has_princ && !c->has_barlat && !c->has_svc && !c->has_svc3 &&
+                            !c->has_svcwh && !c->svc_row_all;
+    const bool direct = (c->direct_snap & 1) && spec && plane_only && skip_heavy && !c->M_dirty && !c->op.colr && !wh_seq && c->Mop;
+    const bool direct_only = direct && (c->direct_snap & 2);
+    if (!direct)
+        if (int rcw = before_M_write(c)) return rcw;
     EvPair *ev;
     tim_begin(c, 0, &ev);
 #define SWEEP_ARGS(lds) c->dmat, c->nmat, c->dcls, c->ncls, lds, c->nel, c->e0, c->dconn, c->dcls_id,          \
@@ -643,7 +659,14 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list
     if (c->has_analytic || (c->has_elastic && !c->has_princ && !c->has_svc && !c->has_svc3 && !c->has_barlat && !c->has_svcwh && !c->svc_cols_mask)) {
         if (plane_active(c)) {   // (the same timing family)
-            hipLaunchKernelGGL(k_sweep_light_plane, dim3(plane_sweep_grid(c)), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead);
+            if (direct)   // (SWEEP_ARGS with the live array left out or not)
+                hipLaunchKernelGGL(k_sweep_light_plane, dim3(plane_sweep_grid(c)), dim3(BLOCK), 0, c->stream, c->dmat, c->nmat, c->dcls,
+                                   c->ncls, 0, c->nel, c->e0, c->dconn, c->dcls_id, (const double2 *)c->du, c->sig, c->epl, tan_store(c),
+                                   direct_only ? (double *)nullptr : c->Mel + c->e0, c->nel_total, c->res_sig, c->res_depl, c->fyn,
+                                   c->max_steps, nit, c->flags, c->bflags, c->heavy_list, first, 0u, dead, c->Mop);
+            else
+                hipLaunchKernelGGL(k_sweep_light_plane, dim3(plane_sweep_grid(c)), dim3(BLOCK), 0, c->stream, SWEEP_ARGS(0), first, 0u, dead,
+                                   (double *)nullptr);
             c->n_plane_sweeps++;
         } else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sweep_light<1>), dim3(c->grid_el), dim3(BLOCK), 0, c->stream,
@@ -699,8 +722,6 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     // phase 2 reads the list length from the device; an empty list costs one empty launch per kind.  Single GPU with the mailbox:
     // after a sweep whose list was empty the launches are left out, k_sweep_flags reports a list that turned up after all, and
     // the launches follow then (one more round trip, in the first sweep that grows a list: DESIGN 22)
-    const bool mb_flags = !comm_active(c) && c->mbox && c->mb_cap >= 2;
-    const bool skip_heavy = mb_flags && !c->strip.on && c->last_heavy == 0;
     auto launch_phase2 = [&]() {
         tim_begin(c, 6, &ev);  // family 6: the compacted 50-sub-step corrector
         if (c->has_analytic)
@@ -740,8 +761,6 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
     else
         launch_phase2();
     int h[4];
-    const bool spec = c->spec_arm && !comm_active(c) && c->mbox && c->mb_cap >= 2 && matfree(c) && !c->strip.on && c->assembled;
-    c->spec_arm = false;
     if (mb_flags) {   // single GPU: the flags kernel posts its results itself
         const unsigned long long seq = ++c->mbox_seq;
         hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4,
@@ -750,13 +769,16 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         if (spec) {
             // what the host would enqueue after reading the flags, enqueued now (the round trip overlaps it): the set-up pass of
             // plfx_assemble if a tangent changed, else -- if every element converged as well -- the K du of plfx_finish_step
-            launch_spec_setup(c);
+            if (!direct) launch_spec_setup(c);
             // (u += du and f += K du in the same pass, MODE 3: the predicate is exactly "plfx_finish_step comes next")
             launch_kdu_uf(c, c->spec_sc);
             c->spec_was_clean = !c->M_dirty;
-            c->spec_setup = c->spec_kdu = true;
+            c->spec_setup = !direct;
+            c->spec_kdu = true;
+            if (direct) c->n_direct_sweeps++;
         }
         HIPCHK(c, hipGetLastError());
+        bool recovered = false;
         const int rcw = mbox_wait(c, seq);
         if (rcw) return rcw;
         memcpy(h, c->mb_buf, sizeof(h));
@@ -765,6 +787,11 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
             // do nothing; the corrector launches and an unarmed flags kernel follow, and their results are the sweep's
             c->n_heavy_recovered++;
             c->spec_setup = c->spec_kdu = false;
+            recovered = true;
+            if (direct_only) {   // the corrector writes part of the live array: what this sweep left in the snapshot alone first
+                c->live_owed = true;
+                if (int rcl = ensure_live_M(c)) return rcl;
+            }
             launch_phase2();
             const unsigned long long seq2 = ++c->mbox_seq;
             hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4,
@@ -779,6 +806,11 @@ static int sweep_once(plfx_ctx *c, int nit, int *changed, int *conv, bool wh_seq
         // the speculative set-up pass rewrote c->diag exactly if the flags kernel it sits behind reported a changed tangent
         // (its predicate flags[8] is "h[0] == 0" of that kernel; after a recovery it was told to skip, and plfx_assemble launches)
         if (spec && h[0]) c->dinv_ok = false;
+        // a direct sweep that changed tangents and needed no corrector: the snapshot is taken, plfx_assemble has nothing to launch
+        if (direct && h[0] && !recovered) {
+            c->direct_done = true;
+            if (direct_only) c->live_owed = true;
+        }
     } else {
         hipLaunchKernelGGL(k_sweep_flags, dim3(1), dim3(BLOCK), 0, c->stream, c->bflags, c->flags, c->flags + 4);
         HIPCHK(c, hipGetLastError());
@@ -829,6 +861,7 @@ static int sweep_wh_sequential(plfx_ctx *c, int nit, int *changed, int *conv)
             (rc = dalloc(c, &c->wh_snap_ms, ne)))
             return rc;
     }
+    if ((rc = before_M_write(c))) return rc;   // (the snapshot copies read the live generators)
     HIPCHK(c, hipMemcpyAsync(c->wh_snap_el, c->tan_buf, tan_words(ne) * 8, hipMemcpyDeviceToDevice, c->stream));  // tags and factors too
     HIPCHK(c, hipMemcpyAsync(c->wh_snap_M, c->Mel, (size_t)6 * c->nel_total * 8, hipMemcpyDeviceToDevice, c->stream));
     // max_steps is a running maximum (sweep_epilogue): passes that ran with entry moduli the chain does not confirm must not leave their counts
