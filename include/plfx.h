@@ -407,6 +407,17 @@ int plfx_short_info(plfx_ctx *ctx, int64_t *dinv_deferred, int64_t *dinv_formed_
  * launched after all in front of a reader of the fine diagonal or of the level-1 generators (setup_formed_late; the rest were
  * superseded unread); copies of the snapshot back into the live array (live_restored).  Results are the same bit for bit. */
 int plfx_snap_info(plfx_ctx *ctx, int64_t *direct_sweeps, int64_t *direct_acknowledged, int64_t *setup_formed_late, int64_t *live_restored);
+/* Node code (one GPU, matrix-free grid of one column width, no strip, no communicator; PLFX_NODE_CODE at
+ * plfx_create is a bit mask -- 1: the kernels of an interpolated start read the Dirichlet set from a byte per node instead of
+ * the doubles of dinv / is_presc; 2 (needs 1): the two start kernels load rhs on the rows next to prescribed nodes alone while
+ * it is zero elsewhere (no force vector) -- default 1, 0 or PLFX_REUSE=0: the launches as they were, the last three counters
+ * stay 0).  Codes formed (built: one per apply_bc with another Dirichlet set); k_cg_start_test / k_cg_start_pred launches that
+ * read the code (start_launches) and those among them with the sparse rhs (b_sparse_launches); k_pred_dots, k_pred_try,
+ * k_pred_finish and k_compose_du launches that read it (vector_launches).  Results are the same bit for bit either way. */
+int plfx_code_info(plfx_ctx *ctx, int64_t *built, int64_t *start_launches, int64_t *b_sparse_launches, int64_t *vector_launches);
+/* The node code of the last apply_bc, a byte per node -- bit 0 / 1: the x / y DOF is prescribed, bit 2: a row of K next to a
+ * prescribed node (rhs can be non-zero there without a force vector).  out: nnode bytes.  PLFX_ERR_STATE before the first apply_bc. */
+int plfx_code_get(plfx_ctx *ctx, uint8_t *out);
 /* Stores that nothing reads (one GPU, no strip; PLFX_DEAD_STORES=0 or PLFX_REUSE=0 at plfx_create: all
  * four stay 0).  Sweeps of plfx_load_step that were certain to be repeated if they changed a tangent, and in which the
  * elements whose tangent changed therefore left res_sig, res_depl and fyn to the next sweep (armed_sweeps; the tangents they

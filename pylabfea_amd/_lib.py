@@ -66,7 +66,7 @@ SYMBOLS = [
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info', 'plfx_load_path', 'plfx_load_path_info',
-    'plfx_dead_store_info', 'plfx_plane_info', 'plfx_short_info', 'plfx_snap_info',
+    'plfx_dead_store_info', 'plfx_plane_info', 'plfx_short_info', 'plfx_snap_info', 'plfx_code_info', 'plfx_code_get',
     'plfx_set_svc_cols', 'plfx_mg_info',
     'plfx_set_svc_textures', 'plfx_set_element_textures', 'plfx_response_batch_tid', 'plfx_full_yf_batch_tid',
     'plfx_svc_textures_info',
@@ -859,6 +859,21 @@ class Context(object):
         a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
         self._chk(self.lib.plfx_snap_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
         return a.value, b.value, r.value, d.value
+
+    def code_info(self):
+        """(node codes formed, k_cg_start_test / k_cg_start_pred launches that read the code, those among them that loaded rhs
+        on the boundary rows alone, k_pred_dots / k_pred_try / k_pred_finish / k_compose_du launches that read it) since the
+        context was created; PLFX_NODE_CODE=0: the last three stay zero"""
+        a, b, r, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_code_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(d)))
+        return a.value, b.value, r.value, d.value
+
+    def code_get(self):
+        """the node code of the last apply_bc, uint8[nnode]: bit 0 / 1 the x / y DOF is prescribed, bit 2 the node is a row next
+        to a prescribed node"""
+        out = np.empty(self.ndof // 2, dtype=np.uint8)
+        self._chk(self.lib.plfx_code_get(self.h, _dp(out)))
+        return out
 
     def dead_store_info(self):
         """(sweeps of load steps whose changed elements left res_sig / res_depl / fyn to the next sweep, tangents rewritten in

@@ -459,6 +459,7 @@ void free_mesh(plfx_ctx *c)
     dfree(c->dinv);
     dfree(c->diag);
     dfree(c->is_presc);
+    dfree(c->ncode);
     dfree(c->dup);
     dfree(c->wv);
     dfree(c->fext);
@@ -508,7 +509,7 @@ void free_mesh(plfx_ctx *c)
     c->assembled = c->bc_set = false;
     c->M_dirty = true;
     c->x_is_du = false;
-    c->bc_valid = false;
+    c->bc_valid = c->code_ok = false;
     c->bc_idx.clear();
     c->plan.valid = false;
     dfree(c->fin_idx);
@@ -1392,6 +1393,8 @@ int plfx_create(int device, plfx_ctx **out)
     if (!c->reuse) c->plane_switch = false;
     if (const char *e12 = getenv("PLFX_SHORT_SOLVE")) c->short_solve = atoi(e12) & 3;
     if (!c->reuse) c->short_solve = 0;
+    if (const char *e14 = getenv("PLFX_NODE_CODE")) c->node_code = atoi(e14) & 3;
+    if (!(c->node_code & 1) || !c->reuse) c->node_code = 0;   // (the sparse b needs the mask)
     if (const char *e13 = getenv("PLFX_DIRECT_SNAP")) c->direct_snap = atoi(e13) & 3;
     if (!(c->direct_snap & 1) || !c->reuse) c->direct_snap = 0;   // (B needs A)
     if (const char *e9 = getenv("PLFX_PREDICT")) c->predict = atoi(e9) != 0;
@@ -1651,6 +1654,7 @@ static int set_mesh_impl(plfx_ctx *c, int nel, int nnode, const int32_t *conn, c
     ALLOC(c->dinv, nd);
     ALLOC(c->diag, nd);
     ALLOC(c->is_presc, nd);
+    ALLOC(c->ncode, ((size_t)nnode + 255) / 256 * 256);
     ALLOC(c->dup, nd);
     ALLOC(c->wv, nd);
     ALLOC(c->fext, nd);
@@ -2022,6 +2026,7 @@ int plfx_set_grid(plfx_ctx *c, int nx, int ny)
     }
     c->gx = nx;
     c->gy = ny;
+    c->code_ok = false;   // (built again with the next Dirichlet set)
     mg_graph_drop(c);
     for (auto &L : c->mg) {  // drop a previous hierarchy
         if (L.owned) {
@@ -2226,7 +2231,7 @@ int plfx_set_strip(plfx_ctx *c, int own_col0, int own_col1, int global_col0, int
     c->grid_nodes = MAXPART;
     c->assembled = false, c->M_dirty = true;
     c->bc_set = false;
-    c->bc_valid = false;
+    c->bc_valid = c->code_ok = false;
     c->rhs_rows_ok = c->dinv_ok = false;
     c->dinv_late = c->pred_d_kept = false;   // (a strip never defers: the full k_bc_finish of its first apply_bc writes dinv)
     c->x_is_du = false;
@@ -2273,7 +2278,7 @@ int plfx_set_operator(plfx_ctx *c, int kind)
         mg_graph_drop(c);
         c->want_matfree = kind;
         c->assembled = false, c->M_dirty = true;  // diagonal / matrix values of the other form have to be rebuilt
-        c->bc_set = false;
+        c->bc_set = c->code_ok = false;
     }
     return PLFX_OK;
 }
@@ -2316,6 +2321,26 @@ int plfx_short_info(plfx_ctx *c, int64_t *dinv_deferred, int64_t *dinv_formed_la
     if (dinv_formed_late) *dinv_formed_late = c->n_dinv_late;
     if (d_kept) *d_kept = c->n_d_kept;
     if (spec_merged) *spec_merged = 0;   // (no merged launch behind a sweep's flags in this library: DESIGN 38 C)
+    return PLFX_OK;
+}
+
+int plfx_code_info(plfx_ctx *c, int64_t *built, int64_t *start_launches, int64_t *b_sparse_launches, int64_t *vector_launches)
+{
+    if (!c) return PLFX_ERR_ARG;
+    if (built) *built = c->n_code_built;
+    if (start_launches) *start_launches = c->n_code_start;
+    if (b_sparse_launches) *b_sparse_launches = c->n_code_bsparse;
+    if (vector_launches) *vector_launches = c->n_code_vector;
+    return PLFX_OK;
+}
+
+int plfx_code_get(plfx_ctx *c, uint8_t *out)
+{
+    if (!c || !c->ncode) return c ? fail(c, PLFX_ERR_STATE, "set_mesh first") : PLFX_ERR_STATE;
+    if (!out) return fail(c, PLFX_ERR_ARG, "bad argument");
+    if (!c->code_ok) return fail(c, PLFX_ERR_STATE, "no node code: apply_bc first");
+    HIPCHK(c, hipMemcpyAsync(out, c->ncode, (size_t)c->nnode, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, stream_sync(c));
     return PLFX_OK;
 }
 
@@ -2667,6 +2692,7 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
     const bool same_set = c->bc_valid && (int)c->bc_idx.size() == n &&
                           (n == 0 || memcmp(c->bc_idx.data(), idx, (size_t)4 * n) == 0);
     if (!same_set) {
+        c->code_ok = false;
         c->x_is_du = false;  // another Dirichlet mask: x0 has to be rebuilt from du
         c->pred_d_kept = false;   // (and pred_d was masked with the old one)
         HIPCHK(c, hipMemsetAsync(c->is_presc, 0, 8 * nd, c->stream));
@@ -2703,7 +2729,15 @@ int apply_bc_impl(plfx_ctx *c, int n, const int32_t *idx, const double *du_presc
             if (!c->kw && (rc = dalloc(c, &c->kw, nd))) return rc;
             HIPCHK(c, hipMemsetAsync(c->kw, 0, 8 * nd, c->stream));
             c->rhs_rows_ok = false;   // another row list, kw rebuilt: rhs needs one full pass
-            HIPCHK(c, stream_sync(c));  // `rows` goes out of scope
+            // the node code of the same idx and the same mark: the mask as is_presc will hold it, the rows as bc_rows does
+            std::vector<uint8_t> code(((size_t)nn + 255) / 256 * 256, 0);
+            for (int i = 0; i < nn; i++)
+                if (mark[i]) code[i] = 4;
+            for (int k = 0; k < n; k++) code[idx[k] >> 1] |= (uint8_t)(1 << (idx[k] & 1));
+            HIPCHK(c, hipMemcpyAsync(c->ncode, code.data(), code.size(), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, stream_sync(c));  // `rows` and `code` go out of scope
+            c->code_ok = true;
+            c->n_code_built++;
         }
         c->bc_valid = true;
         c->rhs_rows_ok = c->dinv_ok = false;   // (another mask: dinv and the zeros of rhs belong to the old one)

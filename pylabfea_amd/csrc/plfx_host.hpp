@@ -224,6 +224,16 @@ struct plfx_ctx {
     int short_solve = 3;
     bool dinv_late = false, pred_d_kept = false;
     long long n_dinv_deferred = 0, n_dinv_late = 0, n_d_kept = 0;   // plfx_short_info
+    // Node code (PLFX_NODE_CODE at plfx_create, a bit mask: 1 = the Dirichlet set from the code, 2 = sparse b, which
+    // needs 1; default 1 -- the sparse b did not
+    // show against the mask alone, DESIGN 44 -- PLFX_REUSE=0: 0).  ncode: a byte per node (padded to a multiple of 256) -- bit 0 / 1: the x / y DOF is
+    // prescribed, bit 2: the node is in bc_rows.  code_ok: ncode, is_presc and bc_rows come from one bc_idx; set where apply_bc_impl
+    // forms the three, cleared wherever bc_valid or bc_set is.  The kernels of an interpolated start read it in place of the zero
+    // pattern of dinv / is_presc, and (bit 2, while rhs_rows_ok stands) in place of the zeros of rhs (node_code, plfx_solve.hip).
+    int node_code = 1;
+    uint8_t *ncode = nullptr;
+    bool code_ok = false;
+    long long n_code_built = 0, n_code_start = 0, n_code_bsparse = 0, n_code_vector = 0;   // plfx_code_info
     int last_heavy = -1;  // elements that needed the sub-divided corrector in the last sweep (-1: no sweep yet)
     long long n_heavy_skipped = 0, n_heavy_recovered = 0;   // sweeps that left the corrector launches out / had to add them after all
     bool x_is_du = false;  // c->x still holds the last solution on the free DOFs (0 on the prescribed ones) = the warm start

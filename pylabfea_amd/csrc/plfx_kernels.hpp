@@ -2767,22 +2767,36 @@ k_cg_update(int nnode, const double2 *__restrict__ p, const double2 *__restrict_
 // Start of a PCG solve in one pass: q = K x0 (warm start), r = mask (b - q), z = dinv r and the partial sums of r.z,
 // r.r, b.b -- k_spmv<0> + k_cg_init without the round trip of q through memory.
 // TEST_ONLY (k_cg_start_test): the partial sums of r.r and b.b alone -- no r, no z, no r.z.
-template <int GRID, bool TEST_ONLY>
+// CODED (TEST_ONLY alone): the Dirichlet set comes from the node code -- bit 0 / 1: the x / y DOF is prescribed -- and
+// dinv is not read; b_sparse != 0: b is +0.0 on every node without bit 2 (plfx_ctx::rhs_rows_ok) and is loaded on the others
+// alone, the literal standing in for the zero it would have loaded.  Every expression behind the loads is the one of the
+// plain form.
+template <int GRID, bool TEST_ONLY, bool CODED = false>
 __device__ __forceinline__ void
 cg_start_body(const KOp &op, int nnode, int warm, const double2 *__restrict__ x, const double2 *__restrict__ b,
               const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ z,
               double *__restrict__ part_rz_out, double *__restrict__ part_rr_out, double *__restrict__ part_bb_out,
-              int own_lo, int own_hi)
+              int own_lo, int own_hi, const uint8_t *__restrict__ code = nullptr, int b_sparse = 0)
 {
+    static_assert(!CODED || TEST_ONLY, "z = dinv r needs dinv's values");
     __shared__ double sh[BLOCK / 64];
     double a_rz = 0., a_rr = 0., a_bb = 0.;
     const int nb = gridDim.x;
     for (int t = xcd_tile(blockIdx.x, nb); t * BLOCK < nnode; t += nb) {
         const int i = t * BLOCK + threadIdx.x;
         if (i >= nnode) continue;
+        int m = 0;
+        if (CODED) m = code[i];
         double2 qi = make_double2(0., 0.);
         if (warm) qi = op_apply<GRID>(op, i, [&](int j) { return x[j]; });
-        const double2 bi = b[i], di = dinv[i];
+        double2 bi, di;
+        if (CODED) {
+            bi = (!b_sparse || (m & 4)) ? b[i] : make_double2(0., 0.);
+            di = make_double2((m & 1) == 0 ? 1. : 0., (m & 2) == 0 ? 1. : 0.);   // (tested against zero alone)
+        } else {
+            bi = b[i];
+            di = dinv[i];
+        }
         double2 ri, zi;
         ri.x = (di.x != 0.) ? bi.x - qi.x : 0.;
         ri.y = (di.y != 0.) ? bi.y - qi.y : 0.;
@@ -2826,9 +2840,13 @@ template <int GRID>
 __global__ void __launch_bounds__(BLOCK)
 k_cg_start_test(KOp op, int nnode, int warm, const double2 *__restrict__ x, const double2 *__restrict__ b,
                 const double2 *__restrict__ dinv, double *__restrict__ part_rr_out, double *__restrict__ part_bb_out,
-                int own_lo, int own_hi)
+                int own_lo, int own_hi, const uint8_t *__restrict__ code = nullptr, int b_sparse = 0)
 {
-    cg_start_body<GRID, true>(op, nnode, warm, x, b, dinv, nullptr, nullptr, nullptr, part_rr_out, part_bb_out, own_lo, own_hi);
+    if (GRID == 1 && code)   // (the host passes a code to the instantiation of cells all alike only)
+        cg_start_body<GRID, true, true>(op, nnode, warm, x, b, dinv, nullptr, nullptr, nullptr, part_rr_out, part_bb_out, own_lo, own_hi,
+                                        code, b_sparse);
+    else
+        cg_start_body<GRID, true>(op, nnode, warm, x, b, dinv, nullptr, nullptr, nullptr, part_rr_out, part_bb_out, own_lo, own_hi);
 }
 
 // k_cg_start of a warm-started multigrid-PCG solve that will try the interpolated start x + alpha d (plfx_solve):
@@ -2836,11 +2854,13 @@ k_cg_start_test(KOp op, int nnode, int warm, const double2 *__restrict__ x, cons
 // the d that k_pred_diff has just written).  No z and no r.z: the V-cycle that follows a failed test starts from a zero guess
 // and writes every entry of z, and its last smoothing launch (or k_dot_rz) writes the r.z partials.  One GPU, no strip: the
 // sums run over all nodes.
+// code != null: the Dirichlet set and the sparse b as in cg_start_body<.., CODED>.
 #ifdef PLFX_UNIT_SOLVE
-__global__ void __launch_bounds__(BLOCK)
-k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 *__restrict__ d, const double2 *__restrict__ b,
-                const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ kd,
-                double *__restrict__ part_rr_out, double *__restrict__ part_bb_out)
+template <bool CODED>
+__device__ __forceinline__ void
+cg_start_pred_body(const KOp &op, int nnode, const double2 *__restrict__ x, const double2 *__restrict__ d, const double2 *__restrict__ b,
+                   const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ kd,
+                   double *__restrict__ part_rr_out, double *__restrict__ part_bb_out, const uint8_t *__restrict__ code, int b_sparse)
 {
     __shared__ double sh[BLOCK / 64];
     double a_rr = 0., a_bb = 0.;
@@ -2848,6 +2868,8 @@ k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 
     for (int t = xcd_tile(blockIdx.x, nb); t * BLOCK < nnode; t += nb) {
         const int i = t * BLOCK + threadIdx.x;
         if (i >= nnode) continue;
+        int m = 0;
+        if (CODED) m = code[i];
         double2 qi, qd;
         op_apply2(
             op, i,
@@ -2856,7 +2878,14 @@ k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 
                 dj = d[j];
             },
             qi, qd);
-        const double2 bi = b[i], di = dinv[i];
+        double2 bi, di;
+        if (CODED) {
+            bi = (!b_sparse || (m & 4)) ? b[i] : make_double2(0., 0.);
+            di = make_double2((m & 1) == 0 ? 1. : 0., (m & 2) == 0 ? 1. : 0.);   // (tested against zero alone)
+        } else {
+            bi = b[i];
+            di = dinv[i];
+        }
         double2 ri;
         ri.x = (di.x != 0.) ? bi.x - qi.x : 0.;
         ri.y = (di.y != 0.) ? bi.y - qi.y : 0.;
@@ -2872,6 +2901,18 @@ k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 
         part_rr_out[blockIdx.x] = t2;
         part_bb_out[blockIdx.x] = t3;
     }
+}
+
+__global__ void __launch_bounds__(BLOCK)
+k_cg_start_pred(KOp op, int nnode, const double2 *__restrict__ x, const double2 *__restrict__ d, const double2 *__restrict__ b,
+                const double2 *__restrict__ dinv, double2 *__restrict__ r, double2 *__restrict__ kd,
+                double *__restrict__ part_rr_out, double *__restrict__ part_bb_out, const uint8_t *__restrict__ code = nullptr,
+                int b_sparse = 0)
+{
+    if (code)
+        cg_start_pred_body<true>(op, nnode, x, d, b, dinv, r, kd, part_rr_out, part_bb_out, code, b_sparse);
+    else
+        cg_start_pred_body<false>(op, nnode, x, d, b, dinv, r, kd, part_rr_out, part_bb_out, nullptr, 0);
 }
 
 // r = mask (b - q), z = dinv r, partial r.z, r.r   (initial residual; q = K x0)
@@ -3127,9 +3168,14 @@ k_dinv(size_t ndof, const double *__restrict__ diag, const double *__restrict__ 
 #ifdef PLFX_UNIT_SOLVE
 __global__ void __launch_bounds__(BLOCK)
 k_compose_du(size_t ndof, const double *__restrict__ x, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du,
-             const CgScalars *__restrict__ gate = nullptr)
+             const CgScalars *__restrict__ gate = nullptr, const uint8_t *__restrict__ code = nullptr)
 {
     if (gate && gate->done != 1) return;
+    if (code) {   // the Dirichlet set from the node code: bit (i & 1) of node i >> 1
+        for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK)
+            du[i] = ((code[i >> 1] >> (i & 1)) & 1) ? dup[i] : x[i];
+        return;
+    }
     for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK)
         du[i] = (is_presc[i] != 0.) ? dup[i] : x[i];
 }
@@ -3164,13 +3210,14 @@ k_pred_advance(size_t ndof, double *__restrict__ xprev, const double *__restrict
 // partials of (K d) . r and (K d) . (K d) over the free DOFs (r = P (b - K x)): the step alpha that minimises | r - alpha P K d |
 __global__ void __launch_bounds__(BLOCK)
 k_pred_dots(size_t dof_lo, size_t dof_hi /* owned DOFs (a strip: its owned node columns) */, const double *__restrict__ dinv,
-            const double *__restrict__ r, const double *__restrict__ kd, double *__restrict__ part, const CgScalars *__restrict__ sc)
+            const double *__restrict__ r, const double *__restrict__ kd, double *__restrict__ part, const CgScalars *__restrict__ sc,
+            const uint8_t *__restrict__ code = nullptr)
 {
     __shared__ double sh[BLOCK / 64];
     if (sc->done) return;
     double a0 = 0., a1 = 0.;
     for (size_t i = dof_lo + blockIdx.x * (size_t)BLOCK + threadIdx.x; i < dof_hi; i += (size_t)gridDim.x * BLOCK) {
-        if (dinv[i] == 0.) continue;
+        if (code ? ((code[i >> 1] >> (i & 1)) & 1) != 0 : dinv[i] == 0.) continue;
         const double v = kd[i];
         a0 = fma(v, r[i], a0);
         a1 = fma(v, v, a1);
@@ -3187,7 +3234,8 @@ k_pred_dots(size_t dof_lo, size_t dof_hi /* owned DOFs (a strip: its owned node 
 // interpolated start is taken only when it FINISHES the solve; a solve that iterates starts from x, bit for bit the plain warm start.)
 __global__ void __launch_bounds__(BLOCK)
 k_pred_try(int nnode, CgScalars *__restrict__ sc, const double *__restrict__ part_dots, int gp, const double2 *__restrict__ r,
-           const double2 *__restrict__ kd, const double2 *__restrict__ dinv, double *__restrict__ part_rr_out, int own_lo, int own_hi)
+           const double2 *__restrict__ kd, const double2 *__restrict__ dinv, double *__restrict__ part_rr_out, int own_lo, int own_hi,
+           const uint8_t *__restrict__ code = nullptr)
 {
     __shared__ double sh[BLOCK / 64];
     if (sc->done) return;
@@ -3207,9 +3255,17 @@ k_pred_try(int nnode, CgScalars *__restrict__ sc, const double *__restrict__ par
     double a_rr = 0.;
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < nnode; i += gridDim.x * BLOCK) {
         if (i < own_lo || i >= own_hi) continue;
-        const double2 ki = kd[i], dv = dinv[i], ri = r[i];
-        const double rx = (dv.x != 0.) ? fma(-alpha, ki.x, ri.x) : 0.;
-        const double ry = (dv.y != 0.) ? fma(-alpha, ki.y, ri.y) : 0.;
+        const double2 ki = kd[i], ri = r[i];
+        bool fx, fy;   // free DOFs: from the node code where there is one
+        if (code) {
+            const int m = code[i];
+            fx = (m & 1) == 0, fy = (m & 2) == 0;
+        } else {
+            const double2 dv = dinv[i];
+            fx = dv.x != 0., fy = dv.y != 0.;
+        }
+        const double rx = fx ? fma(-alpha, ki.x, ri.x) : 0.;
+        const double ry = fy ? fma(-alpha, ki.y, ri.y) : 0.;
         a_rr = fma(rx, rx, fma(ry, ry, a_rr));
     }
     const double t = block_sum(a_rr, sh);
@@ -3233,7 +3289,7 @@ k_pred_commit(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict_
 __global__ void __launch_bounds__(BLOCK)
 k_pred_finish(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict__ x, double *__restrict__ d,
               double *__restrict__ xprev, const double *__restrict__ dup, const double *__restrict__ is_presc, double *__restrict__ du,
-              int keep_d)
+              int keep_d, const uint8_t *__restrict__ code = nullptr)
 {
     // enqueued BEFORE the host has seen the test (its round trip overlaps this pass): does nothing unless the interpolated
     // start was accepted (k_cg_check marks that with iters = -2)
@@ -3242,12 +3298,12 @@ k_pred_finish(size_t ndof, const CgScalars *__restrict__ sc, double *__restrict_
     for (size_t i = blockIdx.x * (size_t)BLOCK + threadIdx.x; i < ndof; i += (size_t)gridDim.x * BLOCK) {
         const double di = d[i];
         const double xi = fma(alpha, di, x[i]);
-        const double mi = is_presc[i];
+        const bool presc = code ? ((code[i >> 1] >> (i & 1)) & 1) != 0 : is_presc[i] != 0.;
         x[i] = xi;
-        du[i] = (mi != 0.) ? dup[i] : xi;
+        du[i] = presc ? dup[i] : xi;
         const double xp = xprev[i] + di;
         xprev[i] = xp;
-        if (keep_d) d[i] = (mi == 0.) ? xi - xp : 0.;
+        if (keep_d) d[i] = presc ? 0. : xi - xp;
     }
 }
 #endif

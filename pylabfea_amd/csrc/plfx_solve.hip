@@ -330,6 +330,16 @@ struct SolveRun {
 // PLFX_WAIT_FIRST=0: a solve never waits for its first test before it enqueues the interpolated start (always speculate, as before DESIGN 24)
 bool wait_first_on() { static const bool on = !(getenv("PLFX_WAIT_FIRST") && atoi(getenv("PLFX_WAIT_FIRST")) == 0); return on; }
 
+// The node code for the kernels of an interpolated start, or null: they read dinv / is_presc as ever.  One GPU, no
+// strip, no communicator, the matrix-free operator of cells all alike, and a code formed with the Dirichlet set in force.
+const uint8_t *node_code(plfx_ctx *c)
+{
+    return ((c->node_code & 1) && c->code_ok && !c->sharded && !c->strip.on && !comm_active(c) && matfree(c) && !c->op.colr) ? c->ncode : nullptr;
+}
+// ... and whether a start kernel given that code may take rhs as +0.0 off bc_rows: asked at the launch, where rhs_rows_ok says
+// that the last full k_bc_finish ran without a force vector and only k_spmv_rows has written rhs since
+int code_b_sparse(plfx_ctx *c, const uint8_t *code) { return (code && (c->node_code & 2) && c->rhs_rows_ok) ? 1 : 0; }
+
 bool solve_debug_on() { static const bool on = getenv("PLFX_SOLVE_DEBUG") && atoi(getenv("PLFX_SOLVE_DEBUG")) != 0; return on; }
 
 // z = (the rest of the V-cycle)(r) and the partials of r.z in `slot`: written by the last post-smoothing launch of the cycle
@@ -368,11 +378,15 @@ void launch_direction(plfx_ctx *c, const SolveRun &s, int it)
 }
 
 // du = x on the free DOFs, the prescribed values elsewhere (strip: x is valid on owned + 2 columns: complete the halo first)
-int compose_du(plfx_ctx *c)
+// (coded: the Dirichlet set from the node code where there is one -- the end of a PCG solve; GMRES and the Jacobi fall-back read is_presc)
+int compose_du(plfx_ctx *c, bool coded = false)
 {
     int rc;
     if (c->strip.on && (rc = halo_refresh(c, c->x))) return rc;
-    hipLaunchKernelGGL(k_compose_du, dim3(grid_for(c->ndof)), dim3(BLOCK), 0, c->stream, c->ndof, c->x, c->dup, c->is_presc, c->du);
+    const uint8_t *code = coded ? node_code(c) : nullptr;
+    hipLaunchKernelGGL(k_compose_du, dim3(grid_for(c->ndof)), dim3(BLOCK), 0, c->stream, c->ndof, c->x, c->dup, c->is_presc, c->du,
+                       (const CgScalars *)nullptr, code);
+    if (code) c->n_code_vector++;
     HIPCHK(c, hipGetLastError());
     return 0;
 }
@@ -438,17 +452,24 @@ int solve_start(plfx_ctx *c, SolveRun &s, double rtol, int warm, int site)
         else
             hipLaunchKernelGGL(k_pred_diff, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->pred_x, c->dinv, c->pred_d,
                                (const CgScalars *)nullptr);
+        const uint8_t *code = node_code(c);
+        const int b_sparse = code_b_sparse(c, code);
         hipLaunchKernelGGL(k_cg_start_pred, dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, (const double2 *)c->x, (const double2 *)c->pred_d,
-                           (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], s.P_rr[1], s.P_bb);
+                           (const double2 *)c->rhs, (const double2 *)c->dinv, (double2 *)c->r, (double2 *)c->p[0], s.P_rr[1], s.P_bb,
+                           code, b_sparse);
+        if (code) c->n_code_start++, c->n_code_bsparse += b_sparse;
     } else if (c->test_starts && s.mg && wait_first_on() && s.pred_active && site >= 0 && c->first_test_hint[site] && !c->strip.on &&
                !comm_active(c) && matfree(c)) {
         // solve_first_test will wait for the first test before it enqueues anything that reads r or z, and expects it to pass:
         // the sums of that test alone.  If it fails, k_cg_start follows there.
+        const uint8_t *code = node_code(c);   // (null with per-column widths)
+        const int b_sparse = code_b_sparse(c, code);
 #define TEST_START(G)                                                                                                          \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cg_start_test<G>), dim3(gn), dim3(BLOCK), 0, c->stream, c->op, nn, 1, (const double2 *)c->x, \
-                       (const double2 *)c->rhs, (const double2 *)c->dinv, s.P_rr[1], s.P_bb, s.olo, s.ohi)
+                       (const double2 *)c->rhs, (const double2 *)c->dinv, s.P_rr[1], s.P_bb, s.olo, s.ohi, code, b_sparse)
         if (c->op.colr) TEST_START(2); else TEST_START(1);   // (the matrix-free instantiations, as LAUNCH_OP1 picks them)
 #undef TEST_START
+        if (code) c->n_code_start++, c->n_code_bsparse += b_sparse;
         s.test_only = true;
         c->n_test_starts++;
     } else {   // r = P(b - K x0), z = Minv r; partials -> slot 1 ("iteration -1"); one pass (no q round trip)
@@ -483,8 +504,10 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
         // du of a passed test is composed under the round trip: gated on the flag the test just wrote, a no-op otherwise
         const bool early = c->bc_rows_on && c->reuse && !comm_active(c);
         if (early) {
+            const uint8_t *code = node_code(c);
             hipLaunchKernelGGL(k_compose_du, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, c->x, c->dup, c->is_presc, c->du,
-                               (const CgScalars *)c->sc);
+                               (const CgScalars *)c->sc, code);
+            if (code) c->n_code_vector++;
             HIPCHK(c, hipGetLastError());
         }
         if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
@@ -520,19 +543,23 @@ int solve_first_test(plfx_ctx *c, SolveRun &s, double rtol, int site)
             launch_spmv_plain(c, c->pred_d, c->p[0], c->sc);
         }
         const int gp = MAXPART;   // (one size on every rank: the all-reduce of the partial sums pairs up)
+        const uint8_t *code = node_code(c);
         hipLaunchKernelGGL(k_pred_dots, dim3(gp), dim3(BLOCK), 0, c->stream, (size_t)2 * olo, (size_t)2 * ohi, c->dinv, c->r, c->p[0],
-                           c->part, c->sc);
+                           c->part, c->sc, code);
         HIPCHK(c, hipGetLastError());
         if (c->strip.on && (rc = part_allreduce(c, c->part, (size_t)2 * MAXPART))) return rc;
         hipLaunchKernelGGL(k_pred_try, dim3(gn), dim3(BLOCK), 0, c->stream, nn, c->sc, (const double *)c->part, gp, (const double2 *)c->r,
-                           (const double2 *)c->p[0], (const double2 *)c->dinv, s.P_rr[0], olo, ohi);
+                           (const double2 *)c->p[0], (const double2 *)c->dinv, s.P_rr[0], olo, ohi, code);
+        if (code) c->n_code_vector += 2;
         HIPCHK(c, hipGetLastError());
         if (c->strip.on && (rc = part_allreduce(c, s.P_rr[0], gn))) return rc;
         seq = cg_check_post(c, s.P_rr[0], gn, -2);   // (iters = -2 marks "converged by the interpolated start")
-        if (!c->strip.on)   // x, du and the history in one pass -- behind the test, before the host has seen it (no-op unless accepted)
+        if (!c->strip.on) {   // x, du and the history in one pass -- behind the test, before the host has seen it (no-op unless accepted)
             hipLaunchKernelGGL(k_pred_finish, dim3(grid_for(nd)), dim3(BLOCK), 0, c->stream, nd, (const CgScalars *)c->sc, c->x,
                                c->pred_d, c->pred_x, (const double *)c->dup, (const double *)c->is_presc, c->du,
-                               ((c->short_solve & 2) && !comm_active(c)) ? 1 : 0);
+                               ((c->short_solve & 2) && !comm_active(c)) ? 1 : 0, code);
+            if (code) c->n_code_vector++;
+        }
         if ((rc = cg_check_wait(c, seq, &s.hs))) return rc;
         s.done = s.hs.done;
         if (s.done == 1 && s.hs.iters == -2) {   // it is the solution: commit x (r, z are not read again: the loop is skipped)
@@ -776,7 +803,7 @@ int solve_finish(plfx_ctx *c, SolveRun &s, double rtol, int *iters, double *relr
         HIPCHK(c, hipMemcpyAsync(&hs, c->sc, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, stream_sync(c));
     }
-    if (!s.pred_finished && !s.du_early && (rc = compose_du(c))) return rc;
+    if (!s.pred_finished && !s.du_early && (rc = compose_du(c, true))) return rc;
     c->x_is_du = true;  // x = du on the free DOFs, 0 on the prescribed ones: the next warm start
     const int its_done = (done && hs.iters >= 0) ? hs.iters : it;
     // history of the initial guess: the solution this solve started from becomes "the one before" -- only if this solve moved
