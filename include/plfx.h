@@ -223,6 +223,26 @@ int plfx_load_path(plfx_ctx *ctx, int mat, int n, int K, const double *dload, in
 /* launches of the load-path kernels by this context */
 int plfx_load_path_info(plfx_ctx *ctx, int64_t *launches);
 
+/* Load paths of a material with work-hardening features (PLFX_SVC_WH): plfx_load_path with the hardening
+ * modulus as state of each path.  khard0[n]: the modulus at the start of every path, finite and >= 0 -- the material record's
+ * khard is neither read nor written.  Every trial of a step enters with the step's modulus (as a plfx_response_batch_kh call
+ * with khard_in); on acceptance the modulus is the accepted trial's khard_out, unchanged where that trial evaluated no
+ * gradient.  khard[K][n]: the modulus after each completed step, NaN from ksteps[i] on.  Every other argument and output is
+ * plfx_load_path's (there is no tex_id: no texture field lies on this kind).
+ * form: 1 one thread per path (k_path_batch<7>): with strain control alone sig, epl, fy, nsteps, khard and ct have the bits of K
+ * plfx_response_batch_kh calls with epl += depl and the modulus carried in between; 2 one wave per path (k_path_wh_wave): the
+ * support-vector sums are split over 64 lanes, so results differ from form 1 by the order of those sums; 0 the faster
+ * form by n: form 2 at every n, by the measurement of DESIGN section 45.  One launch per call.
+ * PLFX_ERR_UNSUPPORTED, with nothing launched: a material of another kind, or one with an SVR flow rule attached.
+ * PLFX_ERR_ARG, with nothing launched: every case of plfx_load_path, a form other than 0, 1, 2, khard0 NULL, not finite or
+ * negative, K n 20 > INT32_MAX.  n = 0 or K = 0 is PLFX_OK with nothing launched, as in plfx_load_path. */
+int plfx_load_path_wh(plfx_ctx *ctx, int mat, int n, int K, const double *dload, int shared, const int32_t *control,
+                      const double *sig0, const double *epl0, const double *khard0, int form, int maxit, int newton, double stol,
+                      double eps_cap, double *sig, double *epl, double *deps, double *fy, double *khard, int32_t *nsteps,
+                      int32_t *newton_out, int32_t *ksteps, int32_t *status, double *ct);
+/* launches of k_path_batch<7> and of k_path_wh_wave by this context (plfx_load_path_info does not count them) */
+int plfx_load_path_wh_info(plfx_ctx *ctx, int64_t *launches_thread, int64_t *launches_wave);
+
 /* A committee of SVC yield functions on n shared unit stresses su[n*6] (query by committee): member k is
  * material mats[k] of the context, 1 <= nmem <= 16, duplicates allowed, each a 6-feature SVC on Voigt stresses (PLFX_SVC6,
  * dev_only or not), with its own stress scale scale[k] (finite, > 0).  One launch of k_committee_yf, whatever nmem is:

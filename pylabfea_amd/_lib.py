@@ -66,6 +66,7 @@ SYMBOLS = [
     'plfx_tex_svc_set', 'plfx_tex_svc_yf', 'plfx_tex_svc_yield_scale', 'plfx_tex_svc_info',
     'plfx_tex_svc_fgrad', 'plfx_tex_svc_full_yf', 'plfx_tex_svc_response', 'plfx_tex_svc_flow_info',
     'plfx_flow_curve', 'plfx_flow_info', 'plfx_load_path', 'plfx_load_path_info',
+    'plfx_load_path_wh', 'plfx_load_path_wh_info',
     'plfx_dead_store_info', 'plfx_plane_info', 'plfx_short_info', 'plfx_snap_info', 'plfx_code_info', 'plfx_code_get',
     'plfx_set_svc_cols', 'plfx_mg_info',
     'plfx_set_svc_textures', 'plfx_set_element_textures', 'plfx_response_batch_tid', 'plfx_full_yf_batch_tid',
@@ -437,6 +438,58 @@ class Context(object):
         nl = C.c_int64()
         self._chk(self.lib.plfx_load_path_info(self.h, C.byref(nl)))
         return dict(launches=int(nl.value))
+
+    PATH_WH_FORMS = {'auto': 0, 'thread': 1, 'wave': 2}
+
+    def load_path_wh(self, mat, dload, khard0, control=None, sig0=None, epl0=None, form='auto', maxit=50, newton=30, stol=1.,
+                     eps_cap=0.05, return_tangent=False):
+        """Load paths of N points of the work-hardening SVC material ``mat`` in one launch (plfx_load_path_wh): load_path with
+        the hardening modulus as state of each path.  khard0: scalar or (N,), the modulus at the start of the paths (it counts
+        towards N when it is an array); form 'thread' (a thread per path: the bits of the loop over response(khard_in=,
+        return_khard=True)), 'wave' (a wave per path) or 'auto' (by N).  The dict of load_path plus khard (K,N): the modulus
+        after each completed step, NaN past ksteps."""
+        if form not in self.PATH_WH_FORMS:
+            raise ValueError("load_path: form must be 'auto', 'thread' or 'wave'; got %r" % (form,))
+        dload = _f64(dload)
+        shared = dload.ndim == 2
+        if dload.ndim not in (2, 3) or dload.shape[-1] != 6:
+            raise ValueError('load_path: dload of shape (K, N, 6) or (K, 6) expected')
+        control = None if control is None else _i32(control).reshape(-1)
+        sig0 = None if sig0 is None else _f64(sig0).reshape(-1, 6)
+        epl0 = None if epl0 is None else _f64(epl0).reshape(-1, 6)
+        khard0 = _f64(khard0)
+        if khard0.ndim > 1:
+            raise ValueError('load_path: khard0 must be a scalar or (N,)')
+        given = [len(a) for a in (control, sig0, epl0, khard0 if khard0.ndim else None) if a is not None]
+        n = dload.shape[1] if not shared else (given[0] if given else 1)
+        if any(g != n for g in given):
+            raise ValueError('load_path: one row of control, sig0, epl0 and khard0 per point expected')
+        khard0 = np.ascontiguousarray(np.broadcast_to(khard0, (n,)))
+        K = len(dload)
+        # one block in the order of the library's device buffer, as in load_path
+        KN, nct = K * n, 36 * n if return_tangent else 0
+        buf = np.empty(20 * KN + nct + KN + n)
+        ints = buf[20 * KN + nct:].view(np.int32)
+        out = dict(sig=buf[:6 * KN].reshape(K, n, 6), epl=buf[6 * KN:12 * KN].reshape(K, n, 6),
+                   deps=buf[12 * KN:18 * KN].reshape(K, n, 6), fy=buf[18 * KN:19 * KN].reshape(K, n),
+                   khard=buf[19 * KN:20 * KN].reshape(K, n),
+                   nsteps=ints[:KN].reshape(K, n), newton=ints[KN:2 * KN].reshape(K, n), ksteps=ints[2 * KN:2 * KN + n],
+                   status=ints[2 * KN + n:])
+        ct = buf[20 * KN:20 * KN + nct].reshape(n, 6, 6) if return_tangent else None
+        self._chk(self.lib.plfx_load_path_wh(self.h, int(mat), n, K, _dp(dload), int(shared), _dp(control), _dp(sig0), _dp(epl0),
+                                             _dp(khard0), self.PATH_WH_FORMS[form], int(maxit), int(newton), C.c_double(stol),
+                                             C.c_double(eps_cap), _dp(out['sig']), _dp(out['epl']), _dp(out['deps']),
+                                             _dp(out['fy']), _dp(out['khard']), _dp(out['nsteps']), _dp(out['newton']),
+                                             _dp(out['ksteps']), _dp(out['status']), _dp(ct)))
+        if return_tangent:
+            out['ct'] = ct
+        return out
+
+    def load_path_wh_info(self):
+        """dict(launches_thread, launches_wave): launches of k_path_batch<7> and of k_path_wh_wave by this context"""
+        nt, nw = C.c_int64(), C.c_int64()
+        self._chk(self.lib.plfx_load_path_wh_info(self.h, C.byref(nt), C.byref(nw)))
+        return dict(launches_thread=int(nt.value), launches_wave=int(nw.value))
 
     def committee_yf(self, mats, scale, su, want_yf=True, want_mean=False, want_var=False, want_best=False):
         """A committee of 6-feature SVC materials on N shared unit stresses su (N,6) in one launch (plfx_committee_yf):

@@ -105,6 +105,7 @@ struct plfx_ctx {
     int64_t tex_fgrad_launches = 0, tex_full_launches = 0, tex_resp_launches = 0;   // the flow-rule calls
     int64_t flow_launches = 0;        // k_flow_curve / k_flow_curve_analytic launches of this context (plfx_flow_info)
     int64_t path_launches = 0;        // k_path_batch / k_path_row launches of this context (plfx_load_path_info)
+    int64_t path_wh_launches[2] = {0, 0};   // k_path_batch<7> / k_path_wh_wave launches (plfx_load_path_wh_info)
     // texture fields (plfx_set_svc_textures): coefficient rows of material k, a PLFX_SVC6_COLS record; coef and sabs are
     // owned device memory, ids is filled in per launch.  tex_ids / htex_ids: the row of every owned element (null / empty: row 0),
     // checked against the attached rows by tex_field_check before a sweep or calc_scf (tex_ids_ok: since the last change of either)

@@ -4,6 +4,9 @@
 //                    response_point, which is shared with the response kernels and not copied
 //   k_path_batch     one thread per path (KIND 1 | 2 | 5, the policies of k_response_batch)
 //   k_path_row       16 lanes per path on the row policy of k_response_row; lane 0 of a row stores
+// and, for the work-hardening SVC (kind 7), whose hardening modulus is state of the path:
+//   k_path_batch<7>  one thread per path on the policy and the tables of k_response_batch<7>: the yardstick form
+//   k_path_wh_wave   one wave per path on YfSvcWhT<1>, the policy of k_sweep_wh_wave; lane 0 of a wave stores
 #pragma once
 
 namespace plfx {
@@ -23,6 +26,24 @@ struct PathArgs {
     int32_t *nsteps, *newton_out;   // [K][n]
     int32_t *ksteps, *status;  // [n]
     double *ct;                // [n][36] or null
+};
+
+// ... and what the paths of a work-hardening SVC material take on top: the hardening modulus at the start of every path and
+// the one after every accepted step.  A type of its own: the kernels on PathArgs keep their arguments.
+struct PathArgsWh : PathArgs {
+    const double *khard0;      // [n]
+    double *khard;             // [K][n]
+};
+
+// Whether a path on policy YF carries the hardening modulus from step to step: the work-hardening policies do (their modulus
+// is a by-product of every gradient evaluation), no other has such state.
+template <class YF>
+struct PathCarriesKh {
+    static constexpr bool value = false;
+};
+template <int WAVE>
+struct PathCarriesKh<YfSvcWhT<WAVE>> {
+    static constexpr bool value = true;
 };
 
 // LDL^T of the masked tangent A = M Ct M + (I - M), M the 0/1 diagonal of the stress-controlled components `ctrl`, without
@@ -113,11 +134,17 @@ __device__ __noinline__ int path_trial(const MatDev &m, const YF &yf, const doub
 // is the same in its 16 lanes.  Loops: K steps, at most newton + 1 trials per step, the fixed counts of the solve.
 // Contraction is off in this function: epl + depl is one rounded add of the rounded depl, as NumPy forms it between two
 // response_batch calls, and no product formed here is fused into an addition of response_point.
-template <bool OUTLINE, class YF>
-__device__ __forceinline__ void path_point(const MatDev &m, const YF &yf, bool elastic, const PathArgs &a, int i, bool store)
+// Work-hardening policies (PathCarriesKh, A = PathArgsWh): every trial of a step runs on a policy of its own that enters with
+// the step's modulus kh, as k_response_batch<7> builds one from kh_in[i]; the accepted trial's modulus is the next step's.
+// For every other policy none of this exists: the trial runs on the path's one policy object.
+template <bool OUTLINE, class YF, class A>
+__device__ __forceinline__ void path_point(const MatDev &m, const YF &yf, bool elastic, const A &a, int i, bool store)
 {
 #pragma clang fp contract(off)
+    constexpr bool CARRY = PathCarriesKh<YF>::value;
     const PathYf<YF> pyf(yf);
+    double kh = 0., kh2 = 0.;
+    if constexpr (CARRY) kh = a.khard0[i];
     const int ctrl = a.control ? (a.control[i] & 63) : 0;
     const size_t n = (size_t)a.n;
     double sig[6], epl[6], tgt[6], Ct[21];
@@ -179,6 +206,13 @@ __device__ __forceinline__ void path_point(const MatDev &m, const YF &yf, bool e
                 for (int c = 0; c < 21; c++) Ct2[c] = m.CV[c];
                 f = 0.;
                 ns = 0;
+            } else if constexpr (CARRY) {
+                const PathYf<YF> tyf(YF(m, yf.sv, yf.dual, kh));
+                if constexpr (OUTLINE)
+                    ns = path_trial(m, tyf, sig, epl, deps, a.maxit, &f, s2, depl, Ct2);
+                else
+                    ns = response_point(m, tyf, s2, epl, deps, f, depl, Ct2, a.maxit);
+                kh2 = tyf.kh();
             } else {
                 if constexpr (OUTLINE)
                     ns = path_trial(m, pyf, sig, epl, deps, a.maxit, &f, s2, depl, Ct2);
@@ -214,6 +248,7 @@ __device__ __forceinline__ void path_point(const MatDev &m, const YF &yf, bool e
         }
 #pragma unroll
         for (int c = 0; c < 21; c++) Ct[c] = Ct2[c];
+        if constexpr (CARRY) kh = kh2;
         if (store) {
             const size_t rec = (size_t)k * n + i;
 #pragma unroll
@@ -225,6 +260,7 @@ __device__ __forceinline__ void path_point(const MatDev &m, const YF &yf, bool e
             a.fy[rec] = f;
             a.nsteps[rec] = ns;
             a.newton_out[rec] = nw;
+            if constexpr (CARRY) a.khard[rec] = kh;
         }
     }
     if (!store) return;
@@ -238,6 +274,7 @@ __device__ __forceinline__ void path_point(const MatDev &m, const YF &yf, bool e
         a.fy[rec] = nan;
         a.nsteps[rec] = -1;
         a.newton_out[rec] = -1;
+        if constexpr (CARRY) a.khard[rec] = nan;
     }
     if (a.ct) {
 #pragma unroll
@@ -260,6 +297,54 @@ k_path_batch(const MatDev *gmat, int nmat, int mat, PathArgs a)
     for (int i = blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += gridDim.x * BLOCK)
         path_point<true>(m, yf, KIND == 1 && m.kind == 0, a, i, true);
 }
+
+// ... of the work-hardening SVC material `mat` (kind 7): the tables where k_response_batch<7> takes them from -- staged in
+// dynamic LDS by stage_svc where they fit, read from device memory otherwise -- and the trial out of line through path_trial,
+// so that a strain-controlled path has the bits of the host loop over plfx_response_batch_kh.
+template <int KIND>
+__global__ void __launch_bounds__(BLOCK)
+k_path_batch(const MatDev *gmat, int nmat, int lds_doubles, int mat, PathArgsWh a)
+{
+    static_assert(KIND == 7, "the kinds without tables take PathArgs");
+    __shared__ MatDev smat[MAXMAT];
+    stage_materials(smat, gmat, nmat);
+    __syncthreads();
+    int svc_mat = -1;
+    const double *sv = nullptr, *dual = nullptr;
+    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, KIND, mat);
+    __syncthreads();
+    const MatDev &m = smat[mat];
+    const bool staged = (mat == svc_mat);
+    const YfSvcWh yf(m, staged ? sv : m.sv, staged ? dual : m.dual, 0.);   // (every trial enters with its step's modulus)
+    for (int i = blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += gridDim.x * BLOCK)
+        path_point<true>(m, yf, false, a, i, true);
+}
+
+// ... and one wave per path, blockDim / 64 paths per block: the policy of k_sweep_wh_wave, which splits the support-vector
+// sums over the 64 lanes and closes each with wave_allsum, so that every lane holds the same bits and every value the wave
+// branches on is wave-uniform; all other arithmetic runs redundantly in lock-step.  Lane 0 stores.  A path's sums depend on
+// nsv alone, not on n, the path's place or the grid.  The trial goes through path_trial, out of line: the state of the path
+// (sig, epl, targets, deps, two tangents, kh: some 100 doubles) then lies in scratch between two trials and not in registers
+// across the sum loops -- inlined, the kernel spills 137 VGPRs around them (DESIGN.md section 45 has both sets of figures).
+#ifdef PLFX_UNIT_MATERIALS
+__global__ void __launch_bounds__(BLOCK)
+k_path_wh_wave(const MatDev *__restrict__ gmat, int nmat, int lds_doubles, int mat, PathArgsWh a)
+{
+    __shared__ MatDev smat[MAXMAT];
+    stage_materials(smat, gmat, nmat);
+    __syncthreads();
+    int svc_mat = -1;
+    const double *sv = nullptr, *dual = nullptr;
+    stage_svc(smat, nmat, dyn_lds, lds_doubles, svc_mat, sv, dual, 7, mat);
+    __syncthreads();
+    const MatDev &m = smat[mat];
+    const bool staged = (mat == svc_mat);
+    const YfSvcWhT<1> yf(m, staged ? sv : m.sv, staged ? dual : m.dual, 0.);
+    const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+    for (int i = blockIdx.x * wpb + (threadIdx.x >> 6); i < a.n; i += gridDim.x * wpb)   // wave-uniform
+        path_point<true>(m, yf, false, a, i, lane == 0);
+}
+#endif
 
 // ... and 16 lanes per path for the row-kernel SVC material `mat` (tables in LDS or in device memory, column scales, texture
 // field: the instantiations of k_response_row, and its grid)

@@ -1551,7 +1551,7 @@ class Material(object):
         return bits, (len(bits) if m.ndim == 2 else None)
 
     def load_path(self, dload, control=None, sig0=None, epl0=None, CV=None, maxit=50, newton=30, stol=None, eps_cap=0.05,
-                  tex_id=None, return_tangent=False):
+                  tex_id=None, return_tangent=False, khard0=None, form=None):
         """EXTENSION: material points driven along load paths, every path in one launch -- what the reference's
         ``examples/UMAT/calc_properties.py`` hands to a one-element block of an FE code: uniaxial and biaxial curves,
         r-values, plane-strain compression, cyclic paths.  ``dload`` is (K,N,6): K increments of N points, or (K,6), one path
@@ -1579,28 +1579,62 @@ class Material(object):
         Limit: full stress control across the yield point of a weakly hardening material ends with status 1 (the elastic
         tangent overshoots, the plastic one is nearly singular); drive at least one component by strain there.
 
-        Offered for elastic, Hill / J2 / Drucker (``sdim`` 6 and 3), Barlat with ``enable_barlat_normal`` and 6-feature ML
-        yield functions, materials bound to a texture and texture fields (``tex_id``: int or (N,)) included.
-        ``NotImplementedError`` for ``sdim = 3`` ML yield functions, work-hardening ML yield functions, ``ML_grad``, a
-        parent texture material, Tresca and Barlat without a flow rule."""
+        Work-hardening ML yield functions (``from_data`` on ``wh_data``): the hardening modulus, which every
+        gradient evaluation overwrites, is state of a path like ``sig`` and ``epl``.  ``khard0``, a scalar or (N,), finite
+        and ``>= 0``, is the modulus at the start of each path; it is required -- ``Material.khard`` is neither read nor
+        written, the initial modulus is part of the initial state and not taken from the call history -- and counts towards
+        the number of points like ``sig0``.  Every trial of a step enters with the step's modulus (``response`` with
+        ``khard_in``); on acceptance the modulus is the accepted trial's, unchanged where that trial evaluated no gradient.
+        The dict then also holds ``khard`` (K,N): the modulus after each step, NaN past ``ksteps``.  ``form``: ``'thread'``
+        runs one thread per path -- with strain control the bits of the loop over ``response(khard_in=, return_khard=True)``
+        --, ``'wave'`` one wave per path with the support-vector sums split over its 64 lanes (results differ from
+        ``'thread'`` by the order of those sums, §45 has the measured size), ``'auto'`` (the default with ``khard0``) picks
+        the faster one by N: the wave form at every N measured, 1 to 100 000 (§45).  ``khard0`` with any other material, ``form`` without ``khard0`` and an unknown ``form`` are ``ValueError``.
+
+        Offered for elastic, Hill / J2 / Drucker (``sdim`` 6 and 3), Barlat with ``enable_barlat_normal``, 6-feature ML
+        yield functions, materials bound to a texture and texture fields (``tex_id``: int or (N,)) included, and, with
+        ``khard0``, work-hardening ML yield functions.
+        ``NotImplementedError`` for ``sdim = 3`` ML yield functions, work-hardening ML yield functions without ``khard0``,
+        ``ML_grad``, a parent texture material, Tresca and Barlat without a flow rule."""
         if getattr(self, '_bound', None) is None:
             self._tex_refuse('load_path')
         self._no_svr_gradient('load_path')
         if self.ML_yf and self.sdim != 6:
             raise NotImplementedError('load_path: not offered for sdim = 3 ML yield functions; only the 6-feature SVC runs on '
                                       'the row kernels that follow a path')
-        if self.ML_yf and getattr(self, 'whdat', False):
+        wh = bool(self.ML_yf and getattr(self, 'whdat', False))
+        if wh and khard0 is None:
             raise NotImplementedError('load_path: not offered for work-hardening ML yield functions, whose khard is carried '
-                                      'from one gradient evaluation to the next; flow_curve follows their hardening')
+                                      'from one gradient evaluation to the next, unless khard0 gives the hardening modulus '
+                                      'at the start of the paths; flow_curve follows their hardening')
         if not self.ML_yf and self.sy is not None and (self.tresca or (self.barlat and not getattr(self, 'barlat_normal', False))):
             raise NotImplementedError('load_path: %s has no flow rule (calc_fgrad raises in the reference, material.py:822-825)%s'
                                       % ('Tresca' if self.tresca else 'Barlat',
                                          '' if self.tresca else '; enable_barlat_normal() gives Barlat one'))
+        if khard0 is not None and not wh:
+            raise ValueError('load_path: khard0 is the initial hardening modulus of a work-hardening ML yield function; the '
+                             'modulus of this material is not state of a path')
+        if form is not None and khard0 is None:
+            raise ValueError('load_path: form selects the kernel of a work-hardening ML yield function and is accepted only '
+                             'together with khard0')
+        if khard0 is not None:
+            form = 'auto' if form is None else form
+            if form not in ('auto', 'thread', 'wave'):
+                raise ValueError("load_path: form must be 'auto', 'thread' or 'wave'; got %r" % (form,))
+            if tex_id is not None:
+                raise ValueError('load_path: tex_id selects rows of a texture field; a work-hardening ML yield function has none')
         d = np.asarray(dload, dtype=float)
         if d.ndim not in (2, 3) or d.shape[-1] != 6:
             raise ValueError('load_path: dload must be (K, N, 6), or (K, 6) shared by the points; got shape %s' % (d.shape,))
         bits, nc = self._path_control(control)
         sizes = {}
+        k0 = None
+        if khard0 is not None:
+            k0 = np.asarray(khard0, dtype=float)
+            if k0.ndim > 1:
+                raise ValueError('load_path: khard0 must be a scalar or (N,); got shape %s' % (k0.shape,))
+            if not np.all(np.isfinite(k0)) or np.any(k0 < 0.):
+                raise ValueError('load_path: khard0 must be finite and >= 0')
         if d.ndim == 3:
             sizes['dload'] = d.shape[1]
         if nc is not None:
@@ -1617,6 +1651,8 @@ class Material(object):
             rows[name] = a
         if tex_id is not None and np.ndim(tex_id) == 1:
             sizes['tex_id'] = len(tex_id)
+        if k0 is not None and k0.ndim == 1:
+            sizes['khard0'] = len(k0)
         if len(set(sizes.values())) > 1:
             raise ValueError('load_path: the number of points differs between the arguments: %s'
                              % ', '.join('%s %d' % kv for kv in sizes.items()))
@@ -1649,6 +1685,10 @@ class Material(object):
             dd = np.abs(d) if d.ndim == 3 else np.abs(d)[:, None, :]
             if np.any((dd > eps_cap) & strain[None]):
                 raise ValueError('load_path: a strain increment of dload is beyond eps_cap = %g' % eps_cap)
+        if k0 is not None:
+            return self._load(CV).load_path_wh(0, np.ascontiguousarray(d), np.ascontiguousarray(np.broadcast_to(k0, (n,))),
+                                               control=bits if mixed else None, sig0=s0, epl0=e0, form=form, maxit=maxit,
+                                               newton=newton, stol=stol, eps_cap=eps_cap, return_tangent=bool(return_tangent))
         return self._load(CV).load_path(0, np.ascontiguousarray(d), control=bits if mixed else None, sig0=s0, epl0=e0, tex_id=tid,
                                         maxit=maxit, newton=newton, stol=stol, eps_cap=eps_cap,
                                         return_tangent=bool(return_tangent))
